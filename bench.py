@@ -34,7 +34,17 @@ communicator, `ranks` lists every rank's device as RCCL reports it.
            keys (strong scaling: the total work is fixed).
 
 value = events voted by all ranks / max-over-ranks time.  Prints ONE JSON line (rank 0).
-Data: synthetic (dvs_mcemvs_amd/synthetic.py).
+Data: synthetic (dvs_mcemvs_amd/synthetic.py), seeded: the same arguments give the same inputs on every run.
+
+A plain run sets up, ramps the clocks (--clock-ramp), runs the W warm-up steps, times the K steps and prints the
+line: `value`, `ms_per_step` (one timed step), the configuration and the per-step HIP-event times.  Everything else
+the bench measures or checks is behind --full: the same K steps timed before the clock ramp (value_no_ramp), the
+roofline of the voting kernel (kernel times from HIP events, LDS-atomic and HBM figures), the collective alone
+(N > 1), the HBM stream kernels, the host-fed rates, the CPU baseline, the parity block against the CPU oracle,
+the exact tie resolver's figures, the input sensitivity, the paired-cell mode and the other workloads' lines;
+the --no-* options below narrow a --full run.
+--dump-outputs DIR (e.g. bench_outputs/) writes what the last timed step computed (the depth map; for stereo on one
+GPU also the fused DSI) as DIR/<name>.npy in float32, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -98,7 +108,7 @@ def parse():
                     help="cameras4: n-ary geometric mean as the balanced tree of the reference's 2-ary sqrt(a*b) "
                          "(DSI_ACC_GM_TREE, default) or as exp(mean(log)) (DSI_ACC_LOG_SUM)")
     ap.add_argument("--no-extra", action="store_true",
-                    help="default (stereo, 1 GPU) run only: do not append the one-GPU lines of the windows and "
+                    help="--full (stereo, 1 GPU) only: do not append the one-GPU lines of the windows and "
                          "cameras4 workloads (each is a sub-run of this script) to the JSON line")
     ap.add_argument("--camera-streams", type=int, default=2,
                     help="cameras4: contexts (HIP streams) the cameras are dealt over, 1 to 4.  With 2, camera c+1's packet "
@@ -115,8 +125,13 @@ def parse():
                          "which the host generated the inputs (default: ~0.25 s worth: 100 stereo steps, 600 windows, 40 "
                          "cameras4 steps; 0 = none).  The same count on every rank (steps contain collectives)")
     ap.add_argument("--no-sensitivity", action="store_true",
-                    help="default (stereo, 1 GPU) run only: skip the input-sensitivity sub-records (the voting kernel on "
+                    help="--full (stereo, 1 GPU) only: skip the input-sensitivity sub-records (the voting kernel on "
                          "uniformly random pixels, on a dense scene and on the recorded zurich_city_04 trajectory)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (see the module docstring); "
+                         "a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (float32)")
     a = ap.parse_args()
     defaults = {"stereo": ((346, 260, 100), 10_000_000, 100, 5), "windows": ((512, 512, 200), 500_000, 100, 8),
                 "cameras4": ((1024, 1024, 256), 2_000_000, 5, 1)}[a.workload]
@@ -126,6 +141,8 @@ def parse():
     a.warmup = a.warmup if a.warmup is not None else defaults[3]
     if a.clock_ramp is None:
         a.clock_ramp = {"stereo": 100, "windows": 600, "cameras4": 40}[a.workload]
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     return a
 
 
@@ -592,7 +609,7 @@ def other_workloads():
                                "--clock-ramp", "1"]))
     for name, flags in runs:
         # (the windows line carries its host-fed rates: Python from pageable / page-locked arrays, C++ from std::vector<Event>)
-        cmd = [sys.executable, os.path.abspath(__file__)] + flags + ["--no-cpu", "--no-extra"] + ([] if name == "windows" else ["--no-host-fed"])
+        cmd = [sys.executable, os.path.abspath(__file__)] + flags + ["--full", "--no-cpu", "--no-extra"] + ([] if name == "windows" else ["--no-host-fed"])
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
             line = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1]
@@ -708,6 +725,13 @@ def main():
             if temporal is not None:
                 temporal.drain()
 
+        def outputs():
+            depth, conf, idx = (mappers[0] if temporal is None else mapper_fused).fetchDepthMap()
+            res = {"depth_map": depth, "confidence_map": conf, "depth_cell_indices": idx}
+            if temporal is None:
+                res["fused_dsi"] = fused.download()       # [Z][Y][X], the volume the depth map was taken from
+            return res
+
         voted_per_step = voted
         workload = ("stereo (2-cam) synthetic DSEC-like rig, %d events/cam per GPU, %dx%dx%d DSI, harmonic camera "
                     "fusion + arg-max%s" % (args.events, nx, ny, nz, "" if world == 1 else
@@ -747,20 +771,24 @@ def main():
             host_wins.append((host, b))
             closers += per_cam
         closers.append(ws)
-        state = {"w": 0, "pending": []}
+        state = {"w": 0, "pending": [], "fetched": None}
 
         def step():
             per_cam, ts = wins[state["w"] % len(wins)]
             state["pending"].append(ws.submit(None, rig["trajectories"], ts, batches=per_cam))
             while len(state["pending"]) >= depth:
-                ws.fetch(state["pending"].pop(0))     # depth map of the oldest window in flight (device -> host)
+                state["fetched"] = ws.fetch(state["pending"].pop(0))   # depth map of the oldest window in flight (device -> host)
             state["w"] += 1
 
         def sync():
             while state["pending"]:
-                ws.fetch(state["pending"].pop(0))
+                state["fetched"] = ws.fetch(state["pending"].pop(0))
             for c_ in ws.contexts:
                 c_.synchronize()
+
+        def outputs():
+            depth, conf, idx = state["fetched"]          # the last window's, fetched by sync()
+            return {"depth_map": depth, "confidence_map": conf, "depth_cell_indices": idx}
 
         extra["concurrent"] = concurrent
         extra["serial_step"] = (step, sync)
@@ -855,6 +883,10 @@ def main():
             for cc in cam_ctxs:
                 cc.synchronize()
 
+        def outputs():
+            depth, conf, idx = (out_mapper if fused4 else mappers[0]).fetchDepthMap()
+            return {"depth_map": depth, "confidence_map": conf, "depth_cell_indices": idx}
+
         if len(cam_ctxs) > 1 and not fused4:
             # an event pair around a kernel also times its wait for the other stream's workgroups to leave the CUs: the
             # dominant kernel's duration is measured on un-overlapped steps after the timed region (like the windows)
@@ -889,10 +921,10 @@ def main():
     # clock ramp (untimed, before the contract's W warm-up steps): the GPU idled for seconds while the host generated the
     # inputs, and the first launches after an idle stretch run 1-2 % slow (measured: stereo 2.623 -> 2.589 ms per step,
     # windows 0.451 -> 0.443, cameras4 6.51 -> 6.37 with a long warm-up); a stream of real windows never idles
-    # ... and the same K steps timed WITHOUT it first (after the W warm-up steps only, the contract's letter), reported
-    # beside `value` as value_no_ramp
+    # ... and (--full) the same K steps timed WITHOUT it first (after the W warm-up steps only, the contract's letter),
+    # reported beside `value` as value_no_ramp
     no_ramp = None
-    if args.clock_ramp > 0 and world == 1:
+    if args.full and args.clock_ramp > 0 and world == 1:
         for _ in range(args.warmup):
             step()
         barrier()
@@ -915,7 +947,7 @@ def main():
     barrier()
     overlapped = bool(extra.get("concurrent"))
     for m in vote_mappers:
-        m.set_kernel_timing(not overlapped)
+        m.set_kernel_timing(args.full and not overlapped)      # (HIP events around the voting kernel: the roofline's)
         m.vote_kernel_time()
     t0 = time.perf_counter()
     ctx.timer_start()
@@ -927,7 +959,9 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     step_ms = ctx.timeline_read()
-    if overlapped:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs())
+    if args.full and overlapped:
         # consecutive windows overlap on the device (two streams), so an event pair around a kernel also times
         # its wait for the previous window's workgroups: the dominant kernel's duration is measured on extra,
         # un-overlapped launches AFTER the timed region (one window at a time)
@@ -953,7 +987,9 @@ def main():
     # accepted event-planes of one launch = sum of the DSI it writes (the 4 bilinear weights of a vote sum to 1);
     # accepted RECORDS = the same after the packet sort merged same-pixel events of a packet (one record = 4 LDS
     # atomics actually issued): dsi_mapper_vote_statistics, outside the timed region
-    if extra.get("fused_vote"):
+    if not args.full:
+        accepted = records = None
+    elif extra.get("fused_vote"):
         # the fused kernel writes no DSI: the two camera DSIs of one window are built here, once, to count the work
         # of a launch (both cameras are voted by one launch)
         accepted = records = 0.0
@@ -969,7 +1005,7 @@ def main():
     # the collective alone (N > 1, stereo): K un-overlapped all-reduces of the accumulator-sized volume on the compute
     # stream, all ranks in step -- the xGMI cost the pipelined run hides behind the next step's voting
     collective_block = None
-    if comm is not None and args.workload == "stereo":
+    if args.full and comm is not None and args.workload == "stereo":
         reps = 10
         allreduce(fused, d.REDUCE_SUM)
         barrier()
@@ -987,6 +1023,37 @@ def main():
 
     out = None
     if rank == 0:
+        out = {
+            "metric": "Mevents/s into DSI (346x260x100) + DSI-fuse GB/s",
+            "value": value, "unit": "Mevents/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+            "scaling": scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": workload, "events_voted_per_step": voted_all, "vote_algo": info["algo"],
+                       "bands": info["bands"], "band_rows": info["band_rows"], "chunks": info["chunks"],
+                       "block_threads": info["block_threads"], "lds_bytes": info["lds_bytes"],
+                       "packed_lanes": info["packed"], "parallelism": parallelism, "collective": collective,
+                       "launched_by": ("a launcher (RANK / WORLD_SIZE in the environment)" if not D.spawned else
+                                       "bench.py itself (dvs_mcemvs_amd.launch.spawn_ranks), one process per GPU")
+                       if world > 1 else "single process",
+                       "n_points": int(max(args.points, 6000) if args.workload == "windows" else args.points),
+                       "noise_frac": 0.10},
+            "launch_env": launch.environment_report() if world > 1 else None,
+            "rccl_ranks": rccl[0] if rccl else 1,
+            "ranks": ranks,
+            "gpu_ms_per_step_hip_events": gpu_ms / args.steps,
+            "timed_region_s": elapsed,
+            "clock_ramp": {"steps": args.clock_ramp, "seconds": t_ramp,
+                           "note": "untimed steps before the warm-up steps: brings the clocks up after the idle input generation"},
+            "input_gen_s": t_gen,
+            "step_ms": {"min": float(step_ms.min()), "median": float(np.median(step_ms)), "max": float(step_ms.max()),
+                        "n": int(step_ms.shape[0]), "source": "HIP events between consecutive steps on the compute stream" +
+                        (" of slot 0 (with two streams a step's events bracket parts of two windows)" if overlapped else "")}
+            if step_ms.shape[0] else None,
+        }
+        if args.workload == "windows":
+            out["windows_per_s"] = world * args.steps / elapsed
+            out["x_real_time"] = (args.events / 10.0e6) * world * args.steps / elapsed
+    if rank == 0 and args.full:
         # PMC traffic of the dominant kernel is a separate rocprofv3 run (tools/profile_round.sh ->
         # profiles/traffic.json); it is quoted here only if that run profiled THIS kernel source on THIS
         # workload shape -- otherwise null (a stale constant would look like a measurement)
@@ -1162,21 +1229,7 @@ def main():
             except Exception as e:                  # report, do not fail the headline
                 paired = {"error": str(e)[:300]}
         others = args.workload == "stereo" and world == 1 and not args.no_extra and not args.no_host_fed
-        out = {
-            "metric": "Mevents/s into DSI (346x260x100) + DSI-fuse GB/s",
-            "value": value, "unit": "Mevents/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-            "scaling": scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": workload, "events_voted_per_step": voted_all, "vote_algo": info["algo"],
-                       "bands": info["bands"], "band_rows": info["band_rows"], "chunks": info["chunks"],
-                       "block_threads": info["block_threads"], "lds_bytes": info["lds_bytes"],
-                       "packed_lanes": info["packed"], "parallelism": parallelism, "collective": collective,
-                       "launched_by": ("a launcher (RANK / WORLD_SIZE in the environment)" if not D.spawned else
-                                       "bench.py itself (dvs_mcemvs_amd.launch.spawn_ranks), one process per GPU")
-                       if world > 1 else "single process"},
-            "launch_env": launch.environment_report() if world > 1 else None,
-            "rccl_ranks": rccl[0] if rccl else 1,
-            "ranks": ranks,
+        out.update({
             "collective": collective_block,
             "dsi_fuse_GBps": streams["dsi_fuse"]["GBps"] if streams else None,
             "dsi_fuse_ms": streams["dsi_fuse"]["ms"] if streams else None,
@@ -1184,27 +1237,17 @@ def main():
             "argmax_GBps": streams["argmax"]["GBps"] if streams else None,
             "argmax_ms": streams["argmax"]["ms"] if streams else None,
             "stream_kernels": streams,
-            "gpu_ms_per_step_hip_events": gpu_ms / args.steps,
-            "timed_region_s": elapsed,
             "value_no_ramp": no_ramp["value"] if no_ramp else None,
             "no_ramp": no_ramp,
-            "clock_ramp": {"steps": args.clock_ramp, "seconds": t_ramp,
-                           "note": "untimed steps before the warm-up steps: brings the clocks up after the idle input generation"},
-            "host_fed": h2d, "roofline": roofline, "cpu_baseline": cpu, "input_gen_s": t_gen,
-            "step_ms": {"min": float(step_ms.min()), "median": float(np.median(step_ms)), "max": float(step_ms.max()),
-                        "n": int(step_ms.shape[0]), "source": "HIP events between consecutive steps on the compute stream" +
-                        (" of slot 0 (with two streams a step's events bracket parts of two windows)" if overlapped else "")}
-            if step_ms.shape[0] else None,
+            "host_fed": h2d, "roofline": roofline, "cpu_baseline": cpu,
             "parity": parity,
             "paired_mode": paired,
             "exact_ties": exact_ties if args.workload == "windows" else None,
             "sensitivity": sensitivity,
             "device_memory": device_memory(),
-        }
+        })
         if others:
             out["other_workloads_pending"] = True
-        out["config"]["n_points"] = int(max(args.points, 6000) if args.workload == "windows" else args.points)
-        out["config"]["noise_frac"] = 0.10
         if parity:
             out["argmax_agree_frac"] = parity["argmax_agree_frac"]
             out["near_tie_frac"] = parity["near_tie_frac"]
@@ -1233,9 +1276,6 @@ def main():
             out["dsi_fuse_at_metric_shape"] = streams.get("dsi_fuse_at_metric_shape")
         if args.workload == "windows" and exact_ties:
             out["ms_per_window_exact"] = ms_per_step + exact_ties["plus_ms_per_window"]
-        if args.workload == "windows":
-            out["windows_per_s"] = world * args.steps / elapsed
-            out["x_real_time"] = (args.events / 10.0e6) * world * args.steps / elapsed
     for o in closers:
         o.close()
     if args.workload == "stereo" and world > 1:
@@ -1298,6 +1338,28 @@ def device_memory():
 
 def info_nz(mapper):
     return mapper.dsi_.getDimensions()[2]
+
+
+DUMP_BYTES = 60 * 10**6          # the arrays' bytes: under 64 MB with the .npy headers
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32 (float64 stays float64), in the order given.  An array
+    that would take the total past DUMP_BYTES is written as <name>_sample.npy instead: its elements at flat indices drawn
+    with a fixed seed (sorted), as many as the remaining budget holds -- the same elements on every run of the same
+    shape."""
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BYTES
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > left:
+            k = left // a.itemsize
+            if k == 0:
+                raise SystemExit("bench.py: --dump-outputs: no room left for %s under %d bytes" % (name, DUMP_BYTES))
+            pick = np.sort(np.random.default_rng(0).integers(0, a.size, k))
+            a, name = a.reshape(-1)[pick], name + "_sample"
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
 
 
 if __name__ == "__main__":

@@ -1,16 +1,19 @@
 """Extracts the control poses of the reference's only real recording that fall into the window its own
 configuration processes, as a small fixture (DATA, not code):
 
-    /root/reference/data/DSEC/zurich_city_04-odometry/pose.bag   (LiDAR-IMU odometry, PoseStamped @ ~10 Hz)
+    tests/golden/zurich_city_04_pose.bag.xz   (the reference's data/DSEC/zurich_city_04-odometry/pose.bag, xz-compressed;
+                                              LiDAR-IMU odometry, PoseStamped @ ~10 Hz)
     window: --start_time_s=10 --stop_time_s=15  (mapper_emvs_stereo/cfg/DSEC/zurich_04_a_full/dsec.conf:13-14),
     read like data_loading::parse_rosbag_gt (stamps relative to the first pose message), one second of
     margin on either side so that every event time of the window can be interpolated.
 
-Run in the build container (the reference checkout does not exist on the GPU box):
+Run:
     python tests/golden/make_zurich_poses.py   ->   tests/golden/zurich_city_04_poses_9_16s.npz
 """
+import lzma
 import os
 import sys
+import tempfile
 
 import numpy as np
 
@@ -18,11 +21,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 from dvs_mcemvs_amd import io  # noqa: E402
 
-BAG = "/root/reference/data/DSEC/zurich_city_04-odometry/pose.bag"
+BAG_XZ = os.path.join(ROOT, "tests", "golden", "zurich_city_04_pose.bag.xz")
 OUT = os.path.join(ROOT, "tests", "golden", "zurich_city_04_poses_9_16s.npz")
 
 if __name__ == "__main__":
-    times, poses = io.parse_rosbag_gt(BAG, topic="/pose", tmin=9.0, tmax=16.0)
+    with tempfile.TemporaryDirectory() as tmp:
+        bag = os.path.join(tmp, "pose.bag")
+        with open(bag, "wb") as f:
+            f.write(lzma.decompress(open(BAG_XZ, "rb").read()))
+        times, poses = io.parse_rosbag_gt(bag, topic="/pose", tmin=9.0, tmax=16.0)
     assert 60 <= times.shape[0] <= 80, times.shape
     np.savez_compressed(OUT, times=times, poses=poses,
                         source="zurich_city_04-odometry/pose.bag, /pose, relative stamps 9..16 s "

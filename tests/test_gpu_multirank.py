@@ -308,7 +308,7 @@ def test_bench_gpus_2_is_two_rccl_ranks_or_an_error(built):
     import subprocess
     import dvs_mcemvs_amd as d
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "DSI_BENCH_DEVICE")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu",
            "--no-host-fed", "--events", "2000000"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1200)
     if d.device_count() < 2:

@@ -1,4 +1,5 @@
 """On-disk formats: .npy DSI dump, depth-points text, ROSBAG v2 pose reader."""
+import lzma
 import os
 
 import numpy as np
@@ -6,7 +7,8 @@ import pytest
 
 from dvs_mcemvs_amd import io
 
-REF_BAG = "/root/reference/data/DSEC/zurich_city_04-odometry/pose.bag"
+# the reference's data/DSEC/zurich_city_04-odometry/pose.bag as it ships, xz-compressed
+REF_BAG_XZ = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "zurich_city_04_pose.bag.xz")
 
 
 def test_grid_npy_layout(tmp_path):
@@ -74,11 +76,12 @@ def test_parse_rosbag_gt_keeps_the_first_of_equal_stamps(tmp_path):
     assert np.all(np.diff(t) > 0)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_BAG), reason="reference checkout not present on this box")
-def test_reads_the_reference_dsec_odometry_bag():
+def test_reads_the_reference_dsec_odometry_bag(tmp_path):
     """The only real data in the reference repo: LiDAR-IMU odometry of
     DSEC zurich_city_04, 6205 PoseStamped at ~9.92 Hz over 625.7 s, median speed 3.6 m/s."""
-    t, p = io.read_pose_bag(REF_BAG, topic="/pose")
+    bag = tmp_path / "pose.bag"
+    bag.write_bytes(lzma.decompress(open(REF_BAG_XZ, "rb").read()))
+    t, p = io.read_pose_bag(bag, topic="/pose")
     assert t.shape[0] == 6205
     assert t[-1] - t[0] == pytest.approx(625.7, abs=0.1)
     assert np.median(np.diff(t)) == pytest.approx(1 / 9.92, rel=0.02)

@@ -1,7 +1,7 @@
 # A/B of the fused kernel's pair assignment (experiments flavour): 0 contiguous pieces, 1 pairs in turn, 2 pairs drawn
 cd $GRAFT_REPO_ROOT
 export DSI_ENGINE_EXPERIMENTS=1
-B="python bench.py --no-cpu --no-host-fed --no-extra"
+B="python bench.py --full --no-cpu --no-host-fed --no-extra"
 DSI_FUSED_INTERLEAVE=2 timeout 1200 python -m pytest tests/test_gpu_fused_vote.py tests/test_gpu_windows.py -q -m gpu -x 2>&1 | tail -2
 for rep in 1 2; do
 for il in 0 1 2; do

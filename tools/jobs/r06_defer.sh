@@ -1,7 +1,7 @@
 cd $GRAFT_REPO_ROOT
 timeout 1500 python -m pytest tests/test_gpu_fused_vote.py tests/test_gpu_windows.py -q -m gpu -x > gpurun_out/defer_tests.txt 2>&1
 tail -3 gpurun_out/defer_tests.txt
-B="python bench.py --workload windows --no-cpu --no-host-fed --no-extra"
+B="python bench.py --full --workload windows --no-cpu --no-host-fed --no-extra"
 for i in 1 2; do
 DSI_ENGINE_EXPERIMENTS=1 DSI_FUSED_DEFER=0 $B > gpurun_out/win_nodefer_$i.json 2> gpurun_out/win_nodefer_$i.err
 DSI_ENGINE_EXPERIMENTS=1 $B > gpurun_out/win_defer_$i.json 2> gpurun_out/win_defer_$i.err

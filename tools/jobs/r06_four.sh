@@ -3,7 +3,7 @@ timeout 1500 python -m pytest tests/test_gpu_fused_vote.py -q -m gpu -x -k "four
 tail -5 gpurun_out/four_tests.txt
 timeout 600 python -m pytest tests/test_gpu_parity.py -q -m gpu -x -k "paired" > gpurun_out/paired_tests2.txt 2>&1
 tail -3 gpurun_out/paired_tests2.txt
-B="python bench.py --workload cameras4 --no-cpu --no-host-fed --no-extra"
+B="python bench.py --full --workload cameras4 --no-cpu --no-host-fed --no-extra"
 $B > gpurun_out/cam4_unfused.json 2> gpurun_out/cam4_unfused.err
 $B --fused-vote > gpurun_out/cam4_fused.json 2> gpurun_out/cam4_fused.err
 $B --fused-vote --packed 1 > gpurun_out/cam4_fused_p1.json 2> gpurun_out/cam4_fused_p1.err

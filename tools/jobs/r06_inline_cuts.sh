@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 timeout 1500 python -m pytest tests/test_gpu_parity.py -q -m gpu -x -k "inline_cuts or hand_scheduled or both_lane or baseline_large or configs4_camera" > gpurun_out/inline_tests.txt 2>&1
 tail -3 gpurun_out/inline_tests.txt
-B="python bench.py --no-cpu --no-host-fed --no-extra --no-sensitivity"
+B="python bench.py --full --no-cpu --no-host-fed --no-extra --no-sensitivity"
 for ic in 1000000000 0; do
   $B --workload cameras4 --events 100000000 --tile 10 --steps 3 --warmup 1 --clock-ramp 1 --inline-cuts $ic > gpurun_out/full_ic$ic.json 2> gpurun_out/full_ic$ic.err
   $B --dims 1024 1024 256 --events 10000000 --steps 10 --warmup 2 --inline-cuts $ic > gpurun_out/d1024_ic$ic.json 2> gpurun_out/d1024_ic$ic.err

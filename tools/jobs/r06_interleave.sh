@@ -1,6 +1,6 @@
 cd $GRAFT_REPO_ROOT
 export DSI_ENGINE_EXPERIMENTS=1
-B="python bench.py --no-cpu --no-host-fed --no-extra"
+B="python bench.py --full --no-cpu --no-host-fed --no-extra"
 for il in 0 1; do
   DSI_FUSED_INTERLEAVE=$il $B --workload cameras4 > gpurun_out/il_cam4_$il.json 2> gpurun_out/il_cam4_$il.err
   DSI_FUSED_INTERLEAVE=$il $B --workload windows > gpurun_out/il_win_$il.json 2> gpurun_out/il_win_$il.err

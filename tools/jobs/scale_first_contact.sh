@@ -54,10 +54,10 @@ run_line() {   # name, gpus, extra flags...
 echo "== 2. bench lines"
 for n in 1 2 4 8; do
     [ "$n" -gt "$MAXG" ] && continue
-    run_line stereo_allreduce "$n" --steps 20 --warmup 5 --no-cpu --no-extra --no-host-fed --temporal-collective allreduce
-    [ "$n" -gt 1 ] && run_line stereo_reduce_scatter "$n" --steps 20 --warmup 5 --no-cpu --no-extra --no-host-fed --temporal-collective reduce_scatter
-    run_line windows "$n" --workload windows --no-cpu --no-extra --no-host-fed
-    run_line cameras4 "$n" --workload cameras4 --no-cpu --no-extra --no-host-fed
+    run_line stereo_allreduce "$n" --steps 20 --warmup 5 --full --no-cpu --no-extra --no-host-fed --temporal-collective allreduce
+    [ "$n" -gt 1 ] && run_line stereo_reduce_scatter "$n" --steps 20 --warmup 5 --full --no-cpu --no-extra --no-host-fed --temporal-collective reduce_scatter
+    run_line windows "$n" --workload windows --full --no-cpu --no-extra --no-host-fed
+    run_line cameras4 "$n" --workload cameras4 --full --no-cpu --no-extra --no-host-fed
 done
 
 echo "== 3. summary"

@@ -17,14 +17,14 @@ one() {  # TAG "bench args for the trace" "bench args for the PMC passes" groups
   local TAG=$1 TARGS=$2 PARGS=$3; shift 3
   local OUT=gpurun_out/profiles_$TAG
   mkdir -p $OUT
-  timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- python bench.py --no-cpu --no-extra $TARGS > $OUT/trace.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- python bench.py --full --no-cpu --no-extra $TARGS > $OUT/trace.log 2>&1
   echo "$TAG trace rc=$?"
   python tools/rocpd_summary.py $OUT/trace/*.db > $OUT/kernel_trace_stats.txt 2>&1
   grep "^{" $OUT/trace.log | tail -1 > $OUT/bench_line_under_rocprof.json
   local i=0
   for grp in "$@"; do
     i=$((i+1))
-    timeout 900 rocprofv3 --pmc $grp --kernel-trace -d $OUT/pmc$i -o pmc$i -- python bench.py --no-cpu --no-extra $PARGS > $OUT/pmc$i.log 2>&1
+    timeout 900 rocprofv3 --pmc $grp --kernel-trace -d $OUT/pmc$i -o pmc$i -- python bench.py --full --no-cpu --no-extra $PARGS > $OUT/pmc$i.log 2>&1
     echo "$TAG pmc$i ($grp) rc=$?"
   done
   python tools/rocpd_summary.py $OUT/pmc*/*.db > $OUT/pmc_counters.txt 2>&1

@@ -6,7 +6,7 @@ CFGS=${CFGS:-"0,0,0 52,16,1024 52,8,512 26,8,512 26,8,256 26,16,512 20,8,256 13,
 for cfg in $CFGS; do
   c=$(echo $cfg | tr ',' ' ')
   echo -n "band $c : "
-  timeout 300 python bench.py --events $EV --steps 5 --warmup 2 --no-cpu --band $c 2>&1 | tail -1 | python -c "
+  timeout 300 python bench.py --full --events $EV --steps 5 --warmup 2 --no-cpu --band $c 2>&1 | tail -1 | python -c "
 import sys, json
 try:
     j = json.loads(sys.stdin.read())
