@@ -96,6 +96,47 @@ struct TmpDev {  // call-scoped device memory
     }
 };
 
+// device scratch of the point-cloud path (dsi_mapper_get_pointcloud, dsi_radius_outlier_removal): grown, never shrunk
+struct PcBuffers {
+    DevBuf<float> depth;    // host-supplied maps
+    DevBuf<uint8_t> mask;
+    DevBuf<float4> pts, spts, out;
+    DevBuf<unsigned long long> key, skey;
+    DevBuf<uint32_t> slot, bstart, tiles, blk, blk2, n;
+    DevBuf<uint8_t> keep;
+    hipError_t reserve(size_t n_max)
+    {
+        const size_t buckets = dsi::pc_buckets(n_max), blocks = dsi::pc_block_words(n_max);
+        hipError_t e;
+        if ((e = pts.reserve(n_max)) != hipSuccess || (e = spts.reserve(n_max)) != hipSuccess ||
+            (e = out.reserve(n_max)) != hipSuccess || (e = key.reserve(n_max)) != hipSuccess ||
+            (e = skey.reserve(n_max)) != hipSuccess || (e = slot.reserve(n_max)) != hipSuccess ||
+            (e = keep.reserve(n_max)) != hipSuccess || (e = bstart.reserve(buckets + 1)) != hipSuccess ||
+            (e = tiles.reserve(dsi::pc_scan_tile_words(std::max(buckets, blocks)))) != hipSuccess ||
+            (e = blk.reserve(blocks)) != hipSuccess || (e = blk2.reserve(blocks)) != hipSuccess || (e = n.reserve(1)) != hipSuccess)
+            return e;
+        return hipSuccess;
+    }
+    dsi::PcScratch scratch() const { return dsi::PcScratch{spts.p, key.p, skey.p, slot.p, bstart.p, tiles.p}; }
+    void release()
+    {
+        depth.release();
+        mask.release();
+        pts.release();
+        spts.release();
+        out.release();
+        key.release();
+        skey.release();
+        slot.release();
+        bstart.release();
+        tiles.release();
+        blk.release();
+        blk2.release();
+        n.release();
+        keep.release();
+    }
+};
+
 }  // namespace
 
 struct dsi_context {
@@ -131,6 +172,7 @@ struct dsi_context {
     // grids, mappers and batches created from this context and not yet destroyed: each holds a pointer to it, so the
     // context refuses to go while any is alive (destroying it first was a use-after-free in their destroy)
     std::atomic<int> children{0};
+    PcBuffers pc;  // dsi_radius_outlier_removal
 };
 
 // the per-device upload stream (see dsi_context::upload_stream)
@@ -322,6 +364,10 @@ struct dsi_mapper {
     DevBuf<uint8_t> idx, conf8, mask, idx_filtered;
     DevBuf<uint32_t> minmax;
     bool depth_valid = false;
+    // m->depth / m->mask hold the FILTERED map and mask of the last dsi_mapper_filter_depth_map (the device-resident input of
+    // dsi_mapper_get_pointcloud); cleared by every call that writes a new depth map (depth_buffers_ready)
+    bool filtered_valid = false;
+    PcBuffers pc;
     bool fused_keys_dirty = false;  // the fused kernel may have written keys that no unpack cleared
     // The depth map leaves the device on the context's COPY stream, so that fetching window w's map
     // does not queue behind window w+1's kernels on the compute stream: "ready" (compute stream, after
@@ -650,6 +696,7 @@ int depth_buffers_ready(dsi_mapper* m)
     }
     HIP_TRY(hipEventRecord(m->ev_depth_ready, m->ctx->stream));
     m->depth_valid = true;
+    m->filtered_valid = false;
     return DSI_OK;
 }
 
@@ -904,6 +951,7 @@ int dsi_context_destroy(dsi_context_t* ctx)
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     if (ctx->ms_accum) (void)hipFree(ctx->ms_accum);
     if (ctx->collapse_scratch) (void)hipFree(ctx->collapse_scratch);
+    ctx->pc.release();
     for (hipEvent_t ev : ctx->marks) (void)hipEventDestroy(ev);
     ctx->marks.clear();
     if (ctx->t0) (void)hipEventDestroy(ctx->t0);
@@ -1344,6 +1392,7 @@ int dsi_mapper_destroy(dsi_mapper_t* m)
     m->mask.release();
     m->idx_filtered.release();
     m->minmax.release();
+    m->pc.release();
     for (auto& pr : m->timing_pairs) {
         (void)hipEventDestroy(pr.first);
         (void)hipEventDestroy(pr.second);
@@ -2614,6 +2663,7 @@ int dsi_mapper_filter_depth_map(dsi_mapper_t* m, const dsi_depthmap_options_t* o
         HIP_TRY(hipMemcpyAsync(idx_filtered_host, m->idx_filtered.p, npix, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     m->depth_valid = false;  // m->depth now holds the filtered map, m->conf has (0,0) overwritten
+    m->filtered_valid = true;
     return DSI_OK;
 }
 
@@ -2626,6 +2676,119 @@ int dsi_mapper_get_depth_map_from_dsi(dsi_mapper_t* m, dsi_grid_t* g, const dsi_
     if (!g) g = m->grid;
     if (int rc = dsi_mapper_depth_map_of(m, g)) return rc;  // collapseMaxZSlice, :368 (acquires the buffers)
     return dsi_mapper_filter_depth_map(m, opts, depth_host, conf_host, mask_host, idx_filtered_host);
+}
+
+// ---- the point cloud (mapper_emvs_stereo.cpp:440-480) ----
+
+static int check_radius_filter_args(float radius, int min_neighbors)
+{
+    REQUIRE(std::isfinite(radius) && radius > 0.f, DSI_ERR_INVALID, "radius_search must be finite and > 0 (got %g)", (double)radius);
+    REQUIRE(min_neighbors >= 0, DSI_ERR_INVALID, "min_num_neighbors must be >= 0 (got %d): PCL's k = 0 search is undefined",
+            min_neighbors);
+    return DSI_OK;
+}
+
+// keep flags of the first *n_dev of pc.pts (n_max of them at most) on `st`
+static int radius_filter_device(hipStream_t st, PcBuffers& pc, const uint32_t* n_dev, size_t n_max, float radius, int min_neighbors)
+{
+    HIP_TRY(dsi::launch_pc_radius_filter(st, pc.pts.p, n_dev, (uint32_t)n_max, radius, (uint32_t)min_neighbors + 1u, pc.scratch(),
+                                         pc.keep.p));
+    return DSI_OK;
+}
+
+int dsi_mapper_get_pointcloud(dsi_mapper_t* m, const float* depth_host, const uint8_t* mask_host,
+                              const dsi_pointcloud_options_t* opts, float* xyzi_host, size_t capacity, size_t* n_points,
+                              size_t* n_unfiltered)
+{
+    REQUIRE(m && opts && n_points, DSI_ERR_INVALID, "null argument");
+    REQUIRE(xyzi_host || capacity == 0, DSI_ERR_INVALID, "xyzi_host is null");
+    if (int rc = check_radius_filter_args(opts->radius_search, opts->min_num_neighbors)) return rc;
+    REQUIRE(!depth_host == !mask_host, DSI_ERR_INVALID,
+            "depth_host and mask_host must both be given, or both be NULL (the maps left on the device)");
+    REQUIRE((size_t)m->geom.nz == m->planes_full.size(), DSI_ERR_INVALID,
+            "a plane-sharded mapper holds no whole depth map of its own: the point cloud needs the whole arg-max");
+    const int nx = m->geom.nx, ny = m->geom.ny;
+    const size_t npix = (size_t)nx * ny;
+    REQUIRE(npix <= ((size_t)1 << 30), DSI_ERR_INVALID, "at most 2^30 pixels");
+    const bool resident = !depth_host;
+    if (resident) {
+        REQUIRE(m->filtered_valid, DSI_ERR_INVALID,
+                "no filtered depth map on the device: call dsi_mapper_filter_depth_map or dsi_mapper_get_depth_map_from_dsi "
+                "after the depth map was computed, or pass the maps");
+    } else {
+        for (size_t i = 0; i < npix; ++i)
+            REQUIRE(!mask_host[i] || std::isfinite(depth_host[i]), DSI_ERR_INVALID,
+                    "non-finite depth %g at masked pixel (%zu, %zu)", (double)depth_host[i], i % (size_t)nx, i / (size_t)nx);
+    }
+    dsi_context* ctx = m->ctx;
+    hipStream_t st = ctx->stream;
+    if (int rc = set_device(ctx)) return rc;
+    PcBuffers& pc = m->pc;
+    HIP_TRY(pc.reserve(npix));
+    const float* depth = m->depth.p;
+    const uint8_t* mask = m->mask.p;
+    if (resident) {
+        if (int rc = depth_buffers_acquire(m)) return rc;
+    } else {
+        HIP_TRY(pc.depth.reserve(npix));
+        HIP_TRY(pc.mask.reserve(npix));
+        HIP_TRY(hipMemcpyAsync(pc.depth.p, depth_host, npix * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(pc.mask.p, mask_host, npix, hipMemcpyHostToDevice, st));
+        depth = pc.depth.p;
+        mask = pc.mask.p;
+    }
+    const dsi::Geom& g = m->geom;
+    HIP_TRY(dsi::launch_pc_backproject(st, depth, mask, nx, ny, g.vfx, g.vfy, g.vcx, g.vcy, pc.blk.p, pc.tiles.p, pc.pts.p));
+    // (the count of the back-projected points stays on the device: the filter's kernels read it, sized for every pixel)
+    const uint32_t* n_dev = pc.blk.p + dsi::pc_block_words(npix) - 1;
+    uint32_t counts[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&counts[0], n_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (int rc = radius_filter_device(st, pc, n_dev, npix, opts->radius_search, opts->min_num_neighbors)) return rc;
+    // (the compaction's block counts go to a buffer of their own: n_dev still lives in pc.blk)
+    HIP_TRY(dsi::launch_pc_compact(st, pc.pts.p, pc.keep.p, (uint32_t)npix, pc.blk2.p, pc.tiles.p, pc.out.p));
+    HIP_TRY(hipMemcpyAsync(&counts[1], pc.blk2.p + dsi::pc_block_words(npix) - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (n_unfiltered) *n_unfiltered = counts[0];
+    *n_points = counts[1];
+    REQUIRE(capacity >= counts[1], DSI_ERR_INVALID, "capacity of %zu points is too small: %u needed", capacity, counts[1]);
+    if (counts[1]) {
+        HIP_TRY(hipMemcpyAsync(xyzi_host, pc.out.p, (size_t)counts[1] * sizeof(float4), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return DSI_OK;
+}
+
+int dsi_radius_outlier_removal(dsi_context_t* ctx, const float* xyz_host, size_t stride_floats, size_t n, float radius,
+                               int min_neighbors, uint8_t* keep_host)
+{
+    REQUIRE(ctx, DSI_ERR_INVALID, "ctx is null");
+    REQUIRE(stride_floats == 3 || stride_floats == 4, DSI_ERR_INVALID, "stride_floats must be 3 or 4 (got %zu)", stride_floats);
+    if (int rc = check_radius_filter_args(radius, min_neighbors)) return rc;
+    REQUIRE(n == 0 || (xyz_host && keep_host), DSI_ERR_INVALID, "null array");
+    REQUIRE(n <= ((size_t)1 << 30), DSI_ERR_INVALID, "at most 2^30 points");
+    if (n == 0) return DSI_OK;
+    if ((size_t)min_neighbors + 1 > n) {  // fewer points than a neighbourhood needs: everything is removed
+        std::memset(keep_host, 0, n);
+        return DSI_OK;
+    }
+    if (int rc = set_device(ctx)) return rc;
+    hipStream_t st = ctx->stream;
+    PcBuffers& pc = ctx->pc;
+    HIP_TRY(pc.reserve(n));
+    const uint32_t n32 = (uint32_t)n;
+    if (stride_floats == 4) {
+        HIP_TRY(hipMemcpyAsync(pc.pts.p, xyz_host, n * sizeof(float4), hipMemcpyHostToDevice, st));
+    } else {
+        std::vector<float4> packed(n);
+        for (size_t i = 0; i < n; ++i) packed[i] = make_float4(xyz_host[3 * i], xyz_host[3 * i + 1], xyz_host[3 * i + 2], 0.f);
+        HIP_TRY(hipMemcpyAsync(pc.pts.p, packed.data(), n * sizeof(float4), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));  // (packed is pageable and goes out of scope)
+    }
+    HIP_TRY(hipMemcpyAsync(pc.n.p, &n32, sizeof n32, hipMemcpyHostToDevice, st));
+    if (int rc = radius_filter_device(st, pc, pc.n.p, n, radius, min_neighbors)) return rc;
+    HIP_TRY(hipMemcpyAsync(keep_host, pc.keep.p, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
 }
 
 int dsi_mapper_last_vote_info(const dsi_mapper_t* m, dsi_vote_info_t* info)

@@ -282,4 +282,27 @@ hipError_t launch_div_probe(hipStream_t s, const float* n, const float* d, size_
 
 size_t max_dynamic_lds();
 
+// ---- point cloud (MapperEMVS::getPointcloud): back-projection, radius outlier removal, compaction ----
+// The radius filter's scratch, for up to n_max points: spts / key / skey / slot [n_max], bstart [pc_buckets(n_max) + 1],
+// tiles [pc_scan_tile_words(max(pc_buckets(n_max), pc_block_words(n_max)))].
+struct PcScratch {
+    float4* spts;
+    unsigned long long *key, *skey;
+    uint32_t *slot, *bstart, *tiles;
+};
+size_t pc_block_words(size_t n);       // per-workgroup counts of a compaction of n items, + the total
+size_t pc_scan_tile_words(size_t len);  // scan scratch for `len` values
+uint32_t pc_buckets(size_t n);          // hash buckets for n points: a power of two >= 2 n (n <= 2^30)
+// the masked pixels of depth / mask (nx x ny, row-major) as points (x, y, z, 1/z) in pixel order; the count lands in
+// blk[pc_block_words(nx * ny) - 1] (blk: pc_block_words(nx * ny) words)
+hipError_t launch_pc_backproject(hipStream_t s, const float* depth, const uint8_t* mask, int nx, int ny, float fx, float fy,
+                                 float cx, float cy, uint32_t* blk, uint32_t* tiles, float4* pts);
+// keep[i] (i < n_max) = 1 iff point i of the first *n_dev has >= need points j (itself included) with
+// (double) d2_f32(i, j) <= (double) radius^2; 0 from *n_dev on
+hipError_t launch_pc_radius_filter(hipStream_t s, const float4* pts, const uint32_t* n_dev, uint32_t n_max, float radius,
+                                   uint32_t need, const PcScratch& w, uint8_t* keep);
+// out = the points with keep > 0 in input order; their count lands in blk[pc_block_words(n_max) - 1]
+hipError_t launch_pc_compact(hipStream_t s, const float4* pts, const uint8_t* keep, uint32_t n_max, uint32_t* blk, uint32_t* tiles,
+                             float4* out);
+
 }  // namespace dsi

@@ -6309,4 +6309,306 @@ hipError_t launch_tie_patch(hipStream_t s, const uint32_t* pix, const uint8_t* n
     return hipExtGetLastError();
 }
 
+
+// ---- the point cloud: MapperEMVS::getPointcloud (mapper_emvs_stereo.cpp:440-480) ----
+// Back-projection of the masked pixels through the virtual camera, compacted in row-major pixel order (PCL's push_back
+// order), then PCL's RadiusOutlierRemoval restated as a count: point i is kept iff at least need = min_neighbors + 1
+// points j (j = i and duplicates included) have (double) d2_f32(i, j) <= (double) r * (double) r, with
+// d2_f32 = ((dx*dx) + dy*dy) + dz*dz in fp32 without FMA (FLANN's L2_Simple<float> over x, y, z).
+// The count runs over a uniform grid of cells of edge h = r (1 + 2^-10), hashed into a power-of-two number of buckets:
+//   * an fp32-accepted pair has |xi - xj| <= r (1 + 2^-23) < h (each fp32 term is <= the rounded sum), so their cells differ
+//     by at most one per axis -- the 27-cell neighbourhood holds every pair the test can accept;
+//   * the cell coordinate floor(x / h) is taken in double and clamped to +-kPcCellMax: below the clamp the quotient's rounding
+//     (<= 2^-32) is far inside the 2^-11 margin, beyond it far-away points share the boundary cell (more candidates, never
+//     fewer); NaN lands in a boundary cell and is never within the radius of anything;
+//   * a candidate of a visited bucket counts only if its OWN cell is the visited cell: hash collisions, and two neighbour
+//     cells that share a bucket, cannot count a point twice or count a point of a cell outside the neighbourhood.
+// The bucket fill uses atomics (the order inside a bucket varies); the keep flags do not depend on it.  Both compactions
+// are a per-block count, a scan and a scatter: deterministic.  No kernel here uses scratch memory (tests audit it).
+namespace {
+
+constexpr int kPcBlock = 256;      // threads per workgroup of every k_pc_ kernel
+constexpr int kPcScanTile = 1024;  // elements per workgroup of the scan kernels (4 per thread)
+constexpr int kPcCellMax = (1 << 20) - 2;  // |cell coordinate| <= kPcCellMax: 21 bits per axis with the +-1 neighbours
+
+__device__ inline uint32_t pc_wave_inclusive(uint32_t v)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t t = __shfl_up(v, off, 64);
+        if (lane >= off) v += t;
+    }
+    return v;
+}
+
+// exclusive prefix of v over the workgroup (kPcBlock threads, all of them call); *total: the workgroup's sum
+__device__ inline uint32_t pc_block_exclusive(uint32_t v, uint32_t* total)
+{
+    __shared__ uint32_t wsum[kPcBlock / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t inc = pc_wave_inclusive(v);
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    uint32_t before = 0, sum = 0;
+#pragma unroll
+    for (int k = 0; k < kPcBlock / 64; ++k) {
+        const uint32_t s = wsum[k];
+        before += k < w ? s : 0u;
+        sum += s;
+    }
+    __syncthreads();  // (wsum is reused by the next call)
+    *total = sum;
+    return before + inc - v;
+}
+
+__device__ inline int pc_cell(float v, double inv_h)
+{
+    const double q = floor((double)v * inv_h);
+    return (int)fmin(fmax(q, (double)-kPcCellMax), (double)kPcCellMax);
+}
+
+__device__ inline unsigned long long pc_key(int cx, int cy, int cz)
+{
+    return (unsigned long long)(cx + kPcCellMax + 1) | ((unsigned long long)(cy + kPcCellMax + 1) << 21) |
+           ((unsigned long long)(cz + kPcCellMax + 1) << 42);
+}
+
+__device__ inline uint32_t pc_hash(unsigned long long k, uint32_t bmask)
+{
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ull;
+    k ^= k >> 33;
+    return (uint32_t)k & bmask;
+}
+
+// blk[b] = number of flags > 0 in [b * kPcBlock, (b + 1) * kPcBlock) of the first n
+__global__ void __launch_bounds__(kPcBlock) k_pc_flag_count(const uint8_t* __restrict__ flag, uint32_t n, uint32_t* __restrict__ blk)
+{
+    const uint32_t i = blockIdx.x * kPcBlock + threadIdx.x;
+    const bool f = i < n && flag[i] > 0;
+    uint32_t total;
+    (void)pc_block_exclusive(f ? 1u : 0u, &total);
+    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+}
+
+// exclusive scan of a[0, L) in place, a[L] = the sum: tile sums, their scan (one workgroup), then each tile
+__global__ void __launch_bounds__(kPcBlock) k_pc_scan_tiles(const uint32_t* __restrict__ a, uint32_t L, uint32_t* __restrict__ tiles)
+{
+    const size_t base = (size_t)blockIdx.x * kPcScanTile + threadIdx.x * 4;
+    uint32_t s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s += base + k < L ? a[base + k] : 0u;
+    uint32_t total;
+    (void)pc_block_exclusive(s, &total);
+    if (threadIdx.x == 0) tiles[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(kPcBlock) k_pc_scan_top(uint32_t* __restrict__ tiles, uint32_t T)
+{
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < T; base += kPcScanTile) {
+        const uint32_t j = base + threadIdx.x * 4;
+        uint32_t v[4], s = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[k] = j + k < T ? tiles[j + k] : 0u;
+            s += v[k];
+        }
+        uint32_t total;
+        uint32_t run = carry + pc_block_exclusive(s, &total);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (j + k < T) tiles[j + k] = run;
+            run += v[k];
+        }
+        carry += total;
+    }
+    if (threadIdx.x == 0) tiles[T] = carry;
+}
+
+__global__ void __launch_bounds__(kPcBlock) k_pc_scan_apply(uint32_t* __restrict__ a, uint32_t L, const uint32_t* __restrict__ tiles, uint32_t T)
+{
+    const size_t base = (size_t)blockIdx.x * kPcScanTile + threadIdx.x * 4;
+    uint32_t v[4], s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        v[k] = base + k < L ? a[base + k] : 0u;
+        s += v[k];
+    }
+    uint32_t total;
+    uint32_t run = tiles[blockIdx.x] + pc_block_exclusive(s, &total);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (base + k < L) a[base + k] = run;
+        run += v[k];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) a[L] = tiles[T];
+}
+
+// mapper_emvs_stereo.cpp:455-464 in double: projectPixelTo3dRay (geometry_utils.hpp:56-59, float members), Eigen's normalize()
+// (squaredNorm, then / sqrt when > 0), b / b[2] * depth; stored as float, intensity = 1.0 / z of the stored z.  IEEE divide and
+// square root (no fast-math; -ffp-contract=off).  Point k of the compacted cloud: blk_off[block] + rank inside the block.
+__global__ void __launch_bounds__(kPcBlock) k_pc_backproject(const float* __restrict__ depth, const uint8_t* __restrict__ mask,
+                                                             int nx, uint32_t npix, float fx, float fy, float cx, float cy,
+                                                             const uint32_t* __restrict__ blk_off, float4* __restrict__ pts)
+{
+    const uint32_t i = blockIdx.x * kPcBlock + threadIdx.x;
+    const bool f = i < npix && mask[i] > 0;
+    uint32_t total;
+    const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);
+    if (!f) return;
+    const uint32_t y = i / (uint32_t)nx, x = i - y * (uint32_t)nx;
+    double bx = ((double)x - (double)cx) / (double)fx;
+    double by = ((double)y - (double)cy) / (double)fy;
+    double bz = 1.0;
+    const double sq = (bx * bx + by * by) + bz * bz;
+    if (sq > 0.0) {
+        const double nrm = sqrt(sq);
+        bx = bx / nrm;
+        by = by / nrm;
+        bz = bz / nrm;
+    }
+    const double d = (double)depth[i];
+    const float X = (float)((bx / bz) * d), Y = (float)((by / bz) * d), Z = (float)((bz / bz) * d);
+    pts[blk_off[blockIdx.x] + rank] = make_float4(X, Y, Z, (float)(1.0 / (double)Z));
+}
+
+// each point's cell key and its slot in its bucket (bcount zeroed by the caller)
+__global__ void __launch_bounds__(kPcBlock) k_pc_cells(const float4* __restrict__ pts, const uint32_t* __restrict__ n_dev,
+                                                       double inv_h, uint32_t bmask, unsigned long long* __restrict__ key,
+                                                       uint32_t* __restrict__ bcount, uint32_t* __restrict__ slot)
+{
+    const uint32_t i = blockIdx.x * kPcBlock + threadIdx.x;
+    if (i >= *n_dev) return;
+    const float4 p = pts[i];
+    const unsigned long long k = pc_key(pc_cell(p.x, inv_h), pc_cell(p.y, inv_h), pc_cell(p.z, inv_h));
+    key[i] = k;
+    slot[i] = atomicAdd(&bcount[pc_hash(k, bmask)], 1u);
+}
+
+// counting sort by bucket: bstart = exclusive scan of the bucket counts
+__global__ void __launch_bounds__(kPcBlock) k_pc_bucket_scatter(const float4* __restrict__ pts, const unsigned long long* __restrict__ key,
+                                                                const uint32_t* __restrict__ slot, const uint32_t* __restrict__ bstart,
+                                                                const uint32_t* __restrict__ n_dev, uint32_t bmask,
+                                                                float4* __restrict__ spts, unsigned long long* __restrict__ skey)
+{
+    const uint32_t i = blockIdx.x * kPcBlock + threadIdx.x;
+    if (i >= *n_dev) return;
+    const unsigned long long k = key[i];
+    const uint32_t pos = bstart[pc_hash(k, bmask)] + slot[i];
+    spts[pos] = pts[i];
+    skey[pos] = k;
+}
+
+// keep[i] = at least `need` points within the radius (the count rule above); keep[i] = 0 for n <= i < n_max
+__global__ void __launch_bounds__(kPcBlock) k_pc_count(const float4* __restrict__ pts, const unsigned long long* __restrict__ key,
+                                                       const uint32_t* __restrict__ n_dev, uint32_t n_max,
+                                                       const uint32_t* __restrict__ bstart, const float4* __restrict__ spts,
+                                                       const unsigned long long* __restrict__ skey, uint32_t bmask, double rr,
+                                                       uint32_t need, uint8_t* __restrict__ keep)
+{
+    const uint32_t i = blockIdx.x * kPcBlock + threadIdx.x;
+    if (i >= n_max) return;
+    if (i >= *n_dev) {
+        keep[i] = 0;
+        return;
+    }
+    const float4 p = pts[i];
+    const unsigned long long k = key[i];
+    uint32_t cnt = 0;
+    for (int dz = -1; dz <= 1 && cnt < need; ++dz)
+        for (int dy = -1; dy <= 1 && cnt < need; ++dy)
+            for (int dx = -1; dx <= 1 && cnt < need; ++dx) {
+                const unsigned long long nb =
+                    k + (unsigned long long)((long long)dx + ((long long)dy << 21) + ((long long)dz << 42));
+                const uint32_t b = pc_hash(nb, bmask);
+                const uint32_t e = bstart[b + 1];
+                for (uint32_t j = bstart[b]; j < e; ++j) {
+                    if (skey[j] != nb) continue;
+                    const float4 q = spts[j];
+                    const float ddx = p.x - q.x, ddy = p.y - q.y, ddz = p.z - q.z;
+                    const float d2 = (ddx * ddx + ddy * ddy) + ddz * ddz;
+                    if ((double)d2 <= rr && ++cnt >= need) break;
+                }
+            }
+    keep[i] = cnt >= need ? 1 : 0;
+}
+
+// out[blk_off[block] + rank] = pts[i] for every kept i, in input order
+__global__ void __launch_bounds__(kPcBlock) k_pc_compact(const float4* __restrict__ pts, const uint8_t* __restrict__ keep, uint32_t n_max,
+                                                         const uint32_t* __restrict__ blk_off, float4* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * kPcBlock + threadIdx.x;
+    const bool f = i < n_max && keep[i] > 0;
+    uint32_t total;
+    const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);
+    if (f) out[blk_off[blockIdx.x] + rank] = pts[i];
+}
+
+uint32_t pc_blocks(size_t n) { return (uint32_t)((n + kPcBlock - 1) / kPcBlock); }
+
+// exclusive scan of a[0, L) in place with a[L] = the sum; tiles: pc_scan_tile_words(L) words
+hipError_t pc_scan(hipStream_t s, uint32_t* a, uint32_t L, uint32_t* tiles)
+{
+    const uint32_t T = (L + kPcScanTile - 1) / kPcScanTile;  // (L > 0: the callers skip empty inputs)
+    hipLaunchKernelGGL(k_pc_scan_tiles, dim3(T), dim3(kPcBlock), 0, s, a, L, tiles);
+    hipLaunchKernelGGL(k_pc_scan_top, dim3(1), dim3(kPcBlock), 0, s, tiles, T);
+    hipLaunchKernelGGL(k_pc_scan_apply, dim3(T), dim3(kPcBlock), 0, s, a, L, tiles, T);
+    return hipExtGetLastError();
+}
+
+}  // namespace
+
+size_t pc_block_words(size_t n) { return pc_blocks(n) + 1; }
+size_t pc_scan_tile_words(size_t L) { return (L + kPcScanTile - 1) / kPcScanTile + 1; }
+uint32_t pc_buckets(size_t n)
+{
+    uint32_t m = 64;
+    while (m < 2 * n) m <<= 1;
+    return m;
+}
+
+hipError_t launch_pc_backproject(hipStream_t s, const float* depth, const uint8_t* mask, int nx, int ny, float fx, float fy,
+                                 float cx, float cy, uint32_t* blk, uint32_t* tiles, float4* pts)
+{
+    const uint32_t npix = (uint32_t)nx * (uint32_t)ny, nb = pc_blocks(npix);
+    hipLaunchKernelGGL(k_pc_flag_count, dim3(nb), dim3(kPcBlock), 0, s, mask, npix, blk);
+    hipError_t e = pc_scan(s, blk, nb, tiles);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_pc_backproject, dim3(nb), dim3(kPcBlock), 0, s, depth, mask, nx, npix, fx, fy, cx, cy, blk, pts);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_pc_radius_filter(hipStream_t s, const float4* pts, const uint32_t* n_dev, uint32_t n_max, float radius,
+                                   uint32_t need, const PcScratch& w, uint8_t* keep)
+{
+    if (n_max == 0) return hipSuccess;
+    const uint32_t nb = pc_blocks(n_max), M = pc_buckets(n_max), bmask = M - 1;
+    const double h = (double)radius * (1.0 + 0x1p-10);  // (exact: 24 + 11 bits)
+    const double rr = (double)radius * (double)radius;   // (exact: 48 bits)
+    hipError_t e = hipMemsetAsync(w.bstart, 0, (size_t)M * sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_pc_cells, dim3(nb), dim3(kPcBlock), 0, s, pts, n_dev, 1.0 / h, bmask, w.key, w.bstart, w.slot);
+    if ((e = pc_scan(s, w.bstart, M, w.tiles)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_pc_bucket_scatter, dim3(nb), dim3(kPcBlock), 0, s, pts, w.key, w.slot, w.bstart, n_dev, bmask, w.spts, w.skey);
+    hipLaunchKernelGGL(k_pc_count, dim3(nb), dim3(kPcBlock), 0, s, pts, w.key, n_dev, n_max, w.bstart, w.spts, w.skey, bmask, rr,
+                       need, keep);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_pc_compact(hipStream_t s, const float4* pts, const uint8_t* keep, uint32_t n_max, uint32_t* blk, uint32_t* tiles,
+                             float4* out)
+{
+    if (n_max == 0) return hipSuccess;
+    const uint32_t nb = pc_blocks(n_max);
+    hipLaunchKernelGGL(k_pc_flag_count, dim3(nb), dim3(kPcBlock), 0, s, keep, n_max, blk);
+    hipError_t e = pc_scan(s, blk, nb, tiles);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_pc_compact, dim3(nb), dim3(kPcBlock), 0, s, pts, keep, n_max, blk, out);
+    return hipExtGetLastError();
+}
+
 }  // namespace dsi

@@ -52,6 +52,10 @@ class _DepthMapOptions(C.Structure):
                 ("median_filter_size", C.c_int), ("max_confidence", C.c_double)]
 
 
+class _PointCloudOptions(C.Structure):
+    _fields_ = [("radius_search", C.c_float), ("min_num_neighbors", C.c_int)]
+
+
 class _ScatterPlan(C.Structure):
     _fields_ = [("q", C.c_int), ("own_begin", C.c_int), ("own_count", C.c_int), ("tail_begin", C.c_int),
                 ("tail_count", C.c_int)]
@@ -186,6 +190,9 @@ def load_library():
         "dsi_mapper_get_depth_map_from_dsi": (C.c_int, [vp, vp, C.POINTER(_DepthMapOptions), f32p, f32p,
                                                        u8p, u8p]),
         "dsi_mapper_filter_depth_map": (C.c_int, [vp, C.POINTER(_DepthMapOptions), f32p, f32p, u8p, u8p]),
+        "dsi_mapper_get_pointcloud": (C.c_int, [vp, f32p, u8p, C.POINTER(_PointCloudOptions), f32p, C.c_size_t, szp,
+                                                szp]),
+        "dsi_radius_outlier_removal": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, C.c_float, C.c_int, u8p]),
         "dsi_mapper_last_vote_info": (C.c_int, [vp, C.POINTER(_VoteInfo)]),
         "dsi_mapper_set_kernel_timing": (C.c_int, [vp, C.c_int]),
         "dsi_mapper_vote_kernel_time": (C.c_int, [vp, f32p, intp]),
@@ -685,6 +692,29 @@ class OptionsDepthMap:
         self.max_confidence = float(max_confidence)
 
 
+class OptionsPointCloud:
+    """mapper_emvs_stereo.hpp:84-89 (defaults of main.cpp:80-81: --radius_search, --min_num_neighbors)."""
+
+    def __init__(self, radius_search_=0.05, min_num_neighbors_=3):
+        self.radius_search_ = float(radius_search_)
+        self.min_num_neighbors_ = int(min_num_neighbors_)
+
+
+def radius_outlier_removal(ctx, xyz, radius, min_neighbors):
+    """pcl::RadiusOutlierRemoval on the device (dsi_radius_outlier_removal): xyz (N, 3) or (N, 4) float32 -- x, y, z
+    first -- to a bool keep mask.  Point i is kept iff at least min_neighbors + 1 points j (j = i and duplicates
+    included) satisfy (double) d2_f32(i, j) <= (double) radius**2, d2_f32 = ((dx*dx) + dy*dy) + dz*dz in fp32 without
+    FMA (FLANN's L2_Simple<float>); radius is taken as float32 like OptionsPointCloud::radius_search_."""
+    xyz = _arr(xyz, np.float32)
+    if xyz.ndim != 2 or xyz.shape[1] not in (3, 4):
+        raise ValueError("xyz must be (N, 3) or (N, 4)")
+    n = xyz.shape[0]
+    keep = np.zeros(n, np.uint8)
+    _check(load_library().dsi_radius_outlier_removal(ctx._h, _ptr(xyz, C.c_float), xyz.shape[1], n, C.c_float(radius),
+                                                     int(min_neighbors), _ptr(keep, C.c_uint8)))
+    return keep.astype(bool)
+
+
 class PinnedArray:
     """numpy array in page-locked host memory (dsi_host_alloc): the source / destination of
     asynchronous uploads and depth-map fetches.  `a` is the array; close() frees the memory."""
@@ -919,6 +949,31 @@ class MapperEMVS:
             self._h, C.byref(opts), _ptr(depth, C.c_float), _ptr(conf, C.c_float), _ptr(mask, C.c_uint8),
             _ptr(self.depth_cell_indices_filtered, C.c_uint8)))
         return depth, conf, mask
+
+    def getPointcloud(self, depth_map=None, mask=None, options_pc=None):
+        """MapperEMVS::getPointcloud (mapper_emvs_stereo.cpp:440-480) on the device: the pixels with mask > 0
+        back-projected through the virtual camera (double, row-major order), then PCL's RadiusOutlierRemoval
+        (radius_outlier_removal's count rule).  Returns an (N, 4) float32 array of x, y, z, intensity = 1 / z;
+        self.n_unfiltered_ is the count before the filter.  With depth_map and mask both None: the filtered maps the
+        last getDepthMapFromDSI(..., options_depth_map) / filterDepthMap left on the device (no upload)."""
+        if (depth_map is None) != (mask is None):
+            raise ValueError("pass both depth_map and mask, or neither")
+        o = options_pc or OptionsPointCloud()
+        opts = _PointCloudOptions(o.radius_search_, o.min_num_neighbors_)
+        npix = self.dimX * self.dimY
+        out = np.empty((npix, 4), np.float32)
+        n, n0 = C.c_size_t(), C.c_size_t()
+        dp = mp = None
+        if depth_map is not None:
+            depth_map = _arr(depth_map, np.float32)
+            mask = _arr(mask, np.uint8)
+            if depth_map.shape != (self.dimY, self.dimX) or mask.shape != (self.dimY, self.dimX):
+                raise ValueError("depth_map and mask must be (dimY, dimX)")
+            dp, mp = _ptr(depth_map, C.c_float), _ptr(mask, C.c_uint8)
+        _check(load_library().dsi_mapper_get_pointcloud(self._h, dp, mp, C.byref(opts), _ptr(out, C.c_float), npix,
+                                                        C.byref(n), C.byref(n0)))
+        self.n_unfiltered_ = n0.value
+        return out[:n.value].copy()
 
     def computeDepthMap(self, grid=None):
         """Asynchronous half of getDepthMapFromDSI; pair with fetchDepthMap()."""

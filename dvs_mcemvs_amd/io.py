@@ -4,11 +4,13 @@ trajectories can be replayed without ROS:
 
   write_grid_npy        Grid3D::writeGridNpy           cartesian3dgrid_IO.cpp:30-36   (.npy, shape {Z,Y,X} f32)
   save_depth_points     saveDepthMaps (txt part)        utils.cpp:31-46                ("col row depth" lines)
+  save_pcd_ascii        pcl::io::savePCDFileASCII       main.cpp:397-402               (.pcd v0.7, PointXYZI, ascii)
   read_pose_bag         parse of geometry_msgs/PoseStamped bags   data_loading.cpp:221-302 (ROSBAG v2.0; none / bz2 chunks)
   read_event_bag        parse of dvs_msgs/EventArray bags         data_loading.cpp:31-107, 211-216
   write_pose_bag, write_event_bag   test helpers: minimal writers of the same subset of the format
 
-Host-side file I/O only; nothing here touches voxels.
+Host-side file I/O only; nothing here touches voxels.  The .pcd layout is restated from PCL's documentation of the
+format and is not pinned against a PCL build (none is available to this project).
 """
 import bz2
 import struct
@@ -37,6 +39,40 @@ def save_depth_points(path, depth_map, mask):
         for r, c in zip(rows, cols):
             f.write("%d %d %g\n" % (c, r, depth_map[r, c]))
     return rows.shape[0]
+
+
+def save_pcd_ascii(path, points):
+    """What pcl::io::savePCDFileASCII(path, cloud) writes for a pcl::PointCloud<pcl::PointXYZI> of N points (main.cpp:
+    397-402 saves every run's getPointcloud output so): the "# .PCD v0.7" header with FIELDS x y z intensity, SIZE 4 4 4 4,
+    TYPE F F F F, COUNT 1 1 1 1, WIDTH N, HEIGHT 1, VIEWPOINT 0 0 0 1 0 0 0 (the cloud's default sensor pose), POINTS N,
+    DATA ascii, then one line per point, the four values at 8 significant digits (the default precision of
+    savePCDFileASCII; an ostream's default float format, i.e. %.8g; NaN as "nan").  UNPINNED: restated from PCL's
+    documentation of the format, not compared with PCL's own output.  points: (N, >= 4) array, x y z intensity first."""
+    pts = np.asarray(points, np.float32)
+    if pts.size == 0:
+        pts = pts.reshape(0, 4)
+    if pts.ndim != 2 or pts.shape[1] < 4:
+        raise ValueError("points must be (N, 4): x, y, z, intensity")
+    n = pts.shape[0]
+
+    def fmt(v):
+        return "nan" if np.isnan(v) else "%.8g" % float(v)
+
+    with open(path, "w") as f:
+        f.write("# .PCD v0.7 - Point Cloud Data file format\n"
+                "VERSION 0.7\n"
+                "FIELDS x y z intensity\n"
+                "SIZE 4 4 4 4\n"
+                "TYPE F F F F\n"
+                "COUNT 1 1 1 1\n"
+                "WIDTH %d\n"
+                "HEIGHT 1\n"
+                "VIEWPOINT 0 0 0 1 0 0 0\n"
+                "POINTS %d\n"
+                "DATA ascii\n" % (n, n))
+        for p in pts[:, :4]:
+            f.write(" ".join(fmt(v) for v in p) + "\n")
+    return n
 
 
 # ------------------------------------------------------------------ ROSBAG v2.0 (subset)

@@ -571,14 +571,21 @@ class WindowStream:
         self.k += 1
         return slot
 
-    def fetch(self, slot, options_depth_map=None):
+    def fetch(self, slot, options_depth_map=None, options_point_cloud=None):
         """(depth, confidence, indices) of the window submitted into `slot` (synchronises).  With
         options_depth_map (OptionsDepthMap): the reference's per-window outputs instead --
         (depth_map, confidence_map, mask) after the adaptive threshold, masked median and border removal
         of getDepthMapFromDSI (main.cpp:281 -> mapper_emvs_stereo.cpp:390-437), whichever way the
-        window's arg-max was produced."""
+        window's arg-max was produced.  With options_point_cloud (OptionsPointCloud; needs options_depth_map) as
+        well: (depth_map, confidence_map, mask, points), points the (N, 4) cloud of getPointcloud (main.cpp:396)
+        made of the filtered maps still on the device."""
+        if options_point_cloud is not None and options_depth_map is None:
+            raise ValueError("options_point_cloud needs options_depth_map: the point cloud is made of the filtered maps")
         if options_depth_map is not None:
-            return self.extract[slot].filterDepthMap(options_depth_map)
+            out = self.extract[slot].filterDepthMap(options_depth_map)
+            if options_point_cloud is not None:
+                out = out + (self.extract[slot].getPointcloud(options_pc=options_point_cloud),)
+            return out
         # (every slot has its own context when the stream is concurrent: the copies follow the window's kernels on its
         #  compute stream -- one stream per window in flight, plus the device's shared upload stream)
         return self.extract[slot].fetchDepthMap(in_order=self.concurrent)
@@ -606,10 +613,14 @@ class WindowStream:
 
 
 def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop_time_s, duration,
-                  out_skip, fusion_method=E.FUSE_HM, forward_looking=True, rv_pos=0.0, options_depth_map=None, **kw):
+                  out_skip, fusion_method=E.FUSE_HM, forward_looking=True, rv_pos=0.0, options_depth_map=None,
+                  options_point_cloud=None, **kw):
     """Generator over the windows of main.cpp:177-302: yields (ts, depth, confidence, indices) per
     window, pipelined one window deep; with options_depth_map, (ts, depth_map, confidence_map, mask)
-    -- the filtered outputs the reference saves per window."""
+    -- the filtered outputs the reference saves per window; with options_point_cloud as well, the window's
+    point cloud (main.cpp:396, an (N, 4) array: WindowStream.fetch) as a fifth element."""
+    if options_point_cloud is not None and options_depth_map is None:
+        raise ValueError("options_point_cloud needs options_depth_map: the point cloud is made of the filtered maps")
     ws = WindowStream(ctx, cams, dsi_shape, fusion_method, **kw)
     pending = None
     try:
@@ -618,9 +629,9 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
             ev = [window_events(events[c], t0, t1) for c in range(2)]
             slot = ws.submit(ev, trajectories, ts, rv_pos)
             if pending is not None:
-                yield (pending[0],) + ws.fetch(pending[1], options_depth_map)
+                yield (pending[0],) + ws.fetch(pending[1], options_depth_map, options_point_cloud)
             pending = (ts, slot)
         if pending is not None:
-            yield (pending[0],) + ws.fetch(pending[1], options_depth_map)
+            yield (pending[0],) + ws.fetch(pending[1], options_depth_map, options_point_cloud)
     finally:
         ws.close()

@@ -649,6 +649,34 @@ DSI_API int dsi_mapper_get_depth_map_from_dsi(dsi_mapper_t *m, dsi_grid_t *g, co
 DSI_API int dsi_mapper_filter_depth_map(dsi_mapper_t *m, const dsi_depthmap_options_t *opts, float *depth_host,
                                         float *conf_host, uint8_t *mask_host, uint8_t *idx_filtered_host);
 
+/* OptionsPointCloud (mapper_emvs_stereo.hpp:84-89; main.cpp:80-81) */
+typedef struct {
+    float radius_search;   /* --radius_search, default 0.05: must be finite and > 0 */
+    int min_num_neighbors; /* --min_num_neighbors, default 3: must be >= 0 */
+} dsi_pointcloud_options_t;
+
+/* MapperEMVS::getPointcloud(depth_map, mask, options_pc, pc) (mapper_emvs_stereo.cpp:440-480) on the device:
+ * every pixel with mask > 0 back-projected through the virtual camera in double (projectPixelTo3dRay, normalize(),
+ * b / b[2] * depth; intensity = 1 / z), in row-major pixel order, then PCL's RadiusOutlierRemoval as the count rule
+ * of dsi_radius_outlier_removal below.  depth_host (f32) / mask_host (u8) are ny x nx maps; both NULL = the filtered
+ * depth map and mask that the last dsi_mapper_filter_depth_map / dsi_mapper_get_depth_map_from_dsi left on the device
+ * (no upload; DSI_ERR_INVALID if there is none, i.e. none since the last call that wrote a new depth map).  Output:
+ * *n_points points of 4 floats (x, y, z, intensity) into xyzi_host; when capacity < *n_points nothing is written,
+ * *n_points is the size needed and the call returns DSI_ERR_INVALID (nx * ny is always enough).  n_unfiltered
+ * (may be NULL): the point count before the filter.  Refused on plane-sharded mappers and for a non-finite depth
+ * at a masked pixel.  Synchronises. */
+DSI_API int dsi_mapper_get_pointcloud(dsi_mapper_t *m, const float *depth_host, const uint8_t *mask_host,
+                                      const dsi_pointcloud_options_t *opts, float *xyzi_host, size_t capacity,
+                                      size_t *n_points, size_t *n_unfiltered);
+
+/* pcl::RadiusOutlierRemoval (radius_outlier_removal.hpp, dense cloud) on its own: point i of the n points xyz_host
+ * (stride_floats = 3 or 4 floats per point; x, y, z first) is kept (keep_host[i] = 1) iff at least min_neighbors + 1
+ * points j -- j = i and duplicates included -- satisfy (double) d2(i, j) <= (double) radius * (double) radius, with
+ * d2 = ((dx*dx) + dy*dy) + dz*dz in fp32 without FMA (FLANN's L2_Simple<float>).  n = 0 and n < min_neighbors + 1 are
+ * legal (everything is removed).  radius must be finite and > 0, min_neighbors >= 0.  Synchronises. */
+DSI_API int dsi_radius_outlier_removal(dsi_context_t *ctx, const float *xyz_host, size_t stride_floats, size_t n,
+                                       float radius, int min_neighbors, uint8_t *keep_host);
+
 /* HIP-event stopwatch around the voting kernel (the replacement of fillVoxelGrid's hot
  * loop, mapper_emvs_stereo.cpp:168-203) on the context's stream: enable, run any number of
  * evaluate/fill calls, then read the summed kernel time and launch count (synchronises and

@@ -150,6 +150,57 @@ inline bool inpaint_depth_cell_indices(const ImgT& /*filtered u8*/, const ImgT& 
     return false;
 }
 
+// The point cloud of MapperEMVS::getPointcloud (mapper_emvs_stereo.cpp:440-480): pcl::PointXYZI's four fields, and a
+// default cloud with the members of pcl::PointCloud<PointT> the reference's callers use (points, width, height, clear,
+// push_back, size, Ptr) -- no PCL header needed here.
+struct PointXYZI {
+    float x, y, z, intensity;
+};
+struct PointCloud {
+    typedef std::shared_ptr<PointCloud> Ptr;
+    std::vector<PointXYZI> points;
+    uint32_t width = 0, height = 0;  // unorganised: width = size(), height = 1 once it holds points
+    void clear()
+    {
+        points.clear();
+        width = height = 0;
+    }
+    void push_back(const PointXYZI& p)
+    {
+        points.push_back(p);
+        width = (uint32_t)points.size();
+        height = 1;
+    }
+    size_t size() const { return points.size(); }
+};
+
+// Customisation point: how the n points (x, y, z, intensity) of the engine's cloud are written into the caller's cloud
+// type.  Defaults: dsi::PointCloud and any pcl-like PointCloud<PointT> (points, clear(), width, height; PointT with
+// x y z intensity), and a smart pointer to either (Ptr: created when empty, then filled through it).  Overload it (in
+// the cloud type's namespace, or in namespace dsi before this header) for anything else.
+template <typename CloudT>
+inline auto point_cloud_assign(CloudT& cloud, const PointXYZI* p, size_t n)
+    -> decltype(cloud.clear(), cloud.points.resize(n), cloud.width = 0u, cloud.height = 0u, void())
+{
+    cloud.clear();
+    cloud.points.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        cloud.points[i].x = p[i].x;
+        cloud.points[i].y = p[i].y;
+        cloud.points[i].z = p[i].z;
+        cloud.points[i].intensity = p[i].intensity;
+    }
+    cloud.width = (uint32_t)n;  // pcl::PointCloud::push_back's bookkeeping
+    cloud.height = 1;
+}
+template <typename PtrT>
+inline auto point_cloud_assign(PtrT& cloud, const PointXYZI* p, size_t n)
+    -> decltype(cloud.reset(new typename PtrT::element_type), void())
+{
+    if (!cloud) cloud.reset(new typename PtrT::element_type);
+    point_cloud_assign(*cloud, p, n);
+}
+
 // One GPU + one stream; shared by every Grid3D / MapperEMVS created from it.
 class Context {
 public:
@@ -584,6 +635,11 @@ struct OptionsDepthMap {  // mapper_emvs_stereo.hpp:68-82
     double rv_pos = 0.;
 };
 
+struct OptionsPointCloud {  // mapper_emvs_stereo.hpp:84-89 (defaults of main.cpp:80-81)
+    float radius_search_ = 0.05f;
+    int min_num_neighbors_ = 3;
+};
+
 typedef LinearTrajectory TrajectoryType;
 
 class MapperEMVS {  // mapper_emvs_stereo.hpp:94-155
@@ -718,6 +774,32 @@ public:
         dsi::check(dsi_mapper_filter_depth_map(h_, &o, depth, conf, mk, nullptr));
     }
 
+    // void getPointcloud(const cv::Mat& depth_map, const cv::Mat& mask, const OptionsPointCloud&, PointCloud::Ptr& pc_)
+    //                                                                          mapper_emvs_stereo.hpp:111, .cpp:440-480
+    // on the device: the pixels with mask > 0 back-projected through the virtual camera (in double, like the reference),
+    // in row-major order, then PCL's RadiusOutlierRemoval (radius_search_, min_num_neighbors_) as an exact count over a
+    // uniform grid (dsi_mapper_get_pointcloud).  depth_map CV_32F / mask CV_8U of the DSI's size (any image type
+    // dsi::image_data reads); pc_ a dsi::PointCloud, a pcl-like PointCloud<PointXYZI> or a Ptr to either
+    // (dsi::point_cloud_assign).  The reference's call main.cpp:396 compiles as spelled there.
+    template <typename DepthImg, typename MaskImg, typename CloudT>
+    void getPointcloud(const DepthImg& depth_map, const MaskImg& mask, const OptionsPointCloud& options_pc, CloudT& pc_)
+    {
+        int nx, ny, nz;
+        dsi_.getDimensions(&nx, &ny, &nz);
+        if (depth_map.rows != ny || depth_map.cols != nx || mask.rows != ny || mask.cols != nx)
+            throw dsi::Error(DSI_ERR_INVALID, "getPointcloud: depth_map and mask must be dimY x dimX");  // :446-447
+        pointcloud(dsi::image_data<float>(const_cast<DepthImg&>(depth_map)),
+                   dsi::image_data<uint8_t>(const_cast<MaskImg&>(mask)), options_pc, pc_);
+    }
+    // the same on the filtered depth map and mask the last getDepthMapFromDSI(..., options) / filterDepthMap left on the
+    // device (no upload; dsi::Error if there is none since the last new depth map)
+    template <typename CloudT>
+    void getPointcloud(const OptionsPointCloud& options_pc, CloudT& pc_)
+    {
+        pointcloud(nullptr, nullptr, options_pc, pc_);
+    }
+    size_t pointsBeforeFilter() const { return pc_unfiltered_; }  // of the last getPointcloud
+
     // MapperEMVS::convertDepthIndicesToValues (mapper_emvs_stereo.cpp:302-313) on host images: depth = cellIndexToDepth(index)
     template <typename IdxImg, typename DepthImg>
     void convertDepthIndicesToValues(IdxImg& depth_cell_indices, DepthImg& depth_map)
@@ -789,6 +871,22 @@ private:
         else
             dsi::image_release(*depth_map_dense);
     }
+    template <typename CloudT>
+    void pointcloud(const float* depth, const uint8_t* mask, const OptionsPointCloud& options_pc, CloudT& pc_)
+    {
+        int nx, ny, nz;
+        dsi_.getDimensions(&nx, &ny, &nz);
+        const size_t npix = (size_t)nx * ny;
+        pc_buf_.resize(npix);  // (nx * ny points always fit; kept from call to call)
+        dsi_pointcloud_options_t o{};
+        o.radius_search = options_pc.radius_search_;
+        o.min_num_neighbors = options_pc.min_num_neighbors_;
+        size_t n = 0;
+        dsi::check(dsi_mapper_get_pointcloud(h_, depth, mask, &o, reinterpret_cast<float*>(pc_buf_.data()), npix, &n,
+                                             &pc_unfiltered_));
+        using dsi::point_cloud_assign;  // the defaults; an overload for CloudT found by ADL wins over them
+        point_cloud_assign(pc_, pc_buf_.data(), n);
+    }
     template <typename CamT>
     static dsi::PinholeCameraModel convert(const CamT& cam)
     {
@@ -801,6 +899,8 @@ private:
     std::vector<uint16_t> xs_, ys_;
     std::vector<double> ts_;
     size_t events_voted_ = 0;
+    std::vector<dsi::PointXYZI> pc_buf_;
+    size_t pc_unfiltered_ = 0;
 };
 
 }  // namespace EMVS

@@ -352,7 +352,8 @@ inline dsi::Transformation process_1_depth_map(const LinearTrajectory& trajector
 // mapper_fused.getDepthMapFromDSI(...) before the filters, bit for bit (process_1_depth_map above is the one-window form).
 //
 // on_window(const dsi::WindowDepthMap&) is called once per window, in window order, from the calling thread; with
-// options_depth_map it also carries the filtered outputs of main.cpp:281.
+// options_depth_map it also carries the filtered outputs of main.cpp:281, with options_point_cloud (which needs
+// options_depth_map) the point cloud of main.cpp:396 as well.
 namespace dsi {
 
 struct WindowDepthMap {
@@ -367,6 +368,9 @@ struct WindowDepthMap {
     // the window (adaptive threshold, masked median, border removal: mapper_emvs_stereo.cpp:390-437)
     Image<float> filtered_depth_map, filtered_confidence_map;
     Image<uint8_t> semidense_mask;
+    // with options_point_cloud as well: main.cpp:396's getPointcloud(depth_map, semidense_mask, opts_pc, pc) of those
+    // filtered maps, in the reference view (mapper_emvs_stereo.cpp:440-480; T_rv_w above takes it to the world frame)
+    PointCloud point_cloud;
 };
 
 // where the calling thread of full_sequence_depth_maps spent its time (milliseconds, summed over the windows)
@@ -474,7 +478,8 @@ inline size_t full_sequence_depth_maps(const std::vector<int>& devices, const Pi
                                        double duration, double out_skip, bool forward_looking, int fusion_method,
                                        OnWindow&& on_window, int depth = 2, double rv_pos = 0.0,
                                        const EMVS::OptionsDepthMap* options_depth_map = nullptr,
-                                       WindowStreamStats* stats = nullptr)
+                                       WindowStreamStats* stats = nullptr,
+                                       const EMVS::OptionsPointCloud* options_point_cloud = nullptr)
 {
     using clock = std::chrono::steady_clock;
     const clock::time_point t_call = clock::now();
@@ -483,6 +488,9 @@ inline size_t full_sequence_depth_maps(const std::vector<int>& devices, const Pi
     if (!(duration > 0) || !(out_skip > 0)) throw Error(DSI_ERR_INVALID, "full_sequence_depth_maps: duration and out_skip must be > 0");
     if (depth < 1) depth = 1;
     if (devices.empty()) throw Error(DSI_ERR_INVALID, "full_sequence_depth_maps: no device");
+    if (options_point_cloud && !options_depth_map)
+        throw Error(DSI_ERR_INVALID, "full_sequence_depth_maps: the point cloud is made of the filtered maps: options_point_cloud "
+                                     "needs options_depth_map");
     struct Slot {
         Context ctx;
         EMVS::MapperEMVS m0, m1, out;
@@ -566,6 +574,8 @@ inline size_t full_sequence_depth_maps(const std::vector<int>& devices, const Pi
         fill(s.w.depth_cell_indices, s.host[2]);
         if (options_depth_map)  // the filters run on the arg-max the slot's mapper still holds on the device
             s.out.filterDepthMap(s.w.filtered_depth_map, s.w.filtered_confidence_map, s.w.semidense_mask, *options_depth_map);
+        if (options_point_cloud)  // ... and the point cloud is made of the filtered maps the filters left there
+            s.out.getPointcloud(*options_point_cloud, s.w.point_cloud);
         on_window(static_cast<const WindowDepthMap&>(s.w));
         st.deliver_ms += since(t0);
     };
@@ -702,11 +712,13 @@ inline size_t full_sequence_depth_maps(int device, const PinholeCameraModel& cam
                                        double duration, double out_skip, bool forward_looking, int fusion_method,
                                        OnWindow&& on_window, int depth = 2, double rv_pos = 0.0,
                                        const EMVS::OptionsDepthMap* options_depth_map = nullptr,
-                                       WindowStreamStats* stats = nullptr)
+                                       WindowStreamStats* stats = nullptr,
+                                       const EMVS::OptionsPointCloud* options_point_cloud = nullptr)
 {
     return full_sequence_depth_maps(std::vector<int>{device}, cam0, cam1, dsi_shape, trajectory0, trajectory1, events0, events1,
                                     start_time_s, stop_time_s, duration, out_skip, forward_looking, fusion_method,
-                                    std::forward<OnWindow>(on_window), depth, rv_pos, options_depth_map, stats);
+                                    std::forward<OnWindow>(on_window), depth, rv_pos, options_depth_map, stats,
+                                    options_point_cloud);
 }
 
 }  // namespace dsi
