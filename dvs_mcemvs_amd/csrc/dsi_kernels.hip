@@ -752,15 +752,37 @@ constexpr int kFusedCellsTwoPerCu = 10;  // k_vote_fuse_argmax_2cu: half the LDS
 constexpr float kFixScale = 2147483648.f;      // 2^31
 constexpr double kFixInv = 1.0 / 2147483648.0;  // 2^-31
 
-// Q33.31 sum -> fp32, ONE rounding.  For v < 2^52 the double whose bits are (1044 << 52) | v is exactly
-// 2^21 + v * 2^-31; subtracting 2^21 is exact, so two double-rate instructions replace the 64-bit
-// integer -> double conversion (two conversions, a scale and an add).  Larger sums (> 2 M votes in one
-// voxel) take the general conversion, exact up to 2^53.
+// Q33.31 sum -> fp32, ONE rounding (to nearest, ties to even) for EVERY v < 2^64: the contract of DESIGN.md
+// ("GPU vs oracle"), asserted bit for bit by tests/test_gpu_exact_voxels.py (sums of 2^52 and more:
+// test_large_sums_are_rounded_once) against oracle.q31_to_float.
+//
+// Any v: below 2^53 the double of v is exact, and the conversion to fp32 rounds once.  From 2^53 up
+// (double)v would round first, and rounding that double to fp32 again can go wrong (2^53 + 2^30 + 2^29 - 1
+// -> 4194305.0 instead of 4194304.5).  There the low 11 bits are folded into bit 11 as one sticky bit
+// (round to odd): they lie below fp32's rounding bit (bit 29 at the least), so the folded value rounds to
+// fp32 exactly as v does, and with no set bit below bit 11 it is exact in a double.  (32-bit operations on
+// the low word only: the fused kernel's read-back converts a wave of these next to its register-resident
+// state.)
+__device__ __forceinline__ float fix_to_float_any(acc_t v)
+{
+    const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
+    const uint32_t folded = (lo & ~0x7ffu) | (((lo & 0x7ffu) + 0x7ffu) & 0x800u);
+    const acc_t w = ((acc_t)hi << 32) | (hi >= (1u << 21) ? folded : lo);
+    return (float)((double)w * kFixInv);
+}
+
+// For v < 2^52 the double whose bits are (1044 << 52) | v is exactly 2^21 + v * 2^-31; subtracting 2^21 is
+// exact, so two double-rate instructions replace the 64-bit integer -> double conversion (two conversions, a
+// scale and an add).
+__device__ __forceinline__ float fix_to_float_narrow(acc_t v)
+{
+    return (float)(__longlong_as_double((long long)(v | 0x4140000000000000ull)) - 2097152.0);
+}
+
 __device__ __forceinline__ float fix_to_float(acc_t v)
 {
-    if (__builtin_expect((v >> 52) == 0ull, 1))
-        return (float)(__longlong_as_double((long long)(v | 0x4140000000000000ull)) - 2097152.0);
-    return (float)((double)v * kFixInv);
+    if (__builtin_expect((v >> 52) == 0ull, 1)) return fix_to_float_narrow(v);
+    return fix_to_float_any(v);  // sums of 2^52 and more (> 2 M votes in one voxel)
 }
 
 // the four bilinear votes of m identical events (cartesian3dgrid.h:261-270) into the band
@@ -2667,12 +2689,11 @@ __device__ __forceinline__ void fused_consume(acc_t* __restrict__ band, int nx, 
             acc_t* cell = i < n_own ? own + i : band;  // band[0]: first halo row, cleared below
             *cell = 0;
         }
-        // sums of 2^52 and more (2 M votes in one voxel) take the general conversion: decided per wave
+        // sums of 2^52 and more (2 M votes in one voxel) take the wide conversion: decided per wave, then per lane
         const bool big = __builtin_amdgcn_ballot_w64((hi_or >> 20) != 0u) != 0ull;
 #pragma unroll
         for (int k = 0; k < HALF; ++k) {
-            const float v = big ? (float)((double)raw[k] * kFixInv)
-                                : (float)(__longlong_as_double((long long)(raw[k] | 0x4140000000000000ull)) - 2097152.0);
+            const float v = big ? fix_to_float_any(raw[k]) : fix_to_float_narrow(raw[k]);
             const int kk = h + k;
             if (MODE == FUSED_KEEP || MODE == FUSED_READ1) {
                 va[kk] = v;

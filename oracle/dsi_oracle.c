@@ -274,6 +274,77 @@ void orc_fill_voxel_grid_rows(const float *xy_z0, const float *centers, size_t n
     }
 }
 
+/* ---- the exact reference of the engine's voxels ---------------------------
+ * The same loop, coordinates, accept test and fp32 weights as orc_fill_voxel_grid, but every weight w is
+ * added as trunc(w * 2^31) into a uint64_t per voxel: the exact sum the engine's exact voting paths form
+ * (Q33.31).  count (may be NULL) receives the number of votes (four per accepted event, zero weights
+ * included) that touched each voxel.  Accumulated into, like orc_fill_voxel_grid. */
+static void orc_vote_q31(float x_f, float y_f, uint64_t *acc, uint32_t *count, int nx, int ny)
+{
+    if (x_f >= 0.f && y_f >= 0.f && x_f < (float)(nx - 1) && y_f < (float)(ny - 1)) {
+        const int x = (int)x_f, y = (int)y_f;
+        const size_t i = x + (size_t)y * nx;
+        const float fx = x_f - x, fy = y_f - y, fx1 = 1.f - fx, fy1 = 1.f - fy;
+        /* w <= 1: w * 2^31 is exact in fp32 and below 2^32; the cast truncates */
+        acc[i] += (uint64_t)((fx1 * fy1) * 0x1p31f);
+        acc[i + 1] += (uint64_t)((fx * fy1) * 0x1p31f);
+        acc[i + nx] += (uint64_t)((fx1 * fy) * 0x1p31f);
+        acc[i + nx + 1] += (uint64_t)((fx * fy) * 0x1p31f);
+        if (count) {
+            ++count[i];
+            ++count[i + 1];
+            ++count[i + nx];
+            ++count[i + nx + 1];
+        }
+    }
+}
+
+void orc_fill_voxel_grid_q31(const float *xy_z0, const float *centers, size_t n_packets,
+                             const float *raw_depths, int nz, const float *Kv, int nx, int ny,
+                             uint64_t *acc, uint32_t *count)
+{
+    enum { N = 128 };
+    const float z0 = raw_depths[0];
+    const float vfx = Kv[0], vfy = Kv[1], vcx = Kv[2], vcy = Kv[3];
+    const size_t n_events = n_packets * ORC_PACKET_SIZE;
+
+#pragma omp parallel for if (n_events >= 20000)
+    for (int depth_plane = 0; depth_plane < nz; ++depth_plane) {
+        const float *pe = xy_z0;
+        const size_t plane = (size_t)depth_plane * nx * ny;
+        for (size_t packet = 0; packet < n_packets; ++packet) {
+            const float *C = centers + 3 * packet;
+            const float zi = raw_depths[depth_plane];
+            const float a = z0 * (zi - C[2]);
+            const float bx = (z0 - zi) * (C[0] * vfx + C[2] * vcx);
+            const float by = (z0 - zi) * (C[1] * vfy + C[2] * vcy);
+            const float d = zi * (z0 - C[2]);
+            for (int batch = 0; batch < ORC_PACKET_SIZE / N; ++batch, pe += 2 * N) {
+                float X[N], Y[N];
+                for (int i = 0; i < N; ++i) {
+                    X[i] = (pe[2 * i] * a + bx) / d;
+                    Y[i] = (pe[2 * i + 1] * a + by) / d;
+                }
+                for (int i = 0; i < N; ++i)
+                    orc_vote_q31(X[i], Y[i], acc + plane, count ? count + plane : NULL, nx, ny);
+            }
+        }
+    }
+}
+
+/* Q33.31 -> fp32 with ONE rounding (to nearest, ties to even) for every v < 2^64: the x87 long double
+ * holds 64 significant bits, so v * 2^-31 is exact there and the conversion to float rounds once. */
+float orc_q31_to_float(uint64_t v)
+{
+    return (float)((long double)v * 0x1p-31L);
+}
+
+void orc_q31_to_float_n(const uint64_t *v, size_t n, float *out)
+{
+    for (size_t i = 0; i < n; ++i)
+        out[i] = orc_q31_to_float(v[i]);
+}
+
 /* ---- packetisation: mapper_emvs_stereo.cpp:67-99 ------------------------ */
 long orc_packetize(size_t n_events, const uint8_t *pose_ok, size_t *first_event,
                    size_t *mid_event)

@@ -85,6 +85,17 @@ void orc_fill_voxel_grid_rows(const float *xy_z0, const float *centers, size_t n
                               const float *raw_depths, int nz, const float *Kv, int nx, int ny,
                               int row_begin, int row_count, float *strip);
 
+/* The exact reference of the engine's exact voting paths: the loop of orc_fill_voxel_grid with every fp32
+ * weight w added as trunc(w * 2^31) into a uint64_t per voxel ([nz][ny][nx], ACCUMULATED INTO).  count
+ * (NULL allowed) is incremented once per vote (four per accepted event) on the voxels it touches.  A voxel
+ * of the engine's DSI is orc_q31_to_float of its sum ("GPU vs oracle"). */
+void orc_fill_voxel_grid_q31(const float *xy_z0, const float *centers, size_t n_packets,
+                             const float *raw_depths, int nz, const float *Kv, int nx, int ny,
+                             uint64_t *acc, uint32_t *count);
+/* fl32(v * 2^-31), correctly rounded (nearest, ties to even) for every v < 2^64 */
+float orc_q31_to_float(uint64_t v);
+void orc_q31_to_float_n(const uint64_t *v, size_t n, float *out);
+
 /* cartesian3dgrid.h:253-273 (single vote into one plane). */
 void orc_vote(float x_f, float y_f, float *plane, int nx, int ny);
 

@@ -63,6 +63,13 @@ def _load(path):
     L.orc_fill_voxel_grid_rows.argtypes = [f32p, f32p, C.c_size_t, f32p, C.c_int, f32p, C.c_int, C.c_int, C.c_int,
                                            C.c_int, f32p]
     L.orc_vote.argtypes = [C.c_float, C.c_float, f32p, C.c_int, C.c_int]
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    L.orc_fill_voxel_grid_q31.argtypes = [f32p, f32p, C.c_size_t, f32p, C.c_int, f32p, C.c_int, C.c_int, u64p, u32p]
+    L.orc_fill_voxel_grid_q31.restype = None
+    L.orc_q31_to_float.argtypes = [C.c_uint64]
+    L.orc_q31_to_float.restype = C.c_float
+    L.orc_q31_to_float_n.argtypes = [u64p, C.c_size_t, f32p]
+    L.orc_q31_to_float_n.restype = None
     L.orc_packetize.argtypes = [C.c_size_t, u8p, szp, szp]
     L.orc_packetize.restype = C.c_long
     L.orc_fuse2.argtypes = [f32p, f32p, C.c_size_t, C.c_int]
@@ -170,6 +177,42 @@ def fill_voxel_grid_rows(xy_z0, centers, raw_depths, Kv, nx, ny, row_begin, row_
     lib().orc_fill_voxel_grid_rows(_p(xy_z0, C.c_float), _p(centers, C.c_float), npk, _p(raw_depths, C.c_float), nz,
                                    _p(Kv, C.c_float), nx, ny, int(row_begin), int(row_count), _p(strip, C.c_float))
     return strip
+
+
+def fill_voxel_grid_q31(xy_z0, centers, raw_depths, Kv, nx, ny, acc=None, count=None):
+    """The exact reference of the engine's exact voting paths: fill_voxel_grid's votes, each fp32 weight w added as
+    trunc(w * 2^31) into a uint64 per voxel.  Returns (acc [nz][ny][nx] uint64, count [nz][ny][nx] uint32: votes per
+    voxel); both are accumulated into when given."""
+    xy_z0 = _f32(xy_z0).reshape(-1, 2)
+    centers = _f32(centers).reshape(-1, 3)
+    raw_depths = _f32(raw_depths)
+    Kv = _f32(Kv)
+    npk = centers.shape[0]
+    assert xy_z0.shape[0] == npk * PACKET
+    nz = raw_depths.shape[0]
+    if acc is None:
+        acc = np.zeros((nz, ny, nx), np.uint64)
+    if count is None:
+        count = np.zeros((nz, ny, nx), np.uint32)
+    assert acc.dtype == np.uint64 and count.dtype == np.uint32 and acc.flags.c_contiguous and count.flags.c_contiguous
+    assert acc.shape == (nz, ny, nx) and count.shape == (nz, ny, nx)
+    lib().orc_fill_voxel_grid_q31(_p(xy_z0, C.c_float), _p(centers, C.c_float), npk, _p(raw_depths, C.c_float), nz,
+                                  _p(Kv, C.c_float), nx, ny, _p(acc, C.c_uint64), _p(count, C.c_uint32))
+    return acc, count
+
+
+def q31_to_float(acc):
+    """fl32(acc * 2^-31), correctly rounded for every uint64 (one rounding)."""
+    acc = np.ascontiguousarray(acc, np.uint64)
+    out = np.empty(acc.shape, np.float32)
+    lib().orc_q31_to_float_n(_p(acc, C.c_uint64), acc.size, _p(out, C.c_float))
+    return out
+
+
+def fill_voxel_grid_exact(xy_z0, centers, raw_depths, Kv, nx, ny):
+    """-> (raw uint64 volume, fp32 volume): what every exact voting path of the engine must produce, bit for bit."""
+    acc, _ = fill_voxel_grid_q31(xy_z0, centers, raw_depths, Kv, nx, ny)
+    return acc, q31_to_float(acc)
 
 
 def vote(x_f, y_f, plane):

@@ -86,17 +86,15 @@ def warp_z0(x, y, H, lut=None, W=0):
     return np.stack([px / pz, py / pz], axis=1).astype(F)
 
 
-def fill_voxel_grid(xy_z0, centers, planes, Kv, nx, ny, dsi=None):
-    """mapper_emvs_stereo.cpp:151-205 + Grid3D::accumulateGridValueAt (cartesian3dgrid.h:253-273).
-    Per plane the votes are applied in packet order, event order, corner order g[0], g[1], g[nx],
-    g[nx+1] -- one unbuffered np.add.at over that exact sequence."""
+def _plane_votes(xy_z0, centers, planes, Kv, nx, ny):
+    """mapper_emvs_stereo.cpp:151-205 + Grid3D::accumulateGridValueAt (cartesian3dgrid.h:253-273): per plane k, the
+    flat voxel indices [n][4] and fp32 weights [n][4] of its accepted votes, in packet order, event order, corner
+    order g[0], g[1], g[nx], g[nx+1]."""
     xy = np.asarray(xy_z0, F).reshape(-1, 2)
     centers = np.asarray(centers, F).reshape(-1, 3)
     planes = np.asarray(planes, F)
     fx, fy, cx, cy = (F(v) for v in Kv)
     nz = planes.shape[0]
-    if dsi is None:
-        dsi = np.zeros((nz, ny, nx), F)
     z0 = planes[0]                                                    # :163
     npk = centers.shape[0]
     x0 = xy[:, 0].reshape(npk, PACKET)
@@ -125,8 +123,52 @@ def fill_voxel_grid(xy_z0, centers, planes, Kv, nx, ny, dsi=None):
             w = np.stack([(one - fxx) * (one - fyy), fxx * (one - fyy), (one - fxx) * fyy, fxx * fyy], axis=1)
             base = yi * nx + xi
             idx = np.stack([base, base + 1, base + nx, base + nx + 1], axis=1)
-            np.add.at(dsi[k].reshape(-1), idx.reshape(-1), w.astype(F).reshape(-1))   # :261-270, in order
+            yield k, idx, w.astype(F)
+
+
+def fill_voxel_grid(xy_z0, centers, planes, Kv, nx, ny, dsi=None):
+    """The reference's fp32 sums: per plane the votes are applied in their exact sequence by one unbuffered
+    np.add.at (:261-270, in order)."""
+    nz = np.asarray(planes).shape[0]
+    if dsi is None:
+        dsi = np.zeros((nz, ny, nx), F)
+    for k, idx, w in _plane_votes(xy_z0, centers, planes, Kv, nx, ny):
+        np.add.at(dsi[k].reshape(-1), idx.reshape(-1), w.reshape(-1))
     return dsi
+
+
+def fill_voxel_grid_q31(xy_z0, centers, planes, Kv, nx, ny):
+    """The engine's exact contract restated: every fp32 weight w enters its voxel as trunc(w * 2^31) (w * 2^31 is
+    exact in fp32), summed exactly in 64-bit integers.  -> (uint64 sums, vote counts), both [nz][ny][nx]."""
+    nz = np.asarray(planes).shape[0]
+    acc = np.zeros((nz, ny, nx), np.uint64)
+    count = np.zeros((nz, ny, nx), np.uint32)
+    for k, idx, w in _plane_votes(xy_z0, centers, planes, Kv, nx, ny):
+        q = np.trunc(w.astype(np.float64) * 2.0 ** 31).astype(np.uint64)
+        np.add.at(acc[k].reshape(-1), idx.reshape(-1), q.reshape(-1))
+        np.add.at(count[k].reshape(-1), idx.reshape(-1), np.uint32(1))
+    return acc, count
+
+
+def q31_to_f32(v):
+    """fl32(v * 2^-31) for a Python int 0 <= v < 2^64, rounded to nearest, ties to even, in integer arithmetic."""
+    v = int(v)
+    if v == 0:
+        return F(0.0)
+    shift = max(v.bit_length() - 24, 0)                              # keep 24 significant bits
+    q, r = divmod(v, 1 << shift)
+    half = (1 << shift) >> 1
+    if shift and (r > half or (r == half and q & 1)):
+        q += 1                                                        # (q may become 2^24: still exact)
+    return F(float(q) * 2.0 ** (shift - 31))                          # q * 2^(shift-31): exact in double and in fp32
+
+
+def q31_volume_to_f32(acc):
+    """q31_to_f32 over a volume (once per distinct value)."""
+    acc = np.asarray(acc, np.uint64)
+    vals, inv = np.unique(acc, return_inverse=True)
+    conv = np.array([q31_to_f32(v) for v in vals.tolist()], F)
+    return conv[inv].reshape(acc.shape)
 
 
 def fuse2(a, g, op):

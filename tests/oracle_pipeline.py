@@ -11,7 +11,10 @@ class OracleMapper:
     """MapperEMVS restated with oracle calls (mapper_emvs_stereo.cpp:29-64, 208-241)."""
 
     def __init__(self, cam, dimX=0, dimY=0, dimZ=100, min_depth=0.3, max_depth=5.0, fov=0.0,
-                 lut=None, inverse_depth=False):
+                 lut=None, inverse_depth=False, exact=False):
+        """exact=True: the DSI is the engine's exact contract instead of the reference's fp32 event-order sums -- every
+        weight added as trunc(w * 2^31) into a uint64 per voxel (self.acc), rounded to fp32 once (self.dsi);
+        self.count holds the votes per voxel."""
         w, h, fx, fy, cx, cy = cam
         self.W, self.H = int(w), int(h)
         self.K = np.array([fx, fy, cx, cy], np.float32)
@@ -23,6 +26,8 @@ class OracleMapper:
         self.Kv = np.array([f, f, np.float32(cx), np.float32(cy)], np.float32)
         self.lut = None if lut is None else np.ascontiguousarray(lut, np.float32)
         self.dsi = np.zeros((self.nz, self.ny, self.nx), np.float32)
+        self.exact = bool(exact)
+        self.acc = self.count = None
 
     def packetize(self, ts, trajectory, T_rv_w):
         """mapper_emvs_stereo.cpp:67-105 -> (first[np], Rt[np][12]) or None."""
@@ -50,6 +55,10 @@ class OracleMapper:
 
     def evaluate_packets(self, x, y, first, Rt):
         xy, centers = self.stage_a(x, y, first, Rt)
+        if self.exact:
+            self.acc, self.count = orc.fill_voxel_grid_q31(xy, centers, self.planes, self.Kv, self.nx, self.ny)
+            self.dsi = orc.q31_to_float(self.acc)
+            return xy, centers
         self.dsi[:] = 0  # resetGrid, :145
         orc.fill_voxel_grid(xy, centers, self.planes, self.Kv, self.nx, self.ny, self.dsi)
         return xy, centers
