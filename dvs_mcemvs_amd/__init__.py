@@ -21,6 +21,11 @@ from .engine import (  # noqa: F401
     FUSE_MAX,
     FUSE_MIN,
     FUSE_RMS,
+    FOCUS_DOG,
+    FOCUS_GRAD_MAG,
+    FOCUS_LAPLACIAN,
+    FOCUS_LOCAL_MS,
+    FOCUS_LOCAL_VAR,
     PACKET_SIZE,
     REDUCE_MAX,
     REDUCE_MIN,
@@ -57,5 +62,6 @@ __all__ = [
     "library_path", "load_library", "packetize", "packetize_strided", "pose_at", "radius_outlier_removal", "PACKET_SIZE",
     "FUSE_MIN", "FUSE_HM", "FUSE_GM", "FUSE_AM", "FUSE_RMS", "FUSE_MAX", "ACC_SUM", "ACC_INV_SUM", "ACC_LOG_SUM", "ACC_SQ_SUM", "ACC_MIN", "ACC_MAX", "ACC_GM_TREE",
     "REDUCE_SUM", "REDUCE_MIN", "REDUCE_MAX", "acc_reduce_op",
+    "FOCUS_LOCAL_VAR", "FOCUS_LOCAL_MS", "FOCUS_GRAD_MAG", "FOCUS_LAPLACIAN", "FOCUS_DOG",
     "VOTE_AUTO", "VOTE_GLOBAL_ATOMIC", "VOTE_LDS_BANDS", "VOTE_FUSED_ARGMAX",
 ]

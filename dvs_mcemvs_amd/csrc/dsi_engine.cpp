@@ -169,6 +169,9 @@ struct dsi_context {
     // i.e. no device synchronisation -- per call)
     void* collapse_scratch = nullptr;
     size_t collapse_scratch_bytes = 0;
+    // focus-based collapses: one arg-max key per pixel and plane range; dsi_grid_local_focus in place: the new volume
+    DevBuf<unsigned long long> focus_keys;
+    DevBuf<float> focus_volume;
     // grids, mappers and batches created from this context and not yet destroyed: each holds a pointer to it, so the
     // context refuses to go while any is alive (destroying it first was a use-after-free in their destroy)
     std::atomic<int> children{0};
@@ -951,6 +954,8 @@ int dsi_context_destroy(dsi_context_t* ctx)
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     if (ctx->ms_accum) (void)hipFree(ctx->ms_accum);
     if (ctx->collapse_scratch) (void)hipFree(ctx->collapse_scratch);
+    ctx->focus_keys.release();
+    ctx->focus_volume.release();
     ctx->pc.release();
     for (hipEvent_t ev : ctx->marks) (void)hipEventDestroy(ev);
     ctx->marks.clear();
@@ -1234,12 +1239,9 @@ int dsi_grid_collapse_max_z_dev(dsi_grid_t* g, float* conf_dev, uint8_t* idx_dev
     return DSI_OK;
 }
 
-int dsi_grid_collapse_max_z(dsi_grid_t* g, float* conf_host, uint8_t* idx_host)
+// the context's grow-only scratch of the host-output collapses: conf[npix] f32 + idx[npix] u8
+static int collapse_scratch(dsi_context* ctx, size_t npix, float** conf, uint8_t** idx)
 {
-    REQUIRE(g && conf_host && idx_host, DSI_ERR_INVALID, "null argument");
-    dsi_context* ctx = g->ctx;
-    if (int rc = set_device(ctx)) return rc;
-    const size_t npix = (size_t)g->nx * g->ny;
     const size_t need = npix * sizeof(float) + npix;
     if (ctx->collapse_scratch_bytes < need) {
         if (ctx->collapse_scratch) {
@@ -1251,12 +1253,110 @@ int dsi_grid_collapse_max_z(dsi_grid_t* g, float* conf_host, uint8_t* idx_host)
         HIP_TRY(hipMalloc(&ctx->collapse_scratch, need));
         ctx->collapse_scratch_bytes = need;
     }
-    float* conf = static_cast<float*>(ctx->collapse_scratch);
-    uint8_t* idx = reinterpret_cast<uint8_t*>(conf + npix);
-    if (int rc = dsi_grid_collapse_max_z_dev(g, conf, idx, nullptr, nullptr)) return rc;
+    *conf = static_cast<float*>(ctx->collapse_scratch);
+    *idx = reinterpret_cast<uint8_t*>(*conf + npix);
+    return DSI_OK;
+}
+
+// copy a collapse's outputs from the scratch to the host and wait
+static int collapse_download(dsi_context* ctx, size_t npix, const float* conf, const uint8_t* idx, float* conf_host,
+                             uint8_t* idx_host)
+{
     HIP_TRY(hipMemcpyAsync(conf_host, conf, npix * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(idx_host, idx, npix, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DSI_OK;
+}
+
+int dsi_grid_collapse_max_z(dsi_grid_t* g, float* conf_host, uint8_t* idx_host)
+{
+    REQUIRE(g && conf_host && idx_host, DSI_ERR_INVALID, "null argument");
+    dsi_context* ctx = g->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    const size_t npix = (size_t)g->nx * g->ny;
+    float* conf;
+    uint8_t* idx;
+    if (int rc = collapse_scratch(ctx, npix, &conf, &idx)) return rc;
+    if (int rc = dsi_grid_collapse_max_z_dev(g, conf, idx, nullptr, nullptr)) return rc;
+    return collapse_download(ctx, npix, conf, idx, conf_host, idx_host);
+}
+
+// ---- focus-based collapses and local focus (cartesian3dgrid.cpp:139-483) ----
+
+static int check_focus_args(const dsi_grid_t* g, int method, int half_patchsize)
+{
+    REQUIRE(method >= DSI_FOCUS_LOCAL_VAR && method <= DSI_FOCUS_DOG, DSI_ERR_BAD_OP,
+            "focus method %d is not one of 0..4 (LocalVar, LocalMeanSquare, GradMag, LaplacianMag, DoG)", method);
+    REQUIRE(half_patchsize >= 0 && half_patchsize <= 8, DSI_ERR_INVALID, "half_patchsize must be in 0..8 (got %d)",
+            half_patchsize);
+    REQUIRE(g->nz <= 256, DSI_ERR_INVALID, "arg-max indices are u8: dimZ must be <= 256 (got %d)", g->nz);
+    return DSI_OK;
+}
+
+// the focus collapse of g on ctx's stream, with ctx's key scratch
+static int focus_collapse(dsi_context* ctx, const dsi_grid_t* g, int method, int half_patchsize, float* conf, uint8_t* idx,
+                          const float* planes, float* depth)
+{
+    const size_t words = (size_t)dsi::focus_chunks(g->nx, g->ny, g->nz) * g->nx * g->ny;
+    HIP_TRY(ctx->focus_keys.reserve(words));
+    HIP_TRY(dsi::launch_focus_collapse(ctx->stream, g->data, g->nx, g->ny, g->nz, method, half_patchsize, ctx->focus_keys.p,
+                                       conf, idx, planes, depth));
+    return DSI_OK;
+}
+
+int dsi_grid_collapse_focus_dev(dsi_grid_t* g, int method, int half_patchsize, float* conf_dev, uint8_t* idx_dev,
+                                const float* planes_dev, float* depth_dev)
+{
+    REQUIRE(g && conf_dev && idx_dev, DSI_ERR_INVALID, "null argument");
+    if (int rc = check_focus_args(g, method, half_patchsize)) return rc;
+    REQUIRE(!depth_dev || planes_dev, DSI_ERR_INVALID, "depth output needs the plane depths");
+    if (int rc = set_device(g->ctx)) return rc;
+    return focus_collapse(g->ctx, g, method, half_patchsize, conf_dev, idx_dev, planes_dev, depth_dev);
+}
+
+int dsi_grid_collapse_focus(dsi_grid_t* g, int method, int half_patchsize, float* conf_host, uint8_t* idx_host)
+{
+    REQUIRE(g && conf_host && idx_host, DSI_ERR_INVALID, "null argument");
+    if (int rc = check_focus_args(g, method, half_patchsize)) return rc;
+    dsi_context* ctx = g->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    const size_t npix = (size_t)g->nx * g->ny;
+    float* conf;
+    uint8_t* idx;
+    if (int rc = collapse_scratch(ctx, npix, &conf, &idx)) return rc;
+    if (int rc = focus_collapse(ctx, g, method, half_patchsize, conf, idx, nullptr, nullptr)) return rc;
+    return collapse_download(ctx, npix, conf, idx, conf_host, idx_host);
+}
+
+int dsi_grid_collapse_min_z(dsi_grid_t* g, float* val_host, uint8_t* idx_host)
+{
+    REQUIRE(g && val_host && idx_host, DSI_ERR_INVALID, "null argument");
+    REQUIRE(g->nz <= 256, DSI_ERR_INVALID, "arg-min indices are u8: dimZ must be <= 256 (got %d)", g->nz);
+    dsi_context* ctx = g->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    const size_t npix = (size_t)g->nx * g->ny;
+    float* val;
+    uint8_t* idx;
+    if (int rc = collapse_scratch(ctx, npix, &val, &idx)) return rc;
+    HIP_TRY(dsi::launch_collapse_min_z(ctx->stream, g->data, g->nx, g->ny, g->nz, val, idx));
+    return collapse_download(ctx, npix, val, idx, val_host, idx_host);
+}
+
+static int release_to(dsi_context* owner, dsi_context* reader);
+
+int dsi_grid_local_focus(dsi_grid_t* dst, const dsi_grid_t* src, int focus_method)
+{
+    if (int rc = check_pair(dst, src)) return rc;
+    dsi_context* ctx = dst->ctx;
+    if (dst != src) {  // src may live in another context of the device: read it after its stream's work, as the reference would
+        if (int rc = dsi_context_wait_for(ctx, src->ctx)) return rc;
+        HIP_TRY(dsi::launch_local_focus(ctx->stream, src->data, dst->data, dst->nx, dst->ny, dst->nz, focus_method));
+        return release_to(src->ctx, ctx);
+    }
+    // in place: every tile reads its neighbours' planes, so the new volume goes to scratch first
+    HIP_TRY(ctx->focus_volume.reserve(dst->n));
+    HIP_TRY(dsi::launch_local_focus(ctx->stream, src->data, ctx->focus_volume.p, dst->nx, dst->ny, dst->nz, focus_method));
+    HIP_TRY(hipMemcpyAsync(dst->data, ctx->focus_volume.p, dst->n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     return DSI_OK;
 }
 
@@ -1742,6 +1842,25 @@ int dsi_mapper_depth_map_of(dsi_mapper_t* m, dsi_grid_t* g)
     if (int rc = depth_buffers_acquire(m)) return rc;
     HIP_TRY(dsi::launch_collapse_max_z(m->ctx->stream, g->data, g->nx, g->ny, g->nz, m->conf.p, m->idx.p,
                                        m->planes_dev, m->depth.p));
+    if (int rc = release_to(g->ctx, m->ctx)) return rc;
+    return depth_buffers_ready(m);
+}
+
+int dsi_mapper_depth_map_of_focus(dsi_mapper_t* m, dsi_grid_t* g, int method)
+{
+    if (method < DSI_FOCUS_LOCAL_VAR || method > DSI_FOCUS_DOG) return dsi_mapper_depth_map_of(m, g);  // :366-367
+    REQUIRE(m && g, DSI_ERR_INVALID, "null argument");
+    REQUIRE(m->ctx->device == g->ctx->device, DSI_ERR_CONTEXT, "mapper and grid live on different devices");
+    REQUIRE(same_shape(m->grid, g), DSI_ERR_SHAPE, "grid shape differs from the mapper's DSI");
+    if (int rc = check_focus_args(g, method, 1)) return rc;  // collapseZSliceByGradMag's default half_patchsize
+    if (int rc = set_device(m->ctx)) return rc;
+    const size_t npix = (size_t)g->nx * g->ny;
+    HIP_TRY(m->conf.reserve(npix));
+    HIP_TRY(m->depth.reserve(npix));
+    HIP_TRY(m->idx.reserve(npix));
+    if (int rc = dsi_context_wait_for(m->ctx, g->ctx)) return rc;
+    if (int rc = depth_buffers_acquire(m)) return rc;
+    if (int rc = focus_collapse(m->ctx, g, method, 1, m->conf.p, m->idx.p, m->planes_dev, m->depth.p)) return rc;
     if (int rc = release_to(g->ctx, m->ctx)) return rc;
     return depth_buffers_ready(m);
 }

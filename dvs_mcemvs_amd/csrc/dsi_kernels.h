@@ -305,4 +305,17 @@ hipError_t launch_pc_radius_filter(hipStream_t s, const float4* pts, const uint3
 hipError_t launch_pc_compact(hipStream_t s, const float4* pts, const uint8_t* keep, uint32_t n_max, uint32_t* blk, uint32_t* tiles,
                              float4* out);
 
+
+// focus-based collapses (Grid3D::collapseZSliceBy*, cartesian3dgrid.cpp:192-414; DESIGN.md "Focus-based collapses"):
+// method 0 LocalVar, 1 LocalMeanSquare, 2 GradMag (half_patchsize 0..8), 3 LaplacianMag, 4 DoG.  keys: scratch of
+// focus_chunks(nx, ny, nz) * nx * ny words, fully written before it is read.  planes / depth as launch_collapse_max_z.
+int focus_chunks(int nx, int ny, int nz);
+hipError_t launch_focus_collapse(hipStream_t s, const float* dsi, int nx, int ny, int nz, int method, int half_patchsize,
+                                 unsigned long long* keys, float* conf, uint8_t* idx, const float* planes, float* depth);
+// Grid3D::computeLocalFocusInPlace (cartesian3dgrid.cpp:417-483) into dst (dst != src): focus_method 1 the local mean
+// square, any other value the local standard deviation
+hipError_t launch_local_focus(hipStream_t s, const float* src, float* dst, int nx, int ny, int nz, int focus_method);
+// Grid3D::collapseMinZSlice (cartesian3dgrid.cpp:139-161)
+hipError_t launch_collapse_min_z(hipStream_t s, const float* dsi, int nx, int ny, int nz, float* val, uint8_t* idx);
+
 }  // namespace dsi

@@ -6632,4 +6632,374 @@ hipError_t launch_pc_compact(hipStream_t s, const float4* pts, const uint8_t* ke
     return hipExtGetLastError();
 }
 
+// ---- focus-based collapses of a DSI (cartesian3dgrid.cpp:139-483; DESIGN.md "Focus-based collapses") ----
+//
+// Every z-slice of the volume is filtered by a 2-D separable stencil (Sobel, Laplacian, Gaussian) and a focus value
+// per pixel is formed; the collapses keep the first plane of strictly largest focus (conf starts at +0, so values
+// <= 0 and NaN are never taken), the local-focus transform writes the focus volume itself.  Arithmetic (the project's
+// definition, restated in tests/focus_reference.py): OpenCV's borderInterpolate per axis (REFLECT_101 for Sobel and
+// Laplacian, REFLECT for GaussianBlur), rows filtered first into fp32, then columns; a symmetric tap set is
+// s = S0*c0, then s = s + (S[-j] + S[j])*cj for j = 1..r; an antisymmetric one s = (S[1] - S[-1])*c1; zero taps are
+// skipped; fp32 per operation, no contraction.
+//
+// A workgroup of 256 threads owns a 64 x 16 tile of output pixels and a range of planes.  Per plane: the tile and its
+// halo (border-reflected source offsets computed once) go to LDS, a row pass writes the fp32 intermediates to LDS, a
+// column pass forms the focus in registers, where the running (conf, idx) of the thread's four pixels stay.  The
+// next plane's loads are issued before the current plane is filtered.  The plane range is split over workgroups when
+// the tiles alone would not fill the chip; each range leaves one arg-max key per pixel
+// ((conf bits << 32) | ~k: conf > 0 and not NaN, so larger bits = larger value, ties to the smaller k) and
+// k_focus_finish takes the largest key over the ranges -- the same pick as one strict-'>' walk in ascending k.
+namespace {
+
+constexpr int kFocusTX = 64, kFocusTY = 16, kFocusThreads = 256;
+
+// the five collapses of MapperEMVS::getDepthMapFromDSI's switch (mapper_emvs_stereo.cpp:348-364) and the two
+// computeLocalFocusInPlace transforms (cartesian3dgrid.cpp:417-483)
+enum FocusKind { FK_LOCAL_VAR = 0, FK_LOCAL_MS = 1, FK_GRAD_MAG = 2, FK_LAPLACIAN = 3, FK_DOG = 4, FK_LF_MS = 5, FK_LF_STD = 6 };
+
+// getGaussianKernel(5 | 7, sigma 0.5 | 0.8, CV_32F): the correctly rounded normalised taps
+constexpr float kG5_0 = __builtin_bit_cast(float, 0x3f495cb3u), kG5_1 = __builtin_bit_cast(float, 0x3dda02ddu),
+                           kG5_2 = __builtin_bit_cast(float, 0x398a575fu);
+constexpr float kG7_0 = __builtin_bit_cast(float, 0x3eff5285u), kG7_1 = __builtin_bit_cast(float, 0x3e69ca49u),
+                           kG7_2 = __builtin_bit_cast(float, 0x3cb37d42u), kG7_3 = __builtin_bit_cast(float, 0x39e71393u);
+
+// cv::borderInterpolate for BORDER_REFLECT (delta 0) and BORDER_REFLECT_101 (delta 1)
+__device__ __forceinline__ int focus_border(int p, int len, int delta)
+{
+    if ((unsigned)p < (unsigned)len) return p;
+    if (len == 1) return 0;
+    do {
+        if (p < 0) p = -p - 1 + delta;
+        else p = len - 1 - (p - len) - delta;
+    } while ((unsigned)p >= (unsigned)len);
+    return p;
+}
+
+template <int ST> __device__ __forceinline__ float gauss5(const float* p)
+{
+    float s = p[0] * kG5_0;
+    s = s + (p[-ST] + p[ST]) * kG5_1;
+    s = s + (p[-2 * ST] + p[2 * ST]) * kG5_2;
+    return s;
+}
+template <int ST> __device__ __forceinline__ float gauss5_sq(const float* p)  // gauss5 of the squared samples
+{
+    const float a = p[-2 * ST], b = p[-ST], c = p[0], d = p[ST], e = p[2 * ST];
+    float s = (c * c) * kG5_0;
+    s = s + (b * b + d * d) * kG5_1;
+    s = s + (a * a + e * e) * kG5_2;
+    return s;
+}
+template <int ST> __device__ __forceinline__ float gauss7(const float* p)
+{
+    float s = p[0] * kG7_0;
+    s = s + (p[-ST] + p[ST]) * kG7_1;
+    s = s + (p[-2 * ST] + p[2 * ST]) * kG7_2;
+    s = s + (p[-3 * ST] + p[3 * ST]) * kG7_3;
+    return s;
+}
+template <int ST> __device__ __forceinline__ float taps_121(const float* p) { return p[0] * 2.f + (p[-ST] + p[ST]) * 1.f; }
+template <int ST> __device__ __forceinline__ float taps_m101(const float* p) { return (p[ST] - p[-ST]) * 1.f; }
+template <int ST> __device__ __forceinline__ float taps_14641(const float* p)
+{
+    float s = p[0] * 6.f;
+    s = s + (p[-ST] + p[ST]) * 4.f;
+    s = s + (p[-2 * ST] + p[2 * ST]) * 1.f;
+    return s;
+}
+template <int ST> __device__ __forceinline__ float taps_10m201(const float* p) { return p[0] * -2.f + (p[-2 * ST] + p[2 * ST]) * 1.f; }
+
+template <int K> struct FocusTraits;  // R: halo of the source tile; TWO: two intermediates per pixel; DELTA: border
+template <> struct FocusTraits<FK_LOCAL_VAR> { static constexpr int R = 2, TWO = 1, DELTA = 0; };
+template <> struct FocusTraits<FK_LOCAL_MS> { static constexpr int R = 2, TWO = 0, DELTA = 0; };
+template <> struct FocusTraits<FK_GRAD_MAG> { static constexpr int R = 1, TWO = 1, DELTA = 1; };  // + half_patchsize
+template <> struct FocusTraits<FK_LAPLACIAN> { static constexpr int R = 2, TWO = 1, DELTA = 1; };
+template <> struct FocusTraits<FK_DOG> { static constexpr int R = 3, TWO = 1, DELTA = 0; };
+template <> struct FocusTraits<FK_LF_MS> { static constexpr int R = 2, TWO = 0, DELTA = 0; };
+template <> struct FocusTraits<FK_LF_STD> { static constexpr int R = 2, TWO = 1, DELTA = 0; };
+
+template <int K>
+__device__ __forceinline__ void focus_row(const float* p, float& r0, float& r1)
+{
+    if constexpr (K == FK_LOCAL_VAR || K == FK_LF_STD) { r0 = gauss5<1>(p); r1 = gauss5_sq<1>(p); }
+    else if constexpr (K == FK_LOCAL_MS || K == FK_LF_MS) { r0 = gauss5_sq<1>(p); r1 = 0.f; }
+    else if constexpr (K == FK_GRAD_MAG) { r0 = taps_m101<1>(p); r1 = taps_121<1>(p); }      // d/dx row, d/dy row
+    else if constexpr (K == FK_LAPLACIAN) { r0 = taps_10m201<1>(p); r1 = taps_14641<1>(p); }  // Dxx row, Dyy row
+    else { r0 = gauss5<1>(p); r1 = gauss7<1>(p); }                                          // DoG
+}
+
+// focus (for GradMag: the squared gradient magnitude g) from the column pass over the intermediates
+template <int K, int ST>
+__device__ __forceinline__ float focus_col(const float* q0, const float* q1)
+{
+    if constexpr (K == FK_LOCAL_VAR || K == FK_LF_STD) {
+        const float m = gauss5<ST>(q0), q = gauss5<ST>(q1);
+        float v = q - m * m;
+        v = v > 0.f ? v : 0.f;  // cv::threshold(THRESH_TOZERO, 0): NaN -> 0
+        if constexpr (K == FK_LF_STD) return sqrtf(v);
+        return fabsf(v);
+    } else if constexpr (K == FK_LOCAL_MS || K == FK_LF_MS) {
+        return gauss5<ST>(q0);
+    } else if constexpr (K == FK_GRAD_MAG) {
+        const float gx = taps_121<ST>(q0), gy = taps_m101<ST>(q1);
+        return gx * gx + gy * gy;
+    } else if constexpr (K == FK_LAPLACIAN) {
+        const float l = taps_14641<ST>(q0) + taps_10m201<ST>(q1);
+        return l * l;
+    } else {
+        return fabsf(gauss5<ST>(q0) - gauss7<ST>(q1));
+    }
+}
+
+// K: FocusKind; E: GradMag's half_patchsize (0 otherwise).  COLLAPSE: keys[chunk][npix] of the arg-max over the
+// workgroup's planes; otherwise out[k][npix] = focus (the local-focus volume).
+template <int K, int E, bool COLLAPSE>
+__global__ __launch_bounds__(kFocusThreads) void k_focus_tile(const float* __restrict__ src, int nx, int ny, int nz,
+                                                              float* __restrict__ out, unsigned long long* __restrict__ keys)
+{
+    constexpr int R = FocusTraits<K>::R + E, TWO = FocusTraits<K>::TWO, DELTA = FocusTraits<K>::DELTA;
+    constexpr int HI = kFocusTY + 2 * R, WI = kFocusTX + 2 * R;  // source tile
+    constexpr int WO = kFocusTX + 2 * E;                          // intermediates: HI x WO
+    constexpr int HG = kFocusTY + 2 * E;                          // GradMag: g over HG x WO
+    constexpr int NL = (HI * WI + kFocusThreads - 1) / kFocusThreads;
+    constexpr int PER = kFocusTX * kFocusTY / kFocusThreads;     // output pixels per thread (4)
+    static_assert(PER * kFocusThreads == kFocusTX * kFocusTY, "tile");
+    __shared__ float s_in[HI * WI];
+    __shared__ float s_r0[HI * WO];
+    __shared__ float s_r1[TWO ? HI * WO : 1];
+    __shared__ float s_g[E ? HG * WO : 1];
+
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * kFocusTX, y0 = blockIdx.y * kFocusTY;
+    const size_t npix = (size_t)nx * ny;
+    const int k0 = (int)((long long)blockIdx.z * nz / gridDim.z), k1 = (int)((long long)(blockIdx.z + 1) * nz / gridDim.z);
+
+    int off[NL];  // border-reflected offsets of the source tile within a plane (-1: no element)
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+        const int i = tid + j * kFocusThreads;
+        off[j] = -1;
+        if (i < HI * WI) {
+            const int yy = i / WI, xx = i - yy * WI;
+            off[j] = focus_border(y0 - R + yy, ny, DELTA) * nx + focus_border(x0 - R + xx, nx, DELTA);
+        }
+    }
+    float nxt[NL];
+#pragma unroll
+    for (int j = 0; j < NL; ++j) nxt[j] = off[j] >= 0 ? src[(size_t)k0 * npix + off[j]] : 0.f;
+#pragma unroll
+    for (int j = 0; j < NL; ++j)
+        if (off[j] >= 0) s_in[tid + j * kFocusThreads] = nxt[j];
+    __syncthreads();
+
+    float conf[PER];
+    int idx[PER];
+#pragma unroll
+    for (int t = 0; t < PER; ++t) {
+        conf[t] = 0.f;
+        idx[t] = 0;
+    }
+    const int lx = tid % kFocusTX, ly = tid / kFocusTX;  // pixel t of the thread: (x0 + lx, y0 + ly + 4 t)
+    for (int k = k0; k < k1; ++k) {
+        if (k + 1 < k1) {  // the next plane's loads in flight while this one is filtered
+#pragma unroll
+            for (int j = 0; j < NL; ++j)
+                if (off[j] >= 0) nxt[j] = src[(size_t)(k + 1) * npix + off[j]];
+        }
+        // row pass: intermediates of rows y0 - R .. y0 + TY + R, columns x0 - E .. x0 + TX + E
+        for (int i = tid; i < HI * WO; i += kFocusThreads) {
+            const int yy = i / WO, xo = i - yy * WO;
+            float r0, r1;
+            focus_row<K>(&s_in[yy * WI + xo + (R - E)], r0, r1);
+            s_r0[i] = r0;
+            if constexpr (TWO != 0) s_r1[i] = r1;
+        }
+        __syncthreads();
+        float f[PER];
+        if constexpr (E == 0) {  // (GradMag with half_patchsize 0: the mean of one g is g)
+#pragma unroll
+            for (int t = 0; t < PER; ++t) {
+                const int c = (ly + 4 * t + R) * WO + lx;
+                f[t] = focus_col<K, WO>(&s_r0[c], TWO ? &s_r1[c] : nullptr);
+            }
+        } else {
+            // GradMag: g over the tile + E on each side, then the (2E+1)^2 patch mean in double, row-major
+            for (int i = tid; i < HG * WO; i += kFocusThreads) {
+                const int yo = i / WO, xo = i - yo * WO;
+                const int c = (yo + (R - E)) * WO + xo;
+                s_g[i] = focus_col<K, WO>(&s_r0[c], &s_r1[c]);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int t = 0; t < PER; ++t) {
+                double sum = 0.0;
+                const float* g = &s_g[(ly + 4 * t) * WO + lx];
+#pragma unroll 1
+                for (int dy = 0; dy <= 2 * E; ++dy)
+#pragma unroll
+                    for (int dx = 0; dx <= 2 * E; ++dx) sum += (double)g[dy * WO + dx];
+                f[t] = (float)(sum * (1.0 / (double)((2 * E + 1) * (2 * E + 1))));
+            }
+        }
+        if constexpr (COLLAPSE) {
+#pragma unroll
+            for (int t = 0; t < PER; ++t) {
+                bool ok = true;
+                if constexpr (K == FK_GRAD_MAG) {  // cartesian3dgrid.cpp:225-226: only [h, n - h) in x and y
+                    const int x = x0 + lx, y = y0 + ly + 4 * t;
+                    ok = x >= E && x < nx - E && y >= E && y < ny - E;
+                }
+                if (ok && f[t] > conf[t]) {
+                    conf[t] = f[t];
+                    idx[t] = k;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < PER; ++t) {
+                const int x = x0 + lx, y = y0 + ly + 4 * t;
+                if (x < nx && y < ny) out[(size_t)k * npix + (size_t)y * nx + x] = f[t];
+            }
+        }
+        if (k + 1 < k1) {
+#pragma unroll
+            for (int j = 0; j < NL; ++j)
+                if (off[j] >= 0) s_in[tid + j * kFocusThreads] = nxt[j];
+        }
+        __syncthreads();
+    }
+    if constexpr (COLLAPSE) {
+#pragma unroll
+        for (int t = 0; t < PER; ++t) {
+            const int x = x0 + lx, y = y0 + ly + 4 * t;
+            if (x < nx && y < ny) {
+                const unsigned long long key =
+                    conf[t] > 0.f ? ((unsigned long long)__float_as_uint(conf[t]) << 32) | (0xffffffffu - (unsigned)idx[t]) : 0ull;
+                keys[(size_t)blockIdx.z * npix + (size_t)y * nx + x] = key;
+            }
+        }
+    }
+}
+
+// the largest key over the plane ranges; conf = +0, idx = 0 where no plane was taken; sqrtf for GradMag / LaplacianMag
+__global__ __launch_bounds__(256) void k_focus_finish(const unsigned long long* __restrict__ keys, int npix, int chunks,
+                                                      int take_sqrt, float* __restrict__ conf, uint8_t* __restrict__ idx,
+                                                      const float* __restrict__ planes, float* __restrict__ depth)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    unsigned long long best = 0;
+    for (int c = 0; c < chunks; ++c) {
+        const unsigned long long v = keys[(size_t)c * npix + p];
+        best = v > best ? v : best;
+    }
+    float v = __uint_as_float((unsigned)(best >> 32));
+    const int k = best ? (int)(0xffffffffu - (unsigned)best) : 0;
+    if (take_sqrt) v = sqrtf(v);
+    conf[p] = v;
+    idx[p] = (uint8_t)k;
+    if (depth) depth[p] = planes[k];
+}
+
+// Grid3D::collapseMinZSlice (cartesian3dgrid.cpp:139-161): std::min_element, the first minimum wins -- the mirror of
+// k_collapse_max_z
+__global__ __launch_bounds__(256) void k_collapse_min_z(const float* __restrict__ dsi, int npix, int nz,
+                                                        float* __restrict__ val, uint8_t* __restrict__ idx)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    const float* col = dsi + p;
+    float best = col[0];
+    int best_k = 0;
+    int k = 1;
+    for (; k + 8 <= nz; k += 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = col[(size_t)(k + u) * npix];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (v[u] < best) {
+                best = v[u];
+                best_k = k + u;
+            }
+    }
+    for (; k < nz; ++k) {
+        const float v = col[(size_t)k * npix];
+        if (v < best) {
+            best = v;
+            best_k = k;
+        }
+    }
+    val[p] = best;
+    idx[p] = (uint8_t)best_k;
+}
+
+template <int K, int E, bool COLLAPSE>
+hipError_t focus_launch(hipStream_t s, const float* src, int nx, int ny, int nz, int chunks, float* out,
+                        unsigned long long* keys)
+{
+    const dim3 grid((nx + kFocusTX - 1) / kFocusTX, (ny + kFocusTY - 1) / kFocusTY, chunks);
+    hipLaunchKernelGGL((k_focus_tile<K, E, COLLAPSE>), grid, dim3(kFocusThreads), 0, s, src, nx, ny, nz, out, keys);
+    return hipExtGetLastError();
+}
+
+}  // namespace
+
+int focus_chunks(int nx, int ny, int nz)
+{
+    // about four workgroups per CU of the 256, with at least 4 planes per range
+    const long long tiles = (long long)((nx + kFocusTX - 1) / kFocusTX) * ((ny + kFocusTY - 1) / kFocusTY);
+    long long c = (1024 + tiles - 1) / tiles;
+    c = std::min<long long>(c, std::max(1, nz / 4));
+    return (int)std::max<long long>(1, c);
+}
+
+hipError_t launch_focus_collapse(hipStream_t s, const float* dsi, int nx, int ny, int nz, int method, int half_patchsize,
+                                 unsigned long long* keys, float* conf, uint8_t* idx, const float* planes, float* depth)
+{
+    const int chunks = focus_chunks(nx, ny, nz);
+    hipError_t e = hipErrorInvalidValue;
+    switch (method) {
+    case FK_LOCAL_VAR: e = focus_launch<FK_LOCAL_VAR, 0, true>(s, dsi, nx, ny, nz, chunks, nullptr, keys); break;
+    case FK_LOCAL_MS: e = focus_launch<FK_LOCAL_MS, 0, true>(s, dsi, nx, ny, nz, chunks, nullptr, keys); break;
+    case FK_GRAD_MAG:
+        switch (half_patchsize) {
+        case 0: e = focus_launch<FK_GRAD_MAG, 0, true>(s, dsi, nx, ny, nz, chunks, nullptr, keys); break;
+        case 1: e = focus_launch<FK_GRAD_MAG, 1, true>(s, dsi, nx, ny, nz, chunks, nullptr, keys); break;
+        case 2: e = focus_launch<FK_GRAD_MAG, 2, true>(s, dsi, nx, ny, nz, chunks, nullptr, keys); break;
+        case 3: e = focus_launch<FK_GRAD_MAG, 3, true>(s, dsi, nx, ny, nz, chunks, nullptr, keys); break;
+        case 4: e = focus_launch<FK_GRAD_MAG, 4, true>(s, dsi, nx, ny, nz, chunks, nullptr, keys); break;
+        case 5: e = focus_launch<FK_GRAD_MAG, 5, true>(s, dsi, nx, ny, nz, chunks, nullptr, keys); break;
+        case 6: e = focus_launch<FK_GRAD_MAG, 6, true>(s, dsi, nx, ny, nz, chunks, nullptr, keys); break;
+        case 7: e = focus_launch<FK_GRAD_MAG, 7, true>(s, dsi, nx, ny, nz, chunks, nullptr, keys); break;
+        case 8: e = focus_launch<FK_GRAD_MAG, 8, true>(s, dsi, nx, ny, nz, chunks, nullptr, keys); break;
+        default: return hipErrorInvalidValue;
+        }
+        break;
+    case FK_LAPLACIAN: e = focus_launch<FK_LAPLACIAN, 0, true>(s, dsi, nx, ny, nz, chunks, nullptr, keys); break;
+    case FK_DOG: e = focus_launch<FK_DOG, 0, true>(s, dsi, nx, ny, nz, chunks, nullptr, keys); break;
+    default: return hipErrorInvalidValue;
+    }
+    if (e != hipSuccess) return e;
+    const int npix = nx * ny;
+    const int take_sqrt = method == FK_GRAD_MAG || method == FK_LAPLACIAN;  // cartesian3dgrid.cpp:243, :283
+    hipLaunchKernelGGL(k_focus_finish, dim3((npix + 255) / 256), dim3(256), 0, s, keys, npix, chunks, take_sqrt, conf, idx,
+                       planes, depth);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_local_focus(hipStream_t s, const float* src, float* dst, int nx, int ny, int nz, int focus_method)
+{
+    const int chunks = focus_chunks(nx, ny, nz);
+    if (focus_method == 1) return focus_launch<FK_LF_MS, 0, false>(s, src, nx, ny, nz, chunks, dst, nullptr);
+    return focus_launch<FK_LF_STD, 0, false>(s, src, nx, ny, nz, chunks, dst, nullptr);  // any other value: :423-425
+}
+
+hipError_t launch_collapse_min_z(hipStream_t s, const float* dsi, int nx, int ny, int nz, float* val, uint8_t* idx)
+{
+    const int npix = nx * ny;
+    hipLaunchKernelGGL(k_collapse_min_z, dim3((npix + 255) / 256), dim3(256), 0, s, dsi, npix, nz, val, idx);
+    return hipExtGetLastError();
+}
+
 }  // namespace dsi

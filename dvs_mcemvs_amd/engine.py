@@ -24,6 +24,7 @@ FUSE_MIN, FUSE_HM, FUSE_GM, FUSE_AM, FUSE_RMS, FUSE_MAX = 1, 2, 3, 4, 5, 6
 ACC_SUM, ACC_INV_SUM, ACC_LOG_SUM, ACC_SQ_SUM, ACC_MIN, ACC_MAX, ACC_GM_TREE = 0, 1, 2, 3, 4, 5, 6
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2
 VOTE_AUTO, VOTE_GLOBAL_ATOMIC, VOTE_LDS_BANDS, VOTE_FUSED_ARGMAX = 0, 1, 2, 3
+FOCUS_LOCAL_VAR, FOCUS_LOCAL_MS, FOCUS_GRAD_MAG, FOCUS_LAPLACIAN, FOCUS_DOG = 0, 1, 2, 3, 4
 
 (OK, ERR_INVALID, ERR_TOO_FEW_EVENTS, ERR_HIP, ERR_SHAPE, ERR_BAD_OP, ERR_NO_DEVICE,
  ERR_CONTEXT, ERR_COMM) = range(9)
@@ -151,6 +152,10 @@ def load_library():
         "dsi_grid_collapse_max_z": (C.c_int, [vp, f32p, u8p]),
         "dsi_grid_collapse_max_z_dev": (C.c_int, [vp, vp, vp, vp, vp]),
         "dsi_grid_mean_square": (C.c_int, [vp, f64p]),
+        "dsi_grid_collapse_focus": (C.c_int, [vp, C.c_int, C.c_int, f32p, u8p]),
+        "dsi_grid_collapse_focus_dev": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+        "dsi_grid_collapse_min_z": (C.c_int, [vp, f32p, u8p]),
+        "dsi_grid_local_focus": (C.c_int, [vp, vp, C.c_int]),
         "dsi_mapper_create": (C.c_int, [vp, C.POINTER(_MapperConfig), C.POINTER(vp)]),
         "dsi_mapper_destroy": (C.c_int, [vp]),
         "dsi_mapper_grid": (vp, [vp]),
@@ -182,6 +187,7 @@ def load_library():
         "dsi_pose_at": (C.c_int, [f64p, f64p, C.c_size_t, C.c_double, f64p]),
         "dsi_mapper_depth_map": (C.c_int, [vp, f32p, f32p, u8p]),
         "dsi_mapper_depth_map_of": (C.c_int, [vp, vp]),
+        "dsi_mapper_depth_map_of_focus": (C.c_int, [vp, vp, C.c_int]),
         "dsi_mapper_fetch_depth_map": (C.c_int, [vp, f32p, f32p, u8p]),
         "dsi_mapper_depth_map_of_fusion": (C.c_int, [vp, vp, vp, C.c_int]),
         "dsi_mapper_depth_map_of_fusion_n": (C.c_int, [vp, C.POINTER(vp), C.c_int, C.c_int]),
@@ -667,6 +673,47 @@ class Grid3D:
                                                       _ptr(idx, C.c_uint8)))
         return conf, idx
 
+    # -- focus-based collapses, cartesian3dgrid.cpp:139-483 (arithmetic: DESIGN.md "Focus-based collapses") --------
+    def _collapse_focus(self, method, half_patchsize=1):
+        nz, ny, nx = self.shape
+        conf = np.empty((ny, nx), np.float32)
+        idx = np.empty((ny, nx), np.uint8)
+        _check(load_library().dsi_grid_collapse_focus(self._h, int(method), int(half_patchsize), _ptr(conf, C.c_float),
+                                                      _ptr(idx, C.c_uint8)))
+        return conf, idx
+
+    def collapseZSliceByLocalVar(self):
+        """Returns (confidence float32 [dimY][dimX], depth_cell_indices uint8 [dimY][dimX])."""
+        return self._collapse_focus(FOCUS_LOCAL_VAR)
+
+    def collapseZSliceByLocalMeanSquare(self):
+        return self._collapse_focus(FOCUS_LOCAL_MS)
+
+    def collapseZSliceByGradMag(self, half_patchsize=1):
+        return self._collapse_focus(FOCUS_GRAD_MAG, half_patchsize)
+
+    def collapseZSliceByLaplacianMag(self):
+        return self._collapse_focus(FOCUS_LAPLACIAN)
+
+    def collapseZSliceByDoG(self):
+        return self._collapse_focus(FOCUS_DOG)
+
+    def collapseMinZSlice(self):
+        """Returns (min_val float32 [dimY][dimX], min_pos uint8 [dimY][dimX]): the first minimum wins."""
+        nz, ny, nx = self.shape
+        val = np.empty((ny, nx), np.float32)
+        idx = np.empty((ny, nx), np.uint8)
+        _check(load_library().dsi_grid_collapse_min_z(self._h, _ptr(val, C.c_float), _ptr(idx, C.c_uint8)))
+        return val, idx
+
+    def computeLocalFocusInPlace(self, focus_method):
+        """focus_method 1: Gaussian local mean square; any other value: local standard deviation."""
+        _check(load_library().dsi_grid_local_focus(self._h, self._h, int(focus_method)))
+
+    def setToLocalFocusOf(self, grid, focus_method):
+        """self = grid with computeLocalFocusInPlace(focus_method) applied, in one pass (grid is unchanged)."""
+        _check(load_library().dsi_grid_local_focus(self._h, grid._h, int(focus_method)))
+
     def computeMeanSquare(self):
         out = C.c_double()
         _check(load_library().dsi_grid_mean_square(self._h, C.byref(out)))
@@ -911,13 +958,20 @@ class MapperEMVS:
         _check(load_library().dsi_mapper_fill_voxel_grid(self._h, _ptr(xy, C.c_float),
                                                          _ptr(cc, C.c_float), cc.shape[0]))
 
-    def getDepthMapFromDSI(self, grid=None, options_depth_map=None):
+    def getDepthMapFromDSI(self, grid=None, options_depth_map=None, method=-1):
         """mapper_emvs_stereo.cpp:339-437.  With options_depth_map (OptionsDepthMap): the full
         extraction -- arg-max, confidence normalisation, Gaussian adaptive threshold, masked
         median, border removal -- returning (depth_map, confidence_map, mask) like the
         reference's signature (dense inpainted map excluded).  Without: the raw arg-max
-        (:368) + convertDepthIndicesToValues (:302-313), returning (depth, confidence, indices)."""
+        (:368) + convertDepthIndicesToValues (:302-313), returning (depth, confidence, indices).
+        method 0..4 (FOCUS_*) replaces the arg-max by that focus-based collapse (:348-364; GradMag with
+        half_patchsize 1); any other value is the arg-max."""
         L = load_library()
+        if 0 <= method <= 4:
+            _check(L.dsi_mapper_depth_map_of_focus(self._h, (grid or self.dsi_)._h, int(method)))
+            if options_depth_map is None:
+                return self.fetchDepthMap()
+            return self.filterDepthMap(options_depth_map)
         if options_depth_map is not None:
             o = options_depth_map
             opts = _DepthMapOptions(o.adaptive_threshold_kernel_size_, o.adaptive_threshold_c_,

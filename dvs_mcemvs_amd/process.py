@@ -286,6 +286,23 @@ def exact_depth_map_process_2(ctx, cams, dsi_shape, events, trajectories, num_su
     return info
 
 
+def fuseDSIs_HarmonicMeanOfLocalFocus(mapper0, mapper1, cam0, cam1, dsi_shape, focus_method, mapper_focus_fused):
+    """utils.cpp:155-181: the harmonic mean of the two DSIs' local focus volumes (computeLocalFocusInPlace;
+    focus_method 0 the local standard deviation, 1 the local mean square) into mapper_focus_fused.dsi_.  The
+    reference builds two scratch mappers from cam0 / cam1 / dsi_shape; here two scratch grids of the fused
+    mapper's context hold the focus volumes, and mapper0 / mapper1 are left unchanged."""
+    shape = mapper0.dsi_.getDimensions()
+    ctx = mapper_focus_fused.ctx
+    focus = [E.Grid3D(ctx, *shape), E.Grid3D(ctx, *shape)]
+    try:
+        focus[0].setToLocalFocusOf(mapper0.dsi_, focus_method)   # resetGrid; addTwoGrids; computeLocalFocusInPlace
+        focus[1].setToLocalFocusOf(mapper1.dsi_, focus_method)
+        mapper_focus_fused.dsi_.setToFusionOf(focus[0], focus[1], E.FUSE_HM)
+    finally:
+        for g in focus:
+            g.close()   # (waits for the context's stream)
+
+
 def process_5(*args, **kw):
     """process5.cpp:28-260: process_2 with the right camera's sub-intervals circularly shifted."""
     kw["shuffle_right"] = True

@@ -192,6 +192,32 @@ DSI_API int dsi_grid_collapse_max_z_dev(dsi_grid_t *g, float *conf_dev, uint8_t 
 /* Grid3D::computeMeanSquare (cartesian3dgrid.cpp:164-174), accumulated in double */
 DSI_API int dsi_grid_mean_square(dsi_grid_t *g, double *out);
 
+/* focus measures of getDepthMapFromDSI's `method` switch (mapper_emvs_stereo.cpp:348-364) */
+typedef enum {
+    DSI_FOCUS_LOCAL_VAR = 0,   /* Grid3D::collapseZSliceByLocalVar         cartesian3dgrid.cpp:327-365 */
+    DSI_FOCUS_LOCAL_MS = 1,    /* Grid3D::collapseZSliceByLocalMeanSquare  cartesian3dgrid.cpp:368-402 */
+    DSI_FOCUS_GRAD_MAG = 2,    /* Grid3D::collapseZSliceByGradMag          cartesian3dgrid.cpp:192-244 */
+    DSI_FOCUS_LAPLACIAN = 3,   /* Grid3D::collapseZSliceByLaplacianMag     cartesian3dgrid.cpp:247-284 */
+    DSI_FOCUS_DOG = 4          /* Grid3D::collapseZSliceByDoG              cartesian3dgrid.cpp:287-324 */
+} dsi_focus_method_t;
+/* Focus-based collapse: per z-slice a 2-D focus measure, then the first plane of strictly largest focus per pixel
+ * (conf starts at +0 and idx at 0: values <= 0 and NaN are never taken); GradMag and LaplacianMag return the square
+ * root of the selected focus.  Arithmetic: DESIGN.md "Focus-based collapses".  half_patchsize (0..8, else
+ * DSI_ERR_INVALID) is read by GradMag only (the reference's default is 1).  method outside 0..4: DSI_ERR_BAD_OP;
+ * dimZ > 256: DSI_ERR_INVALID (u8 indices).  Host outputs conf[ny*nx] f32, idx[ny*nx] u8; synchronises. */
+DSI_API int dsi_grid_collapse_focus(dsi_grid_t *g, int method, int half_patchsize, float *conf_host, uint8_t *idx_host);
+/* same, device outputs, asynchronous; planes_dev / depth_dev as dsi_grid_collapse_max_z_dev */
+DSI_API int dsi_grid_collapse_focus_dev(dsi_grid_t *g, int method, int half_patchsize, float *conf_dev, uint8_t *idx_dev,
+                                        const float *planes_dev, float *depth_dev);
+/* Grid3D::collapseMinZSlice (cartesian3dgrid.cpp:139-161): val[ny*nx] f32, idx[ny*nx] u8, first minimum wins
+ * (std::min_element).  dimZ > 256: DSI_ERR_INVALID.  Host outputs; synchronises. */
+DSI_API int dsi_grid_collapse_min_z(dsi_grid_t *g, float *val_host, uint8_t *idx_host);
+/* Grid3D::computeLocalFocusInPlace (cartesian3dgrid.cpp:417-483): dst = per z-slice local focus of src --
+ * focus_method 1 the Gaussian (sigma 0.5) local mean square, any other value the local standard deviation.
+ * dst == src is the reference's in-place call: the result is written to a scratch volume of dst's context and copied
+ * back, so no reader of the grid sees it half written.  Same shape, same device.  Asynchronous. */
+DSI_API int dsi_grid_local_focus(dsi_grid_t *dst, const dsi_grid_t *src, int focus_method);
+
 /* ---------------------------------------------------------- multi-GPU (RCCL) */
 /* The temporal fusion of process_2 (process2.cpp:211-242: one accumulate per sub-interval, one
  * finalize) and of the sliding window (main.cpp:177) shards by time slice: every GPU accumulates
@@ -368,6 +394,11 @@ DSI_API int dsi_mapper_depth_map(dsi_mapper_t *m, float *depth_host, float *conf
 /* the same for any grid of the mapper's shape (e.g. a fused DSI); asynchronous variant
  * keeps results in the mapper's device buffers until dsi_mapper_fetch_depth_map */
 DSI_API int dsi_mapper_depth_map_of(dsi_mapper_t *m, dsi_grid_t *g);
+/* getDepthMapFromDSI's switch (mapper_emvs_stereo.cpp:348-369): method 0..4 (dsi_focus_method_t; GradMag with
+ * half_patchsize 1, the reference's default) is the focus-based collapse of g + convertDepthIndicesToValues, any
+ * other value exactly dsi_mapper_depth_map_of(m, g).  The raw map stays in the mapper like dsi_mapper_depth_map_of's
+ * (dsi_mapper_filter_depth_map / dsi_mapper_fetch_depth_map apply unchanged). */
+DSI_API int dsi_mapper_depth_map_of_focus(dsi_mapper_t *m, dsi_grid_t *g, int method);
 /* depth map of op(a, b) (op = dsi_fuse_op_t) WITHOUT materialising the fused DSI: exactly what
  * "fused.resetGrid(); fused.addTwoGrids(a); fused.<op>TwoGrids(b)" (process1.cpp:126-158) followed by
  * dsi_mapper_depth_map_of(m, fused) gives, bit for bit, in one pass over a and b.  For streams of

@@ -559,6 +559,48 @@ public:
         uint8_t* pos = dsi::image_create<uint8_t>(*max_pos, ny, nx);
         dsi::check(dsi_grid_collapse_max_z(h_, val, pos));
     }
+    // The focus-based collapses (cartesian3dgrid.h:208-216, cartesian3dgrid.cpp:139-414) with the reference's names and
+    // arities; outputs as collapseMaxZSlice's.  Arithmetic: DESIGN.md "Focus-based collapses".
+    template <typename ValImg, typename PosImg>
+    void collapseMinZSlice(ValImg* min_val, PosImg* min_pos) const
+    {
+        int nx, ny, nz;
+        getDimensions(&nx, &ny, &nz);
+        float* val = dsi::image_create<float>(*min_val, ny, nx);
+        uint8_t* pos = dsi::image_create<uint8_t>(*min_pos, ny, nx);
+        dsi::check(dsi_grid_collapse_min_z(h_, val, pos));
+    }
+    template <typename ValImg, typename PosImg>
+    void collapseZSliceByGradMag(ValImg* confidence, PosImg* depth_cell_indices, int half_patchsize = 1)
+    {
+        collapseFocus(DSI_FOCUS_GRAD_MAG, half_patchsize, confidence, depth_cell_indices);
+    }
+    template <typename ValImg, typename PosImg>
+    void collapseZSliceByLaplacianMag(ValImg* confidence, PosImg* depth_cell_indices)
+    {
+        collapseFocus(DSI_FOCUS_LAPLACIAN, 1, confidence, depth_cell_indices);
+    }
+    template <typename ValImg, typename PosImg>
+    void collapseZSliceByDoG(ValImg* confidence, PosImg* depth_cell_indices)
+    {
+        collapseFocus(DSI_FOCUS_DOG, 1, confidence, depth_cell_indices);
+    }
+    template <typename ValImg, typename PosImg>
+    void collapseZSliceByLocalVar(ValImg* confidence, PosImg* depth_cell_indices)
+    {
+        collapseFocus(DSI_FOCUS_LOCAL_VAR, 1, confidence, depth_cell_indices);
+    }
+    template <typename ValImg, typename PosImg>
+    void collapseZSliceByLocalMeanSquare(ValImg* confidence, PosImg* depth_cell_indices)
+    {
+        collapseFocus(DSI_FOCUS_LOCAL_MS, 1, confidence, depth_cell_indices);
+    }
+    // cartesian3dgrid.cpp:417-429: focus_method 1 the local mean square, any other value the local standard deviation
+    void computeLocalFocusInPlace(int focus_method) { dsi::check(dsi_grid_local_focus(h_, h_, focus_method)); }
+    // this = grid2 after computeLocalFocusInPlace(focus_method), in one pass (not in the reference)
+    void setToLocalFocusOf(const Grid3D& grid2, int focus_method) { dsi::check(dsi_grid_local_focus(h_, grid2.h_, focus_method)); }
+    // this = op(a, b) in one pass: resetGrid(); addTwoGrids(a); <op>TwoGrids(b) (not in the reference)
+    void setToFusionOf(const Grid3D& a, const Grid3D& b, int op) { dsi::check(dsi_grid_fuse2_into(h_, a.h_, b.h_, op)); }
     // cartesian3dgrid.cpp:164-174
     double computeMeanSquare() const
     {
@@ -602,6 +644,15 @@ public:
     }
 
 private:
+    template <typename ValImg, typename PosImg>
+    void collapseFocus(int method, int half_patchsize, ValImg* confidence, PosImg* depth_cell_indices)
+    {
+        int nx, ny, nz;
+        getDimensions(&nx, &ny, &nz);
+        float* val = dsi::image_create<float>(*confidence, ny, nx);
+        uint8_t* pos = dsi::image_create<uint8_t>(*depth_cell_indices, ny, nx);
+        dsi::check(dsi_grid_collapse_focus(h_, method, half_patchsize, val, pos));
+    }
     dsi_grid_t* h_ = nullptr;
     bool owned_ = false;
 };
@@ -733,8 +784,9 @@ public:
     // removeMaskBoundary (:426-427), index -> depth of the filtered indices (:435).  Outputs as the reference leaves
     // them: depth_map CV_32F, confidence_map CV_32F (element (0,0) overwritten), mask CV_8U in {0, 1}.
     // method: the reference's switch (:348-368) takes 0..4 to the focus-based collapses (collapseZSliceByLocalVar ...,
-    // never selected by any caller: every call site passes the default) and everything else to collapseMaxZSlice;
-    // 0..4 are refused with dsi::Error (DSI_ERR_BAD_OP) -- SURVEY 2 marks them out of scope -- anything else is the arg-max.
+    // never selected by any caller: every call site passes the default) and everything else to collapseMaxZSlice.
+    // These overloads refuse 0..4 with dsi::Error (DSI_ERR_BAD_OP), as they always have; anything else is the arg-max.
+    // The focus-based depth map with the same filters is getDepthMapFromDSIByFocus below.
     // depth_map_dense: see dsi::inpaint_depth_cell_indices above -- filled when the caller supplies OpenCV's inpainting,
     // otherwise left empty.
     template <typename DepthImg, typename ConfImg, typename MaskImg>
@@ -750,6 +802,17 @@ public:
     {
         MaskImg idx_filtered;
         extract(nullptr, depth_map, confidence_map, mask, options_depth_map, &idx_filtered, &depth_map_dense, method);
+    }
+    // getDepthMapFromDSI(depth_map, confidence_map, mask, options, method) for method 0..4 (mapper_emvs_stereo.cpp:350-364):
+    // the focus-based collapse (dsi_mapper_depth_map_of_focus; GradMag with half_patchsize 1) of the mapper's own dsi_, or
+    // of *grid, then the same filters as the overloads above.  Any other method is collapseMaxZSlice, as there.
+    template <typename DepthImg, typename ConfImg, typename MaskImg>
+    void getDepthMapFromDSIByFocus(DepthImg& depth_map, ConfImg& confidence_map, MaskImg& mask,
+                                   const OptionsDepthMap& options_depth_map, int method, const Grid3D* grid = nullptr)
+    {
+        const bool focus = method >= DSI_FOCUS_LOCAL_VAR && method <= DSI_FOCUS_DOG;
+        extract(grid, depth_map, confidence_map, mask, options_depth_map, (MaskImg*)nullptr, (DepthImg*)nullptr,
+                focus ? method : -1, focus);
     }
     // the same for a DSI other than the mapper's own (not in the reference, which copies the DSI into a mapper first)
     template <typename DepthImg, typename ConfImg, typename MaskImg>
@@ -845,13 +908,15 @@ private:
     }
     template <typename DepthImg, typename ConfImg, typename MaskImg, typename DenseImg>
     void extract(const Grid3D* grid, DepthImg& depth_map, ConfImg& confidence_map, MaskImg& mask,
-                 const OptionsDepthMap& options_depth_map, MaskImg* idx_filtered, DenseImg* depth_map_dense, int method)
+                 const OptionsDepthMap& options_depth_map, MaskImg* idx_filtered, DenseImg* depth_map_dense, int method,
+                 bool focus = false)
     {
-        if (method >= 0 && method <= 4)
+        if (!focus && method >= 0 && method <= 4)
             throw dsi::Error(DSI_ERR_BAD_OP, "getDepthMapFromDSI: method " + std::to_string(method) +
                                                  " is one of the focus-based collapses (collapseZSliceByLocalVar / "
                                                  "LocalMeanSquare / GradMag / LaplacianMag / DoG, mapper_emvs_stereo.cpp:350-364), "
-                                                 "which this engine does not provide; pass the default (-1): collapseMaxZSlice");
+                                                 "which this overload refuses; call getDepthMapFromDSIByFocus for them, or pass "
+                                                 "the default (-1): collapseMaxZSlice");
         int nx, ny, nz;
         dsi_.getDimensions(&nx, &ny, &nz);
         float* depth = dsi::image_create<float>(depth_map, ny, nx);
@@ -859,7 +924,12 @@ private:
         uint8_t* mk = dsi::image_create<uint8_t>(mask, ny, nx);
         uint8_t* filtered = idx_filtered ? dsi::image_create<uint8_t>(*idx_filtered, ny, nx) : nullptr;
         const dsi_depthmap_options_t o = options_of(options_depth_map);
-        dsi::check(dsi_mapper_get_depth_map_from_dsi(h_, grid ? grid->handle() : nullptr, &o, depth, conf, mk, filtered));
+        if (focus) {  // :350-364
+            dsi::check(dsi_mapper_depth_map_of_focus(h_, grid ? grid->handle() : dsi_.handle(), method));
+            dsi::check(dsi_mapper_filter_depth_map(h_, &o, depth, conf, mk, filtered));
+        } else {
+            dsi::check(dsi_mapper_get_depth_map_from_dsi(h_, grid ? grid->handle() : nullptr, &o, depth, conf, mk, filtered));
+        }
         if (!depth_map_dense) return;
         // mapper_emvs_stereo.cpp:430-436
         MaskImg inpaint_mask, inpainted;

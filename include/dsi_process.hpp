@@ -57,6 +57,33 @@ inline void fuseTwoGrids(Grid3D& dst, const Grid3D& g, int method, const char* w
 
 }  // namespace dsi
 
+// utils.cpp:155-181 (utils.hpp:54-60): the harmonic mean of the two DSIs' local focus volumes
+// (Grid3D::computeLocalFocusInPlace: focus_method 0 the local standard deviation, 1 the local mean square) into
+// mapper_focus_fused.dsi_, with the reference's seven arguments.  The reference builds two scratch mappers from cam0 /
+// cam1 / dsi_shape; here two scratch grids of mapper_focus_fused's context hold the focus volumes (each written in one
+// pass from its DSI: copy + computeLocalFocusInPlace), and the fusion is resetGrid(); addTwoGrids(focus0);
+// harmonicMeanTwoGrids(focus1) in one pass.  mapper0 and mapper1 are left unchanged.
+template <typename CamT>
+inline void fuseDSIs_HarmonicMeanOfLocalFocus(const EMVS::MapperEMVS& mapper0, const EMVS::MapperEMVS& mapper1,
+                                              const CamT& cam0, const CamT& cam1, const EMVS::ShapeDSI& dsi_shape,
+                                              const int focus_method, EMVS::MapperEMVS& mapper_focus_fused)
+{
+    (void)cam0;
+    (void)cam1;
+    (void)dsi_shape;
+    struct Scratch {  // grids owned by this call
+        dsi_grid_t* h = nullptr;
+        ~Scratch() { if (h) dsi_grid_destroy(h); }
+    } focus0, focus1;
+    int nx, ny, nz;
+    mapper0.dsi_.getDimensions(&nx, &ny, &nz);
+    dsi::check(dsi_grid_create(mapper_focus_fused.context(), nx, ny, nz, &focus0.h));
+    dsi::check(dsi_grid_create(mapper_focus_fused.context(), nx, ny, nz, &focus1.h));
+    dsi::check(dsi_grid_local_focus(focus0.h, mapper0.dsi_.handle(), focus_method));
+    dsi::check(dsi_grid_local_focus(focus1.h, mapper1.dsi_.handle(), focus_method));
+    dsi::check(dsi_grid_fuse2_into(mapper_focus_fused.dsi_.handle(), focus0.h, focus1.h, DSI_FUSE_HM));
+}
+
 // Alg. 1.  A camera with no events (events2.empty(), the stereo case) is skipped like
 // process1.cpp:105.  rv_pos: position of the reference view along the baseline (process1.cpp:58-66;
 // a flag in the reference).  Returns T_rv_w; the fused DSI is mapper_fused.dsi_.
