@@ -45,6 +45,7 @@ from .engine import (  # noqa: F401
     PinnedArray,
     ShapeDSI,
     acc_reduce_op,
+    alg2_subintervals,
     allreduce_all,
     depth_map_reduce_scattered_all,
     depth_map_sharded_all,
@@ -61,7 +62,7 @@ __all__ = [
     "Comm", "allreduce_all", "depth_map_sharded_all", "depth_map_reduce_scattered_all", "Context", "Grid3D", "MapperEMVS", "ShapeDSI", "OptionsDepthMap", "OptionsPointCloud", "EventBatch", "PinnedArray", "DsiError", "device_count",
     "library_path", "load_library", "packetize", "packetize_strided", "pose_at", "radius_outlier_removal", "PACKET_SIZE",
     "FUSE_MIN", "FUSE_HM", "FUSE_GM", "FUSE_AM", "FUSE_RMS", "FUSE_MAX", "ACC_SUM", "ACC_INV_SUM", "ACC_LOG_SUM", "ACC_SQ_SUM", "ACC_MIN", "ACC_MAX", "ACC_GM_TREE",
-    "REDUCE_SUM", "REDUCE_MIN", "REDUCE_MAX", "acc_reduce_op",
+    "REDUCE_SUM", "REDUCE_MIN", "REDUCE_MAX", "acc_reduce_op", "alg2_subintervals",
     "FOCUS_LOCAL_VAR", "FOCUS_LOCAL_MS", "FOCUS_GRAD_MAG", "FOCUS_LAPLACIAN", "FOCUS_DOG",
     "VOTE_AUTO", "VOTE_GLOBAL_ATOMIC", "VOTE_LDS_BANDS", "VOTE_FUSED_ARGMAX",
 ]

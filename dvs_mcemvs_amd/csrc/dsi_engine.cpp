@@ -249,7 +249,9 @@ void pool_give(dsi_context* ctx, const dsi_context::PoolBlock& blk)
     if (!blk.p) return;
     (void)hipEventRecord(blk.freed, ctx->stream);  // everything that read the block was queued before
     ctx->batch_pool.push_back(blk);
-    if (ctx->batch_pool.size() > 8) {  // keep a handful; drop the oldest
+    // keep a handful -- two windows of Alg. 2's up to 2 x 8 sub-interval batches (dsi_mapper_depth_map_of_events_alg2), so
+    // that a stream's batches are reused instead of freed (a free waits for the stream) -- and drop the oldest
+    if (ctx->batch_pool.size() > 4 * (size_t)dsi::kAlg2MaxSub) {
         (void)hipStreamSynchronize(ctx->stream);
         (void)hipFree(ctx->batch_pool.front().p);
         (void)hipEventDestroy(ctx->batch_pool.front().freed);
@@ -371,6 +373,25 @@ struct dsi_mapper {
     // dsi_mapper_get_pointcloud); cleared by every call that writes a new depth map (depth_buffers_ready)
     bool filtered_valid = false;
     PcBuffers pc;
+    // dsi_mapper_depth_map_of_events_alg2, on its time_camera output mapper: the banded-vote tables of each of the 2 N
+    // event batches of a window (what a camera mapper holds for one batch in the fused path)
+    struct BatchTables {
+        DevBuf<float> centers;
+        DevBuf<dsi::EvRec> sxy;
+        DevBuf<uint32_t> nvalid, cuts;
+        DevBuf<uint16_t> rowstart;
+        DevBuf<dsi::PlaneCoef> coef;
+        void release()
+        {
+            centers.release();
+            sxy.release();
+            nvalid.release();
+            cuts.release();
+            rowstart.release();
+            coef.release();
+        }
+    };
+    std::vector<BatchTables> alg2_tables;
     bool fused_keys_dirty = false;  // the fused kernel may have written keys that no unpack cleared
     // The depth map leaves the device on the context's COPY stream, so that fetching window w's map
     // does not queue behind window w+1's kernels on the compute stream: "ready" (compute stream, after
@@ -558,22 +579,26 @@ bool plan_bands(const dsi_mapper* m, size_t n_packets, dsi::BandPlan* bp)
 // Band decomposition of the fused vote -> camera fusion -> arg-max kernel (k_vote_fuse_argmax): one
 // 1024-thread workgroup per CU, the band as tall as the LDS (and the per-thread register arrays) allow,
 // a halo row on either side of the owned rows instead of a carry row, one chunk.
-bool plan_fused(const dsi_mapper* m, size_t n_packets_max, dsi::BandPlan* bp, int n_cameras = 2)
+// max_cells (k_vote_fuse_argmax_alg2): cells per 1024-thread workgroup the kernel of mapping m keeps in registers, 0 = the fused
+// kernel's own (dsi::fused_max_cells)
+bool plan_fused(const dsi_mapper* m, size_t n_packets_max, dsi::BandPlan* bp, int n_cameras = 2,
+                size_t (*max_cells)(int mapping) = nullptr)
 {
+    auto cells = [&](int mapping) { return max_cells ? max_cells(mapping) : dsi::fused_max_cells(mapping, n_cameras); };
     const dsi::Geom& g = m->geom;
     const size_t row_bytes = (size_t)g.nx * sizeof(unsigned long long);
     if (g.nx < 2 || g.ny < 2 || g.ny > 16000 || g.nz > 256) return false;
     int packed = m->want_packed;
     if (!(packed == 1 || packed == 3 || packed == 5 || packed == 6)) {
         // the rule of plan_bands for one workgroup per CU: vector fill below ~72 records per (packet, band)
-        const long rows_full = (long)std::min(dsi::max_dynamic_lds() / row_bytes, dsi::fused_max_cells(1, n_cameras) / (size_t)g.nx);
+        const long rows_full = (long)std::min(dsi::max_dynamic_lds() / row_bytes, cells(1) / (size_t)g.nx);
         packed = 1024L * rows_full / g.ny < 72 ? 5 : 1;
     }
     // the hand-scheduled loops address records with 32-bit byte offsets (see vote_device)
     if ((n_packets_max + 1) * dsi::kPacket * sizeof(dsi::EvRec) > 0xffffffffull) packed = packed == 1 ? 3 : (packed == 5 ? 6 : packed);
     const size_t scratch_bytes = (packed == 5 || packed == 6) ? (size_t)(1024 / 64) * dsi::kVfillScratchWords * 8 : 0;
     const long max_rows_total =
-        (long)std::min((dsi::max_dynamic_lds() - scratch_bytes) / row_bytes, dsi::fused_max_cells(packed, n_cameras) / (size_t)g.nx);
+        (long)std::min((dsi::max_dynamic_lds() - scratch_bytes) / row_bytes, cells(packed) / (size_t)g.nx);
     if (max_rows_total < 3) return false;
     long max_owned = max_rows_total - 2;  // + the two halo rows
     if (m->want_band_rows > 0) max_owned = std::min<long>(max_owned, m->want_band_rows);
@@ -1493,6 +1518,7 @@ int dsi_mapper_destroy(dsi_mapper_t* m)
     m->idx_filtered.release();
     m->minmax.release();
     m->pc.release();
+    for (auto& t : m->alg2_tables) t.release();
     for (auto& pr : m->timing_pairs) {
         (void)hipEventDestroy(pr.first);
         (void)hipEventDestroy(pr.second);
@@ -2053,6 +2079,169 @@ static int depth_map_of_events_impl(dsi_mapper_t* out, dsi_mapper_t* const* mapp
                                       out->depth.p, /*clear=*/1));
     out->fused_keys_dirty = false;
     return depth_buffers_ready(out);
+}
+
+/* ---- Alg. 2 of one window without a DSI (include/dsi_engine.h) ---- */
+constexpr size_t kAlg2PlanEventsPerSub = 1250000;  // both cameras' events per sub-interval (dsi_alg2_plan)
+int dsi_alg2_subintervals(size_t n_events, int n_sub, int process_method, int camera, size_t* ranges)
+{
+    REQUIRE(ranges, DSI_ERR_INVALID, "null argument");
+    REQUIRE(n_sub >= 1, DSI_ERR_INVALID, "num_subintervals must be >= 1 (got %d)", n_sub);
+    REQUIRE(process_method == 2 || process_method == 5, DSI_ERR_INVALID, "process_method 2 or 5 (got %d)", process_method);
+    REQUIRE(camera == 0 || camera == 1, DSI_ERR_INVALID, "camera 0 or 1 (got %d)", camera);
+    const size_t per = n_events / (size_t)n_sub;  // process2.cpp:46-47 (the tail is dropped)
+    // process5.cpp:89-93: the right camera starts at shift * per, shift = N / 2, and wraps around the end of its events
+    const bool shuffled = process_method == 5 && camera == 1;
+    size_t idx = shuffled ? (size_t)(n_sub / 2) * per : 0;
+    for (int k = 0; k < n_sub; ++k) {
+        size_t* r = ranges + 4 * (size_t)k;
+        if (shuffled && idx + per >= n_events) {  // process5.cpp:135-143 (note the >=)
+            r[0] = idx;
+            r[1] = n_events;
+            r[2] = 0;
+            r[3] = idx + per - n_events;
+            idx = idx + per - n_events;
+        } else {  // process2.cpp:105-107, :132-134; process5.cpp:144-149
+            r[0] = idx;
+            r[1] = idx + per;
+            r[2] = r[3] = 0;
+            idx += per;
+        }
+    }
+    return DSI_OK;
+}
+
+int dsi_alg2_plan(int n_sub, size_t n_events, int nx, int camera_time)
+{
+    if (n_sub < 1 || n_sub > dsi::kAlg2MaxSub) return 0;
+    // the band of the kernel's smallest register plan (lane mappings 5 / 6) must hold 3 rows: 2 halo + 1 owned
+    if (nx < 2 || (size_t)3 * (size_t)nx > std::min(dsi::alg2_max_cells(5, camera_time != 0), dsi::alg2_max_cells(6, camera_time != 0)))
+        return 0;
+    // measured: the DSI-less kernel's cost grows with the voting phases times the records, the
+    // materialising path's with the records plus 2 N volume passes; past ~2.5 M events per sub-interval pair the
+    // materialising path wins
+    return n_events <= (size_t)kAlg2PlanEventsPerSub * (size_t)n_sub ? 1 : 0;
+}
+
+int dsi_mapper_depth_map_of_events_alg2(dsi_mapper_t* out_tc, dsi_mapper_t* out_ct, dsi_mapper_t* const* cams,
+                                        const dsi_batch_t* const* batches, int n_sub, int stereo_fusion, int temporal_fusion)
+{
+    REQUIRE(out_tc && cams && batches && cams[0] && cams[1], DSI_ERR_INVALID, "null argument");
+    REQUIRE(n_sub >= 1 && n_sub <= dsi::kAlg2MaxSub, DSI_ERR_INVALID, "num_subintervals must be 1..%d here (got %d)",
+            dsi::kAlg2MaxSub, n_sub);
+    REQUIRE(stereo_fusion >= 1 && stereo_fusion <= 6, DSI_ERR_BAD_OP, "Improper stereo fusion method %d (expected 1..6)",
+            stereo_fusion);
+    REQUIRE(out_ct != out_tc, DSI_ERR_INVALID, "time_camera and camera_time need distinct output mappers");
+    dsi_context* ctx = out_tc->ctx;
+    dsi_mapper* outs[2] = {out_tc, out_ct};
+    const int n_out = out_ct ? 2 : 1;
+    const int n_batches = 2 * n_sub;
+    for (int i = 0; i < n_batches; ++i) {
+        REQUIRE(batches[i], DSI_ERR_INVALID, "batch %d: null", i);
+        REQUIRE(batches[i]->ctx == ctx, DSI_ERR_CONTEXT, "batches and output mappers must share one context");
+    }
+    for (int c = 0; c < 2; ++c) {
+        REQUIRE(cams[c]->ctx == ctx, DSI_ERR_CONTEXT, "camera mappers and output mappers must share one context");
+        REQUIRE(same_shape(out_tc->grid, cams[c]->grid), DSI_ERR_SHAPE, "camera %d: DSI shape differs from the output mapper's", c);
+    }
+    if (out_ct) {
+        REQUIRE(out_ct->ctx == ctx, DSI_ERR_CONTEXT, "the two output mappers must share one context");
+        REQUIRE(same_shape(out_tc->grid, out_ct->grid), DSI_ERR_SHAPE, "the two output mappers' DSI shapes differ");
+    }
+    REQUIRE(out_tc->geom.nz <= 256, DSI_ERR_INVALID, "arg-max indices are u8: dimZ must be <= 256 (got %d)", out_tc->geom.nz);
+    if (int rc = set_device(ctx)) return rc;
+    hipStream_t st = ctx->stream;
+    const dsi::Geom& geom = cams[0]->geom;
+    const size_t npix = (size_t)geom.nx * geom.ny;
+    for (int o = 0; o < n_out; ++o) {
+        HIP_TRY(outs[o]->conf.reserve(npix));
+        HIP_TRY(outs[o]->depth.reserve(npix));
+        HIP_TRY(outs[o]->idx.reserve(npix));
+    }
+    size_t np_max = 0;
+    for (int i = 0; i < n_batches; ++i) np_max = std::max(np_max, batches[i]->n_packets);
+    if (temporal_fusion != 2 && temporal_fusion != 4) {
+        // process2.cpp:213, :227, :240-243: no temporal accumulation -- every grid stays zero, and the depth map is the
+        // first maximum of a zero grid: plane 0, confidence 0 (no vote is needed)
+        for (int o = 0; o < n_out; ++o) {
+            dsi_mapper* m = outs[o];
+            if (int rc = depth_buffers_acquire(m)) return rc;
+            HIP_TRY(hipMemsetAsync(m->conf.p, 0, npix * sizeof(float), st));
+            HIP_TRY(hipMemsetAsync(m->idx.p, 0, npix, st));
+            HIP_TRY(dsi::launch_fill(st, m->depth.p, npix, m->planes[0]));
+            m->info = dsi_vote_info_t{};
+            m->info.algo = DSI_VOTE_FUSED_ARGMAX;
+            m->info.n_packets = np_max;
+            if (int rc = depth_buffers_ready(m)) return rc;
+        }
+        return DSI_OK;
+    }
+    dsi::BandPlan bp{};
+    auto cells_ct = [](int mapping) { return dsi::alg2_max_cells(mapping, true); };
+    auto cells_tc = [](int mapping) { return dsi::alg2_max_cells(mapping, false); };
+    REQUIRE(plan_fused(out_tc, np_max, &bp, 2, out_ct ? +cells_ct : +cells_tc), DSI_ERR_INVALID,
+            "grid rows of %d floats do not fit the fused Alg. 2 kernel", geom.nx);
+    bp.interleave = 0;  // contiguous pieces of the pair list per workgroup
+    if (out_tc->alg2_tables.size() < (size_t)n_batches) out_tc->alg2_tables.resize(n_batches);
+    dsi::Alg2Batches bt{};
+    bt.n_sub = n_sub;
+    dsi::PrepCameraArgs prep[dsi::kFusedMaxCameras] = {};
+    int n_prep = 0;
+    for (int i = 0; i < n_batches; ++i) {
+        dsi_mapper* m = cams[i & 1];  // k-major: (camera 0, camera 1) of sub-interval i / 2
+        const dsi_batch* b = batches[i];
+        auto& t = out_tc->alg2_tables[i];
+        const size_t np = b->n_packets;
+        HIP_TRY(t.centers.reserve(std::max<size_t>(np, 1) * 3));
+        HIP_TRY(t.sxy.reserve(np * dsi::kPacket + 1));
+        HIP_TRY(t.nvalid.reserve(np + (size_t)geom.nz + 9));
+        HIP_TRY(t.rowstart.reserve(np * (size_t)(geom.ny + 2 * bp.row_pad + 3) + 2));
+        HIP_TRY(t.coef.reserve(np * geom.nz + 1));
+        HIP_TRY(t.cuts.reserve(std::max<size_t>(np * geom.nz * bp.bands, 64)));
+        if (b->ready) HIP_TRY(hipStreamWaitEvent(st, b->ready, 0));  // uploaded on the copy stream
+        // no packets (< 1024 events): evaluateDSI returns false and the sub-interval's DSI stays zero
+        if (np == 0) HIP_TRY(hipMemsetAsync(t.nvalid.p, 0, ((size_t)geom.nz + 8) * sizeof(uint32_t), st));
+        prep[n_prep++] = dsi::PrepCameraArgs{b->Rt, b->x, b->y, b->first, m->lut_dev, m->sensor_w, m->sensor_h, t.centers.p, (int)np,
+                                             t.sxy.p, t.nvalid.p, t.rowstart.p, m->planes_dev, t.coef.p, t.cuts.p, nullptr, m->geom};
+        bt.b[i] = dsi::FusedCamera{t.sxy.p, t.coef.p, t.cuts.p, t.nvalid.p + np, (int)np};
+        if (n_prep == dsi::kFusedMaxCameras || i == n_batches - 1) {
+            HIP_TRY(dsi::launch_prepare_cameras(st, prep, n_prep, geom, bp));
+            n_prep = 0;
+        }
+    }
+    for (int o = 0; o < n_out; ++o) {
+        dsi_mapper* m = outs[o];
+        m->info = dsi_vote_info_t{};
+        m->info.algo = DSI_VOTE_FUSED_ARGMAX;
+        m->info.n_packets = np_max;
+        m->info.bands = bp.bands;
+        m->info.band_rows = bp.band_rows;
+        m->info.chunks = 1;
+        m->info.block_threads = bp.block_threads;
+        m->info.lds_bytes = bp.lds_bytes;
+        m->info.packed = bp.packed;
+        m->info.group_packets = 1;
+        if (int rc = depth_buffers_acquire(m)) return rc;
+        if (m->fused_keys.cap < npix + dsi::kFusedKeyTail || m->fused_keys_dirty) {
+            HIP_TRY(m->fused_keys.reserve(npix + dsi::kFusedKeyTail));
+            HIP_TRY(hipMemsetAsync(m->fused_keys.p, 0, m->fused_keys.cap * sizeof(unsigned long long), st));
+        }
+        m->fused_keys_dirty = true;
+    }
+    {
+        VoteTimer vt(out_tc);
+        HIP_TRY(dsi::launch_vote_alg2_argmax(st, bt, geom, bp, stereo_fusion, temporal_fusion, out_tc->fused_keys.p,
+                                             out_ct ? out_ct->fused_keys.p : nullptr));
+        vt.stop();
+    }
+    for (int o = 0; o < n_out; ++o) {
+        dsi_mapper* m = outs[o];
+        HIP_TRY(dsi::launch_unpack_argmax(st, m->fused_keys.p, (int)npix, m->planes_dev, m->conf.p, m->idx.p, m->depth.p,
+                                          /*clear=*/1));
+        m->fused_keys_dirty = false;
+        if (int rc = depth_buffers_ready(m)) return rc;
+    }
+    return DSI_OK;
 }
 
 /* ---- exact tie resolver (include/dsi_engine.h) ---- */

@@ -149,6 +149,24 @@ static_assert(offsetof(FusedCamera, sxy) == 0 && offsetof(FusedCamera, coef) == 
               "FusedCamera field offsets are read from the kernarg segment");
 static_assert(offsetof(FusedCameras, cam) == 0 && sizeof(FusedCameras) == kFusedMaxCameras * sizeof(FusedCamera) + 8,
               "FusedCameras: the camera table starts the struct (and so the kernel-argument segment)");
+// Alg. 2 without a DSI (k_vote_fuse_argmax_alg2, dsi_mapper_depth_map_of_events_alg2): the tables of 2 N event batches, k-major --
+// b[2 k] camera 0's and b[2 k + 1] camera 1's share of sub-interval k -- for N <= kAlg2MaxSub sub-intervals.  Read like
+// FusedCameras: `bt` is the kernel's FIRST parameter and b[] starts the struct, so b[i] lies at 40 i bytes of the
+// kernel-argument segment (LAYOUT LOCK, the same two conditions as FusedCameras'; FusedCamera's own asserts above).
+constexpr int kAlg2MaxSub = 8;
+struct Alg2Batches {
+    FusedCamera b[2 * kAlg2MaxSub];
+    int n_sub;  // N, 1 .. kAlg2MaxSub
+};
+static_assert(offsetof(Alg2Batches, b) == 0 && sizeof(Alg2Batches) == 2 * kAlg2MaxSub * sizeof(FusedCamera) + 8,
+              "Alg2Batches: the batch table starts the struct (and so the kernel-argument segment)");
+static_assert(sizeof(Alg2Batches) <= 1024, "Alg2Batches travels in the kernel-argument segment");
+// cells per thread of k_vote_fuse_argmax_alg2 ((band_rows + 2) * nx <= 1024 x this): camera_time keeps four fp32 arrays per
+// thread (c0, A_tc, A_l, A_r) beside two running maxima, time_camera alone two
+size_t alg2_max_cells(int mapping, bool camera_time);
+// keys_tc / keys_ct (nullptr: camera_time not computed) as launch_vote_fuse_argmax's keys; sf 1..6, tf 2 or 4
+hipError_t launch_vote_alg2_argmax(hipStream_t s, const Alg2Batches& bt, const Geom& g, const BandPlan& bp, int sf, int tf,
+                                   unsigned long long* keys_tc, unsigned long long* keys_ct);
 // The preparation of up to three cameras in two launches instead of two per camera (stage A + packet sort; coefficient /
 // cut tables), optionally counting the records per (band, plane) pair for launch_fused_splits.
 struct PrepCameraArgs {

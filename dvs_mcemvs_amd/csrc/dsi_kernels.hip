@@ -2660,10 +2660,11 @@ __device__ __forceinline__ void fused_deferred_argmax(const float* __restrict__ 
     }
 }
 
-template <int CELLS, int OP, int MODE>
-__device__ __forceinline__ void fused_consume(acc_t* __restrict__ band, int nx, int n_own, int rows_lds,
-                                              float* __restrict__ va, FusedBest<CELLS>& fb, int z,
-                                              const float* __restrict__ vpair = nullptr /* FUSED_LAST4: cameras 2's values */)
+// The read-back itself, shared by every consumer of a voted band: the owned cells read in parts of HALF (the reads of a
+// part in flight together), zeroed, converted (one rounding, the wide conversion decided per wave) and handed to
+// cell(kk, v) in cell order; then the two halo rows are cleared.
+template <int CELLS, int HALF, typename Cell>
+__device__ __forceinline__ void fused_readback(acc_t* __restrict__ band, int nx, int n_own, int rows_lds, Cell&& cell)
 {
     acc_t* own = band + nx;
     // (the thread index is re-read behind an opaque barrier so that the compiler recomputes the 20 cell
@@ -2671,9 +2672,6 @@ __device__ __forceinline__ void fused_consume(acc_t* __restrict__ band, int nx, 
     //  the voting loops, which name 40 physical registers themselves)
     int t = (int)threadIdx.x;
     asm volatile("" : "+v"(t));
-    // cells read back together.  With camera 1's values parked in a second register array (DEFER) the kernel has ~20
-    // registers fewer for the reads in flight: quarters instead of halves there
-    constexpr int HALF = (MODE == FUSED_READ1 || (MODE == FUSED_KEEP && CELLS % 4 == 0 && CELLS == 20)) ? CELLS / 4 : CELLS / 2;
     static_assert(CELLS % 2 == 0 && CELLS % HALF == 0, "whole parts");
 #pragma unroll
     for (int h = 0; h < CELLS; h += HALF) {
@@ -2686,40 +2684,49 @@ __device__ __forceinline__ void fused_consume(acc_t* __restrict__ band, int nx, 
 #pragma unroll
         for (int k = 0; k < HALF; ++k) {
             const int i = t + (h + k) * 1024;
-            acc_t* cell = i < n_own ? own + i : band;  // band[0]: first halo row, cleared below
-            *cell = 0;
+            acc_t* c = i < n_own ? own + i : band;  // band[0]: first halo row, cleared below
+            *c = 0;
         }
         // sums of 2^52 and more (2 M votes in one voxel) take the wide conversion: decided per wave, then per lane
         const bool big = __builtin_amdgcn_ballot_w64((hi_or >> 20) != 0u) != 0ull;
 #pragma unroll
-        for (int k = 0; k < HALF; ++k) {
-            const float v = big ? fix_to_float_any(raw[k]) : fix_to_float_narrow(raw[k]);
-            const int kk = h + k;
-            if (MODE == FUSED_KEEP || MODE == FUSED_READ1) {
-                va[kk] = v;
-            } else if (MODE == FUSED_MID) {
-                va[kk] = fuse_op<OP>(0.f + va[kk], v);
-            } else {
-                // process1.cpp:126-158: fused = 0; fused += dsi0; fused.<op>TwoGrids(dsi1)
-                // process1.cpp:169-191: fused.minTwoGrids / harmonicMeanTwoGrids(dsi2, 3) / maxTwoGrids(dsi2)
-                // (FUSED_LAST4: gm_tree<4> of k_fuse_gm_tree -- t0 = va = sqrt(c0 c1), t1 = sqrt(c2 c3), sqrt(t0 t1))
-                const float f = MODE == FUSED_LAST2   ? fuse_op<OP>(0.f + va[kk], v)
-                                : MODE == FUSED_LAST3 ? (OP == 2 ? harmonic_mean_n(va[kk], v, 3.f, 2.f) : fuse_op<OP>(va[kk], v))
-                                : MODE == FUSED_LAST4 ? fuse_op<3>(va[kk], fuse_op<3>(vpair[kk], v))
-                                                      : v;
-                const bool better = fb.best[kk] < f;  // strict: the first maximum wins (cartesian3dgrid.cpp:132-134)
-                fb.best[kk] = better ? f : fb.best[kk];
-                const int sh = (kk & 3) * 8;
-                const uint32_t with_z = (fb.idx4[kk >> 2] & ~(0xffu << sh)) | ((uint32_t)z << sh);
-                fb.idx4[kk >> 2] = better ? with_z : fb.idx4[kk >> 2];
-            }
-        }
+        for (int k = 0; k < HALF; ++k) cell(h + k, big ? fix_to_float_any(raw[k]) : fix_to_float_narrow(raw[k]));
     }
     acc_t* last = band + (size_t)(rows_lds - 1) * nx;
     for (int i = threadIdx.x; i < nx; i += 1024) {
         band[i] = 0;
         last[i] = 0;
     }
+}
+
+template <int CELLS, int OP, int MODE>
+__device__ __forceinline__ void fused_consume(acc_t* __restrict__ band, int nx, int n_own, int rows_lds,
+                                              float* __restrict__ va, FusedBest<CELLS>& fb, int z,
+                                              const float* __restrict__ vpair = nullptr /* FUSED_LAST4: cameras 2's values */)
+{
+    // cells read back together.  With camera 1's values parked in a second register array (DEFER) the kernel has ~20
+    // registers fewer for the reads in flight: quarters instead of halves there
+    constexpr int HALF = (MODE == FUSED_READ1 || (MODE == FUSED_KEEP && CELLS % 4 == 0 && CELLS == 20)) ? CELLS / 4 : CELLS / 2;
+    fused_readback<CELLS, HALF>(band, nx, n_own, rows_lds, [&](int kk, float v) {
+        if (MODE == FUSED_KEEP || MODE == FUSED_READ1) {
+            va[kk] = v;
+        } else if (MODE == FUSED_MID) {
+            va[kk] = fuse_op<OP>(0.f + va[kk], v);
+        } else {
+            // process1.cpp:126-158: fused = 0; fused += dsi0; fused.<op>TwoGrids(dsi1)
+            // process1.cpp:169-191: fused.minTwoGrids / harmonicMeanTwoGrids(dsi2, 3) / maxTwoGrids(dsi2)
+            // (FUSED_LAST4: gm_tree<4> of k_fuse_gm_tree -- t0 = va = sqrt(c0 c1), t1 = sqrt(c2 c3), sqrt(t0 t1))
+            const float f = MODE == FUSED_LAST2   ? fuse_op<OP>(0.f + va[kk], v)
+                            : MODE == FUSED_LAST3 ? (OP == 2 ? harmonic_mean_n(va[kk], v, 3.f, 2.f) : fuse_op<OP>(va[kk], v))
+                            : MODE == FUSED_LAST4 ? fuse_op<3>(va[kk], fuse_op<3>(vpair[kk], v))
+                                                  : v;
+            const bool better = fb.best[kk] < f;  // strict: the first maximum wins (cartesian3dgrid.cpp:132-134)
+            fb.best[kk] = better ? f : fb.best[kk];
+            const int sh = (kk & 3) * 8;
+            const uint32_t with_z = (fb.idx4[kk >> 2] & ~(0xffu << sh)) | ((uint32_t)z << sh);
+            fb.idx4[kk >> 2] = better ? with_z : fb.idx4[kk >> 2];
+        }
+    });
 }
 
 // DEFER (round 6, the one-workgroup-per-CU kernel with the packed stream): with two cameras, camera 1's read-back only
@@ -3580,6 +3587,198 @@ __global__ __launch_bounds__(256) void k_elementwise(float* __restrict__ a,
         const size_t i = n4 * 4 + threadIdx.x;
         a[i] = ew_op<KIND>(a[i], has_g ? g[i] : 0.f, fn, fn1, log_tab);
     }
+}
+
+// (3e) FUSED Alg. 2: process_2 / process_5 of one window (process2.cpp:98-289) without a DSI.
+//
+// The (band, plane) pairs of k_vote_fuse_argmax, each voted in 2N phases in the reference's order -- sub-interval k
+// ascending, camera 0 before camera 1 -- with the zeroed-band LDS stream and the read-back of that kernel.  Per cell a
+// thread keeps camera 0's value c0_k of the running sub-interval and the temporal accumulator of the fused volume A_tc
+// (camera_time: also A_l, A_r of the two cameras) in registers across the pair's phases:
+//   s_k = fuse_op<sf>(0 + c0_k, c1_k)                                         (process2.cpp:159-189, k_fuse2)
+//   tf 2: A = A + 1 / (0.01 + x), then N / A; tf 4: A = A + x, then A / N      (ew_op EW_ADD_INV / EW_ADD, EW_FIN_*)
+//   time_camera = fin(A_tc); camera_time = fuse_op<sf'>(0 + fin(A_l), fin(A_r)) (process2.cpp:266-289, 3 <-> 4 swapped)
+// -- the functions k_fuse2, k_elementwise and dsi_grid_finalize apply to the grids, in the same order per cell: the
+// same bits.  After the last phase each output's running (maximum, first index) is updated; keys leave as in
+// k_vote_fuse_argmax (atomicMax of conf bits << 8 | 255 - plane, k_unpack_argmax).
+__host__ __device__ constexpr int alg2_converse_op(int sf) { return sf == 3 ? 4 : (sf == 4 ? 3 : sf); }
+
+template <int TF>
+__device__ __forceinline__ float alg2_accumulate(float a, float x)
+{
+    return ew_op<TF == 2 ? EW_ADD_INV : EW_ADD>(a, x, 0.f, 0.f);
+}
+
+template <int TF>
+__device__ __forceinline__ float alg2_finalize(float a, float fn)
+{
+    return ew_op<TF == 2 ? EW_FIN_HM : EW_FIN_AM>(a, 0.f, fn, 0.f);
+}
+
+template <int CELLS>
+__device__ __forceinline__ void alg2_better(FusedBest<CELLS>& fb, int kk, float f, int z)
+{
+    const bool better = fb.best[kk] < f;  // strict: the first maximum wins (cartesian3dgrid.cpp:132-134)
+    fb.best[kk] = better ? f : fb.best[kk];
+    const int sh = (kk & 3) * 8;
+    const uint32_t with_z = (fb.idx4[kk >> 2] & ~(0xffu << sh)) | ((uint32_t)z << sh);
+    fb.idx4[kk >> 2] = better ? with_z : fb.idx4[kk >> 2];
+}
+
+// camera 1's read-back of sub-interval k (fused_readback, as fused_consume): the camera fusion and the temporal
+// accumulators per cell, then -- after the last sub-interval -- the finalisation and the arg-max update
+template <int CELLS, int SF, int TF, bool CT>
+__device__ __forceinline__ void alg2_consume_c1(acc_t* __restrict__ band, int nx, int n_own, int rows_lds,
+                                                const float* __restrict__ c0, float* __restrict__ atc, float* __restrict__ al,
+                                                float* __restrict__ ar, FusedBest<CELLS>& fb_tc, FusedBest<CELLS>& fb_ct, int z,
+                                                bool last, float fn)
+{
+    fused_readback<CELLS, CELLS / 2>(band, nx, n_own, rows_lds, [&](int kk, float v) {
+        atc[kk] = alg2_accumulate<TF>(atc[kk], fuse_op<SF>(0.f + c0[kk], v));
+        if (CT) {
+            al[kk] = alg2_accumulate<TF>(al[kk], c0[kk]);
+            ar[kk] = alg2_accumulate<TF>(ar[kk], v);
+        }
+    });
+    if (last) {
+#pragma unroll
+        for (int kk = 0; kk < CELLS; ++kk) {
+            alg2_better(fb_tc, kk, alg2_finalize<TF>(atc[kk], fn), z);
+            if (CT)
+                alg2_better(fb_ct, kk, fuse_op<alg2_converse_op(SF)>(0.f + alg2_finalize<TF>(al[kk], fn), alg2_finalize<TF>(ar[kk], fn)), z);
+        }
+    }
+}
+
+template <int MAPPING, int CELLS, bool CT>
+__global__ __launch_bounds__(1024) void k_vote_fuse_argmax_alg2(Alg2Batches bt, Geom g, BandPlan bp, int sf, int tf,
+                                                           unsigned long long* __restrict__ keys_tc,
+                                                           unsigned long long* __restrict__ keys_ct)
+{
+    constexpr int BLOCK = 1024;
+    extern __shared__ acc_t band[];
+    __shared__ int s_pass;
+    constexpr int kPass0 = 2 * (BLOCK / kWave);
+    const int nx = g.nx;
+    // contiguous pieces of the band-major pair list: XCD x takes the x-th eighth, split evenly over its workgroups
+    const int P = bp.bands * g.nz;
+    const int x = blockIdx.x & 7, l = blockIdx.x >> 3, per = gridDim.x >> 3;
+    const int lo = (int)(((long long)P * x) / 8), hi = (int)(((long long)P * (x + 1)) / 8);
+    const int q_begin = lo + (int)(((long long)(hi - lo) * l) / per);
+    const int q_end = lo + (int)(((long long)(hi - lo) * (l + 1)) / per);
+    if (q_begin >= q_end) return;
+    {
+        const int all_cells = (bp.band_rows + 2) * nx;
+        for (int i = threadIdx.x; i < all_cells; i += BLOCK) band[i] = 0;
+        if (threadIdx.x == 0) s_pass = kPass0;
+    }
+    __syncthreads();
+    // the batch table is read where it lies, in the kernel-argument segment (`bt` is the FIRST parameter; layout lock:
+    // dsi_kernels.h, next to Alg2Batches), with scalar loads at the uniform batch index -- as k_vote_fuse_argmax does
+    typedef const FusedCamera __attribute__((address_space(4))) * KernargBatches;
+    const KernargBatches kb = (KernargBatches)__builtin_amdgcn_kernarg_segment_ptr();
+    auto batch = [&](int b) -> FusedCamera {
+        FusedCamera o;
+        o.sxy = kb[b].sxy;
+        o.coef = kb[b].coef;
+        o.cuts = kb[b].cuts;
+        o.slow_any = kb[b].slow_any;
+        o.np = kb[b].np;
+        return o;
+    };
+    float c0[CELLS], atc[CELLS];
+    float al[CT ? CELLS : 1], ar[CT ? CELLS : 1];
+    FusedBest<CELLS> fb_tc;
+    FusedBest<CELLS> fb_ct;  // (unused without camera_time: the compiler drops it)
+    int cur_j = -1, r0 = 0, r1 = 0, n_own = 0;
+    auto emit_one = [&](unsigned long long* keys, auto& fb) {
+        unsigned long long* kp = keys + (size_t)r0 * nx;
+        int t = (int)threadIdx.x;
+        asm volatile("" : "+v"(t));
+#pragma unroll
+        for (int k = 0; k < CELLS; ++k) {
+            const int i = t + k * 1024;
+            if (i < n_own) {
+                const uint32_t zi = (fb.idx4[k >> 2] >> ((k & 3) * 8)) & 0xffu;
+                atomicMax(kp + i, ((unsigned long long)__float_as_uint(fb.best[k]) << 8) | (255u - zi));
+            }
+        }
+    };
+    for (int q = q_begin; q < q_end; ++q) {
+        const int j = q / g.nz, z = q - j * g.nz;
+        if (j != cur_j) {
+            if (cur_j >= 0) {
+                emit_one(keys_tc, fb_tc);
+                if constexpr (CT) emit_one(keys_ct, fb_ct);
+            }
+            cur_j = j;
+            r0 = j * bp.band_rows;
+            r1 = min(g.ny, r0 + bp.band_rows);
+            n_own = (r1 - r0) * nx;
+#pragma unroll
+            for (int k = 0; k < CELLS; ++k) fb_tc.best[k] = -1.f;  // below every DSI value (>= 0)
+#pragma unroll
+            for (int k = 0; k < (CELLS + 3) / 4; ++k) fb_tc.idx4[k] = 0u;
+            if constexpr (CT) {
+#pragma unroll
+                for (int k = 0; k < CELLS; ++k) fb_ct.best[k] = -1.f;
+#pragma unroll
+                for (int k = 0; k < (CELLS + 3) / 4; ++k) fb_ct.idx4[k] = 0u;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < CELLS; ++k) {
+            atc[k] = 0.f;  // the reference's accumulators start from reset grids (process2.cpp:90, fresh left / right)
+            if (CT) {
+                al[k] = 0.f;
+                ar[k] = 0.f;
+            }
+        }
+        const int rows_lds = r1 - r0 + 2;
+        const int Li = max(r0 - 1, 0), Ui = min(r1, g.ny - 1);
+#pragma nounroll
+        for (int p = 0; p < 2 * bt.n_sub; ++p) {
+            const FusedCamera cam = batch(p);
+            uint32_t first_cuts = 0u;
+            if (MAPPING == 1 && cam.np > 0) {  // (the rule of k_vote_fuse_argmax's first_cuts_of)
+                int lg = cam.np >= (BLOCK / kWave) * 16 ? 3 : 2;
+                while (lg < 5 && cam.np >= (((BLOCK / kWave) * 16) << (lg + 1))) ++lg;
+                if (bp.pass_lg > 0) lg = bp.pass_lg;
+                const int pk = min((int)((threadIdx.x / kWave) << lg) + (int)(threadIdx.x & 63), cam.np - 1);
+                first_cuts = cam.cuts[((size_t)j * g.nz + z) * cam.np + pk];
+            }
+            stream_item<BLOCK, MAPPING, true, true>(cam.sxy, cam.coef, cam.cuts, cam.slow_any, cam.np, g, bp, j, z, 0, cam.np,
+                                                    reinterpret_cast<char*>(band), Li, Ui, r0 - 1, &s_pass, first_cuts);
+            __syncthreads();
+            if (threadIdx.x == 0) s_pass = kPass0;
+            if ((p & 1) == 0) {
+                fused_consume<CELLS, 1, FUSED_KEEP>(band, nx, n_own, rows_lds, c0, fb_tc, z);
+            } else {
+                const bool last = p == 2 * bt.n_sub - 1;
+                const float fn = (float)bt.n_sub;
+#define DSI_ALG2_C1(SF, TF) alg2_consume_c1<CELLS, SF, TF, CT>(band, nx, n_own, rows_lds, c0, atc, al, ar, fb_tc, fb_ct, z, last, fn)
+#define DSI_ALG2_SF(TF)            \
+    switch (sf) {                  \
+    case 1: DSI_ALG2_C1(1, TF); break; \
+    case 2: DSI_ALG2_C1(2, TF); break; \
+    case 3: DSI_ALG2_C1(3, TF); break; \
+    case 4: DSI_ALG2_C1(4, TF); break; \
+    case 5: DSI_ALG2_C1(5, TF); break; \
+    default: DSI_ALG2_C1(6, TF); break; \
+    }
+                if (tf == 2) {
+                    DSI_ALG2_SF(2)
+                } else {
+                    DSI_ALG2_SF(4)
+                }
+#undef DSI_ALG2_SF
+#undef DSI_ALG2_C1
+            }
+            __syncthreads();
+        }
+    }
+    emit_one(keys_tc, fb_tc);
+    if constexpr (CT) emit_one(keys_ct, fb_ct);
 }
 
 // n-ary fusion in ONE pass: dst = finalize(accumulate(... accumulate(identity, src[0]) ..., src[n-1]))
@@ -5344,6 +5543,49 @@ hipError_t launch_vote_fuse_argmax(hipStream_t s, const FusedCameras& cams, cons
     case 6: return launch_vote_fuse_argmax_t<6>(s, cams, g, bp, op, splits, blocks, keys, trace);
     default: return hipErrorInvalidValue;
     }
+}
+
+// camera_time on: c0, A_tc, A_l, A_r and two running maxima per cell; off: c0, A_tc and one
+constexpr int alg2_cells_per_thread(int mapping, bool camera_time)
+{
+    return camera_time ? ((mapping == 5 || mapping == 6) ? 6 : 8) : ((mapping == 5 || mapping == 6) ? 12 : 16);
+}
+
+size_t alg2_max_cells(int mapping, bool camera_time) { return (size_t)alg2_cells_per_thread(mapping, camera_time) * 1024; }
+
+template <int MAPPING, bool CT>
+static hipError_t launch_vote_alg2_argmax_t(hipStream_t s, const Alg2Batches& bt, const Geom& g, const BandPlan& bp, int sf,
+                                            int tf, unsigned long long* keys_tc, unsigned long long* keys_ct)
+{
+    constexpr int CELLS = alg2_cells_per_thread(MAPPING, CT);
+    if ((size_t)(bp.band_rows + 2) * g.nx > (size_t)CELLS * 1024) return hipErrorInvalidValue;
+    const void* kern = reinterpret_cast<const void*>(&k_vote_fuse_argmax_alg2<MAPPING, CELLS, CT>);
+    if (hipError_t e = allow_dynamic_lds(kern, bp.lds_bytes)) return e;
+    hipLaunchKernelGGL((k_vote_fuse_argmax_alg2<MAPPING, CELLS, CT>), dim3(fused_grid_blocks()), dim3(1024), bp.lds_bytes, s, bt, g, bp,
+                       sf, tf, keys_tc, keys_ct);
+    return hipExtGetLastError();
+}
+
+template <bool CT>
+static hipError_t launch_vote_alg2_argmax_m(hipStream_t s, const Alg2Batches& bt, const Geom& g, const BandPlan& bp, int sf,
+                                            int tf, unsigned long long* keys_tc, unsigned long long* keys_ct)
+{
+    switch (bp.packed) {
+    case 1: return launch_vote_alg2_argmax_t<1, CT>(s, bt, g, bp, sf, tf, keys_tc, keys_ct);
+    case 3: return launch_vote_alg2_argmax_t<3, CT>(s, bt, g, bp, sf, tf, keys_tc, keys_ct);
+    case 5: return launch_vote_alg2_argmax_t<5, CT>(s, bt, g, bp, sf, tf, keys_tc, keys_ct);
+    case 6: return launch_vote_alg2_argmax_t<6, CT>(s, bt, g, bp, sf, tf, keys_tc, keys_ct);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_vote_alg2_argmax(hipStream_t s, const Alg2Batches& bt, const Geom& g, const BandPlan& bp, int sf, int tf,
+                                   unsigned long long* keys_tc, unsigned long long* keys_ct)
+{
+    if (bt.n_sub < 1 || bt.n_sub > kAlg2MaxSub || sf < 1 || sf > 6 || (tf != 2 && tf != 4) || !keys_tc) return hipErrorInvalidValue;
+    if (bp.block_threads != 1024 || bp.chunks != 1 || !bp.halo || g.nz > 256) return hipErrorInvalidValue;
+    return keys_ct ? launch_vote_alg2_argmax_m<true>(s, bt, g, bp, sf, tf, keys_tc, keys_ct)
+                   : launch_vote_alg2_argmax_m<false>(s, bt, g, bp, sf, tf, keys_tc, nullptr);
 }
 
 hipError_t launch_sort_groups(hipStream_t s, const float2* xy, int np, int S, int ny, int nz, int pad,

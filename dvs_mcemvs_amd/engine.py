@@ -193,6 +193,9 @@ def load_library():
         "dsi_mapper_depth_map_of_fusion_n": (C.c_int, [vp, C.POINTER(vp), C.c_int, C.c_int]),
         "dsi_mapper_depth_map_of_events": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int]),
         "dsi_mapper_depth_map_of_events_n": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int]),
+        "dsi_mapper_depth_map_of_events_alg2": (C.c_int, [vp, vp, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.c_int]),
+        "dsi_alg2_subintervals": (C.c_int, [C.c_size_t, C.c_int, C.c_int, C.c_int, szp]),
+        "dsi_alg2_plan": (C.c_int, [C.c_int, C.c_size_t, C.c_int, C.c_int]),
         "dsi_mapper_get_depth_map_from_dsi": (C.c_int, [vp, vp, C.POINTER(_DepthMapOptions), f32p, f32p,
                                                        u8p, u8p]),
         "dsi_mapper_filter_depth_map": (C.c_int, [vp, C.POINTER(_DepthMapOptions), f32p, f32p, u8p, u8p]),
@@ -1065,6 +1068,22 @@ class MapperEMVS:
         _check(load_library().dsi_mapper_depth_map_of_events_n(self._h, hm, hb, len(mappers),
                                                                int(ACC_GM_TREE if mode is None else mode)))
 
+    def computeDepthMapOfEventsAlg2(self, mapper_camera_time, mappers, batches, num_subintervals, stereo_fusion,
+                                    temporal_fusion):
+        """Alg. 2 of one window (process_2 / process_5) without a DSI (dsi_mapper_depth_map_of_events_alg2): THIS mapper
+        receives the depth map of the reference's mapper_fused ("time_camera"), mapper_camera_time (None: not computed)
+        that of mapper_fused_camera_time -- bit-identical to process.process_2 + computeDepthMap of those two DSIs.
+        mappers: the two cameras' mappers (calibrations; their DSIs are not touched); batches: 2 * num_subintervals
+        EventBatch, k-major (camera 0, camera 1 of sub-interval k), packetised against reference_view_process2."""
+        n = int(num_subintervals)
+        if len(mappers) != 2 or len(batches) != 2 * n:
+            raise DsiError(ERR_INVALID, "two camera mappers and 2 * num_subintervals batches")
+        hm = (C.c_void_p * 2)(*[m._h for m in mappers])
+        hb = (C.c_void_p * len(batches))(*[b._h for b in batches])
+        _check(load_library().dsi_mapper_depth_map_of_events_alg2(
+            self._h, mapper_camera_time._h if mapper_camera_time is not None else None, hm, hb, n, int(stereo_fusion),
+            int(temporal_fusion)))
+
     def resolveNearTies(self, mappers, batches, fusion_method=FUSE_HM, rel_gap=0.0):
         """Exact tie resolver (dsi_mapper_resolve_near_ties): after the mappers' DSIs were built from `batches`
         (evaluateDSI_batch) and this mapper holds the depth map of their fusion, re-sum the contending voxels of the
@@ -1253,6 +1272,27 @@ def packetize(ts, trajectory, T_rv_w):
         return None
     _check(rc)
     return first[:n.value].copy(), Rt[:n.value].copy()
+
+
+def alg2_subintervals(n_events, num_subintervals, process_method=2, camera=0):
+    """The event ranges of Alg. 2's sub-intervals for one camera (dsi_alg2_subintervals): a list of num_subintervals
+    (begin0, end0, begin1, end1); sub-interval k is events [begin0, end0) followed by [begin1, end1) -- the second range
+    is empty unless camera 1 of process_method 5 wraps around the end of its events (process5.cpp:135-150)."""
+    n = int(num_subintervals)
+    if n < 1:
+        raise DsiError(ERR_INVALID, "num_subintervals must be >= 1")
+    out = np.empty(4 * n, np.uint64)
+    _check(load_library().dsi_alg2_subintervals(int(n_events), n, int(process_method), int(camera),
+                                                out.ctypes.data_as(C.POINTER(C.c_size_t))))
+    return [tuple(int(v) for v in out[4 * k:4 * k + 4]) for k in range(n)]
+
+
+def alg2_plan(num_subintervals, n_events, nx, camera_time=True):
+    """The engine's Alg. 2 planner (dsi_alg2_plan): 'fused' when a window of n_events events (both cameras),
+    num_subintervals sub-intervals and nx DSI columns goes through the DSI-less kernel, 'materialize' when through
+    process_2 (more than 8 sub-intervals, rows too wide for the kernel, or past the measured break-even)."""
+    ok = load_library().dsi_alg2_plan(int(num_subintervals), int(n_events), int(nx), 1 if camera_time else 0)
+    return "fused" if ok == 1 else "materialize"
 
 
 def packetize_strided(ts_view, trajectory, T_rv_w):

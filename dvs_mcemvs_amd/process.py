@@ -106,6 +106,40 @@ def shuffled_subintervals(n_events, num_subintervals):
     return out
 
 
+def subinterval_ranges(n_events, num_subintervals, process_method=2, camera=0):
+    """Python restatement of engine.alg2_subintervals (dsi_alg2_subintervals): per sub-interval (begin0, end0, begin1,
+    end1) -- per = n_events // N, the tail dropped (process2.cpp:46-47, :105-107, :132-134); camera 1 of process_method 5
+    starts at (N // 2) * per and wraps around the end of its events when idx + per >= n_events (process5.cpp:89-93,
+    :135-150), as shuffled_subintervals does with index arrays."""
+    n_events, n = int(n_events), int(num_subintervals)
+    per = n_events // n
+    shuffled = int(process_method) == 5 and int(camera) == 1
+    idx = (n // 2) * per if shuffled else 0
+    out = []
+    for _ in range(n):
+        if shuffled and idx + per >= n_events:
+            out.append((idx, n_events, 0, idx + per - n_events))
+            idx = idx + per - n_events
+        else:
+            out.append((idx, idx + per, 0, 0))
+            idx += per
+    return out
+
+
+def subinterval_events(events, r):
+    """The events (x, y, ts) of one sub-interval range (begin0, end0, begin1, end1) of subinterval_ranges."""
+    b0, e0, b1, e1 = r
+    if e1 > b1:
+        return tuple(np.concatenate([a[b0:e0], a[b1:e1]]) for a in events)
+    return tuple(a[b0:e0] for a in events)
+
+
+def alg2_plan(num_subintervals, n_events, nx, camera_time=True):
+    """'fused' (the DSI-less kernel) or 'materialize' (process_2 and the arg-max of its DSIs) for one window: the engine's
+    planner (engine.alg2_plan, dsi_alg2_plan), the one dsi::full_sequence_depth_maps_alg2 uses too."""
+    return E.alg2_plan(num_subintervals, n_events, nx, camera_time)
+
+
 def process_2(ctx, cams, dsi_shape, events, trajectories, num_subintervals, mapper_fused,
               mapper_fused_camera_time, ts, stereo_fusion, temporal_fusion, luts=(None, None),
               inverse_depth=False, shuffle_right=False):
@@ -488,10 +522,15 @@ class WindowStream:
 
     def __init__(self, ctx, cams, dsi_shape, fusion_method=E.FUSE_HM, luts=(None, None),
                  inverse_depth=False, depth=2, materialize_fused=True, fused_vote=False, concurrent=False,
-                 exact_ties=False):
+                 exact_ties=False, process_method=1, num_subintervals=4, temporal_fusion=4, camera_time=None):
         """materialize_fused=False: the fused DSI (the reference's mapper_fused.dsi_) is not written;
         the camera fusion happens inside the arg-max kernel (same bits, one pass less over the
         volume) -- for streams that only keep the depth maps.
+        process_method 2 / 5 (main.cpp:275-299): Alg. 2 per window -- fusion_method is the stereo fusion, num_subintervals /
+        temporal_fusion as the reference's flags; camera_time (default: on for 2, off for 5, which saves time_camera only)
+        also computes mapper_fused_camera_time's map.  Windows go through the DSI-less kernel
+        (MapperEMVS.computeDepthMapOfEventsAlg2) or, where alg2_plan says so, through process_2; fetch() then returns
+        (time_camera outputs, camera_time outputs or None), each shaped like a process_method 1 result.
         fused_vote=True (implies materialize_fused=False): not even the camera DSIs are written -- one
         kernel votes, fuses and keeps the running arg-max on the CU (MapperEMVS.computeDepthMapOfEvents;
         the same depth maps bit for bit).
@@ -499,6 +538,21 @@ class WindowStream:
         that its plane index map equals the CPU reference's on every pixel; it needs the camera DSIs, so it excludes
         fused_vote; the call's statistics (and cost) are in `last_resolve`."""
         self.ctx = ctx
+        self.process_method = int(process_method)
+        if self.process_method not in (1, 2, 5):
+            raise ValueError("process_method 1, 2 or 5 (got %r)" % (process_method,))
+        self.num_subintervals = int(num_subintervals)
+        self.temporal_fusion = int(temporal_fusion)
+        self.camera_time = (self.process_method == 2) if camera_time is None else bool(camera_time)
+        self.cams, self.dsi_shape, self.luts, self.inverse_depth = cams, dsi_shape, luts, inverse_depth
+        self.last_plan = None
+        if self.process_method != 1:
+            if self.num_subintervals < 1:
+                raise ValueError("num_subintervals must be >= 1")
+            # (the options of the process_method 1 paths have no meaning here: refused rather than ignored)
+            if fused_vote or exact_ties or materialize_fused is not True:
+                raise ValueError("fused_vote, materialize_fused and exact_ties apply to process_method 1 only")
+            materialize_fused = False
         self.exact_ties = bool(exact_ties)
         self.last_resolve = None
         fused_vote = bool(fused_vote) and not self.exact_ties
@@ -521,6 +575,8 @@ class WindowStream:
         self.fused = [E.Grid3D(self.contexts[k % sets], *dims) if self.materialize_fused else None for k in range(depth)]
         self.extract = [E.MapperEMVS(self.contexts[k % sets], cams[0], dsi_shape, inverse_depth=inverse_depth)
                         for k in range(depth)]
+        self.extract_ct = [E.MapperEMVS(self.contexts[k % sets], cams[0], dsi_shape, inverse_depth=inverse_depth)
+                           for k in range(depth)] if self.process_method != 1 and self.camera_time else []
         self.k = 0
         self.voted = 0
         self._pins = {}     # (slot, camera) -> page-locked (Rt, packet_first) staging of asynchronous uploads
@@ -545,6 +601,13 @@ class WindowStream:
         slot = self.k % len(self.fused)
         ctx = self.contexts[slot % len(self.contexts)]
         mappers = self.mapper_sets[slot % len(self.mapper_sets)]
+        if self.process_method != 1:
+            if batches is not None or asynchronous or rv_pos != 0.0:
+                raise ValueError("batches, asynchronous and rv_pos apply to process_method 1 only (Alg. 2 cuts and packetises "
+                                 "its sub-intervals itself; its reference view is the left camera, process2.cpp:79-81)")
+            self._submit_alg2(slot, ctx, mappers, events, trajectories, ts)
+            self.k += 1
+            return slot
         T_rv_w = reference_view_process1(trajectories[0], ts, rv_pos)
         own, fused_batches, all_batches = [], [], []
         for c in range(2):
@@ -588,6 +651,39 @@ class WindowStream:
         self.k += 1
         return slot
 
+    def _submit_alg2(self, slot, ctx, mappers, events, trajectories, ts):
+        """process_2 / process_5 of one window (process2.cpp:28-302) into extract[slot] (time_camera) and
+        extract_ct[slot] (camera_time)."""
+        n = self.num_subintervals
+        out_ct = self.extract_ct[slot] if self.camera_time else None
+        self.last_plan = alg2_plan(n, sum(int(events[c][0].shape[0]) for c in range(2)), self.extract[slot].dimX,
+                                   self.camera_time)
+        if self.last_plan == "materialize":
+            # the materialising path: the reference's sequence on the engine's grids, then the arg-max of each DSI
+            scratch_ct = out_ct or E.MapperEMVS(ctx, self.cams[0], self.dsi_shape, inverse_depth=self.inverse_depth)
+            scratch_ct.dsi_.resetGrid()                 # (a fresh mapper_fused_camera_time per window, main.cpp:262-275)
+            res = process_2(ctx, self.cams, self.dsi_shape, events, trajectories, n, self.extract[slot], scratch_ct, ts,
+                            self.fusion_method, self.temporal_fusion, luts=self.luts, inverse_depth=self.inverse_depth,
+                            shuffle_right=self.process_method == 5)
+            res["left"].close()
+            res["right"].close()
+            self.extract[slot].computeDepthMap()
+            if out_ct is not None:
+                out_ct.computeDepthMap()
+            else:
+                scratch_ct.close()
+            self.voted += sum(int(events[c][0].shape[0]) // n * n for c in range(2))
+            return
+        # (temporal_fusion 1, 3, 5, 6: the engine votes nothing -- every grid stays zero, process2.cpp:240-243)
+        batches = alg2_window_batches(ctx, events, trajectories, ts, n, self.process_method)
+        try:
+            self.extract[slot].computeDepthMapOfEventsAlg2(out_ct, mappers, batches, n, self.fusion_method,
+                                                           self.temporal_fusion)
+            self.voted += sum(b.n_packets for b in batches) * E.PACKET_SIZE
+        finally:
+            for b in batches:
+                b.close()
+
     def fetch(self, slot, options_depth_map=None, options_point_cloud=None):
         """(depth, confidence, indices) of the window submitted into `slot` (synchronises).  With
         options_depth_map (OptionsDepthMap): the reference's per-window outputs instead --
@@ -598,14 +694,21 @@ class WindowStream:
         made of the filtered maps still on the device."""
         if options_point_cloud is not None and options_depth_map is None:
             raise ValueError("options_point_cloud needs options_depth_map: the point cloud is made of the filtered maps")
+        if self.process_method != 1:
+            ct = self.extract_ct[slot] if self.camera_time else None
+            return (self._fetch_from(self.extract[slot], options_depth_map, options_point_cloud),
+                    None if ct is None else self._fetch_from(ct, options_depth_map, options_point_cloud))
+        return self._fetch_from(self.extract[slot], options_depth_map, options_point_cloud)
+
+    def _fetch_from(self, m, options_depth_map, options_point_cloud):
         if options_depth_map is not None:
-            out = self.extract[slot].filterDepthMap(options_depth_map)
+            out = m.filterDepthMap(options_depth_map)
             if options_point_cloud is not None:
-                out = out + (self.extract[slot].getPointcloud(options_pc=options_point_cloud),)
+                out = out + (m.getPointcloud(options_pc=options_point_cloud),)
             return out
         # (every slot has its own context when the stream is concurrent: the copies follow the window's kernels on its
         #  compute stream -- one stream per window in flight, plus the device's shared upload stream)
-        return self.extract[slot].fetchDepthMap(in_order=self.concurrent)
+        return m.fetchDepthMap(in_order=self.concurrent)
 
     def fused_grid(self, slot):
         return self.fused[slot]
@@ -618,7 +721,8 @@ class WindowStream:
         return self.contexts[slot % len(self.contexts)]
 
     def close(self):
-        for o in [m for ms in self.mapper_sets for m in ms] + [f for f in self.fused if f is not None] + self.extract:
+        for o in ([m for ms in self.mapper_sets for m in ms] + [f for f in self.fused if f is not None] + self.extract +
+                  self.extract_ct):
             o.close()
         for c in self._own_contexts:
             c.close()
@@ -635,7 +739,10 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
     """Generator over the windows of main.cpp:177-302: yields (ts, depth, confidence, indices) per
     window, pipelined one window deep; with options_depth_map, (ts, depth_map, confidence_map, mask)
     -- the filtered outputs the reference saves per window; with options_point_cloud as well, the window's
-    point cloud (main.cpp:396, an (N, 4) array: WindowStream.fetch) as a fifth element."""
+    point cloud (main.cpp:396, an (N, 4) array: WindowStream.fetch) as a fifth element.
+    process_method=2 / 5 (keywords of WindowStream: num_subintervals, temporal_fusion, camera_time; fusion_method is the
+    stereo fusion): yields (ts, time_camera outputs, camera_time outputs or None), each output element shaped like what
+    process_method 1 yields after ts (main.cpp:275-299)."""
     if options_point_cloud is not None and options_depth_map is None:
         raise ValueError("options_point_cloud needs options_depth_map: the point cloud is made of the filtered maps")
     ws = WindowStream(ctx, cams, dsi_shape, fusion_method, **kw)
@@ -646,9 +753,35 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
             ev = [window_events(events[c], t0, t1) for c in range(2)]
             slot = ws.submit(ev, trajectories, ts, rv_pos)
             if pending is not None:
-                yield (pending[0],) + ws.fetch(pending[1], options_depth_map, options_point_cloud)
+                yield _window_result(ws, pending, options_depth_map, options_point_cloud)
             pending = (ts, slot)
         if pending is not None:
-            yield (pending[0],) + ws.fetch(pending[1], options_depth_map, options_point_cloud)
+            yield _window_result(ws, pending, options_depth_map, options_point_cloud)
     finally:
         ws.close()
+
+
+def _window_result(ws, pending, options_depth_map, options_point_cloud):
+    out = ws.fetch(pending[1], options_depth_map, options_point_cloud)
+    return (pending[0],) + (out if ws.process_method == 1 else tuple(out))
+
+
+def alg2_window_batches(ctx, events, trajectories, ts, num_subintervals, process_method=2):
+    """The 2 N EventBatch of one Alg. 2 window, k-major (camera 0, camera 1 of sub-interval k): each sub-interval
+    packetised on its own against T_rv_w = T_w_l(ts)^-1 (process2.cpp:79-81, :119, :146); one with fewer than 1024
+    events becomes a batch without packets (evaluateDSI returns false: its DSI stays zero)."""
+    T_rv_w = reference_view_process2(trajectories[0], ts)
+    ranges = [subinterval_ranges(events[c][0].shape[0], num_subintervals, process_method, c) for c in range(2)]
+    batches = []
+    try:
+        for k in range(int(num_subintervals)):
+            for c in range(2):
+                ev = subinterval_events(events[c], ranges[c][k])
+                pk = E.packetize(ev[2], trajectories[c], T_rv_w)
+                first, Rt = pk if pk is not None else (np.zeros(0, np.uint32), np.zeros((0, 12), np.float32))
+                batches.append(E.EventBatch(ctx, ev[0], ev[1], Rt, first))
+    except Exception:
+        for b in batches:
+            b.close()
+        raise
+    return batches

@@ -436,6 +436,33 @@ DSI_API int dsi_mapper_depth_map_of_events(dsi_mapper_t *out, dsi_mapper_t *cons
  * the reference's 2-ary op).  Everything else as dsi_mapper_depth_map_of_events. */
 DSI_API int dsi_mapper_depth_map_of_events_n(dsi_mapper_t *out, dsi_mapper_t *const *mappers,
                                              const dsi_batch_t *const *batches, int n, int mode);
+/* Alg. 2 of one window (process_2 / process_5, process2.cpp:98-289) without a DSI: bit for bit the depth maps of
+ * mapper_fused.dsi_ ("time_camera") and of mapper_fused_camera_time.dsi_ ("camera_time") after the reference's
+ *     for k in 0..n_sub-1: evaluateDSI(camera 0, batches[2k]); evaluateDSI(camera 1, batches[2k+1]);
+ *                          s_k = fuse(0 + dsi0, dsi1) by stereo_fusion; temporal accumulation of s_k, dsi0, dsi1
+ *     finalisation (temporal_fusion 2: n_sub / sum of 1 / (0.01 + x), 4: sum / n_sub; 1, 3, 5, 6: all grids stay zero)
+ *     camera_time = fuse(0 + left, right) by the converse switch (stereo_fusion 3 and 4 swapped, process2.cpp:266-289)
+ * computed by one kernel that votes the 2 n_sub batches of each (band, plane) into LDS and keeps the accumulators and the
+ * running arg-max in registers.  cams[0] / cams[1]: the two cameras' mappers (calibration; their grids are not touched);
+ * batches: k-major, packetised against T_rv_w = T_w_l(ts)^-1 (dsi_alg2_subintervals gives the event ranges);
+ * out_camera_time NULL: camera_time is not computed.  n_sub 1..8.  The batches' tables live in scratch of
+ * out_time_camera.  Results stay in the output mappers' depth-map buffers (dsi_mapper_fetch_depth_map*,
+ * dsi_mapper_filter_depth_map, dsi_mapper_get_pointcloud).  DSI_ERR_BAD_OP: stereo_fusion not in 1..6; DSI_ERR_INVALID:
+ * n_sub not in 1..8 or a NULL argument; DSI_ERR_SHAPE / DSI_ERR_CONTEXT as dsi_mapper_depth_map_of_events.  Asynchronous. */
+DSI_API int dsi_mapper_depth_map_of_events_alg2(dsi_mapper_t *out_time_camera, dsi_mapper_t *out_camera_time,
+                                                dsi_mapper_t *const *cams, const dsi_batch_t *const *batches, int n_sub,
+                                                int stereo_fusion, int temporal_fusion);
+/* Host only: the event ranges of Alg. 2's sub-intervals for one camera of n_events events.  ranges[4 k .. 4 k + 3] =
+ * (begin0, end0, begin1, end1): sub-interval k is events [begin0, end0) followed by [begin1, end1) (empty unless wrapped).
+ * per = n_events / n_sub (the tail is dropped); process_method 2, and camera 0 of 5: [k per, (k + 1) per)
+ * (process2.cpp:46-47, :105-107); camera 1 of process_method 5: from (n_sub / 2) per on, wrapping around the end of the
+ * events when idx + per >= n_events (process5.cpp:89-93, :135-150). */
+DSI_API int dsi_alg2_subintervals(size_t n_events, int n_sub, int process_method, int camera, size_t *ranges);
+/* Host only: the planner of the Alg. 2 streams (process.WindowStream, dsi::full_sequence_depth_maps_alg2).  1: a window of
+ * n_events events (both cameras), n_sub sub-intervals and nx DSI columns goes through dsi_mapper_depth_map_of_events_alg2;
+ * 0: through the materialising process_2 (n_sub > 8, rows too wide for the kernel's registers, or more events per
+ * sub-interval than the measured break-even). */
+DSI_API int dsi_alg2_plan(int n_sub, size_t n_events, int nx, int camera_time);
 DSI_API int dsi_mapper_fetch_depth_map(dsi_mapper_t *m, float *depth_host, float *conf_host, uint8_t *idx_host);
 /* the same without waiting: the copies are queued (on the context's copy stream, behind the arg-max
  * only -- not behind later work of the compute stream); the outputs (page-locked memory from

@@ -7,6 +7,7 @@
 //   process_1_exact_depth_map                                process_1 + arg-max whose index map equals the CPU reference's on every pixel
 //   process_1_depth_map                                      the same + the arg-max of getDepthMapFromDSI, without
 //                                                            writing any DSI (one fused kernel)
+//   dsi::full_sequence_depth_maps_alg2  main.cpp:275-299      the --full_seq loop with process_method 2 / 5 (DSI-less)
 //   dsi::full_sequence_depth_maps   main.cpp:177-302          the --full_seq loop (process_method 1) as a stream of
 //                                                            windows, `depth` of them in flight, one fused kernel each
 //   process_2   mapper_emvs_stereo/src/process2.cpp:28-302   sub-intervals: camera fusion then
@@ -24,6 +25,7 @@
 #ifndef DSI_PROCESS_HPP
 #define DSI_PROCESS_HPP
 
+#include <array>
 #include <chrono>
 #include <condition_variable>
 #include <cstring>
@@ -1076,5 +1078,346 @@ inline Process2Result process_5(dsi::Context& ctx, const dsi::PinholeCameraModel
     return process_2(ctx, cam0, cam1, trajectory0, trajectory1, events0, events1, dsi_shape, num_subintervals,
                      mapper_fused, mapper_fused_camera_time, ts, stereo_fusion, temporal_fusion, true);
 }
+
+
+// main.cpp:275-299 with --process_method=2 or 5 as a stream: the --full_seq loop of Alg. 2 (process2.cpp:28-302,
+// process5.cpp:28-260).  Per window the 2 N sub-interval batches are cut (dsi_alg2_subintervals), packetised against
+// T_rv_w = T_w_l(ts)^-1 by the preparation threads into the slot's page-locked staging and uploaded asynchronously, and
+// dsi_mapper_depth_map_of_events_alg2 leaves the maps of mapper_fused ("time_camera") and, with camera_time, of
+// mapper_fused_camera_time -- no DSI written.  Windows that dsi_alg2_plan sends to the materialising path (N > 8, rows
+// too wide, many events per sub-interval) run ::process_2 / ::process_5 on the slot's mappers instead: the same maps.
+// The slots, the page-locked staging, the preparation threads and the devices are those of full_sequence_depth_maps.
+namespace dsi {
+
+struct Alg2Options {
+    int process_method = 2;   // 2 or 5
+    int num_subintervals = 4;  // main.cpp:84-90 defaults
+    int stereo_fusion = 2;
+    int temporal_fusion = 4;
+    int camera_time = -1;      // -1: on for process_method 2 (process2.cpp:299-300), off for 5 (process5.cpp:258-259)
+};
+
+struct WindowDepthMapsAlg2 {
+    WindowDepthMap time_camera, camera_time;  // (camera_time is empty unless has_camera_time)
+    bool has_camera_time = false;
+};
+
+template <typename OnWindow>
+inline size_t full_sequence_depth_maps_alg2(const std::vector<int>& devices, const PinholeCameraModel& cam0,
+                                            const PinholeCameraModel& cam1, const EMVS::ShapeDSI& dsi_shape,
+                                            const LinearTrajectory& trajectory0, const LinearTrajectory& trajectory1,
+                                            const std::vector<Event>& events0, const std::vector<Event>& events1,
+                                            double start_time_s, double stop_time_s, double duration, double out_skip,
+                                            bool forward_looking, const Alg2Options& alg2, OnWindow&& on_window, int depth = 2,
+                                            const EMVS::OptionsDepthMap* options_depth_map = nullptr,
+                                            WindowStreamStats* stats = nullptr,
+                                            const EMVS::OptionsPointCloud* options_point_cloud = nullptr)
+{
+    using clock = std::chrono::steady_clock;
+    const clock::time_point t_call = clock::now();
+    WindowStreamStats st;
+    auto since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
+    const int n_sub = alg2.num_subintervals, pm = alg2.process_method;
+    const bool ct = alg2.camera_time < 0 ? pm == 2 : alg2.camera_time != 0;
+    if (!(duration > 0) || !(out_skip > 0)) throw Error(DSI_ERR_INVALID, "full_sequence_depth_maps_alg2: duration and out_skip must be > 0");
+    if (pm != 2 && pm != 5) throw Error(DSI_ERR_INVALID, "full_sequence_depth_maps_alg2: process_method 2 or 5");
+    if (n_sub < 1) throw Error(DSI_ERR_INVALID, "full_sequence_depth_maps_alg2: num_subintervals must be >= 1");
+    if (alg2.stereo_fusion < 1 || alg2.stereo_fusion > 6) throw Error(DSI_ERR_BAD_OP, "Improper stereo fusion method selected");
+    if (depth < 1) depth = 1;
+    if (devices.empty()) throw Error(DSI_ERR_INVALID, "full_sequence_depth_maps_alg2: no device");
+    if (options_point_cloud && !options_depth_map)
+        throw Error(DSI_ERR_INVALID, "full_sequence_depth_maps_alg2: options_point_cloud needs options_depth_map");
+    const size_t nb = 2 * (size_t)n_sub;
+    struct Slot {
+        Context ctx;
+        EMVS::MapperEMVS m0, m1, out, out_ct;
+        std::vector<dsi_batch_t*> batch;
+        void* host[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};  // page-locked maps per output
+        // page-locked staging per camera: x, y (the sub-intervals' events one after the other), ts, packet_first, Rt
+        void* in[2][5] = {{nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr}};
+        size_t in_events[2] = {0, 0}, in_packets[2] = {0, 0};
+        std::vector<size_t> ev_off, ev_n, pk_off, np;  // per batch (k-major)
+        std::vector<int> prc;
+        WindowDepthMapsAlg2 w, next;
+        bool busy = false, fused = true, next_fused = true;
+        Slot(int dev, const PinholeCameraModel& c0, const PinholeCameraModel& c1, const EMVS::ShapeDSI& sh, size_t nb)
+            : ctx(dev), m0(ctx, c0, sh), m1(ctx, c1, sh), out(ctx, c0, sh), out_ct(ctx, c0, sh), batch(nb, nullptr),
+              ev_off(nb), ev_n(nb), pk_off(nb), np(nb), prc(nb, DSI_OK) {}
+        ~Slot()
+        {
+            if (busy) {
+                dsi_mapper_fetch_wait(out.handle());
+                dsi_mapper_fetch_wait(out_ct.handle());
+            }
+            for (dsi_batch_t* b : batch) dsi_batch_destroy(b);
+            for (auto& o : host)
+                for (void* p : o) dsi_host_free(p);
+            for (auto& cam : in)
+                for (void* p : cam) dsi_host_free(p);
+        }
+        void reserve_inputs(int c, size_t ne, size_t npk)
+        {
+            if (ne > in_events[c] || !in[c][0]) {
+                const size_t cap = ne + ne / 4 + 1024;
+                for (int k = 0; k < 3; ++k) {
+                    dsi_host_free(in[c][k]);
+                    in[c][k] = nullptr;
+                }
+                check(dsi_host_alloc(cap * sizeof(uint16_t), &in[c][0]));
+                check(dsi_host_alloc(cap * sizeof(uint16_t), &in[c][1]));
+                check(dsi_host_alloc(cap * sizeof(double), &in[c][2]));
+                in_events[c] = cap;
+            }
+            if (npk > in_packets[c] || !in[c][3]) {
+                const size_t cap = npk + npk / 4 + 16;
+                for (int k = 3; k < 5; ++k) {
+                    dsi_host_free(in[c][k]);
+                    in[c][k] = nullptr;
+                }
+                check(dsi_host_alloc(cap * sizeof(uint32_t), &in[c][3]));
+                check(dsi_host_alloc(cap * 12 * sizeof(float), &in[c][4]));
+                in_packets[c] = cap;
+            }
+        }
+    };
+    std::vector<std::unique_ptr<Slot>> slots;
+    for (int k = 0; k < depth; ++k) slots.emplace_back(new Slot(devices[(size_t)k % devices.size()], cam0, cam1, dsi_shape, nb));
+    int nx = 0, ny = 0, nz = 0;
+    slots[0]->out.dsi_.getDimensions(&nx, &ny, &nz);
+    const size_t npix = (size_t)nx * ny;
+    for (auto& s : slots)
+        for (auto& o : s->host) {
+            check(dsi_host_alloc(npix * sizeof(float), &o[0]));
+            check(dsi_host_alloc(npix * sizeof(float), &o[1]));
+            check(dsi_host_alloc(npix, &o[2]));
+        }
+    // the slot's output mappers: time_camera, and camera_time (nullptr when it is not computed)
+    auto outs = [&](Slot& s) { return std::array<EMVS::MapperEMVS*, 2>{&s.out, ct ? &s.out_ct : nullptr}; };
+    auto complete = [&](Slot& s) {
+        const clock::time_point t0 = clock::now();
+        for (EMVS::MapperEMVS* m : outs(s))
+            if (m) check(dsi_mapper_fetch_wait(m->handle()));
+        st.wait_gpu_ms += since(t0);
+        for (dsi_batch_t*& b : s.batch) {
+            dsi_batch_destroy(b);  // (the window is done: no wait behind it)
+            b = nullptr;
+        }
+        s.busy = false;
+    };
+    auto deliver = [&](Slot& s) {
+        const clock::time_point t0 = clock::now();
+        WindowDepthMap* ws[2] = {&s.w.time_camera, &s.w.camera_time};
+        const auto ms = outs(s);
+        for (int o = 0; o < 2; ++o) {
+            if (!ms[o]) continue;
+            WindowDepthMap& w = *ws[o];
+            auto fill = [&](auto& img, const void* src) {
+                using T = typename std::remove_reference<decltype(img.data)>::type::value_type;
+                img.rows = ny;
+                img.cols = nx;
+                img.data.assign(static_cast<const T*>(src), static_cast<const T*>(src) + npix);
+            };
+            fill(w.depth_map, s.host[o][0]);
+            fill(w.confidence_map, s.host[o][1]);
+            fill(w.depth_cell_indices, s.host[o][2]);
+            if (options_depth_map) ms[o]->filterDepthMap(w.filtered_depth_map, w.filtered_confidence_map, w.semidense_mask, *options_depth_map);
+            if (options_point_cloud) ms[o]->getPointcloud(*options_point_cloud, w.point_cloud);
+        }
+        s.w.has_camera_time = ct;
+        on_window(static_cast<const WindowDepthMapsAlg2&>(s.w));
+        st.deliver_ms += since(t0);
+    };
+    const LinearTrajectory* trs[2] = {&trajectory0, &trajectory1};
+    const std::vector<Event>* evs[2] = {&events0, &events1};
+    std::vector<double> starts;  // main.cpp:177
+    for (double interval_start = start_time_s; interval_start + duration <= stop_time_s; interval_start += out_skip)
+        starts.push_back(interval_start);
+    const size_t n_windows = starts.size();
+    constexpr int kPrepSplit = 4;
+    WindowPrepWorker workers[2 * kPrepSplit];
+    auto prepare = [&](size_t i) {
+        Slot& s = *slots[i % slots.size()];
+        {
+            const clock::time_point t0 = clock::now();
+            for (dsi_batch_t* b : s.batch)
+                while (b && !dsi_batch_uploaded(b)) std::this_thread::yield();
+            st.wait_upload_ms += since(t0);
+        }
+        const double interval_start = starts[i], interval_stop = interval_start + duration;
+        const double ts = forward_looking ? interval_stop : (interval_start + interval_stop) / 2;  // main.cpp:184-188
+        Transformation T_w_l;
+        if (!trajectory0.getPoseAt(ts, T_w_l)) throw Error(DSI_ERR_INVALID, "no pose at the reference timestamp of a window");
+        WindowDepthMap d{};
+        d.index = (int)i;
+        d.t_start = interval_start;
+        d.t_stop = interval_stop;
+        d.ts = ts;
+        d.T_rv_w = inverse(T_w_l);  // process2.cpp:79-81
+        size_t range[2][2];
+        for (int c = 0; c < 2; ++c) {
+            window_event_range(*evs[c], interval_start, interval_stop, &range[c][0], &range[c][1]);
+            d.n_events[c] = range[c][1] - range[c][0];
+        }
+        s.next.time_camera = d;
+        s.next.camera_time = d;
+        s.next_fused = dsi_alg2_plan(n_sub, d.n_events[0] + d.n_events[1], nx, ct ? 1 : 0) == 1;
+        if (!s.next_fused) return;  // (the materialising path reads the events where they lie)
+        double T7[7];
+        d.T_rv_w.to7(T7);
+        for (int c = 0; c < 2; ++c) {
+            const size_t ne = d.n_events[c];
+            std::vector<size_t> r(4 * (size_t)n_sub);
+            check(dsi_alg2_subintervals(ne, n_sub, pm, c, r.data()));
+            s.reserve_inputs(c, ne, ne / DSI_PACKET_SIZE + (size_t)n_sub + 1);
+            size_t eo = 0, po = 0;
+            for (int k = 0; k < n_sub; ++k) {
+                const size_t b = 2 * (size_t)k + (size_t)c, n = (r[4 * k + 1] - r[4 * k]) + (r[4 * k + 3] - r[4 * k + 2]);
+                s.ev_off[b] = eo;
+                s.ev_n[b] = n;
+                s.pk_off[b] = po;
+                eo += n;
+                po += n / DSI_PACKET_SIZE + 1;
+            }
+            const Event* src = evs[c]->data() + range[c][0];
+            uint16_t* xs = static_cast<uint16_t*>(s.in[c][0]);
+            uint16_t* ys = static_cast<uint16_t*>(s.in[c][1]);
+            double* tss = static_cast<double*>(s.in[c][2]);
+            uint32_t* first = static_cast<uint32_t*>(s.in[c][3]);
+            float* Rt = static_cast<float*>(s.in[c][4]);
+            const LinearTrajectory* tr = trs[c];
+            Slot* sp = &s;
+            for (int part = 0; part < kPrepSplit; ++part) {
+                // sub-intervals part, part + kPrepSplit, ...: copied into the staging in the order the sub-interval takes
+                // its events (a wrapped one: the tail of the window, then its head), then packetised on their own
+                workers[c * kPrepSplit + part].start([=] {
+                    for (int k = part; k < n_sub; k += kPrepSplit) {
+                        const size_t b = 2 * (size_t)k + (size_t)c;
+                        size_t o = sp->ev_off[b];
+                        for (int seg = 0; seg < 2; ++seg)
+                            for (size_t e = r[4 * k + 2 * seg]; e < r[4 * k + 2 * seg + 1]; ++e, ++o) {
+                                xs[o] = src[e].x;
+                                ys[o] = src[e].y;
+                                tss[o] = src[e].ts;
+                            }
+                        sp->prc[b] = dsi_packetize(tss + sp->ev_off[b], sp->ev_n[b], tr->times().data(), tr->poses7().data(),
+                                                   tr->times().size(), T7, first + sp->pk_off[b], Rt + 12 * sp->pk_off[b],
+                                                   &sp->np[b]);
+                    }
+                });
+            }
+        }
+    };
+    auto submit = [&](Slot& s, size_t i) {
+        const clock::time_point t0 = clock::now();
+        auto keep_images = [](WindowDepthMap& w, const WindowDepthMap& d) {  // (the images keep their storage)
+            w.index = d.index;
+            w.t_start = d.t_start;
+            w.t_stop = d.t_stop;
+            w.ts = d.ts;
+            w.T_rv_w = d.T_rv_w;
+            w.n_events[0] = d.n_events[0];
+            w.n_events[1] = d.n_events[1];
+        };
+        keep_images(s.w.time_camera, s.next.time_camera);
+        keep_images(s.w.camera_time, s.next.camera_time);
+        s.fused = s.next_fused;
+        const auto ms = outs(s);
+        if (s.fused) {
+            dsi_mapper_t* cams[2] = {s.m0.handle(), s.m1.handle()};
+            for (size_t b = 0; b < nb; ++b) {
+                const int c = (int)(b & 1);
+                if (s.prc[b] == DSI_ERR_TOO_FEW_EVENTS) s.np[b] = 0;  // evaluateDSI returns false: the sub-interval's DSI stays zero
+                else if (s.prc[b] != DSI_OK) throw Error(s.prc[b], "dsi_packetize failed for a sub-interval (preparation thread)");
+                check(dsi_batch_create_async(s.ctx.handle(), static_cast<uint16_t*>(s.in[c][0]) + s.ev_off[b],
+                                             static_cast<uint16_t*>(s.in[c][1]) + s.ev_off[b], s.ev_n[b],
+                                             static_cast<uint32_t*>(s.in[c][3]) + s.pk_off[b],
+                                             static_cast<float*>(s.in[c][4]) + 12 * s.pk_off[b], s.np[b], &s.batch[b]));
+            }
+            check(dsi_mapper_depth_map_of_events_alg2(s.out.handle(), ms[1] ? ms[1]->handle() : nullptr, cams, s.batch.data(),
+                                                      n_sub, alg2.stereo_fusion, alg2.temporal_fusion));
+        } else {
+            // the materialising path: the reference's sequence on the engine's grids (fresh grids per window, main.cpp:262-275)
+            const double t_start = starts[i], t_stop = t_start + duration;
+            std::vector<Event> ev[2];
+            for (int c = 0; c < 2; ++c) {
+                size_t a = 0, b = 0;
+                window_event_range(*evs[c], t_start, t_stop, &a, &b);
+                ev[c].assign(evs[c]->begin() + (long)a, evs[c]->begin() + (long)b);
+            }
+            s.out_ct.dsi_.resetGrid();
+            ::process_2(s.ctx, cam0, cam1, trajectory0, trajectory1, ev[0], ev[1], dsi_shape, n_sub, s.out, s.out_ct,
+                        s.w.time_camera.ts, alg2.stereo_fusion, alg2.temporal_fusion, pm == 5);
+            for (EMVS::MapperEMVS* m : ms)
+                if (m) check(dsi_mapper_depth_map_of(m->handle(), m->dsi_.handle()));
+        }
+        for (int o = 0; o < 2; ++o)
+            if (ms[o])
+                check(dsi_mapper_fetch_depth_map_in_order(ms[o]->handle(), static_cast<float*>(s.host[o][0]),
+                                                          static_cast<float*>(s.host[o][1]), static_cast<uint8_t*>(s.host[o][2])));
+        s.busy = true;
+        st.submit_ms += since(t0);
+    };
+    auto wait_workers = [&]() {
+        const clock::time_point t0 = clock::now();
+        for (WindowPrepWorker& w : workers) w.wait();
+        st.wait_prepare_ms += since(t0);
+    };
+    const bool ahead = slots.size() >= 2;
+    if (n_windows) prepare(0);
+    for (size_t i = 0; i < n_windows; ++i) {
+        Slot& s = *slots[i % slots.size()];
+        wait_workers();
+        if (s.busy) {  // the window this slot holds, before submit() replaces it (its staging is read by prepare below)
+            complete(s);
+            deliver(s);
+        }
+        submit(s, i);
+        if (i + 1 < n_windows) {
+            if (ahead) {
+                Slot& s2 = *slots[(i + 1) % slots.size()];
+                if (s2.busy) {  // (prepare(i + 1) overwrites s2's staging and plan: collect its window first)
+                    complete(s2);
+                    deliver(s2);
+                }
+            } else {
+                complete(s);
+                deliver(s);
+            }
+            prepare(i + 1);
+        }
+    }
+    wait_workers();
+    for (size_t k = 0; k < slots.size(); ++k) {
+        Slot& s = *slots[(n_windows + k) % slots.size()];
+        if (s.busy) {
+            complete(s);
+            deliver(s);
+        }
+    }
+    if (stats) {
+        st.total_ms = since(t_call);
+        st.windows = n_windows;
+        *stats = st;
+    }
+    return n_windows;
+}
+
+// one GPU
+template <typename OnWindow>
+inline size_t full_sequence_depth_maps_alg2(int device, const PinholeCameraModel& cam0, const PinholeCameraModel& cam1,
+                                            const EMVS::ShapeDSI& dsi_shape, const LinearTrajectory& trajectory0,
+                                            const LinearTrajectory& trajectory1, const std::vector<Event>& events0,
+                                            const std::vector<Event>& events1, double start_time_s, double stop_time_s,
+                                            double duration, double out_skip, bool forward_looking, const Alg2Options& alg2,
+                                            OnWindow&& on_window, int depth = 2, const EMVS::OptionsDepthMap* options_depth_map = nullptr,
+                                            WindowStreamStats* stats = nullptr,
+                                            const EMVS::OptionsPointCloud* options_point_cloud = nullptr)
+{
+    return full_sequence_depth_maps_alg2(std::vector<int>{device}, cam0, cam1, dsi_shape, trajectory0, trajectory1, events0,
+                                         events1, start_time_s, stop_time_s, duration, out_skip, forward_looking, alg2,
+                                         std::forward<OnWindow>(on_window), depth, options_depth_map, stats, options_point_cloud);
+}
+
+}  // namespace dsi
 
 #endif
