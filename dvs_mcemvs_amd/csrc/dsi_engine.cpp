@@ -172,6 +172,9 @@ struct dsi_context {
     // focus-based collapses: one arg-max key per pixel and plane range; dsi_grid_local_focus in place: the new volume
     DevBuf<unsigned long long> focus_keys;
     DevBuf<float> focus_volume;
+    // Grid3D min/max, slices and slice images: partial extremes and per-slice scales; device side of the host-output forms
+    DevBuf<unsigned long long> grid_words;
+    DevBuf<uint8_t> grid_bytes;
     // grids, mappers and batches created from this context and not yet destroyed: each holds a pointer to it, so the
     // context refuses to go while any is alive (destroying it first was a use-after-free in their destroy)
     std::atomic<int> children{0};
@@ -981,6 +984,8 @@ int dsi_context_destroy(dsi_context_t* ctx)
     if (ctx->collapse_scratch) (void)hipFree(ctx->collapse_scratch);
     ctx->focus_keys.release();
     ctx->focus_volume.release();
+    ctx->grid_words.release();
+    ctx->grid_bytes.release();
     ctx->pc.release();
     for (hipEvent_t ev : ctx->marks) (void)hipEventDestroy(ev);
     ctx->marks.clear();
@@ -1396,6 +1401,150 @@ int dsi_grid_mean_square(dsi_grid_t* g, double* out)
     HIP_TRY(hipMemcpyAsync(&sum, ctx->ms_accum, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *out = sum / (double)g->n;  // cartesian3dgrid.cpp:173
+    return DSI_OK;
+}
+
+// ---- the rest of Grid3D: binary ops, min/max, slices, slice images ----
+
+int dsi_grid_binary_op(dsi_grid_t* dst, const dsi_grid_t* src, int op)
+{
+    if (int rc = check_pair(dst, src)) return rc;
+    REQUIRE(op >= DSI_GRID_OP_SUBTRACT && op <= DSI_GRID_OP_CUBIC_MEAN, DSI_ERR_BAD_OP,
+            "grid op %d is not one of 1..4 (subtract, ratio, quadratic mean, cubic mean)", op);
+    // dst == src is op(a, a): every voxel is read (both operands) before it is written, by the same thread
+    HIP_TRY(dsi::launch_grid_binary(dst->ctx->stream, dst->data, src->data, dst->n, op));
+    return DSI_OK;
+}
+
+int dsi_grid_min_max(dsi_grid_t* g, float* min_val, float* max_val, uint64_t* min_pos, uint64_t* max_pos)
+{
+    REQUIRE(g && min_val && max_val, DSI_ERR_INVALID, "null argument");
+    dsi_context* ctx = g->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    HIP_TRY(ctx->grid_words.reserve(dsi::grid_min_max_words()));
+    HIP_TRY(dsi::launch_grid_min_max(ctx->stream, g->data, g->n, ctx->grid_words.p, 0));
+    unsigned long long r[3];
+    HIP_TRY(hipMemcpyAsync(r, ctx->grid_words.p, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const uint32_t lo = (uint32_t)r[0], hi = (uint32_t)(r[0] >> 32);  // (float min, float max) in the first word
+    std::memcpy(min_val, &lo, 4);
+    std::memcpy(max_val, &hi, 4);
+    if (min_pos) *min_pos = r[1];
+    if (max_pos) *max_pos = r[2];
+    return DSI_OK;
+}
+
+static int check_slice_args(const dsi_grid_t* g, unsigned slice_idx, unsigned dim_idx)
+{
+    REQUIRE(dim_idx <= 2u, DSI_ERR_INVALID, "dimIdx should be 0, 1 or 2 (got %u)", dim_idx);
+    const unsigned size = (unsigned)(dim_idx == 0 ? g->nx : (dim_idx == 1 ? g->ny : g->nz));
+    REQUIRE(slice_idx < size, DSI_ERR_INVALID, "slice %u is outside dimension %u of size %u", slice_idx, dim_idx, size);
+    return DSI_OK;
+}
+
+static size_t slice_elems(const dsi_grid_t* g, unsigned dim_idx)
+{
+    return dim_idx == 0 ? (size_t)g->ny * g->nz : (dim_idx == 1 ? (size_t)g->nx * g->nz : (size_t)g->nx * g->ny);
+}
+
+int dsi_grid_get_slice_dev(dsi_grid_t* g, unsigned slice_idx, unsigned dim_idx, float* slice_dev)
+{
+    REQUIRE(g && slice_dev, DSI_ERR_INVALID, "null argument");
+    if (int rc = check_slice_args(g, slice_idx, dim_idx)) return rc;
+    if (int rc = set_device(g->ctx)) return rc;
+    HIP_TRY(dsi::launch_grid_get_slice(g->ctx->stream, g->data, g->nx, g->ny, g->nz, (int)slice_idx, (int)dim_idx, slice_dev));
+    return DSI_OK;
+}
+
+int dsi_grid_get_slice(dsi_grid_t* g, unsigned slice_idx, unsigned dim_idx, float* slice_host)
+{
+    REQUIRE(g && slice_host, DSI_ERR_INVALID, "null argument");
+    if (int rc = check_slice_args(g, slice_idx, dim_idx)) return rc;
+    dsi_context* ctx = g->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    const size_t bytes = slice_elems(g, dim_idx) * sizeof(float);
+    HIP_TRY(ctx->grid_bytes.reserve(bytes));
+    float* dev = reinterpret_cast<float*>(ctx->grid_bytes.p);
+    if (int rc = dsi_grid_get_slice_dev(g, slice_idx, dim_idx, dev)) return rc;
+    HIP_TRY(hipMemcpyAsync(slice_host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DSI_OK;
+}
+
+int dsi_grid_accumulate_z_slice(dsi_grid_t* g, unsigned iz, const float* img_host, int rows, int cols)
+{
+    REQUIRE(g && img_host, DSI_ERR_INVALID, "null argument");
+    REQUIRE(rows >= 0 && cols >= 0 && rows <= g->ny && cols <= g->nx, DSI_ERR_INVALID,
+            "a %d x %d image does not fit the %d x %d plane", rows, cols, g->ny, g->nx);
+    REQUIRE(iz < (unsigned)g->nz, DSI_ERR_INVALID, "slice %u is outside dimZ = %d", iz, g->nz);
+    dsi_context* ctx = g->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    const size_t bytes = (size_t)rows * cols * sizeof(float);
+    if (bytes == 0) return DSI_OK;
+    HIP_TRY(ctx->grid_bytes.reserve(bytes));
+    float* dev = reinterpret_cast<float*>(ctx->grid_bytes.p);
+    HIP_TRY(hipMemcpyAsync(dev, img_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(dsi::launch_grid_accumulate_z_slice(ctx->stream, g->data, g->nx, g->ny, (int)iz, dev, rows, cols));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the image and the scratch are free again on return
+    return DSI_OK;
+}
+
+int dsi_grid_value_at(dsi_grid_t* g, uint64_t p, float* out)
+{
+    REQUIRE(g && out, DSI_ERR_INVALID, "null argument");
+    REQUIRE(p < g->n, DSI_ERR_INVALID, "voxel %llu is outside the grid of %zu cells", (unsigned long long)p, g->n);
+    if (int rc = set_device(g->ctx)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, g->data + p, sizeof(float), hipMemcpyDeviceToHost, g->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(g->ctx->stream));
+    return DSI_OK;
+}
+
+int dsi_grid_set_value_at(dsi_grid_t* g, uint64_t p, float v)
+{
+    REQUIRE(g, DSI_ERR_INVALID, "grid is null");
+    REQUIRE(p < g->n, DSI_ERR_INVALID, "voxel %llu is outside the grid of %zu cells", (unsigned long long)p, g->n);
+    if (int rc = set_device(g->ctx)) return rc;
+    HIP_TRY(hipMemcpyAsync(g->data + p, &v, sizeof(float), hipMemcpyHostToDevice, g->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(g->ctx->stream));
+    return DSI_OK;
+}
+
+int dsi_grid_accumulate_value_at(dsi_grid_t* g, uint64_t p, float v)
+{
+    float old = 0.f;
+    if (int rc = dsi_grid_value_at(g, p, &old)) return rc;
+    return dsi_grid_set_value_at(g, p, old + v);  // one fp32 addition, as data_array_.at(p) += fval
+}
+
+static size_t slices_words(const dsi_grid_t* g, unsigned dim_idx)
+{
+    const size_t n_slices = (size_t)(dim_idx == 0 ? g->nx : (dim_idx == 1 ? g->ny : g->nz));
+    return dsi::grid_min_max_words() + 2 * n_slices;
+}
+
+int dsi_grid_slices_u8_dev(dsi_grid_t* g, unsigned dim_idx, int normalize_by_minmax, uint8_t* out_dev)
+{
+    REQUIRE(g && out_dev, DSI_ERR_INVALID, "null argument");
+    REQUIRE(dim_idx <= 2u, DSI_ERR_INVALID, "dimIdx should be 0, 1 or 2 (got %u)", dim_idx);
+    REQUIRE((reinterpret_cast<uintptr_t>(out_dev) & 3u) == 0, DSI_ERR_INVALID, "the device output must be 4-byte aligned");
+    dsi_context* ctx = g->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    HIP_TRY(ctx->grid_words.reserve(slices_words(g, dim_idx)));
+    HIP_TRY(dsi::launch_grid_slices_u8(ctx->stream, g->data, g->nx, g->ny, g->nz, (int)dim_idx, normalize_by_minmax != 0,
+                                       ctx->grid_words.p, out_dev));
+    return DSI_OK;
+}
+
+int dsi_grid_slices_u8(dsi_grid_t* g, unsigned dim_idx, int normalize_by_minmax, uint8_t* out_host)
+{
+    REQUIRE(g && out_host, DSI_ERR_INVALID, "null argument");
+    REQUIRE(dim_idx <= 2u, DSI_ERR_INVALID, "dimIdx should be 0, 1 or 2 (got %u)", dim_idx);
+    dsi_context* ctx = g->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    HIP_TRY(ctx->grid_bytes.reserve(g->n));
+    if (int rc = dsi_grid_slices_u8_dev(g, dim_idx, normalize_by_minmax, ctx->grid_bytes.p)) return rc;
+    HIP_TRY(hipMemcpyAsync(out_host, ctx->grid_bytes.p, g->n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return DSI_OK;
 }
 

@@ -336,4 +336,18 @@ hipError_t launch_local_focus(hipStream_t s, const float* src, float* dst, int n
 // Grid3D::collapseMinZSlice (cartesian3dgrid.cpp:139-161)
 hipError_t launch_collapse_min_z(hipStream_t s, const float* dsi, int nx, int ny, int nz, float* val, uint8_t* idx);
 
+// ---- Grid3D: binary ops 1..4 (subtract, ratio, quadratic mean, cubic mean; cartesian3dgrid.h:95-109,166-184), getMinMax,
+// getSlice, accumulateZSliceAt and the 8-bit slice images of imwriteSlices ----
+hipError_t launch_grid_binary(hipStream_t s, float* a, const float* g, size_t n, int op);
+// words[0..3): (min, max | min_pos | max_pos) once the stream has run; grid_min_max_words() 64-bit words of scratch in all.
+// max_blocks: 0 for the default number of workgroups; the result does not depend on it ((value, position) is a total order).
+constexpr int kGridMinMaxBlocks = 1024;
+size_t grid_min_max_words();
+hipError_t launch_grid_min_max(hipStream_t s, const float* vol, size_t n, unsigned long long* words, int max_blocks);
+hipError_t launch_grid_get_slice(hipStream_t s, const float* vol, int nx, int ny, int nz, int slice, int dim, float* out);
+hipError_t launch_grid_accumulate_z_slice(hipStream_t s, float* vol, int nx, int ny, int iz, const float* img, int rows, int cols);
+// words: grid_min_max_words() + 2 * (slices of the orientation) words of scratch; out: nx * ny * nz bytes, 4-byte aligned
+hipError_t launch_grid_slices_u8(hipStream_t s, const float* vol, int nx, int ny, int nz, int dim, int normalize_by_minmax,
+                                 unsigned long long* words, uint8_t* out);
+
 }  // namespace dsi

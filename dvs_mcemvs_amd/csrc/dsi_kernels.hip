@@ -7244,4 +7244,482 @@ hipError_t launch_collapse_min_z(hipStream_t s, const float* dsi, int nx, int ny
     return hipExtGetLastError();
 }
 
+// ------------------------------------------------- Grid3D: the rest of the class ---
+// subtractTwoGrids / ratioTwoGrids / quadraticMeanTwoGrids / cubicMeanTwoGrids (cartesian3dgrid.h:95-109,166-184), getMinMax
+// (cartesian3dgrid.cpp:177-188), getSlice (:72-113), accumulateZSliceAt (.h:195-204) and the 8-bit slice images of
+// imwriteSlices (cartesian3dgrid_IO.cpp:39-76).  Arithmetic: DESIGN.md 7d.
+namespace {
+
+// the float nearest to the real cube root of x.  The estimate y (good to an ulp or two of a double) rounds to the right
+// float unless it lies next to the midpoint m of two floats; there m^3 is compared with |x| exactly: m has 25 significant
+// bits, so m*m is exact, (m*m)*m = h + e with e from one FMA, and m^3 (75 significant bits) never equals a double.
+__device__ __forceinline__ float cbrt_rn_f32(double x)
+{
+    if (!(x == x) || x == 0.0 || __builtin_isinf(x)) return (float)x;  // cbrt keeps +-0, +-inf and NaN
+    const double ax = __builtin_fabs(x);
+    const double y = cbrt(ax);
+    float f = (float)y;  // a normal float: |x| >= 2^-150, so y >= 2^-50
+    const double fd = (double)f;
+    const float o = __uint_as_float(fd <= y ? __float_as_uint(f) + 1u : __float_as_uint(f) - 1u);
+    const double mid = 0.5 * (fd + (double)o);
+    if (__builtin_fabs(y - mid) <= y * 0x1p-48) {
+        const double p = mid * mid;
+        const double h = p * mid;
+        const double e = __builtin_fma(p, mid, -h);
+        const bool mid_below = h < ax || (h == ax && e < 0.0);
+        f = mid_below ? (f < o ? o : f) : (f < o ? f : o);
+    }
+    return x < 0.0 ? -f : f;
+}
+
+enum { GRID_OP_SUBTRACT = 1, GRID_OP_RATIO = 2, GRID_OP_QUADRATIC_MEAN = 3, GRID_OP_CUBIC_MEAN = 4 };
+
+template <int OP>
+__device__ __forceinline__ float grid_op(float a, float g)
+{
+    if (OP == GRID_OP_SUBTRACT) return a - g;  // :99
+    if (OP == GRID_OP_RATIO)                   // :107, fabs is double fabs(double) there: sum and quotient in double
+        return (float)((double)a / (__builtin_fabs((double)g) + (double)0.1f));
+    if (OP == GRID_OP_QUADRATIC_MEAN) {        // :170-172, float sum of squares, 0.5 and sqrt in double
+        const float s = a * a + g * g;
+        return (float)sqrt(0.5 * (double)s);
+    }
+    const float s = (a * a) * a + (g * g) * g;  // :180-182
+    return cbrt_rn_f32(0.5 * (double)s);
+}
+
+template <int OP>
+__global__ __launch_bounds__(256) void k_grid_binary(float* __restrict__ a, const float* __restrict__ g, size_t n)
+{
+    const size_t n4 = n / 4;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        float4 va = reinterpret_cast<float4*>(a)[i];
+        const float4 vg = reinterpret_cast<const float4*>(g)[i];
+        va.x = grid_op<OP>(va.x, vg.x);
+        va.y = grid_op<OP>(va.y, vg.y);
+        va.z = grid_op<OP>(va.z, vg.z);
+        va.w = grid_op<OP>(va.w, vg.w);
+        reinterpret_cast<float4*>(a)[i] = va;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const size_t i = n4 * 4 + threadIdx.x;
+        a[i] = grid_op<OP>(a[i], g[i]);
+    }
+}
+
+// std::minmax_element: the FIRST smallest and the LAST largest element.  (value, position) pairs under a total order --
+// equal values (+0 and -0 included) are told apart by position -- so any reduction tree gives the same answer.
+struct MinMaxItem {
+    float mn, mx;
+    unsigned long long mn_pos, mx_pos;
+};
+__device__ __forceinline__ void minmax_merge(MinMaxItem& a, float mn, unsigned long long mn_pos, float mx, unsigned long long mx_pos)
+{
+    if (mn < a.mn || (mn == a.mn && mn_pos < a.mn_pos)) {
+        a.mn = mn;
+        a.mn_pos = mn_pos;
+    }
+    if (mx > a.mx || (mx == a.mx && mx_pos > a.mx_pos)) {
+        a.mx = mx;
+        a.mx_pos = mx_pos;
+    }
+}
+// a thread visits its elements in ascending position: a strictly smaller value replaces the minimum, a larger OR EQUAL one
+// the maximum.  The neutral items (+inf at the last possible position, -inf at position 0) lose every tie.
+__device__ __forceinline__ void minmax_take(MinMaxItem& a, float v, unsigned long long pos)
+{
+    if (v < a.mn || (v == a.mn && pos < a.mn_pos)) {
+        a.mn = v;
+        a.mn_pos = pos;
+    }
+    if (v >= a.mx) {
+        a.mx = v;
+        a.mx_pos = pos;
+    }
+}
+__device__ __forceinline__ MinMaxItem minmax_block_reduce(MinMaxItem it, MinMaxItem* part)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        const float mn = __shfl_down(it.mn, off, 64), mx = __shfl_down(it.mx, off, 64);
+        const unsigned long long mn_pos = __shfl_down(it.mn_pos, off, 64), mx_pos = __shfl_down(it.mx_pos, off, 64);
+        minmax_merge(it, mn, mn_pos, mx, mx_pos);
+    }
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = it;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < 4; ++w) minmax_merge(it, part[w].mn, part[w].mn_pos, part[w].mx, part[w].mx_pos);
+    return it;  // thread 0 holds the block's item
+}
+
+__global__ __launch_bounds__(256) void k_grid_min_max(const float* __restrict__ vol, size_t n, MinMaxItem* __restrict__ partials)
+{
+    __shared__ MinMaxItem part[4];
+    MinMaxItem it{INFINITY, -INFINITY, ~0ull, 0ull};
+    const size_t n4 = n / 4;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const float4 v = reinterpret_cast<const float4*>(vol)[i];
+        minmax_take(it, v.x, 4 * i);
+        minmax_take(it, v.y, 4 * i + 1);
+        minmax_take(it, v.z, 4 * i + 2);
+        minmax_take(it, v.w, 4 * i + 3);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {  // the tail lies behind everything this thread has seen
+        const size_t i = n4 * 4 + threadIdx.x;
+        minmax_take(it, vol[i], i);
+    }
+    it = minmax_block_reduce(it, part);
+    if (threadIdx.x == 0) partials[blockIdx.x] = it;
+}
+
+// the finishing step: one workgroup folds the partials; positions of a volume without any comparable value (all NaN:
+// unspecified result) are clamped into the volume
+__global__ __launch_bounds__(256) void k_grid_min_max_finish(const MinMaxItem* __restrict__ partials, int n_part, size_t n,
+                                                             MinMaxItem* __restrict__ result)
+{
+    __shared__ MinMaxItem part[4];
+    MinMaxItem it{INFINITY, -INFINITY, ~0ull, 0ull};
+    for (int i = threadIdx.x; i < n_part; i += 256)
+        minmax_merge(it, partials[i].mn, partials[i].mn_pos, partials[i].mx, partials[i].mx_pos);
+    it = minmax_block_reduce(it, part);
+    if (threadIdx.x == 0) {
+        if (it.mn_pos >= n) it.mn_pos = n - 1;
+        if (it.mx_pos >= n) it.mx_pos = n - 1;
+        *result = it;
+    }
+}
+
+// getSlice: one thread per output element
+__global__ __launch_bounds__(256) void k_grid_get_slice(const float* __restrict__ vol, int nx, int ny, int nz, int slice, int dim,
+                                                        float* __restrict__ out)
+{
+    const int cols = dim == 2 ? nx : nz, rows = dim == 0 ? ny : (dim == 1 ? nx : ny);
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= rows * cols) return;
+    const int v = o / cols, u = o - v * cols;
+    size_t src;
+    if (dim == 0) src = ((size_t)u * ny + v) * nx + slice;       // (x = slice, y = v, z = u)
+    else if (dim == 1) src = ((size_t)u * ny + slice) * nx + v;  // (x = v, y = slice, z = u)
+    else src = ((size_t)slice * ny + v) * nx + u;                // (x = u, y = v, z = slice)
+    out[o] = vol[src];
+}
+
+// accumulateZSliceAt: vol(ix, iy, iz) += img(iy, ix), one thread per image element
+__global__ __launch_bounds__(256) void k_grid_accumulate_z_slice(float* __restrict__ vol, int nx, int ny, int iz,
+                                                                 const float* __restrict__ img, int rows, int cols)
+{
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= rows * cols) return;
+    const int iy = o / cols, ix = o - iy * cols;
+    const size_t p = ((size_t)iz * ny + iy) * nx + ix;
+    vol[p] = vol[p] + img[o];
+}
+
+// ---- slice images.  cvRound + saturate_cast<uchar>: nearest, ties to even, clamped, NaN -> 0
+__device__ __forceinline__ uint32_t round_u8(float w)
+{
+    if (!(w == w)) return 0u;
+    const float r = __builtin_rintf(w);
+    return (uint32_t)(r < 0.f ? 0.f : (r > 255.f ? 255.f : r));
+}
+// normalize_by_minmax: (v - min) / range * 255, three roundings.  Per slice: v * a + b, two roundings (a, b of cv::normalize)
+template <bool MINMAX>
+__device__ __forceinline__ uint32_t slice_u8(float v, float p0, float p1)
+{
+    if (MINMAX) {
+        float t = v - p0;
+        t = t / p1;
+        return round_u8(t * 255.f);
+    }
+    const float t = v * p0;
+    return round_u8(t + p1);
+}
+
+// per-slice minima and maxima of one orientation in ONE pass over the volume, as monotone integer keys (integer atomics:
+// min and max are exact in any order).  keys[2 s], keys[2 s + 1]: min and max of slice s, preset to 0xffffffff / 0.
+// DIM 0: thread = x column of a chunk of (y, z) rows; DIM 1 / 2: blockIdx.y = the slice, the loop runs over the other axis.
+template <int DIM>
+__global__ __launch_bounds__(256) void k_grid_slice_minmax(const float* __restrict__ vol, int nx, int ny, int nz, int rows_per_block,
+                                                           uint32_t* __restrict__ keys)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    uint32_t kmin = 0xffffffffu, kmax = 0u;
+    if (DIM == 0) {
+        if (x >= nx) return;
+        const size_t rows = (size_t)ny * nz;
+        const size_t r0 = (size_t)blockIdx.y * rows_per_block;
+        const size_t r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
+        for (size_t r = r0; r < r1; ++r) {
+            const float v = vol[r * nx + x];
+            if (v == v) {
+                const uint32_t k = float_key(v);
+                kmin = k < kmin ? k : kmin;
+                kmax = k > kmax ? k : kmax;
+            }
+        }
+        if (kmin <= kmax) {
+            atomicMin(&keys[2 * x], kmin);
+            atomicMax(&keys[2 * x + 1], kmax);
+        }
+        return;
+    }
+    const int s = blockIdx.y;
+    const int n_other = DIM == 1 ? nz : ny;
+    if (x < nx)
+        for (int j = 0; j < n_other; ++j) {
+            const size_t row = DIM == 1 ? (size_t)j * ny + s : (size_t)s * ny + j;
+            const float v = vol[row * nx + x];
+            if (v == v) {
+                const uint32_t k = float_key(v);
+                kmin = k < kmin ? k : kmin;
+                kmax = k > kmax ? k : kmax;
+            }
+        }
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t a = __shfl_down(kmin, off, 64), b = __shfl_down(kmax, off, 64);
+        kmin = a < kmin ? a : kmin;
+        kmax = b > kmax ? b : kmax;
+    }
+    if ((threadIdx.x & 63) == 0 && kmin <= kmax) {
+        atomicMin(&keys[2 * s], kmin);
+        atomicMax(&keys[2 * s + 1], kmax);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_grid_slice_keys_init(uint32_t* __restrict__ keys, int n_slices)
+{
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= n_slices) return;
+    keys[2 * s] = 0xffffffffu;
+    keys[2 * s + 1] = 0u;
+}
+
+// cv::normalize(NORM_MINMAX, 0, 255): scale = 255 * (1 / (smax - smin)) if smax - smin > DBL_EPSILON else 0, shift =
+// -smin * scale, in double, both cast to float (the arithmetic of the confidence image, k_conf8's)
+__global__ __launch_bounds__(256) void k_grid_slice_scale(const uint32_t* __restrict__ keys, int n_slices, float2* __restrict__ ab)
+{
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= n_slices) return;
+    const double smin = (double)key_float(keys[2 * s]), smax = (double)key_float(keys[2 * s + 1]);
+    const double rng = smax - smin;
+    const double scale = 255.0 * (rng > 2.220446049250313e-16 ? 1.0 / rng : 0.0);
+    const double shift = 0.0 - smin * scale;
+    ab[s] = make_float2((float)scale, (float)shift);
+}
+
+// dim_idx 2: the images are the volume's own planes -- a streaming conversion, four voxels to one packed word
+template <bool MINMAX, typename IDX>
+__global__ __launch_bounds__(256) void k_grid_slices_u8_z(const float* __restrict__ vol, size_t n, IDX npix,
+                                                          const MinMaxItem* __restrict__ mm, const float2* __restrict__ ab,
+                                                          uint8_t* __restrict__ out)
+{
+    float p0 = 0.f, p1 = 0.f;
+    if (MINMAX) {
+        p0 = mm->mn;
+        p1 = mm->mx - mm->mn;
+    }
+    const size_t n4 = n / 4;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const float4 v = reinterpret_cast<const float4*>(vol)[i];
+        const float e[4] = {v.x, v.y, v.z, v.w};
+        IDX z = 0, r = 0;
+        if (!MINMAX) {
+            z = (IDX)(4 * i) / npix;
+            r = (IDX)(4 * i) - z * npix;
+        }
+        uint32_t pk = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!MINMAX) {
+                while (r >= npix) {
+                    r -= npix;
+                    ++z;
+                }
+                const float2 c = ab[z];
+                p0 = c.x;
+                p1 = c.y;
+                ++r;
+            }
+            pk |= slice_u8<MINMAX>(e[k], p0, p1) << (8 * k);
+        }
+        reinterpret_cast<uint32_t*>(out)[i] = pk;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const size_t i = n4 * 4 + threadIdx.x;
+        if (!MINMAX) {
+            const float2 c = ab[i / npix];
+            p0 = c.x;
+            p1 = c.y;
+        }
+        out[i] = (uint8_t)slice_u8<MINMAX>(vol[i], p0, p1);
+    }
+}
+
+// dim_idx 0 (out[x][y][z]) and 1 (out[y][x][z]): z becomes the fastest axis, so for a fixed y a 64 x 64 tile of (x, z)
+// goes through LDS, ALREADY AS BYTES: a thread converts four consecutive z of its x and stores them as one word.
+//   global reads   a wave reads 64 consecutive x of one (y, z) row: 256 contiguous bytes
+//   LDS            word (x, d) of the tile -- d = z / 4 -- lies at x * 16 + ((d + x / 2) & 15).  The store (32 lanes = 32
+//                  consecutive x, one d) hits banks 16 (x & 1) + ((d + x / 2) & 15): all different.  The transposed load (32
+//                  lanes = 2 consecutive x, 16 d) hits 16 (x & 1) + a rotation of 0..15: all different.  (A rotation where
+//                  one would pad: a row pitch of 17 words keeps the store conflict-free but makes rows x and x + 1 collide
+//                  in one bank of the load; 64 banks of 4 bytes, ds_read/write_b32 served in two groups of 32 lanes.)
+//   global writes  16 lanes write the 64 contiguous bytes of one (x, y) row, a wave four such rows; words when dimZ is a
+//                  multiple of 4 (every row then starts on a word), bytes otherwise
+// out[x * stride_x + y * stride_y + z]; slice_is_x selects the per-slice (a, b) by x (dim_idx 0) or by y (dim_idx 1).
+template <bool MINMAX>
+__global__ __launch_bounds__(256) void k_grid_slices_u8(const float* __restrict__ vol, int nx, int ny, int nz, size_t stride_x,
+                                                        size_t stride_y, int slice_is_x, int words,
+                                                        const MinMaxItem* __restrict__ mm, const float2* __restrict__ ab,
+                                                        uint8_t* __restrict__ out)
+{
+    __shared__ uint32_t tile[64 * 16];
+    const int y = blockIdx.x, z0 = blockIdx.y * 64, x0 = blockIdx.z * 64;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int x = x0 + lane;
+    float p0 = 0.f, p1 = 0.f;
+    if (MINMAX) {
+        p0 = mm->mn;
+        p1 = mm->mx - mm->mn;
+    } else if (x < nx) {
+        const float2 c = ab[slice_is_x ? x : y];
+        p0 = c.x;
+        p1 = c.y;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int d = w + 4 * j;
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int z = z0 + 4 * d + k;
+            v[k] = (x < nx && z < nz) ? vol[((size_t)z * ny + y) * nx + x] : 0.f;
+        }
+        uint32_t pk = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) pk |= slice_u8<MINMAX>(v[k], p0, p1) << (8 * k);
+        tile[lane * 16 + ((d + (lane >> 1)) & 15)] = pk;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int xl = (threadIdx.x >> 4) + 16 * j, d = threadIdx.x & 15;
+        const uint32_t pk = tile[xl * 16 + ((d + (xl >> 1)) & 15)];
+        const int xo = x0 + xl, z = z0 + 4 * d;
+        if (xo < nx && z < nz) {
+            uint8_t* o = out + (size_t)xo * stride_x + (size_t)y * stride_y + z;
+            if (words) {
+                *reinterpret_cast<uint32_t*>(o) = pk;
+            } else {
+                for (int k = 0; k < 4 && z + k < nz; ++k) o[k] = (uint8_t)(pk >> (8 * k));
+            }
+        }
+    }
+}
+
+}  // namespace
+
+size_t grid_min_max_words() { return (sizeof(MinMaxItem) / 8) * (size_t)(kGridMinMaxBlocks + 1); }
+
+hipError_t launch_grid_binary(hipStream_t s, float* a, const float* g, size_t n, int op)
+{
+    const dim3 grid(grid_for(n / 4 + 1, 256)), block(256);
+    switch (op) {
+    case 1: hipLaunchKernelGGL(k_grid_binary<1>, grid, block, 0, s, a, g, n); break;
+    case 2: hipLaunchKernelGGL(k_grid_binary<2>, grid, block, 0, s, a, g, n); break;
+    case 3: hipLaunchKernelGGL(k_grid_binary<3>, grid, block, 0, s, a, g, n); break;
+    case 4: hipLaunchKernelGGL(k_grid_binary<4>, grid, block, 0, s, a, g, n); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipExtGetLastError();
+}
+
+hipError_t launch_grid_min_max(hipStream_t s, const float* vol, size_t n, unsigned long long* words, int max_blocks)
+{
+    static_assert(sizeof(MinMaxItem) == 24, "three words per item");
+    MinMaxItem* items = reinterpret_cast<MinMaxItem*>(words);  // [0]: the result, [1..]: one partial per workgroup
+    if (max_blocks < 1 || max_blocks > kGridMinMaxBlocks) max_blocks = kGridMinMaxBlocks;
+    const int blocks = grid_for(n / 4 + 1, 256, max_blocks);
+    hipLaunchKernelGGL(k_grid_min_max, dim3(blocks), dim3(256), 0, s, vol, n, items + 1);
+    hipError_t e = hipExtGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_grid_min_max_finish, dim3(1), dim3(256), 0, s, items + 1, blocks, n, items);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_grid_get_slice(hipStream_t s, const float* vol, int nx, int ny, int nz, int slice, int dim, float* out)
+{
+    const size_t count = dim == 0 ? (size_t)ny * nz : (dim == 1 ? (size_t)nx * nz : (size_t)nx * ny);
+    if (count > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_grid_get_slice, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, vol, nx, ny, nz, slice, dim, out);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_grid_accumulate_z_slice(hipStream_t s, float* vol, int nx, int ny, int iz, const float* img, int rows, int cols)
+{
+    const size_t count = (size_t)rows * cols;
+    if (count == 0) return hipSuccess;
+    if (count > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_grid_accumulate_z_slice, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, vol, nx, ny, iz, img, rows,
+                       cols);
+    return hipExtGetLastError();
+}
+
+// words: grid_min_max_words() for the volume's extremes, then one word of keys and one word of (a, b) per slice
+hipError_t launch_grid_slices_u8(hipStream_t s, const float* vol, int nx, int ny, int nz, int dim, int normalize_by_minmax,
+                                 unsigned long long* words, uint8_t* out)
+{
+    const size_t n = (size_t)nx * ny * nz;
+    const int n_slices = dim == 0 ? nx : (dim == 1 ? ny : nz);
+    const MinMaxItem* mm = reinterpret_cast<const MinMaxItem*>(words);
+    uint32_t* keys = reinterpret_cast<uint32_t*>(words + grid_min_max_words());
+    float2* ab = reinterpret_cast<float2*>(words + grid_min_max_words() + n_slices);
+    hipError_t e;
+    if (normalize_by_minmax) {
+        if ((e = launch_grid_min_max(s, vol, n, words, 0)) != hipSuccess) return e;
+    } else {
+        hipLaunchKernelGGL(k_grid_slice_keys_init, dim3((n_slices + 255) / 256), dim3(256), 0, s, keys, n_slices);
+        if ((e = hipExtGetLastError()) != hipSuccess) return e;
+        const unsigned xb = (unsigned)((nx + 255) / 256);
+        if (dim == 0) {
+            const size_t rows = (size_t)ny * nz;
+            const int rows_per_block = (int)((rows + 1023) / 1024 < 16 ? 16 : (rows + 1023) / 1024);
+            const unsigned yb = (unsigned)((rows + rows_per_block - 1) / rows_per_block);
+            hipLaunchKernelGGL(k_grid_slice_minmax<0>, dim3(xb, yb), dim3(256), 0, s, vol, nx, ny, nz, rows_per_block, keys);
+        } else if (dim == 1) {
+            hipLaunchKernelGGL(k_grid_slice_minmax<1>, dim3(xb, (unsigned)ny), dim3(256), 0, s, vol, nx, ny, nz, 0, keys);
+        } else {
+            hipLaunchKernelGGL(k_grid_slice_minmax<2>, dim3(xb, (unsigned)nz), dim3(256), 0, s, vol, nx, ny, nz, 0, keys);
+        }
+        if ((e = hipExtGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_grid_slice_scale, dim3((n_slices + 255) / 256), dim3(256), 0, s, keys, n_slices, ab);
+        if ((e = hipExtGetLastError()) != hipSuccess) return e;
+    }
+    if (dim == 2) {
+        const dim3 grid(grid_for(n / 4 + 1, 256)), block(256);
+        const size_t npix = (size_t)nx * ny;
+        if (normalize_by_minmax)
+            hipLaunchKernelGGL((k_grid_slices_u8_z<true, uint32_t>), grid, block, 0, s, vol, n, 1u, mm, ab, out);
+        else if (n <= 0xffffffffull)
+            hipLaunchKernelGGL((k_grid_slices_u8_z<false, uint32_t>), grid, block, 0, s, vol, n, (uint32_t)npix, mm, ab, out);
+        else
+            hipLaunchKernelGGL((k_grid_slices_u8_z<false, size_t>), grid, block, 0, s, vol, n, npix, mm, ab, out);
+        return hipExtGetLastError();
+    }
+    // out[x][y][z] (dim 0) or out[y][x][z] (dim 1)
+    const size_t stride_x = dim == 0 ? (size_t)ny * nz : (size_t)nz;
+    const size_t stride_y = dim == 0 ? (size_t)nz : (size_t)nx * nz;
+    const dim3 grid((unsigned)ny, (unsigned)((nz + 63) / 64), (unsigned)((nx + 63) / 64));
+    if (grid.y > 65535u || grid.z > 65535u) return hipErrorInvalidValue;
+    const int words_ok = (nz % 4) == 0;
+    if (normalize_by_minmax)
+        hipLaunchKernelGGL(k_grid_slices_u8<true>, grid, dim3(256), 0, s, vol, nx, ny, nz, stride_x, stride_y, dim == 0, words_ok, mm,
+                           ab, out);
+    else
+        hipLaunchKernelGGL(k_grid_slices_u8<false>, grid, dim3(256), 0, s, vol, nx, ny, nz, stride_x, stride_y, dim == 0, words_ok, mm,
+                           ab, out);
+    return hipExtGetLastError();
+}
+
 }  // namespace dsi

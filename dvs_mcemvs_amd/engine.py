@@ -25,6 +25,7 @@ ACC_SUM, ACC_INV_SUM, ACC_LOG_SUM, ACC_SQ_SUM, ACC_MIN, ACC_MAX, ACC_GM_TREE = 0
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2
 VOTE_AUTO, VOTE_GLOBAL_ATOMIC, VOTE_LDS_BANDS, VOTE_FUSED_ARGMAX = 0, 1, 2, 3
 FOCUS_LOCAL_VAR, FOCUS_LOCAL_MS, FOCUS_GRAD_MAG, FOCUS_LAPLACIAN, FOCUS_DOG = 0, 1, 2, 3, 4
+GRID_OP_SUBTRACT, GRID_OP_RATIO, GRID_OP_QUADRATIC_MEAN, GRID_OP_CUBIC_MEAN = 1, 2, 3, 4
 
 (OK, ERR_INVALID, ERR_TOO_FEW_EVENTS, ERR_HIP, ERR_SHAPE, ERR_BAD_OP, ERR_NO_DEVICE,
  ERR_CONTEXT, ERR_COMM) = range(9)
@@ -156,6 +157,16 @@ def load_library():
         "dsi_grid_collapse_focus_dev": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
         "dsi_grid_collapse_min_z": (C.c_int, [vp, f32p, u8p]),
         "dsi_grid_local_focus": (C.c_int, [vp, vp, C.c_int]),
+        "dsi_grid_binary_op": (C.c_int, [vp, vp, C.c_int]),
+        "dsi_grid_min_max": (C.c_int, [vp, f32p, f32p, u64p, u64p]),
+        "dsi_grid_get_slice": (C.c_int, [vp, C.c_uint, C.c_uint, f32p]),
+        "dsi_grid_get_slice_dev": (C.c_int, [vp, C.c_uint, C.c_uint, vp]),
+        "dsi_grid_accumulate_z_slice": (C.c_int, [vp, C.c_uint, f32p, C.c_int, C.c_int]),
+        "dsi_grid_value_at": (C.c_int, [vp, C.c_uint64, f32p]),
+        "dsi_grid_set_value_at": (C.c_int, [vp, C.c_uint64, C.c_float]),
+        "dsi_grid_accumulate_value_at": (C.c_int, [vp, C.c_uint64, C.c_float]),
+        "dsi_grid_slices_u8": (C.c_int, [vp, C.c_uint, C.c_int, u8p]),
+        "dsi_grid_slices_u8_dev": (C.c_int, [vp, C.c_uint, C.c_int, vp]),
         "dsi_mapper_create": (C.c_int, [vp, C.POINTER(_MapperConfig), C.POINTER(vp)]),
         "dsi_mapper_destroy": (C.c_int, [vp]),
         "dsi_mapper_grid": (vp, [vp]),
@@ -721,6 +732,92 @@ class Grid3D:
         out = C.c_double()
         _check(load_library().dsi_grid_mean_square(self._h, C.byref(out)))
         return out.value
+
+    # -- the members that are no camera fusion, cartesian3dgrid.h:95-109,166-184 ----------------
+    def _binary(self, other, op):
+        _check(load_library().dsi_grid_binary_op(self._h, other._h, int(op)))
+
+    def subtractTwoGrids(self, grid2):
+        self._binary(grid2, GRID_OP_SUBTRACT)
+
+    def ratioTwoGrids(self, grid2, eps=None):
+        """self /= |grid2| + 0.1f.  Only the reference's default eps is offered."""
+        if eps is not None and np.float32(eps) != np.float32(1e-1):
+            raise DsiError(ERR_INVALID, "ratioTwoGrids: only the default eps = 1e-1f is supported")
+        self._binary(grid2, GRID_OP_RATIO)
+
+    def quadraticMeanTwoGrids(self, grid2):
+        self._binary(grid2, GRID_OP_QUADRATIC_MEAN)
+
+    def cubicMeanTwoGrids(self, grid2):
+        self._binary(grid2, GRID_OP_CUBIC_MEAN)
+
+    # -- cartesian3dgrid.cpp:72-113, :177-188, cartesian3dgrid.h:40-58,195-204 ------------------------------------
+    def getMinMax(self):
+        """(min, max, min_pos, max_pos): the first smallest and the last largest element of the flat array."""
+        lo, hi = C.c_float(), C.c_float()
+        lo_pos, hi_pos = C.c_uint64(), C.c_uint64()
+        _check(load_library().dsi_grid_min_max(self._h, C.byref(lo), C.byref(hi), C.byref(lo_pos), C.byref(hi_pos)))
+        return np.float32(lo.value), np.float32(hi.value), int(lo_pos.value), int(hi_pos.value)
+
+    def _slice_shape(self, dimIdx):
+        nx, ny, nz = self.getDimensions()
+        if dimIdx not in (0, 1, 2):
+            raise DsiError(ERR_INVALID, "dimIdx should be 0, 1 or 2 (got %r)" % (dimIdx,))
+        return ((nx, ny, nz)[dimIdx],) + ((ny, nz), (nx, nz), (ny, nx))[dimIdx]
+
+    def getSlice(self, sliceIdx, dimIdx):
+        """float32 [rows][cols]: dimIdx 0 -> (dimY, dimZ) at x, 1 -> (dimX, dimZ) at y, 2 -> (dimY, dimX) at z."""
+        if sliceIdx < 0:
+            raise DsiError(ERR_INVALID, "negative slice index")
+        out = np.empty(self._slice_shape(dimIdx)[1:], np.float32)
+        _check(load_library().dsi_grid_get_slice(self._h, int(sliceIdx), int(dimIdx), _ptr(out, C.c_float)))
+        return out
+
+    def accumulateZSliceAt(self, iz, img):
+        """vol(ix, iy, iz) += img[iy, ix]; the image may be smaller than the plane."""
+        img = _arr(img, np.float32)
+        if img.ndim != 2 or iz < 0:
+            raise DsiError(ERR_INVALID, "accumulateZSliceAt takes a 2-D image and a slice index >= 0")
+        _check(load_library().dsi_grid_accumulate_z_slice(self._h, int(iz), _ptr(img, C.c_float), img.shape[0], img.shape[1]))
+
+    def _flat(self, p, iy=None, iz=None):
+        if iy is None:
+            if p < 0:
+                raise DsiError(ERR_INVALID, "negative voxel index")
+            return int(p)
+        nx, ny, nz = self.getDimensions()
+        if not (0 <= p < nx and 0 <= iy < ny and 0 <= iz < nz):
+            raise DsiError(ERR_INVALID, "voxel (%d,%d,%d) is outside the grid (%d,%d,%d)" % (p, iy, iz, nx, ny, nz))
+        return int(p) + nx * (int(iy) + ny * int(iz))
+
+    def getGridValueAt(self, p, iy=None, iz=None):
+        """getGridValueAt(p) or getGridValueAt(ix, iy, iz)."""
+        out = C.c_float()
+        _check(load_library().dsi_grid_value_at(self._h, self._flat(p, iy, iz), C.byref(out)))
+        return np.float32(out.value)
+
+    def setGridValueAt(self, p, fval):
+        _check(load_library().dsi_grid_set_value_at(self._h, self._flat(p), float(np.float32(fval))))
+
+    def accumulateGridValueAt(self, p, fval):
+        _check(load_library().dsi_grid_accumulate_value_at(self._h, self._flat(p), float(np.float32(fval))))
+
+    # -- cartesian3dgrid_IO.cpp:39-76 ------------------------------------------------------------------------------
+    def slicesU8(self, dimIdx, normalize_by_minmax=True):
+        """Every slice of one orientation as an 8-bit image: uint8 [size[dimIdx]][rows][cols], getSlice's shapes."""
+        out = np.empty(self._slice_shape(dimIdx), np.uint8)
+        _check(load_library().dsi_grid_slices_u8(self._h, int(dimIdx), int(bool(normalize_by_minmax)), _ptr(out, C.c_uint8)))
+        return out
+
+    def imwriteSlices(self, prefix, dimIdx, normalize_by_minmax=True):
+        """prefix + three-digit zero-padded slice index + ".png", 8-bit grayscale; returns the file names."""
+        from . import io as _io
+        names = []
+        for i, img in enumerate(self.slicesU8(dimIdx, normalize_by_minmax)):
+            names.append("%s%03d.png" % (prefix, i))
+            _io.write_png_gray8(names[-1], img)
+        return names
 
 
 class ShapeDSI:

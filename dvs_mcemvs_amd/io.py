@@ -3,6 +3,7 @@ reference's own Python tools can consume this engine's outputs and its recorded
 trajectories can be replayed without ROS:
 
   write_grid_npy        Grid3D::writeGridNpy           cartesian3dgrid_IO.cpp:30-36   (.npy, shape {Z,Y,X} f32)
+  write_png_gray8       cv::imwrite of a CV_8UC1 slice  cartesian3dgrid_IO.cpp:74              (.png, 8-bit grayscale)
   save_depth_points     saveDepthMaps (txt part)        utils.cpp:31-46                ("col row depth" lines)
   save_pcd_ascii        pcl::io::savePCDFileASCII       main.cpp:397-402               (.pcd v0.7, PointXYZI, ascii)
   read_pose_bag         parse of geometry_msgs/PoseStamped bags   data_loading.cpp:221-302 (ROSBAG v2.0; none / bz2 chunks)
@@ -14,6 +15,7 @@ format and is not pinned against a PCL build (none is available to this project)
 """
 import bz2
 import struct
+import zlib
 
 import numpy as np
 
@@ -27,6 +29,26 @@ def write_grid_npy(path, grid):
     with open(path, "wb") as f:
         np.save(f, vol, allow_pickle=False)
     return vol.shape
+
+
+def write_png_gray8(path, img):
+    """An 8-bit grayscale PNG of a uint8 [rows][cols] image (Grid3D.imwriteSlices): IHDR, one IDAT holding the zlib
+    stream of the scanlines, each with filter type 0, IEND.  Any PNG reader shows the pixels that were written; the
+    bytes of the file are not those of OpenCV's encoder (other filters, other compression level)."""
+    img = np.ascontiguousarray(img)
+    if img.dtype != np.uint8 or img.ndim != 2 or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError("write_png_gray8 takes a non-empty 2-D uint8 image")
+    rows, cols = img.shape
+    raw = np.zeros((rows, cols + 1), np.uint8)
+    raw[:, 1:] = img
+
+    def chunk(kind, body):
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xffffffff)
+
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", cols, rows, 8, 0, 0, 0, 0)) +
+                chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + chunk(b"IEND", b""))
+    return rows, cols
 
 
 def save_depth_points(path, depth_map, mask):

@@ -218,6 +218,44 @@ DSI_API int dsi_grid_collapse_min_z(dsi_grid_t *g, float *val_host, uint8_t *idx
  * back, so no reader of the grid sees it half written.  Same shape, same device.  Asynchronous. */
 DSI_API int dsi_grid_local_focus(dsi_grid_t *dst, const dsi_grid_t *src, int focus_method);
 
+/* ---- the rest of Grid3D (arithmetic and definitions: DESIGN.md 7d) ---- */
+/* Voxel-wise members that are NOT camera fusions (no --stereo_fusion value selects them): their own enum; dsi_fuse_op_t and
+ * every call that takes it are unchanged. */
+typedef enum {
+    DSI_GRID_OP_SUBTRACT = 1,       /* Grid3D::subtractTwoGrids       cartesian3dgrid.h:95-101   a - g */
+    DSI_GRID_OP_RATIO = 2,          /* Grid3D::ratioTwoGrids          cartesian3dgrid.h:103-109  a / (|g| + 0.1f), in double */
+    DSI_GRID_OP_QUADRATIC_MEAN = 3, /* Grid3D::quadraticMeanTwoGrids  cartesian3dgrid.h:166-174  sqrt(0.5 (a a + g g)) */
+    DSI_GRID_OP_CUBIC_MEAN = 4      /* Grid3D::cubicMeanTwoGrids      cartesian3dgrid.h:176-184  cbrt(0.5 (a a a + g g g)) */
+} dsi_grid_op_t;
+/* dst = op(dst, src), in place, op = dsi_grid_op_t.  dst == src is legal and gives op(a, a) (the reference takes grid2 by
+ * value).  DSI_ERR_SHAPE: different dimensions; DSI_ERR_CONTEXT: different devices; DSI_ERR_BAD_OP: op not in 1..4. */
+DSI_API int dsi_grid_binary_op(dsi_grid_t *dst, const dsi_grid_t *src, int op);
+/* Grid3D::getMinMax (cartesian3dgrid.cpp:177-188) = std::minmax_element over the flat array: the FIRST smallest and the
+ * LAST largest element; -0.f == +0.f, so position decides and the value returned carries that element's bits.  min_pos /
+ * max_pos may be NULL.  A volume holding NaN gives an unspecified result (still DSI_OK).  Synchronises. */
+DSI_API int dsi_grid_min_max(dsi_grid_t *g, float *min_val, float *max_val, uint64_t *min_pos, uint64_t *max_pos);
+/* Grid3D::getSlice (cartesian3dgrid.cpp:72-113), row-major rows x cols floats:
+ *   dim_idx 0: ny x nz, out[v*nz+u] = vol(slice, v, u);  1: nx x nz, out[v*nz+u] = vol(v, slice, u);  2: the ny x nx plane.
+ * dim_idx > 2 or slice_idx outside the dimension: DSI_ERR_INVALID.  Host output; synchronises. */
+DSI_API int dsi_grid_get_slice(dsi_grid_t *g, unsigned slice_idx, unsigned dim_idx, float *slice_host);
+/* same, device output, asynchronous */
+DSI_API int dsi_grid_get_slice_dev(dsi_grid_t *g, unsigned slice_idx, unsigned dim_idx, float *slice_dev);
+/* Grid3D::accumulateZSliceAt (cartesian3dgrid.h:195-204): vol(ix, iy, iz) += img(iy, ix) for iy < rows, ix < cols (row-major
+ * host image).  rows <= ny, cols <= nx, iz < nz, else DSI_ERR_INVALID; an image smaller than the plane is legal. */
+DSI_API int dsi_grid_accumulate_z_slice(dsi_grid_t *g, unsigned iz, const float *img_host, int rows, int cols);
+/* Grid3D::getGridValueAt(p) / setGridValueAt / accumulateGridValueAt(p, fval) (cartesian3dgrid.h:40-58): single voxels,
+ * ordered on the context's stream; p >= nx*ny*nz: DSI_ERR_INVALID (the reference: std::out_of_range).  Synchronise. */
+DSI_API int dsi_grid_value_at(dsi_grid_t *g, uint64_t p, float *out);
+DSI_API int dsi_grid_set_value_at(dsi_grid_t *g, uint64_t p, float v);
+DSI_API int dsi_grid_accumulate_value_at(dsi_grid_t *g, uint64_t p, float v);
+/* What Grid3D::imwriteSlices (cartesian3dgrid_IO.cpp:39-76) computes before it writes files: EVERY slice of one orientation
+ * as an 8-bit image, slice after slice, each of dsi_grid_get_slice's shape -- nx*ny*nz bytes.  normalize_by_minmax != 0:
+ * (v - min) / (max - min) * 255 with the volume's extremes; 0: cv::normalize(NORM_MINMAX, 0, 255) per slice.  Rounded to
+ * nearest (ties to even), clamped to 0..255, NaN -> 0.  dim_idx > 2: DSI_ERR_INVALID.  Host output; synchronises. */
+DSI_API int dsi_grid_slices_u8(dsi_grid_t *g, unsigned dim_idx, int normalize_by_minmax, uint8_t *out_host);
+/* same, device output (4-byte aligned, else DSI_ERR_INVALID), asynchronous */
+DSI_API int dsi_grid_slices_u8_dev(dsi_grid_t *g, unsigned dim_idx, int normalize_by_minmax, uint8_t *out_dev);
+
 /* ---------------------------------------------------------- multi-GPU (RCCL) */
 /* The temporal fusion of process_2 (process2.cpp:211-242: one accumulate per sub-interval, one
  * finalize) and of the sliding window (main.cpp:177) shards by time slice: every GPU accumulates

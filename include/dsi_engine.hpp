@@ -18,6 +18,7 @@
 // dsi::Error (carrying the C status code).
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -148,6 +149,80 @@ inline bool inpaint_depth_cell_indices(const ImgT& /*filtered u8*/, const ImgT& 
                                        ImgT& /*inpainted u8*/)
 {
     return false;
+}
+
+// Customisation point for Grid3D::imwriteSlices (cartesian3dgrid_IO.cpp:74: imwrite(ss.str(), slice_u)).  The default
+// writes an 8-bit grayscale PNG with a minimal encoder of its own -- signature, IHDR, one IDAT whose zlib stream holds
+// STORED deflate blocks (no compression), every scanline with filter type 0, IEND; CRC-32 per chunk, Adler-32 of the raw
+// scanlines -- because neither libpng nor OpenCV may be assumed here.  Any PNG reader decodes it to the pixels written.  A
+// caller with OpenCV adds, in namespace cv or in namespace dsi before this header,
+//     inline bool imwrite_gray8(const std::string& path, const cv::Mat& img) { return cv::imwrite(path, img); }
+// and calls imwriteSlices<cv::Mat>(...): the overload is found by ADL and wins over this template.
+inline bool write_png_gray8(const std::string& path, const uint8_t* pixels, int rows, int cols)
+{
+    if (!pixels || rows < 1 || cols < 1) return false;
+    static const std::vector<uint32_t> table = [] {
+        std::vector<uint32_t> t(256);
+        for (uint32_t n = 0; n < 256; ++n) {
+            uint32_t c = n;
+            for (int k = 0; k < 8; ++k) c = (c & 1u) ? 0xedb88320u ^ (c >> 1) : c >> 1;
+            t[n] = c;
+        }
+        return t;
+    }();
+    auto be32 = [](std::vector<uint8_t>& v, uint32_t x) {
+        for (int sh = 24; sh >= 0; sh -= 8) v.push_back((uint8_t)(x >> sh));
+    };
+    auto chunk = [&](std::vector<uint8_t>& file, const char kind[4], const std::vector<uint8_t>& body) {
+        be32(file, (uint32_t)body.size());
+        const size_t start = file.size();
+        file.insert(file.end(), kind, kind + 4);
+        file.insert(file.end(), body.begin(), body.end());
+        uint32_t c = 0xffffffffu;
+        for (size_t i = start; i < file.size(); ++i) c = table[(c ^ file[i]) & 0xffu] ^ (c >> 8);
+        be32(file, c ^ 0xffffffffu);
+    };
+    std::vector<uint8_t> raw;  // the scanlines, each behind its filter byte
+    raw.reserve((size_t)rows * (cols + 1));
+    for (int y = 0; y < rows; ++y) {
+        raw.push_back(0);
+        raw.insert(raw.end(), pixels + (size_t)y * cols, pixels + (size_t)(y + 1) * cols);
+    }
+    std::vector<uint8_t> z = {0x78, 0x01};  // zlib header: deflate, 32 KiB window, no preset dictionary
+    uint32_t a = 1, b = 0;
+    for (size_t pos = 0; pos < raw.size();) {
+        const size_t len = std::min<size_t>(65535, raw.size() - pos);
+        z.push_back(pos + len == raw.size() ? 1 : 0);  // BFINAL, BTYPE = 00 (stored)
+        z.push_back((uint8_t)(len & 0xff));
+        z.push_back((uint8_t)(len >> 8));
+        z.push_back((uint8_t)(~len & 0xff));
+        z.push_back((uint8_t)((~len >> 8) & 0xff));
+        z.insert(z.end(), raw.begin() + (long)pos, raw.begin() + (long)(pos + len));
+        for (size_t i = pos; i < pos + len; ++i) {
+            a = (a + raw[i]) % 65521u;
+            b = (b + a) % 65521u;
+        }
+        pos += len;
+    }
+    be32(z, (b << 16) | a);
+    std::vector<uint8_t> file = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+    std::vector<uint8_t> ihdr;
+    be32(ihdr, (uint32_t)cols);
+    be32(ihdr, (uint32_t)rows);
+    const uint8_t rest[5] = {8, 0, 0, 0, 0};  // bit depth 8, colour type 0 (grayscale), deflate, adaptive filtering, no interlace
+    ihdr.insert(ihdr.end(), rest, rest + 5);
+    chunk(file, "IHDR", ihdr);
+    chunk(file, "IDAT", z);
+    chunk(file, "IEND", std::vector<uint8_t>());
+    std::FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const bool ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
+    return (std::fclose(f) == 0) && ok;
+}
+template <typename ImgT>
+inline bool imwrite_gray8(const std::string& path, const ImgT& img)
+{
+    return write_png_gray8(path, dsi::image_data<uint8_t>(const_cast<ImgT&>(img)), img.rows, img.cols);
 }
 
 // The point cloud of MapperEMVS::getPointcloud (mapper_emvs_stereo.cpp:440-480): pcl::PointXYZI's four fields, and a
@@ -601,6 +676,86 @@ public:
     void setToLocalFocusOf(const Grid3D& grid2, int focus_method) { dsi::check(dsi_grid_local_focus(h_, grid2.h_, focus_method)); }
     // this = op(a, b) in one pass: resetGrid(); addTwoGrids(a); <op>TwoGrids(b) (not in the reference)
     void setToFusionOf(const Grid3D& a, const Grid3D& b, int op) { dsi::check(dsi_grid_fuse2_into(h_, a.h_, b.h_, op)); }
+    // the voxel-wise members that are no camera fusion (cartesian3dgrid.h:95-109,166-184; arithmetic: DESIGN.md 7d)
+    void subtractTwoGrids(const Grid3D& grid2) { dsi::check(dsi_grid_binary_op(h_, grid2.h_, DSI_GRID_OP_SUBTRACT)); }
+    // only the reference's default eps is offered: any other value throws DSI_ERR_INVALID
+    void ratioTwoGrids(const Grid3D& grid2, const float eps = 1e-1)
+    {
+        if (eps != 1e-1f) throw dsi::Error(DSI_ERR_INVALID, "ratioTwoGrids: only the default eps = 1e-1 is supported");
+        dsi::check(dsi_grid_binary_op(h_, grid2.h_, DSI_GRID_OP_RATIO));
+    }
+    void quadraticMeanTwoGrids(const Grid3D& grid2) { dsi::check(dsi_grid_binary_op(h_, grid2.h_, DSI_GRID_OP_QUADRATIC_MEAN)); }
+    void cubicMeanTwoGrids(const Grid3D& grid2) { dsi::check(dsi_grid_binary_op(h_, grid2.h_, DSI_GRID_OP_CUBIC_MEAN)); }
+
+    // single voxels (cartesian3dgrid.h:40-58); an index outside the grid throws DSI_ERR_INVALID where .at() throws
+    float getGridValueAt(const unsigned int ix, const unsigned int iy, const unsigned int iz) const
+    {
+        int nx, ny, nz;
+        getDimensions(&nx, &ny, &nz);
+        if (ix >= (unsigned)nx || iy >= (unsigned)ny || iz >= (unsigned)nz) throw dsi::Error(DSI_ERR_INVALID, "getGridValueAt: outside the grid");
+        return getGridValueAt64((uint64_t)ix + (uint64_t)nx * ((uint64_t)iy + (uint64_t)ny * iz));
+    }
+    float getGridValueAt(const unsigned int p) const { return getGridValueAt64(p); }
+    void accumulateGridValueAt(const unsigned int p, const float fval) { dsi::check(dsi_grid_accumulate_value_at(h_, p, fval)); }
+    void setGridValueAt(const unsigned int p, const float fval) { dsi::check(dsi_grid_set_value_at(h_, p, fval)); }
+
+    // void accumulateZSliceAt(const unsigned int iz, const cv::Mat& img) (cartesian3dgrid.h:195-204): a float image no larger
+    // than the plane, of any type dsi::image_data reads (members rows, cols)
+    template <typename Img>
+    void accumulateZSliceAt(const unsigned int iz, const Img& img)
+    {
+        dsi::check(dsi_grid_accumulate_z_slice(h_, iz, dsi::image_data<float>(const_cast<Img&>(img)), img.rows, img.cols));
+    }
+    // cv::Mat getSlice(sliceIdx, dimIdx) const (cartesian3dgrid.cpp:72-113): getSlice<cv::Mat>(...) for the reference's type
+    template <typename Img = dsi::Image<float>>
+    Img getSlice(const unsigned int sliceIdx, const unsigned int dimIdx) const
+    {
+        int nx, ny, nz;
+        getDimensions(&nx, &ny, &nz);
+        if (dimIdx > 2) throw dsi::Error(DSI_ERR_INVALID, "dimIdx should be 0, 1 or 2");
+        Img slice;
+        float* px = dsi::image_create<float>(slice, dimIdx == 1 ? nx : ny, dimIdx == 2 ? nx : nz);
+        dsi::check(dsi_grid_get_slice(h_, sliceIdx, dimIdx, px));
+        return slice;
+    }
+    // cartesian3dgrid.cpp:177-188
+    void getMinMax(float* min_val, float* max_val, unsigned long* min_pos = NULL, unsigned long* max_pos = NULL) const
+    {
+        uint64_t lo = 0, hi = 0;
+        dsi::check(dsi_grid_min_max(h_, min_val, max_val, &lo, &hi));
+        if (min_pos != NULL) *min_pos = (unsigned long)lo;
+        if (max_pos != NULL) *max_pos = (unsigned long)hi;
+    }
+    // every slice of one orientation as 8-bit images, slice after slice (what imwriteSlices computes before it writes)
+    std::vector<uint8_t> slicesU8(const unsigned int dimIdx, bool normalize_by_minmax = true) const
+    {
+        int nx, ny, nz;
+        getDimensions(&nx, &ny, &nz);
+        std::vector<uint8_t> v((size_t)nx * ny * nz);
+        dsi::check(dsi_grid_slices_u8(h_, dimIdx, normalize_by_minmax ? 1 : 0, v.data()));
+        return v;
+    }
+    // cartesian3dgrid_IO.cpp:39-76: prefix + three-digit zero-padded slice index + ".png", 8-bit grayscale, through the
+    // dsi::imwrite_gray8 customisation point (imwriteSlices<cv::Mat> + an overload for cv::Mat routes to cv::imwrite)
+    template <typename Img = dsi::Image<uint8_t>>
+    void imwriteSlices(const char prefix[], const unsigned int dimIdx, bool normalize_by_minmax = true) const
+    {
+        int nx, ny, nz;
+        getDimensions(&nx, &ny, &nz);
+        const std::vector<uint8_t> all = slicesU8(dimIdx, normalize_by_minmax);
+        const int n_slices = dimIdx == 0 ? nx : (dimIdx == 1 ? ny : nz);
+        const int rows = dimIdx == 1 ? nx : ny, cols = dimIdx == 2 ? nx : nz;
+        for (int i = 0; i < n_slices; ++i) {
+            Img slice_u;
+            uint8_t* px = dsi::image_create<uint8_t>(slice_u, rows, cols);
+            std::copy(all.begin() + (size_t)i * rows * cols, all.begin() + (size_t)(i + 1) * rows * cols, px);
+            char num[16];
+            std::snprintf(num, sizeof num, "%03d", i);  // std::setfill('0') << std::setw(3)
+            using dsi::imwrite_gray8;
+            if (!imwrite_gray8(std::string(prefix) + num + ".png", slice_u))
+                throw dsi::Error(DSI_ERR_INVALID, std::string("imwriteSlices: cannot write ") + prefix + num + ".png");
+        }
+    }
     // cartesian3dgrid.cpp:164-174
     double computeMeanSquare() const
     {
@@ -652,6 +807,12 @@ private:
         float* val = dsi::image_create<float>(*confidence, ny, nx);
         uint8_t* pos = dsi::image_create<uint8_t>(*depth_cell_indices, ny, nx);
         dsi::check(dsi_grid_collapse_focus(h_, method, half_patchsize, val, pos));
+    }
+    float getGridValueAt64(uint64_t p) const
+    {
+        float v = 0.f;
+        dsi::check(dsi_grid_value_at(h_, p, &v));
+        return v;
     }
     dsi_grid_t* h_ = nullptr;
     bool owned_ = false;
