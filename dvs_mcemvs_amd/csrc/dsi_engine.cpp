@@ -175,6 +175,10 @@ struct dsi_context {
     // Grid3D min/max, slices and slice images: partial extremes and per-slice scales; device side of the host-output forms
     DevBuf<unsigned long long> grid_words;
     DevBuf<uint8_t> grid_bytes;
+    // the run's pictures (dsi_event_image*, dsi_depth_images, dsi_mapper_depth_images): counts and extremes; uploaded inputs,
+    // the colour table and the device side of the host-output forms
+    DevBuf<uint32_t> img_words;
+    DevBuf<uint8_t> img_bytes;
     // grids, mappers and batches created from this context and not yet destroyed: each holds a pointer to it, so the
     // context refuses to go while any is alive (destroying it first was a use-after-free in their destroy)
     std::atomic<int> children{0};
@@ -986,6 +990,8 @@ int dsi_context_destroy(dsi_context_t* ctx)
     ctx->focus_volume.release();
     ctx->grid_words.release();
     ctx->grid_bytes.release();
+    ctx->img_words.release();
+    ctx->img_bytes.release();
     ctx->pc.release();
     for (hipEvent_t ev : ctx->marks) (void)hipEventDestroy(ev);
     ctx->marks.clear();
@@ -3213,6 +3219,229 @@ int dsi_mapper_get_pointcloud(dsi_mapper_t* m, const float* depth_host, const ui
         HIP_TRY(hipStreamSynchronize(st));
     }
     return DSI_OK;
+}
+
+// ---- the run's pictures: accumulateEvents and the two images of saveDepthMaps ----
+
+static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+static int check_event_image_args(int width, int height, int use_polarity, const void* polarity, size_t n)
+{
+    REQUIRE(width >= 1 && height >= 1, DSI_ERR_INVALID, "the sensor must be at least 1 x 1 (got %d x %d)", width, height);
+    REQUIRE((size_t)width * height <= ((size_t)1 << 30), DSI_ERR_INVALID, "at most 2^30 pixels");
+    REQUIRE(n < ((size_t)1 << 31), DSI_ERR_INVALID, "at most 2^31-1 events (the per-pixel counters are int32)");
+    REQUIRE(!use_polarity || polarity || n == 0, DSI_ERR_INVALID, "use_polarity needs the polarity bytes");
+    return DSI_OK;
+}
+
+// x_dev / y_dev: the events on the device (16-byte aligned); pol_dev: n bytes (8-byte aligned; not read when use_polarity == 0);
+// out_dev: 4-byte aligned
+static int event_image_device(dsi_context* ctx, const uint16_t* x_dev, const uint16_t* y_dev, uint8_t* pol_dev, size_t n, int width,
+                              int height, int use_polarity, uint8_t* out_dev, uint32_t* n_dropped_dev)
+{
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx->img_words.reserve(dsi::event_image_scratch_words(width, height)));
+    HIP_TRY(dsi::launch_event_image(st, x_dev, y_dev, use_polarity ? pol_dev : nullptr, n, width, height, use_polarity,
+                                    ctx->img_words.p, out_dev));
+    if (n_dropped_dev)
+        HIP_TRY(hipMemcpyAsync(n_dropped_dev, ctx->img_words.p + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    return DSI_OK;
+}
+
+static int event_image_finish(dsi_context* ctx, const uint8_t* out_dev, size_t npix, uint8_t* out_host, size_t* n_dropped)
+{
+    uint32_t dropped = 0;
+    HIP_TRY(hipMemcpyAsync(out_host, out_dev, npix, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&dropped, ctx->img_words.p + 2, sizeof dropped, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (n_dropped) *n_dropped = dropped;
+    return DSI_OK;
+}
+
+// uploads the host events into ctx->img_bytes: x | y | polarity | `extra` bytes (256-byte aligned parts)
+static int event_image_upload(dsi_context* ctx, const uint16_t* x, const uint16_t* y, const uint8_t* polarity, size_t n,
+                              int use_polarity, size_t extra, uint16_t** x_dev, uint16_t** y_dev, uint8_t** pol_dev, uint8_t** extra_dev)
+{
+    const size_t ev = up256(std::max<size_t>(n, 1) * sizeof(uint16_t)), pb = up256(std::max<size_t>(n, 1));
+    HIP_TRY(ctx->img_bytes.reserve(2 * ev + pb + extra));
+    uint8_t* base = ctx->img_bytes.p;
+    *x_dev = reinterpret_cast<uint16_t*>(base);
+    *y_dev = reinterpret_cast<uint16_t*>(base + ev);
+    *pol_dev = base + 2 * ev;
+    *extra_dev = base + 2 * ev + pb;
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(*x_dev, x, n * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(*y_dev, y, n * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
+        if (use_polarity) HIP_TRY(hipMemcpyAsync(*pol_dev, polarity, n, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return DSI_OK;
+}
+
+int dsi_event_image_dev(dsi_context_t* ctx, const uint16_t* x, const uint16_t* y, const uint8_t* polarity, size_t n, int width,
+                        int height, int use_polarity, uint8_t* out_u8_dev, uint32_t* n_dropped_dev)
+{
+    REQUIRE(ctx && out_u8_dev, DSI_ERR_INVALID, "null argument");
+    REQUIRE(n == 0 || (x && y), DSI_ERR_INVALID, "null event arrays");
+    if (int rc = check_event_image_args(width, height, use_polarity, polarity, n)) return rc;
+    REQUIRE((reinterpret_cast<uintptr_t>(out_u8_dev) & 3u) == 0, DSI_ERR_INVALID, "the device output must be 4-byte aligned");
+    if (int rc = set_device(ctx)) return rc;
+    uint16_t *xd, *yd;
+    uint8_t *pd, *extra;
+    if (int rc = event_image_upload(ctx, x, y, polarity, n, use_polarity, 0, &xd, &yd, &pd, &extra)) return rc;
+    return event_image_device(ctx, xd, yd, pd, n, width, height, use_polarity, out_u8_dev, n_dropped_dev);
+}
+
+int dsi_event_image(dsi_context_t* ctx, const uint16_t* x, const uint16_t* y, const uint8_t* polarity, size_t n, int width,
+                    int height, int use_polarity, uint8_t* out_u8_host, size_t* n_dropped)
+{
+    REQUIRE(ctx && out_u8_host, DSI_ERR_INVALID, "null argument");
+    REQUIRE(n == 0 || (x && y), DSI_ERR_INVALID, "null event arrays");
+    if (int rc = check_event_image_args(width, height, use_polarity, polarity, n)) return rc;
+    if (int rc = set_device(ctx)) return rc;
+    const size_t npix = (size_t)width * height;
+    uint16_t *xd, *yd;
+    uint8_t *pd, *out;
+    if (int rc = event_image_upload(ctx, x, y, polarity, n, use_polarity, npix, &xd, &yd, &pd, &out)) return rc;
+    if (int rc = event_image_device(ctx, xd, yd, pd, n, width, height, use_polarity, out, nullptr)) return rc;
+    return event_image_finish(ctx, out, npix, out_u8_host, n_dropped);
+}
+
+// the batch's x / y stay where they are; only the polarity bytes travel: ctx->img_bytes = polarity | `extra`
+static int batch_event_image_prepare(const dsi_batch_t* batch, const uint8_t* polarity_host, int use_polarity, size_t extra,
+                                     uint8_t** pol_dev, uint8_t** extra_dev)
+{
+    dsi_context* ctx = batch->ctx;
+    const size_t n = batch->n_events, pb = up256(std::max<size_t>(n, 1));
+    HIP_TRY(ctx->img_bytes.reserve(pb + extra));
+    *pol_dev = ctx->img_bytes.p;
+    *extra_dev = ctx->img_bytes.p + pb;
+    if (batch->ready) HIP_TRY(hipStreamWaitEvent(ctx->stream, batch->ready, 0));  // uploaded on the copy stream
+    if (n && use_polarity) HIP_TRY(hipMemcpyAsync(*pol_dev, polarity_host, n, hipMemcpyHostToDevice, ctx->stream));
+    return DSI_OK;
+}
+
+int dsi_batch_event_image_dev(const dsi_batch_t* batch, const uint8_t* polarity_host, int width, int height, int use_polarity,
+                              uint8_t* out_u8_dev, uint32_t* n_dropped_dev)
+{
+    REQUIRE(batch && out_u8_dev, DSI_ERR_INVALID, "null argument");
+    if (int rc = check_event_image_args(width, height, use_polarity, polarity_host, batch->n_events)) return rc;
+    REQUIRE((reinterpret_cast<uintptr_t>(out_u8_dev) & 3u) == 0, DSI_ERR_INVALID, "the device output must be 4-byte aligned");
+    if (int rc = set_device(batch->ctx)) return rc;
+    uint8_t *pd, *extra;
+    if (int rc = batch_event_image_prepare(batch, polarity_host, use_polarity, 0, &pd, &extra)) return rc;
+    return event_image_device(batch->ctx, batch->x, batch->y, pd, batch->n_events, width, height, use_polarity, out_u8_dev,
+                              n_dropped_dev);
+}
+
+int dsi_batch_event_image(const dsi_batch_t* batch, const uint8_t* polarity_host, int width, int height, int use_polarity,
+                          uint8_t* out_u8_host, size_t* n_dropped)
+{
+    REQUIRE(batch && out_u8_host, DSI_ERR_INVALID, "null argument");
+    if (int rc = check_event_image_args(width, height, use_polarity, polarity_host, batch->n_events)) return rc;
+    if (int rc = set_device(batch->ctx)) return rc;
+    const size_t npix = (size_t)width * height;
+    uint8_t *pd, *out;
+    if (int rc = batch_event_image_prepare(batch, polarity_host, use_polarity, npix, &pd, &out)) return rc;
+    if (int rc = event_image_device(batch->ctx, batch->x, batch->y, pd, batch->n_events, width, height, use_polarity, out, nullptr))
+        return rc;
+    return event_image_finish(batch->ctx, out, npix, out_u8_host, n_dropped);
+}
+
+static int check_depth_image_range(float min_depth, float max_depth)
+{
+    REQUIRE(std::isfinite(min_depth) && std::isfinite(max_depth) && min_depth > 0.f && max_depth > 0.f && min_depth != max_depth,
+            DSI_ERR_INVALID, "min_depth and max_depth must be finite, > 0 and different (got %g, %g)", (double)min_depth,
+            (double)max_depth);
+    return DSI_OK;
+}
+
+// ctx->img_bytes: colour table (1 KiB) | `inputs` bytes for the caller | conf_negated | inv_depth_bgr; runs both kernels on the
+// device maps given and brings the images home
+static int depth_images_run(dsi_context* ctx, const float* host_maps_depth, const float* host_maps_conf, const uint8_t* host_maps_mask,
+                            const float* depth_dev, const float* conf_dev, const uint8_t* mask_dev, int rows, int cols,
+                            float min_depth, float max_depth, const uint8_t* lut_bgr, uint8_t* conf_negated_host,
+                            uint8_t* inv_depth_bgr_host)
+{
+    hipStream_t st = ctx->stream;
+    const size_t npix = (size_t)rows * cols;
+    const bool upload = host_maps_depth || host_maps_conf || host_maps_mask;
+    const size_t fb = up256(npix * sizeof(float)), mb = up256(npix);
+    const size_t inputs = upload ? 2 * fb + mb : 0;
+    HIP_TRY(ctx->img_bytes.reserve(1024 + inputs + mb + up256(3 * npix)));
+    HIP_TRY(ctx->img_words.reserve(dsi::kEventImageHeadWords));
+    uint8_t* base = ctx->img_bytes.p;
+    uint8_t* lut_dev = base;
+    uint8_t* neg_dev = base + 1024 + inputs;
+    uint8_t* bgr_dev = neg_dev + mb;
+    if (upload) {
+        float* d = reinterpret_cast<float*>(base + 1024);
+        float* c = reinterpret_cast<float*>(base + 1024 + fb);
+        uint8_t* m = base + 1024 + 2 * fb;
+        if (inv_depth_bgr_host) {
+            HIP_TRY(hipMemcpyAsync(d, host_maps_depth, npix * sizeof(float), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(m, host_maps_mask, npix, hipMemcpyHostToDevice, st));
+        }
+        if (conf_negated_host) HIP_TRY(hipMemcpyAsync(c, host_maps_conf, npix * sizeof(float), hipMemcpyHostToDevice, st));
+        depth_dev = d;
+        conf_dev = c;
+        mask_dev = m;
+    }
+    uint8_t jet[768];
+    if (inv_depth_bgr_host) {
+        if (!lut_bgr) {
+            dsi::default_jet_lut(jet);
+            lut_bgr = jet;
+        }
+        HIP_TRY(hipMemcpyAsync(lut_dev, lut_bgr, 768, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(dsi::launch_depth_images(st, depth_dev, conf_dev, mask_dev, rows, cols, min_depth, max_depth, lut_dev, ctx->img_words.p,
+                                     conf_negated_host ? neg_dev : nullptr, inv_depth_bgr_host ? bgr_dev : nullptr));
+    if (conf_negated_host) HIP_TRY(hipMemcpyAsync(conf_negated_host, neg_dev, npix, hipMemcpyDeviceToHost, st));
+    if (inv_depth_bgr_host) HIP_TRY(hipMemcpyAsync(inv_depth_bgr_host, bgr_dev, 3 * npix, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));  // (also: `jet` and the caller's arrays are free again)
+    return DSI_OK;
+}
+
+int dsi_default_jet_lut(uint8_t* lut_bgr)
+{
+    REQUIRE(lut_bgr, DSI_ERR_INVALID, "null argument");
+    dsi::default_jet_lut(lut_bgr);
+    return DSI_OK;
+}
+
+int dsi_depth_images(dsi_context_t* ctx, const float* depth_host, const float* conf_host, const uint8_t* mask_host, int rows,
+                     int cols, float min_depth, float max_depth, const uint8_t* lut_bgr, uint8_t* conf_negated_host,
+                     uint8_t* inv_depth_bgr_host)
+{
+    REQUIRE(ctx, DSI_ERR_INVALID, "null argument");
+    REQUIRE(rows >= 1 && cols >= 1, DSI_ERR_INVALID, "the maps must be at least 1 x 1 (got %d x %d)", rows, cols);
+    REQUIRE((size_t)rows * cols <= ((size_t)1 << 29), DSI_ERR_INVALID, "at most 2^29 pixels");
+    REQUIRE(!conf_negated_host || conf_host, DSI_ERR_INVALID, "the negated confidence image needs conf_host");
+    REQUIRE(!inv_depth_bgr_host || (depth_host && mask_host), DSI_ERR_INVALID,
+            "the inverse-depth image needs depth_host and mask_host");
+    if (inv_depth_bgr_host)
+        if (int rc = check_depth_image_range(min_depth, max_depth)) return rc;
+    if (!conf_negated_host && !inv_depth_bgr_host) return DSI_OK;
+    if (int rc = set_device(ctx)) return rc;
+    return depth_images_run(ctx, depth_host, conf_host, mask_host, nullptr, nullptr, nullptr, rows, cols, min_depth, max_depth,
+                            lut_bgr, conf_negated_host, inv_depth_bgr_host);
+}
+
+int dsi_mapper_depth_images(dsi_mapper_t* m, float min_depth, float max_depth, const uint8_t* lut_bgr, uint8_t* conf_negated_host,
+                            uint8_t* inv_depth_bgr_host)
+{
+    REQUIRE(m, DSI_ERR_INVALID, "null argument");
+    REQUIRE(m->filtered_valid, DSI_ERR_INVALID,
+            "no filtered depth map on the device: call dsi_mapper_filter_depth_map or dsi_mapper_get_depth_map_from_dsi "
+            "after the depth map was computed, or pass the maps to dsi_depth_images");
+    if (inv_depth_bgr_host)
+        if (int rc = check_depth_image_range(min_depth, max_depth)) return rc;
+    if (!conf_negated_host && !inv_depth_bgr_host) return DSI_OK;
+    if (int rc = set_device(m->ctx)) return rc;
+    if (int rc = depth_buffers_acquire(m)) return rc;
+    // m->conf is the confidence map as the filter call returned it: element (0,0) = max_confidence, nothing else touched
+    return depth_images_run(m->ctx, nullptr, nullptr, nullptr, m->depth.p, m->conf.p, m->mask.p, m->geom.ny, m->geom.nx, min_depth,
+                            max_depth, lut_bgr, conf_negated_host, inv_depth_bgr_host);
 }
 
 int dsi_radius_outlier_removal(dsi_context_t* ctx, const float* xyz_host, size_t stride_floats, size_t n, float radius,

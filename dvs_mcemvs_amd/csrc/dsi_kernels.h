@@ -350,4 +350,22 @@ hipError_t launch_grid_accumulate_z_slice(hipStream_t s, float* vol, int nx, int
 hipError_t launch_grid_slices_u8(hipStream_t s, const float* vol, int nx, int ny, int nz, int dim, int normalize_by_minmax,
                                  unsigned long long* words, uint8_t* out);
 
+// ---- the run's pictures: accumulateEvents (utils.cpp:184-216) and the two images of saveDepthMaps (utils.cpp:55-58, 82-93;
+// DESIGN.md 7e) ----
+// scratch: event_image_scratch_words(width, height) 32-bit words -- [0] ~key of the minimum, [1] key of the maximum, [2] events
+// outside the sensor, then the height x width int32 counts; zeroed by the launch.  x, y: 16-byte aligned, pol: 8-byte aligned
+// (NULL when use_polarity == 0), out: height * width bytes, 4-byte aligned.  The signed count equals the reference's fp32
+// += +-1 while no pixel holds more than 2^24 events; the callers keep n <= 2^31 - 1, which int32 counters hold.
+constexpr size_t kEventImageHeadWords = 4;
+size_t event_image_scratch_words(int width, int height);
+hipError_t launch_event_image(hipStream_t s, const uint16_t* x, const uint16_t* y, const uint8_t* pol, size_t n, int width,
+                              int height, int use_polarity, uint32_t* scratch, uint8_t* out);
+// the engine's default colour table (256 x BGR; host): a piecewise-linear jet, NOT OpenCV's COLORMAP_JET table
+void default_jet_lut(uint8_t* lut_bgr);
+// mm: 2 words of scratch; lut_dev: 768 bytes; conf_negated (rows * cols bytes) / inv_depth_bgr (rows * cols * 3 bytes) may be
+// NULL (conf / depth, mask, lut_dev are then not read)
+hipError_t launch_depth_images(hipStream_t s, const float* depth, const float* conf, const uint8_t* mask, int rows, int cols,
+                               float min_depth, float max_depth, const uint8_t* lut_dev, uint32_t* mm, uint8_t* conf_negated,
+                               uint8_t* inv_depth_bgr);
+
 }  // namespace dsi

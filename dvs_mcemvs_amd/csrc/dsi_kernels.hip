@@ -7722,4 +7722,257 @@ hipError_t launch_grid_slices_u8(hipStream_t s, const float* vol, int nx, int ny
     return hipExtGetLastError();
 }
 
+
+// ------------------------------------------------ the run's pictures ---
+// accumulateEvents (utils.cpp:184-216) and the two images of saveDepthMaps (utils.cpp:55-58, 82-93).
+namespace {
+
+// monotone int -> uint, so that a zeroed word is the identity of atomicMax for the maximum (key) and the minimum (~key)
+__device__ __forceinline__ uint32_t int_key(int c) { return (uint32_t)c ^ 0x80000000u; }
+__device__ __forceinline__ int key_int(uint32_t k) { return (int)(k ^ 0x80000000u); }
+
+__device__ __forceinline__ void event_vote(int* __restrict__ count, uint32_t ex, uint32_t ey, int d, int width, int height,
+                                           uint32_t& dropped)
+{
+    if (ex < (uint32_t)width && ey < (uint32_t)height)
+        (void)__hip_atomic_fetch_add(count + (size_t)ey * width + ex, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else
+        ++dropped;
+}
+
+// Per-pixel event counts: a thread takes 8 consecutive events per step -- one 16-byte load of x, one of y, one 8-byte load
+// of the polarity bytes -- and adds +-1 (POL) or +1 to count[y][x] with atomics whose result nobody reads.  x, y 16-byte
+// aligned, pol 8-byte aligned.  scratch[2] += events outside the sensor.
+template <bool POL>
+__global__ __launch_bounds__(256) void k_event_image_count(const uint16_t* __restrict__ x, const uint16_t* __restrict__ y,
+                                                           const uint8_t* __restrict__ pol, size_t n, int width, int height,
+                                                           int* __restrict__ count, uint32_t* __restrict__ scratch)
+{
+    uint32_t dropped = 0;
+    const size_t n8 = n / 8;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
+        const uint4 vx = reinterpret_cast<const uint4*>(x)[i];
+        const uint4 vy = reinterpret_cast<const uint4*>(y)[i];
+        uint2 vp = make_uint2(0u, 0u);
+        if (POL) vp = reinterpret_cast<const uint2*>(pol)[i];
+        const uint32_t wx[4] = {vx.x, vx.y, vx.z, vx.w}, wy[4] = {vy.x, vy.y, vy.z, vy.w}, wp[2] = {vp.x, vp.y};
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t ex = (wx[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+            const uint32_t ey = (wy[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+            const int d = POL ? (((wp[k >> 2] >> (8 * (k & 3))) & 0xffu) ? 1 : -1) : 1;
+            event_vote(count, ex, ey, d, width, height, dropped);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {
+        const size_t i = n8 * 8 + threadIdx.x;
+        event_vote(count, x[i], y[i], POL ? (pol[i] ? 1 : -1) : 1, width, height, dropped);
+    }
+    for (int off = 32; off > 0; off >>= 1) dropped += __shfl_down(dropped, off, 64);
+    if ((threadIdx.x & 63) == 0 && dropped) atomicAdd(&scratch[2], dropped);
+}
+
+// what the image is made of: the signed count (POL), or the count modulo 256 (the reference's uchar += 1 wraps)
+template <bool POL>
+__device__ __forceinline__ int event_value(int c) { return POL ? c : (c & 255); }
+
+// scratch[0] = max of ~key (the minimum), scratch[1] = max of key (the maximum); both zero before
+template <bool POL>
+__global__ __launch_bounds__(256) void k_event_image_minmax(const int* __restrict__ count, int npix, uint32_t* __restrict__ scratch)
+{
+    uint32_t lo = 0u, hi = 0u;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
+        const uint32_t k = int_key(event_value<POL>(count[i]));
+        lo = max(lo, ~k);
+        hi = max(hi, k);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        lo = max(lo, (uint32_t)__shfl_down((int)lo, off, 64));
+        hi = max(hi, (uint32_t)__shfl_down((int)hi, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicMax(&scratch[0], lo);
+        atomicMax(&scratch[1], hi);
+    }
+}
+
+// POL: c * (float)(128 / half) + 128, half = max(|min|, |max|) in double, 128 everywhere when half == 0 (utils.cpp:196-206).
+// Otherwise cv::normalize(NORM_MINMAX, 0, 255) of the wrapped counts with k_conf8's scale / shift.  Four pixels per thread,
+// one word per store (out is 4-byte aligned); the last npix % 4 pixels as bytes.
+template <bool POL>
+__global__ __launch_bounds__(256) void k_event_image_u8(const int* __restrict__ count, int npix, const uint32_t* __restrict__ scratch,
+                                                        uint8_t* __restrict__ out)
+{
+    const int i4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i4 >= npix) return;
+    const double smin = (double)key_int(~scratch[0]), smax = (double)key_int(scratch[1]);
+    float a, b;
+    bool flat = false;
+    if (POL) {
+        const double half = fmax(fabs(smin), fabs(smax));
+        flat = !(half > 0.0);
+        a = flat ? 0.f : (float)(128.0 / half);
+        b = 128.f;
+    } else {
+        const double range = smax - smin;
+        const double scale = 255.0 * (range > 2.220446049250313e-16 ? 1. / range : 0.);
+        a = (float)scale;
+        b = (float)(0.0 - smin * scale);
+    }
+    uint32_t pk = 0;
+    const int m = npix - i4 < 4 ? npix - i4 : 4;
+    for (int k = 0; k < m; ++k) {
+        const float v = (float)event_value<POL>(count[i4 + k]) * a + b;
+        pk |= (uint32_t)(flat ? (uint8_t)128 : saturate_u8(v)) << (8 * k);
+    }
+    if (m == 4) {
+        reinterpret_cast<uint32_t*>(out)[i4 >> 2] = pk;
+    } else {
+        for (int k = 0; k < m; ++k) out[i4 + k] = (uint8_t)(pk >> (8 * k));
+    }
+}
+
+// extremes of the confidence map as float keys: mm[0] = max of ~key (the minimum), mm[1] = max of key; both zero before
+__global__ __launch_bounds__(256) void k_image_conf_minmax(const float* __restrict__ conf, int n, uint32_t* __restrict__ mm)
+{
+    uint32_t lo = 0u, hi = 0u;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const uint32_t k = float_key(conf[i]);
+        lo = max(lo, ~k);
+        hi = max(hi, k);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        lo = max(lo, (uint32_t)__shfl_down((int)lo, off, 64));
+        hi = max(hi, (uint32_t)__shfl_down((int)hi, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicMax(&mm[0], lo);
+        atomicMax(&mm[1], hi);
+    }
+}
+
+// utils.cpp:55-58: 255 - normalize(conf, 0, 255, NORM_MINMAX) written as 8 bit (k_conf8's scale / shift, no reset of (0,0))
+__global__ __launch_bounds__(256) void k_conf_negated_u8(const float* __restrict__ conf, int n, const uint32_t* __restrict__ mm,
+                                                         uint8_t* __restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double smin = (double)key_float(~mm[0]), smax = (double)key_float(mm[1]);
+    const double range = smax - smin;
+    const double scale = 255.0 * (range > 2.220446049250313e-16 ? 1. / range : 0.);
+    const double shift = 0.0 - smin * scale;
+    const float a = (float)scale, b = (float)shift;
+    const float nrm = conf[i] * a + b;
+    out[i] = saturate_u8(255.f - nrm);
+}
+
+// colour of one pixel before the dilation (utils.cpp:83-89): lut[saturate_u8((1 / depth) * a + b)] where mask > 0, else black
+__device__ __forceinline__ uint32_t inv_depth_bgr(const float* __restrict__ depth, const uint8_t* __restrict__ mask,
+                                                  const uint8_t* __restrict__ lut, int p, float a, float b)
+{
+    if (!mask[p]) return 0u;
+    const float inv = 1.0f / depth[p];
+    const float v = inv * a + b;
+    const int i = (v == v) ? (int)saturate_u8(v) : 0;
+    return (uint32_t)lut[3 * i] | ((uint32_t)lut[3 * i + 1] << 8) | ((uint32_t)lut[3 * i + 2] << 16);
+}
+
+__device__ __forceinline__ uint32_t max_bgr(uint32_t p, uint32_t q)
+{
+    return max(p & 0xffu, q & 0xffu) | max(p & 0xff00u, q & 0xff00u) | max(p & 0xff0000u, q & 0xff0000u);
+}
+
+// utils.cpp:82-93: the coloured inverse-depth image dilated by the 3 x 3 cross, per channel; neighbours outside the image do
+// not contribute.  One thread per pixel; it recomputes its four neighbours' colours.
+__global__ __launch_bounds__(256) void k_inv_depth_colored_dilated(const float* __restrict__ depth, const uint8_t* __restrict__ mask,
+                                                                   const uint8_t* __restrict__ lut, int rows, int cols, float a,
+                                                                   float b, uint8_t* __restrict__ out)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= rows * cols) return;
+    const int r = p / cols, c = p - r * cols;
+    uint32_t v = inv_depth_bgr(depth, mask, lut, p, a, b);
+    if (r > 0) v = max_bgr(v, inv_depth_bgr(depth, mask, lut, p - cols, a, b));
+    if (r + 1 < rows) v = max_bgr(v, inv_depth_bgr(depth, mask, lut, p + cols, a, b));
+    if (c > 0) v = max_bgr(v, inv_depth_bgr(depth, mask, lut, p - 1, a, b));
+    if (c + 1 < cols) v = max_bgr(v, inv_depth_bgr(depth, mask, lut, p + 1, a, b));
+    out[3 * (size_t)p] = (uint8_t)v;
+    out[3 * (size_t)p + 1] = (uint8_t)(v >> 8);
+    out[3 * (size_t)p + 2] = (uint8_t)(v >> 16);
+}
+
+}  // namespace
+
+size_t event_image_scratch_words(int width, int height) { return kEventImageHeadWords + (size_t)width * height; }
+
+hipError_t launch_event_image(hipStream_t s, const uint16_t* x, const uint16_t* y, const uint8_t* pol, size_t n, int width,
+                              int height, int use_polarity, uint32_t* scratch, uint8_t* out)
+{
+    const size_t npix_z = (size_t)width * height;
+    if (width < 1 || height < 1 || npix_z > 0x7fffffffull || (use_polarity && n && !pol)) return hipErrorInvalidValue;
+    const int npix = (int)npix_z;
+    int* count = reinterpret_cast<int*>(scratch + kEventImageHeadWords);
+    hipError_t e = hipMemsetAsync(scratch, 0, event_image_scratch_words(width, height) * sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    if (n) {
+        const dim3 grid(grid_for(n / 8 + 1, 256, 4096)), block(256);
+        if (use_polarity)
+            hipLaunchKernelGGL(k_event_image_count<true>, grid, block, 0, s, x, y, pol, n, width, height, count, scratch);
+        else
+            hipLaunchKernelGGL(k_event_image_count<false>, grid, block, 0, s, x, y, pol, n, width, height, count, scratch);
+        if ((e = hipExtGetLastError()) != hipSuccess) return e;
+    }
+    const dim3 rgrid(grid_for(npix_z, 256, 256)), ugrid((unsigned)((npix_z + 1023) / 1024)), block(256);
+    if (use_polarity) {
+        hipLaunchKernelGGL(k_event_image_minmax<true>, rgrid, block, 0, s, count, npix, scratch);
+        hipLaunchKernelGGL(k_event_image_u8<true>, ugrid, block, 0, s, count, npix, scratch, out);
+    } else {
+        hipLaunchKernelGGL(k_event_image_minmax<false>, rgrid, block, 0, s, count, npix, scratch);
+        hipLaunchKernelGGL(k_event_image_u8<false>, ugrid, block, 0, s, count, npix, scratch, out);
+    }
+    return hipExtGetLastError();
+}
+
+void default_jet_lut(uint8_t* lut_bgr)
+{
+    for (int i = 0; i < 256; ++i) {
+        const double t = (double)i / 255.0;
+        const double ch[3] = {1.5 - std::fabs(4.0 * t - 1.0), 1.5 - std::fabs(4.0 * t - 2.0), 1.5 - std::fabs(4.0 * t - 3.0)};  // b, g, r
+        for (int k = 0; k < 3; ++k) {
+            const double c = ch[k] < 0.0 ? 0.0 : (ch[k] > 1.0 ? 1.0 : ch[k]);
+            lut_bgr[3 * i + k] = (uint8_t)std::nearbyint(c * 255.0);  // half to even (the default rounding mode)
+        }
+    }
+}
+
+hipError_t launch_depth_images(hipStream_t s, const float* depth, const float* conf, const uint8_t* mask, int rows, int cols,
+                               float min_depth, float max_depth, const uint8_t* lut_dev, uint32_t* mm, uint8_t* conf_negated,
+                               uint8_t* inv_depth_bgr)
+{
+    const size_t npix_z = (size_t)rows * cols;
+    if (rows < 1 || cols < 1 || npix_z > 0x7fffffffull / 3) return hipErrorInvalidValue;
+    const int npix = (int)npix_z;
+    const dim3 pgrid((unsigned)((npix_z + 255) / 256)), block(256);
+    hipError_t e;
+    if (conf_negated) {
+        if ((e = hipMemsetAsync(mm, 0, 2 * sizeof(uint32_t), s)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_image_conf_minmax, dim3(grid_for(npix_z, 256, 256)), block, 0, s, conf, npix, mm);
+        hipLaunchKernelGGL(k_conf_negated_u8, pgrid, block, 0, s, conf, npix, mm, conf_negated);
+        if ((e = hipExtGetLastError()) != hipSuccess) return e;
+    }
+    if (inv_depth_bgr) {
+        // utils.cpp:85: (invmap - 1./max_depth) / (1./min_depth - 1./max_depth) * 255. -- the scalars of the matrix expression
+        // fold into one scale and one shift in double, applied to the float image in float
+        const double s1 = 1.0 / (double)max_depth;
+        const double s2 = 1.0 / (double)min_depth - s1;
+        const double k = 1.0 / s2;
+        const double alpha = k * 255.0, beta = ((-s1) * k) * 255.0;
+        hipLaunchKernelGGL(k_inv_depth_colored_dilated, pgrid, block, 0, s, depth, mask, lut_dev, rows, cols, (float)alpha,
+                           (float)beta, inv_depth_bgr);
+        if ((e = hipExtGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 }  // namespace dsi

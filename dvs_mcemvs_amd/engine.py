@@ -213,6 +213,13 @@ def load_library():
         "dsi_mapper_get_pointcloud": (C.c_int, [vp, f32p, u8p, C.POINTER(_PointCloudOptions), f32p, C.c_size_t, szp,
                                                 szp]),
         "dsi_radius_outlier_removal": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, C.c_float, C.c_int, u8p]),
+        "dsi_event_image": (C.c_int, [vp, u16p, u16p, u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, u8p, szp]),
+        "dsi_event_image_dev": (C.c_int, [vp, u16p, u16p, u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "dsi_batch_event_image": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_int, u8p, szp]),
+        "dsi_batch_event_image_dev": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "dsi_depth_images": (C.c_int, [vp, f32p, f32p, u8p, C.c_int, C.c_int, C.c_float, C.c_float, u8p, u8p, u8p]),
+        "dsi_mapper_depth_images": (C.c_int, [vp, C.c_float, C.c_float, u8p, u8p, u8p]),
+        "dsi_default_jet_lut": (C.c_int, [u8p]),
         "dsi_mapper_last_vote_info": (C.c_int, [vp, C.POINTER(_VoteInfo)]),
         "dsi_mapper_set_kernel_timing": (C.c_int, [vp, C.c_int]),
         "dsi_mapper_vote_kernel_time": (C.c_int, [vp, f32p, intp]),
@@ -862,6 +869,69 @@ def radius_outlier_removal(ctx, xyz, radius, min_neighbors):
     return keep.astype(bool)
 
 
+def _polarity_bytes(polarity, n, use_polarity):
+    if polarity is None:
+        if use_polarity:
+            raise ValueError("use_polarity needs the events' polarities")
+        return None
+    polarity = np.ascontiguousarray(np.asarray(polarity) != 0, np.uint8)
+    if polarity.shape != (n,):
+        raise ValueError("one polarity per event")
+    return polarity
+
+
+def accumulate_events(ctx, x, y, polarity, width, height, use_polarity=True, return_dropped=False):
+    """accumulateEvents(events, use_polarity, img) (utils.cpp:184-216) on the device (dsi_event_image): the uint8
+    [height][width] event image of the events x, y (uint16) with polarity (non-zero / True = positive; None is legal
+    with use_polarity=False).  width x height is the sensor's size.  use_polarity: 128 = no events, the largest
+    |#positive - #negative| maps to 0 / 255; otherwise the count modulo 256, min-max normalised.  Events outside the
+    sensor are dropped; return_dropped=True returns (image, number dropped)."""
+    x, y = _arr(x, np.uint16), _arr(y, np.uint16)
+    if x.ndim != 1 or x.shape != y.shape:
+        raise ValueError("x and y must be 1-D arrays of one length")
+    pol = _polarity_bytes(polarity, x.shape[0], use_polarity)
+    out = np.empty((max(int(height), 0), max(int(width), 0)), np.uint8)
+    dropped = C.c_size_t()
+    _check(load_library().dsi_event_image(ctx._h, _ptr(x, C.c_uint16), _ptr(y, C.c_uint16),
+                                          None if pol is None else _ptr(pol, C.c_uint8), x.shape[0], int(width), int(height),
+                                          int(bool(use_polarity)), _ptr(out, C.c_uint8), C.byref(dropped)))
+    return (out, dropped.value) if return_dropped else out
+
+
+def default_jet_lut():
+    """The engine's default colour table of depth_images: uint8 [256][3], B G R -- a piecewise-linear jet, not OpenCV's
+    COLORMAP_JET table (pass cv2.applyColorMap of a 0..255 ramp as `lut` for that)."""
+    lut = np.empty((256, 3), np.uint8)
+    _check(load_library().dsi_default_jet_lut(_ptr(lut, C.c_uint8)))
+    return lut
+
+
+def _lut_bytes(lut):
+    if lut is None:
+        return None
+    lut = _arr(lut, np.uint8)
+    if lut.shape != (256, 3):
+        raise ValueError("lut must be a (256, 3) uint8 table, B G R")
+    return lut
+
+
+def depth_images(ctx, depth, conf, mask, min_depth, max_depth, lut=None):
+    """The two images saveDepthMaps writes (utils.cpp:55-58, 82-93) of host maps (dsi_depth_images): (confidence_negated
+    uint8 [rows][cols], inv_depth_colored_dilated uint8 [rows][cols][3], B G R).  conf is the confidence map as
+    getDepthMapFromDSI returns it; lut a (256, 3) B G R table, None = default_jet_lut()."""
+    depth, conf, mask = _arr(depth, np.float32), _arr(conf, np.float32), _arr(mask, np.uint8)
+    if depth.ndim != 2 or conf.shape != depth.shape or mask.shape != depth.shape:
+        raise ValueError("depth, conf and mask must be 2-D maps of one shape")
+    rows, cols = depth.shape
+    lut = _lut_bytes(lut)
+    neg = np.empty((rows, cols), np.uint8)
+    bgr = np.empty((rows, cols, 3), np.uint8)
+    _check(load_library().dsi_depth_images(ctx._h, _ptr(depth, C.c_float), _ptr(conf, C.c_float), _ptr(mask, C.c_uint8), rows, cols,
+                                           C.c_float(min_depth), C.c_float(max_depth),
+                                           None if lut is None else _ptr(lut, C.c_uint8), _ptr(neg, C.c_uint8), _ptr(bgr, C.c_uint8)))
+    return neg, bgr
+
+
 class PinnedArray:
     """numpy array in page-locked host memory (dsi_host_alloc): the source / destination of
     asynchronous uploads and depth-map fetches.  `a` is the array; close() frees the memory."""
@@ -913,6 +983,17 @@ class EventBatch:
 
     def uploaded(self):
         return bool(load_library().dsi_batch_uploaded(self._h))
+
+    def event_image(self, polarity, width, height, use_polarity=True, return_dropped=False):
+        """accumulate_events of the events this batch holds on the device (dsi_batch_event_image): only the polarity
+        bytes are uploaded."""
+        pol = _polarity_bytes(polarity, self.n_events, use_polarity)
+        out = np.empty((max(int(height), 0), max(int(width), 0)), np.uint8)
+        dropped = C.c_size_t()
+        _check(load_library().dsi_batch_event_image(self._h, None if pol is None else _ptr(pol, C.c_uint8), int(width),
+                                                    int(height), int(bool(use_polarity)), _ptr(out, C.c_uint8),
+                                                    C.byref(dropped)))
+        return (out, dropped.value) if return_dropped else out
 
     def close(self):
         if self._h:
@@ -1128,6 +1209,17 @@ class MapperEMVS:
                                                         C.byref(n), C.byref(n0)))
         self.n_unfiltered_ = n0.value
         return out[:n.value].copy()
+
+    def depthImages(self, min_depth, max_depth, lut=None):
+        """depth_images of the filtered maps the last getDepthMapFromDSI(..., options_depth_map) / filterDepthMap left on
+        the device (dsi_mapper_depth_images; no upload): (confidence_negated, inv_depth_colored_dilated)."""
+        lut = _lut_bytes(lut)
+        neg = np.empty((self.dimY, self.dimX), np.uint8)
+        bgr = np.empty((self.dimY, self.dimX, 3), np.uint8)
+        _check(load_library().dsi_mapper_depth_images(self._h, C.c_float(min_depth), C.c_float(max_depth),
+                                                      None if lut is None else _ptr(lut, C.c_uint8), _ptr(neg, C.c_uint8),
+                                                      _ptr(bgr, C.c_uint8)))
+        return neg, bgr
 
     def computeDepthMap(self, grid=None):
         """Asynchronous half of getDepthMapFromDSI; pair with fetchDepthMap()."""

@@ -4,7 +4,9 @@ trajectories can be replayed without ROS:
 
   write_grid_npy        Grid3D::writeGridNpy           cartesian3dgrid_IO.cpp:30-36   (.npy, shape {Z,Y,X} f32)
   write_png_gray8       cv::imwrite of a CV_8UC1 slice  cartesian3dgrid_IO.cpp:74              (.png, 8-bit grayscale)
+  write_png_rgb8        cv::imwrite of a CV_8UC3 image  utils.cpp:93                            (.png, 8-bit colour, from B G R)
   save_depth_points     saveDepthMaps (txt part)        utils.cpp:31-46                ("col row depth" lines)
+  save_depth_maps       saveDepthMaps                   utils.cpp:22-104               (the txt and the two .png it writes)
   save_pcd_ascii        pcl::io::savePCDFileASCII       main.cpp:397-402               (.pcd v0.7, PointXYZI, ascii)
   read_pose_bag         parse of geometry_msgs/PoseStamped bags   data_loading.cpp:221-302 (ROSBAG v2.0; none / bz2 chunks)
   read_event_bag        parse of dvs_msgs/EventArray bags         data_loading.cpp:31-107, 211-216
@@ -31,6 +33,10 @@ def write_grid_npy(path, grid):
     return vol.shape
 
 
+def _png_chunk(kind, body):
+    return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xffffffff)
+
+
 def write_png_gray8(path, img):
     """An 8-bit grayscale PNG of a uint8 [rows][cols] image (Grid3D.imwriteSlices): IHDR, one IDAT holding the zlib
     stream of the scanlines, each with filter type 0, IEND.  Any PNG reader shows the pixels that were written; the
@@ -42,13 +48,44 @@ def write_png_gray8(path, img):
     raw = np.zeros((rows, cols + 1), np.uint8)
     raw[:, 1:] = img
 
-    def chunk(kind, body):
-        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xffffffff)
-
     with open(path, "wb") as f:
-        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", cols, rows, 8, 0, 0, 0, 0)) +
-                chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + chunk(b"IEND", b""))
+        f.write(b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", cols, rows, 8, 0, 0, 0, 0)) +
+                _png_chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + _png_chunk(b"IEND", b""))
     return rows, cols
+
+
+def write_png_rgb8(path, img_bgr):
+    """An 8-bit colour PNG (colour type 2) of a uint8 [rows][cols][3] image in OpenCV's channel order B G R, swapped to
+    R G B on writing; scanlines with filter type 0, like write_png_gray8."""
+    img = np.ascontiguousarray(img_bgr)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError("write_png_rgb8 takes a non-empty uint8 image of shape (rows, cols, 3)")
+    rows, cols = img.shape[:2]
+    raw = np.zeros((rows, 3 * cols + 1), np.uint8)
+    raw[:, 1:] = img[:, :, ::-1].reshape(rows, 3 * cols)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", cols, rows, 8, 2, 0, 0, 0)) +
+                _png_chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + _png_chunk(b"IEND", b""))
+    return rows, cols
+
+
+def save_depth_maps(out_path, suffix, depth, conf, mask, min_depth, max_depth, images=None, ctx=None, lut=None):
+    """saveDepthMaps (utils.cpp:22-104): out_path + "depth_points_" + suffix + ".txt", "confidence_map_negated_" + suffix +
+    ".png" and "inv_depth_colored_dilated_" + suffix + ".png" (out_path is a prefix, as in the reference).  images =
+    (confidence_negated, inv_depth_colored_dilated) as engine.depth_images / MapperEMVS.depthImages return them; None
+    computes them on the device of `ctx` (engine.Context) with the colour table `lut`.  Returns the three file names."""
+    if images is None:
+        if ctx is None:
+            raise ValueError("save_depth_maps needs images, or a ctx to compute them with")
+        from . import engine as _engine
+        images = _engine.depth_images(ctx, depth, conf, mask, min_depth, max_depth, lut)
+    neg, bgr = images
+    names = [out_path + "depth_points_" + suffix + ".txt", out_path + "confidence_map_negated_" + suffix + ".png",
+             out_path + "inv_depth_colored_dilated_" + suffix + ".png"]
+    save_depth_points(names[0], depth, mask)
+    write_png_gray8(names[1], neg)
+    write_png_rgb8(names[2], bgr)
+    return names
 
 
 def save_depth_points(path, depth_map, mask):

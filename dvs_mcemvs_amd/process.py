@@ -735,34 +735,85 @@ class WindowStream:
 
 def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop_time_s, duration,
                   out_skip, fusion_method=E.FUSE_HM, forward_looking=True, rv_pos=0.0, options_depth_map=None,
-                  options_point_cloud=None, **kw):
+                  options_point_cloud=None, polarities=None, save_images=False, out_path=None, lut=None, **kw):
     """Generator over the windows of main.cpp:177-302: yields (ts, depth, confidence, indices) per
     window, pipelined one window deep; with options_depth_map, (ts, depth_map, confidence_map, mask)
     -- the filtered outputs the reference saves per window; with options_point_cloud as well, the window's
     point cloud (main.cpp:396, an (N, 4) array: WindowStream.fetch) as a fifth element.
     process_method=2 / 5 (keywords of WindowStream: num_subintervals, temporal_fusion, camera_time; fusion_method is the
     stereo fusion): yields (ts, time_camera outputs, camera_time outputs or None), each output element shaped like what
-    process_method 1 yields after ts (main.cpp:275-299)."""
+    process_method 1 yields after ts (main.cpp:275-299).
+    save_images=True (process_method 1, needs options_depth_map and polarities = one array per camera, aligned with its
+    events): each window's result gains a last element, a dict of the pictures the reference writes per window --
+    "event_images" (one per camera, accumulateEvents with polarity, main.cpp:245-252; the sensor's size),
+    "confidence_negated" and "inv_depth_colored_dilated" (saveDepthMaps, process1.cpp:209-223; B G R, colour table `lut`)
+    -- all computed on the device.  The event images go through the host-array form (accumulate_events), before the
+    window is submitted as in main.cpp: x and y travel a second time and the slot's stream is synchronised per window, so
+    this opt-in path gives up the overlap of consecutive windows; a caller who keeps EventBatch objects uses
+    EventBatch.event_image instead, which uploads the polarity bytes only.  out_path and lut are keywords of this path
+    alone.  With out_path (a prefix, like --out_path) they are written as well:
+    out_path + "%f" % ts + "events_<c>.png" (main.cpp:251) and saveDepthMaps' three files as process1.cpp:121-122, 223 names
+    them: prefix out_path + "%013.9f" % ts, suffix "fused_<fusion_method>"."""
     if options_point_cloud is not None and options_depth_map is None:
         raise ValueError("options_point_cloud needs options_depth_map: the point cloud is made of the filtered maps")
+    if save_images:
+        if options_depth_map is None:
+            raise ValueError("save_images needs options_depth_map: saveDepthMaps' images are made of the filtered maps")
+        if polarities is None or len(polarities) != 2 or any(p is None for p in polarities):
+            raise ValueError("save_images needs polarities: one array per camera")
+        if kw.get("process_method", 1) != 1:
+            raise ValueError("save_images applies to process_method 1 only")
+        for c in range(2):
+            if np.shape(polarities[c]) != np.shape(events[c][0]):
+                raise ValueError("polarities[%d] must hold one polarity per event of camera %d" % (c, c))
+    elif out_path is not None or polarities is not None or lut is not None:
+        raise ValueError("polarities, out_path and lut are used by save_images=True only")
     ws = WindowStream(ctx, cams, dsi_shape, fusion_method, **kw)
     pending = None
+    images = None
+    if save_images:
+        images = {"fusion_method": int(fusion_method), "min_depth": dsi_shape.min_depth_, "max_depth": dsi_shape.max_depth_, "out_path": out_path,
+                  "lut": lut}
     try:
         for t0, t1 in window_bounds(start_time_s, stop_time_s, duration, out_skip):
             ts = t1 if forward_looking else 0.5 * (t0 + t1)          # main.cpp:185-189
             ev = [window_events(events[c], t0, t1) for c in range(2)]
+            event_images = None
+            if save_images:                                          # main.cpp:245-252, before the window is processed
+                event_images = [_window_event_image(ws.context_of_slot(ws.k % len(ws.fused)), events[c], polarities[c], t0, t1,
+                                                    cams[0]) for c in range(2)]       # cam0.fullResolution(), :246
             slot = ws.submit(ev, trajectories, ts, rv_pos)
             if pending is not None:
-                yield _window_result(ws, pending, options_depth_map, options_point_cloud)
-            pending = (ts, slot)
+                yield _window_result(ws, pending, options_depth_map, options_point_cloud, images)
+            pending = (ts, slot, event_images)
         if pending is not None:
-            yield _window_result(ws, pending, options_depth_map, options_point_cloud)
+            yield _window_result(ws, pending, options_depth_map, options_point_cloud, images)
     finally:
         ws.close()
 
 
-def _window_result(ws, pending, options_depth_map, options_point_cloud):
+def _window_event_image(ctx, events, polarity, t_start, t_stop, cam):
+    """accumulateEvents(interval_events, true, event_image) of one camera's window (the slice window_events takes)."""
+    x, y, ts = events
+    a = int(np.searchsorted(ts, t_start, side="left"))               # window_events' cut
+    b = int(np.searchsorted(ts, t_stop, side="right"))
+    x, y = x[a:b], y[a:b]
+    return E.accumulate_events(ctx, x, y, np.asarray(polarity)[a:b], int(cam[0]), int(cam[1]), True)
+
+
+def _window_result(ws, pending, options_depth_map, options_point_cloud, images=None):
     out = ws.fetch(pending[1], options_depth_map, options_point_cloud)
+    if images is not None:
+        from . import io as _io
+        ts = pending[0]
+        neg, bgr = ws.extract[pending[1]].depthImages(images["min_depth"], images["max_depth"], images["lut"])
+        pics = {"event_images": pending[2], "confidence_negated": neg, "inv_depth_colored_dilated": bgr}
+        if images["out_path"] is not None:
+            for c, img in enumerate(pending[2]):
+                _io.write_png_gray8(images["out_path"] + "%f" % ts + "events_%d.png" % c, img)
+            _io.save_depth_maps(images["out_path"] + "%013.9f" % ts, "fused_%d" % images["fusion_method"], out[0], out[1], out[2], images["min_depth"],
+                                images["max_depth"], images=(neg, bgr))
+        out = out + (pics,)
     return (pending[0],) + (out if ws.process_method == 1 else tuple(out))
 
 

@@ -366,8 +366,8 @@ DSI_API int dsi_mapper_set_inline_cuts(dsi_mapper_t *m, long long min_packets);
  * resetting it (the reset is evaluateDSI's, :145). */
 DSI_API int dsi_mapper_fill_voxel_grid(dsi_mapper_t *m, const float *xy_z0, const float *centers, size_t n_packets);
 
-/* Device-resident input of one evaluateDSI call: raw events (pixel x,y; polarity and
- * timestamps are not needed past packetisation) plus the packetisation done by
+/* Device-resident input of one evaluateDSI call: raw events (pixel x,y; timestamps are not needed
+ * past packetisation, and polarity only by dsi_batch_event_image, which takes it separately) plus the packetisation done by
  * mapper_emvs_stereo.cpp:88-105: packet k covers events
  * [packet_first[k], packet_first[k]+1024) (packet_first == NULL: k*1024) and has
  * pose Rt[12k..12k+11] = R (row-major 3x3) then t of T_ev_rv, already cast to float.
@@ -764,6 +764,56 @@ typedef struct {
 DSI_API int dsi_mapper_get_pointcloud(dsi_mapper_t *m, const float *depth_host, const uint8_t *mask_host,
                                       const dsi_pointcloud_options_t *opts, float *xyzi_host, size_t capacity,
                                       size_t *n_points, size_t *n_unfiltered);
+
+/* ---- the run's pictures: accumulateEvents and the two images of saveDepthMaps (definitions: DESIGN.md 7e) ---- */
+/* accumulateEvents(events, use_polarity, img) (utils.cpp:184-216) on the device: the 8-bit height x width event image of
+ * n events with pixel coordinates x, y (host arrays) and polarity bytes (non-zero = positive; NULL is legal only when
+ * use_polarity == 0 or n == 0 -- an empty event list gives 128 everywhere, or 0 without polarity).  n <= 2^31 - 1.  width x height is the SENSOR's size (cam.fullResolution()), not the DSI's.
+ *   use_polarity != 0: c = (#positive - #negative) per pixel, an integer -- equal to the reference's fp32 += +-1 while no
+ *     pixel holds more than 2^24 events; the counters are int32, which n <= 2^31 - 1 cannot overflow.  half = max(|min c|, |max c|); half == 0 (no events
+ *     included): 128 everywhere; else a = (float)(128.0 / half), v = (float)c * a + 128.f in fp32 without FMA, rounded to
+ *     nearest (ties to even) and clamped to 0..255: +half gives 255, -half gives 0.
+ *   use_polarity == 0: the count modulo 256 (the reference's uchar += 1 wraps), then cv::normalize(NORM_MINMAX, 0, 255):
+ *     scale = 255 * (range > DBL_EPSILON ? 1 / range : 0), shift = -min * scale in double, applied as floats, rounded alike.
+ * An event with x >= width or y >= height is dropped (the reference would write out of bounds); *n_dropped (may be NULL)
+ * is their number.  DSI_ERR_INVALID: width or height < 1, use_polarity without polarity (n > 0), n > 2^31 - 1.  Host output;
+ * synchronises. */
+DSI_API int dsi_event_image(dsi_context_t *ctx, const uint16_t *x, const uint16_t *y, const uint8_t *polarity, size_t n,
+                            int width, int height, int use_polarity, uint8_t *out_u8_host, size_t *n_dropped);
+/* same, device output (4-byte aligned, else DSI_ERR_INVALID) and device count (one uint32, may be NULL); asynchronous.
+ * Host arrays in page-locked memory must stay unchanged until the context's stream has run. */
+DSI_API int dsi_event_image_dev(dsi_context_t *ctx, const uint16_t *x, const uint16_t *y, const uint8_t *polarity, size_t n,
+                                int width, int height, int use_polarity, uint8_t *out_u8_dev, uint32_t *n_dropped_dev);
+/* The same image of the events a batch already holds on the device: only the polarity bytes travel (the batch's n_events
+ * of them, host array; NULL only when use_polarity == 0 or the batch holds no events).  Runs on the batch's context. */
+DSI_API int dsi_batch_event_image(const dsi_batch_t *batch, const uint8_t *polarity_host, int width, int height,
+                                  int use_polarity, uint8_t *out_u8_host, size_t *n_dropped);
+DSI_API int dsi_batch_event_image_dev(const dsi_batch_t *batch, const uint8_t *polarity_host, int width, int height,
+                                      int use_polarity, uint8_t *out_u8_dev, uint32_t *n_dropped_dev);
+/* The two images saveDepthMaps writes (utils.cpp:55-58 and :82-93) of rows x cols host maps: depth f32, confidence f32
+ * exactly as getDepthMapFromDSI returns it (element (0,0) = max_confidence), mask u8.  Either output may be NULL.
+ *   conf_negated_host (rows * cols bytes): n = conf * a + b with cv::normalize(NORM_MINMAX, 0, 255)'s a, b of the map's
+ *     extremes (scale and shift in double, applied as floats), v = 255.f - n, rounded to nearest (ties to even), clamped.
+ *     A constant map gives 255 everywhere.  A map holding NaN gives an unspecified image.
+ *   inv_depth_bgr_host (rows * cols * 3 bytes, B G R): i = round_clamp((1.f / depth) * a + b) -- NaN gives 0 -- with
+ *     s1 = 1 / max_depth, k = 1 / (1 / min_depth - s1), a = (float)(k * 255), b = (float)((-s1 * k) * 255) (doubles);
+ *     colour lut_bgr[i] where mask > 0, black elsewhere; then dilated by the 3 x 3 cross (MORPH_ELLIPSE, Size(3,3)),
+ *     the maximum per channel, neighbours outside the image not contributing.
+ * lut_bgr: 256 x 3 bytes, B G R; NULL selects the engine's default table (dsi_default_jet_lut), a piecewise-linear jet
+ * that is NOT OpenCV's COLORMAP_JET table -- a caller with OpenCV passes cv::applyColorMap of a 0..255 ramp.
+ * DSI_ERR_INVALID: rows or cols < 1, an output without its input maps, and -- for the colour image -- min_depth or
+ * max_depth not finite, not > 0, or equal.  Synchronises. */
+DSI_API int dsi_depth_images(dsi_context_t *ctx, const float *depth_host, const float *conf_host, const uint8_t *mask_host,
+                             int rows, int cols, float min_depth, float max_depth, const uint8_t *lut_bgr,
+                             uint8_t *conf_negated_host, uint8_t *inv_depth_bgr_host);
+/* same, of the filtered depth map, confidence map and mask that the last dsi_mapper_filter_depth_map /
+ * dsi_mapper_get_depth_map_from_dsi left on the device (ny x nx; no upload): the bytes dsi_depth_images gives for what
+ * that call returned.  DSI_ERR_INVALID if there are none (dsi_mapper_get_pointcloud's rule). */
+DSI_API int dsi_mapper_depth_images(dsi_mapper_t *m, float min_depth, float max_depth, const uint8_t *lut_bgr,
+                                    uint8_t *conf_negated_host, uint8_t *inv_depth_bgr_host);
+/* the default colour table, 256 x 3 bytes B G R: with t = i / 255, r = clamp01(1.5 - |4t - 3|), g = clamp01(1.5 - |4t - 2|),
+ * b = clamp01(1.5 - |4t - 1|), each x 255 in double, rounded to nearest (ties to even) */
+DSI_API int dsi_default_jet_lut(uint8_t *lut_bgr);
 
 /* pcl::RadiusOutlierRemoval (radius_outlier_removal.hpp, dense cloud) on its own: point i of the n points xyz_host
  * (stride_floats = 3 or 4 floats per point; x, y, z first) is kept (keep_host[i] = 1) iff at least min_neighbors + 1

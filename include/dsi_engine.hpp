@@ -158,9 +158,10 @@ inline bool inpaint_depth_cell_indices(const ImgT& /*filtered u8*/, const ImgT& 
 // caller with OpenCV adds, in namespace cv or in namespace dsi before this header,
 //     inline bool imwrite_gray8(const std::string& path, const cv::Mat& img) { return cv::imwrite(path, img); }
 // and calls imwriteSlices<cv::Mat>(...): the overload is found by ADL and wins over this template.
-inline bool write_png_gray8(const std::string& path, const uint8_t* pixels, int rows, int cols)
+// write_png_rgb8 is its colour twin (colour type 2) for OpenCV-ordered pixels: B G R in memory, swapped to R G B on writing.
+inline bool write_png8(const std::string& path, const uint8_t* pixels, int rows, int cols, int channels)
 {
-    if (!pixels || rows < 1 || cols < 1) return false;
+    if (!pixels || rows < 1 || cols < 1 || (channels != 1 && channels != 3)) return false;
     static const std::vector<uint32_t> table = [] {
         std::vector<uint32_t> t(256);
         for (uint32_t n = 0; n < 256; ++n) {
@@ -183,10 +184,17 @@ inline bool write_png_gray8(const std::string& path, const uint8_t* pixels, int 
         be32(file, c ^ 0xffffffffu);
     };
     std::vector<uint8_t> raw;  // the scanlines, each behind its filter byte
-    raw.reserve((size_t)rows * (cols + 1));
+    const size_t pitch = (size_t)cols * channels;
+    raw.reserve((size_t)rows * (pitch + 1));
     for (int y = 0; y < rows; ++y) {
         raw.push_back(0);
-        raw.insert(raw.end(), pixels + (size_t)y * cols, pixels + (size_t)(y + 1) * cols);
+        const uint8_t* row = pixels + (size_t)y * pitch;
+        if (channels == 1) {
+            raw.insert(raw.end(), row, row + pitch);
+        } else {
+            for (int x = 0; x < cols; ++x)
+                for (int k = 2; k >= 0; --k) raw.push_back(row[3 * x + k]);
+        }
     }
     std::vector<uint8_t> z = {0x78, 0x01};  // zlib header: deflate, 32 KiB window, no preset dictionary
     uint32_t a = 1, b = 0;
@@ -209,7 +217,8 @@ inline bool write_png_gray8(const std::string& path, const uint8_t* pixels, int 
     std::vector<uint8_t> ihdr;
     be32(ihdr, (uint32_t)cols);
     be32(ihdr, (uint32_t)rows);
-    const uint8_t rest[5] = {8, 0, 0, 0, 0};  // bit depth 8, colour type 0 (grayscale), deflate, adaptive filtering, no interlace
+    // bit depth 8, colour type 0 (grayscale) or 2 (truecolour), deflate, adaptive filtering, no interlace
+    const uint8_t rest[5] = {8, (uint8_t)(channels == 3 ? 2 : 0), 0, 0, 0};
     ihdr.insert(ihdr.end(), rest, rest + 5);
     chunk(file, "IHDR", ihdr);
     chunk(file, "IDAT", z);
@@ -218,6 +227,14 @@ inline bool write_png_gray8(const std::string& path, const uint8_t* pixels, int 
     if (!f) return false;
     const bool ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
     return (std::fclose(f) == 0) && ok;
+}
+inline bool write_png_gray8(const std::string& path, const uint8_t* pixels, int rows, int cols)
+{
+    return write_png8(path, pixels, rows, cols, 1);
+}
+inline bool write_png_rgb8(const std::string& path, const uint8_t* pixels_bgr, int rows, int cols)
+{
+    return write_png8(path, pixels_bgr, rows, cols, 3);
 }
 template <typename ImgT>
 inline bool imwrite_gray8(const std::string& path, const ImgT& img)
@@ -1135,3 +1152,100 @@ private:
 };
 
 }  // namespace EMVS
+
+// ---- the run's pictures (utils.hpp:23-52, utils.cpp:22-117, 184-216; arithmetic: dsi_engine.h) ----
+namespace dsi {
+
+// Customisation point: the 256-entry colour table (B G R per entry) of saveDepthMaps' inverse-depth image.  The default is
+// the engine's piecewise-linear jet (dsi_default_jet_lut), NOT OpenCV's COLORMAP_JET table.  A caller with OpenCV adds,
+// in namespace dsi before this header,
+//     inline bool color_map_jet(uint8_t (&lut)[256][3]) { /* cv::applyColorMap of a 0..255 ramp, COLORMAP_JET */ return true; }
+// and that non-template wins over this template.  (Its argument is an array of a built-in type, which has no associated
+// namespace: unlike inpaint_depth_cell_indices it cannot be found by ADL in the image type's namespace.)
+template <typename Tag = void>
+inline bool color_map_jet(uint8_t (&lut)[256][3])
+{
+    check(dsi_default_jet_lut(&lut[0][0]));
+    return true;
+}
+
+// accumulateEvents(events, use_polarity, img) on the device of ctx: img is an existing 8-bit single-channel image of the
+// sensor's size (cv::Mat(full_resolution, CV_8UC1), main.cpp:246-249), any type dsi::image_data reads; events any type
+// with .x .y .polarity (dvs_msgs::Event).  Returns the number of events outside the image, which are dropped.
+template <typename EventT, typename ImgT>
+inline size_t accumulateEvents(Context& ctx, const std::vector<EventT>& events, const bool use_polarity, ImgT& img)
+{
+    const size_t n = events.size();
+    std::vector<uint16_t> x(n), y(n);
+    std::vector<uint8_t> pol(n);
+    for (size_t i = 0; i < n; ++i) {
+        x[i] = (uint16_t)events[i].x;
+        y[i] = (uint16_t)events[i].y;
+        pol[i] = events[i].polarity ? 1 : 0;
+    }
+    size_t dropped = 0;
+    check(dsi_event_image(ctx.handle(), x.data(), y.data(), pol.data(), n, img.cols, img.rows, use_polarity ? 1 : 0,
+                          img.rows > 0 && img.cols > 0 ? dsi::image_data<uint8_t>(img) : nullptr, &dropped));
+    return dropped;
+}
+
+// saveDepthMaps on the device of ctx: depth_points_<suffix>.txt (utils.cpp:31-46), confidence_map_negated_<suffix>.png
+// (:55-58, through dsi::imwrite_gray8) and inv_depth_colored_dilated_<suffix>.png (:82-93, dsi::write_png_rgb8), each
+// prefixed by out_path.  conf_negated / inv_depth_bgr (may be NULL) receive the two images.
+template <typename DepthImg, typename ConfImg, typename MaskImg>
+inline void saveDepthMaps(Context& ctx, const DepthImg& depth_map, const ConfImg& confidence_map, const MaskImg& semidense_mask,
+                          const float min_depth, const float max_depth, const std::string& suffix, const std::string& out_path,
+                          std::vector<uint8_t>* conf_negated = nullptr, std::vector<uint8_t>* inv_depth_bgr = nullptr)
+{
+    const int rows = depth_map.rows, cols = depth_map.cols;
+    if (confidence_map.rows != rows || confidence_map.cols != cols || semidense_mask.rows != rows || semidense_mask.cols != cols)
+        throw Error(DSI_ERR_INVALID, "saveDepthMaps: the three maps must have one size");
+    const float* depth = dsi::image_data<float>(const_cast<DepthImg&>(depth_map));
+    const float* conf = dsi::image_data<float>(const_cast<ConfImg&>(confidence_map));
+    const uint8_t* mask = dsi::image_data<uint8_t>(const_cast<MaskImg&>(semidense_mask));
+    if (std::FILE* of = std::fopen((out_path + "depth_points_" + suffix + ".txt").c_str(), "w")) {  // :31-46
+        for (int r = 0; r < rows; ++r)
+            for (int c = 0; c < cols; ++c)
+                if (mask[(size_t)r * cols + c] > 0)  // operator<<(float): %g
+                    std::fprintf(of, "%d %d %g\n", c, r, (double)depth[(size_t)r * cols + c]);
+        std::fclose(of);
+    }
+    uint8_t lut[256][3];
+    const bool own_table = color_map_jet(lut);
+    MaskImg negated;
+    uint8_t* neg = dsi::image_create<uint8_t>(negated, rows, cols);
+    std::vector<uint8_t> bgr((size_t)rows * cols * 3);
+    check(dsi_depth_images(ctx.handle(), depth, conf, mask, rows, cols, min_depth, max_depth, own_table ? &lut[0][0] : nullptr, neg,
+                           bgr.data()));
+    using dsi::imwrite_gray8;
+    if (!imwrite_gray8(out_path + "confidence_map_negated_" + suffix + ".png", negated))
+        throw Error(DSI_ERR_INVALID, "saveDepthMaps: cannot write " + out_path + "confidence_map_negated_" + suffix + ".png");
+    if (!write_png_rgb8(out_path + "inv_depth_colored_dilated_" + suffix + ".png", bgr.data(), rows, cols))
+        throw Error(DSI_ERR_INVALID, "saveDepthMaps: cannot write " + out_path + "inv_depth_colored_dilated_" + suffix + ".png");
+    if (conf_negated) conf_negated->assign(neg, neg + (size_t)rows * cols);
+    if (inv_depth_bgr) inv_depth_bgr->swap(bgr);
+}
+
+}  // namespace dsi
+
+// the reference's spellings (utils.hpp:23-52), on the process-wide default context: main.cpp:249-250 and
+// process1.cpp:209-223 compile as they stand
+template <typename EventT, typename ImgT>
+inline void accumulateEvents(const std::vector<EventT>& events, const bool use_polarity, ImgT& img)
+{
+    dsi::accumulateEvents(dsi::default_context(), events, use_polarity, img);
+}
+template <typename DepthImg, typename ConfImg, typename MaskImg>
+inline void saveDepthMaps(const DepthImg& depth_map, const ConfImg& confidence_map, const MaskImg& semidense_mask,
+                          const float min_depth, const float max_depth, const std::string& suffix, const std::string& out_path)
+{
+    dsi::saveDepthMaps(dsi::default_context(), depth_map, confidence_map, semidense_mask, min_depth, max_depth, suffix, out_path);
+}
+// (depth_map_dense is not used by the reference's body either: its block is commented out, utils.cpp:95-103)
+template <typename DepthImg, typename ConfImg, typename MaskImg, typename DenseImg>
+inline void saveDepthMaps(const DepthImg& depth_map, const ConfImg& confidence_map, const MaskImg& semidense_mask,
+                          const DenseImg& /*depth_map_dense*/, const float min_depth, const float max_depth,
+                          const std::string& suffix, const std::string& out_path)
+{
+    dsi::saveDepthMaps(dsi::default_context(), depth_map, confidence_map, semidense_mask, min_depth, max_depth, suffix, out_path);
+}
