@@ -969,7 +969,7 @@ int dsi_context_destroy(dsi_context_t* ctx)
 {
     if (!ctx) return DSI_OK;
     REQUIRE(ctx->children.load() == 0, DSI_ERR_CONTEXT,
-            "%d object(s) created from this context (grids, mappers, batches) are still alive: destroy them first",
+            "%d object(s) created from this context (grids, mappers, batches, scores) are still alive: destroy them first",
             ctx->children.load());
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
@@ -3442,6 +3442,281 @@ int dsi_mapper_depth_images(dsi_mapper_t* m, float min_depth, float max_depth, c
     // m->conf is the confidence map as the filter call returned it: element (0,0) = max_confidence, nothing else touched
     return depth_images_run(m->ctx, nullptr, nullptr, nullptr, m->depth.p, m->conf.p, m->mask.p, m->geom.ny, m->geom.nx, min_depth,
                             max_depth, lut_bgr, conf_negated_host, inv_depth_bgr_host);
+}
+
+// ---- depth-map scores against ground truth ----
+
+struct dsi_score {
+    dsi_context* ctx = nullptr;
+    size_t capacity = 0;
+    double baseline = 0.0, focal = 0.0, gt_min = 0.0;
+    double* buf = nullptr;  // capacity errors, then kScoreGuardWords words that nothing may touch
+    // state | extremes (2) | select work area
+    unsigned long long* words = nullptr;
+    double* partials = nullptr;  // 4 * kScoreMaxBlocks
+    DevBuf<float> depth, gt;     // uploaded maps
+    DevBuf<uint8_t> mask;
+    DevBuf<unsigned long long> counts;
+};
+
+namespace {
+
+constexpr size_t kScoreGuardWords = 64;
+constexpr unsigned long long kScoreGuardPattern = 0xa5c3a5c3a5c3a5c3ull;
+constexpr size_t kScoreStateWords = sizeof(dsi::ScoreState) / sizeof(unsigned long long);
+static_assert(sizeof(dsi::ScoreState) % sizeof(unsigned long long) == 0, "ScoreState is made of 64-bit words");
+
+dsi::ScoreState* score_state(dsi_score* s) { return reinterpret_cast<dsi::ScoreState*>(s->words); }
+unsigned long long* score_mm(dsi_score* s) { return s->words + kScoreStateWords; }
+unsigned long long* score_select_words(dsi_score* s) { return s->words + kScoreStateWords + 2; }
+
+void score_free(dsi_score* s)
+{
+    if (s->buf) (void)hipFree(s->buf);
+    if (s->words) (void)hipFree(s->words);
+    if (s->partials) (void)hipFree(s->partials);
+    s->depth.release();
+    s->gt.release();
+    s->mask.release();
+    s->counts.release();
+    delete s;
+}
+
+int score_add_device(dsi_score* s, const float* depth_dev, const uint8_t* mask_dev, const float* gt_dev, size_t n)
+{
+    HIP_TRY(dsi::launch_score_accumulate(s->ctx->stream, depth_dev, mask_dev, gt_dev, n, s->gt_min, s->baseline, s->focal,
+                                         score_state(s), s->buf, s->capacity, s->partials));
+    return DSI_OK;
+}
+
+int score_check_add(const dsi_score* s, const void* a, const void* b, const void* c, size_t n)
+{
+    REQUIRE(s && a && b && c, DSI_ERR_INVALID, "null argument");
+    REQUIRE(n >= 1 && n <= ((size_t)1 << 40), DSI_ERR_INVALID, "a map holds 1 .. 2^40 pixels (got %zu)", n);
+    return DSI_OK;
+}
+
+// the state as it stands once the stream has run; synchronises
+int score_read_state(dsi_score* s, dsi::ScoreState* st, size_t* n_stored)
+{
+    HIP_TRY(hipMemcpyAsync(st, s->words, sizeof *st, hipMemcpyDeviceToHost, s->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    *n_stored = (size_t)std::min<unsigned long long>(st->cursor, s->capacity);
+    return DSI_OK;
+}
+
+// np.ma.median of the n stored errors; synchronises
+int score_median_of(dsi_score* s, size_t n, double* out)
+{
+    unsigned long long mid[2] = {0, 0};
+    unsigned long long* work = score_select_words(s);
+    HIP_TRY(dsi::launch_score_select(s->ctx->stream, s->buf, n, (n - 1) / 2, n / 2, work));
+    HIP_TRY(hipMemcpyAsync(mid, work, sizeof mid, hipMemcpyDeviceToHost, s->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    double lo, hi;
+    std::memcpy(&lo, &mid[0], sizeof lo);
+    std::memcpy(&hi, &mid[1], sizeof hi);
+    *out = (n & 1) ? lo : (lo + hi) / 2.0;  // numpy: mid.sum() / 2 of the two middle elements
+    return DSI_OK;
+}
+
+}  // namespace
+
+int dsi_score_create(dsi_context_t* ctx, size_t capacity_points, double baseline, double focal, double gt_min, dsi_score_t** out)
+{
+    REQUIRE(ctx && out, DSI_ERR_INVALID, "null argument");
+    REQUIRE(capacity_points >= 1 && capacity_points <= ((size_t)1 << 40), DSI_ERR_INVALID,
+            "capacity_points must be in 1 .. 2^40 (got %zu)", capacity_points);
+    REQUIRE(std::isfinite(baseline) && baseline > 0.0 && std::isfinite(focal) && focal > 0.0, DSI_ERR_INVALID,
+            "baseline and focal must be finite and > 0 (got %g, %g)", baseline, focal);
+    REQUIRE(std::isfinite(gt_min) && gt_min > 0.0, DSI_ERR_INVALID, "gt_min must be finite and > 0 (got %g)", gt_min);
+    if (int rc = set_device(ctx)) return rc;
+    dsi_score* s = new (std::nothrow) dsi_score;
+    REQUIRE(s, DSI_ERR_INVALID, "out of host memory");
+    s->ctx = ctx;
+    s->capacity = capacity_points;
+    s->baseline = baseline;
+    s->focal = focal;
+    s->gt_min = gt_min;
+    const size_t nwords = kScoreStateWords + 2 + dsi::kScoreSelectWords;
+    std::vector<unsigned long long> guard(kScoreGuardWords, kScoreGuardPattern);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->buf), (capacity_points + kScoreGuardWords) * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->words), nwords * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->partials), 4 * (size_t)dsi::kScoreMaxBlocks * sizeof(double));
+    if (e == hipSuccess) e = hipMemsetAsync(s->words, 0, nwords * sizeof(unsigned long long), ctx->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(s->buf + capacity_points, guard.data(), kScoreGuardWords * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (`guard` is free again)
+    if (e != hipSuccess) {
+        score_free(s);
+        return fail(DSI_ERR_HIP, "score allocation of %zu points failed: %s", capacity_points, hipGetErrorString(e));
+    }
+    ++ctx->children;
+    *out = s;
+    return DSI_OK;
+}
+
+int dsi_score_destroy(dsi_score_t* s)
+{
+    if (!s) return DSI_OK;
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
+    --s->ctx->children;
+    score_free(s);
+    return DSI_OK;
+}
+
+int dsi_score_reset(dsi_score_t* s)
+{
+    REQUIRE(s, DSI_ERR_INVALID, "null argument");
+    if (int rc = set_device(s->ctx)) return rc;
+    HIP_TRY(hipMemsetAsync(s->words, 0, kScoreStateWords * sizeof(unsigned long long), s->ctx->stream));
+    return DSI_OK;
+}
+
+int dsi_score_add(dsi_score_t* s, const float* depth_host, const uint8_t* mask_host, const float* gt_host, size_t n_pixels)
+{
+    if (int rc = score_check_add(s, depth_host, mask_host, gt_host, n_pixels)) return rc;
+    if (int rc = set_device(s->ctx)) return rc;
+    hipStream_t st = s->ctx->stream;
+    HIP_TRY(s->depth.reserve(n_pixels));
+    HIP_TRY(s->gt.reserve(n_pixels));
+    HIP_TRY(s->mask.reserve(n_pixels));
+    HIP_TRY(hipMemcpyAsync(s->depth.p, depth_host, n_pixels * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->mask.p, mask_host, n_pixels, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->gt.p, gt_host, n_pixels * sizeof(float), hipMemcpyHostToDevice, st));
+    return score_add_device(s, s->depth.p, s->mask.p, s->gt.p, n_pixels);
+}
+
+int dsi_score_add_dev(dsi_score_t* s, const float* depth_dev, const uint8_t* mask_dev, const float* gt_dev, size_t n_pixels)
+{
+    if (int rc = score_check_add(s, depth_dev, mask_dev, gt_dev, n_pixels)) return rc;
+    if (int rc = set_device(s->ctx)) return rc;
+    return score_add_device(s, depth_dev, mask_dev, gt_dev, n_pixels);
+}
+
+int dsi_score_add_mapper(dsi_score_t* s, dsi_mapper_t* m, const float* gt_host)
+{
+    REQUIRE(s && m && gt_host, DSI_ERR_INVALID, "null argument");
+    REQUIRE(m->ctx == s->ctx, DSI_ERR_CONTEXT, "mapper and score belong to different contexts");
+    REQUIRE(m->filtered_valid, DSI_ERR_INVALID,
+            "no filtered depth map on the device: call dsi_mapper_filter_depth_map or dsi_mapper_get_depth_map_from_dsi "
+            "after the depth map was computed, or pass the maps to dsi_score_add");
+    if (int rc = set_device(s->ctx)) return rc;
+    if (int rc = depth_buffers_acquire(m)) return rc;
+    const size_t npix = (size_t)m->geom.nx * m->geom.ny;
+    HIP_TRY(s->gt.reserve(npix));
+    HIP_TRY(hipMemcpyAsync(s->gt.p, gt_host, npix * sizeof(float), hipMemcpyHostToDevice, s->ctx->stream));
+    return score_add_device(s, m->depth.p, m->mask.p, s->gt.p, npix);
+}
+
+int dsi_score_median(dsi_score_t* s, double* median_abs)
+{
+    REQUIRE(s && median_abs, DSI_ERR_INVALID, "null argument");
+    if (int rc = set_device(s->ctx)) return rc;
+    dsi::ScoreState st;
+    size_t n = 0;
+    if (int rc = score_read_state(s, &st, &n)) return rc;
+    REQUIRE(!st.overflow && st.cursor <= s->capacity, DSI_ERR_INVALID,
+            "the error buffer overflowed (%llu joint pixels, capacity %zu): the median needs every error", st.cursor, s->capacity);
+    *median_abs = std::nan("");
+    if (n == 0) return DSI_OK;
+    return score_median_of(s, n, median_abs);
+}
+
+int dsi_score_metrics(dsi_score_t* s, dsi_score_metrics_t* out)
+{
+    REQUIRE(s && out, DSI_ERR_INVALID, "null argument");
+    if (int rc = set_device(s->ctx)) return rc;
+    dsi::ScoreState st;
+    size_t n_stored = 0;
+    unsigned long long guard[kScoreGuardWords];
+    HIP_TRY(hipMemcpyAsync(guard, s->buf + s->capacity, sizeof guard, hipMemcpyDeviceToHost, s->ctx->stream));
+    if (int rc = score_read_state(s, &st, &n_stored)) return rc;
+    dsi_score_metrics_t r{};
+    r.n_est = st.count[0];
+    r.n_gt = st.count[1];
+    r.n_joint = st.count[2];
+    for (int k = 0; k < 3; ++k) r.n_delta[k] = st.count[3 + k];
+    r.n_bad = st.count[6];
+    r.n_stored = n_stored;
+    r.overflow = (st.overflow || st.cursor > s->capacity) ? 1 : 0;
+    r.guard_intact = 1;
+    for (size_t i = 0; i < kScoreGuardWords; ++i)
+        if (guard[i] != kScoreGuardPattern) r.guard_intact = 0;
+    r.sum_di = st.sum[0];
+    r.sum_di2 = st.sum[1];
+    r.sum_are = st.sum[2];
+    r.sum_abs = st.sum[3];
+    const double nan = std::nan("");
+    r.max_gt = nan;
+    if (st.max_gt_key) std::memcpy(&r.max_gt, &st.max_gt_key, sizeof r.max_gt);
+    r.delta[0] = r.delta[1] = r.delta[2] = r.silog = r.are = r.lrmse = r.badp = r.mean_abs = r.median_abs = nan;
+    if (r.n_joint) {
+        const double n = (double)r.n_joint;
+        for (int k = 0; k < 3; ++k) r.delta[k] = (double)r.n_delta[k] / n;                    // depth_metrics.py:10-12
+        r.silog = 1.0 / n * r.sum_di2 - 1.0 / (n * n) * (r.sum_di * r.sum_di);                // :17
+        r.are = 1.0 / n * r.sum_are;                                                          // :20
+        r.lrmse = std::sqrt(1.0 / n * r.sum_di2);                                             // :23
+        r.badp = (double)r.n_bad / n;                                                         // :28
+        r.mean_abs = r.sum_abs / n;                                                           // np.ma.mean
+        if (!r.overflow)
+            if (int rc = score_median_of(s, n_stored, &r.median_abs)) return rc;
+    }
+    *out = r;
+    return DSI_OK;
+}
+
+int dsi_score_histogram(dsi_score_t* s, double binwidth, uint64_t* counts, size_t cap, size_t* n_bins, double* first_edge,
+                        double* last_edge)
+{
+    REQUIRE(s && n_bins && first_edge && last_edge, DSI_ERR_INVALID, "null argument");
+    REQUIRE(std::isfinite(binwidth) && binwidth > 0.0, DSI_ERR_INVALID, "binwidth must be finite and > 0 (got %g)", binwidth);
+    if (int rc = set_device(s->ctx)) return rc;
+    hipStream_t stream = s->ctx->stream;
+    dsi::ScoreState st;
+    size_t n = 0;
+    if (int rc = score_read_state(s, &st, &n)) return rc;
+    REQUIRE(!st.overflow && st.cursor <= s->capacity, DSI_ERR_INVALID,
+            "the error buffer overflowed (%llu joint pixels, capacity %zu): the histogram needs every error", st.cursor,
+            s->capacity);
+    *n_bins = 0;
+    *first_edge = *last_edge = std::nan("");
+    if (n == 0) return DSI_OK;
+    unsigned long long mm[2];
+    HIP_TRY(dsi::launch_score_minmax(stream, s->buf, n, score_mm(s)));
+    HIP_TRY(hipMemcpyAsync(mm, score_mm(s), sizeof mm, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    double lo, hi;
+    std::memcpy(&lo, &mm[0], sizeof lo);
+    std::memcpy(&hi, &mm[1], sizeof hi);
+    const double fbins = hi / binwidth;  // bins = int(np.amax(err) / binwidth)
+    REQUIRE(fbins < (double)dsi::kScoreMaxBins + 1.0, DSI_ERR_INVALID, "max(err) / binwidth = %g: more than 2^24 bins", fbins);
+    const long long nb = (long long)fbins;
+    REQUIRE(nb <= dsi::kScoreMaxBins, DSI_ERR_INVALID, "more than 2^24 bins");
+    if (nb < 1) return DSI_OK;  // (numpy raises "`bins` must be positive")
+    dsi::ScoreBins B{};
+    B.first = lo;
+    B.last = hi;
+    if (lo == hi) {  // _get_outer_edges
+        B.first = lo - 0.5;
+        B.last = hi + 0.5;
+    }
+    B.delta = B.last - B.first;
+    B.nb = nb;
+    B.step = B.delta / (double)nb;
+    B.step_zero = B.step == 0.0;
+    *n_bins = (size_t)nb;
+    *first_edge = B.first;
+    *last_edge = B.last;
+    if (!counts) return DSI_OK;
+    REQUIRE(cap >= (size_t)nb, DSI_ERR_INVALID, "counts holds %zu bins, the histogram has %lld", cap, nb);
+    HIP_TRY(s->counts.reserve((size_t)nb));
+    HIP_TRY(dsi::launch_score_histogram(stream, s->buf, n, B, s->counts.p));
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "64-bit counts");
+    HIP_TRY(hipMemcpyAsync(counts, s->counts.p, (size_t)nb * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return DSI_OK;
 }
 
 int dsi_radius_outlier_removal(dsi_context_t* ctx, const float* xyz_host, size_t stride_floats, size_t n, float radius,

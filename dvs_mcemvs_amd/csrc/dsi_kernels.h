@@ -368,4 +368,33 @@ hipError_t launch_depth_images(hipStream_t s, const float* depth, const float* c
                                float min_depth, float max_depth, const uint8_t* lut_dev, uint32_t* mm, uint8_t* conf_negated,
                                uint8_t* inv_depth_bgr);
 
+// ---- depth-map scores against ground truth: depth_metrics.py:4-37, precision_completeness.py:43-92 ----
+// the accumulators of one score object, on the device; zero = empty
+struct ScoreState {
+    unsigned long long count[7];    // n_est, n_gt, n_joint, n_delta[0..2], n_bad
+    unsigned long long cursor;      // errors appended so far, dropped ones included (stored: min(cursor, capacity))
+    unsigned long long overflow;    // non-zero once an error was dropped
+    unsigned long long max_gt_key;  // bit pattern of the largest valid ground-truth depth (0: none)
+    double sum[4];                  // sum di, sum di^2, sum |d - g| / d, sum |g - d|
+};
+// np.histogram's uniform bins: delta = last - first, step = delta / nb (step_zero: it underflowed)
+struct ScoreBins {
+    double first, last, delta, step;
+    long long nb;
+    int step_zero;
+};
+constexpr int kScoreMaxBlocks = 512;                    // partials: 4 * kScoreMaxBlocks doubles
+constexpr long long kScoreMaxBins = 1ll << 24;
+constexpr size_t kScoreSelectWords = 4 + 8 * 2 * 256;   // launch_score_select's work area (64-bit words)
+// one map of n >= 1 pixels into st, its joint errors |g - d| appended to buf (capacity doubles; what does not fit is dropped
+// and st->overflow set); then st->sum += this map's sums.  The order of every addition depends on n alone.
+hipError_t launch_score_accumulate(hipStream_t s, const float* depth, const uint8_t* mask, const float* gt, size_t n, double gt_min,
+                                   double baseline, double focal, ScoreState* st, double* buf, size_t capacity, double* partials);
+// mm[0] / mm[1] = bit patterns of the smallest / largest of the n stored errors (all ones / zero when n == 0)
+hipError_t launch_score_minmax(hipStream_t s, const double* buf, size_t n, unsigned long long* mm);
+// counts[0 .. bins.nb) = np.histogram(buf[:n], bins=nb) over [first, last], which must hold every stored error
+hipError_t launch_score_histogram(hipStream_t s, const double* buf, size_t n, const ScoreBins& bins, unsigned long long* counts);
+// work[0] / work[1] = bit patterns of the elements of rank rank0 / rank1 (0-based, < n) of the n stored errors
+hipError_t launch_score_select(hipStream_t s, const double* buf, size_t n, size_t rank0, size_t rank1, unsigned long long* work);
+
 }  // namespace dsi

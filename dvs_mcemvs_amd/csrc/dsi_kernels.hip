@@ -7975,4 +7975,323 @@ hipError_t launch_depth_images(hipStream_t s, const float* depth, const float* c
     return hipSuccess;
 }
 
+
+// ------------------------------------------------ depth-map scores against ground truth ---
+// The metrics of depth_metrics.py:4-37 and the error histogram of precision_completeness.py:43-92 over every window added.
+namespace {
+
+constexpr int kScoreBlock = 256;  // four waves of 64
+
+__device__ __forceinline__ double score_wave_sum(double v)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;  // lane 0 holds the sum, always of the same tree
+}
+
+__device__ __forceinline__ unsigned long long score_wave_max(unsigned long long v)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_down(v, off, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// One pass over a map of n pixels.  Every count is a wave-uniform population count of a ballot, summed per block in LDS and
+// added to st with one integer atomic per counter and block.  The four float64 sums go lane -> wave (shuffles) -> block (LDS,
+// waves in order) into partials[blockIdx.x * 4 + k]: no floating-point atomic, so the same map gives the same bits.  A joint
+// pixel's err = |g - d| is appended at st->cursor, which each wave advances once per step by its number of joint pixels;
+// positions >= capacity are not written and raise st->overflow.  The loop is uniform per wave (all 64 lanes take every step).
+__global__ __launch_bounds__(kScoreBlock) void k_score_accumulate(const float* __restrict__ depth, const uint8_t* __restrict__ mask,
+                                                                  const float* __restrict__ gt, size_t n, double gt_min, double b,
+                                                                  double f, ScoreState* __restrict__ st, double* __restrict__ buf,
+                                                                  unsigned long long capacity, double* __restrict__ partials)
+{
+    __shared__ double sh_sum[kScoreBlock / 64][4];
+    __shared__ unsigned long long sh_cnt[kScoreBlock / 64][8];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double s_di = 0.0, s_di2 = 0.0, s_are = 0.0, s_abs = 0.0;
+    unsigned long long c_est = 0, c_gt = 0, c_joint = 0, c_d1 = 0, c_d2 = 0, c_d3 = 0, c_bad = 0, maxkey = 0;
+    bool over = false;
+    const size_t stride = (size_t)gridDim.x * kScoreBlock;
+    for (size_t base = (size_t)blockIdx.x * kScoreBlock; base < n; base += stride) {
+        const size_t i = base + threadIdx.x;
+        bool est = false, gtv = false;
+        double d = 1.0, g = 1.0;
+        if (i < n) {
+            const float df = depth[i], gf = gt[i];
+            d = (double)df;
+            g = (double)gf;
+            est = mask[i] != 0 && isfinite(df) && df > 0.f;
+            gtv = isfinite(gf) && g >= gt_min;
+        }
+        const bool joint = est && gtv;
+        if (gtv) {
+            const unsigned long long k = (unsigned long long)__double_as_longlong(g);  // g > 0: the bits order as the values
+            maxkey = k > maxkey ? k : maxkey;
+        }
+        bool d1 = false, d2 = false, d3 = false, bad = false;
+        double err = 0.0;
+        if (joint) {
+            const double ratio = fmax(d / g, g / d);                 // depth_metrics.py:9
+            d1 = ratio < 1.25;
+            d2 = ratio < 1.5625;
+            d3 = ratio < 1.953125;
+            const double di = log(g) - log(d);                       // :15
+            s_di += di;
+            s_di2 += di * di;
+            s_are += fabs(d - g) / d;                                // :20
+            err = fabs(g - d);
+            s_abs += err;
+            const double e = fabs(1.0 / d - 1.0 / g) * b * f;        // :26
+            const double r = e * g / b / f;                          // :27
+            bad = e > 5.0 && r > 0.05;                               // :28
+        }
+        const unsigned long long jb = __ballot(joint);
+        c_est += __popcll(__ballot(est));
+        c_gt += __popcll(__ballot(gtv));
+        c_joint += __popcll(jb);
+        c_d1 += __popcll(__ballot(d1));
+        c_d2 += __popcll(__ballot(d2));
+        c_d3 += __popcll(__ballot(d3));
+        c_bad += __popcll(__ballot(bad));
+        if (jb) {
+            const unsigned long long cnt = (unsigned long long)__popcll(jb);
+            unsigned long long start = 0;
+            if (lane == 0) start = atomicAdd(&st->cursor, cnt);
+            start = __shfl(start, 0, 64);
+            if (start + cnt > capacity) over = true;
+            const unsigned long long pos = start + (unsigned long long)__popcll(jb & ((1ull << lane) - 1ull));
+            if (joint && pos < capacity) buf[pos] = err;
+        }
+    }
+    s_di = score_wave_sum(s_di);
+    s_di2 = score_wave_sum(s_di2);
+    s_are = score_wave_sum(s_are);
+    s_abs = score_wave_sum(s_abs);
+    maxkey = score_wave_max(maxkey);
+    if (lane == 0) {
+        sh_sum[wave][0] = s_di;
+        sh_sum[wave][1] = s_di2;
+        sh_sum[wave][2] = s_are;
+        sh_sum[wave][3] = s_abs;
+        sh_cnt[wave][0] = c_est;
+        sh_cnt[wave][1] = c_gt;
+        sh_cnt[wave][2] = c_joint;
+        sh_cnt[wave][3] = c_d1;
+        sh_cnt[wave][4] = c_d2;
+        sh_cnt[wave][5] = c_d3;
+        sh_cnt[wave][6] = c_bad;
+        sh_cnt[wave][7] = maxkey;
+        if (over) atomicOr(&st->overflow, 1ull);
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        double p = sh_sum[0][threadIdx.x];
+        for (int w = 1; w < kScoreBlock / 64; ++w) p += sh_sum[w][threadIdx.x];
+        partials[(size_t)blockIdx.x * 4 + threadIdx.x] = p;
+    } else if (threadIdx.x >= 64 && threadIdx.x < 72) {
+        const int k = threadIdx.x - 64;
+        unsigned long long* dst = k < 7 ? &st->count[k] : &st->max_gt_key;
+        if (k < 7) {
+            unsigned long long c = 0;
+            for (int w = 0; w < kScoreBlock / 64; ++w) c += sh_cnt[w][k];
+            if (c) atomicAdd(dst, c);
+        } else {
+            unsigned long long c = 0;
+            for (int w = 0; w < kScoreBlock / 64; ++w) c = sh_cnt[w][7] > c ? sh_cnt[w][7] : c;
+            if (c) atomicMax(dst, c);
+        }
+    }
+}
+
+// st->sum[k] += the block partials of one k_score_accumulate, folded in an order that depends on nblocks alone: wave k takes
+// sum k, lane l adds partials l, l + 64, ... in turn, then the shuffle tree.  One block of four waves.
+__global__ __launch_bounds__(kScoreBlock) void k_score_finish(const double* __restrict__ partials, int nblocks, ScoreState* __restrict__ st)
+{
+    const int lane = threadIdx.x & 63, k = threadIdx.x >> 6;
+    double acc = 0.0;
+    for (int j = lane; j < nblocks; j += 64) acc += partials[(size_t)j * 4 + k];
+    acc = score_wave_sum(acc);
+    if (lane == 0) st->sum[k] = st->sum[k] + acc;
+}
+
+// extremes of the n stored errors as bit patterns (non-negative doubles order as integers): mm[0] = min (all ones before),
+// mm[1] = max (zero before)
+__global__ __launch_bounds__(kScoreBlock) void k_score_minmax(const double* __restrict__ buf, size_t n, unsigned long long* __restrict__ mm)
+{
+    unsigned long long lo = ~0ull, hi = 0ull;
+    const size_t stride = (size_t)gridDim.x * kScoreBlock;
+    for (size_t i = (size_t)blockIdx.x * kScoreBlock + threadIdx.x; i < n; i += stride) {
+        const unsigned long long k = (unsigned long long)__double_as_longlong(buf[i]);
+        lo = k < lo ? k : lo;
+        hi = k > hi ? k : hi;
+    }
+    hi = score_wave_max(hi);
+    lo = ~score_wave_max(~lo);
+    if ((threadIdx.x & 63) == 0 && lo <= hi) {
+        atomicMin(&mm[0], lo);
+        atomicMax(&mm[1], hi);
+    }
+}
+
+// numpy's linspace(first, last, nb + 1)[i]: arange * step + first, the last edge set to `last`; a step that underflows to
+// zero takes the (i / nb) * delta form
+__device__ __forceinline__ double score_edge(const ScoreBins& B, long long i)
+{
+    if (i == B.nb) return B.last;
+    return B.step_zero ? ((double)i / (double)B.nb) * B.delta + B.first : (double)i * B.step + B.first;
+}
+
+// np.histogram's uniform-bin index of x in [first, last] (numpy/lib/_histograms_impl.py, the fast path): truncate
+// ((x - first) / delta) * nb, fold nb into nb - 1, then correct by one against the edges; the last bin is closed on the right
+__device__ __forceinline__ long long score_bin(const ScoreBins& B, double x)
+{
+    long long idx = (long long)(((x - B.first) / B.delta) * (double)B.nb);
+    if (idx == B.nb) --idx;
+    idx = idx < 0 ? 0 : (idx > B.nb - 1 ? B.nb - 1 : idx);  // (no effect on values inside the range; keeps every access in bounds)
+    if (x < score_edge(B, idx) && idx > 0) --idx;
+    if (x >= score_edge(B, idx + 1) && idx != B.nb - 1) ++idx;
+    return idx;
+}
+
+constexpr int kScoreLdsBins = 8192;  // 32 KiB of 32-bit LDS counters
+
+// counts[bin] += the number of stored errors per bin.  LDSBINS (nb <= kScoreLdsBins): 32-bit LDS atomics, then one 64-bit
+// global atomic per non-empty bin and block; otherwise 64-bit global atomics.
+template <bool LDSBINS>
+__global__ __launch_bounds__(kScoreBlock) void k_score_histogram(const double* __restrict__ buf, size_t n, ScoreBins B,
+                                                                 unsigned long long* __restrict__ counts)
+{
+    __shared__ uint32_t bins[LDSBINS ? kScoreLdsBins : 1];
+    const int nb = (int)B.nb;
+    if (LDSBINS) {
+        for (int k = threadIdx.x; k < nb; k += kScoreBlock) bins[k] = 0u;
+        __syncthreads();
+    }
+    const size_t stride = (size_t)gridDim.x * kScoreBlock;
+    for (size_t i = (size_t)blockIdx.x * kScoreBlock + threadIdx.x; i < n; i += stride) {
+        const long long idx = score_bin(B, buf[i]);
+        if (LDSBINS)
+            atomicAdd(&bins[idx], 1u);
+        else
+            atomicAdd(&counts[idx], 1ull);
+    }
+    if (LDSBINS) {
+        __syncthreads();
+        for (int k = threadIdx.x; k < nb; k += kScoreBlock)
+            if (bins[k]) atomicAdd(&counts[k], (unsigned long long)bins[k]);
+    }
+}
+
+// Radix select on the bit patterns, most significant byte first (pass 0 .. 7), of two ranks at once.  sel[0..1]: the bytes
+// chosen so far for each rank (zero before pass 0), hist: [8][2][256] counters, zero before pass 0.  This pass counts, per
+// rank, the next byte of the errors whose higher bytes equal that rank's.
+__global__ __launch_bounds__(kScoreBlock) void k_score_select(const double* __restrict__ buf, size_t n, const unsigned long long* __restrict__ sel,
+                                                              int pass, unsigned long long* __restrict__ hist)
+{
+    __shared__ uint32_t h[2][256];
+    h[0][threadIdx.x] = 0u;
+    h[1][threadIdx.x] = 0u;
+    __syncthreads();
+    const int shift = 56 - 8 * pass;
+    // the bytes above `shift`: (key >> shift) >> 8 keeps the shift count below 64 in pass 0
+    const unsigned long long p0 = (sel[0] >> shift) >> 8, p1 = (sel[1] >> shift) >> 8;
+    const size_t stride = (size_t)gridDim.x * kScoreBlock;
+    for (size_t i = (size_t)blockIdx.x * kScoreBlock + threadIdx.x; i < n; i += stride) {
+        const unsigned long long k = (unsigned long long)__double_as_longlong(buf[i]) >> shift;
+        const unsigned long long hi = k >> 8;
+        const uint32_t dg = (uint32_t)(k & 255ull);
+        if (hi == p0) atomicAdd(&h[0][dg], 1u);
+        if (hi == p1) atomicAdd(&h[1][dg], 1u);
+    }
+    __syncthreads();
+    unsigned long long* out = hist + (size_t)pass * 512;
+    if (h[0][threadIdx.x]) atomicAdd(&out[threadIdx.x], (unsigned long long)h[0][threadIdx.x]);
+    if (h[1][threadIdx.x]) atomicAdd(&out[256 + threadIdx.x], (unsigned long long)h[1][threadIdx.x]);
+}
+
+// After pass `pass`: for each rank, the byte whose bucket holds it (exclusive prefix <= rank < inclusive prefix) joins
+// sel[j], and sel[2 + j] becomes the rank inside that bucket.  Pass 0 takes the ranks from rank0 / rank1.  One block.
+__global__ __launch_bounds__(kScoreBlock) void k_score_select_pick(unsigned long long* __restrict__ sel, int pass,
+                                                                   const unsigned long long* __restrict__ hist, unsigned long long rank0,
+                                                                   unsigned long long rank1)
+{
+    __shared__ unsigned long long scan[2][256];
+    const int t = threadIdx.x, shift = 56 - 8 * pass;
+    for (int j = 0; j < 2; ++j) {
+        const unsigned long long c = hist[(size_t)pass * 512 + j * 256 + t];
+        const unsigned long long r = pass == 0 ? (j ? rank1 : rank0) : sel[2 + j];
+        int cur = 0;
+        scan[0][t] = c;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {  // Hillis-Steele inclusive scan, ping-pong
+            const unsigned long long v = scan[cur][t] + (t >= off ? scan[cur][t - off] : 0ull);
+            scan[cur ^ 1][t] = v;
+            cur ^= 1;
+            __syncthreads();
+        }
+        const unsigned long long incl = scan[cur][t], excl = incl - c;
+        __syncthreads();  // everyone has read sel[2 + j] and the scan before the one owner writes
+        if (excl <= r && r < incl) {
+            sel[j] |= (unsigned long long)t << shift;
+            sel[2 + j] = r - excl;
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace
+
+static int score_blocks(size_t n)
+{
+    const size_t b = (n + kScoreBlock - 1) / kScoreBlock;
+    return (int)(b < 1 ? 1 : (b > (size_t)kScoreMaxBlocks ? (size_t)kScoreMaxBlocks : b));
+}
+
+hipError_t launch_score_accumulate(hipStream_t s, const float* depth, const uint8_t* mask, const float* gt, size_t n, double gt_min,
+                                   double baseline, double focal, ScoreState* st, double* buf, size_t capacity, double* partials)
+{
+    if (!depth || !mask || !gt || !st || !buf || !partials || n == 0) return hipErrorInvalidValue;
+    const int blocks = score_blocks(n);  // a function of n alone: the order of every sum is
+    hipLaunchKernelGGL(k_score_accumulate, dim3(blocks), dim3(kScoreBlock), 0, s, depth, mask, gt, n, gt_min, baseline, focal, st, buf,
+                       (unsigned long long)capacity, partials);
+    hipLaunchKernelGGL(k_score_finish, dim3(1), dim3(kScoreBlock), 0, s, partials, blocks, st);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_score_minmax(hipStream_t s, const double* buf, size_t n, unsigned long long* mm)
+{
+    hipError_t e = hipMemsetAsync(mm, 0xff, sizeof(unsigned long long), s);
+    if (e == hipSuccess) e = hipMemsetAsync(mm + 1, 0, sizeof(unsigned long long), s);
+    if (e != hipSuccess || n == 0) return e;
+    hipLaunchKernelGGL(k_score_minmax, dim3(score_blocks(n)), dim3(kScoreBlock), 0, s, buf, n, mm);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_score_histogram(hipStream_t s, const double* buf, size_t n, const ScoreBins& bins, unsigned long long* counts)
+{
+    if (bins.nb < 1 || bins.nb > kScoreMaxBins || !(bins.delta > 0.0)) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(counts, 0, (size_t)bins.nb * sizeof(unsigned long long), s);
+    if (e != hipSuccess || n == 0) return e;
+    if (bins.nb <= kScoreLdsBins)
+        hipLaunchKernelGGL(k_score_histogram<true>, dim3(score_blocks(n)), dim3(kScoreBlock), 0, s, buf, n, bins, counts);
+    else
+        hipLaunchKernelGGL(k_score_histogram<false>, dim3(score_blocks(n)), dim3(kScoreBlock), 0, s, buf, n, bins, counts);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_score_select(hipStream_t s, const double* buf, size_t n, size_t rank0, size_t rank1, unsigned long long* work)
+{
+    if (n == 0 || rank0 >= n || rank1 >= n) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(work, 0, kScoreSelectWords * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    for (int pass = 0; pass < 8; ++pass) {
+        hipLaunchKernelGGL(k_score_select, dim3(score_blocks(n)), dim3(kScoreBlock), 0, s, buf, n, work, pass, work + 4);
+        hipLaunchKernelGGL(k_score_select_pick, dim3(1), dim3(kScoreBlock), 0, s, work, pass, work + 4, (unsigned long long)rank0,
+                           (unsigned long long)rank1);
+    }
+    return hipExtGetLastError();
+}
+
 }  // namespace dsi

@@ -82,6 +82,14 @@ class _VoteInfo(C.Structure):
                 ("n_packets", C.c_size_t), ("packed", C.c_int), ("group_packets", C.c_int)]
 
 
+class _ScoreMetrics(C.Structure):
+    _fields_ = [("n_est", C.c_uint64), ("n_gt", C.c_uint64), ("n_joint", C.c_uint64), ("n_delta", C.c_uint64 * 3),
+                ("n_bad", C.c_uint64), ("n_stored", C.c_uint64), ("overflow", C.c_int32), ("guard_intact", C.c_int32),
+                ("sum_di", C.c_double), ("sum_di2", C.c_double), ("sum_are", C.c_double), ("sum_abs", C.c_double),
+                ("max_gt", C.c_double), ("delta", C.c_double * 3), ("silog", C.c_double), ("are", C.c_double),
+                ("lrmse", C.c_double), ("badp", C.c_double), ("mean_abs", C.c_double), ("median_abs", C.c_double)]
+
+
 def experiments_requested():
     """DSI_ENGINE_EXPERIMENTS=1 in the environment of THIS process: load the experiments flavour of the library
     (libdsi_engine_experiments.so: environment knobs + dsi_test_* hooks of the timing experiments, some of which make
@@ -220,6 +228,15 @@ def load_library():
         "dsi_depth_images": (C.c_int, [vp, f32p, f32p, u8p, C.c_int, C.c_int, C.c_float, C.c_float, u8p, u8p, u8p]),
         "dsi_mapper_depth_images": (C.c_int, [vp, C.c_float, C.c_float, u8p, u8p, u8p]),
         "dsi_default_jet_lut": (C.c_int, [u8p]),
+        "dsi_score_create": (C.c_int, [vp, C.c_size_t, C.c_double, C.c_double, C.c_double, C.POINTER(vp)]),
+        "dsi_score_destroy": (C.c_int, [vp]),
+        "dsi_score_reset": (C.c_int, [vp]),
+        "dsi_score_add": (C.c_int, [vp, f32p, u8p, f32p, C.c_size_t]),
+        "dsi_score_add_dev": (C.c_int, [vp, vp, vp, vp, C.c_size_t]),
+        "dsi_score_add_mapper": (C.c_int, [vp, vp, f32p]),
+        "dsi_score_metrics": (C.c_int, [vp, C.POINTER(_ScoreMetrics)]),
+        "dsi_score_median": (C.c_int, [vp, f64p]),
+        "dsi_score_histogram": (C.c_int, [vp, C.c_double, u64p, C.c_size_t, szp, f64p, f64p]),
         "dsi_mapper_last_vote_info": (C.c_int, [vp, C.POINTER(_VoteInfo)]),
         "dsi_mapper_set_kernel_timing": (C.c_int, [vp, C.c_int]),
         "dsi_mapper_vote_kernel_time": (C.c_int, [vp, f32p, intp]),
@@ -930,6 +947,98 @@ def depth_images(ctx, depth, conf, mask, min_depth, max_depth, lut=None):
                                            C.c_float(min_depth), C.c_float(max_depth),
                                            None if lut is None else _ptr(lut, C.c_uint8), _ptr(neg, C.c_uint8), _ptr(bgr, C.c_uint8)))
     return neg, bgr
+
+
+class DepthScore:
+    """Depth maps scored against ground-truth depth on the device (dsi_score_*): what the reference's
+    scripts/depth_metrics.py and precision_completeness.py compute over the consolidated (windows x H x W) stack, from maps
+    added one window at a time.  capacity_points: how many joint pixels' errors the object can hold for the median and the
+    curves (8 bytes each); baseline, focal: the b and f of the bad-pixel measure; gt_min: ground truth below it (or not
+    finite) is no measurement (the script's 0.05)."""
+
+    def __init__(self, ctx, capacity_points, baseline, focal, gt_min=0.05):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        _check(load_library().dsi_score_create(ctx._h, int(capacity_points), float(baseline), float(focal), float(gt_min),
+                                               C.byref(self._h)))
+        _track(self)
+
+    def add(self, depth, mask, gt):
+        """One window: estimated depth (float32), its mask (non-zero = estimated) and the ground-truth depth, arrays of one
+        shape.  Queued on the context's stream."""
+        depth, mask, gt = _arr(depth, np.float32), _arr(np.asarray(mask) != 0, np.uint8), _arr(gt, np.float32)
+        if depth.shape != mask.shape or depth.shape != gt.shape:
+            raise ValueError("depth, mask and gt must have one shape")
+        _check(load_library().dsi_score_add(self._h, _ptr(depth, C.c_float), _ptr(mask, C.c_uint8), _ptr(gt, C.c_float),
+                                            depth.size))
+
+    def addMapper(self, mapper, gt):
+        """One window from the filtered depth map and mask that mapper.getDepthMapFromDSI(..., options_depth_map) /
+        filterDepthMap left on the device: only gt is uploaded."""
+        gt = _arr(gt, np.float32)
+        if gt.shape != (mapper.dimY, mapper.dimX):
+            raise ValueError("gt must have the mapper's (dimY, dimX) shape")
+        _check(load_library().dsi_score_add_mapper(self._h, mapper._h, _ptr(gt, C.c_float)))
+
+    def metrics(self):
+        """dict of the counts (n_est, n_gt, n_joint, n_delta, n_bad, n_stored), overflow, the raw sums (sum_di, sum_di2,
+        sum_are, sum_abs), max_gt and the derived delta (3), silog, are, lrmse, badp, mean_abs, median_abs.  After an overflow
+        median_abs is NaN; without a joint pixel every real-valued entry is."""
+        m = _ScoreMetrics()
+        _check(load_library().dsi_score_metrics(self._h, C.byref(m)))
+        out = {k: int(getattr(m, k)) for k in ("n_est", "n_gt", "n_joint", "n_bad", "n_stored")}
+        out["n_delta"] = [int(v) for v in m.n_delta]
+        out["overflow"] = bool(m.overflow)
+        out["guard_intact"] = bool(m.guard_intact)
+        for k in ("sum_di", "sum_di2", "sum_are", "sum_abs", "max_gt", "silog", "are", "lrmse", "badp", "mean_abs", "median_abs"):
+            out[k] = float(getattr(m, k))
+        out["delta"] = [float(v) for v in m.delta]
+        return out
+
+    def median(self):
+        """np.ma.median of the absolute error; raises DsiError after an overflow."""
+        v = C.c_double()
+        _check(load_library().dsi_score_median(self._h, C.byref(v)))
+        return v.value
+
+    def histogram(self, binwidth=0.01):
+        """(counts int64 [n_bins], first_edge, last_edge) of np.histogram(err, bins=int(max(err) / binwidth)); n_bins may be 0."""
+        L = load_library()
+        n, lo, hi = C.c_size_t(), C.c_double(), C.c_double()
+        _check(L.dsi_score_histogram(self._h, float(binwidth), None, 0, C.byref(n), C.byref(lo), C.byref(hi)))
+        counts = np.zeros(n.value, np.uint64)
+        if n.value:
+            _check(L.dsi_score_histogram(self._h, float(binwidth), _ptr(counts, C.c_uint64), counts.size, C.byref(n), C.byref(lo),
+                                         C.byref(hi)))
+        return counts.astype(np.int64), lo.value, hi.value
+
+    def curves(self, binwidth=0.01):
+        """precision_completeness.py:43-92: dict of base (the bins' left edges), precision, recall, f1 and outliers (per
+        cent, cumulative over the error bins), host arithmetic on the exact counts as the script writes it."""
+        m = self.metrics()
+        counts, lo, hi = self.histogram(binwidth)
+        if counts.size == 0:
+            empty = np.zeros(0)
+            return {"base": empty, "precision": empty, "recall": empty, "f1": empty, "outliers": empty}
+        base = np.linspace(lo, hi, counts.size + 1)[:-1]
+        cum = np.cumsum(counts)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            precision = cum / m["n_est"] * 100
+            recall = cum / m["n_gt"] * 100
+            f1 = 2 * precision * recall / (precision + recall)
+            outliers = (m["n_joint"] - cum) / m["n_joint"] * 100
+        return {"base": base, "precision": precision, "recall": recall, "f1": f1, "outliers": outliers}
+
+    def reset(self):
+        _check(load_library().dsi_score_reset(self._h))
+
+    def close(self):
+        if self._h:
+            load_library().dsi_score_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        _safe_del(self)
 
 
 class PinnedArray:

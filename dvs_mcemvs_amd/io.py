@@ -6,6 +6,7 @@ trajectories can be replayed without ROS:
   write_png_gray8       cv::imwrite of a CV_8UC1 slice  cartesian3dgrid_IO.cpp:74              (.png, 8-bit grayscale)
   write_png_rgb8        cv::imwrite of a CV_8UC3 image  utils.cpp:93                            (.png, 8-bit colour, from B G R)
   save_depth_points     saveDepthMaps (txt part)        utils.cpp:31-46                ("col row depth" lines)
+  load_depth_points     its inverse, as scripts/evaluate_mcemvs_dsec.py:69-79 reads it (255 = no estimate)
   save_depth_maps       saveDepthMaps                   utils.cpp:22-104               (the txt and the two .png it writes)
   save_pcd_ascii        pcl::io::savePCDFileASCII       main.cpp:397-402               (.pcd v0.7, PointXYZI, ascii)
   read_pose_bag         parse of geometry_msgs/PoseStamped bags   data_loading.cpp:221-302 (ROSBAG v2.0; none / bz2 chunks)
@@ -98,6 +99,28 @@ def save_depth_points(path, depth_map, mask):
         for r, c in zip(rows, cols):
             f.write("%d %d %g\n" % (c, r, depth_map[r, c]))
     return rows.shape[0]
+
+
+def load_depth_points(path, height, width, no_estimate=255.0):
+    """The inverse of save_depth_points, as scripts/evaluate_mcemvs_dsec.py:69-79 reads a run's depth_points_*.txt:
+    (depth float32 [height][width], mask uint8) from "col row depth" lines; a later line for a pixel replaces an earlier
+    one.  A depth of exactly `no_estimate` counts as no estimate, because the script marks empty pixels with 255 and masks
+    every pixel that equals it.  An empty file gives an empty mask.  Pixels outside height x width raise ValueError."""
+    depth = np.zeros((int(height), int(width)), np.float32)
+    mask = np.zeros((int(height), int(width)), np.uint8)
+    with open(path) as f:
+        vals = np.array(f.read().split(), np.float64)
+    if vals.size % 3:
+        raise ValueError("%s: expected lines of 'col row depth'" % path)
+    pts = vals.reshape(-1, 3)
+    if pts.shape[0]:
+        c, r = pts[:, 0].astype(int), pts[:, 1].astype(int)
+        if c.min() < 0 or r.min() < 0 or c.max() >= width or r.max() >= height:
+            raise ValueError("%s: a point lies outside %d x %d" % (path, width, height))
+        depth[r, c] = pts[:, 2]
+        mask[r, c] = pts[:, 2] != no_estimate
+        depth[mask == 0] = 0
+    return depth, mask
 
 
 def save_pcd_ascii(path, points):

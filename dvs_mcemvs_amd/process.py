@@ -735,7 +735,8 @@ class WindowStream:
 
 def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop_time_s, duration,
                   out_skip, fusion_method=E.FUSE_HM, forward_looking=True, rv_pos=0.0, options_depth_map=None,
-                  options_point_cloud=None, polarities=None, save_images=False, out_path=None, lut=None, **kw):
+                  options_point_cloud=None, polarities=None, save_images=False, out_path=None, lut=None, score=None,
+                  ground_truth=None, **kw):
     """Generator over the windows of main.cpp:177-302: yields (ts, depth, confidence, indices) per
     window, pipelined one window deep; with options_depth_map, (ts, depth_map, confidence_map, mask)
     -- the filtered outputs the reference saves per window; with options_point_cloud as well, the window's
@@ -753,7 +754,16 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
     EventBatch.event_image instead, which uploads the polarity bytes only.  out_path and lut are keywords of this path
     alone.  With out_path (a prefix, like --out_path) they are written as well:
     out_path + "%f" % ts + "events_<c>.png" (main.cpp:251) and saveDepthMaps' three files as process1.cpp:121-122, 223 names
-    them: prefix out_path + "%013.9f" % ts, suffix "fused_<fusion_method>"."""
+    them: prefix out_path + "%013.9f" % ts, suffix "fused_<fusion_method>".
+    score= (an engine.DepthScore) with ground_truth= (a callable ts -> ground-truth depth map of the DSI's (dimY, dimX), or
+    None for a window without one: nearest_ground_truth picks the frame as the reference's script does): every window's
+    filtered depth map and mask -- the host arrays this generator yields anyway, for process_method 2 / 5 those of the
+    time_camera output -- are added to the score against that window's ground truth before the window is yielded.  Needs
+    options_depth_map.  Nothing more is downloaded for it; the caller reads score.metrics() / score.curves() at the end."""
+    if (score is None) != (ground_truth is None):
+        raise ValueError("score and ground_truth go together")
+    if score is not None and options_depth_map is None:
+        raise ValueError("score needs options_depth_map: the filtered depth maps are what is scored")
     if options_point_cloud is not None and options_depth_map is None:
         raise ValueError("options_point_cloud needs options_depth_map: the point cloud is made of the filtered maps")
     if save_images:
@@ -771,6 +781,7 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
     ws = WindowStream(ctx, cams, dsi_shape, fusion_method, **kw)
     pending = None
     images = None
+    scoring = None if score is None else (score, ground_truth)
     if save_images:
         images = {"fusion_method": int(fusion_method), "min_depth": dsi_shape.min_depth_, "max_depth": dsi_shape.max_depth_, "out_path": out_path,
                   "lut": lut}
@@ -784,10 +795,10 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
                                                     cams[0]) for c in range(2)]       # cam0.fullResolution(), :246
             slot = ws.submit(ev, trajectories, ts, rv_pos)
             if pending is not None:
-                yield _window_result(ws, pending, options_depth_map, options_point_cloud, images)
+                yield _window_result(ws, pending, options_depth_map, options_point_cloud, images, scoring)
             pending = (ts, slot, event_images)
         if pending is not None:
-            yield _window_result(ws, pending, options_depth_map, options_point_cloud, images)
+            yield _window_result(ws, pending, options_depth_map, options_point_cloud, images, scoring)
     finally:
         ws.close()
 
@@ -801,8 +812,24 @@ def _window_event_image(ctx, events, polarity, t_start, t_stop, cam):
     return E.accumulate_events(ctx, x, y, np.asarray(polarity)[a:b], int(cam[0]), int(cam[1]), True)
 
 
-def _window_result(ws, pending, options_depth_map, options_point_cloud, images=None):
+def nearest_ground_truth(gt_times, t, max_dt=0.1):
+    """evaluate_mcemvs_dsec.py:98-105: the index of the ground-truth frame nearest in time to t (gt_times and t in one
+    unit and origin; the first of equally near frames, as argmin), or None when even that one is max_dt or more away --
+    the script skips such a window."""
+    gt_times = np.asarray(gt_times, np.float64)
+    if gt_times.ndim != 1 or gt_times.size == 0:
+        return None
+    i = int(np.abs(gt_times - float(t)).argmin())
+    return None if abs(float(gt_times[i]) - float(t)) >= max_dt else i
+
+
+def _window_result(ws, pending, options_depth_map, options_point_cloud, images=None, scoring=None):
     out = ws.fetch(pending[1], options_depth_map, options_point_cloud)
+    if scoring is not None:
+        gt = scoring[1](pending[0])
+        if gt is not None:
+            maps = out if ws.process_method == 1 else out[0]
+            scoring[0].add(maps[0], maps[2], gt)
     if images is not None:
         from . import io as _io
         ts = pending[0]

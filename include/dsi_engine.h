@@ -815,6 +815,63 @@ DSI_API int dsi_mapper_depth_images(dsi_mapper_t *m, float min_depth, float max_
  * b = clamp01(1.5 - |4t - 1|), each x 255 in double, rounded to nearest (ties to even) */
 DSI_API int dsi_default_jet_lut(uint8_t *lut_bgr);
 
+/* ---- scoring depth maps against ground-truth depth (scripts/depth_metrics.py:4-37, precision_completeness.py:43-92,
+ * evaluate_mcemvs_dsec.py:127-141; definitions: DESIGN.md 7f) ----
+ * A score object lives on the device of its context.  Maps are added one window at a time; the metrics and the error
+ * histogram are those of the reference's scripts over the consolidated (windows x H x W) stack.  Per pixel, with estimate d,
+ * ground truth g (float32, taken to float64 exactly; all arithmetic in float64 without contraction):
+ *   est_valid = mask != 0 && isfinite(d) && d > 0;   gt_valid = isfinite(g) && g >= gt_min;   joint = both.
+ * Counts (exact): n_est, n_gt, n_joint, n_delta[k] = #joint with max(d/g, g/d) < 1.25, 1.5625, 1.953125, n_bad = #joint with
+ * e > 5 && r > 0.05, e = fabs(1/d - 1/g) * baseline * focal, r = e * g / baseline / focal (left to right).
+ * Sums over the joint pixels: di = log(g) - log(d): sum_di, sum_di2; sum_are = sum fabs(d - g) / d; sum_abs = sum fabs(g - d);
+ * max_gt over the gt_valid pixels.  The sums are reduced in a fixed order (no floating-point atomics): the same adds in the
+ * same order give the same bits.  Each joint pixel's fabs(g - d) is also stored (8 bytes; capacity_points of them), which the
+ * median and the histogram read; what does not fit is dropped, never written out of bounds, and `overflow` is set. */
+typedef struct dsi_score dsi_score_t;
+typedef struct dsi_score_metrics {
+    uint64_t n_est, n_gt, n_joint, n_delta[3], n_bad;
+    uint64_t n_stored;  /* errors held in the buffer: min(n_joint, capacity_points) */
+    int32_t overflow;   /* non-zero: n_joint > capacity_points; median_abs is NaN and dsi_score_median / _histogram refuse */
+    int32_t guard_intact; /* the 64 words the object keeps behind its buffer still hold their pattern (always 1) */
+    double sum_di, sum_di2, sum_are, sum_abs, max_gt;
+    /* derived as the scripts write them, n = n_joint: delta[k] = n_delta[k] / n; silog = 1/n * sum_di2 - 1/(n*n) * sum_di^2;
+     * are = 1/n * sum_are; lrmse = sqrt(1/n * sum_di2); badp = n_bad / n; mean_abs = sum_abs / n; median_abs = np.ma.median:
+     * the middle stored error, or (lower + upper) / 2 of the two middle ones when n is even.  n == 0: all NaN
+     * (max_gt: NaN when n_gt == 0). */
+    double delta[3], silog, are, lrmse, badp, mean_abs, median_abs;
+} dsi_score_metrics_t;
+/* capacity_points >= 1 (8 bytes each), baseline > 0, focal > 0 (the b and f of depth_metrics.py:26-27), gt_min > 0 (the script's
+ * 0.05, evaluate_mcemvs_dsec.py:122), all finite, else DSI_ERR_INVALID.  The context refuses to be destroyed before its scores. */
+DSI_API int dsi_score_create(dsi_context_t *ctx, size_t capacity_points, double baseline, double focal, double gt_min,
+                             dsi_score_t **out);
+DSI_API int dsi_score_destroy(dsi_score_t *s);
+/* forgets every map added (the buffer's contents included); ordered on the context's stream */
+DSI_API int dsi_score_reset(dsi_score_t *s);
+/* adds one map of n_pixels >= 1 pixels from host arrays (depth f32, mask u8, ground truth f32): uploaded and scored on the
+ * context's stream, without a synchronise -- arrays in page-locked memory must stay unchanged until the stream has run */
+DSI_API int dsi_score_add(dsi_score_t *s, const float *depth_host, const uint8_t *mask_host, const float *gt_host,
+                          size_t n_pixels);
+/* same, the three arrays on the score's device; ordered on the context's stream */
+DSI_API int dsi_score_add_dev(dsi_score_t *s, const float *depth_dev, const uint8_t *mask_dev, const float *gt_dev,
+                              size_t n_pixels);
+/* same, of the filtered depth map and mask that the last dsi_mapper_filter_depth_map / dsi_mapper_get_depth_map_from_dsi
+ * left on the device (what dsi_mapper_depth_images reads; DSI_ERR_INVALID if there are none) against gt_host[ny * nx]: only
+ * the ground truth travels.  The mapper must belong to the score's context, else DSI_ERR_CONTEXT. */
+DSI_API int dsi_score_add_mapper(dsi_score_t *s, dsi_mapper_t *m, const float *gt_host);
+/* everything above; after an overflow all but median_abs (NaN) stays valid.  Synchronises. */
+DSI_API int dsi_score_metrics(dsi_score_t *s, dsi_score_metrics_t *out);
+/* median_abs alone (a 64-bit radix select on the bit patterns of the stored errors): NaN when n_joint == 0;
+ * DSI_ERR_INVALID after an overflow.  Synchronises. */
+DSI_API int dsi_score_median(dsi_score_t *s, double *median_abs);
+/* np.histogram(err, bins = int(max(err) / binwidth)) of the stored errors, bin for bin: *n_bins uniform bins over
+ * [*first_edge, *last_edge] = [min(err), max(err)] (widened by -+0.5 when equal), numpy's index arithmetic with its edge
+ * correction against np.linspace's edges, the last bin closed on the right.  counts == NULL: only *n_bins and the edges
+ * are returned (ask, allocate, call again); otherwise cap >= *n_bins counts are written, and cap < *n_bins is
+ * DSI_ERR_INVALID with *n_bins set.  Zero bins (no joint pixel, or max(err) < binwidth: numpy raises there) is DSI_OK with
+ * *n_bins = 0.  DSI_ERR_INVALID: binwidth not finite or <= 0, more than 2^24 bins, or after an overflow.  Synchronises. */
+DSI_API int dsi_score_histogram(dsi_score_t *s, double binwidth, uint64_t *counts, size_t cap, size_t *n_bins,
+                                double *first_edge, double *last_edge);
+
 /* pcl::RadiusOutlierRemoval (radius_outlier_removal.hpp, dense cloud) on its own: point i of the n points xyz_host
  * (stride_floats = 3 or 4 floats per point; x, y, z first) is kept (keep_host[i] = 1) iff at least min_neighbors + 1
  * points j -- j = i and duplicates included -- satisfy (double) d2(i, j) <= (double) radius * (double) radius, with

@@ -1226,6 +1226,91 @@ inline void saveDepthMaps(Context& ctx, const DepthImg& depth_map, const ConfImg
     if (inv_depth_bgr) inv_depth_bgr->swap(bgr);
 }
 
+// Depth maps scored against ground-truth depth on the device (dsi_score_*): the metrics of the reference's
+// scripts/depth_metrics.py and the curves of precision_completeness.py over every window added.  Images are of any type
+// dsi::image_data reads (cv::Mat CV_32FC1 / CV_8UC1, dsi::Image<T>).
+struct ScoreCurves {  // precision_completeness.py:43-92, one entry per error bin
+    std::vector<double> base, precision, recall, f1, outliers;
+};
+class DepthScore {
+public:
+    DepthScore(Context& ctx, size_t capacity_points, double baseline, double focal, double gt_min = 0.05)
+    {
+        check(dsi_score_create(ctx.handle(), capacity_points, baseline, focal, gt_min, &h_));
+    }
+    ~DepthScore() { dsi_score_destroy(h_); }
+    DepthScore(const DepthScore&) = delete;
+    DepthScore& operator=(const DepthScore&) = delete;
+    dsi_score_t* handle() const { return h_; }
+
+    // one window: the estimated depth (f32), its mask (u8, non-zero = estimated) and the ground truth (f32), of one size
+    template <typename DepthImg, typename MaskImg, typename GtImg>
+    void add(const DepthImg& depth_map, const MaskImg& mask, const GtImg& ground_truth)
+    {
+        if (mask.rows != depth_map.rows || mask.cols != depth_map.cols || ground_truth.rows != depth_map.rows ||
+            ground_truth.cols != depth_map.cols)
+            throw Error(DSI_ERR_INVALID, "DepthScore::add: the three maps must have one size");
+        check(dsi_score_add(h_, dsi::image_data<float>(const_cast<DepthImg&>(depth_map)),
+                            dsi::image_data<uint8_t>(const_cast<MaskImg&>(mask)),
+                            dsi::image_data<float>(const_cast<GtImg&>(ground_truth)), (size_t)depth_map.rows * depth_map.cols));
+    }
+    // one window from the filtered maps a mapper's getDepthMapFromDSI(..., options) left on the device
+    template <typename MapperT, typename GtImg>
+    void addMapper(MapperT& mapper, const GtImg& ground_truth)
+    {
+        check(dsi_score_add_mapper(h_, mapper.handle(), dsi::image_data<float>(const_cast<GtImg&>(ground_truth))));
+    }
+    dsi_score_metrics_t metrics() const
+    {
+        dsi_score_metrics_t m;
+        check(dsi_score_metrics(h_, &m));
+        return m;
+    }
+    double median() const
+    {
+        double v = 0;
+        check(dsi_score_median(h_, &v));
+        return v;
+    }
+    // np.histogram(err, bins = int(max(err) / binwidth)): the counts; [first_edge, last_edge] is the range
+    std::vector<uint64_t> histogram(double binwidth, double* first_edge = nullptr, double* last_edge = nullptr) const
+    {
+        size_t n = 0;
+        double lo = 0, hi = 0;
+        check(dsi_score_histogram(h_, binwidth, nullptr, 0, &n, &lo, &hi));
+        std::vector<uint64_t> counts(n);
+        if (n) check(dsi_score_histogram(h_, binwidth, counts.data(), n, &n, &lo, &hi));
+        if (first_edge) *first_edge = lo;
+        if (last_edge) *last_edge = hi;
+        return counts;
+    }
+    // host arithmetic on the exact counts, written as the script writes it; base = np.linspace(first, last, bins + 1)[:-1]
+    ScoreCurves curves(double binwidth = 0.01) const
+    {
+        const dsi_score_metrics_t m = metrics();
+        double lo = 0, hi = 0;
+        const std::vector<uint64_t> counts = histogram(binwidth, &lo, &hi);
+        ScoreCurves c;
+        const size_t nb = counts.size();
+        const double delta = hi - lo, step = nb ? delta / (double)nb : 0.0;
+        uint64_t cum = 0;
+        for (size_t i = 0; i < nb; ++i) {
+            cum += counts[i];
+            c.base.push_back(step != 0.0 ? (double)i * step + lo : ((double)i / (double)nb) * delta + lo);
+            const double p = (double)cum / (double)m.n_est * 100.0, r = (double)cum / (double)m.n_gt * 100.0;
+            c.precision.push_back(p);
+            c.recall.push_back(r);
+            c.f1.push_back(2.0 * p * r / (p + r));
+            c.outliers.push_back((double)(m.n_joint - cum) / (double)m.n_joint * 100.0);
+        }
+        return c;
+    }
+    void reset() { check(dsi_score_reset(h_)); }
+
+private:
+    dsi_score_t* h_ = nullptr;
+};
+
 }  // namespace dsi
 
 // the reference's spellings (utils.hpp:23-52), on the process-wide default context: main.cpp:249-250 and
