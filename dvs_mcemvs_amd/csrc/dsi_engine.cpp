@@ -340,6 +340,9 @@ struct dsi_mapper {
     // 512 x 512 x 200: a phase without records takes 8.6 us, a full one 18.7 us for ~38 k records)
     DevBuf<uint32_t> pair_work, fused_splits;
     DevBuf<unsigned long long> fused_prefix;
+#ifdef DSI_TIMING_EXPERIMENTS
+    int fused_solo = -1;  // test hook dsi_test_fused_solo: >= 0 = one workgroup acting as workgroup 0 of that XCD
+#endif
     int fused_fixed_cost = -1;  // < 0: equal pair counts per workgroup (default: balancing by records did not pay at
                                 // 512 x 512 x 200 -- 446 vs 447 us, the slow workgroups are slow per record, not by count)
     int want_pass_lg = 0;  // test hook: log2(packets per pass) of the packed / vector-fill streams (0 = automatic)
@@ -2157,13 +2160,26 @@ static int depth_map_of_events_impl(dsi_mapper_t* out, dsi_mapper_t* const* mapp
         const int at_once = std::min(32, bp.bands / 8 + 1);
         bp.interleave = band_bytes * at_once > 3.0e6 ? 2 : 0;
     }
+#ifdef DSI_TIMING_EXPERIMENTS
+    if (out->fused_solo >= 0) {  // test hook dsi_test_fused_solo: the dealt mode, one workgroup (k_vote_fuse_argmax's body)
+        bp.interleave = 2;
+        bp.experiment = 310 + out->fused_solo;
+    }
+#endif
     const dsi::Geom& geom = mappers[0]->geom;
     hipStream_t st = ctx->stream;
     dsi::FusedCameras cams{};
     cams.n = n;
     dsi::PrepCameraArgs prep[dsi::kFusedMaxCameras] = {};
     const int n_pairs = bp.bands * geom.nz;
+#ifdef DSI_TIMING_EXPERIMENTS
+    const bool balance = n <= 2 && n_pairs <= dsi::fused_max_pairs() && out->fused_fixed_cost >= 0 && out->fused_solo < 0;
+    // (dsi_test_fused_grid_blocks may have changed the workgroup count since dsi_test_fused_trace_enable sized the trace)
+    REQUIRE(!out->fused_trace_on || out->fused_trace.cap >= dsi::fused_trace_words(), DSI_ERR_INVALID,
+            "the trace buffer was sized for another workgroup count: enable tracing again");
+#else
     const bool balance = n <= 2 && n_pairs <= dsi::fused_max_pairs() && out->fused_fixed_cost >= 0;
+#endif
     for (int i = 0; i < n; ++i) {
         dsi_mapper* m = mappers[i];
         const dsi_batch* b = batches[i];
@@ -3811,6 +3827,37 @@ DSI_API int dsi_test_fused_fixed_cost(dsi_mapper_t* m, int records)
 {
     REQUIRE(m, DSI_ERR_INVALID, "mapper is null");
     m->fused_fixed_cost = records;
+    return DSI_OK;
+}
+
+/* test hook (not in the public header): the workgroup count of the fused kernels (k_vote_fuse_argmax, its two-per-CU
+ * sibling at twice the count, k_vote_fuse_argmax_alg2), of the balanced partition and of the trace, for every later call of
+ * this process: a multiple of 8 that is >= 8 -- a CPX / QPX partition of the device has 32 / 64 CUs --, 0 = the device's own */
+DSI_API int dsi_test_fused_grid_blocks(int blocks)
+{
+    REQUIRE(dsi::fused_grid_blocks_force(blocks), DSI_ERR_INVALID, "a multiple of 8 in [8, 4096], or 0 (got %d)", blocks);
+    return DSI_OK;
+}
+
+/* test hook (not in the public header): what the last launch of a DSI-less kernel in this process was -- its grid size,
+ * bp.interleave (0 pieces, 1 in turn, 2 dealt), the kernel (1 k_vote_fuse_argmax, 2 k_vote_fuse_argmax_2cu, 3 the
+ * instantiation that defers camera 1's arg-max update, 4 four cameras, 5 k_vote_fuse_argmax_alg2) and whether it read a
+ * balanced partition: lets a test observe that a forced count or mode took effect and which kernel a shape reaches */
+DSI_API int dsi_test_fused_last_launch(int* blocks, int* interleave, int* kernel, int* splits)
+{
+    REQUIRE(blocks && interleave && kernel && splits, DSI_ERR_INVALID, "null argument");
+    dsi::fused_last_launch(blocks, interleave, kernel, splits);
+    return DSI_OK;
+}
+
+/* test hook (not in the public header): the next fused vote kernels that mapper m leads run in the dealt mode as ONE
+ * workgroup that acts as workgroup 0 of XCD `xcd` (0..7): it votes every (band, plane) pair, beginning at pair P xcd / 8 and
+ * wrapping round to P xcd / 8 - 1 -- a fixed draw order that descends within a band.  -1 switches it off */
+DSI_API int dsi_test_fused_solo(dsi_mapper_t* m, int xcd)
+{
+    REQUIRE(m, DSI_ERR_INVALID, "mapper is null");
+    REQUIRE(xcd >= -1 && xcd <= 7, DSI_ERR_INVALID, "XCD 0..7, or -1 (got %d)", xcd);
+    m->fused_solo = xcd;
     return DSI_OK;
 }
 

@@ -197,6 +197,14 @@ int fused_max_pairs();
 // launch_unpack_argmax.  splits: optional balanced partition of the (band-major) pair list, one entry
 // per workgroup + 1 (fused_grid_blocks() workgroups)
 int fused_grid_blocks();
+#ifdef DSI_TIMING_EXPERIMENTS
+// test hook (experiments flavour only): every later fused_grid_blocks() returns `blocks` (a multiple of 8, >= 8); 0 = the device's
+bool fused_grid_blocks_force(int blocks);
+// test hook (experiments flavour only): the last launch of a DSI-less kernel -- its grid size, bp.interleave, the kernel
+// (1 k_vote_fuse_argmax, 2 its two-per-CU sibling, 3 the instantiation that defers camera 1's arg-max, 4 four cameras,
+// 5 k_vote_fuse_argmax_alg2) and whether it read a balanced partition
+void fused_last_launch(int* blocks, int* interleave, int* kernel, int* splits);
+#endif
 size_t fused_max_cells(int mapping, int n_cameras = 2);  // (band_rows + 2) * nx may not exceed this (four cameras: 16 cells per thread)
 hipError_t launch_vote_fuse_argmax(hipStream_t s, const FusedCameras& cams, const Geom& g, const BandPlan& bp, int op,
                                    const uint32_t* splits, unsigned long long* keys, unsigned long long* trace = nullptr);

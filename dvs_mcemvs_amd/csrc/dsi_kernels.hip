@@ -17,6 +17,7 @@
 #include "dsi_vote_asm.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -2755,12 +2756,26 @@ __device__ __forceinline__ void vote_fuse_argmax_body(const FusedCameras& cams, 
     // k_fused_splits has balanced the partition by the records each pair holds.
     const int P = bp.bands * g.nz;
     int q_begin, q_end, q_step = 1;
+#ifdef DSI_TIMING_EXPERIMENTS
+    // test hook dsi_test_fused_solo (experiments flavour only): bp.experiment 310 + k -- ONE workgroup, launched alone
+    // (gridDim.x == 1, so `per` is 0), acts as workgroup 0 of XCD k of the dealt mode: it begins at pair P k / 8, draws that
+    // pair once more, runs to the end of the list, wraps to pair 0 and ends at P k / 8 - 1 -- a draw order that is the same
+    // on every run and descends inside a band at the wrap
+    const unsigned wg = (bp.experiment >= 310 && bp.experiment < 318) ? (unsigned)(bp.experiment - 310) : blockIdx.x;
+#else
+    const unsigned wg = blockIdx.x;
+#endif
     // DEALT (bp.interleave == 2, round 6): as "in turn", but only a workgroup's FIRST pair is fixed; every further pair is drawn
     // from its XCD's counter (one global atomic per pair, by thread 0, while the other waves finish camera 0's stream), and a
-    // workgroup whose XCD has run dry draws from the next XCD's counter.  The pairs a workgroup meets still ascend within a
-    // stretch (few band changes), the workgroups of an XCD still share one band's records at a time, and the kernel no
+    // workgroup whose XCD has run dry draws from the next XCD's counter.  The pairs a workgroup draws from ONE counter ascend
+    // (few band changes), the workgroups of an XCD still share one band's records at a time, and the kernel no
     // longer lasts as long as the workgroup whose FIXED share was the slowest (span / mean busy time 1.11 with fixed
-    // shares: the dense middle bands are slow per record).  Which workgroup votes a pair changes no bit.
+    // shares: the dense middle bands are slow per record).  Across counters the pairs do NOT ascend: a workgroup whose XCD
+    // is dry moves on to XCD (xcd + tries) & 7, round the ring, and may be handed a LOWER plane of the band it is in (any
+    // two neighbouring stretches share a band when bands < 8; the straggler may be any XCD, not only 0 after 7).  The
+    // running first maximum is a strict compare and needs ascending planes, so the pair loop keeps this invariant: z ascends
+    // between two emits, or the band is re-opened (emit + reset, as at a band change; the keys' atomic MAX then takes the
+    // first maximum over the pieces).  With it, which workgroup votes a pair -- and in which order -- changes no bit.
     // Counters: 8 words behind the keys, zero at launch (k_unpack_argmax re-zeroes them with the keys).
     // (DEAL = false: the two-workgroups-per-CU kernel, at 64 registers, takes its pairs in turn instead)
     const bool dealt = DEAL && !splits && bp.interleave == 2;
@@ -2768,11 +2783,11 @@ __device__ __forceinline__ void vote_fuse_argmax_body(const FusedCameras& cams, 
     __shared__ int s_deal_tries;
     if (splits) {
         // rank = position of this workgroup in XCD-major order: XCD x still covers one contiguous stretch
-        const int rank = (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
+        const int rank = (int)(wg & 7) * (int)(gridDim.x >> 3) + (int)(wg >> 3);
         q_begin = (int)splits[rank];
         q_end = (int)splits[rank + 1];
     } else {
-        const int x = blockIdx.x & 7, l = blockIdx.x >> 3, per = gridDim.x >> 3;
+        const int x = wg & 7, l = wg >> 3, per = gridDim.x >> 3;
         const int lo = (int)(((long long)P * x) / 8), hi = (int)(((long long)P * (x + 1)) / 8);
         if (dealt) {
             q_begin = lo + l;
@@ -2836,7 +2851,7 @@ __device__ __forceinline__ void vote_fuse_argmax_body(const FusedCameras& cams, 
         }
         pend_z = -1;
     };
-    int cur_j = -1, r0 = 0, r1 = 0, n_own = 0;
+    int cur_j = -1, prev_z = -1, r0 = 0, r1 = 0, n_own = 0;
     // the cut words of this wave's first pass of phase (pair q, camera c) -- see packed_stream_asm_dealt
     constexpr bool kPrefetchCuts = MAPPING == 1;
     auto first_cuts_of = [&](int q, int c) -> uint32_t {
@@ -2870,7 +2885,9 @@ __device__ __forceinline__ void vote_fuse_argmax_body(const FusedCameras& cams, 
     for (int q = q_begin; q < q_end; ++it) {
         const int j = q / g.nz, z = q - j * g.nz;
         int q_next = q + q_step;  // (DEALT: read from s_next_q behind the last phase's first barrier)
-        if (j != cur_j) {
+        // a band change -- or a pair that does not ascend within the band (DEALT: drawn from another XCD's counter), which
+        // re-opens the band: the strict compare below keeps the FIRST maximum only while z ascends
+        if (j != cur_j || z <= prev_z) {
             run_pending();  // (the last pair of the band that ends here)
             if (cur_j >= 0) emit();
             cur_j = j;
@@ -2882,6 +2899,7 @@ __device__ __forceinline__ void vote_fuse_argmax_body(const FusedCameras& cams, 
 #pragma unroll
             for (int k = 0; k < (CELLS + 3) / 4; ++k) fb.idx4[k] = 0u;
         }
+        prev_z = z;
         const int rows_lds = r1 - r0 + 2;
         // events with floor(Y) in [r0 - 1, r1 - 1] (and in [0, ny - 2], cartesian3dgrid.h:255-259)
         const int Li = max(r0 - 1, 0), Ui = min(r1, g.ny - 1);
@@ -2897,7 +2915,7 @@ __device__ __forceinline__ void vote_fuse_argmax_body(const FusedCameras& cams, 
             if (trace) {
                 const int phase = it * cams.n + c;
                 if (phase < kFusedTracePhases)
-                    tr = __builtin_amdgcn_readfirstlane((((int)blockIdx.x * kFusedTracePhases + phase) * (BLOCK / kWave) + (int)(threadIdx.x / kWave)) * 4);
+                    tr = __builtin_amdgcn_readfirstlane((((int)wg * kFusedTracePhases + phase) * (BLOCK / kWave) + (int)(threadIdx.x / kWave)) * 4);
             }
 #define DSI_FUSED_STAMP(k) do { if (tr >= 0 && (threadIdx.x & 63) == 0) trace[tr + (k)] = wall_clock64(); } while (0)
 #else
@@ -2918,7 +2936,7 @@ __device__ __forceinline__ void vote_fuse_argmax_body(const FusedCameras& cams, 
                 // the next pair of this workgroup: its XCD's counter first, then the other XCDs' in turn (the first `per`
                 // pairs of every stretch are the workgroups' fixed first pairs).  Wave 0, scalar code but for the atomic.
                 // (P < 2^24: at most 2^16 rows -- 16-bit row tables -- and 256 planes -- 8-bit plane indices in the keys)
-                const int xcd = (int)(blockIdx.x & 7), per = (int)(gridDim.x >> 3);
+                const int xcd = (int)(wg & 7), per = (int)(gridDim.x >> 3);
                 unsigned* const ctr = reinterpret_cast<unsigned*>(keys + (size_t)g.nx * g.ny);
                 int tries = __builtin_amdgcn_readfirstlane(s_deal_tries);  // XCDs this workgroup has found dry
                 int nq = 0x7fffffff;
@@ -5464,6 +5482,33 @@ hipError_t launch_fused_splits(hipStream_t s, const uint32_t* work0, const uint3
     return hipExtGetLastError();
 }
 
+// test hook dsi_test_fused_solo (experiments flavour only; bp.experiment 310 + k): see vote_fuse_argmax_body
+static inline bool fused_solo(const BandPlan& bp)
+{
+#ifdef DSI_TIMING_EXPERIMENTS
+    return bp.experiment >= 310 && bp.experiment < 318;
+#else
+    (void)bp;
+    return false;
+#endif
+}
+
+#ifdef DSI_TIMING_EXPERIMENTS
+// test hook dsi_test_fused_last_launch (experiments flavour only): what the last launch of a DSI-less kernel was
+static std::atomic<int> g_last_blocks{0}, g_last_interleave{-1}, g_last_kernel{0}, g_last_splits{0};
+void fused_last_launch(int* blocks, int* interleave, int* kernel, int* splits)
+{
+    *blocks = g_last_blocks.load();
+    *interleave = g_last_interleave.load();
+    *kernel = g_last_kernel.load();
+    *splits = g_last_splits.load();
+}
+#define DSI_FUSED_LAUNCHED(blocks, interleave, kernel, splits) \
+    (g_last_blocks.store((int)(blocks)), g_last_interleave.store(interleave), g_last_kernel.store(kernel), g_last_splits.store((splits) ? 1 : 0))
+#else
+#define DSI_FUSED_LAUNCHED(blocks, interleave, kernel, splits) ((void)0)
+#endif
+
 template <int MAPPING>
 static hipError_t launch_vote_fuse_argmax_t(hipStream_t s, const FusedCameras& cams, const Geom& g, const BandPlan& bp,
                                             int op, const uint32_t* splits, unsigned blocks, unsigned long long* keys,
@@ -5480,13 +5525,15 @@ static hipError_t launch_vote_fuse_argmax_t(hipStream_t s, const FusedCameras& c
         if (hipError_t e = allow_dynamic_lds(kern4, bp.lds_bytes)) return e;
         hipLaunchKernelGGL((k_vote_fuse_argmax<MAPPING, CELLS4, false, true>), dim3(blocks), dim3(1024), bp.lds_bytes, s, cams, g, bp, op,
                            splits, keys, trace);
+        DSI_FUSED_LAUNCHED(blocks, bp.interleave, 4, splits);
         return hipExtGetLastError();
     }
     if constexpr (MAPPING == 1 || MAPPING == 3) {
         // a band of at most half the LDS and half the cells: two workgroups per CU, the variant with <= 64 VGPRs
         constexpr int HALF = kFusedCellsTwoPerCu;
         // (bp.experiment 300: experiments flavour, DSI_FUSED_2CU=0 -- the same small band with ONE workgroup per CU, for A/B)
-        if (bp.experiment != 300 && bp.lds_bytes * 2 <= max_dynamic_lds() && (size_t)(bp.band_rows + 2) * g.nx <= (size_t)HALF * 1024) {
+        // (a solo launch is the one-per-CU kernel's: the two-per-CU kernel does not deal)
+        if (bp.experiment != 300 && !fused_solo(bp) && bp.lds_bytes * 2 <= max_dynamic_lds() && (size_t)(bp.band_rows + 2) * g.nx <= (size_t)HALF * 1024) {
             const void* kern2 = reinterpret_cast<const void*>(&k_vote_fuse_argmax_2cu<MAPPING, HALF>);
             if (hipError_t e = allow_dynamic_lds(kern2, bp.lds_bytes)) return e;
             // ... only if the runtime agrees that two fit (static LDS and the allocation granularity also count: a band just
@@ -5496,6 +5543,7 @@ static hipError_t launch_vote_fuse_argmax_t(hipStream_t s, const FusedCameras& c
             // (the balanced partition, an experiments-flavour option, is laid out for one workgroup per CU: not used here)
             hipLaunchKernelGGL((k_vote_fuse_argmax_2cu<MAPPING, HALF>), dim3(2 * blocks), dim3(1024), bp.lds_bytes, s, cams, g, bp, op,
                                nullptr, keys, trace);
+            DSI_FUSED_LAUNCHED(2 * blocks, bp.interleave, 2, nullptr);
             return hipExtGetLastError();
         }
     }
@@ -5508,12 +5556,14 @@ one_per_cu:
             if (hipError_t e = allow_dynamic_lds(kern_d, bp.lds_bytes)) return e;
             hipLaunchKernelGGL((k_vote_fuse_argmax<MAPPING, CELLS, true>), dim3(blocks), dim3(1024), bp.lds_bytes, s, cams, g, bp, op, splits,
                                keys, trace);
+            DSI_FUSED_LAUNCHED(blocks, bp.interleave, 3, splits);
             return hipExtGetLastError();
         }
     }
     const void* kern = reinterpret_cast<const void*>(&k_vote_fuse_argmax<MAPPING, CELLS>);
     if (hipError_t e = allow_dynamic_lds(kern, bp.lds_bytes)) return e;
     hipLaunchKernelGGL((k_vote_fuse_argmax<MAPPING, CELLS>), dim3(blocks), dim3(1024), bp.lds_bytes, s, cams, g, bp, op, splits, keys, trace);
+    DSI_FUSED_LAUNCHED(blocks, bp.interleave, 1, splits);
     return hipExtGetLastError();
 }
 
@@ -5524,8 +5574,23 @@ size_t fused_max_cells(int mapping, int n_cameras)
 
 size_t fused_trace_words() { return (size_t)2 * fused_grid_blocks() * kFusedTracePhases * 16 * 4; }  // (two workgroups per CU at most)
 
+#ifdef DSI_TIMING_EXPERIMENTS
+// test hook dsi_test_fused_grid_blocks (experiments flavour only): the workgroup count every user of fused_grid_blocks()
+// sees -- the three launches, the balanced partition and the trace -- as on a CPX / QPX partition (32 / 64 CUs); 0: the device's
+static std::atomic<int> g_fused_grid_blocks_forced{0};
+bool fused_grid_blocks_force(int blocks)
+{
+    if (blocks != 0 && (blocks < 8 || blocks > 4096 || blocks % 8 != 0)) return false;
+    g_fused_grid_blocks_forced.store(blocks);
+    return true;
+}
+#endif
+
 int fused_grid_blocks()
 {
+#ifdef DSI_TIMING_EXPERIMENTS
+    if (const int forced = g_fused_grid_blocks_forced.load()) return forced;
+#endif
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     return std::max(8, cus - cus % 8);  // one 1024-thread workgroup per CU, whole groups of 8 (XCDs)
@@ -5535,7 +5600,9 @@ hipError_t launch_vote_fuse_argmax(hipStream_t s, const FusedCameras& cams, cons
                                    const uint32_t* splits, unsigned long long* keys, unsigned long long* trace)
 {
     if (cams.n < 1 || cams.n > kFusedMaxCameras || bp.block_threads != 1024 || bp.chunks != 1 || !bp.halo) return hipErrorInvalidValue;
-    const unsigned blocks = (unsigned)fused_grid_blocks();
+    // (solo: the dealing arithmetic alone is written for gridDim.x == 1 -- the other modes divide by gridDim.x / 8)
+    if (fused_solo(bp) && (splits || bp.interleave != 2 || bp.bands * g.nz < 8)) return hipErrorInvalidValue;
+    const unsigned blocks = fused_solo(bp) ? 1u : (unsigned)fused_grid_blocks();
     switch (bp.packed) {
     case 1: return launch_vote_fuse_argmax_t<1>(s, cams, g, bp, op, splits, blocks, keys, trace);
     case 3: return launch_vote_fuse_argmax_t<3>(s, cams, g, bp, op, splits, blocks, keys, trace);
@@ -5563,6 +5630,7 @@ static hipError_t launch_vote_alg2_argmax_t(hipStream_t s, const Alg2Batches& bt
     if (hipError_t e = allow_dynamic_lds(kern, bp.lds_bytes)) return e;
     hipLaunchKernelGGL((k_vote_fuse_argmax_alg2<MAPPING, CELLS, CT>), dim3(fused_grid_blocks()), dim3(1024), bp.lds_bytes, s, bt, g, bp,
                        sf, tf, keys_tc, keys_ct);
+    DSI_FUSED_LAUNCHED(fused_grid_blocks(), bp.interleave, 5, nullptr);
     return hipExtGetLastError();
 }
 

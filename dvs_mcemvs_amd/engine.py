@@ -283,6 +283,9 @@ def load_library():
             "dsi_test_div_probe": (C.c_int, [vp, f32p, f32p, C.c_size_t, f32p, f32p]),
             "dsi_test_pass_lg": (C.c_int, [vp, C.c_int]),
             "dsi_test_fused_fixed_cost": (C.c_int, [vp, C.c_int]),
+            "dsi_test_fused_grid_blocks": (C.c_int, [C.c_int]),
+            "dsi_test_fused_solo": (C.c_int, [vp, C.c_int]),
+            "dsi_test_fused_last_launch": (C.c_int, [intp, intp, intp, intp]),
             "dsi_test_fused_trace_enable": (C.c_int, [vp, szp]),
             "dsi_test_fused_trace_read": (C.c_int, [vp, vp, C.c_size_t]),
             "dsi_test_run_length_total": (C.c_int, [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),

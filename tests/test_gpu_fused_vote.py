@@ -433,7 +433,10 @@ def test_fused_kernel_with_the_pairs_taken_in_turn(ctx, n_cams):
     consecutive planes of one band -- instead of a contiguous piece each: the first pair fixed, every further pair DRAWN from
     the XCD's counter behind the arg-max keys (and from the other XCDs' once that one is dry).  Which workgroup votes a
     pair changes no bit: the depth map is that of evaluateDSI x n + the fusion inside the arg-max.  Called twice: the
-    counters must be zero again for the second call (k_unpack_argmax clears them with the keys)."""
+    counters must be zero again for the second call (k_unpack_argmax clears them with the keys).
+    (One workgroup count -- the device's -- and whatever draw order the run happens to produce: with 14 (four cameras: 18) bands x 24 planes on 256
+    workgroups a draw from another XCD's counter lands in another band.  The count and the order are pinned by
+    tests/test_gpu_fused_schedule.py.)"""
     nx, ny, nz = 512, 512, 24
     rig = syn.stereo_rig(1_200_000, width=nx, height=ny, duration=0.3, seed=91, n_points=4000, n_cams=4)
     sh = d.ShapeDSI(0, 0, nz, 4.0, 150.0, 0.0)
