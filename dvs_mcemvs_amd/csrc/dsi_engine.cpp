@@ -972,7 +972,7 @@ int dsi_context_destroy(dsi_context_t* ctx)
 {
     if (!ctx) return DSI_OK;
     REQUIRE(ctx->children.load() == 0, DSI_ERR_CONTEXT,
-            "%d object(s) created from this context (grids, mappers, batches, scores) are still alive: destroy them first",
+            "%d object(s) created from this context (grids, mappers, batches, scores, projectors) are still alive: destroy them first",
             ctx->children.load());
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
@@ -3732,6 +3732,170 @@ int dsi_score_histogram(dsi_score_t* s, double binwidth, uint64_t* counts, size_
     static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "64-bit counts");
     HIP_TRY(hipMemcpyAsync(counts, s->counts.p, (size_t)nb * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
+    return DSI_OK;
+}
+
+// ---- ground-truth depth from disparity images ----
+
+struct dsi_gt {
+    dsi_context* ctx = nullptr;
+    int width = 0, height = 0, mode = 0;
+    dsi::GtCalib calib{};
+    // winner table | output map | disparity upload (4 bytes per pixel each), counters
+    uint32_t* words = nullptr;
+    unsigned int* counters = nullptr;
+};
+
+namespace {
+
+size_t gt_npix(const dsi_gt* g) { return (size_t)g->width * g->height; }
+float* gt_out(const dsi_gt* g) { return reinterpret_cast<float*>(g->words + gt_npix(g)); }
+void* gt_upload(const dsi_gt* g) { return g->words + 2 * gt_npix(g); }
+
+dsi::GtWork gt_work(const dsi_gt* g) { return dsi::GtWork{g->words, g->counters, gt_out(g)}; }
+
+void gt_free(dsi_gt* g)
+{
+    if (g->words) (void)hipFree(g->words);
+    if (g->counters) (void)hipFree(g->counters);
+    delete g;
+}
+
+}  // namespace
+
+int dsi_gt_create(dsi_context_t* ctx, int width, int height, const double* Q, const double* T, const double* K, int mode,
+                  dsi_gt_t** out)
+{
+    REQUIRE(ctx && Q && T && K && out, DSI_ERR_INVALID, "null argument");
+    REQUIRE(width >= 1 && height >= 1, DSI_ERR_INVALID, "the image must be at least 1 x 1 (got %d x %d)", width, height);
+    REQUIRE((unsigned long long)width * (unsigned long long)height < 0xffffffffull, DSI_ERR_INVALID,
+            "width * height must be below 2^32 - 1 (got %d x %d)", width, height);
+    REQUIRE(mode == DSI_GT_AS_SCRIPT || mode == DSI_GT_DROP_OUTSIDE, DSI_ERR_INVALID, "unknown mode %d", mode);
+    for (int i = 0; i < 16; ++i)
+        REQUIRE(std::isfinite(Q[i]) && std::isfinite(T[i]), DSI_ERR_INVALID, "Q and T must be finite (entry %d)", i);
+    for (int i = 0; i < 12; ++i) REQUIRE(std::isfinite(K[i]), DSI_ERR_INVALID, "K must be finite (entry %d)", i);
+    if (int rc = set_device(ctx)) return rc;
+    dsi_gt* g = new (std::nothrow) dsi_gt;
+    REQUIRE(g, DSI_ERR_INVALID, "out of host memory");
+    g->ctx = ctx;
+    g->width = width;
+    g->height = height;
+    g->mode = mode;
+    std::memcpy(g->calib.Q, Q, sizeof g->calib.Q);
+    std::memcpy(g->calib.T, T, sizeof g->calib.T);
+    std::memcpy(g->calib.K, K, sizeof g->calib.K);
+    const size_t n = gt_npix(g);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&g->words), 3 * n * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->counters), 2 * sizeof(unsigned int));
+    if (e == hipSuccess) e = hipMemsetAsync(g->words, 0, 2 * n * sizeof(uint32_t), ctx->stream);  // (a fetch before a projection)
+    if (e == hipSuccess) e = hipMemsetAsync(g->counters, 0, 2 * sizeof(unsigned int), ctx->stream);
+    if (e != hipSuccess) {
+        gt_free(g);
+        return fail(DSI_ERR_HIP, "projector allocation of %d x %d pixels failed: %s", width, height, hipGetErrorString(e));
+    }
+    ++ctx->children;
+    *out = g;
+    return DSI_OK;
+}
+
+int dsi_gt_destroy(dsi_gt_t* gt)
+{
+    if (!gt) return DSI_OK;
+    (void)hipSetDevice(gt->ctx->device);
+    (void)hipStreamSynchronize(gt->ctx->stream);
+    --gt->ctx->children;
+    gt_free(gt);
+    return DSI_OK;
+}
+
+int dsi_gt_project(dsi_gt_t* gt, const float* disp_f32_host)
+{
+    REQUIRE(gt && disp_f32_host, DSI_ERR_INVALID, "null argument");
+    if (int rc = set_device(gt->ctx)) return rc;
+    float* up = static_cast<float*>(gt_upload(gt));
+    HIP_TRY(hipMemcpyAsync(up, disp_f32_host, gt_npix(gt) * sizeof(float), hipMemcpyHostToDevice, gt->ctx->stream));
+    HIP_TRY(dsi::launch_gt_project(gt->ctx->stream, up, gt->calib, gt->width, gt->height, gt->mode, gt_work(gt)));
+    return DSI_OK;
+}
+
+int dsi_gt_project_u16(dsi_gt_t* gt, const uint16_t* raw_u16_host)
+{
+    REQUIRE(gt && raw_u16_host, DSI_ERR_INVALID, "null argument");
+    if (int rc = set_device(gt->ctx)) return rc;
+    uint16_t* up = static_cast<uint16_t*>(gt_upload(gt));
+    HIP_TRY(hipMemcpyAsync(up, raw_u16_host, gt_npix(gt) * sizeof(uint16_t), hipMemcpyHostToDevice, gt->ctx->stream));
+    HIP_TRY(dsi::launch_gt_project_u16(gt->ctx->stream, up, gt->calib, gt->width, gt->height, gt->mode, gt_work(gt)));
+    return DSI_OK;
+}
+
+int dsi_gt_fetch(dsi_gt_t* gt, float* depth_host, uint64_t* n_points, uint64_t* n_outside)
+{
+    REQUIRE(gt, DSI_ERR_INVALID, "null argument");
+    if (int rc = set_device(gt->ctx)) return rc;
+    unsigned int counters[2] = {0, 0};
+    hipStream_t st = gt->ctx->stream;
+    if (depth_host) HIP_TRY(hipMemcpyAsync(depth_host, gt_out(gt), gt_npix(gt) * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(counters, gt->counters, sizeof counters, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (n_points) *n_points = counters[0];
+    if (n_outside) *n_outside = counters[1];
+    return DSI_OK;
+}
+
+float* dsi_gt_device_ptr(dsi_gt_t* gt) { return gt ? gt_out(gt) : nullptr; }
+
+int dsi_score_add_gt(dsi_score_t* s, const float* depth_host, const uint8_t* mask_host, size_t n_pixels, dsi_gt_t* gt)
+{
+    if (int rc = score_check_add(s, depth_host, mask_host, gt, n_pixels)) return rc;
+    REQUIRE(gt->ctx == s->ctx, DSI_ERR_CONTEXT, "projector and score belong to different contexts");
+    REQUIRE(n_pixels == gt_npix(gt), DSI_ERR_INVALID, "the maps hold %zu pixels, the projector's %d x %d", n_pixels, gt->width,
+            gt->height);
+    if (int rc = set_device(s->ctx)) return rc;
+    hipStream_t st = s->ctx->stream;
+    HIP_TRY(s->depth.reserve(n_pixels));
+    HIP_TRY(s->mask.reserve(n_pixels));
+    HIP_TRY(hipMemcpyAsync(s->depth.p, depth_host, n_pixels * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->mask.p, mask_host, n_pixels, hipMemcpyHostToDevice, st));
+    return score_add_device(s, s->depth.p, s->mask.p, gt_out(gt), n_pixels);
+}
+
+int dsi_score_add_mapper_gt(dsi_score_t* s, dsi_mapper_t* m, dsi_gt_t* gt)
+{
+    REQUIRE(s && m && gt, DSI_ERR_INVALID, "null argument");
+    REQUIRE(m->ctx == s->ctx, DSI_ERR_CONTEXT, "mapper and score belong to different contexts");
+    REQUIRE(gt->ctx == s->ctx, DSI_ERR_CONTEXT, "projector and score belong to different contexts");
+    const size_t npix = (size_t)m->geom.nx * m->geom.ny;
+    REQUIRE(npix == gt_npix(gt), DSI_ERR_INVALID, "the mapper's maps hold %zu pixels, the projector's %d x %d", npix, gt->width,
+            gt->height);
+    REQUIRE(m->filtered_valid, DSI_ERR_INVALID,
+            "no filtered depth map on the device: call dsi_mapper_filter_depth_map or dsi_mapper_get_depth_map_from_dsi "
+            "after the depth map was computed, or pass the maps to dsi_score_add_gt");
+    if (int rc = set_device(s->ctx)) return rc;
+    if (int rc = depth_buffers_acquire(m)) return rc;
+    return score_add_device(s, m->depth.p, m->mask.p, gt_out(gt), npix);
+}
+
+int dsi_depth_erode(dsi_context_t* ctx, const float* depth_host, const uint8_t* mask_host, int rows, int cols, float no_estimate,
+                    float* out_depth_host, uint8_t* out_mask_host)
+{
+    REQUIRE(ctx && depth_host && mask_host && out_depth_host && out_mask_host, DSI_ERR_INVALID, "null argument");
+    REQUIRE(rows >= 1 && cols >= 1, DSI_ERR_INVALID, "the maps must be at least 1 x 1 (got %d x %d)", rows, cols);
+    REQUIRE((size_t)rows * cols <= ((size_t)1 << 29), DSI_ERR_INVALID, "at most 2^29 pixels");
+    if (int rc = set_device(ctx)) return rc;
+    hipStream_t st = ctx->stream;
+    const size_t npix = (size_t)rows * cols;
+    const size_t fb = up256(npix * sizeof(float)), mb = up256(npix);
+    HIP_TRY(ctx->img_bytes.reserve(2 * fb + 2 * mb));
+    float* d_in = reinterpret_cast<float*>(ctx->img_bytes.p);
+    float* d_out = reinterpret_cast<float*>(ctx->img_bytes.p + fb);
+    uint8_t* m_in = ctx->img_bytes.p + 2 * fb;
+    uint8_t* m_out = m_in + mb;
+    HIP_TRY(hipMemcpyAsync(d_in, depth_host, npix * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m_in, mask_host, npix, hipMemcpyHostToDevice, st));
+    HIP_TRY(dsi::launch_depth_erode_cross(st, d_in, m_in, rows, cols, no_estimate, d_out, m_out));
+    HIP_TRY(hipMemcpyAsync(out_depth_host, d_out, npix * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_mask_host, m_out, npix, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return DSI_OK;
 }
 

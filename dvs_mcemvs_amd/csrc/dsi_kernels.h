@@ -405,4 +405,25 @@ hipError_t launch_score_histogram(hipStream_t s, const double* buf, size_t n, co
 // work[0] / work[1] = bit patterns of the elements of rank rank0 / rank1 (0-based, < n) of the n stored errors
 hipError_t launch_score_select(hipStream_t s, const double* buf, size_t n, size_t rank0, size_t rank1, unsigned long long* work);
 
+// ---- ground-truth depth from disparity images: scripts/evaluate_mcemvs_dsec.py:75-79, 108-122 ----
+constexpr int GT_AS_SCRIPT = 0, GT_DROP_OUTSIDE = 1;  // DSI_GT_AS_SCRIPT, DSI_GT_DROP_OUTSIDE
+struct GtCalib {
+    double Q[16], T[16], K[12];  // row-major; T is the matrix that is applied
+};
+// device memory of one projection of width * height pixels: the winner table and the output map (both cleared by the
+// launch), two counters (kept points, outside points)
+struct GtWork {
+    uint32_t* winner;
+    unsigned int* counters;
+    float* out;
+};
+// out[height][width] = the depth map of the float32 disparity image disp[height][width]; width * height < 2^32 - 1
+hipError_t launch_gt_project(hipStream_t s, const float* disp, const GtCalib& calib, int width, int height, int mode, const GtWork& w);
+// same, of the raw 16-bit image: d = (float32(raw) / 65535f) * 256f
+hipError_t launch_gt_project_u16(hipStream_t s, const uint16_t* raw, const GtCalib& calib, int width, int height, int mode,
+                                 const GtWork& w);
+// thicken_edges: e = min over the 3 x 3 cross of (mask ? depth : no_estimate); out_depth = e, out_mask = e != no_estimate
+hipError_t launch_depth_erode_cross(hipStream_t s, const float* depth, const uint8_t* mask, int rows, int cols, float no_estimate,
+                                    float* out_depth, uint8_t* out_mask);
+
 }  // namespace dsi

@@ -8362,4 +8362,156 @@ hipError_t launch_score_select(hipStream_t s, const double* buf, size_t n, size_
     return hipExtGetLastError();
 }
 
+
+// ------------------------------- ground-truth depth from disparity images ---
+// scripts/evaluate_mcemvs_dsec.py:108-122: reproject with Q, transform with T, project with K, forward-splat with numpy's
+// scatter rules (the largest row-major source index wins a target pixel).
+namespace {
+
+constexpr int kGtBlock = 256;  // four waves of 64
+
+struct GtPoint {
+    bool kept;      // Z < +inf as float32
+    bool write;     // has a target pixel in this mode
+    bool outside;   // kept and not indexable (numpy's IndexError)
+    uint32_t target;
+    float value;    // float32(P_2)
+};
+
+__device__ __forceinline__ float gt_disparity(float d) { return d; }
+// matplotlib's 16-bit rule, then the script's * 256: two fp32 operations, the divide correctly rounded
+__device__ __forceinline__ float gt_disparity(uint16_t raw) { return __fdiv_rn((float)raw, 65535.0f) * 256.0f; }
+
+// steps 1-4 of DESIGN.md 7g for source pixel (x, y): float64 throughout, sums left to right, no contraction
+__device__ __forceinline__ GtPoint gt_point(const GtCalib& c, int x, int y, float disp, int W, int H, int mode)
+{
+    GtPoint r{false, false, false, 0u, 0.0f};
+    const double xd = (double)x, yd = (double)y, d = (double)disp;
+    double h[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) h[i] = ((c.Q[4 * i] * xd + c.Q[4 * i + 1] * yd) + c.Q[4 * i + 2] * d) + c.Q[4 * i + 3];
+    const float Xf = (float)(h[0] / h[3]), Yf = (float)(h[1] / h[3]), Zf = (float)(h[2] / h[3]);
+    r.kept = Zf < __builtin_inff();  // NaN and +inf are dropped; -inf and negative values stay
+    if (!r.kept) return r;
+    const double X = (double)Xf, Y = (double)Yf, Z = (double)Zf;
+    double P[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) P[i] = ((c.T[4 * i] * X + c.T[4 * i + 1] * Y) + c.T[4 * i + 2] * Z) + c.T[4 * i + 3];
+    double p[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) p[i] = ((c.K[4 * i] * P[0] + c.K[4 * i + 1] * P[1]) + c.K[4 * i + 2] * P[2]) + c.K[4 * i + 3] * P[3];
+    const double tu = trunc(p[0] / p[2]), tv = trunc(p[1] / p[2]);  // NaN / inf stay NaN / inf and fail the range test
+    r.value = (float)P[2];
+    const double Wd = (double)W, Hd = (double)H;
+    if (!(tu >= -Wd && tu < Wd && tv >= -Hd && tv < Hd)) {
+        r.outside = true;
+        return r;
+    }
+    long long iu = (long long)tu, iv = (long long)tv;
+    if (iu < 0 || iv < 0) {
+        if (mode == GT_DROP_OUTSIDE) return r;  // no wrap: dropped on its own
+        iu += iu < 0 ? W : 0;                  // numpy's negative indices
+        iv += iv < 0 ? H : 0;
+    }
+    r.write = true;
+    r.target = (uint32_t)((unsigned long long)iv * (unsigned long long)W + (unsigned long long)iu);
+    return r;
+}
+
+// One thread per source pixel: winner[target] = max(source index + 1), counters[0] += kept points, counters[1] += outside
+// points (a ballot's population count, one integer atomic per wave and counter; every lane of a wave reaches the ballots).
+template <typename In>
+__global__ __launch_bounds__(kGtBlock) void k_gt_project(const In* __restrict__ disp, GtCalib c, int W, int H, int mode,
+                                                         uint32_t* __restrict__ winner, unsigned int* __restrict__ counters)
+{
+    const unsigned long long n = (unsigned long long)W * (unsigned long long)H;
+    const unsigned long long i = (unsigned long long)blockIdx.x * kGtBlock + threadIdx.x;
+    GtPoint r{false, false, false, 0u, 0.0f};
+    if (i < n) {
+        const int y = (int)(i / (unsigned long long)W), x = (int)(i - (unsigned long long)y * (unsigned long long)W);
+        r = gt_point(c, x, y, gt_disparity(disp[i]), W, H, mode);
+        if (r.write) atomicMax(&winner[r.target], (uint32_t)i + 1u);
+    }
+    const unsigned int c_kept = (unsigned int)__popcll(__ballot(r.kept));
+    const unsigned int c_out = (unsigned int)__popcll(__ballot(r.outside));
+    if ((threadIdx.x & 63) == 0) {
+        if (c_kept) atomicAdd(&counters[0], c_kept);
+        if (c_out) atomicAdd(&counters[1], c_out);
+    }
+}
+
+// One thread per source pixel: it computes its point again, and the winner of a target pixel writes float32(P_2) there.
+// In script mode one outside point leaves the whole (cleared) output as it is.
+template <typename In>
+__global__ __launch_bounds__(kGtBlock) void k_gt_write(const In* __restrict__ disp, GtCalib c, int W, int H, int mode,
+                                                       const uint32_t* __restrict__ winner, const unsigned int* __restrict__ counters,
+                                                       float* __restrict__ out)
+{
+    if (mode == GT_AS_SCRIPT && counters[1] != 0u) return;
+    const unsigned long long n = (unsigned long long)W * (unsigned long long)H;
+    const unsigned long long i = (unsigned long long)blockIdx.x * kGtBlock + threadIdx.x;
+    if (i >= n) return;
+    const int y = (int)(i / (unsigned long long)W), x = (int)(i - (unsigned long long)y * (unsigned long long)W);
+    const GtPoint r = gt_point(c, x, y, gt_disparity(disp[i]), W, H, mode);
+    if (r.write && winner[r.target] == (uint32_t)i + 1u) out[r.target] = r.value;
+}
+
+// evaluate_mcemvs_dsec.py:75-79 (thicken_edges): erosion of the map with the 3 x 3 cross, pixels without an estimate
+// standing at no_estimate; neighbours outside the image do not contribute
+__global__ __launch_bounds__(kGtBlock) void k_depth_erode_cross(const float* __restrict__ depth, const uint8_t* __restrict__ mask,
+                                                                int rows, int cols, float no_estimate, float* __restrict__ out_depth,
+                                                                uint8_t* __restrict__ out_mask)
+{
+    const size_t p = (size_t)blockIdx.x * kGtBlock + threadIdx.x;
+    if (p >= (size_t)rows * cols) return;
+    const int r = (int)(p / (size_t)cols), c = (int)(p - (size_t)r * cols);
+    auto at = [&](size_t q) { return mask[q] ? depth[q] : no_estimate; };
+    float e = at(p);
+    if (r > 0) e = fminf(e, at(p - cols));
+    if (r + 1 < rows) e = fminf(e, at(p + cols));
+    if (c > 0) e = fminf(e, at(p - 1));
+    if (c + 1 < cols) e = fminf(e, at(p + 1));
+    out_depth[p] = e;
+    out_mask[p] = e != no_estimate ? 1 : 0;
+}
+
+template <typename In>
+hipError_t gt_project_any(hipStream_t s, const In* disp, const GtCalib& calib, int W, int H, int mode, const GtWork& w)
+{
+    const size_t n = (size_t)W * H;
+    if (!disp || !w.winner || !w.counters || !w.out || W < 1 || H < 1 || n >= 0xffffffffull) return hipErrorInvalidValue;
+    if (mode != GT_AS_SCRIPT && mode != GT_DROP_OUTSIDE) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(w.winner, 0, n * sizeof(uint32_t), s);
+    if (e == hipSuccess) e = hipMemsetAsync(w.counters, 0, 2 * sizeof(unsigned int), s);
+    if (e == hipSuccess) e = hipMemsetAsync(w.out, 0, n * sizeof(float), s);
+    if (e != hipSuccess) return e;
+    const dim3 grid((unsigned)((n + kGtBlock - 1) / kGtBlock)), block(kGtBlock);  // n < 2^32: at most 2^24 blocks
+    hipLaunchKernelGGL(k_gt_project<In>, grid, block, 0, s, disp, calib, W, H, mode, w.winner, w.counters);
+    hipLaunchKernelGGL(k_gt_write<In>, grid, block, 0, s, disp, calib, W, H, mode, w.winner, w.counters, w.out);
+    return hipExtGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_gt_project(hipStream_t s, const float* disp, const GtCalib& calib, int width, int height, int mode, const GtWork& w)
+{
+    return gt_project_any(s, disp, calib, width, height, mode, w);
+}
+
+hipError_t launch_gt_project_u16(hipStream_t s, const uint16_t* raw, const GtCalib& calib, int width, int height, int mode,
+                                 const GtWork& w)
+{
+    return gt_project_any(s, raw, calib, width, height, mode, w);
+}
+
+hipError_t launch_depth_erode_cross(hipStream_t s, const float* depth, const uint8_t* mask, int rows, int cols, float no_estimate,
+                                    float* out_depth, uint8_t* out_mask)
+{
+    const size_t npix = (size_t)rows * cols;
+    if (!depth || !mask || !out_depth || !out_mask || rows < 1 || cols < 1 || npix > ((size_t)1 << 29)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_depth_erode_cross, dim3((unsigned)((npix + kGtBlock - 1) / kGtBlock)), dim3(kGtBlock), 0, s, depth, mask, rows,
+                       cols, no_estimate, out_depth, out_mask);
+    return hipExtGetLastError();
+}
+
 }  // namespace dsi

@@ -237,6 +237,15 @@ def load_library():
         "dsi_score_metrics": (C.c_int, [vp, C.POINTER(_ScoreMetrics)]),
         "dsi_score_median": (C.c_int, [vp, f64p]),
         "dsi_score_histogram": (C.c_int, [vp, C.c_double, u64p, C.c_size_t, szp, f64p, f64p]),
+        "dsi_gt_create": (C.c_int, [vp, C.c_int, C.c_int, f64p, f64p, f64p, C.c_int, C.POINTER(vp)]),
+        "dsi_gt_destroy": (C.c_int, [vp]),
+        "dsi_gt_project": (C.c_int, [vp, f32p]),
+        "dsi_gt_project_u16": (C.c_int, [vp, u16p]),
+        "dsi_gt_fetch": (C.c_int, [vp, f32p, u64p, u64p]),
+        "dsi_gt_device_ptr": (vp, [vp]),
+        "dsi_score_add_gt": (C.c_int, [vp, f32p, u8p, C.c_size_t, vp]),
+        "dsi_score_add_mapper_gt": (C.c_int, [vp, vp, vp]),
+        "dsi_depth_erode": (C.c_int, [vp, f32p, u8p, C.c_int, C.c_int, C.c_float, f32p, u8p]),
         "dsi_mapper_last_vote_info": (C.c_int, [vp, C.POINTER(_VoteInfo)]),
         "dsi_mapper_set_kernel_timing": (C.c_int, [vp, C.c_int]),
         "dsi_mapper_vote_kernel_time": (C.c_int, [vp, f32p, intp]),
@@ -1032,6 +1041,18 @@ class DepthScore:
             outliers = (m["n_joint"] - cum) / m["n_joint"] * 100
         return {"base": base, "precision": precision, "recall": recall, "f1": f1, "outliers": outliers}
 
+    def addGroundTruth(self, depth, mask, projector):
+        """add() against the depth map that projector (a GroundTruthProjector of this context and of the maps' size) last
+        made: the ground truth is read where it lies on the device."""
+        depth, mask = _arr(depth, np.float32), _arr(np.asarray(mask) != 0, np.uint8)
+        if depth.shape != mask.shape:
+            raise ValueError("depth and mask must have one shape")
+        _check(load_library().dsi_score_add_gt(self._h, _ptr(depth, C.c_float), _ptr(mask, C.c_uint8), depth.size, projector._h))
+
+    def addMapperGroundTruth(self, mapper, projector):
+        """addMapper() against the projector's depth map: both sides are on the device, nothing is uploaded."""
+        _check(load_library().dsi_score_add_mapper_gt(self._h, mapper._h, projector._h))
+
     def reset(self):
         _check(load_library().dsi_score_reset(self._h))
 
@@ -1042,6 +1063,87 @@ class DepthScore:
 
     def __del__(self):
         _safe_del(self)
+
+
+GT_AS_SCRIPT, GT_DROP_OUTSIDE = 0, 1
+
+
+def disparity_from_png16(raw):
+    """The script's `plt.imread(png).astype(np.float32) * 256` from the PNG's uint16 samples (io.read_png_gray16):
+    matplotlib's 16-bit rule, float32(raw) / 65535, then * 256 -- two float32 operations, the bits that
+    GroundTruthProjector.project_png16 computes on the device."""
+    raw = np.asarray(raw)
+    if raw.dtype != np.uint16:
+        raise ValueError("disparity_from_png16 takes the uint16 samples of the PNG")
+    return np.divide(raw.astype(np.float32), np.float32(65535.0), dtype=np.float32) * np.float32(256.0)
+
+
+class GroundTruthProjector:
+    """Ground-truth depth from DSEC disparity images on the device (dsi_gt_*): what
+    scripts/evaluate_mcemvs_dsec.py:108-122 computes per frame.  Q (4 x 4), T (4 x 4: the matrix that is applied, the
+    script's np.linalg.inv(T_rect0_0)) and K (3 x 4, the script's K_0) are float64.  mode: GT_AS_SCRIPT (a frame with one
+    point outside the image gives zeros, like the script's except branch) or GT_DROP_OUTSIDE (such points, and those with a
+    negative index, are dropped one by one)."""
+
+    def __init__(self, ctx, width, height, Q, T, K, mode=GT_AS_SCRIPT):
+        self.ctx = ctx
+        self.width, self.height, self.mode = int(width), int(height), int(mode)
+        self._h = C.c_void_p()
+        Q, T, K = _arr(Q, np.float64), _arr(T, np.float64), _arr(K, np.float64)
+        if Q.shape != (4, 4) or T.shape != (4, 4) or K.shape != (3, 4):
+            raise ValueError("Q and T are 4 x 4, K is 3 x 4")
+        _check(load_library().dsi_gt_create(ctx._h, self.width, self.height, _ptr(Q, C.c_double), _ptr(T, C.c_double),
+                                            _ptr(K, C.c_double), self.mode, C.byref(self._h)))
+        _track(self)
+
+    def _frame(self, a, dtype):
+        if np.asarray(a).dtype != dtype:
+            raise ValueError("expected a %s image" % np.dtype(dtype).name)
+        a = _arr(a, dtype)
+        if a.shape != (self.height, self.width):
+            raise ValueError("the image must have the projector's (height, width) = (%d, %d)" % (self.height, self.width))
+        return a
+
+    def project(self, disp):
+        """disp: float32 [height][width], the script's d.  Queued on the context's stream; the map stays on the device."""
+        disp = self._frame(disp, np.float32)
+        _check(load_library().dsi_gt_project(self._h, _ptr(disp, C.c_float)))
+
+    def project_png16(self, raw):
+        """raw: the uint16 samples of the disparity PNG (io.read_png_gray16); converted on the device."""
+        raw = self._frame(raw, np.uint16)
+        _check(load_library().dsi_gt_project_u16(self._h, _ptr(raw, C.c_uint16)))
+
+    def fetch(self):
+        """(depth float32 [height][width], n_points, n_outside) of the last projection.  Synchronises."""
+        depth = np.zeros((self.height, self.width), np.float32)
+        n, o = C.c_uint64(), C.c_uint64()
+        _check(load_library().dsi_gt_fetch(self._h, _ptr(depth, C.c_float), C.byref(n), C.byref(o)))
+        return depth, int(n.value), int(o.value)
+
+    def device_ptr(self):
+        return load_library().dsi_gt_device_ptr(self._h)
+
+    def close(self):
+        if self._h:
+            load_library().dsi_gt_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        _safe_del(self)
+
+
+def thicken_edges(ctx, depth, mask, no_estimate=255.0):
+    """scripts/evaluate_mcemvs_dsec.py:75-79 with thicken_edges = True: (depth, mask) eroded by the 3 x 3 cross on the
+    device, pixels without an estimate standing at no_estimate (the script's 255) -- every estimate grows into its four
+    neighbours, the smaller depth winning."""
+    depth, mask = _arr(depth, np.float32), _arr(np.asarray(mask) != 0, np.uint8)
+    if depth.ndim != 2 or depth.shape != mask.shape:
+        raise ValueError("depth and mask must be 2-D and of one shape")
+    out_d, out_m = np.zeros_like(depth), np.zeros_like(mask)
+    _check(load_library().dsi_depth_erode(ctx._h, _ptr(depth, C.c_float), _ptr(mask, C.c_uint8), depth.shape[0], depth.shape[1],
+                                          float(no_estimate), _ptr(out_d, C.c_float), _ptr(out_m, C.c_uint8)))
+    return out_d, out_m
 
 
 class PinnedArray:

@@ -7,7 +7,10 @@ trajectories can be replayed without ROS:
   write_png_rgb8        cv::imwrite of a CV_8UC3 image  utils.cpp:93                            (.png, 8-bit colour, from B G R)
   save_depth_points     saveDepthMaps (txt part)        utils.cpp:31-46                ("col row depth" lines)
   load_depth_points     its inverse, as scripts/evaluate_mcemvs_dsec.py:69-79 reads it (255 = no estimate)
-  save_depth_maps       saveDepthMaps                   utils.cpp:22-104               (the txt and the two .png it writes)
+  read_png_gray16       plt.imread of a DSEC disparity image, scripts/evaluate_mcemvs_dsec.py:99 (.png, 16-bit grayscale: the samples)
+  write_png_gray16      test helper: the same format, with any of the five filter types
+  dsec_disparity_name   the file name of a ground-truth frame, scripts/evaluate_mcemvs_dsec.py:99
+  save_depth_maps       saveDepthMaps                  utils.cpp:22-104               (the txt and the two .png it writes)
   save_pcd_ascii        pcl::io::savePCDFileASCII       main.cpp:397-402               (.pcd v0.7, PointXYZI, ascii)
   read_pose_bag         parse of geometry_msgs/PoseStamped bags   data_loading.cpp:221-302 (ROSBAG v2.0; none / bz2 chunks)
   read_event_bag        parse of dvs_msgs/EventArray bags         data_loading.cpp:31-107, 211-216
@@ -68,6 +71,125 @@ def write_png_rgb8(path, img_bgr):
         f.write(b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", cols, rows, 8, 2, 0, 0, 0)) +
                 _png_chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + _png_chunk(b"IEND", b""))
     return rows, cols
+
+
+def write_png_gray16(path, img, filters=0):
+    """A 16-bit grayscale PNG (colour type 0, samples big-endian) of a uint16 [rows][cols] image, the format of DSEC's
+    disparity images.  filters: one PNG filter type (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth) for every scanline, or one
+    per row."""
+    img = np.ascontiguousarray(img)
+    if img.dtype != np.uint16 or img.ndim != 2 or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError("write_png_gray16 takes a non-empty 2-D uint16 image")
+    rows, cols = img.shape
+    ftypes = np.broadcast_to(np.asarray(filters, np.int64), (rows,))
+    if ((ftypes < 0) | (ftypes > 4)).any():
+        raise ValueError("PNG filter types are 0 .. 4")
+    lines = img.astype(">u2").view(np.uint8).reshape(rows, 2 * cols).astype(np.int64)
+    body = bytearray()
+    prev = np.zeros(2 * cols, np.int64)
+    for r in range(rows):
+        cur = lines[r]
+        a = np.concatenate([np.zeros(2, np.int64), cur[:-2]])        # the byte one pixel (2 bytes) to the left
+        c = np.concatenate([np.zeros(2, np.int64), prev[:-2]])
+        ft = int(ftypes[r])
+        pred = (0, a, prev, (a + prev) // 2, _paeth(a, prev, c))[ft]
+        body.append(ft)
+        body += ((cur - pred) & 255).astype(np.uint8).tobytes()
+        prev = cur
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", cols, rows, 16, 0, 0, 0, 0)) +
+                _png_chunk(b"IDAT", zlib.compress(bytes(body), 6)) + _png_chunk(b"IEND", b""))
+    return rows, cols
+
+
+def _paeth(a, b, c):
+    p = a + b - c
+    pa, pb, pc = np.abs(p - a), np.abs(p - b), np.abs(p - c)
+    return np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
+
+
+def read_png_gray16(path):
+    """The uint16 [rows][cols] samples of a 16-bit grayscale PNG (colour type 0, bit depth 16, not interlaced; the five
+    filter types; any number of IDAT chunks; ancillary chunks skipped), as scripts/evaluate_mcemvs_dsec.py:99 needs
+    them: plt.imread gives these samples / 65535 as float32 (engine.disparity_from_png16).  Any other PNG, a bad
+    checksum or a short file raises ValueError."""
+    with open(path, "rb") as f:
+        buf = f.read()
+    if buf[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError("%s: not a PNG file" % path)
+    pos, header, data, ended = 8, None, [], False
+    while pos + 12 <= len(buf) and not ended:
+        (length,), kind = struct.unpack(">I", buf[pos:pos + 4]), buf[pos + 4:pos + 8]
+        body = buf[pos + 8:pos + 8 + length]
+        if len(body) != length or pos + 12 + length > len(buf):
+            raise ValueError("%s: truncated %r chunk" % (path, kind))
+        if struct.unpack(">I", buf[pos + 8 + length:pos + 12 + length])[0] != (zlib.crc32(kind + body) & 0xffffffff):
+            raise ValueError("%s: bad checksum in %r chunk" % (path, kind))
+        pos += 12 + length
+        if kind == b"IHDR":
+            if length != 13:
+                raise ValueError("%s: bad IHDR" % path)
+            header = struct.unpack(">IIBBBBB", body)
+        elif kind == b"IDAT":
+            data.append(body)
+        elif kind == b"IEND":
+            ended = True
+        elif not (kind[0] & 0x20):
+            raise ValueError("%s: unknown critical chunk %r" % (path, kind))
+    if header is None or not ended:
+        raise ValueError("%s: no IHDR or no IEND chunk" % path)
+    cols, rows, depth, colour, compression, filt, interlace = header
+    if (depth, colour) != (16, 0):
+        raise ValueError("%s: bit depth %d, colour type %d: only 16-bit grayscale is read" % (path, depth, colour))
+    if interlace != 0 or compression != 0 or filt != 0:
+        raise ValueError("%s: interlaced or unknown compression / filter method" % path)
+    if rows < 1 or cols < 1:
+        raise ValueError("%s: empty image" % path)
+    try:
+        raw = zlib.decompress(b"".join(data))
+    except zlib.error as e:
+        raise ValueError("%s: %s" % (path, e))
+    stride = 2 * cols
+    if len(raw) != rows * (stride + 1):
+        raise ValueError("%s: %d bytes of image data, expected %d" % (path, len(raw), rows * (stride + 1)))
+    lines = np.frombuffer(raw, np.uint8).reshape(rows, stride + 1)
+    out = np.zeros((rows, stride), np.uint8)
+    prev = np.zeros(stride, np.int64)
+    for r in range(rows):
+        ft, x = int(lines[r, 0]), lines[r, 1:].astype(np.int64)
+        if ft == 0:
+            cur = x
+        elif ft == 2:
+            cur = (x + prev) & 255
+        elif ft == 1:                                              # each of the two byte lanes is a running sum
+            cur = np.empty(stride, np.int64)
+            cur[0::2], cur[1::2] = np.cumsum(x[0::2]) & 255, np.cumsum(x[1::2]) & 255
+        elif ft in (3, 4):                                         # the left neighbour is a reconstructed byte: serial
+            cur = np.empty(stride, np.int64)
+            xs, ps = x.tolist(), prev.tolist()
+            line = [0] * stride
+            for i in range(stride):
+                a = line[i - 2] if i >= 2 else 0
+                b = ps[i]
+                if ft == 3:
+                    pred = (a + b) >> 1
+                else:
+                    c = ps[i - 2] if i >= 2 else 0
+                    p = a + b - c
+                    pa, pb, pc = abs(p - a), abs(p - b), abs(p - c)
+                    pred = a if (pa <= pb and pa <= pc) else (b if pb <= pc else c)
+                line[i] = (xs[i] + pred) & 255
+            cur[:] = line
+        else:
+            raise ValueError("%s: filter type %d in row %d" % (path, ft, r))
+        out[r] = cur
+        prev = cur
+    return out.view(">u2").astype(np.uint16)
+
+
+def dsec_disparity_name(frame_id):
+    """scripts/evaluate_mcemvs_dsec.py:99: the file of ground-truth frame `frame_id` in DSEC's disparity_event folder."""
+    return str(int(frame_id) * 2).zfill(6) + ".png"
 
 
 def save_depth_maps(out_path, suffix, depth, conf, mask, min_depth, max_depth, images=None, ctx=None, lut=None):

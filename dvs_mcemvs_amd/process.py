@@ -736,7 +736,7 @@ class WindowStream:
 def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop_time_s, duration,
                   out_skip, fusion_method=E.FUSE_HM, forward_looking=True, rv_pos=0.0, options_depth_map=None,
                   options_point_cloud=None, polarities=None, save_images=False, out_path=None, lut=None, score=None,
-                  ground_truth=None, **kw):
+                  ground_truth=None, ground_truth_disparity=None, thicken_edges=False, **kw):
     """Generator over the windows of main.cpp:177-302: yields (ts, depth, confidence, indices) per
     window, pipelined one window deep; with options_depth_map, (ts, depth_map, confidence_map, mask)
     -- the filtered outputs the reference saves per window; with options_point_cloud as well, the window's
@@ -759,9 +759,23 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
     None for a window without one: nearest_ground_truth picks the frame as the reference's script does): every window's
     filtered depth map and mask -- the host arrays this generator yields anyway, for process_method 2 / 5 those of the
     time_camera output -- are added to the score against that window's ground truth before the window is yielded.  Needs
-    options_depth_map.  Nothing more is downloaded for it; the caller reads score.metrics() / score.curves() at the end."""
-    if (score is None) != (ground_truth is None):
-        raise ValueError("score and ground_truth go together")
+    options_depth_map.  Nothing more is downloaded for it; the caller reads score.metrics() / score.curves() at the end.
+    score= with ground_truth_disparity=(frames_u16, gt_times, projector) instead: the ground truth is made on the device
+    from DSEC's disparity images (scripts/evaluate_mcemvs_dsec.py:98-122).  frames_u16: the uint16 samples of the PNGs
+    (io.read_png_gray16), a sequence or a callable index -> image; gt_times: their times in the unit and origin of ts;
+    projector: an engine.GroundTruthProjector of the score's context and the DSI's (dimY, dimX).  Per window
+    nearest_ground_truth picks the frame -- a window whose nearest frame is 0.1 or more away is not scored, as the script
+    skips it --, the projector makes its depth map and the score reads it where it lies: 2 bytes per pixel travel.
+    thicken_edges=True (this path only): the window's depth map and mask go through engine.thicken_edges first, the
+    script's switch of that name (:75-79)."""
+    if ground_truth is not None and ground_truth_disparity is not None:
+        raise ValueError("ground_truth and ground_truth_disparity exclude each other")
+    if thicken_edges and ground_truth_disparity is None:
+        raise ValueError("thicken_edges belongs to ground_truth_disparity")
+    if (score is None) != (ground_truth is None and ground_truth_disparity is None):
+        raise ValueError("score and ground_truth (or ground_truth_disparity) go together")
+    if ground_truth_disparity is not None and len(ground_truth_disparity) != 3:
+        raise ValueError("ground_truth_disparity is (frames_u16, gt_times, projector)")
     if score is not None and options_depth_map is None:
         raise ValueError("score needs options_depth_map: the filtered depth maps are what is scored")
     if options_point_cloud is not None and options_depth_map is None:
@@ -781,7 +795,7 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
     ws = WindowStream(ctx, cams, dsi_shape, fusion_method, **kw)
     pending = None
     images = None
-    scoring = None if score is None else (score, ground_truth)
+    scoring = None if score is None else (score, ground_truth, ground_truth_disparity, bool(thicken_edges))
     if save_images:
         images = {"fusion_method": int(fusion_method), "min_depth": dsi_shape.min_depth_, "max_depth": dsi_shape.max_depth_, "out_path": out_path,
                   "lut": lut}
@@ -825,11 +839,21 @@ def nearest_ground_truth(gt_times, t, max_dt=0.1):
 
 def _window_result(ws, pending, options_depth_map, options_point_cloud, images=None, scoring=None):
     out = ws.fetch(pending[1], options_depth_map, options_point_cloud)
-    if scoring is not None:
+    if scoring is not None and scoring[1] is not None:
         gt = scoring[1](pending[0])
         if gt is not None:
             maps = out if ws.process_method == 1 else out[0]
             scoring[0].add(maps[0], maps[2], gt)
+    elif scoring is not None:
+        frames, gt_times, projector = scoring[2]
+        i = nearest_ground_truth(gt_times, pending[0])               # evaluate_mcemvs_dsec.py:98-105
+        if i is not None:
+            maps = out if ws.process_method == 1 else out[0]
+            depth, mask = maps[0], maps[2]
+            if scoring[3]:
+                depth, mask = E.thicken_edges(projector.ctx, depth, mask)
+            projector.project_png16(frames(i) if callable(frames) else frames[i])
+            scoring[0].addGroundTruth(depth, mask, projector)
     if images is not None:
         from . import io as _io
         ts = pending[0]

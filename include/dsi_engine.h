@@ -872,6 +872,51 @@ DSI_API int dsi_score_median(dsi_score_t *s, double *median_abs);
 DSI_API int dsi_score_histogram(dsi_score_t *s, double binwidth, uint64_t *counts, size_t cap, size_t *n_bins,
                                 double *first_edge, double *last_edge);
 
+/* ---- ground-truth depth from DSEC disparity images (scripts/evaluate_mcemvs_dsec.py:75-79, 108-122; definitions:
+ * DESIGN.md 7g) ----
+ * A projector lives on the device of its context and holds the calibration, a winner table and the output map.  For the
+ * float32 disparity image d[height][width] (the script's disp.astype(np.float32) * 256) and source pixel (x, y), all in
+ * float64 on the exact values, sums left to right, no contraction:
+ *   h_i = ((Q[i][0] x + Q[i][1] y) + Q[i][2] d) + Q[i][3];  (X, Y, Z) = (h_0, h_1, h_2) / h_3, each rounded to float32
+ *   kept iff Z < +inf as float32 (NaN, +inf dropped; -inf and negatives kept);
+ *   P_i = ((T[i][0] X + T[i][1] Y) + T[i][2] Z) + T[i][3];  p_i = ((K[i][0] P_0 + K[i][1] P_1) + K[i][2] P_2) + K[i][3] P_3;
+ *   iu = trunc(p_0 / p_2), iv = trunc(p_1 / p_2);  OUTSIDE: u or v not finite, or not -W <= iu < W, or not -H <= iv < H;
+ *   out[iv][iu] = float32(P_2), negative indices wrapping as numpy's; of several points on one pixel the one with the
+ *   largest row-major source index wins; untouched pixels are 0.
+ * DSI_GT_AS_SCRIPT: one outside point leaves the whole map zero (the script's except branch).  DSI_GT_DROP_OUTSIDE: outside
+ * points and points with a negative index are dropped one by one, the rest is written.  n_points = kept points, n_outside =
+ * kept points that are outside, in both modes.  No floating-point atomics: the map is a function of the inputs alone. */
+typedef struct dsi_gt dsi_gt_t;
+#define DSI_GT_AS_SCRIPT 0
+#define DSI_GT_DROP_OUTSIDE 1
+/* Q[16], T[16] (the matrix that is applied: the script's inv(T_rect0_0)), K[12] (3 x 4, the script's K_0): row-major doubles.
+ * DSI_ERR_INVALID: width or height < 1, width * height >= 2^32 - 1, a non-finite entry, an unknown mode.  The context
+ * refuses to be destroyed before its projectors. */
+DSI_API int dsi_gt_create(dsi_context_t *ctx, int width, int height, const double *Q, const double *T, const double *K,
+                          int mode, dsi_gt_t **out);
+DSI_API int dsi_gt_destroy(dsi_gt_t *gt);
+/* uploads disp_f32_host[height * width] and projects it on the context's stream, without a synchronise (an array in
+ * page-locked memory must stay unchanged until the stream has run); the map stays on the device */
+DSI_API int dsi_gt_project(dsi_gt_t *gt, const float *disp_f32_host);
+/* same, from the 16-bit samples of the disparity PNG: d = (float32(raw) / 65535f) * 256f on the device (matplotlib's 16-bit
+ * rule, then the script's * 256); 2 bytes per pixel travel */
+DSI_API int dsi_gt_project_u16(dsi_gt_t *gt, const uint16_t *raw_u16_host);
+/* synchronises; the last projection's map (depth_host[height * width], may be NULL) and counts (each may be NULL);
+ * before the first projection: zeros */
+DSI_API int dsi_gt_fetch(dsi_gt_t *gt, float *depth_host, uint64_t *n_points, uint64_t *n_outside);
+/* the map on the device (float32 [height][width]); NULL for a NULL projector */
+DSI_API float *dsi_gt_device_ptr(dsi_gt_t *gt);
+/* dsi_score_add against the projector's map on the device: no ground truth travels.  DSI_ERR_CONTEXT unless both belong to
+ * one context; DSI_ERR_INVALID unless n_pixels == width * height */
+DSI_API int dsi_score_add_gt(dsi_score_t *s, const float *depth_host, const uint8_t *mask_host, size_t n_pixels, dsi_gt_t *gt);
+/* dsi_score_add_mapper against the projector's map: nothing travels.  Same context and pixel-count rules. */
+DSI_API int dsi_score_add_mapper_gt(dsi_score_t *s, dsi_mapper_t *m, dsi_gt_t *gt);
+/* the script's thicken_edges (:75-79): v = mask ? depth : no_estimate (the script's 255); e = min of v over the 3 x 3 cross
+ * (MORPH_ELLIPSE, Size(3, 3)), neighbours outside the image not contributing; out_depth = e, out_mask = (e != no_estimate).
+ * NaN inputs give unspecified output.  Synchronises.  rows, cols >= 1, at most 2^29 pixels, else DSI_ERR_INVALID. */
+DSI_API int dsi_depth_erode(dsi_context_t *ctx, const float *depth_host, const uint8_t *mask_host, int rows, int cols,
+                            float no_estimate, float *out_depth_host, uint8_t *out_mask_host);
+
 /* pcl::RadiusOutlierRemoval (radius_outlier_removal.hpp, dense cloud) on its own: point i of the n points xyz_host
  * (stride_floats = 3 or 4 floats per point; x, y, z first) is kept (keep_host[i] = 1) iff at least min_neighbors + 1
  * points j -- j = i and duplicates included -- satisfy (double) d2(i, j) <= (double) radius * (double) radius, with

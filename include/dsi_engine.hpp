@@ -1226,6 +1226,55 @@ inline void saveDepthMaps(Context& ctx, const DepthImg& depth_map, const ConfImg
     if (inv_depth_bgr) inv_depth_bgr->swap(bgr);
 }
 
+// Ground-truth depth from DSEC disparity images on the device (dsi_gt_*): what the reference's
+// scripts/evaluate_mcemvs_dsec.py:108-122 computes per frame.  Q[16], T[16] (the matrix that is applied: the script's
+// inv(T_rect0_0)) and K[12] (3 x 4, the script's K_0) are row-major doubles.  Images are of any type dsi::image_data reads.
+class GroundTruthProjector {
+public:
+    GroundTruthProjector(Context& ctx, int width, int height, const double* Q, const double* T, const double* K,
+                         int mode = DSI_GT_AS_SCRIPT)
+        : width_(width), height_(height)
+    {
+        check(dsi_gt_create(ctx.handle(), width, height, Q, T, K, mode, &h_));
+    }
+    ~GroundTruthProjector() { dsi_gt_destroy(h_); }
+    GroundTruthProjector(const GroundTruthProjector&) = delete;
+    GroundTruthProjector& operator=(const GroundTruthProjector&) = delete;
+    dsi_gt_t* handle() const { return h_; }
+    int width() const { return width_; }
+    int height() const { return height_; }
+
+    // disparity: float32 [height][width], the script's disp.astype(np.float32) * 256; queued on the context's stream
+    template <typename DispImg>
+    void project(const DispImg& disparity)
+    {
+        check_size(disparity.rows, disparity.cols);
+        check(dsi_gt_project(h_, dsi::image_data<float>(const_cast<DispImg&>(disparity))));
+    }
+    // raw: the uint16 samples of the disparity PNG; converted on the device
+    template <typename RawImg>
+    void projectPng16(const RawImg& raw)
+    {
+        check_size(raw.rows, raw.cols);
+        check(dsi_gt_project_u16(h_, dsi::image_data<uint16_t>(const_cast<RawImg&>(raw))));
+    }
+    // the last projection's depth map (float32, created as height x width) and counts; synchronises
+    template <typename DepthImg>
+    void fetch(DepthImg& depth, uint64_t* n_points = nullptr, uint64_t* n_outside = nullptr) const
+    {
+        check(dsi_gt_fetch(h_, dsi::image_create<float>(depth, height_, width_), n_points, n_outside));
+    }
+    float* devicePtr() const { return dsi_gt_device_ptr(h_); }
+
+private:
+    void check_size(int rows, int cols) const
+    {
+        if (rows != height_ || cols != width_) throw Error(DSI_ERR_INVALID, "GroundTruthProjector: the image must be height x width");
+    }
+    dsi_gt_t* h_ = nullptr;
+    int width_ = 0, height_ = 0;
+};
+
 // Depth maps scored against ground-truth depth on the device (dsi_score_*): the metrics of the reference's
 // scripts/depth_metrics.py and the curves of precision_completeness.py over every window added.  Images are of any type
 // dsi::image_data reads (cv::Mat CV_32FC1 / CV_8UC1, dsi::Image<T>).
@@ -1259,6 +1308,22 @@ public:
     void addMapper(MapperT& mapper, const GtImg& ground_truth)
     {
         check(dsi_score_add_mapper(h_, mapper.handle(), dsi::image_data<float>(const_cast<GtImg&>(ground_truth))));
+    }
+    // one window against the depth map a projector last made: the ground truth is read where it lies on the device
+    template <typename DepthImg, typename MaskImg>
+    void add(const DepthImg& depth_map, const MaskImg& mask, const GroundTruthProjector& projector)
+    {
+        if (mask.rows != depth_map.rows || mask.cols != depth_map.cols)
+            throw Error(DSI_ERR_INVALID, "DepthScore::add: depth_map and mask must have one size");
+        check(dsi_score_add_gt(h_, dsi::image_data<float>(const_cast<DepthImg&>(depth_map)),
+                               dsi::image_data<uint8_t>(const_cast<MaskImg&>(mask)), (size_t)depth_map.rows * depth_map.cols,
+                               projector.handle()));
+    }
+    // a mapper's filtered maps against a projector's depth map: nothing is uploaded
+    template <typename MapperT>
+    void addMapper(MapperT& mapper, const GroundTruthProjector& projector)
+    {
+        check(dsi_score_add_mapper_gt(h_, mapper.handle(), projector.handle()));
     }
     dsi_score_metrics_t metrics() const
     {
