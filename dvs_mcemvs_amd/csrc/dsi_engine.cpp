@@ -3899,6 +3899,114 @@ int dsi_depth_erode(dsi_context_t* ctx, const float* depth_host, const uint8_t* 
     return DSI_OK;
 }
 
+// ---- lens rectification table ----
+
+int dsi_lens_check(const dsi_lens_t* lens)
+{
+    REQUIRE(lens, DSI_ERR_INVALID, "null argument");
+    REQUIRE(lens->model == DSI_LENS_PLUMB_BOB || lens->model == DSI_LENS_FISHEYE, DSI_ERR_INVALID,
+            "unknown lens model %d (DSI_LENS_PLUMB_BOB 0, DSI_LENS_FISHEYE 1)", lens->model);
+    const int n = lens->n_dist;
+    if (lens->model == DSI_LENS_PLUMB_BOB)
+        REQUIRE(n == 0 || n == 4 || n == 5 || n == 8, DSI_ERR_INVALID,
+                "plumb_bob takes 0, 4, 5 or 8 distortion coefficients (got %d; thin-prism and tilt terms are not supported)", n);
+    else
+        REQUIRE(n == 4, DSI_ERR_INVALID, "fisheye takes 4 distortion coefficients (got %d)", n);
+    for (int i = 0; i < 9; ++i)
+        REQUIRE(std::isfinite(lens->K[i]) && std::isfinite(lens->R[i]), DSI_ERR_INVALID, "K and R must be finite (entry %d)", i);
+    for (int i = 0; i < n; ++i) REQUIRE(std::isfinite(lens->D[i]), DSI_ERR_INVALID, "D must be finite (entry %d)", i);
+    for (int i = 0; i < 12; ++i) REQUIRE(std::isfinite(lens->P[i]), DSI_ERR_INVALID, "P must be finite (entry %d)", i);
+    REQUIRE(lens->K[0] != 0.0 && lens->K[4] != 0.0, DSI_ERR_INVALID, "fx = K[0] and fy = K[4] must not be 0");
+    return DSI_OK;
+}
+
+int dsi_lens_rr(const dsi_lens_t* lens, double RR[9])
+{
+    REQUIRE(lens && RR, DSI_ERR_INVALID, "null argument");
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double s = 0.0;
+            for (int k = 0; k < 3; ++k) s = s + lens->P[4 * i + k] * lens->R[3 * k + j];
+            RR[3 * i + j] = s;
+        }
+    return DSI_OK;
+}
+
+namespace {
+
+int lens_coef(const dsi_lens_t* lens, dsi::LensCoef* c)
+{
+    if (int rc = dsi_lens_check(lens)) return rc;
+    *c = dsi::LensCoef{};
+    c->fx = lens->K[0];
+    c->fy = lens->K[4];
+    c->cx = lens->K[2];
+    c->cy = lens->K[5];
+    for (int i = 0; i < lens->n_dist; ++i) c->k[i] = lens->D[i];
+    return dsi_lens_rr(lens, c->RR);
+}
+
+int lens_size_check(int width, int height)
+{
+    REQUIRE(width >= 1 && height >= 1, DSI_ERR_INVALID, "the table must be at least 1 x 1 (got %d x %d)", width, height);
+    REQUIRE(width <= 65536 && height <= 65536, DSI_ERR_INVALID, "event coordinates are u16 (got %d x %d)", width, height);
+    REQUIRE((unsigned long long)width * (unsigned long long)height < 0xffffffffull, DSI_ERR_INVALID,
+            "width * height must be below 2^32 - 1 (got %d x %d)", width, height);
+    return DSI_OK;
+}
+
+}  // namespace
+
+int dsi_rectify_lut_dev(dsi_context_t* ctx, const dsi_lens_t* lens, int width, int height, float* lut_dev)
+{
+    REQUIRE(ctx && lens && lut_dev, DSI_ERR_INVALID, "null argument");
+    REQUIRE(((uintptr_t)lut_dev & 7u) == 0, DSI_ERR_INVALID, "the table must be 8-byte aligned");
+    dsi::LensCoef c;
+    if (int rc = lens_coef(lens, &c)) return rc;
+    if (int rc = lens_size_check(width, height)) return rc;
+    if (int rc = set_device(ctx)) return rc;
+    HIP_TRY(dsi::launch_rectify_lut(ctx->stream, lens->model, c, width, height, reinterpret_cast<float2*>(lut_dev)));
+    return DSI_OK;
+}
+
+int dsi_rectify_lut(dsi_context_t* ctx, const dsi_lens_t* lens, int width, int height, float* lut_host)
+{
+    REQUIRE(ctx && lens && lut_host, DSI_ERR_INVALID, "null argument");
+    if (int rc = dsi_lens_check(lens)) return rc;
+    if (int rc = lens_size_check(width, height)) return rc;
+    if (int rc = set_device(ctx)) return rc;
+    const size_t bytes = (size_t)width * height * sizeof(float2);
+    HIP_TRY(ctx->img_bytes.reserve(bytes));
+    float* dev = reinterpret_cast<float*>(ctx->img_bytes.p);
+    if (int rc = dsi_rectify_lut_dev(ctx, lens, width, height, dev)) return rc;
+    HIP_TRY(hipMemcpyAsync(lut_host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DSI_OK;
+}
+
+int dsi_mapper_create_with_lens(dsi_context_t* ctx, const dsi_mapper_config_t* cfg, const dsi_lens_t* lens, dsi_mapper_t** out)
+{
+    REQUIRE(ctx && cfg && lens && out, DSI_ERR_INVALID, "null argument");
+    *out = nullptr;
+    REQUIRE(!cfg->lut, DSI_ERR_INVALID, "a table (cfg->lut) and a lens exclude each other");
+    dsi::LensCoef c;
+    if (int rc = lens_coef(lens, &c)) return rc;
+    if (int rc = lens_size_check(cfg->sensor_width, cfg->sensor_height)) return rc;
+    dsi_mapper* m = nullptr;
+    if (int rc = dsi_mapper_create(ctx, cfg, &m)) return rc;
+    // the table goes straight into the mapper's own buffer; the wait makes it visible to every stream that will read it
+    // (the mapper's preparation stream does not follow the context's) and brings a failed launch back from here
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->lut_dev), (size_t)cfg->sensor_width * cfg->sensor_height * sizeof(float2));
+    if (e == hipSuccess) e = dsi::launch_rectify_lut(ctx->stream, lens->model, c, cfg->sensor_width, cfg->sensor_height, m->lut_dev);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        dsi_mapper_destroy(m);
+        return fail(DSI_ERR_HIP, "mapper lens table failed: %s", hipGetErrorString(e));
+    }
+    *out = m;
+    return DSI_OK;
+}
+
 int dsi_radius_outlier_removal(dsi_context_t* ctx, const float* xyz_host, size_t stride_floats, size_t n, float radius,
                                int min_neighbors, uint8_t* keep_host)
 {

@@ -426,4 +426,15 @@ hipError_t launch_gt_project_u16(hipStream_t s, const uint16_t* raw, const GtCal
 hipError_t launch_depth_erode_cross(hipStream_t s, const float* depth, const uint8_t* mask, int rows, int cols, float no_estimate,
                                     float* out_depth, uint8_t* out_mask);
 
+// ---- lens rectification table: precomputeRectifiedPoints, mapper_emvs_stereo.cpp:256-299 ----
+constexpr int LENS_PLUMB_BOB = 0, LENS_FISHEYE = 1;  // DSI_LENS_PLUMB_BOB, DSI_LENS_FISHEYE
+// what the kernel reads of a dsi_lens_t, by value in the kernel-argument segment (168 bytes)
+struct LensCoef {
+    double fx, fy, cx, cy;
+    double k[8];   // plumb_bob: k1 k2 p1 p2 k3 k4 k5 k6 (missing ones 0); fisheye: k1..k4
+    double RR[9];  // P[:, 0:3] R, row-major
+};
+// lut[y * width + x] = float32 (u, v) of raw pixel (x, y); width * height < 2^32 - 1
+hipError_t launch_rectify_lut(hipStream_t s, int model, const LensCoef& c, int width, int height, float2* lut);
+
 }  // namespace dsi

@@ -8515,3 +8515,112 @@ hipError_t launch_depth_erode_cross(hipStream_t s, const float* depth, const uin
 }
 
 }  // namespace dsi
+
+// ---- lens rectification table: MapperEMVS::precomputeRectifiedPoints (mapper_emvs_stereo.cpp:256-299) ----
+namespace dsi {
+namespace {
+
+constexpr int kLensBlock = 256;
+
+// the plumb_bob inverse as cv::undistortPoints iterates it (5 rounds, no epsilon exit), then RR = P[:, :3] R applied.
+// float64 throughout, every product and sum left to right, no contraction.
+__device__ __forceinline__ void lens_plumb_bob(const LensCoef& c, double x, double y, double* u, double* v)
+{
+    const double k1 = c.k[0], k2 = c.k[1], p1 = c.k[2], p2 = c.k[3], k3 = c.k[4], k4 = c.k[5], k5 = c.k[6], k6 = c.k[7];
+    const double ifx = 1.0 / c.fx, ify = 1.0 / c.fy;
+    const double x0 = (x - c.cx) * ifx, y0 = (y - c.cy) * ify;
+    double X = x0, Y = y0;
+#pragma unroll 1
+    for (int j = 0; j < 5; ++j) {
+        const double r2 = X * X + Y * Y;
+        const double icdist = (1.0 + ((k6 * r2 + k5) * r2 + k4) * r2) / (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2);
+        if (icdist < 0.0) {
+            X = x0;
+            Y = y0;
+            break;
+        }
+        const double dX = 2.0 * p1 * X * Y + p2 * (r2 + 2.0 * X * X);
+        const double dY = p1 * (r2 + 2.0 * Y * Y) + 2.0 * p2 * X * Y;
+        X = (x0 - dX) * icdist;
+        Y = (y0 - dY) * icdist;
+    }
+    const double xx = c.RR[0] * X + c.RR[1] * Y + c.RR[2], yy = c.RR[3] * X + c.RR[4] * Y + c.RR[5];
+    const double ww = 1.0 / (c.RR[6] * X + c.RR[7] * Y + c.RR[8]);
+    *u = xx * ww;
+    *v = yy * ww;
+}
+
+// the Kannala-Brandt inverse as cv::fisheye::undistortPoints iterates it (Newton, at most 10 rounds, |fix| < 1e-8); a pixel
+// that does not converge, or whose angle changes sign, gets OpenCV's -1000000.  sqrt is the correctly rounded one
+// (k_pc_backproject's); tan is the device library's, the only operation here that is not correctly rounded.
+__device__ __forceinline__ void lens_fisheye(const LensCoef& c, double x, double y, double* u, double* v)
+{
+    const double k1 = c.k[0], k2 = c.k[1], k3 = c.k[2], k4 = c.k[3];
+    const double px = (x - c.cx) / c.fx, py = (y - c.cy) / c.fy;
+    const double half_pi = 1.57079632679489661923;
+    double theta_d = sqrt(px * px + py * py);
+    theta_d = fmin(fmax(-half_pi, theta_d), half_pi);
+    double theta = theta_d, scale = 0.0;
+    bool converged = false;
+    if (fabs(theta_d) > 1e-8) {
+#pragma unroll 1
+        for (int j = 0; j < 10; ++j) {
+            const double t2 = theta * theta, t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4;
+            const double a = k1 * t2, b = k2 * t4, cc = k3 * t6, d = k4 * t8;
+            const double fix = (theta * (1.0 + a + b + cc + d) - theta_d) / (1.0 + 3.0 * a + 5.0 * b + 7.0 * cc + 9.0 * d);
+            theta = theta - fix;
+            if (fabs(fix) < 1e-8) {
+                converged = true;
+                break;
+            }
+        }
+        scale = tan(theta) / theta_d;
+    } else {
+        converged = true;
+    }
+    const bool flipped = (theta_d < 0.0 && theta > 0.0) || (theta_d > 0.0 && theta < 0.0);
+    if (converged && !flipped) {
+        const double X = px * scale, Y = py * scale;
+        const double w = c.RR[6] * X + c.RR[7] * Y + c.RR[8];
+        *u = (c.RR[0] * X + c.RR[1] * Y + c.RR[2]) / w;
+        *v = (c.RR[3] * X + c.RR[4] * Y + c.RR[5]) / w;
+    } else {
+        *u = -1000000.0;
+        *v = -1000000.0;
+    }
+}
+
+// One thread per raw pixel (x, y): lut[y W + x] = float32 of its rectified position.  Registers only: no LDS, no atomics;
+// the coefficients and RR arrive in the kernel-argument segment.
+template <int MODEL>
+__global__ __launch_bounds__(kLensBlock) void k_rectify_lut(LensCoef c, int W, unsigned long long npix, float2* __restrict__ lut)
+{
+    const unsigned long long i = (unsigned long long)blockIdx.x * kLensBlock + threadIdx.x;
+    if (i >= npix) return;
+    const unsigned long long yi = i / (unsigned long long)W;
+    const double x = (double)(i - yi * (unsigned long long)W), y = (double)yi;
+    double u, v;
+    if (MODEL == LENS_FISHEYE)
+        lens_fisheye(c, x, y, &u, &v);
+    else
+        lens_plumb_bob(c, x, y, &u, &v);
+    lut[i] = make_float2((float)u, (float)v);
+}
+
+}  // namespace
+
+hipError_t launch_rectify_lut(hipStream_t s, int model, const LensCoef& c, int width, int height, float2* lut)
+{
+    const unsigned long long n = (unsigned long long)width * (unsigned long long)height;
+    if (!lut || width < 1 || height < 1 || n >= 0xffffffffull) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((n + kLensBlock - 1) / kLensBlock)), block(kLensBlock);  // n < 2^32: at most 2^24 workgroups
+    if (model == LENS_PLUMB_BOB)
+        hipLaunchKernelGGL(k_rectify_lut<LENS_PLUMB_BOB>, grid, block, 0, s, c, width, n, lut);
+    else if (model == LENS_FISHEYE)
+        hipLaunchKernelGGL(k_rectify_lut<LENS_FISHEYE>, grid, block, 0, s, c, width, n, lut);
+    else
+        return hipErrorInvalidValue;
+    return hipExtGetLastError();
+}
+
+}  // namespace dsi

@@ -26,6 +26,7 @@ REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2
 VOTE_AUTO, VOTE_GLOBAL_ATOMIC, VOTE_LDS_BANDS, VOTE_FUSED_ARGMAX = 0, 1, 2, 3
 FOCUS_LOCAL_VAR, FOCUS_LOCAL_MS, FOCUS_GRAD_MAG, FOCUS_LAPLACIAN, FOCUS_DOG = 0, 1, 2, 3, 4
 GRID_OP_SUBTRACT, GRID_OP_RATIO, GRID_OP_QUADRATIC_MEAN, GRID_OP_CUBIC_MEAN = 1, 2, 3, 4
+LENS_PLUMB_BOB, LENS_FISHEYE = 0, 1
 
 (OK, ERR_INVALID, ERR_TOO_FEW_EVENTS, ERR_HIP, ERR_SHAPE, ERR_BAD_OP, ERR_NO_DEVICE,
  ERR_CONTEXT, ERR_COMM) = range(9)
@@ -47,6 +48,11 @@ class _MapperConfig(C.Structure):
                 ("min_depth", C.c_float), ("max_depth", C.c_float), ("fov_deg", C.c_float),
                 ("inverse_depth", C.c_int), ("lut", C.POINTER(C.c_float)),
                 ("plane_begin", C.c_int), ("plane_count", C.c_int)]
+
+
+class _Lens(C.Structure):
+    _fields_ = [("model", C.c_int), ("n_dist", C.c_int), ("K", C.c_double * 9), ("D", C.c_double * 8),
+                ("R", C.c_double * 9), ("P", C.c_double * 12)]
 
 
 class _DepthMapOptions(C.Structure):
@@ -246,6 +252,11 @@ def load_library():
         "dsi_score_add_gt": (C.c_int, [vp, f32p, u8p, C.c_size_t, vp]),
         "dsi_score_add_mapper_gt": (C.c_int, [vp, vp, vp]),
         "dsi_depth_erode": (C.c_int, [vp, f32p, u8p, C.c_int, C.c_int, C.c_float, f32p, u8p]),
+        "dsi_lens_check": (C.c_int, [C.POINTER(_Lens)]),
+        "dsi_lens_rr": (C.c_int, [C.POINTER(_Lens), f64p]),
+        "dsi_rectify_lut": (C.c_int, [vp, C.POINTER(_Lens), C.c_int, C.c_int, f32p]),
+        "dsi_rectify_lut_dev": (C.c_int, [vp, C.POINTER(_Lens), C.c_int, C.c_int, vp]),
+        "dsi_mapper_create_with_lens": (C.c_int, [vp, C.POINTER(_MapperConfig), C.POINTER(_Lens), C.POINTER(vp)]),
         "dsi_mapper_last_vote_info": (C.c_int, [vp, C.POINTER(_VoteInfo)]),
         "dsi_mapper_set_kernel_timing": (C.c_int, [vp, C.c_int]),
         "dsi_mapper_vote_kernel_time": (C.c_int, [vp, f32p, intp]),
@@ -1146,6 +1157,61 @@ def thicken_edges(ctx, depth, mask, no_estimate=255.0):
     return out_d, out_m
 
 
+class Lens:
+    """A camera's calibration numbers as sensor_msgs::CameraInfo holds them (dsi_lens_t; DESIGN.md 7h): model "plumb_bob" /
+    "fisheye" (or LENS_PLUMB_BOB / LENS_FISHEYE), K 3 x 3, D the distortion coefficients (plumb_bob: 0, 4, 5 or 8 of
+    k1 k2 p1 p2 k3 k4 k5 k6; fisheye: k1..k4), R 3 x 3 (default: the identity), P 3 x 4 (default: [K | 0]; its fourth column
+    is not read).  The constructor only stores them; check() is dsi_lens_check, which every entry point applies itself."""
+
+    MODELS = {"plumb_bob": LENS_PLUMB_BOB, "fisheye": LENS_FISHEYE}
+
+    def __init__(self, model, K, D, R=None, P=None):
+        if isinstance(model, str):
+            if model not in self.MODELS:
+                raise ValueError("Distortion model not set properly: %r (expected plumb_bob or fisheye)" % (model,))
+            model = self.MODELS[model]
+        self.model = int(model)
+        self.K = np.array(K, np.float64).reshape(3, 3)
+        self.D = np.array(D, np.float64).reshape(-1)
+        if self.D.size > 8:
+            raise ValueError("at most 8 distortion coefficients (got %d)" % self.D.size)
+        self.R = np.eye(3) if R is None else np.array(R, np.float64).reshape(3, 3)
+        self.P = np.hstack([self.K, np.zeros((3, 1))]) if P is None else np.array(P, np.float64).reshape(3, 4)
+
+    def _c(self):
+        c = _Lens()
+        c.model, c.n_dist = self.model, int(self.D.size)
+        c.K = (C.c_double * 9)(*self.K.ravel())
+        c.D = (C.c_double * 8)(*self.D, *([0.0] * (8 - self.D.size)))
+        c.R = (C.c_double * 9)(*self.R.ravel())
+        c.P = (C.c_double * 12)(*self.P.ravel())
+        return c
+
+    def check(self):
+        """Raises DsiError(ERR_INVALID) for what dsi_lens_check refuses.  Host only."""
+        _check(load_library().dsi_lens_check(C.byref(self._c())))
+
+    def rr(self):
+        """P[:, :3] R as the engine multiplies it (dsi_lens_rr): the matrix applied to the undistorted point.  Host only."""
+        out = np.zeros((3, 3), np.float64)
+        _check(load_library().dsi_lens_rr(C.byref(self._c()), _ptr(out, C.c_double)))
+        return out
+
+
+def rectify_lut(ctx, lens, width, height):
+    """The table of precomputeRectifiedPoints (mapper_emvs_stereo.cpp:256-299) for `lens`, made on the device: float32
+    [height * width, 2], entry y * width + x = the rectified position of the raw pixel (x, y).  Synchronises."""
+    n = max(int(width), 0) * max(int(height), 0)
+    lut = np.empty((n, 2), np.float32)
+    _check(load_library().dsi_rectify_lut(ctx._h, C.byref(lens._c()), int(width), int(height), _ptr(lut, C.c_float)))
+    return lut
+
+
+def rectify_lut_dev(ctx, lens, width, height, device_ptr):
+    """The same into device memory (2 * width * height floats, e.g. Grid3D.device_ptr), queued without a synchronise."""
+    _check(load_library().dsi_rectify_lut_dev(ctx._h, C.byref(lens._c()), int(width), int(height), C.c_void_p(device_ptr)))
+
+
 class PinnedArray:
     """numpy array in page-locked host memory (dsi_host_alloc): the source / destination of
     asynchronous uploads and depth-map fetches.  `a` is the array; close() frees the memory."""
@@ -1224,12 +1290,15 @@ class MapperEMVS:
     cam = (width, height, fx, fy, cx, cy): full resolution and the projection-matrix
     intrinsics the reference reads from image_geometry::PinholeCameraModel
     (mapper_emvs_stereo.cpp:34-48).  lut = undistortion table of
-    precomputeRectifiedPoints (mapper_emvs_stereo.cpp:256-299), shape [H*W][2] or None.
+    precomputeRectifiedPoints (mapper_emvs_stereo.cpp:256-299), shape [H*W][2] or None; lens = a Lens
+    instead: the engine makes that table on the device, in the mapper's own buffer (dsi_mapper_create_with_lens).
     """
 
-    def __init__(self, ctx, cam, dsi_shape, lut=None, inverse_depth=False, plane_range=None):
+    def __init__(self, ctx, cam, dsi_shape, lut=None, inverse_depth=False, plane_range=None, lens=None):
         """plane_range = (begin, count): own only those planes of dsi_shape's dimZ planes (plane
         sharding across GPUs; the DSI then has `count` planes and equals that slice of the full one)."""
+        if lut is not None and lens is not None:
+            raise ValueError("lut and lens exclude each other")
         w, h, fx, fy, cx, cy = cam
         cfg = _MapperConfig()
         if plane_range is not None:
@@ -1247,7 +1316,10 @@ class MapperEMVS:
         self.ctx = ctx
         self._h = C.c_void_p()
         L = load_library()
-        _check(L.dsi_mapper_create(ctx._h, C.byref(cfg), C.byref(self._h)))
+        if lens is not None:
+            _check(L.dsi_mapper_create_with_lens(ctx._h, C.byref(cfg), C.byref(lens._c()), C.byref(self._h)))
+        else:
+            _check(L.dsi_mapper_create(ctx._h, C.byref(cfg), C.byref(self._h)))
         _track(self)
         nx, ny, nz = C.c_int(), C.c_int(), C.c_int()
         kv = (C.c_float * 4)()

@@ -142,12 +142,12 @@ def alg2_plan(num_subintervals, n_events, nx, camera_time=True):
 
 def process_2(ctx, cams, dsi_shape, events, trajectories, num_subintervals, mapper_fused,
               mapper_fused_camera_time, ts, stereo_fusion, temporal_fusion, luts=(None, None),
-              inverse_depth=False, shuffle_right=False):
+              inverse_depth=False, shuffle_right=False, lenses=(None, None)):
     """Alg. 2: per sub-interval camera fusion, then temporal fusion; and the converse order
     (process2.cpp:46-289).  shuffle_right=True is process_5.  Returns dict with the left / right
-    temporal DSIs (Grid3D)."""
-    mapper0 = E.MapperEMVS(ctx, cams[0], dsi_shape, lut=luts[0], inverse_depth=inverse_depth)
-    mapper1 = E.MapperEMVS(ctx, cams[1], dsi_shape, lut=luts[1], inverse_depth=inverse_depth)
+    temporal DSIs (Grid3D).  lenses: one engine.Lens (or None) per camera instead of its table in luts."""
+    mapper0 = E.MapperEMVS(ctx, cams[0], dsi_shape, lut=luts[0], inverse_depth=inverse_depth, lens=lenses[0])
+    mapper1 = E.MapperEMVS(ctx, cams[1], dsi_shape, lut=luts[1], inverse_depth=inverse_depth, lens=lenses[1])
     dims = mapper0.dsi_.getDimensions()
     sub = E.Grid3D(ctx, *dims)     # mapper_fused_subinterval.dsi_
     left = E.Grid3D(ctx, *dims)    # mapper_fused_left.dsi_
@@ -195,7 +195,8 @@ def process_2(ctx, cams, dsi_shape, events, trajectories, num_subintervals, mapp
 
 
 def exact_depth_map_process_2(ctx, cams, dsi_shape, events, trajectories, num_subintervals, mapper_fused, ts,
-                              stereo_fusion, temporal_fusion, luts=(None, None), inverse_depth=False, rel_gap=0.0, prove=False):
+                              stereo_fusion, temporal_fusion, luts=(None, None), inverse_depth=False, rel_gap=0.0, prove=False,
+                              lenses=(None, None)):
     """Alg. 2's fused DSI (camera fusion per sub-interval, then temporal fusion; process2.cpp:98-249) and its arg-max
     with the plane index map EQUAL TO THE CPU REFERENCE'S ON EVERY PIXEL (BASELINE configs[3]).  The engine's exact
     vote sums and the reference's fp32, event-ordered sums agree to ~1e-5, so the first-maximum plane can differ in
@@ -214,8 +215,9 @@ def exact_depth_map_process_2(ctx, cams, dsi_shape, events, trajectories, num_su
     carried through the same camera fusion / temporal accumulate / finalize as the values (each widened by its roundings;
     the harmonic accumulation's inverse sums with the directions swapped), MapperEMVS.proveColumns at the end; columns the
     bounds do not settle are re-summed on all their planes (at most 4,096).  info["proof"] holds the statistics:
-    columns_unproven == columns_resolved_fully means the index map is the reference's on every pixel by proof."""
-    mappers = [E.MapperEMVS(ctx, cams[c], dsi_shape, lut=luts[c], inverse_depth=inverse_depth) for c in range(2)]
+    columns_unproven == columns_resolved_fully means the index map is the reference's on every pixel by proof.
+    lenses: one engine.Lens (or None) per camera instead of its table in luts, as in process_2."""
+    mappers = [E.MapperEMVS(ctx, cams[c], dsi_shape, lut=luts[c], inverse_depth=inverse_depth, lens=lenses[c]) for c in range(2)]
     dims = mappers[0].dsi_.getDimensions()
     sub = E.Grid3D(ctx, *dims)
     iv = None
@@ -522,7 +524,8 @@ class WindowStream:
 
     def __init__(self, ctx, cams, dsi_shape, fusion_method=E.FUSE_HM, luts=(None, None),
                  inverse_depth=False, depth=2, materialize_fused=True, fused_vote=False, concurrent=False,
-                 exact_ties=False, process_method=1, num_subintervals=4, temporal_fusion=4, camera_time=None):
+                 exact_ties=False, process_method=1, num_subintervals=4, temporal_fusion=4, camera_time=None,
+                 lenses=(None, None)):
         """materialize_fused=False: the fused DSI (the reference's mapper_fused.dsi_) is not written;
         the camera fusion happens inside the arg-max kernel (same bits, one pass less over the
         volume) -- for streams that only keep the depth maps.
@@ -536,7 +539,10 @@ class WindowStream:
         the same depth maps bit for bit).
         exact_ties=True: every window's arg-max goes through the exact tie resolver (MapperEMVS.resolveNearTies), so
         that its plane index map equals the CPU reference's on every pixel; it needs the camera DSIs, so it excludes
-        fused_vote; the call's statistics (and cost) are in `last_resolve`."""
+        fused_vote; the call's statistics (and cost) are in `last_resolve`.
+        lenses: one engine.Lens (or None) per camera -- the camera mappers' rectification tables are then made on the
+        device from the calibration numbers (MapperEMVS(lens=)) instead of being passed in luts; a camera takes one or
+        the other."""
         self.ctx = ctx
         self.process_method = int(process_method)
         if self.process_method not in (1, 2, 5):
@@ -545,6 +551,7 @@ class WindowStream:
         self.temporal_fusion = int(temporal_fusion)
         self.camera_time = (self.process_method == 2) if camera_time is None else bool(camera_time)
         self.cams, self.dsi_shape, self.luts, self.inverse_depth = cams, dsi_shape, luts, inverse_depth
+        self.lenses = lenses
         self.last_plan = None
         if self.process_method != 1:
             if self.num_subintervals < 1:
@@ -568,8 +575,8 @@ class WindowStream:
         self.contexts = [ctx] + ([E.Context(ctx.device) for _ in range(depth - 1)] if self.concurrent else [])
         self._own_contexts = self.contexts[1:]
         sets = len(self.contexts)
-        self.mapper_sets = [[E.MapperEMVS(self.contexts[k], cams[c], dsi_shape, lut=luts[c], inverse_depth=inverse_depth)
-                             for c in range(2)] for k in range(sets)]
+        self.mapper_sets = [[E.MapperEMVS(self.contexts[k], cams[c], dsi_shape, lut=luts[c], inverse_depth=inverse_depth,
+                                          lens=lenses[c]) for c in range(2)] for k in range(sets)]
         self.mappers = self.mapper_sets[0]
         dims = self.mappers[0].dsi_.getDimensions()
         self.fused = [E.Grid3D(self.contexts[k % sets], *dims) if self.materialize_fused else None for k in range(depth)]
@@ -664,7 +671,7 @@ class WindowStream:
             scratch_ct.dsi_.resetGrid()                 # (a fresh mapper_fused_camera_time per window, main.cpp:262-275)
             res = process_2(ctx, self.cams, self.dsi_shape, events, trajectories, n, self.extract[slot], scratch_ct, ts,
                             self.fusion_method, self.temporal_fusion, luts=self.luts, inverse_depth=self.inverse_depth,
-                            shuffle_right=self.process_method == 5)
+                            shuffle_right=self.process_method == 5, lenses=self.lenses)
             res["left"].close()
             res["right"].close()
             self.extract[slot].computeDepthMap()
@@ -741,6 +748,7 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
     window, pipelined one window deep; with options_depth_map, (ts, depth_map, confidence_map, mask)
     -- the filtered outputs the reference saves per window; with options_point_cloud as well, the window's
     point cloud (main.cpp:396, an (N, 4) array: WindowStream.fetch) as a fifth element.
+    lenses= (a keyword of WindowStream, like luts=): one engine.Lens per camera, the rectification tables made on the device.
     process_method=2 / 5 (keywords of WindowStream: num_subintervals, temporal_fusion, camera_time; fusion_method is the
     stereo fusion): yields (ts, time_camera outputs, camera_time outputs or None), each output element shaped like what
     process_method 1 yields after ts (main.cpp:275-299).

@@ -917,6 +917,37 @@ DSI_API int dsi_score_add_mapper_gt(dsi_score_t *s, dsi_mapper_t *m, dsi_gt_t *g
 DSI_API int dsi_depth_erode(dsi_context_t *ctx, const float *depth_host, const uint8_t *mask_host, int rows, int cols,
                             float no_estimate, float *out_depth_host, uint8_t *out_mask_host);
 
+/* ---- lens rectification: the table of MapperEMVS::precomputeRectifiedPoints (mapper_emvs_stereo.cpp:256-299) made on the
+ * device from the calibration numbers.  Entry y*W+x of the table is float32 of the rectified position of the
+ * raw pixel (x, y): plumb_bob as image_geometry::PinholeCameraModel::rectifyPoint = cv::undistortPoints(K, D, R, P) iterates it
+ * (5 fixed rounds; D = k1 k2 p1 p2 [k3 [k4 k5 k6]], no thin-prism or tilt terms), fisheye as cv::fisheye::undistortPoints(K, D,
+ * R, P) does (Kannala-Brandt, k1..k4, at most 10 Newton rounds, -1000000 where it does not converge).  All in float64; DESIGN.md
+ * 7h states the arithmetic operation by operation -- that statement is the contract, parity with an OpenCV binary is unpinned.
+ * Reading calibration FILES stays with the caller. */
+typedef enum { DSI_LENS_PLUMB_BOB = 0, DSI_LENS_FISHEYE = 1 } dsi_lens_model_t;
+typedef struct {
+    int model;        /* dsi_lens_model_t */
+    int n_dist;       /* coefficients in D: plumb_bob 0, 4, 5 or 8 (missing ones are 0); fisheye 4 */
+    double K[9], D[8], R[9], P[12];   /* row-major, as in sensor_msgs::CameraInfo; P's fourth column is not read */
+} dsi_lens_t;
+/* Host only, needs no GPU.  DSI_ERR_INVALID for an unknown model, a coefficient count the model does not have, a value of K,
+ * R, P or of the first n_dist of D that is not finite, fx = K[0] or fy = K[4] equal to 0. */
+DSI_API int dsi_lens_check(const dsi_lens_t *lens);
+/* Host only: RR = P[:, 0:3] * R (row-major 3 x 3), entry (i, j) = ((0 + p_i0 r_0j) + p_i1 r_1j) + p_i2 r_2j -- the matrix
+ * the kernel applies to the undistorted point */
+DSI_API int dsi_lens_rr(const dsi_lens_t *lens, double RR[9]);
+/* the table, made on the device on the context's stream and copied to lut_host (2 * width * height floats); synchronises.
+ * width, height in 1..65536 (event coordinates are u16), else DSI_ERR_INVALID */
+DSI_API int dsi_rectify_lut(dsi_context_t *ctx, const dsi_lens_t *lens, int width, int height, float *lut_host);
+/* the same into device memory of the caller's (2 * width * height floats, 8-byte aligned), queued on the context's stream,
+ * without a synchronise */
+DSI_API int dsi_rectify_lut_dev(dsi_context_t *ctx, const dsi_lens_t *lens, int width, int height, float *lut_dev);
+/* dsi_mapper_create whose table is made on the device straight into the mapper's own buffer: no host round trip.  cfg->lut must
+ * be NULL (DSI_ERR_INVALID otherwise); the table's size is cfg->sensor_width x cfg->sensor_height.  cfg->K stays the caller's:
+ * fx, fy, cx, cy of P, as for dsi_mapper_create. */
+DSI_API int dsi_mapper_create_with_lens(dsi_context_t *ctx, const dsi_mapper_config_t *cfg, const dsi_lens_t *lens,
+                                        dsi_mapper_t **out);
+
 /* pcl::RadiusOutlierRemoval (radius_outlier_removal.hpp, dense cloud) on its own: point i of the n points xyz_host
  * (stride_floats = 3 or 4 floats per point; x, y, z first) is kept (keep_host[i] = 1) iff at least min_neighbors + 1
  * points j -- j = i and duplicates included -- satisfy (double) d2(i, j) <= (double) radius * (double) radius, with

@@ -11,7 +11,8 @@
 // Types the reference takes from third-party packages are replaced by plain structs:
 //   dvs_msgs::Event                      -> dsi::Event {x, y, ts (seconds), polarity}
 //   geometry_utils::Transformation       -> dsi::Transformation {t[3], q[4] = w,x,y,z}
-//   image_geometry::PinholeCameraModel   -> dsi::PinholeCameraModel {width,height,fx,fy,cx,cy,lut}
+//   image_geometry::PinholeCameraModel   -> dsi::PinholeCameraModel {width,height,fx,fy,cx,cy,lut}; its K, D, R, P ->
+//                                           dsi::Lens (the table is then made on the device)
 //   cv::Mat (CV_32F / CV_8U)             -> cv::Mat itself (anything with create / ptr<T> / isContinuous / release, see
 //                                           image_create below), or dsi::Image<float> / dsi::Image<uint8_t>
 // Where the reference glog-CHECK-aborts or throws std::out_of_range this adapter throws
@@ -350,9 +351,12 @@ inline auto to_pose7(const PoseT& T, double* p) -> decltype(T.getRotation().w(),
 inline void camera_of(const PinholeCameraModel& c, PinholeCameraModel* out) { *out = c; }
 
 // The distortion model the reference reads from cam.cameraInfo().distortion_model
-// (mapper_emvs_stereo.cpp:62): "plumb_bob" -> the camera's own rectifyPoint, "fisheye" ->
-// fisheye_rectifyPoint = cv::fisheye::undistortPoints(K, D, R, P) (:243-254, :256-299).  A camera type
-// without cameraInfo() is taken as plumb_bob (image_geometry's default model).
+// (mapper_emvs_stereo.cpp:62): "plumb_bob" -> rectifyPoint, "fisheye" -> fisheye_rectifyPoint =
+// cv::fisheye::undistortPoints(K, D, R, P) (:243-254, :256-299).  A camera type without cameraInfo() is taken as
+// plumb_bob (image_geometry's default model).  Both models are computed by the engine itself from K, D, R, P --
+// dsi::lens_of(cam) reads them, camera_of(ctx, cam, &out) / rectified_points / MapperEMVS(ctx, cam, lens, shape) make the
+// table on the device, no OpenCV needed; camera_of(cam, &out) without a context is the older path that
+// calls the camera's own rectifyPoint on the host.
 template <typename CamT>
 inline auto distortion_model_of(const CamT& c, int) -> decltype(std::string(c.cameraInfo().distortion_model))
 {
@@ -364,8 +368,9 @@ inline std::string distortion_model_of(const CamT&, long)
     return "plumb_bob";
 }
 
-// Customisation point for fisheye cameras: OpenCV's arithmetic stays on the host side of the boundary, so
-// the caller overloads this for its camera type -- in that type's namespace (camera_of finds it by
+// Customisation point of the host path camera_of(cam, &out) for fisheye cameras (the device path, camera_of(ctx, cam,
+// &out), needs none: the engine has the Kannala-Brandt inverse).  A caller who wants OpenCV's own binary
+// to make the table overloads this for its camera type -- in that type's namespace (camera_of finds it by
 // argument-dependent lookup) or in namespace dsi before this header -- with the reference's own four lines --
 //   cv::Point2f raw32(x, y), rect32;  cv::fisheye::undistortPoints(src(raw32), dst(rect32), c.intrinsicMatrix(),
 //   c.distortionCoeffs(), c.rotationMatrix(), c.fullProjectionMatrix());  *u = rect32.x; *v = rect32.y;
@@ -411,6 +416,134 @@ inline auto camera_of(const CamT& c, PinholeCameraModel* out) -> decltype(c.full
             out->rectified_points[2 * ((size_t)y * out->width + x)] = (float)u;
             out->rectified_points[2 * ((size_t)y * out->width + x) + 1] = (float)v;
         }
+}
+
+// ---- lens rectification on the device (dsi_engine.h "lens rectification") ----
+
+// dsi_lens_t with the defaults of a camera without a rectifying pair: plumb_bob, no coefficients, R = I.  K and P are the
+// caller's (set_K fills P = [K | 0] as well).  All matrices row-major, as in sensor_msgs::CameraInfo.
+struct Lens : dsi_lens_t {
+    Lens() : dsi_lens_t{}
+    {
+        model = DSI_LENS_PLUMB_BOB;
+        R[0] = R[4] = R[8] = 1.0;
+    }
+    Lens& set_K(double fx, double fy, double cx, double cy)
+    {
+        const double k[9] = {fx, 0, cx, 0, fy, cy, 0, 0, 1};
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 4; ++j) P[4 * i + j] = j < 3 ? k[3 * i + j] : 0.0;
+        std::copy(k, k + 9, K);
+        return *this;
+    }
+    Lens& set_D(const std::vector<double>& d)
+    {
+        if (d.size() > 8) throw Error(DSI_ERR_INVALID, "Lens: at most 8 distortion coefficients");
+        std::fill(D, D + 8, 0.0);
+        std::copy(d.begin(), d.end(), D);
+        n_dist = (int)d.size();
+        return *this;
+    }
+    void check() const { dsi::check(dsi_lens_check(this)); }
+    std::string model_name() const { return model == DSI_LENS_FISHEYE ? "fisheye" : model == DSI_LENS_PLUMB_BOB ? "plumb_bob" : "?"; }
+};
+
+// How lens_of reads the camera's matrices: element (r, c) of K, R, P and the count / the i-th of the distortion
+// coefficients.  Defaults, tried in this order: m(r, c) (cv::Matx, cv::Mat_<double>, Eigen), m.at<double>(r, c) (cv::Mat of
+// CV_64F); d.total() (cv::Mat), d.size() (std::vector, Eigen); d(i) (cv::Mat_<double>, Eigen), d[i] (std::vector),
+// d.at<double>(i).  Overload lens_element / lens_count / lens_coefficient for anything else (in the matrix type's
+// namespace, or in namespace dsi before this header).  No OpenCV header is needed here.
+namespace detail {
+template <int N> struct prio : prio<N - 1> {};
+template <> struct prio<0> {};
+template <typename M>
+inline auto element(const M& m, int r, int c, prio<1>) -> decltype((double)m(r, c)) { return (double)m(r, c); }
+template <typename M>
+inline auto element(const M& m, int r, int c, prio<0>) -> decltype((double)m.template at<double>(r, c))
+{
+    return (double)m.template at<double>(r, c);
+}
+template <typename V>
+inline auto count(const V& d, prio<1>) -> decltype((size_t)d.total()) { return (size_t)d.total(); }
+template <typename V>
+inline auto count(const V& d, prio<0>) -> decltype((size_t)d.size()) { return (size_t)d.size(); }
+template <typename V>
+inline auto coefficient(const V& d, int i, prio<2>) -> decltype((double)d(i)) { return (double)d(i); }
+template <typename V>
+inline auto coefficient(const V& d, int i, prio<1>) -> decltype((double)d[i]) { return (double)d[i]; }
+template <typename V>
+inline auto coefficient(const V& d, int i, prio<0>) -> decltype((double)d.template at<double>(i))
+{
+    return (double)d.template at<double>(i);
+}
+}  // namespace detail
+template <typename M>
+inline auto lens_element(const M& m, int r, int c) -> decltype(detail::element(m, r, c, detail::prio<1>()))
+{
+    return detail::element(m, r, c, detail::prio<1>());
+}
+template <typename V>
+inline auto lens_count(const V& d) -> decltype(detail::count(d, detail::prio<1>()))
+{
+    return detail::count(d, detail::prio<1>());
+}
+template <typename V>
+inline auto lens_coefficient(const V& d, int i) -> decltype(detail::coefficient(d, i, detail::prio<2>()))
+{
+    return detail::coefficient(d, i, detail::prio<2>());
+}
+
+// The calibration numbers of a camera type with image_geometry::PinholeCameraModel's accessors: intrinsicMatrix() (K),
+// distortionCoeffs() (D), rotationMatrix() (R), fullProjectionMatrix() (P), and the model of distortion_model_of.
+template <typename CamT>
+inline auto lens_of(const CamT& c) -> decltype(c.intrinsicMatrix(), c.distortionCoeffs(), c.rotationMatrix(), c.fullProjectionMatrix(), Lens())
+{
+    Lens L;
+    const std::string model = distortion_model_of(c, 0);
+    if (model == "plumb_bob")
+        L.model = DSI_LENS_PLUMB_BOB;
+    else if (model == "fisheye")
+        L.model = DSI_LENS_FISHEYE;
+    else
+        throw Error(DSI_ERR_INVALID, "Distortion model not set properly: '" + model + "' (expected plumb_bob or fisheye)");
+    const auto& K = c.intrinsicMatrix();
+    const auto& D = c.distortionCoeffs();
+    const auto& R = c.rotationMatrix();
+    const auto& P = c.fullProjectionMatrix();
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            L.K[3 * i + j] = lens_element(K, i, j);
+            L.R[3 * i + j] = lens_element(R, i, j);
+        }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 4; ++j) L.P[4 * i + j] = lens_element(P, i, j);
+    const size_t n = lens_count(D);
+    if (n > 8) throw Error(DSI_ERR_INVALID, "lens_of: " + std::to_string(n) + " distortion coefficients (thin-prism and tilt terms are not supported)");
+    L.n_dist = (int)n;
+    for (size_t i = 0; i < n; ++i) L.D[i] = lens_coefficient(D, (int)i);
+    return L;
+}
+
+// the table of precomputeRectifiedPoints (2 * width * height floats, entry y * width + x), made on the device
+inline std::vector<float> rectified_points(Context& ctx, const Lens& lens, int width, int height)
+{
+    std::vector<float> lut(width > 0 && height > 0 ? (size_t)2 * width * height : 0);
+    check(dsi_rectify_lut(ctx.handle(), &lens, width, height, lut.empty() ? nullptr : lut.data()));
+    return lut;
+}
+
+// camera_of with the table made by the engine, for both distortion models: never calls the camera's rectifyPoint or
+// fisheye_rectify_point
+template <typename CamT>
+inline auto camera_of(Context& ctx, const CamT& c, PinholeCameraModel* out) -> decltype(c.fullResolution(), lens_of(c), void())
+{
+    out->width = c.fullResolution().width;
+    out->height = c.fullResolution().height;
+    out->fx = (float)c.fx();
+    out->fy = (float)c.fy();
+    out->cx = (float)c.cx();
+    out->cy = (float)c.cy();
+    out->rectified_points = rectified_points(ctx, lens_of(c), out->width, out->height);
 }
 
 // One rank of an RCCL communicator owned by the engine (dsi_engine.h "multi-GPU").
@@ -899,6 +1032,30 @@ public:
         cfg.inverse_depth = inverse_depth ? 1 : 0;
         cfg.lut = cam.rectified_points.empty() ? nullptr : cam.rectified_points.data();
         dsi::check(dsi_mapper_create(ctx.handle(), &cfg, &h_));
+        ctx_ = ctx.handle();
+        dsi_ = Grid3D::view(dsi_mapper_grid(h_));
+    }
+    // the same with the rectification table made on the device from the calibration numbers, straight into the mapper's
+    // buffer (dsi_mapper_create_with_lens); cam holds the size and fx, fy, cx, cy of P, and no table of its own
+    MapperEMVS(dsi::Context& ctx, const dsi::PinholeCameraModel& cam, const dsi::Lens& lens, const ShapeDSI& dsi_shape,
+               bool inverse_depth = false, int plane_begin = 0, int plane_count = 0)
+    {
+        if (!cam.rectified_points.empty())
+            throw dsi::Error(DSI_ERR_INVALID, "MapperEMVS: a camera with rectified_points and a lens exclude each other");
+        dsi_mapper_config_t cfg{};
+        cfg.plane_begin = plane_begin;
+        cfg.plane_count = plane_count;
+        cfg.sensor_width = cam.width;
+        cfg.sensor_height = cam.height;
+        cfg.K[0] = cam.fx; cfg.K[1] = cam.fy; cfg.K[2] = cam.cx; cfg.K[3] = cam.cy;
+        cfg.dim_x = (int)dsi_shape.dimX_;
+        cfg.dim_y = (int)dsi_shape.dimY_;
+        cfg.dim_z = (int)dsi_shape.dimZ_;
+        cfg.min_depth = dsi_shape.min_depth_;
+        cfg.max_depth = dsi_shape.max_depth_;
+        cfg.fov_deg = dsi_shape.fov_;
+        cfg.inverse_depth = inverse_depth ? 1 : 0;
+        dsi::check(dsi_mapper_create_with_lens(ctx.handle(), &cfg, &lens, &h_));
         ctx_ = ctx.handle();
         dsi_ = Grid3D::view(dsi_mapper_grid(h_));
     }
