@@ -5785,6 +5785,15 @@ hipError_t launch_accumulate(hipStream_t s, float* acc, const float* g, size_t n
 
 hipError_t launch_finalize(hipStream_t s, float* acc, size_t n, int mode, int n_maps)
 {
+    // k_elementwise reads float4: a slab in the middle of a volume whose plane is no multiple of 4 pixels (the
+    // reduce-scattered depth map's own planes) starts 4, 8 or 12 bytes past a 16-byte boundary.  Its first 1..3
+    // elements go through the kernel's scalar tail (n < 4: no float4 access), the rest start aligned.  Per element
+    // the operation is the same: the same bits.  Whole grids are aligned and take the one launch below as before.
+    const size_t head = (size_t)((16u - (unsigned)(reinterpret_cast<uintptr_t>(acc) & 15u)) & 15u) / sizeof(float);
+    if (head && n > head) {
+        if (hipError_t e = launch_finalize(s, acc, head, mode, n_maps)) return e;
+        return launch_finalize(s, acc + head, n - head, mode, n_maps);
+    }
     const dim3 grid(grid_for(n / 4 + 1, 256)), block(256);
     const float* none = nullptr;
     const float fn = (float)n_maps;
