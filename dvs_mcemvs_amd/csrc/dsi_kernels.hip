@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cmath>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #pragma clang fp contract(off)
@@ -2610,8 +2611,8 @@ __device__ __forceinline__ float fuse_op(float a, float g)
 // arg-max to read them straight back.  Here a persistent workgroup owns a contiguous range of
 // (band, plane) pairs; for each pair it votes camera 0's events into the band in LDS, reads the
 // owned rows back as fp32 into REGISTERS (one value per thread and 1024-voxel stretch; <= 20 of them),
-// clears the band, votes camera 1, applies the 2-ary op per voxel (fuse_op, the function k_fuse2_into
-// and k_collapse_max_z_fused use: same bits) and keeps a running (maximum, first index) per pixel in
+// clears the band, votes camera 1, applies the 2-ary op per voxel (fuse_op, the function the value Fuse2
+// hands to k_voxelwise and k_collapse_max_z: same bits) and keeps a running (maximum, first index) per pixel in
 // registers.  When its range leaves a band (and at the end) the running maxima go to one 64-bit key
 // per pixel -- confidence bits << 8 | 255 - plane, the key of the plane-sharded arg-max -- with a
 // global atomic MAX, which is collapseMaxZSlice's first-maximum-wins over the plane ranges of all
@@ -2716,7 +2717,7 @@ __device__ __forceinline__ void fused_consume(acc_t* __restrict__ band, int nx, 
         } else {
             // process1.cpp:126-158: fused = 0; fused += dsi0; fused.<op>TwoGrids(dsi1)
             // process1.cpp:169-191: fused.minTwoGrids / harmonicMeanTwoGrids(dsi2, 3) / maxTwoGrids(dsi2)
-            // (FUSED_LAST4: gm_tree<4> of k_fuse_gm_tree -- t0 = va = sqrt(c0 c1), t1 = sqrt(c2 c3), sqrt(t0 t1))
+            // (FUSED_LAST4: gm_tree<4> of the value GmTree -- t0 = va = sqrt(c0 c1), t1 = sqrt(c2 c3), sqrt(t0 t1))
             const float f = MODE == FUSED_LAST2   ? fuse_op<OP>(0.f + va[kk], v)
                             : MODE == FUSED_LAST3 ? (OP == 2 ? harmonic_mean_n(va[kk], v, 3.f, 2.f) : fuse_op<OP>(va[kk], v))
                             : MODE == FUSED_LAST4 ? fuse_op<3>(va[kk], fuse_op<3>(vpair[kk], v))
@@ -2737,7 +2738,7 @@ __device__ __forceinline__ void fused_consume(acc_t* __restrict__ band, int nx, 
 // up to one pass = 2-4 us apart), while the others still vote.  Same values, same order per cell: same bits.
 // FOUR (round 6): four cameras fused by the balanced tree of the reference's 2-ary geometric mean (DSI_ACC_GM_TREE,
 // cartesian3dgrid.h:150-156 applied pairwise: BASELINE configs[4]) -- camera 0 kept, camera 1 folded into it, camera 2 kept in
-// a second register array, camera 3 closes both pairs and the root; same bits as k_collapse_max_z_gm_tree<4> on the four DSIs.
+// a second register array, camera 3 closes both pairs and the root; same bits as k_collapse_max_z<GmTree<4>, 2> on the four DSIs.
 template <int MAPPING, int CELLS, bool DEFER = false, bool FOUR = false, bool DEAL = true>
 __device__ __forceinline__ void vote_fuse_argmax_body(const FusedCameras& cams, const Geom& g, const BandPlan& bp, int op,
                                                       const uint32_t* __restrict__ splits,
@@ -3410,53 +3411,7 @@ __global__ __launch_bounds__(256) void k_reduce_partials(const acc_t* __restrict
 }
 
 // ------------------------------------------------------------ Grid3D ops ---
-template <int OP>
-__global__ __launch_bounds__(256) void k_fuse2(float* __restrict__ a, const float* __restrict__ g,
-                                               size_t n)
-{
-    const size_t n4 = n / 4;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        float4 va = reinterpret_cast<float4*>(a)[i];
-        const float4 vg = reinterpret_cast<const float4*>(g)[i];
-        va.x = fuse_op<OP>(va.x, vg.x);
-        va.y = fuse_op<OP>(va.y, vg.y);
-        va.z = fuse_op<OP>(va.z, vg.z);
-        va.w = fuse_op<OP>(va.w, vg.w);
-        reinterpret_cast<float4*>(a)[i] = va;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const size_t i = n4 * 4 + threadIdx.x;
-        a[i] = fuse_op<OP>(a[i], g[i]);
-    }
-}
-
-// dst = op(a, g): what "dst.resetGrid(); dst.addTwoGrids(a); dst.<op>TwoGrids(g)"
-// (process1.cpp:126-158) leaves in dst, in one pass (0 + a == a exactly for a >= 0)
-template <int OP>
-__global__ __launch_bounds__(256) void k_fuse2_into(float* __restrict__ dst,
-                                                    const float* __restrict__ a,
-                                                    const float* __restrict__ g, size_t n)
-{
-    const size_t n4 = n / 4;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        const float4 va = reinterpret_cast<const float4*>(a)[i];
-        const float4 vg = reinterpret_cast<const float4*>(g)[i];
-        float4 r;
-        r.x = fuse_op<OP>(0.f + va.x, vg.x);
-        r.y = fuse_op<OP>(0.f + va.y, vg.y);
-        r.z = fuse_op<OP>(0.f + va.z, vg.z);
-        r.w = fuse_op<OP>(0.f + va.w, vg.w);
-        reinterpret_cast<float4*>(dst)[i] = r;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const size_t i = n4 * 4 + threadIdx.x;
-        dst[i] = fuse_op<OP>(0.f + a[i], g[i]);
-    }
-}
-
-// generic element-wise driver for the remaining ops
+// the per-voxel kinds of ew_op
 enum { EW_HM_N = 0, EW_ADD = 1, EW_ADD_INV = 2, EW_FIN_AM = 3, EW_FIN_HM = 4,
        EW_ADD_LOG = 5, EW_ADD_SQ = 6, EW_MIN = 7, EW_MAX = 8, EW_FIN_GM = 9, EW_FIN_RMS = 10 };
 
@@ -3580,32 +3535,146 @@ __device__ __forceinline__ float ew_op(float a, float g, float fn, float fn1, co
     return __builtin_sqrtf(ms);
 }
 
-template <int KIND>
-__global__ __launch_bounds__(256) void k_elementwise(float* __restrict__ a,
-                                                     const float* __restrict__ g, size_t n,
-                                                     float fn, float fn1)
+constexpr int kMaxFuseSources = 8;
+struct FuseSources {
+    const float* p[kMaxFuseSources];
+};
+
+// A VALUE says what one voxel of a result is.  A small struct, handed to the kernels by value, with
+//   kSources    how many source volumes it reads at most (sources(): how many in this launch),
+//   kInPlace    whether it also reads the destination's own voxel: then x[0], the sources follow,
+//   kLogTable   whether it needs det_logf's table in LDS,
+//   operator()  the voxel from the loaded floats x[], through the per-voxel functions above.
+// The kernels ask for K voxels at a time through voxels(), just below: the generic one calls operator() per voxel; a value
+// whose voxels share work has no operator() and its own overload instead (FuseN, right after the generic one).
+// k_voxelwise writes a value's volume; k_collapse_max_z takes its arg-max over the planes without writing it -- the same
+// function of the same floats, hence the same bits.
+template <int SOURCES, bool IN_PLACE = false, bool LOG_TABLE = false>
+struct VoxelValue {
+    static constexpr int kSources = SOURCES;
+    static constexpr bool kInPlace = IN_PLACE, kLogTable = LOG_TABLE;
+    __device__ int sources() const { return SOURCES; }
+};
+
+// det_logf's table for the values that ask for it (whole block; ends with a barrier), no LDS and no barrier for the others
+template <bool NEEDED>
+__device__ __forceinline__ const double2* log_table()
 {
-    constexpr bool has_g = (KIND == EW_HM_N || KIND == EW_ADD || KIND == EW_ADD_INV ||
-                            KIND == EW_ADD_LOG || KIND == EW_ADD_SQ || KIND == EW_MIN || KIND == EW_MAX);
-    __shared__ double2 log_tab[KIND == EW_ADD_LOG ? kLogTabSize : 1];
-    if (KIND == EW_ADD_LOG) det_log_table_fill(log_tab);
+    if constexpr (NEEDED) {
+        __shared__ double2 tab[kLogTabSize];
+        det_log_table_fill(tab);
+        return tab;
+    } else {
+        return nullptr;
+    }
+}
+
+template <int K, int L, class V>
+__device__ __forceinline__ void voxels(const V& v, float* r, const float (*x)[L], const double2* log_tab)
+{
+#pragma unroll
+    for (int k = 0; k < K; ++k) r[k] = v(x[k], log_tab);
+}
+
+// The accumulate modes DSI_ACC_SUM, _INV_SUM, _LOG_SUM, _SQ_SUM, _MIN, _MAX (0..5): the kind that accumulates a map, the
+// kind that finalizes the accumulator (-1: none) and the identity element the accumulator starts from.
+template <int MODE>
+struct AccMode {
+    static_assert(MODE >= 0 && MODE <= 5, "an accumulate mode");
+    static constexpr int kAcc = MODE == 0 ? EW_ADD : MODE == 1 ? EW_ADD_INV : MODE == 2 ? EW_ADD_LOG : MODE == 3 ? EW_ADD_SQ : MODE == 4 ? EW_MIN : EW_MAX;
+    static constexpr int kFin = MODE == 0 ? EW_FIN_AM : MODE == 1 ? EW_FIN_HM : MODE == 2 ? EW_FIN_GM : MODE == 3 ? EW_FIN_RMS : -1;
+    static constexpr float kIdentity = MODE == 4 ? __builtin_inff() : MODE == 5 ? -__builtin_inff() : 0.f;
+};
+
+// n-ary fusion in ONE pass: dst = finalize(accumulate(... accumulate(identity, src[0]) ..., src[n-1]))
+// with exactly the operations, in exactly the order, of dsi_grid_accumulate_begin / n x
+// dsi_grid_accumulate / dsi_grid_finalize (so the bits are the same), reading every source once:
+// (n + 1) * 4 B per voxel instead of (3 n + 2) * 4 B.
+template <int MODE>
+struct FuseN : VoxelValue<kMaxFuseSources, false, AccMode<MODE>::kAcc == EW_ADD_LOG> {
+    int n_src;
+    float fn;
+    __device__ int sources() const { return n_src; }
+};
+
+// FuseN's voxels(): source by source for the K voxels together, one test of n_src per source
+template <int K, int MODE>
+__device__ __forceinline__ void voxels(const FuseN<MODE>& v, float* r, const float (*x)[kMaxFuseSources], const double2* log_tab)
+{
+    using M = AccMode<MODE>;
+#pragma unroll
+    for (int k = 0; k < K; ++k) r[k] = M::kIdentity;
+#pragma unroll
+    for (int c = 0; c < kMaxFuseSources; ++c)
+        if (c < v.n_src) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) r[k] = ew_op<M::kAcc>(r[k], x[k][c], 0.f, 0.f, log_tab);
+        }
+    if constexpr (M::kFin >= 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) r[k] = ew_op<M::kFin>(r[k], 0.f, v.fn, 0.f);
+    }
+}
+
+// 128-bit grid-stride body, scalar tail of n & 3 voxels in block 0; launched on grid_for(n / 4 + 1, 256) blocks
+// (launch_voxelwise).  An in-place value's voxel is loaded and then stored by the same thread.
+template <class V>
+__global__ __launch_bounds__(256) void k_voxelwise(float* dst, FuseSources src, size_t n, V v)
+{
+    constexpr int kOwn = V::kInPlace ? 1 : 0, kLoaded = kOwn + V::kSources;
+    const double2* log_tab = log_table<V::kLogTable>();
+    const int n_src = v.sources();
     const size_t n4 = n / 4;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        float4 va = reinterpret_cast<float4*>(a)[i];
-        float4 vg = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (has_g) vg = reinterpret_cast<const float4*>(g)[i];
-        va.x = ew_op<KIND>(va.x, vg.x, fn, fn1, log_tab);
-        va.y = ew_op<KIND>(va.y, vg.y, fn, fn1, log_tab);
-        va.z = ew_op<KIND>(va.z, vg.z, fn, fn1, log_tab);
-        va.w = ew_op<KIND>(va.w, vg.w, fn, fn1, log_tab);
-        reinterpret_cast<float4*>(a)[i] = va;
+        float x[4][kLoaded], r[4];  // all loads of a voxel group in flight before the arithmetic
+        const auto put = [&](int c, const float4 q) {
+            x[0][c] = q.x;
+            x[1][c] = q.y;
+            x[2][c] = q.z;
+            x[3][c] = q.w;
+        };
+        if (V::kInPlace) put(0, reinterpret_cast<const float4*>(dst)[i]);
+#pragma unroll
+        for (int c = 0; c < V::kSources; ++c)
+            if (c < n_src) put(kOwn + c, reinterpret_cast<const float4*>(src.p[c])[i]);
+        voxels<4>(v, r, x, log_tab);
+        reinterpret_cast<float4*>(dst)[i] = make_float4(r[0], r[1], r[2], r[3]);
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const size_t i = n4 * 4 + threadIdx.x;
-        a[i] = ew_op<KIND>(a[i], has_g ? g[i] : 0.f, fn, fn1, log_tab);
+        float x[1][kLoaded], r[1];
+        if (V::kInPlace) x[0][0] = dst[i];
+#pragma unroll
+        for (int c = 0; c < V::kSources; ++c)
+            if (c < n_src) x[0][kOwn + c] = src.p[c][i];
+        voxels<1>(v, r, x, log_tab);
+        dst[i] = r[0];
     }
 }
+
+// 2-ary camera fusion.  In place: dst = op(dst, g).  Else dst = op(0 + a, g): what "dst.resetGrid(); dst.addTwoGrids(a);
+// dst.<op>TwoGrids(g)" (process1.cpp:126-158) leaves in dst, in one pass (0 + a == a exactly for a >= 0)
+template <int OP, bool IN_PLACE>
+struct Fuse2 : VoxelValue<IN_PLACE ? 1 : 2, IN_PLACE> {
+    __device__ float operator()(const float* x, const double2*) const { return fuse_op<OP>(IN_PLACE ? x[0] : 0.f + x[0], x[1]); }
+};
+
+struct HarmonicMeanN : VoxelValue<1, true> {  // harmonicMeanTwoGrids(grid2, n): fn = n, fn1 = n - 1
+    float fn, fn1;
+    __device__ float operator()(const float* x, const double2*) const { return harmonic_mean_n(x[0], x[1], fn, fn1); }
+};
+
+template <int KIND>
+struct Accumulate : VoxelValue<1, true, KIND == EW_ADD_LOG> {
+    __device__ float operator()(const float* x, const double2* log_tab) const { return ew_op<KIND>(x[0], x[1], 0.f, 0.f, log_tab); }
+};
+
+template <int KIND>
+struct Finalize : VoxelValue<0, true> {
+    float fn;
+    __device__ float operator()(const float* x, const double2*) const { return ew_op<KIND>(x[0], 0.f, fn, 0.f); }
+};
 
 // (3e) FUSED Alg. 2: process_2 / process_5 of one window (process2.cpp:98-289) without a DSI.
 //
@@ -3613,10 +3682,10 @@ __global__ __launch_bounds__(256) void k_elementwise(float* __restrict__ a,
 // ascending, camera 0 before camera 1 -- with the zeroed-band LDS stream and the read-back of that kernel.  Per cell a
 // thread keeps camera 0's value c0_k of the running sub-interval and the temporal accumulator of the fused volume A_tc
 // (camera_time: also A_l, A_r of the two cameras) in registers across the pair's phases:
-//   s_k = fuse_op<sf>(0 + c0_k, c1_k)                                         (process2.cpp:159-189, k_fuse2)
+//   s_k = fuse_op<sf>(0 + c0_k, c1_k)                                         (process2.cpp:159-189, Fuse2)
 //   tf 2: A = A + 1 / (0.01 + x), then N / A; tf 4: A = A + x, then A / N      (ew_op EW_ADD_INV / EW_ADD, EW_FIN_*)
 //   time_camera = fin(A_tc); camera_time = fuse_op<sf'>(0 + fin(A_l), fin(A_r)) (process2.cpp:266-289, 3 <-> 4 swapped)
-// -- the functions k_fuse2, k_elementwise and dsi_grid_finalize apply to the grids, in the same order per cell: the
+// -- the functions k_voxelwise<Fuse2 / Accumulate / Finalize> apply to the grids, in the same order per cell: the
 // same bits.  After the last phase each output's running (maximum, first index) is updated; keys leave as in
 // k_vote_fuse_argmax (atomicMax of conf bits << 8 | 255 - plane, k_unpack_argmax).
 __host__ __device__ constexpr int alg2_converse_op(int sf) { return sf == 3 ? 4 : (sf == 4 ? 3 : sf); }
@@ -3799,54 +3868,6 @@ __global__ __launch_bounds__(1024) void k_vote_fuse_argmax_alg2(Alg2Batches bt, 
     if constexpr (CT) emit_one(keys_ct, fb_ct);
 }
 
-// n-ary fusion in ONE pass: dst = finalize(accumulate(... accumulate(identity, src[0]) ..., src[n-1]))
-// with exactly the operations, in exactly the order, of dsi_grid_accumulate_begin / n x
-// dsi_grid_accumulate / dsi_grid_finalize (so the bits are the same), reading every source once:
-// (n + 1) * 4 B per voxel instead of (3 n + 2) * 4 B.
-constexpr int kMaxFuseSources = 8;
-struct FuseSources {
-    const float* p[kMaxFuseSources];
-};
-
-template <int ACC, int FIN>
-__global__ __launch_bounds__(256) void k_fuse_n(float* __restrict__ dst, FuseSources src, int n_src,
-                                                size_t n, float identity, float fn)
-{
-    __shared__ double2 log_tab[ACC == EW_ADD_LOG ? kLogTabSize : 1];
-    if (ACC == EW_ADD_LOG) det_log_table_fill(log_tab);
-    const size_t n4 = n / 4;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        float4 acc = make_float4(identity, identity, identity, identity);
-        float4 v[kMaxFuseSources];  // all loads of a voxel group in flight before the arithmetic
-#pragma unroll
-        for (int c = 0; c < kMaxFuseSources; ++c)
-            if (c < n_src) v[c] = reinterpret_cast<const float4*>(src.p[c])[i];
-#pragma unroll
-        for (int c = 0; c < kMaxFuseSources; ++c)
-            if (c < n_src) {
-                acc.x = ew_op<ACC>(acc.x, v[c].x, 0.f, 0.f, log_tab);
-                acc.y = ew_op<ACC>(acc.y, v[c].y, 0.f, 0.f, log_tab);
-                acc.z = ew_op<ACC>(acc.z, v[c].z, 0.f, 0.f, log_tab);
-                acc.w = ew_op<ACC>(acc.w, v[c].w, 0.f, 0.f, log_tab);
-            }
-        if (FIN >= 0) {
-            acc.x = ew_op<(FIN >= 0 ? FIN : 0)>(acc.x, 0.f, fn, 0.f);
-            acc.y = ew_op<(FIN >= 0 ? FIN : 0)>(acc.y, 0.f, fn, 0.f);
-            acc.z = ew_op<(FIN >= 0 ? FIN : 0)>(acc.z, 0.f, fn, 0.f);
-            acc.w = ew_op<(FIN >= 0 ? FIN : 0)>(acc.w, 0.f, fn, 0.f);
-        }
-        reinterpret_cast<float4*>(dst)[i] = acc;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const size_t i = n4 * 4 + threadIdx.x;
-        float acc = identity;
-        for (int c = 0; c < n_src; ++c) acc = ew_op<ACC>(acc, src.p[c][i], 0.f, 0.f, log_tab);
-        if (FIN >= 0) acc = ew_op<(FIN >= 0 ? FIN : 0)>(acc, 0.f, fn, 0.f);
-        dst[i] = acc;
-    }
-}
-
 // ---- n-ary geometric mean as the balanced TREE of the reference's own 2-ary op (DSI_ACC_GM_TREE):
 //   n = 2: sqrt(a b)                     = Grid3D::geometricMeanTwoGrids, cartesian3dgrid.h:150-156, bit for bit
 //   n = 4: sqrt(sqrt(a b) sqrt(c d))     n = 8: one level more
@@ -3867,196 +3888,60 @@ __device__ __forceinline__ float gm_tree(const float* v)
 }
 
 template <int N>
-__global__ __launch_bounds__(256) void k_fuse_gm_tree(float* __restrict__ dst, FuseSources src, size_t n)
-{
-    const size_t n4 = n / 4;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        float4 v[N];
-#pragma unroll
-        for (int c = 0; c < N; ++c) v[c] = reinterpret_cast<const float4*>(src.p[c])[i];
-        float x[N], y[N], z[N], w[N];
-#pragma unroll
-        for (int c = 0; c < N; ++c) {
-            x[c] = v[c].x;
-            y[c] = v[c].y;
-            z[c] = v[c].z;
-            w[c] = v[c].w;
-        }
-        reinterpret_cast<float4*>(dst)[i] = make_float4(gm_tree<N>(x), gm_tree<N>(y), gm_tree<N>(z), gm_tree<N>(w));
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const size_t i = n4 * 4 + threadIdx.x;
-        float x[N];
-#pragma unroll
-        for (int c = 0; c < N; ++c) x[c] = src.p[c][i];
-        dst[i] = gm_tree<N>(x);
-    }
-}
+struct GmTree : VoxelValue<N> {
+    __device__ float operator()(const float* x, const double2*) const { return gm_tree<N>(x); }
+};
 
-// collapseMaxZSlice of the tree geometric mean without materialising it (same bits as k_fuse_gm_tree + k_collapse_max_z)
-template <int N>
-__global__ __launch_bounds__(256) void k_collapse_max_z_gm_tree(FuseSources src, int npix, int nz,
-                                                                float* __restrict__ conf, uint8_t* __restrict__ idx,
-                                                                const float* __restrict__ planes, float* __restrict__ depth)
-{
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= npix) return;
-    float best = 0.f;
-    int best_k = 0;
-    for (int k = 0; k < nz; k += 2) {
-        float v[2][N];  // two planes' loads in flight before the arithmetic
-        const int k1 = min(k + 1, nz - 1);
-#pragma unroll
-        for (int c = 0; c < N; ++c) {
-            v[0][c] = src.p[c][(size_t)k * npix + p];
-            v[1][c] = src.p[c][(size_t)k1 * npix + p];
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            if (k + u >= nz) break;
-            const float f = gm_tree<N>(v[u]);
-            if (k + u == 0 || best < f) {  // std::max_element: the first maximum wins
-                best = f;
-                best_k = k + u;
-            }
-        }
-    }
-    conf[p] = best;
-    idx[p] = (uint8_t)best_k;
-    if (depth) depth[p] = planes[best_k];
-}
+struct Identity : VoxelValue<1> {  // the volume itself
+    __device__ float operator()(const float* x, const double2*) const { return x[0]; }
+};
 
-// cartesian3dgrid.cpp:115-137: thread = pixel, planes walked in order, strict '<'
-// keeps the first maximum (std::max_element).  Lanes of a wave read consecutive x
-// of one plane row: coalesced 256-B segments.
-__global__ __launch_bounds__(256) void k_collapse_max_z(const float* __restrict__ dsi, int npix,
-                                                        int nz, float* __restrict__ conf,
-                                                        uint8_t* __restrict__ idx,
-                                                        const float* __restrict__ planes,
+// cartesian3dgrid.cpp:115-137 on a value's volume without materialising it: thread = pixel, planes walked in order from
+// plane 0's value, strict '<' keeps the first maximum (std::max_element); U planes' loads in flight before the
+// arithmetic (a last group of fewer than U planes reads the last plane again in their place and does not take it).
+// Lanes of a wave read consecutive x of one plane row: coalesced 256-B segments.
+// Identity: collapseMaxZSlice of a grid.  Fuse2<OP, false>: of "fused.resetGrid(); fused.addTwoGrids(a);
+// fused.<op>TwoGrids(b)" (process1.cpp:126-158 + mapper_emvs_stereo.cpp:368) with 8 instead of 12 + 4 bytes per voxel of
+// traffic, for streams of windows that only need the depth map (main.cpp:177).  FuseN, GmTree: of the n-ary fusion of up
+// to 8 volumes, n * 4 B per voxel read, nothing written but the maps.
+template <class V, int U>
+__global__ __launch_bounds__(256) void k_collapse_max_z(FuseSources src, int npix, int nz, V v, float* __restrict__ conf,
+                                                        uint8_t* __restrict__ idx, const float* __restrict__ planes,
                                                         float* __restrict__ depth)
 {
+    static_assert(!V::kInPlace, "there is no destination volume");
+    const double2* log_tab = log_table<V::kLogTable>();
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= npix) return;
-    const float* col = dsi + p;
-    float best = col[0];
-    int best_k = 0;
-    int k = 1;
-    for (; k + 8 <= nz; k += 8) {
-        float v[8];
+    const int n_src = v.sources();
+    const auto load = [&](float (*x)[V::kSources], int k) {
+        size_t at[U];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = col[(size_t)(k + u) * npix];
+        for (int u = 0; u < U; ++u) at[u] = (size_t)min(k + u, nz - 1) * npix + p;
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
-            if (best < v[u]) {
-                best = v[u];
-                best_k = k + u;
+        for (int c = 0; c < V::kSources; ++c)
+            if (c < n_src) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) x[u][c] = src.p[c][at[u]];
             }
-    }
-    for (; k < nz; ++k) {
-        const float v = col[(size_t)k * npix];
-        if (best < v) {
-            best = v;
-            best_k = k;
+    };
+    float best = 0.f;
+    int best_k = 0;
+    for (int k = 0; k < nz; k += U) {
+        float x[U][V::kSources], f[U];
+        load(x, k);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            voxels<1>(v, &f[u], &x[u], log_tab);
+            // plane 0 starts the maximum; a select, no branch: the loads stay ahead of the arithmetic
+            const bool better = (k + u < nz) & ((k + u == 0) | (best < f[u]));
+            best = better ? f[u] : best;
+            best_k = better ? k + u : best_k;
         }
     }
     conf[p] = best;
     idx[p] = (uint8_t)best_k;
     if (depth) depth[p] = planes[best_k];  // mapper_emvs_stereo.cpp:302-313
-}
-
-// collapseMaxZSlice of op(a, b) without materialising the fused volume: what
-// "fused.resetGrid(); fused.addTwoGrids(a); fused.<op>TwoGrids(b); fused.collapseMaxZSlice()"
-// (process1.cpp:126-158 + mapper_emvs_stereo.cpp:368) yields, bit for bit (the fused value is
-// computed by the same fuse_op as k_fuse2_into), with 8 instead of 12 + 4 bytes per voxel of
-// traffic.  For streams of windows that only need the depth map (main.cpp:177).
-template <int OP>
-__global__ __launch_bounds__(256) void k_collapse_max_z_fused(const float* __restrict__ a,
-                                                              const float* __restrict__ b, int npix,
-                                                              int nz, float* __restrict__ conf,
-                                                              uint8_t* __restrict__ idx,
-                                                              const float* __restrict__ planes,
-                                                              float* __restrict__ depth)
-{
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= npix) return;
-    const float* ca = a + p;
-    const float* cb = b + p;
-    float best = fuse_op<OP>(0.f + ca[0], cb[0]);
-    int best_k = 0;
-    int k = 1;
-    for (; k + 4 <= nz; k += 4) {
-        float va[4], vb[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            va[u] = ca[(size_t)(k + u) * npix];
-            vb[u] = cb[(size_t)(k + u) * npix];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float v = fuse_op<OP>(0.f + va[u], vb[u]);
-            if (best < v) {
-                best = v;
-                best_k = k + u;
-            }
-        }
-    }
-    for (; k < nz; ++k) {
-        const float v = fuse_op<OP>(0.f + ca[(size_t)k * npix], cb[(size_t)k * npix]);
-        if (best < v) {
-            best = v;
-            best_k = k;
-        }
-    }
-    conf[p] = best;
-    idx[p] = (uint8_t)best_k;
-    if (depth) depth[p] = planes[best_k];
-}
-
-// collapseMaxZSlice of the n-ary fusion of up to 8 volumes (dsi_grid_fuse_n's begin / accumulate x n /
-// finalize per voxel, the same operations in the same order, hence the same bits) without
-// materialising the fused volume: n * 4 B per voxel read, nothing written but the maps.
-template <int ACC, int FIN>
-__global__ __launch_bounds__(256) void k_collapse_max_z_fused_n(FuseSources src, int n_src, int npix, int nz,
-                                                                float identity, float fn,
-                                                                float* __restrict__ conf,
-                                                                uint8_t* __restrict__ idx,
-                                                                const float* __restrict__ planes,
-                                                                float* __restrict__ depth)
-{
-    __shared__ double2 log_tab[ACC == EW_ADD_LOG ? kLogTabSize : 1];
-    if (ACC == EW_ADD_LOG) det_log_table_fill(log_tab);
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= npix) return;
-    float best = 0.f;
-    int best_k = 0;
-    for (int k = 0; k < nz; k += 2) {
-        // two planes' loads in flight before the arithmetic
-        float v[2][kMaxFuseSources];
-        const int k1 = min(k + 1, nz - 1);
-#pragma unroll
-        for (int c = 0; c < kMaxFuseSources; ++c)
-            if (c < n_src) {
-                v[0][c] = src.p[c][(size_t)k * npix + p];
-                v[1][c] = src.p[c][(size_t)k1 * npix + p];
-            }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            if (k + u >= nz) break;
-            float acc = identity;
-#pragma unroll
-            for (int c = 0; c < kMaxFuseSources; ++c)
-                if (c < n_src) acc = ew_op<ACC>(acc, v[u][c], 0.f, 0.f, log_tab);
-            if (FIN >= 0) acc = ew_op<(FIN >= 0 ? FIN : 0)>(acc, 0.f, fn, 0.f);
-            if (k + u == 0 || best < acc) {  // std::max_element: the first maximum wins
-                best = acc;
-                best_k = k + u;
-            }
-        }
-    }
-    conf[p] = best;
-    idx[p] = (uint8_t)best_k;
-    if (depth) depth[p] = planes[best_k];
 }
 
 // cartesian3dgrid.cpp:164-174: sum of squares in double (order differs from the
@@ -4238,7 +4123,7 @@ template <int OP>
 __device__ __forceinline__ float tie_value(const float* __restrict__ a, const float* __restrict__ b, size_t i)
 {
     if (OP == 0) return a[i];
-    return fuse_op<OP>(0.f + a[i], b[i]);  // as k_collapse_max_z_fused / k_fuse2_into compute the fused voxel
+    return fuse_op<OP>(0.f + a[i], b[i]);  // as the value Fuse2<OP, false> computes the fused voxel
 }
 
 // (1) thread = pixel, ONE streaming sweep over the column(s): the largest and second largest (fused) value; a column has
@@ -5143,7 +5028,7 @@ __global__ __launch_bounds__(256) void k_tie_add_runs(const float* __restrict__ 
 }
 #undef DSI_TIE_ADD16
 
-// thread = near-tie column: camera fusion of the reference-order values (fuse_op, what k_fuse2_into computes), first
+// thread = near-tie column: camera fusion of the reference-order values (fuse_op, what Fuse2<OP, false> computes), first
 // maximum over the column's contending planes (std::max_element, cartesian3dgrid.cpp:132-134), patch of the depth map
 // (index -> depth: mapper_emvs_stereo.cpp:302-313).  cols[j] = (first entry in vox / exact, pixel, contenders); a column's
 // contenders are contiguous there, planes ascending.  stats[2] += pixels whose plane changed
@@ -5212,6 +5097,53 @@ int grid_for(size_t work_items, int block, int max_blocks = 256 * 8)
     if (b < 1) b = 1;
     if (b > (size_t)max_blocks) b = max_blocks;
     return (int)b;
+}
+
+// f(std::integral_constant<int, v>()) for a runtime v in [LO, HI]: the one op / mode ladder of the launchers
+template <int LO, int HI, class F>
+hipError_t dispatch_int(int v, const F& f)
+{
+    if constexpr (LO <= HI) {
+        if (v == LO) return f(std::integral_constant<int, LO>());
+        return dispatch_int<LO + 1, HI>(v, f);
+    } else {
+        return hipErrorInvalidValue;
+    }
+}
+
+template <class V>
+hipError_t launch_voxelwise(hipStream_t s, float* dst, const FuseSources& src, size_t n, V v)
+{
+    hipLaunchKernelGGL(k_voxelwise<V>, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, s, dst, src, n, v);
+    return hipExtGetLastError();  // status of THIS launch (hipGetLastError is sticky across calls)
+}
+
+template <int U, class V>
+hipError_t launch_collapse(hipStream_t s, const FuseSources& src, int nx, int ny, int nz, V v, float* conf, uint8_t* idx,
+                           const float* planes, float* depth)
+{
+    const int npix = nx * ny;
+    hipLaunchKernelGGL((k_collapse_max_z<V, U>), dim3((npix + 255) / 256), dim3(256), 0, s, src, npix, nz, v, conf, idx, planes, depth);
+    return hipExtGetLastError();  // status of THIS launch (hipGetLastError is sticky across calls)
+}
+
+FuseSources fuse_sources(const float* const* srcs, int n_src)
+{
+    FuseSources fs{};
+    for (int c = 0; c < n_src; ++c) fs.p[c] = srcs[c];
+    return fs;
+}
+
+// f(the value of an n-ary fusion of n_src volumes): modes 0..5 accumulate and finalize (AccMode), mode 6 is the tree of
+// 2-ary geometric means, n = 2, 4, 8
+template <class F>
+hipError_t dispatch_fuse_n(int mode, int n_src, const F& f)
+{
+    if (mode != 6) return dispatch_int<0, 5>(mode, [&](auto MODE) { return f(FuseN<MODE>{{}, n_src, (float)n_src}); });
+    if (n_src == 2) return f(GmTree<2>());
+    if (n_src == 4) return f(GmTree<4>());
+    if (n_src == 8) return f(GmTree<8>());
+    return hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -5733,59 +5665,29 @@ hipError_t launch_reduce_partials(hipStream_t s, const unsigned long long* parti
 
 hipError_t launch_fuse2(hipStream_t s, float* a, const float* g, size_t n, int op)
 {
-    const dim3 grid(grid_for(n / 4 + 1, 256)), block(256);
-    switch (op) {
-    case 1: hipLaunchKernelGGL(k_fuse2<1>, grid, block, 0, s, a, g, n); break;
-    case 2: hipLaunchKernelGGL(k_fuse2<2>, grid, block, 0, s, a, g, n); break;
-    case 3: hipLaunchKernelGGL(k_fuse2<3>, grid, block, 0, s, a, g, n); break;
-    case 4: hipLaunchKernelGGL(k_fuse2<4>, grid, block, 0, s, a, g, n); break;
-    case 5: hipLaunchKernelGGL(k_fuse2<5>, grid, block, 0, s, a, g, n); break;
-    case 6: hipLaunchKernelGGL(k_fuse2<6>, grid, block, 0, s, a, g, n); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipExtGetLastError();  // status of THIS launch (hipGetLastError is sticky across calls)
+    return dispatch_int<1, 6>(op, [&](auto OP) { return launch_voxelwise(s, a, FuseSources{{g}}, n, Fuse2<OP, true>()); });
 }
 
 hipError_t launch_fuse2_into(hipStream_t s, float* dst, const float* a, const float* g, size_t n, int op)
 {
-    const dim3 grid(grid_for(n / 4 + 1, 256)), block(256);
-    switch (op) {
-    case 1: hipLaunchKernelGGL(k_fuse2_into<1>, grid, block, 0, s, dst, a, g, n); break;
-    case 2: hipLaunchKernelGGL(k_fuse2_into<2>, grid, block, 0, s, dst, a, g, n); break;
-    case 3: hipLaunchKernelGGL(k_fuse2_into<3>, grid, block, 0, s, dst, a, g, n); break;
-    case 4: hipLaunchKernelGGL(k_fuse2_into<4>, grid, block, 0, s, dst, a, g, n); break;
-    case 5: hipLaunchKernelGGL(k_fuse2_into<5>, grid, block, 0, s, dst, a, g, n); break;
-    case 6: hipLaunchKernelGGL(k_fuse2_into<6>, grid, block, 0, s, dst, a, g, n); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipExtGetLastError();  // status of THIS launch (hipGetLastError is sticky across calls)
+    return dispatch_int<1, 6>(op, [&](auto OP) { return launch_voxelwise(s, dst, FuseSources{{a, g}}, n, Fuse2<OP, false>()); });
 }
 
 hipError_t launch_fuse_hm_n(hipStream_t s, float* a, const float* g, size_t n, int n_maps)
 {
-    hipLaunchKernelGGL(k_elementwise<EW_HM_N>, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, s, a,
-                       g, n, (float)n_maps, (float)(n_maps - 1));
-    return hipExtGetLastError();  // status of THIS launch (hipGetLastError is sticky across calls)
+    return launch_voxelwise(s, a, FuseSources{{g}}, n, HarmonicMeanN{{}, (float)n_maps, (float)(n_maps - 1)});
 }
 
 hipError_t launch_accumulate(hipStream_t s, float* acc, const float* g, size_t n, int mode)
 {
-    const dim3 grid(grid_for(n / 4 + 1, 256)), block(256);
-    switch (mode) {
-    case 0: hipLaunchKernelGGL(k_elementwise<EW_ADD>, grid, block, 0, s, acc, g, n, 0.f, 0.f); break;
-    case 1: hipLaunchKernelGGL(k_elementwise<EW_ADD_INV>, grid, block, 0, s, acc, g, n, 0.f, 0.f); break;
-    case 2: hipLaunchKernelGGL(k_elementwise<EW_ADD_LOG>, grid, block, 0, s, acc, g, n, 0.f, 0.f); break;
-    case 3: hipLaunchKernelGGL(k_elementwise<EW_ADD_SQ>, grid, block, 0, s, acc, g, n, 0.f, 0.f); break;
-    case 4: hipLaunchKernelGGL(k_elementwise<EW_MIN>, grid, block, 0, s, acc, g, n, 0.f, 0.f); break;
-    case 5: hipLaunchKernelGGL(k_elementwise<EW_MAX>, grid, block, 0, s, acc, g, n, 0.f, 0.f); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipExtGetLastError();  // status of THIS launch (hipGetLastError is sticky across calls)
+    return dispatch_int<0, 5>(mode, [&](auto MODE) {
+        return launch_voxelwise(s, acc, FuseSources{{g}}, n, Accumulate<AccMode<MODE>::kAcc>());
+    });
 }
 
 hipError_t launch_finalize(hipStream_t s, float* acc, size_t n, int mode, int n_maps)
 {
-    // k_elementwise reads float4: a slab in the middle of a volume whose plane is no multiple of 4 pixels (the
+    // k_voxelwise reads float4: a slab in the middle of a volume whose plane is no multiple of 4 pixels (the
     // reduce-scattered depth map's own planes) starts 4, 8 or 12 bytes past a 16-byte boundary.  Its first 1..3
     // elements go through the kernel's scalar tail (n < 4: no float4 access), the rest start aligned.  Per element
     // the operation is the same: the same bits.  Whole grids are aligned and take the one launch below as before.
@@ -5794,19 +5696,10 @@ hipError_t launch_finalize(hipStream_t s, float* acc, size_t n, int mode, int n_
         if (hipError_t e = launch_finalize(s, acc, head, mode, n_maps)) return e;
         return launch_finalize(s, acc + head, n - head, mode, n_maps);
     }
-    const dim3 grid(grid_for(n / 4 + 1, 256)), block(256);
-    const float* none = nullptr;
-    const float fn = (float)n_maps;
-    switch (mode) {
-    case 0: hipLaunchKernelGGL(k_elementwise<EW_FIN_AM>, grid, block, 0, s, acc, none, n, fn, 0.f); break;
-    case 1: hipLaunchKernelGGL(k_elementwise<EW_FIN_HM>, grid, block, 0, s, acc, none, n, fn, 0.f); break;
-    case 2: hipLaunchKernelGGL(k_elementwise<EW_FIN_GM>, grid, block, 0, s, acc, none, n, fn, 0.f); break;
-    case 3: hipLaunchKernelGGL(k_elementwise<EW_FIN_RMS>, grid, block, 0, s, acc, none, n, fn, 0.f); break;
-    case 4:
-    case 5: break;  // min / max need no finalisation
-    default: return hipErrorInvalidValue;
-    }
-    return hipExtGetLastError();  // status of THIS launch (hipGetLastError is sticky across calls)
+    if (mode == 4 || mode == 5) return hipExtGetLastError();  // min / max need no finalisation
+    return dispatch_int<0, 3>(mode, [&](auto MODE) {
+        return launch_voxelwise(s, acc, FuseSources{}, n, Finalize<AccMode<MODE>::kFin>{{}, (float)n_maps});
+    });
 }
 
 // plane-sharded arg-max: (confidence, local index) -> one 64-bit key per pixel whose MAX over the
@@ -5862,27 +5755,8 @@ hipError_t launch_unpack_argmax(hipStream_t s, unsigned long long* keys, int n, 
 hipError_t launch_fuse_n(hipStream_t s, float* dst, const float* const* srcs, int n_src, size_t n, int mode)
 {
     if (n_src < 1 || n_src > kMaxFuseSources) return hipErrorInvalidValue;
-    FuseSources fs{};
-    for (int c = 0; c < n_src; ++c) fs.p[c] = srcs[c];
-    const dim3 grid(grid_for(n / 4 + 1, 256)), block(256);
-    const float fn = (float)n_src;
-    const float inf = __builtin_inff();
-    switch (mode) {
-    case 0: hipLaunchKernelGGL((k_fuse_n<EW_ADD, EW_FIN_AM>), grid, block, 0, s, dst, fs, n_src, n, 0.f, fn); break;
-    case 1: hipLaunchKernelGGL((k_fuse_n<EW_ADD_INV, EW_FIN_HM>), grid, block, 0, s, dst, fs, n_src, n, 0.f, fn); break;
-    case 2: hipLaunchKernelGGL((k_fuse_n<EW_ADD_LOG, EW_FIN_GM>), grid, block, 0, s, dst, fs, n_src, n, 0.f, fn); break;
-    case 3: hipLaunchKernelGGL((k_fuse_n<EW_ADD_SQ, EW_FIN_RMS>), grid, block, 0, s, dst, fs, n_src, n, 0.f, fn); break;
-    case 4: hipLaunchKernelGGL((k_fuse_n<EW_MIN, -1>), grid, block, 0, s, dst, fs, n_src, n, inf, fn); break;
-    case 5: hipLaunchKernelGGL((k_fuse_n<EW_MAX, -1>), grid, block, 0, s, dst, fs, n_src, n, -inf, fn); break;
-    case 6:  // the tree of 2-ary geometric means: n = 2, 4, 8
-        if (n_src == 2) hipLaunchKernelGGL(k_fuse_gm_tree<2>, grid, block, 0, s, dst, fs, n);
-        else if (n_src == 4) hipLaunchKernelGGL(k_fuse_gm_tree<4>, grid, block, 0, s, dst, fs, n);
-        else if (n_src == 8) hipLaunchKernelGGL(k_fuse_gm_tree<8>, grid, block, 0, s, dst, fs, n);
-        else return hipErrorInvalidValue;
-        break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipExtGetLastError();
+    const FuseSources fs = fuse_sources(srcs, n_src);
+    return dispatch_fuse_n(mode, n_src, [&](auto v) { return launch_voxelwise(s, dst, fs, n, v); });
 }
 
 // identity element of an accumulate mode: 0 for the sums, +inf for min, -inf for max
@@ -5933,55 +5807,23 @@ hipError_t launch_fill(hipStream_t s, float* a, size_t n, float v)
 hipError_t launch_collapse_max_z(hipStream_t s, const float* dsi, int nx, int ny, int nz,
                                  float* conf, uint8_t* idx, const float* planes, float* depth)
 {
-    const int npix = nx * ny;
-    hipLaunchKernelGGL(k_collapse_max_z, dim3((npix + 255) / 256), dim3(256), 0, s, dsi, npix, nz,
-                       conf, idx, planes, depth);
-    return hipExtGetLastError();  // status of THIS launch (hipGetLastError is sticky across calls)
+    return launch_collapse<8>(s, FuseSources{{dsi}}, nx, ny, nz, Identity(), conf, idx, planes, depth);
 }
 
 hipError_t launch_collapse_max_z_fused(hipStream_t s, const float* a, const float* b, int nx, int ny, int nz, int op,
                                        float* conf, uint8_t* idx, const float* planes, float* depth)
 {
-    const int npix = nx * ny;
-    const dim3 grid((npix + 255) / 256), block(256);
-    switch (op) {
-    case 1: hipLaunchKernelGGL(k_collapse_max_z_fused<1>, grid, block, 0, s, a, b, npix, nz, conf, idx, planes, depth); break;
-    case 2: hipLaunchKernelGGL(k_collapse_max_z_fused<2>, grid, block, 0, s, a, b, npix, nz, conf, idx, planes, depth); break;
-    case 3: hipLaunchKernelGGL(k_collapse_max_z_fused<3>, grid, block, 0, s, a, b, npix, nz, conf, idx, planes, depth); break;
-    case 4: hipLaunchKernelGGL(k_collapse_max_z_fused<4>, grid, block, 0, s, a, b, npix, nz, conf, idx, planes, depth); break;
-    case 5: hipLaunchKernelGGL(k_collapse_max_z_fused<5>, grid, block, 0, s, a, b, npix, nz, conf, idx, planes, depth); break;
-    case 6: hipLaunchKernelGGL(k_collapse_max_z_fused<6>, grid, block, 0, s, a, b, npix, nz, conf, idx, planes, depth); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipExtGetLastError();
+    return dispatch_int<1, 6>(op, [&](auto OP) {
+        return launch_collapse<4>(s, FuseSources{{a, b}}, nx, ny, nz, Fuse2<OP, false>(), conf, idx, planes, depth);
+    });
 }
 
 hipError_t launch_collapse_max_z_fused_n(hipStream_t s, const float* const* srcs, int n_src, int mode, int nx, int ny,
                                          int nz, float* conf, uint8_t* idx, const float* planes, float* depth)
 {
     if (n_src < 1 || n_src > kMaxFuseSources) return hipErrorInvalidValue;
-    FuseSources fs{};
-    for (int c = 0; c < n_src; ++c) fs.p[c] = srcs[c];
-    const int npix = nx * ny;
-    const dim3 grid((npix + 255) / 256), block(256);
-    const float fn = (float)n_src;
-    const float inf = __builtin_inff();
-    switch (mode) {
-    case 0: hipLaunchKernelGGL((k_collapse_max_z_fused_n<EW_ADD, EW_FIN_AM>), grid, block, 0, s, fs, n_src, npix, nz, 0.f, fn, conf, idx, planes, depth); break;
-    case 1: hipLaunchKernelGGL((k_collapse_max_z_fused_n<EW_ADD_INV, EW_FIN_HM>), grid, block, 0, s, fs, n_src, npix, nz, 0.f, fn, conf, idx, planes, depth); break;
-    case 2: hipLaunchKernelGGL((k_collapse_max_z_fused_n<EW_ADD_LOG, EW_FIN_GM>), grid, block, 0, s, fs, n_src, npix, nz, 0.f, fn, conf, idx, planes, depth); break;
-    case 3: hipLaunchKernelGGL((k_collapse_max_z_fused_n<EW_ADD_SQ, EW_FIN_RMS>), grid, block, 0, s, fs, n_src, npix, nz, 0.f, fn, conf, idx, planes, depth); break;
-    case 4: hipLaunchKernelGGL((k_collapse_max_z_fused_n<EW_MIN, -1>), grid, block, 0, s, fs, n_src, npix, nz, inf, fn, conf, idx, planes, depth); break;
-    case 5: hipLaunchKernelGGL((k_collapse_max_z_fused_n<EW_MAX, -1>), grid, block, 0, s, fs, n_src, npix, nz, -inf, fn, conf, idx, planes, depth); break;
-    case 6:
-        if (n_src == 2) hipLaunchKernelGGL(k_collapse_max_z_gm_tree<2>, grid, block, 0, s, fs, npix, nz, conf, idx, planes, depth);
-        else if (n_src == 4) hipLaunchKernelGGL(k_collapse_max_z_gm_tree<4>, grid, block, 0, s, fs, npix, nz, conf, idx, planes, depth);
-        else if (n_src == 8) hipLaunchKernelGGL(k_collapse_max_z_gm_tree<8>, grid, block, 0, s, fs, npix, nz, conf, idx, planes, depth);
-        else return hipErrorInvalidValue;
-        break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipExtGetLastError();
+    const FuseSources fs = fuse_sources(srcs, n_src);
+    return dispatch_fuse_n(mode, n_src, [&](auto v) { return launch_collapse<2>(s, fs, nx, ny, nz, v, conf, idx, planes, depth); });
 }
 
 hipError_t launch_mean_square(hipStream_t s, const float* dsi, size_t n, double* accum)
@@ -6164,7 +6006,7 @@ __global__ __launch_bounds__(256) void k_tie_prove(const float* __restrict__ a, 
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p < npix) {
         const int y = p / nx, x = p - y * nx;
-        // the engine's arg-max: first maximum of the fused exact values (k_collapse_max_z_fused / k_tie_columns)
+        // the engine's arg-max: first maximum of the fused exact values (k_collapse_max_z<Fuse2> / k_tie_columns)
         float best = tie_value<OP>(a, b, p);
         int zbest = 0;
         for (int z = 1; z < nz; ++z) {
@@ -6493,16 +6335,10 @@ hipError_t launch_tie_prove(hipStream_t s, const float* a, const float* b, const
                             int ny, int nz, float rel_gap, unsigned* stats4, uint2* unproven)
 {
     const dim3 grid((nx * ny + 255) / 256), block(256);
-#define DSI_TIE_PROVE(OPV)                                                                                      \
-    case OPV:                                                                                                   \
-        hipLaunchKernelGGL(k_tie_prove<OPV>, grid, block, 0, s, a, b, Ha, Hb, nx, ny, nz, rel_gap, stats4, unproven); \
-        break;
-    switch (b ? op : 0) {
-        DSI_TIE_PROVE(0) DSI_TIE_PROVE(1) DSI_TIE_PROVE(2) DSI_TIE_PROVE(3) DSI_TIE_PROVE(4) DSI_TIE_PROVE(5) DSI_TIE_PROVE(6)
-    default: return hipErrorInvalidValue;
-    }
-#undef DSI_TIE_PROVE
-    return hipExtGetLastError();
+    return dispatch_int<0, 6>(b ? op : 0, [&](auto OP) {
+        hipLaunchKernelGGL(k_tie_prove<OP>, grid, block, 0, s, a, b, Ha, Hb, nx, ny, nz, rel_gap, stats4, unproven);
+        return hipExtGetLastError();
+    });
 }
 
 hipError_t launch_tie_candidates(hipStream_t s, const float* a, const float* b, int op, int npix, int nz, float rel_gap,
@@ -6511,17 +6347,11 @@ hipError_t launch_tie_candidates(hipStream_t s, const float* a, const float* b, 
     if (nz > 256) return hipErrorInvalidValue;
     const dim3 grid((npix + 255) / 256), block(256);
     const dim3 grid2((unsigned)std::min<size_t>(512, ((size_t)cols_cap + 15) / 16)), block2(1024);
-#define DSI_TIE_CAND(OPV)                                                                                                           \
-    case OPV:                                                                                                                       \
-        hipLaunchKernelGGL(k_tie_columns<OPV>, grid, block, 0, s, a, b, npix, nz, rel_gap, counters, cols, cols_cap);                \
-        hipLaunchKernelGGL(k_tie_contenders<OPV>, grid2, block2, 0, s, a, b, npix, nz, rel_gap, counters, cand, cap, cols, cols_cap); \
-        break;
-    switch (b ? op : 0) {
-        DSI_TIE_CAND(0) DSI_TIE_CAND(1) DSI_TIE_CAND(2) DSI_TIE_CAND(3) DSI_TIE_CAND(4) DSI_TIE_CAND(5) DSI_TIE_CAND(6)
-    default: return hipErrorInvalidValue;
-    }
-#undef DSI_TIE_CAND
-    return hipExtGetLastError();
+    return dispatch_int<0, 6>(b ? op : 0, [&](auto OP) {
+        hipLaunchKernelGGL(k_tie_columns<OP>, grid, block, 0, s, a, b, npix, nz, rel_gap, counters, cols, cols_cap);
+        hipLaunchKernelGGL(k_tie_contenders<OP>, grid2, block2, 0, s, a, b, npix, nz, rel_gap, counters, cand, cap, cols, cols_cap);
+        return hipExtGetLastError();
+    });
 }
 
 hipError_t launch_tie_desc(hipStream_t s, const uint32_t* vox, int n, int nx, int npix, uint2* desc, unsigned* plane_bits)
@@ -6628,17 +6458,11 @@ hipError_t launch_tie_pick(hipStream_t s, int op, const uint4* cols, int n_cols,
 {
     if (n_cols <= 0) return hipSuccess;
     const dim3 grid((n_cols + 255) / 256), block(256);
-#define DSI_TIE_PICK(OPV)                                                                                                        \
-    case OPV:                                                                                                                    \
-        hipLaunchKernelGGL(k_tie_pick<OPV>, grid, block, 0, s, cols, n_cols, vox, nsv, npix, exact, count, diff, planes, conf, idx,   \
-                           depth, stats, rel_gap);                                                                               \
-        break;
-    switch (op) {
-        DSI_TIE_PICK(0) DSI_TIE_PICK(1) DSI_TIE_PICK(2) DSI_TIE_PICK(3) DSI_TIE_PICK(4) DSI_TIE_PICK(5) DSI_TIE_PICK(6)
-    default: return hipErrorInvalidValue;
-    }
-#undef DSI_TIE_PICK
-    return hipExtGetLastError();
+    return dispatch_int<0, 6>(op, [&](auto OP) {
+        hipLaunchKernelGGL(k_tie_pick<OP>, grid, block, 0, s, cols, n_cols, vox, nsv, npix, exact, count, diff, planes, conf, idx,
+                           depth, stats, rel_gap);
+        return hipExtGetLastError();
+    });
 }
 
 hipError_t launch_tie_patch(hipStream_t s, const uint32_t* pix, const uint8_t* new_idx, const float* new_conf, int n,
@@ -7366,24 +7190,9 @@ __device__ __forceinline__ float grid_op(float a, float g)
 }
 
 template <int OP>
-__global__ __launch_bounds__(256) void k_grid_binary(float* __restrict__ a, const float* __restrict__ g, size_t n)
-{
-    const size_t n4 = n / 4;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        float4 va = reinterpret_cast<float4*>(a)[i];
-        const float4 vg = reinterpret_cast<const float4*>(g)[i];
-        va.x = grid_op<OP>(va.x, vg.x);
-        va.y = grid_op<OP>(va.y, vg.y);
-        va.z = grid_op<OP>(va.z, vg.z);
-        va.w = grid_op<OP>(va.w, vg.w);
-        reinterpret_cast<float4*>(a)[i] = va;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const size_t i = n4 * 4 + threadIdx.x;
-        a[i] = grid_op<OP>(a[i], g[i]);
-    }
-}
+struct GridOp : VoxelValue<1, true> {
+    __device__ float operator()(const float* x, const double2*) const { return grid_op<OP>(x[0], x[1]); }
+};
 
 // std::minmax_element: the FIRST smallest and the LAST largest element.  (value, position) pairs under a total order --
 // equal values (+0 and -0 included) are told apart by position -- so any reduction tree gives the same answer.
@@ -7701,15 +7510,7 @@ size_t grid_min_max_words() { return (sizeof(MinMaxItem) / 8) * (size_t)(kGridMi
 
 hipError_t launch_grid_binary(hipStream_t s, float* a, const float* g, size_t n, int op)
 {
-    const dim3 grid(grid_for(n / 4 + 1, 256)), block(256);
-    switch (op) {
-    case 1: hipLaunchKernelGGL(k_grid_binary<1>, grid, block, 0, s, a, g, n); break;
-    case 2: hipLaunchKernelGGL(k_grid_binary<2>, grid, block, 0, s, a, g, n); break;
-    case 3: hipLaunchKernelGGL(k_grid_binary<3>, grid, block, 0, s, a, g, n); break;
-    case 4: hipLaunchKernelGGL(k_grid_binary<4>, grid, block, 0, s, a, g, n); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipExtGetLastError();
+    return dispatch_int<1, 4>(op, [&](auto OP) { return launch_voxelwise(s, a, FuseSources{{g}}, n, GridOp<OP>()); });
 }
 
 hipError_t launch_grid_min_max(hipStream_t s, const float* vol, size_t n, unsigned long long* words, int max_blocks)

@@ -381,17 +381,22 @@ def test_gm_tree_is_the_reference_op_applied_pairwise(ctx, n_maps):
     logs = orc.fuse_nary(maps, d.ACC_LOG_SUM)
     assert ok.sum() > 1000 and np.allclose(got[ok], logs[ok], rtol=1e-5)
     # inside the arg-max kernel
-    m = d.MapperEMVS(ctx, (nx, ny, 50.0, 50.0, 33.0, 16.0), d.ShapeDSI(0, 0, nz, 1.0, 5.0, 0.0))
     finite = [np.where(np.isfinite(v) & (v < 1e30), v, 0).astype(np.float32) for v in maps]
-    for g, v in zip(G, finite):
-        g.upload(v)
-    A.setToFusionOfN(G, d.ACC_GM_TREE)
-    m.computeDepthMap(A)
-    want = m.fetchDepthMap()
-    m.computeDepthMapOfFusionN(G, d.ACC_GM_TREE)
-    have = m.fetchDepthMap()
-    for a_, b_ in zip(have, want):
-        assert np.array_equal(a_, b_)
+    for nz2 in (6, 7):                                # an even and an odd number of planes after plane 0
+        m = d.MapperEMVS(ctx, (nx, ny, 50.0, 50.0, 33.0, 16.0), d.ShapeDSI(0, 0, nz2, 1.0, 5.0, 0.0))
+        G2 = [d.Grid3D(ctx, nx, ny, nz2) for _ in range(n_maps)]
+        for g, v in zip(G2, finite):
+            g.upload(np.concatenate([v, v[:nz2 - nz][:, ::-1]]))   # (the seventh plane: plane 0 upside down)
+        A2 = d.Grid3D(ctx, nx, ny, nz2)
+        A2.setToFusionOfN(G2, d.ACC_GM_TREE)
+        m.computeDepthMap(A2)
+        want = m.fetchDepthMap()
+        m.computeDepthMapOfFusionN(G2, d.ACC_GM_TREE)
+        have = m.fetchDepthMap()
+        for a_, b_ in zip(have, want):
+            assert np.array_equal(a_, b_), nz2
+        for o in G2 + [A2, m]:
+            o.close()
     # not an accumulation, and only for 2 / 4 / 8 grids
     from dvs_mcemvs_amd import engine
     with pytest.raises(d.DsiError) as e:
@@ -400,43 +405,48 @@ def test_gm_tree_is_the_reference_op_applied_pairwise(ctx, n_maps):
     with pytest.raises(d.DsiError) as e:
         A.setToFusionOfN(G[:1] + G[:1] + G[:1], d.ACC_GM_TREE)
     assert e.value.code == engine.ERR_BAD_OP
-    for o in G + [A, m]:
+    for o in G + [A]:
         o.close()
 
 
 @pytest.mark.parametrize("n_maps", [1, 3, 4, 8])
 def test_depth_map_of_nary_fusion_equals_fuse_then_collapse(ctx, n_maps):
     """dsi_mapper_depth_map_of_fusion_n (the n-camera fusion inside the arg-max kernel) = setToFusionOfN
-    followed by computeDepthMap, bit for bit, for every accumulate mode -- zeros, ties and an odd
-    number of planes included -- and equal to the oracle's fuse_nary + collapse."""
+    followed by computeDepthMap, bit for bit, for every accumulate mode -- zeros, ties, an all-equal column, a
+    unique maximum on the last plane, one plane, an even and an odd number of planes included -- and equal to
+    the oracle's fuse_nary + collapse."""
     rng = np.random.default_rng(60 + n_maps)
-    nx, ny, nz = 37, 21, 9
+    nx, ny = 37, 21
     cam = (nx, ny, 30.0, 30.0, 18.0, 10.0)
-    m = make_mapper(ctx, cam, nz, 1.0, 6.0, d.VOTE_AUTO)
-    maps = []
-    for k in range(n_maps):
-        v = np.rint(rng.gamma(2.0, 2.0, (nz, ny, nx))).astype(np.float32)   # small integers: many ties
-        v.flat[k::7] = 0.0
-        maps.append(v)
-    G = [d.Grid3D(ctx, nx, ny, nz) for _ in range(n_maps)]
-    for g, v in zip(G, maps):
-        g.upload(v)
-    F = d.Grid3D(ctx, nx, ny, nz)
-    for mode in (d.ACC_SUM, d.ACC_INV_SUM, d.ACC_LOG_SUM, d.ACC_SQ_SUM, d.ACC_MIN, d.ACC_MAX):
-        m.computeDepthMapOfFusionN(G, mode)
-        depth, conf, idx = m.fetchDepthMap()
-        F.setToFusionOfN(G, mode)
-        m.computeDepthMap(F)
-        depth2, conf2, idx2 = m.fetchDepthMap()
-        assert np.array_equal(idx, idx2) and np.array_equal(depth, depth2), mode
-        assert np.array_equal(conf.view(np.uint32), conf2.view(np.uint32)), mode
-        if mode != d.ACC_INV_SUM:
-            rconf, ridx = orc.collapse_max_z(orc.fuse_nary(maps, mode))
-            assert np.array_equal(idx, ridx) and np.array_equal(conf, rconf), mode
-    with pytest.raises(d.DsiError):
-        m.computeDepthMapOfFusionN(G, 9)
-    for o in G + [F, m]:
-        o.close()
+    for nz in (1, 2, 9):
+        m = make_mapper(ctx, cam, nz, 1.0, 6.0, d.VOTE_AUTO)
+        maps = []
+        for k in range(n_maps):
+            v = np.rint(rng.gamma(2.0, 2.0, (nz, ny, nx))).astype(np.float32)   # small integers: many ties
+            v.flat[k::7] = 0.0
+            v[:, 3, 3] = 2.0                                                    # all equal: index 0
+            v[nz - 1, 4, 4] = 50.0                                              # the unique maximum on the last plane
+            maps.append(v)
+        G = [d.Grid3D(ctx, nx, ny, nz) for _ in range(n_maps)]
+        for g, v in zip(G, maps):
+            g.upload(v)
+        F = d.Grid3D(ctx, nx, ny, nz)
+        for mode in (d.ACC_SUM, d.ACC_INV_SUM, d.ACC_LOG_SUM, d.ACC_SQ_SUM, d.ACC_MIN, d.ACC_MAX):
+            m.computeDepthMapOfFusionN(G, mode)
+            depth, conf, idx = m.fetchDepthMap()
+            F.setToFusionOfN(G, mode)
+            m.computeDepthMap(F)
+            depth2, conf2, idx2 = m.fetchDepthMap()
+            assert np.array_equal(idx, idx2) and np.array_equal(depth, depth2), (nz, mode)
+            assert np.array_equal(conf.view(np.uint32), conf2.view(np.uint32)), (nz, mode)
+            assert idx[3, 3] == 0 and idx[4, 4] == nz - 1, (nz, mode)
+            if mode != d.ACC_INV_SUM:
+                rconf, ridx = orc.collapse_max_z(orc.fuse_nary(maps, mode))
+                assert np.array_equal(idx, ridx) and np.array_equal(conf, rconf), (nz, mode)
+        with pytest.raises(d.DsiError):
+            m.computeDepthMapOfFusionN(G, 9)
+        for o in G + [F, m]:
+            o.close()
 
 
 def test_fusion_errors(ctx):
@@ -451,13 +461,15 @@ def test_fusion_errors(ctx):
         assert e.value.code == 5  # "Improper fusion method selected"
 
 
-@pytest.mark.parametrize("shape", [(33, 17, 1), (64, 48, 16), (50, 40, 100), (31, 9, 256)])
+@pytest.mark.parametrize("shape", [(33, 17, 1), (64, 48, 16), (50, 40, 100), (31, 9, 256),
+                                   # around one and two groups of 8 planes after plane 0
+                                   (37, 5, 2), (37, 5, 8), (37, 5, 9), (37, 5, 10), (37, 5, 17)])
 def test_collapse_max_z_exact(ctx, shape):
     nx, ny, nz = shape
     rng = np.random.default_rng(nz)
     v = rng.integers(0, 6, (nz, ny, nx)).astype(np.float32)  # many ties: first max must win
     v[:, 0, 0] = 0.0                                         # empty column -> conf 0, index 0
-    if nz > 2:
+    if nz > 1:
         v[:, 1, 1] = 3.0                                     # all equal -> index 0
         v[nz - 1, 2, 2] = 99.0                               # max on the last plane
     G = d.Grid3D(ctx, nx, ny, nz)
@@ -487,19 +499,25 @@ def test_depth_map_of_fused_grid(ctx):
     assert np.abs(depth - orc.indices_to_depth(ridx, ms[0].raw_depths_vec_)).max() <= 1e-4
 
 
-@pytest.mark.parametrize("shape", [(64, 48, 16), (50, 40, 7), (33, 17, 1), (96, 72, 130)])
+@pytest.mark.parametrize("shape", [(64, 48, 16), (50, 40, 7), (33, 17, 1), (96, 72, 130),
+                                   # around one and two groups of 4 planes after plane 0
+                                   (37, 5, 4), (37, 5, 5), (37, 5, 6), (37, 5, 9)])
 def test_depth_map_of_fusion_equals_fuse_then_collapse(ctx, shape):
     """dsi_mapper_depth_map_of_fusion (camera fusion inside the arg-max kernel) = the reference's
     sequence resetGrid / addTwoGrids / <op>TwoGrids (process1.cpp:126-158) then collapseMaxZSlice +
-    convertDepthIndicesToValues, for every op code, bit for bit -- ties and all-zero columns included."""
+    convertDepthIndicesToValues, for every op code, bit for bit -- ties, all-zero columns and a unique maximum
+    on the last plane included."""
     nx, ny, nz = shape
     rng = np.random.default_rng(nx + nz)
     a = np.floor(rng.gamma(1.5, 2.0, (nz, ny, nx))).astype(np.float32)      # integers: many ties
     g = np.floor(rng.gamma(1.5, 2.0, (nz, ny, nx))).astype(np.float32)
     a[:, :2] = 0.0
     g[:, 1:3] = 0.0
-    a[:, 5, 5] = 3.25
-    g[:, 5, 5] = 3.25                                                         # a whole column tied: index 0
+    ty, ly = min(5, ny - 1), ny - 1
+    a[:, ty, 5] = 3.25
+    g[:, ty, 5] = 3.25                                                        # a whole column tied: index 0
+    a[nz - 1, ly, 7] = 99.0
+    g[nz - 1, ly, 7] = 99.0                                                   # the unique maximum on the last plane
     cam = (nx, ny, 0.8 * nx, 0.8 * nx, 0.5 * nx, 0.5 * ny)
     m = d.MapperEMVS(ctx, cam, d.ShapeDSI(0, 0, nz, 1.0, 9.0, 0.0))
     A, G, F = d.Grid3D(ctx, nx, ny, nz), d.Grid3D(ctx, nx, ny, nz), d.Grid3D(ctx, nx, ny, nz)
@@ -515,6 +533,7 @@ def test_depth_map_of_fusion_equals_fuse_then_collapse(ctx, shape):
             assert np.array_equal(x, y), "op %d" % op
         rconf, ridx = orc.collapse_max_z(orc.fuse2(a, g, op))
         assert np.array_equal(got[2], ridx) and np.array_equal(got[1], rconf)
+        assert got[2][ty, 5] == 0 and got[2][ly, 7] == nz - 1, "op %d" % op
     with pytest.raises(d.DsiError) as e:
         m.computeDepthMapOfFusion(A, G, 7)
     assert e.value.code == 5

@@ -1,6 +1,6 @@
 """The reduce-scattered and the plane-sharded depth map for 1 to 9 (8) ranks, emulated one rank after another in ONE
 process on ONE device: everything those paths run but the nccl* calls -- dsi::host::scatter_plan / plane_range,
-scattered_local (finalize of an interior slab of the accumulator, k_collapse_max_z on it, k_pack_argmax with
+scattered_local (finalize of an interior slab of the accumulator, k_collapse_max_z<Identity, 8> on it, k_pack_argmax with
 combine), sharded_prepare (k_pack_argmax with plane_begin != 0) and k_unpack_argmax over the full depth vector.
 The all-reduce(MAX) between ranks is np.maximum.reduce over the downloaded keys.  Every comparison is bit-exact.
 

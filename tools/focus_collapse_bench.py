@@ -1,8 +1,8 @@
 """The focus-based collapses (getDepthMapFromDSI's method 0..4: k_focus_tile + k_focus_finish) and the local-focus
 transform (computeLocalFocusInPlace into another grid) at 346 x 260 x 100 (configs[1]), 512 x 512 x 200 and
-1024 x 1024 x 256, beside the arg-max (k_collapse_max_z, method -1) at the same shape.  Times are device-event times of
-`--reps` back-to-back calls on the context's stream, per call; TB/s = compulsory traffic (the volume read once, the
-maps or the new volume written once) over that time.  Cross-check the per-kernel split with
+1024 x 1024 x 256, beside the arg-max (k_collapse_max_z<Identity, 8>, method -1) at the same shape.  Times are
+device-event times of `--reps` back-to-back calls on the context's stream, per call; TB/s = compulsory traffic (the
+volume read once, the maps or the new volume written once) over that time.  Cross-check the per-kernel split with
 rocprofv3 --kernel-trace --stats.  Prints one JSON line per (shape, operation)."""
 import argparse
 import json
