@@ -175,6 +175,10 @@ struct dsi_context {
     // Grid3D min/max, slices and slice images: partial extremes and per-slice scales; device side of the host-output forms
     DevBuf<unsigned long long> grid_words;
     DevBuf<uint8_t> grid_bytes;
+    // volume filters (dsi_grid_laplacian, _smooth_diffuse, _moran_index): the other volume of the ping-pong / the
+    // standardized volume and its smoothed copy; the sums of dsi_grid_mean_std and of Moran's index
+    DevBuf<float> filter_a, filter_b;
+    DevBuf<double> filter_words;
     // the run's pictures (dsi_event_image*, dsi_depth_images, dsi_mapper_depth_images): counts and extremes; uploaded inputs,
     // the colour table and the device side of the host-output forms
     DevBuf<uint32_t> img_words;
@@ -993,6 +997,9 @@ int dsi_context_destroy(dsi_context_t* ctx)
     ctx->focus_volume.release();
     ctx->grid_words.release();
     ctx->grid_bytes.release();
+    ctx->filter_a.release();
+    ctx->filter_b.release();
+    ctx->filter_words.release();
     ctx->img_words.release();
     ctx->img_bytes.release();
     ctx->pc.release();
@@ -1410,6 +1417,138 @@ int dsi_grid_mean_square(dsi_grid_t* g, double* out)
     HIP_TRY(hipMemcpyAsync(&sum, ctx->ms_accum, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *out = sum / (double)g->n;  // cartesian3dgrid.cpp:173
+    return DSI_OK;
+}
+
+// ---- volume filters: cartesian3dgrid_filter.cpp, gaussianiir3d.cpp ----
+
+int dsi_grid_laplacian(dsi_grid_t* g)
+{
+    REQUIRE(g, DSI_ERR_INVALID, "grid is null");
+    dsi_context* ctx = g->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    // every voxel reads its neighbours: the result goes to scratch and is copied back (the grid keeps its storage)
+    HIP_TRY(ctx->filter_a.reserve(g->n));
+    HIP_TRY(dsi::launch_stencil3d(ctx->stream, g->data, ctx->filter_a.p, g->nx, g->ny, g->nz, false, 0.f));
+    HIP_TRY(hipMemcpyAsync(g->data, ctx->filter_a.p, g->n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    return DSI_OK;
+}
+
+int dsi_grid_smooth_diffuse(dsi_grid_t* g, float sigma, int* steps_out)
+{
+    REQUIRE(g, DSI_ERR_INVALID, "grid is null");
+    REQUIRE(std::isfinite(sigma) && sigma > 0.f, DSI_ERR_INVALID, "sigma = %g: the diffusion needs a finite sigma > 0", (double)sigma);
+    // cartesian3dgrid_filter.cpp:24-27, in fp32
+    const float dt_cfl = 1.f / 12.f;
+    const float t_final = 0.5f * sigma * sigma;
+    const float dt = std::min(0.5f * dt_cfl, 0.5f * t_final);
+    REQUIRE(t_final > 0.f && dt > 0.f, DSI_ERR_INVALID, "sigma = %g: sigma * sigma underflows", (double)sigma);
+    const float steps_f = std::ceil(t_final / dt);
+    REQUIRE(steps_f <= 1.0e6f, DSI_ERR_INVALID, "sigma = %g asks for %g diffusion steps (at most 1e6)", (double)sigma, (double)steps_f);
+    const int steps = (int)steps_f;
+    dsi_context* ctx = g->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    HIP_TRY(ctx->filter_a.reserve(g->n));
+    float *from = g->data, *to = ctx->filter_a.p;
+    for (int i = 0; i < steps; ++i) {
+        HIP_TRY(dsi::launch_stencil3d(ctx->stream, from, to, g->nx, g->ny, g->nz, true, dt));
+        std::swap(from, to);
+    }
+    if (from != g->data)  // an odd number of steps ended in the scratch volume
+        HIP_TRY(hipMemcpyAsync(g->data, from, g->n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    if (steps_out) *steps_out = steps;
+    return DSI_OK;
+}
+
+namespace {
+
+struct IirAxis {
+    float nu, boundaryscale, postscale;
+};
+
+// gaussianiir3d.cpp:158-163
+IirAxis iir_axis(float sigma, int numsteps)
+{
+    const float sigma2 = sigma * sigma;
+    const double lambda = (double)sigma2 / (2.0 * numsteps);
+    const double dnu = (1.0 + 2.0 * lambda - std::sqrt(1.0 + 4.0 * lambda)) / (2.0 * lambda);
+    return IirAxis{(float)dnu, (float)(1.0 / (1.0 - dnu)), (float)std::pow(dnu / lambda, (double)numsteps)};
+}
+
+// the 3-sigma gaussianiir3d on nx * ny * nz floats of device memory, on the context's stream
+int iir3d_run(dsi_context* ctx, float* vol, int nx, int ny, int nz, float sigma_x, float sigma_y, float sigma_z, int numsteps)
+{
+    const float sigma[3] = {sigma_x, sigma_y, sigma_z};
+    IirAxis ax[3];
+    float postscale = 1.f;
+    for (int a = 0; a < 3; ++a) {
+        ax[a] = iir_axis(sigma[a], numsteps);
+        postscale *= ax[a].postscale;
+    }
+    for (int a = 0; a < 3; ++a)
+        HIP_TRY(dsi::launch_iir_axis(ctx->stream, vol, nx, ny, nz, a, ax[a].nu, ax[a].boundaryscale, numsteps, a == 2, postscale));
+    return DSI_OK;
+}
+
+}  // namespace
+
+int dsi_grid_smooth_iir(dsi_grid_t* g, float sigma_x, float sigma_y, float sigma_z, int numsteps)
+{
+    REQUIRE(g, DSI_ERR_INVALID, "grid is null");
+    REQUIRE(numsteps <= 16, DSI_ERR_INVALID, "numsteps = %d (at most 16)", numsteps);
+    if (sigma_x <= 0 || sigma_y <= 0 || sigma_z <= 0 || numsteps <= 0) return DSI_OK;  // gaussianiir3d.cpp:153-154
+    if (int rc = set_device(g->ctx)) return rc;
+    return iir3d_run(g->ctx, g->data, g->nx, g->ny, g->nz, sigma_x, sigma_y, sigma_z, numsteps);
+}
+
+int dsi_grid_mean_std(dsi_grid_t* g, double* mean, double* stddev)
+{
+    REQUIRE(g && mean && stddev, DSI_ERR_INVALID, "null argument");
+    dsi_context* ctx = g->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    HIP_TRY(ctx->filter_words.reserve(dsi::volume_sum_words()));
+    HIP_TRY(dsi::launch_volume_mean_std(ctx->stream, g->data, g->n, ctx->filter_words.p));
+    double r[2];
+    HIP_TRY(hipMemcpyAsync(r, ctx->filter_words.p, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *mean = r[0];
+    *stddev = r[1];
+    return DSI_OK;
+}
+
+int dsi_grid_moran_index(dsi_grid_t* g, float sigma, double* out)
+{
+    REQUIRE(g && out, DSI_ERR_INVALID, "null argument");
+    REQUIRE(!std::isnan(sigma) && sigma < 1.0e3f, DSI_ERR_INVALID, "sigma = %g (a number below 1000)", (double)sigma);
+    if (sigma < 0.2) sigma = 0.2;  // cartesian3dgrid_filter.cpp:115-119: a double comparison, an fp32 value
+    double mean = 0, stddev = 0;
+    if (int rc = dsi_grid_mean_std(g, &mean, &stddev)) return rc;
+    REQUIRE(stddev > 0 && std::isfinite(stddev), DSI_ERR_INVALID, "the grid's deviation is %g: Moran's index is undefined", stddev);
+    dsi_context* ctx = g->ctx;
+    // the centre weight: a unit impulse in a k^3 volume through the same kernels (:138-146)
+    const int half = (int)(2 * std::ceil(3.f * sigma));
+    const int k = 2 * half + 1;
+    const size_t nk = (size_t)k * k * k, centre = (size_t)half + (size_t)k * ((size_t)half + (size_t)k * half);
+    HIP_TRY(ctx->filter_a.reserve(std::max(g->n, nk)));
+    HIP_TRY(ctx->filter_b.reserve(g->n));
+    static const float one = 1.f;  // outlives the asynchronous copy on every path
+    float c = 0.f;
+    HIP_TRY(hipMemsetAsync(ctx->filter_a.p, 0, nk * sizeof(float), ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->filter_a.p + centre, &one, sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = iir3d_run(ctx, ctx->filter_a.p, k, k, k, sigma, sigma, sigma, 3)) return rc;
+    HIP_TRY(hipMemcpyAsync(&c, ctx->filter_a.p + centre, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    // the standardized volume and its smoothed copy (:126-135)
+    const float inv_stddev = (float)(1.0 / stddev);
+    HIP_TRY(dsi::launch_volume_standardize(ctx->stream, g->data, g->n, mean, inv_stddev, ctx->filter_a.p, ctx->filter_b.p));
+    if (int rc = iir3d_run(ctx, ctx->filter_b.p, g->nx, g->ny, g->nz, sigma, sigma, sigma, 3)) return rc;
+    HIP_TRY(dsi::launch_volume_moran_numerator(ctx->stream, ctx->filter_a.p, ctx->filter_b.p, g->n, c, ctx->filter_words.p));
+    double numer = 0;
+    HIP_TRY(hipMemcpyAsync(&numer, ctx->filter_words.p + 2, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const float sum_weights = 1.f - c;
+    const double denom = (double)sum_weights * ((double)g->n - 1.0);  // :194-195
+    *out = numer / (denom + 1e-6);
     return DSI_OK;
 }
 
@@ -4204,6 +4343,18 @@ DSI_API int dsi_test_div_probe(dsi_context_t* ctx, const float* n, const float* 
     if (dq) (void)hipFree(dq);
     if (dr) (void)hipFree(dr);
     if (e != hipSuccess) return fail(DSI_ERR_HIP, "div probe failed: %s", hipGetErrorString(e));
+    return DSI_OK;
+}
+
+// one axis (0 x, 1 y, 2 z) of dsi_grid_smooth_iir on its own, for tools/volume_filters_bench.py; with_post: the z kernel's
+// folded post-scale
+DSI_API int dsi_test_iir_axis(dsi_grid_t* g, int axis, float sigma, int numsteps, int with_post)
+{
+    REQUIRE(g && axis >= 0 && axis <= 2 && sigma > 0 && numsteps >= 1 && numsteps <= 16, DSI_ERR_INVALID, "bad argument");
+    if (int rc = set_device(g->ctx)) return rc;
+    const IirAxis ax = iir_axis(sigma, numsteps);
+    HIP_TRY(dsi::launch_iir_axis(g->ctx->stream, g->data, g->nx, g->ny, g->nz, axis, ax.nu, ax.boundaryscale, numsteps,
+                                 with_post != 0, ax.postscale));
     return DSI_OK;
 }
 #endif  // DSI_TIMING_EXPERIMENTS

@@ -437,4 +437,23 @@ struct LensCoef {
 // lut[y * width + x] = float32 (u, v) of raw pixel (x, y); width * height < 2^32 - 1
 hipError_t launch_rectify_lut(hipStream_t s, int model, const LensCoef& c, int width, int height, float2* lut);
 
+// ---- volume filters: laplacianInPlace / smoothInPlace (cartesian3dgrid_filter.cpp:19-110), smoothInPlaceIIR3D
+// (gaussianiir3d.cpp:143-251) and the sums of computeMoranIndexGaussianWeights (cartesian3dgrid_filter.cpp:113-199) ----
+// dst = the 7-point Laplacian of src with index-clamped neighbours (diffuse == false), or src + dt * that (one explicit
+// Euler step of the heat equation).  dst must not be src.
+hipError_t launch_stencil3d(hipStream_t s, const float* src, float* dst, int nx, int ny, int nz, bool diffuse, float dt);
+// numsteps >= 1 forward / backward recurrences along every line of one axis (0 x, 1 y, 2 z), in place; with_post: every
+// voxel * post afterwards (the same single fp32 multiply wherever it is folded in)
+hipError_t launch_iir_axis(hipStream_t s, float* vol, int nx, int ny, int nz, int axis, float nu, float boundaryscale,
+                           int numsteps, bool with_post, float post);
+// words: volume_sum_words() doubles of scratch; words[0] = mean, words[1] = population deviation (two passes), words[2] =
+// the Moran numerator once the stream has run.  The order of every addition depends on n alone.
+constexpr int kVolumeSumBlocks = 1024;
+size_t volume_sum_words();
+hipError_t launch_volume_mean_std(hipStream_t s, const float* vol, size_t n, double* words);
+// z = z_copy = float((double(v) - mean) * double(inv_stddev))
+hipError_t launch_volume_standardize(hipStream_t s, const float* vol, size_t n, double mean, float inv_stddev, float* z, float* z_copy);
+// words[2] = sum of double(float(z * float(smooth - centre * z)))
+hipError_t launch_volume_moran_numerator(hipStream_t s, const float* z, const float* smooth, size_t n, float centre, double* words);
+
 }  // namespace dsi

@@ -8433,4 +8433,397 @@ hipError_t launch_rectify_lut(hipStream_t s, int model, const LensCoef& c, int w
     return hipExtGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------ volume filters ---
+// Grid3D::laplacianInPlace / smoothInPlace (the free functions laplacian3D and diffuse, cartesian3dgrid_filter.cpp:72-104,
+// 19-62), smoothInPlaceIIR3D (the 3-sigma gaussianiir3d, gaussianiir3d.cpp:143-251) and the reductions of
+// computeMoranIndexGaussianWeights (cartesian3dgrid_filter.cpp:113-199).  DESIGN.md 7i.  Every product is an fp32 multiply
+// rounded on its own (-ffp-contract=off), then an fp32 add; nothing flushes subnormals.
+namespace {
+
+// One workgroup owns a 64 x 16 tile of the x-y plane and marches over a chunk of z.  Three LDS slots hold the planes z - 1,
+// z, z + 1 of the tile WITH its one-voxel rim, every cell read from the index-clamped position (homogeneous Neumann:
+// the neighbour of a border voxel is the voxel itself), so a voxel costs one global read per step.  Each thread keeps its
+// four voxels of the planes z - 1, z, z + 1 in registers; x and y neighbours come from the LDS slot of plane z.  The rim
+// loads of plane z + 2 are in flight while plane z is computed.  One barrier per plane: plane z + 2 overwrites the slot of
+// plane z - 1, which no thread reads after the barrier of plane z + 1.
+constexpr int kStTX = 64, kStTY = 16, kStRows = 4;
+constexpr int kStW = kStTX + 2, kStCells = kStW * (kStTY + 2);
+constexpr int kStFill = (kStCells + 255) / 256;
+
+template <bool DIFFUSE>
+__global__ __launch_bounds__(256) void k_stencil3d(const float* __restrict__ src, float* __restrict__ dst, int nx, int ny, int nz,
+                                                   int zchunk, float dt)
+{
+    __shared__ float tile[3][kStCells];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int x0 = blockIdx.x * kStTX, y0 = blockIdx.y * kStTY;
+    const int z_begin = blockIdx.z * zchunk, z_end = min(nz, z_begin + zchunk);
+    const size_t plane = (size_t)nx * (size_t)ny;
+
+    size_t off[kStFill];  // this thread's cells of a slot, as clamped positions in a plane
+#pragma unroll
+    for (int i = 0; i < kStFill; ++i) {
+        const int c = (int)threadIdx.x + 256 * i;
+        const int row = c / kStW, col = c - row * kStW;
+        const int gx = min(max(x0 - 1 + col, 0), nx - 1), gy = min(max(y0 - 1 + row, 0), ny - 1);
+        off[i] = (size_t)gy * (size_t)nx + (size_t)gx;
+    }
+    float t[kStFill];
+    auto load = [&](int z) {
+        const float* base = src + (size_t)min(max(z, 0), nz - 1) * plane;
+#pragma unroll
+        for (int i = 0; i < kStFill; ++i)
+            if ((int)threadIdx.x + 256 * i < kStCells) t[i] = base[off[i]];
+    };
+    auto put = [&](int z) {
+        float* slot = tile[(z + 1) % 3];  // z >= -1
+#pragma unroll
+        for (int i = 0; i < kStFill; ++i)
+            if ((int)threadIdx.x + 256 * i < kStCells) slot[threadIdx.x + 256 * i] = t[i];
+    };
+    int cell[kStRows];
+#pragma unroll
+    for (int r = 0; r < kStRows; ++r) cell[r] = (1 + ty + 4 * r) * kStW + 1 + tx;
+
+    load(z_begin - 1);
+    put(z_begin - 1);
+    load(z_begin);
+    put(z_begin);
+    load(z_begin + 1);
+    __syncthreads();
+    float prev[kStRows], cur[kStRows];
+#pragma unroll
+    for (int r = 0; r < kStRows; ++r) {
+        prev[r] = tile[z_begin % 3][cell[r]];
+        cur[r] = tile[(z_begin + 1) % 3][cell[r]];
+    }
+    const int x = x0 + tx;
+    for (int z = z_begin; z < z_end; ++z) {
+        put(z + 1);
+        load(z + 2);
+        __syncthreads();
+        const float* here = tile[(z + 1) % 3];
+        const float* above = tile[(z + 2) % 3];
+        float* out = dst + (size_t)z * plane;
+#pragma unroll
+        for (int r = 0; r < kStRows; ++r) {
+            const int c = cell[r];
+            const float v = cur[r], nxt = above[c];
+            const float two_v = 2.f * v;
+            const float dxx = (here[c + 1] - two_v) + here[c - 1];
+            const float dyy = (here[c + kStW] - two_v) + here[c - kStW];
+            const float dzz = (nxt - two_v) + prev[r];
+            const float lap = (dxx + dyy) + dzz;
+            const int y = y0 + ty + 4 * r;
+            if (x < nx && y < ny) out[(size_t)y * (size_t)nx + (size_t)x] = DIFFUSE ? v + dt * lap : lap;
+            prev[r] = v;
+            cur[r] = nxt;
+        }
+    }
+}
+
+// The line recurrence of gaussianiir3d (gaussianiir3d.cpp:169-184), sequential by definition: p is one lane's line.  Eight
+// voxels are read ahead of the chain that consumes them (the reads do not depend on it; the chain's order and roundings are
+// those of the plain loop), so a chain link waits for the previous link, not for memory.
+constexpr int kIirAhead = 8;
+template <class Line>
+__device__ __forceinline__ void iir_sweeps(Line p, int n, float nu, float bs, int numsteps)
+{
+    for (int step = 0; step < numsteps; ++step) {
+        float prev = p.get(0) * bs;
+        p.set(0, prev);
+        int i = 1;
+        for (; i + kIirAhead <= n; i += kIirAhead) {
+            float a[kIirAhead];
+#pragma unroll
+            for (int k = 0; k < kIirAhead; ++k) a[k] = p.get(i + k);
+#pragma unroll
+            for (int k = 0; k < kIirAhead; ++k) {
+                prev = a[k] + nu * prev;
+                p.set(i + k, prev);
+            }
+        }
+        for (; i < n; ++i) {
+            prev = p.get(i) + nu * prev;
+            p.set(i, prev);
+        }
+        prev = prev * bs;  // a line of one voxel is scaled twice per step, as the reference does
+        p.set(n - 1, prev);
+        i = n - 1;  // prev is voxel i
+        for (; i - kIirAhead >= 0; i -= kIirAhead) {
+            float a[kIirAhead];
+#pragma unroll
+            for (int k = 0; k < kIirAhead; ++k) a[k] = p.get(i - 1 - k);
+#pragma unroll
+            for (int k = 0; k < kIirAhead; ++k) {
+                prev = a[k] + nu * prev;
+                p.set(i - 1 - k, prev);
+            }
+        }
+        for (; i > 0; --i) {
+            prev = p.get(i - 1) + nu * prev;
+            p.set(i - 1, prev);
+        }
+    }
+}
+
+struct LdsLine {  // element i of the line at base[i * stride]
+    float* base;
+    int stride;
+    __device__ __forceinline__ float get(int i) const { return base[i * stride]; }
+    __device__ __forceinline__ void set(int i, float v) const { base[i * stride] = v; }
+};
+struct GlobalLine {
+    float* base;
+    size_t stride;
+    __device__ __forceinline__ float get(int i) const { return base[(size_t)i * stride]; }
+    __device__ __forceinline__ void set(int i, float v) const { base[(size_t)i * stride] = v; }
+};
+
+// y and z lines: 64 lanes along x (every access coalesced), one wave per workgroup.  Line `outer * tiles + tile` starts at
+// vol[outer * outer_stride + x], x < width, and steps by `stride`.  IN_LDS: the 64 lines live in LDS ([len][64], a lane
+// touches its own column only: no bank conflict, no barrier), so all sweeps cost one global read and one global write;
+// otherwise (a line set larger than the LDS) the sweeps run through global memory.  POST: * post on the way out.
+template <bool IN_LDS, bool POST>
+__global__ __launch_bounds__(64) void k_iir_strided(float* __restrict__ vol, size_t width, unsigned tiles, size_t stride,
+                                                    size_t outer_stride, int len, float nu, float bs, int numsteps, float post)
+{
+    extern __shared__ float s_lines[];
+    const unsigned outer = blockIdx.x / tiles, tile = blockIdx.x - outer * tiles;
+    const size_t x = (size_t)tile * 64 + threadIdx.x;
+    if (x >= width) return;
+    float* p = vol + (size_t)outer * outer_stride + x;
+    if (IN_LDS) {
+        float* mine = s_lines + threadIdx.x;
+#pragma unroll 16  // one wave per workgroup: the loads in flight are what hides HBM latency
+        for (int i = 0; i < len; ++i) mine[i * 64] = p[(size_t)i * stride];
+        iir_sweeps(LdsLine{mine, 64}, len, nu, bs, numsteps);
+#pragma unroll 16
+        for (int i = 0; i < len; ++i) p[(size_t)i * stride] = POST ? mine[i * 64] * post : mine[i * 64];
+    } else {
+        iir_sweeps(GlobalLine{p, stride}, len, nu, bs, numsteps);
+        if (POST)
+            for (int i = 0; i < len; ++i) p[(size_t)i * stride] = p[(size_t)i * stride] * post;
+    }
+}
+
+// x lines: the recurrence runs along the contiguous axis.  A workgroup stages `rows` consecutive rows (one contiguous
+// piece of the volume) into LDS with coalesced loads, row stride `pitch` odd so that the lanes of wave 0, one row each,
+// walk distinct banks; wave 0 sweeps; all four waves store coalesced.
+__global__ __launch_bounds__(256) void k_iir_x_lds(float* __restrict__ vol, int nx, size_t n_rows, int rows, int pitch, float nu,
+                                                   float bs, int numsteps)
+{
+    extern __shared__ float s_lines[];
+    const size_t row0 = (size_t)blockIdx.x * (size_t)rows;
+    const int here = (int)min((size_t)rows, n_rows - row0);
+    float* g = vol + row0 * (size_t)nx;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int r = wave; r < here; r += 4) {
+#pragma unroll 8
+        for (int c = lane; c < nx; c += 64) s_lines[r * pitch + c] = g[(size_t)r * (size_t)nx + c];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < here) iir_sweeps(LdsLine{s_lines + threadIdx.x * pitch, 1}, nx, nu, bs, numsteps);
+    __syncthreads();
+    for (int r = wave; r < here; r += 4)
+        for (int c = lane; c < nx; c += 64) g[(size_t)r * (size_t)nx + c] = s_lines[r * pitch + c];
+}
+
+// rows too long for the LDS: one lane per row, through global memory
+__global__ __launch_bounds__(64) void k_iir_x_global(float* __restrict__ vol, int nx, size_t n_rows, float nu, float bs, int numsteps)
+{
+    const size_t row = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (row >= n_rows) return;
+    iir_sweeps(GlobalLine{vol + row * (size_t)nx, 1}, nx, nu, bs, numsteps);
+}
+
+__global__ __launch_bounds__(256) void k_scale(float* __restrict__ vol, size_t n, float post)
+{
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) vol[i] = vol[i] * post;
+}
+
+// Sums in double with a FIXED tree: a thread's grid-stride partial, 64 lanes by shuffles, 4 waves in order, then the
+// workgroups' partials folded by one workgroup the same way.  The number of workgroups depends on n alone, so two calls
+// return the same bits.  words[0] = mean, words[1] = stddev, words[2] = the Moran numerator.
+constexpr int VF_SUM = 0, VF_SQ_DEV = 1, VF_MORAN = 2;
+
+__device__ __forceinline__ double vf_block_sum(double acc, double* part)
+{
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return (part[0] + part[1]) + (part[2] + part[3]);  // every thread holds the workgroup's sum
+}
+
+template <int WHAT>
+__global__ __launch_bounds__(256) void k_vf_partials(const float* __restrict__ a, const float* __restrict__ b, size_t n,
+                                                     const double* __restrict__ words, float c, double* __restrict__ partials)
+{
+    __shared__ double part[4];
+    const double mean = WHAT == VF_SQ_DEV ? words[0] : 0.0;
+    double acc = 0.0;
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        if (WHAT == VF_SUM) {
+            acc += (double)a[i];
+        } else if (WHAT == VF_SQ_DEV) {
+            const double d = (double)a[i] - mean;
+            acc += d * d;
+        } else {  // cartesian3dgrid_filter.cpp:188-190: a = standardized, b = its smoothed copy, c = the centre weight
+            const float z = a[i];
+            const float cz = c * z;
+            const float nb = b[i] - cz;
+            acc += (double)(z * nb);
+        }
+    }
+    const double sum = vf_block_sum(acc, part);
+    if (threadIdx.x == 0) partials[blockIdx.x] = sum;
+}
+
+template <int WHAT>
+__global__ __launch_bounds__(256) void k_vf_finish(const double* __restrict__ partials, int n_part, double count,
+                                                   double* __restrict__ words)
+{
+    __shared__ double part[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n_part; i += 256) acc += partials[i];
+    const double sum = vf_block_sum(acc, part);
+    if (threadIdx.x == 0) {
+        if (WHAT == VF_SUM) words[0] = sum / count;
+        else if (WHAT == VF_SQ_DEV) words[1] = sqrt(sum / count);
+        else words[2] = sum;
+    }
+}
+
+// cartesian3dgrid_filter.cpp:126-129: (v - mean) in double, times the fp32 reciprocal deviation, rounded to fp32
+__global__ __launch_bounds__(256) void k_standardize(const float* __restrict__ vol, size_t n, double mean, float inv_stddev,
+                                                     float* __restrict__ z, float* __restrict__ z_copy)
+{
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const float v = (float)(((double)vol[i] - mean) * (double)inv_stddev);
+        z[i] = v;
+        z_copy[i] = v;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_stencil3d(hipStream_t s, const float* src, float* dst, int nx, int ny, int nz, bool diffuse, float dt)
+{
+    if (!src || !dst || src == dst || nx < 1 || ny < 1 || nz < 1) return hipErrorInvalidValue;
+    const unsigned bx = (unsigned)((nx + kStTX - 1) / kStTX), by = (unsigned)((ny + kStTY - 1) / kStTY);
+    if (by > 65535u) return hipErrorInvalidValue;
+    // chunks of z: long enough that the two extra planes a chunk reads stay cheap, short enough to fill the machine
+    int zchunk = 32;
+    while (zchunk > 8 && (size_t)bx * by * (size_t)((nz + zchunk - 1) / zchunk) < 2048) zchunk /= 2;
+    unsigned bz = (unsigned)((nz + zchunk - 1) / zchunk);
+    if (bz > 65535u) {
+        zchunk = (nz + 65534) / 65535;
+        bz = (unsigned)((nz + zchunk - 1) / zchunk);
+    }
+    const dim3 grid(bx, by, bz), block(256);
+    if (diffuse)
+        hipLaunchKernelGGL(k_stencil3d<true>, grid, block, 0, s, src, dst, nx, ny, nz, zchunk, dt);
+    else
+        hipLaunchKernelGGL(k_stencil3d<false>, grid, block, 0, s, src, dst, nx, ny, nz, zchunk, dt);
+    return hipExtGetLastError();
+}
+
+// lines along `stride` (y: width = nx, n_outer = nz, outer_stride = nx ny; z: width = nx ny, n_outer = 1)
+static hipError_t launch_iir_strided(hipStream_t s, float* vol, size_t width, size_t n_outer, size_t stride, size_t outer_stride,
+                                     int len, float nu, float bs, int numsteps, bool with_post, float post)
+{
+    const size_t tiles = (width + 63) / 64, blocks = tiles * n_outer;
+    if (tiles > 0x7fffffffull || blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    const size_t lds = (size_t)len * 64 * sizeof(float);
+    const bool in_lds = lds <= max_dynamic_lds();
+    const dim3 grid((unsigned)blocks), block(64);
+#define DSI_IIR_STRIDED(IN_LDS, POST)                                                                                          \
+    do {                                                                                                                       \
+        if (IN_LDS)                                                                                                            \
+            if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(&k_iir_strided<IN_LDS, POST>), lds)) return e;  \
+        hipLaunchKernelGGL((k_iir_strided<IN_LDS, POST>), grid, block, IN_LDS ? lds : 0, s, vol, width, (unsigned)tiles, stride, \
+                           outer_stride, len, nu, bs, numsteps, post);                                                         \
+    } while (0)
+    if (in_lds && with_post) DSI_IIR_STRIDED(true, true);
+    else if (in_lds) DSI_IIR_STRIDED(true, false);
+    else if (with_post) DSI_IIR_STRIDED(false, true);
+    else DSI_IIR_STRIDED(false, false);
+#undef DSI_IIR_STRIDED
+    return hipExtGetLastError();
+}
+
+hipError_t launch_iir_axis(hipStream_t s, float* vol, int nx, int ny, int nz, int axis, float nu, float bs, int numsteps,
+                           bool with_post, float post)
+{
+    if (!vol || nx < 1 || ny < 1 || nz < 1 || numsteps < 1 || axis < 0 || axis > 2) return hipErrorInvalidValue;
+    const size_t plane = (size_t)nx * (size_t)ny, n = plane * (size_t)nz;
+    if (axis == 1) return launch_iir_strided(s, vol, (size_t)nx, (size_t)nz, (size_t)nx, plane, ny, nu, bs, numsteps, with_post, post);
+    if (axis == 2) return launch_iir_strided(s, vol, plane, 1, plane, 0, nz, nu, bs, numsteps, with_post, post);
+    const size_t n_rows = (size_t)ny * (size_t)nz;
+    const int pitch = nx | 1;
+    const size_t fit = max_dynamic_lds() / ((size_t)pitch * sizeof(float));
+    if (fit >= 8) {
+        // as many rows as fit, 64 at the most (one per lane of the sweeping wave); no more than the volume needs to fill the machine
+        size_t rows = std::min<size_t>(fit, 64);
+        while (rows > 16 && (n_rows + rows - 1) / rows < 512) rows /= 2;
+        const size_t blocks = (n_rows + rows - 1) / rows, lds = rows * (size_t)pitch * sizeof(float);
+        if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+        if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(&k_iir_x_lds), lds)) return e;
+        hipLaunchKernelGGL(k_iir_x_lds, dim3((unsigned)blocks), dim3(256), lds, s, vol, nx, n_rows, (int)rows, pitch, nu, bs, numsteps);
+    } else {
+        const size_t blocks = (n_rows + 63) / 64;
+        if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_iir_x_global, dim3((unsigned)blocks), dim3(64), 0, s, vol, nx, n_rows, nu, bs, numsteps);
+    }
+    if (hipError_t e = hipExtGetLastError()) return e;
+    if (with_post) {
+        hipLaunchKernelGGL(k_scale, dim3(grid_for(n, 256)), dim3(256), 0, s, vol, n, post);
+        return hipExtGetLastError();
+    }
+    return hipSuccess;
+}
+
+size_t volume_sum_words() { return 4 + (size_t)kVolumeSumBlocks; }
+
+static hipError_t launch_vf_sum(hipStream_t s, int what, const float* a, const float* b, size_t n, float c, double* words)
+{
+    if (!a || !words || n < 1) return hipErrorInvalidValue;
+    const int blocks = grid_for(n, 256, kVolumeSumBlocks);
+    double* partials = words + 4;
+    const double count = (double)n;
+    if (what == VF_SUM) {
+        hipLaunchKernelGGL(k_vf_partials<VF_SUM>, dim3(blocks), dim3(256), 0, s, a, b, n, words, c, partials);
+        hipLaunchKernelGGL(k_vf_finish<VF_SUM>, dim3(1), dim3(256), 0, s, partials, blocks, count, words);
+    } else if (what == VF_SQ_DEV) {
+        hipLaunchKernelGGL(k_vf_partials<VF_SQ_DEV>, dim3(blocks), dim3(256), 0, s, a, b, n, words, c, partials);
+        hipLaunchKernelGGL(k_vf_finish<VF_SQ_DEV>, dim3(1), dim3(256), 0, s, partials, blocks, count, words);
+    } else {
+        hipLaunchKernelGGL(k_vf_partials<VF_MORAN>, dim3(blocks), dim3(256), 0, s, a, b, n, words, c, partials);
+        hipLaunchKernelGGL(k_vf_finish<VF_MORAN>, dim3(1), dim3(256), 0, s, partials, blocks, count, words);
+    }
+    return hipExtGetLastError();
+}
+
+hipError_t launch_volume_mean_std(hipStream_t s, const float* vol, size_t n, double* words)
+{
+    if (hipError_t e = launch_vf_sum(s, VF_SUM, vol, nullptr, n, 0.f, words)) return e;
+    return launch_vf_sum(s, VF_SQ_DEV, vol, nullptr, n, 0.f, words);
+}
+
+hipError_t launch_volume_standardize(hipStream_t s, const float* vol, size_t n, double mean, float inv_stddev, float* z, float* z_copy)
+{
+    if (!vol || !z || !z_copy || n < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_standardize, dim3(grid_for(n, 256)), dim3(256), 0, s, vol, n, mean, inv_stddev, z, z_copy);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_volume_moran_numerator(hipStream_t s, const float* z, const float* smooth, size_t n, float centre, double* words)
+{
+    if (!smooth) return hipErrorInvalidValue;
+    return launch_vf_sum(s, VF_MORAN, z, smooth, n, centre, words);
+}
+
 }  // namespace dsi

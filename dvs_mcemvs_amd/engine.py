@@ -181,6 +181,11 @@ def load_library():
         "dsi_grid_accumulate_value_at": (C.c_int, [vp, C.c_uint64, C.c_float]),
         "dsi_grid_slices_u8": (C.c_int, [vp, C.c_uint, C.c_int, u8p]),
         "dsi_grid_slices_u8_dev": (C.c_int, [vp, C.c_uint, C.c_int, vp]),
+        "dsi_grid_laplacian": (C.c_int, [vp]),
+        "dsi_grid_smooth_diffuse": (C.c_int, [vp, C.c_float, intp]),
+        "dsi_grid_smooth_iir": (C.c_int, [vp, C.c_float, C.c_float, C.c_float, C.c_int]),
+        "dsi_grid_mean_std": (C.c_int, [vp, f64p, f64p]),
+        "dsi_grid_moran_index": (C.c_int, [vp, C.c_float, f64p]),
         "dsi_mapper_create": (C.c_int, [vp, C.POINTER(_MapperConfig), C.POINTER(vp)]),
         "dsi_mapper_destroy": (C.c_int, [vp]),
         "dsi_mapper_grid": (vp, [vp]),
@@ -309,6 +314,7 @@ def load_library():
             "dsi_test_fused_trace_enable": (C.c_int, [vp, szp]),
             "dsi_test_fused_trace_read": (C.c_int, [vp, vp, C.c_size_t]),
             "dsi_test_run_length_total": (C.c_int, [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+            "dsi_test_iir_axis": (C.c_int, [vp, C.c_int, C.c_float, C.c_int, C.c_int]),
         })
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not export the ABI
@@ -779,6 +785,43 @@ class Grid3D:
         out = C.c_double()
         _check(load_library().dsi_grid_mean_square(self._h, C.byref(out)))
         return out.value
+
+    # -- volume filters, cartesian3dgrid_filter.cpp and gaussianiir3d.cpp -------------------------------
+    def laplacian(self):
+        """laplacianInPlace: the 7-point Laplacian with index-clamped neighbours, in place."""
+        _check(load_library().dsi_grid_laplacian(self._h))
+
+    def smooth_diffuse(self, sigma=1.0):
+        """smoothInPlace: explicit heat-equation steps, in place.  Returns the number of steps taken."""
+        steps = C.c_int()
+        _check(load_library().dsi_grid_smooth_diffuse(self._h, float(np.float32(sigma)), C.byref(steps)))
+        return steps.value
+
+    def smooth_iir(self, sigma_x=1.0, sigma_y=1.0, sigma_z=1.0, numsteps=3):
+        """smoothInPlaceIIR3D (numsteps = 3): the recursive Gaussian of gaussianiir3d, in place.  A sigma <= 0 or
+        numsteps <= 0 leaves the grid unchanged."""
+        _check(load_library().dsi_grid_smooth_iir(self._h, float(np.float32(sigma_x)), float(np.float32(sigma_y)),
+                                                  float(np.float32(sigma_z)), int(numsteps)))
+
+    def mean_std(self):
+        """computeMeanStd: (mean, population standard deviation), accumulated in double; the same bits on every call."""
+        mean, std = C.c_double(), C.c_double()
+        _check(load_library().dsi_grid_mean_std(self._h, C.byref(mean), C.byref(std)))
+        return mean.value, std.value
+
+    def moran_index(self, sigma):
+        """computeMoranIndexGaussianWeights: Moran's index under Gaussian weights; the grid is not modified."""
+        out = C.c_double()
+        _check(load_library().dsi_grid_moran_index(self._h, float(np.float32(sigma)), C.byref(out)))
+        return out.value
+
+    laplacianInPlace = laplacian
+    smoothInPlace = smooth_diffuse
+    computeMeanStd = mean_std
+    computeMoranIndexGaussianWeights = moran_index
+
+    def smoothInPlaceIIR3D(self, sigma_x=1.0, sigma_y=1.0, sigma_z=1.0):
+        self.smooth_iir(sigma_x, sigma_y, sigma_z, 3)
 
     # -- the members that are no camera fusion, cartesian3dgrid.h:95-109,166-184 (DESIGN.md 7d) ----------------
     def _binary(self, other, op):

@@ -256,6 +256,34 @@ DSI_API int dsi_grid_slices_u8(dsi_grid_t *g, unsigned dim_idx, int normalize_by
 /* same, device output (4-byte aligned, else DSI_ERR_INVALID), asynchronous */
 DSI_API int dsi_grid_slices_u8_dev(dsi_grid_t *g, unsigned dim_idx, int normalize_by_minmax, uint8_t *out_dev);
 
+/* ---- volume filters: cartesian3dgrid_filter.cpp and gaussianiir3d.cpp (arithmetic and kernels: DESIGN.md 7i) ----
+ * Each result lands in the grid's own storage (dsi_grid_device_ptr does not change; a second volume, where one is needed,
+ * is scratch of the grid's context).  Every product is an fp32 multiply rounded on its own, then an fp32 add, subnormals
+ * included: bit for bit what the reference's CPU loops compute.  Asynchronous unless stated. */
+/* Grid3D::laplacianInPlace (laplacian3D, cartesian3dgrid_filter.cpp:72-110): per voxel Dxx = (v[+x] - 2 v) + v[-x], likewise
+ * Dyy, Dzz, neighbours by index clamping (homogeneous Neumann); the voxel becomes (Dxx + Dyy) + Dzz. */
+DSI_API int dsi_grid_laplacian(dsi_grid_t *g);
+/* Grid3D::smoothInPlace (diffuse, cartesian3dgrid_filter.cpp:19-69): explicit Euler steps v + dt ((Dxx + Dyy) + Dzz) of the heat
+ * equation, in fp32 dt = min(0.5f / 12.f, 0.5f t) with t = 0.5f sigma sigma, ceil(t / dt) steps, each from the previous step's
+ * volume.  steps_out (may be NULL) receives the step count.  sigma <= 0 or not finite (the reference divides 0 by 0 there),
+ * sigma so small that sigma^2 underflows, or more than 1e6 steps (sigma > 288): DSI_ERR_INVALID. */
+DSI_API int dsi_grid_smooth_diffuse(dsi_grid_t *g, float sigma, int *steps_out);
+/* Grid3D::smoothInPlaceIIR3D = the 3-sigma gaussianiir3d (gaussianiir3d.cpp:143-251; the member passes numsteps = 3):
+ * Alvarez-Mazorra recursive Gaussian, per line and step p[0] *= b; p[i] += nu p[i-1]; p[n-1] *= b; p[i-1] += nu p[i]; x lines,
+ * then y, then z, then every voxel times the fp32 product of the axes' post-scales.  The recurrence is evaluated sequentially
+ * along every line.  Any sigma <= 0 or numsteps <= 0: the grid is left unchanged, DSI_OK (the reference returns silently);
+ * numsteps > 16: DSI_ERR_INVALID. */
+DSI_API int dsi_grid_smooth_iir(dsi_grid_t *g, float sigma_x, float sigma_y, float sigma_z, int numsteps);
+/* computeMeanStd, which the reference calls and never defines; here: mean = sum v / N and stddev = sqrt(sum (v - mean)^2 / N)
+ * (two passes, population deviation), accumulated in double over a fixed tree: two calls return the same bits.  Synchronises. */
+DSI_API int dsi_grid_mean_std(dsi_grid_t *g, double *mean, double *stddev);
+/* Grid3D::computeMoranIndexGaussianWeights (cartesian3dgrid_filter.cpp:113-199): spatial autocorrelation of the grid under
+ * Gaussian weights.  sigma < 0.2 becomes 0.2f; z = the standardized grid (fp32), s = z through the IIR filter (sigma, sigma,
+ * sigma, 3 steps), c = the centre of a unit impulse in a k^3 volume through the same filter, k = 2 (2 ceil(3 sigma)) + 1;
+ * I = sum z (s - c z) / ((1 - c)(N - 1) + 1e-6), the sum in double.  The grid is not modified.  A grid of zero (or non-finite)
+ * deviation, NaN or sigma >= 1000: DSI_ERR_INVALID.  Synchronises. */
+DSI_API int dsi_grid_moran_index(dsi_grid_t *g, float sigma, double *out);
+
 /* ---------------------------------------------------------- multi-GPU (RCCL) */
 /* The temporal fusion of process_2 (process2.cpp:211-242: one accumulate per sub-interval, one
  * finalize) and of the sliding window (main.cpp:177) shards by time slice: every GPU accumulates

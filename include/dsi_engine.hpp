@@ -913,6 +913,21 @@ public:
         dsi::check(dsi_grid_mean_square(h_, &v));
         return v;
     }
+    // cartesian3dgrid_filter.cpp and gaussianiir3d.h:27-29 (spellings and defaults); DESIGN.md 7i
+    void smoothInPlace(const float sigma = 1.f) { dsi::check(dsi_grid_smooth_diffuse(h_, sigma, NULL)); }
+    void smoothInPlaceIIR3D(const float sigma_x = 1.f, const float sigma_y = 1.f, const float sigma_z = 1.f)
+    {
+        dsi::check(dsi_grid_smooth_iir(h_, sigma_x, sigma_y, sigma_z, 3));  // cartesian3dgrid_filter.cpp:11
+    }
+    void laplacianInPlace() { dsi::check(dsi_grid_laplacian(h_)); }
+    double computeMoranIndexGaussianWeights(float sigma) const
+    {
+        double v = 0;
+        dsi::check(dsi_grid_moran_index(h_, sigma, &v));
+        return v;
+    }
+    // the reference declares and calls it but never defines it: mean and population deviation, two passes, in double
+    void computeMeanStd(double* mean, double* stddev) const { dsi::check(dsi_grid_mean_std(h_, mean, stddev)); }
     // host copies (the reference exposes raw pointers via getPointerToSlice; device memory
     // cannot be handed out like that, dsi_grid_device_ptr() is the device-side equivalent)
     std::vector<float> download() const
