@@ -3314,12 +3314,11 @@ static int radius_filter_device(hipStream_t st, PcBuffers& pc, const uint32_t* n
     return DSI_OK;
 }
 
-int dsi_mapper_get_pointcloud(dsi_mapper_t* m, const float* depth_host, const uint8_t* mask_host,
-                              const dsi_pointcloud_options_t* opts, float* xyzi_host, size_t capacity, size_t* n_points,
-                              size_t* n_unfiltered)
+// The cloud of dsi_mapper_get_pointcloud in m->pc.out on the device (dsi_map_integrate_mapper reads it there):
+// counts[0] points before the radius filter, counts[1] after it.  Synchronises.
+static int pointcloud_device(dsi_mapper_t* m, const float* depth_host, const uint8_t* mask_host, const dsi_pointcloud_options_t* opts,
+                             uint32_t counts[2])
 {
-    REQUIRE(m && opts && n_points, DSI_ERR_INVALID, "null argument");
-    REQUIRE(xyzi_host || capacity == 0, DSI_ERR_INVALID, "xyzi_host is null");
     if (int rc = check_radius_filter_args(opts->radius_search, opts->min_num_neighbors)) return rc;
     REQUIRE(!depth_host == !mask_host, DSI_ERR_INVALID,
             "depth_host and mask_host must both be given, or both be NULL (the maps left on the device)");
@@ -3359,18 +3358,30 @@ int dsi_mapper_get_pointcloud(dsi_mapper_t* m, const float* depth_host, const ui
     HIP_TRY(dsi::launch_pc_backproject(st, depth, mask, nx, ny, g.vfx, g.vfy, g.vcx, g.vcy, pc.blk.p, pc.tiles.p, pc.pts.p));
     // (the count of the back-projected points stays on the device: the filter's kernels read it, sized for every pixel)
     const uint32_t* n_dev = pc.blk.p + dsi::pc_block_words(npix) - 1;
-    uint32_t counts[2] = {0, 0};
+    counts[0] = counts[1] = 0;
     HIP_TRY(hipMemcpyAsync(&counts[0], n_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     if (int rc = radius_filter_device(st, pc, n_dev, npix, opts->radius_search, opts->min_num_neighbors)) return rc;
     // (the compaction's block counts go to a buffer of their own: n_dev still lives in pc.blk)
     HIP_TRY(dsi::launch_pc_compact(st, pc.pts.p, pc.keep.p, (uint32_t)npix, pc.blk2.p, pc.tiles.p, pc.out.p));
     HIP_TRY(hipMemcpyAsync(&counts[1], pc.blk2.p + dsi::pc_block_words(npix) - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+int dsi_mapper_get_pointcloud(dsi_mapper_t* m, const float* depth_host, const uint8_t* mask_host,
+                              const dsi_pointcloud_options_t* opts, float* xyzi_host, size_t capacity, size_t* n_points,
+                              size_t* n_unfiltered)
+{
+    REQUIRE(m && opts && n_points, DSI_ERR_INVALID, "null argument");
+    REQUIRE(xyzi_host || capacity == 0, DSI_ERR_INVALID, "xyzi_host is null");
+    uint32_t counts[2];
+    if (int rc = pointcloud_device(m, depth_host, mask_host, opts, counts)) return rc;
     if (n_unfiltered) *n_unfiltered = counts[0];
     *n_points = counts[1];
     REQUIRE(capacity >= counts[1], DSI_ERR_INVALID, "capacity of %zu points is too small: %u needed", capacity, counts[1]);
     if (counts[1]) {
-        HIP_TRY(hipMemcpyAsync(xyzi_host, pc.out.p, (size_t)counts[1] * sizeof(float4), hipMemcpyDeviceToHost, st));
+        hipStream_t st = m->ctx->stream;
+        HIP_TRY(hipMemcpyAsync(xyzi_host, m->pc.out.p, (size_t)counts[1] * sizeof(float4), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     return DSI_OK;
@@ -4175,6 +4186,238 @@ int dsi_radius_outlier_removal(dsi_context_t* ctx, const float* xyz_host, size_t
     HIP_TRY(hipMemcpyAsync(pc.n.p, &n32, sizeof n32, hipMemcpyHostToDevice, st));
     if (int rc = radius_filter_device(st, pc, pc.n.p, n, radius, min_neighbors)) return rc;
     HIP_TRY(hipMemcpyAsync(keep_host, pc.keep.p, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+// ---- the world map (include/dsi_engine.h "the world map") ----
+
+struct dsi_map {
+    dsi_context* ctx = nullptr;
+    double leaf = 0.0;
+    uint32_t cap_log2 = 0;
+    void* block = nullptr;               // the table (dsi::map_table_at)
+    unsigned long long* ctr = nullptr;   // device: occupied, accepted, rejected, table-full
+    unsigned long long host_ctr[4] = {0, 0, 0, 0};  // as read back by the last integrate call
+    uint64_t calls = 0, growths = 0;
+    DevBuf<float> upload, xyz;           // a call's host points; the extraction's outputs
+    DevBuf<uint32_t> blk, tiles, n_out, w_out;
+    DevBuf<unsigned long long> key_out;
+};
+
+namespace {
+
+constexpr int kMapMinLog2 = 8, kMapMaxLog2 = 27;
+
+void map_free(dsi_map* mp)
+{
+    if (mp->block) (void)hipFree(mp->block);
+    if (mp->ctr) (void)hipFree(mp->ctr);
+    mp->upload.release();
+    mp->xyz.release();
+    mp->blk.release();
+    mp->tiles.release();
+    mp->n_out.release();
+    mp->w_out.release();
+    mp->key_out.release();
+    delete mp;
+}
+
+// the table doubled until occupied + n <= 3/4 of its slots (the caller checked that 2^27 slots are enough)
+int map_grow_for(dsi_map* mp, size_t n)
+{
+    uint32_t want = mp->cap_log2;
+    while ((mp->host_ctr[0] + n) * 4 > ((uint64_t)3 << want)) ++want;
+    if (want == mp->cap_log2) return DSI_OK;
+    hipStream_t st = mp->ctx->stream;
+    void* block = nullptr;
+    HIP_TRY(hipMalloc(&block, dsi::map_table_bytes(want)));
+    hipError_t e = hipMemsetAsync(block, 0, dsi::map_table_bytes(want), st);
+    if (e == hipSuccess && mp->host_ctr[0])
+        e = dsi::launch_map_rehash(st, dsi::map_table_at(mp->block, mp->cap_log2), dsi::map_table_at(block, want), mp->ctr);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        (void)hipFree(block);
+        return fail(DSI_ERR_HIP, "growing the map's table to 2^%u slots failed: %s", want, hipGetErrorString(e));
+    }
+    (void)hipFree(mp->block);
+    mp->block = block;
+    mp->growths += want - mp->cap_log2;
+    mp->cap_log2 = want;
+    return DSI_OK;
+}
+
+// one integrate call of n device points (stride floats each) on the map's stream; synchronises
+int map_integrate_device(dsi_map* mp, const float* pts_dev, size_t stride, size_t n, const double T_w_rv[12], size_t* n_rejected)
+{
+    REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
+    REQUIRE(mp->calls < 0xffffffffull, DSI_ERR_INVALID, "at most 2^32 - 1 integrate calls per map");
+    REQUIRE((mp->host_ctr[0] + n) * 4 <= ((uint64_t)3 << kMapMaxLog2), DSI_ERR_INVALID,
+            "%llu cells + %zu points need more than 2^%d slots: the map is unchanged", mp->host_ctr[0], n, kMapMaxLog2);
+    if (int rc = map_grow_for(mp, n)) return rc;
+    hipStream_t st = mp->ctx->stream;
+    const uint32_t serial = (uint32_t)++mp->calls;
+    const unsigned long long rejected_before = mp->host_ctr[2];
+    HIP_TRY(dsi::launch_map_integrate(st, pts_dev, (uint32_t)stride, (uint32_t)n, T_w_rv, mp->leaf, serial,
+                                      dsi::map_table_at(mp->block, mp->cap_log2), mp->ctr));
+    HIP_TRY(hipMemcpyAsync(mp->host_ctr, mp->ctr, sizeof mp->host_ctr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_HIP, "the map's table ran full (%llu points lost): an engine bug, the map is unusable",
+            mp->host_ctr[3]);
+    if (n_rejected) *n_rejected = (size_t)(mp->host_ctr[2] - rejected_before);
+    return DSI_OK;
+}
+
+int check_map_pose(const double T[12])
+{
+    REQUIRE(T, DSI_ERR_INVALID, "T_w_rv is null");
+    return DSI_OK;
+}
+
+// the filtered cells counted and scanned into mp->blk; *total their number.  Synchronises.
+int map_count_device(dsi_map* mp, uint32_t min_points, uint32_t min_windows, size_t* total)
+{
+    const size_t cap = (size_t)1 << mp->cap_log2, words = dsi::pc_block_words(cap);
+    hipStream_t st = mp->ctx->stream;
+    HIP_TRY(mp->blk.reserve(words));
+    HIP_TRY(mp->tiles.reserve(dsi::pc_scan_tile_words(words)));
+    HIP_TRY(dsi::launch_map_count(st, dsi::map_table_at(mp->block, mp->cap_log2), min_points, min_windows, mp->blk.p, mp->tiles.p));
+    uint32_t n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, mp->blk.p + words - 1, sizeof n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *total = n;
+    return DSI_OK;
+}
+
+}  // namespace
+
+int dsi_invert_pose(const double T[12], double out[12])
+{
+    REQUIRE(T && out, DSI_ERR_INVALID, "null argument");
+    double r[12];
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) r[4 * i + j] = T[4 * j + i];
+        r[4 * i + 3] = -((T[i] * T[3] + T[4 + i] * T[7]) + T[8 + i] * T[11]);
+    }
+    std::memcpy(out, r, sizeof r);
+    return DSI_OK;
+}
+
+int dsi_map_create(dsi_context_t* ctx, double leaf, int capacity_log2, dsi_map_t** out)
+{
+    REQUIRE(ctx && out, DSI_ERR_INVALID, "null argument");
+    REQUIRE(std::isfinite(leaf) && leaf > 0.0, DSI_ERR_INVALID, "leaf must be finite and > 0 (got %g)", leaf);
+    REQUIRE(capacity_log2 >= kMapMinLog2 && capacity_log2 <= kMapMaxLog2, DSI_ERR_INVALID, "capacity_log2 must be in %d..%d (got %d)",
+            kMapMinLog2, kMapMaxLog2, capacity_log2);
+    if (int rc = set_device(ctx)) return rc;
+    dsi_map* mp = new (std::nothrow) dsi_map;
+    REQUIRE(mp, DSI_ERR_INVALID, "out of host memory");
+    mp->ctx = ctx;
+    mp->leaf = leaf;
+    mp->cap_log2 = (uint32_t)capacity_log2;
+    const size_t bytes = dsi::map_table_bytes(mp->cap_log2);
+    hipError_t e = hipMalloc(&mp->block, bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&mp->ctr), sizeof mp->host_ctr);
+    if (e == hipSuccess) e = hipMemsetAsync(mp->block, 0, bytes, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(mp->ctr, 0, sizeof mp->host_ctr, ctx->stream);
+    if (e != hipSuccess) {
+        map_free(mp);
+        return fail(DSI_ERR_HIP, "map allocation of 2^%d slots failed: %s", capacity_log2, hipGetErrorString(e));
+    }
+    ++ctx->children;
+    *out = mp;
+    return DSI_OK;
+}
+
+int dsi_map_destroy(dsi_map_t* mp)
+{
+    if (!mp) return DSI_OK;
+    (void)hipSetDevice(mp->ctx->device);
+    (void)hipStreamSynchronize(mp->ctx->stream);
+    --mp->ctx->children;
+    map_free(mp);
+    return DSI_OK;
+}
+
+int dsi_map_reset(dsi_map_t* mp)
+{
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    if (int rc = set_device(mp->ctx)) return rc;
+    HIP_TRY(hipMemsetAsync(mp->block, 0, dsi::map_table_bytes(mp->cap_log2), mp->ctx->stream));
+    HIP_TRY(hipMemsetAsync(mp->ctr, 0, sizeof mp->host_ctr, mp->ctx->stream));
+    std::memset(mp->host_ctr, 0, sizeof mp->host_ctr);
+    mp->calls = mp->growths = 0;
+    return DSI_OK;
+}
+
+int dsi_map_integrate(dsi_map_t* mp, const float* xyz_host, size_t stride_floats, size_t n, const double T_w_rv[12], size_t* n_rejected)
+{
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    REQUIRE(stride_floats == 3 || stride_floats == 4, DSI_ERR_INVALID, "stride_floats must be 3 or 4 (got %zu)", stride_floats);
+    REQUIRE(n == 0 || xyz_host, DSI_ERR_INVALID, "xyz_host is null");
+    if (int rc = check_map_pose(T_w_rv)) return rc;
+    REQUIRE(n <= ((size_t)1 << kMapMaxLog2), DSI_ERR_INVALID, "at most 2^%d points per call (got %zu)", kMapMaxLog2, n);
+    if (int rc = set_device(mp->ctx)) return rc;
+    if (n) {
+        HIP_TRY(mp->upload.reserve(n * stride_floats));
+        HIP_TRY(hipMemcpyAsync(mp->upload.p, xyz_host, n * stride_floats * sizeof(float), hipMemcpyHostToDevice, mp->ctx->stream));
+    }
+    return map_integrate_device(mp, mp->upload.p, stride_floats, n, T_w_rv, n_rejected);
+}
+
+int dsi_map_integrate_mapper(dsi_map_t* mp, dsi_mapper_t* m, const dsi_pointcloud_options_t* opts_pc, const double T_w_rv[12],
+                             size_t* n_points, size_t* n_rejected)
+{
+    REQUIRE(mp && m && opts_pc, DSI_ERR_INVALID, "null argument");
+    if (int rc = check_map_pose(T_w_rv)) return rc;
+    REQUIRE(mp->ctx == m->ctx, DSI_ERR_CONTEXT, "the map and the mapper live on different contexts");
+    uint32_t counts[2];
+    if (int rc = pointcloud_device(m, nullptr, nullptr, opts_pc, counts)) return rc;
+    if (n_points) *n_points = counts[1];
+    return map_integrate_device(mp, reinterpret_cast<const float*>(m->pc.out.p), 4, counts[1], T_w_rv, n_rejected);
+}
+
+int dsi_map_info(dsi_map_t* mp, dsi_map_info_t* info)
+{
+    REQUIRE(mp && info, DSI_ERR_INVALID, "null argument");
+    info->leaf = mp->leaf;
+    info->capacity = (uint64_t)1 << mp->cap_log2;
+    info->occupied = mp->host_ctr[0];
+    info->calls = mp->calls;
+    info->accepted = mp->host_ctr[1];
+    info->rejected = mp->host_ctr[2];
+    info->growths = mp->growths;
+    return DSI_OK;
+}
+
+int dsi_map_count(dsi_map_t* mp, uint32_t min_points, uint32_t min_windows, size_t* n)
+{
+    REQUIRE(mp && n, DSI_ERR_INVALID, "null argument");
+    if (int rc = set_device(mp->ctx)) return rc;
+    return map_count_device(mp, min_points, min_windows, n);
+}
+
+int dsi_map_extract(dsi_map_t* mp, uint32_t min_points, uint32_t min_windows, float* xyz_host, uint32_t* n_points_host,
+                    uint32_t* n_windows_host, uint64_t* keys_host, size_t capacity, size_t* n)
+{
+    REQUIRE(mp && n, DSI_ERR_INVALID, "null argument");
+    if (int rc = set_device(mp->ctx)) return rc;
+    size_t total = 0;
+    if (int rc = map_count_device(mp, min_points, min_windows, &total)) return rc;
+    *n = total;
+    REQUIRE(capacity >= total, DSI_ERR_INVALID, "capacity of %zu cells is too small: %zu needed", capacity, total);
+    if (!total) return DSI_OK;
+    hipStream_t st = mp->ctx->stream;
+    HIP_TRY(mp->xyz.reserve(3 * total));
+    HIP_TRY(mp->n_out.reserve(total));
+    HIP_TRY(mp->w_out.reserve(total));
+    HIP_TRY(mp->key_out.reserve(total));
+    HIP_TRY(dsi::launch_map_extract(st, dsi::map_table_at(mp->block, mp->cap_log2), min_points, min_windows, mp->leaf, mp->blk.p, mp->xyz.p,
+                                    mp->n_out.p, mp->w_out.p, mp->key_out.p));
+    if (xyz_host) HIP_TRY(hipMemcpyAsync(xyz_host, mp->xyz.p, 3 * total * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (n_points_host) HIP_TRY(hipMemcpyAsync(n_points_host, mp->n_out.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (n_windows_host) HIP_TRY(hipMemcpyAsync(n_windows_host, mp->w_out.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (keys_host) HIP_TRY(hipMemcpyAsync(keys_host, mp->key_out.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return DSI_OK;
 }

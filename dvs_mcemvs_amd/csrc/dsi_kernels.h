@@ -331,6 +331,29 @@ hipError_t launch_pc_radius_filter(hipStream_t s, const float4* pts, const uint3
 hipError_t launch_pc_compact(hipStream_t s, const float4* pts, const uint8_t* keep, uint32_t n_max, uint32_t* blk, uint32_t* tiles,
                              float4* out);
 
+// ---- the world map (dsi_map_*): a voxel hash of 2^cap_log2 slots in one device block ----
+// keys [cap] (0 = empty), sums [3 * cap] (u64 sums of the 32-bit cell fractions, x y z per slot), n / windows / stamp [cap]
+struct MapTable {
+    unsigned long long *keys, *sums;
+    uint32_t *n, *windows, *stamp;
+    uint32_t cap_log2;
+};
+size_t map_table_bytes(uint32_t cap_log2);
+MapTable map_table_at(void* block, uint32_t cap_log2);  // the arrays inside a block of map_table_bytes (8-byte aligned)
+// n points (stride floats each, x y z first) through T_w_rv (row-major [R | t]) into the table as call number `serial` (> 0).
+// ctr: four u64 -- occupied slots, accepted points, rejected points, points that found the table full (must stay 0).
+// The caller keeps occupied + n <= 3/4 of the capacity.
+hipError_t launch_map_integrate(hipStream_t s, const float* pts, uint32_t stride, uint32_t n, const double T_w_rv[12], double leaf,
+                                uint32_t serial, const MapTable& t, unsigned long long* ctr);
+// every occupied slot of `from` into `to` (zeroed by the caller, larger than `from`)
+hipError_t launch_map_rehash(hipStream_t s, const MapTable& from, const MapTable& to, unsigned long long* ctr);
+// the cells with n >= min_points and windows >= min_windows: per-workgroup counts, scanned; the total lands in
+// blk[pc_block_words(capacity) - 1] (blk: pc_block_words(capacity) words, tiles: pc_scan_tile_words of that)
+hipError_t launch_map_count(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, uint32_t* blk, uint32_t* tiles);
+// after launch_map_count with the same filter: the cells in slot order -- centroid (3 floats), n, windows, key
+hipError_t launch_map_extract(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, double leaf,
+                              const uint32_t* blk, float* xyz, uint32_t* n_out, uint32_t* w_out, unsigned long long* key_out);
+
 
 // focus-based collapses (Grid3D::collapseZSliceBy*, cartesian3dgrid.cpp:192-414; DESIGN.md "Focus-based collapses"):
 // method 0 LocalVar, 1 LocalMeanSquare, 2 GradMag (half_patchsize 0..8), 3 LaplacianMag, 4 DoG.  keys: scratch of

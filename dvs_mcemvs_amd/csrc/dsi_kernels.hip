@@ -6775,6 +6775,196 @@ hipError_t launch_pc_compact(hipStream_t s, const float4* pts, const uint8_t* ke
     return hipExtGetLastError();
 }
 
+// ---- the world map: per-window clouds fused in a voxel hash (include/dsi_engine.h dsi_map_*) ----
+// A table of 2^cap_log2 slots, open addressing with linear probing from pc_hash(key); key = pc_key of the point's world
+// cell, never 0 (every packed coordinate is >= 1), so 0 marks an empty slot and a zeroed table is an empty map.  Per slot:
+// n (u32 points), S[3] (u64 sums of the 32-bit cell fractions), windows (u32 calls that reached the cell) and stamp (the
+// serial number of the last such call).  Everything a point does to its slot is an integer atomic, so the state does not
+// depend on the order of the threads, on how the points are split into calls or on where the probing put the cell; only
+// the slot ORDER does, and extraction sorts that away on the host (the key comes with every cell).
+// Arithmetic (double, one rounding per operation, no FMA): X = ((r00 x + r01 y) + r02 z) + t0; q = X / leaf; c = floor(q);
+// f = q - c; F = (u64) floor(f * 2^32).  f is exact except for -2^-54 < q < 0, where 1 + q rounds to 1 and F = 2^32: the
+// point then counts at the cell's upper face, still inside the closed cell.  Rejected: a non-finite X, Y or Z (q is then
+// non-finite too) or |c| > kPcCellMax.  ctr: [0] occupied slots, [1] accepted points, [2] rejected points, [3] != 0 when
+// a probe sequence ran through the whole table (the host sizes the table so that it cannot; it is an error, not a hang).
+namespace {
+
+struct MapPose {
+    double m[12];
+};
+
+__device__ inline bool map_axis(double X, double leaf, int* c, unsigned long long* F)
+{
+    const double q = X / leaf;
+    const double cf = floor(q);
+    if (!(fabs(cf) <= (double)kPcCellMax)) return false;  // (NaN included)
+    const double f = q - cf;
+    *c = (int)cf;
+    *F = (unsigned long long)floor(f * 4294967296.0);
+    return true;
+}
+
+// the slot that holds key k, claimed if no slot holds it yet (*fresh); ~0u when every slot holds another key
+__device__ inline uint32_t map_slot(unsigned long long* keys, uint32_t mask, unsigned long long k, bool* fresh)
+{
+    uint32_t h = pc_hash(k, mask);
+    for (uint32_t probe = 0; probe <= mask; ++probe) {
+        const unsigned long long prev = atomicCAS(&keys[h], 0ull, k);
+        if (prev == 0ull || prev == k) {
+            *fresh = prev == 0ull;
+            return h;
+        }
+        h = (h + 1u) & mask;
+    }
+    return ~0u;
+}
+
+// one thread per point; pts: n points of `stride` floats, x y z first
+__global__ void __launch_bounds__(kPcBlock) k_map_integrate(const float* __restrict__ pts, uint32_t stride, uint32_t n, MapPose T,
+                                                            double leaf, uint32_t serial, MapTable t, unsigned long long* __restrict__ ctr)
+{
+    const uint32_t i = blockIdx.x * kPcBlock + threadIdx.x;
+    bool ok = false, fresh = false, full = false;
+    if (i < n) {
+        const float* p = pts + (size_t)i * stride;
+        const double x = (double)p[0], y = (double)p[1], z = (double)p[2];
+        const double X = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
+        const double Y = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
+        const double Z = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
+        int cx, cy, cz;
+        unsigned long long Fx, Fy, Fz;
+        if (map_axis(X, leaf, &cx, &Fx) && map_axis(Y, leaf, &cy, &Fy) && map_axis(Z, leaf, &cz, &Fz)) {
+            const uint32_t slot = map_slot(t.keys, (1u << t.cap_log2) - 1u, pc_key(cx, cy, cz), &fresh);
+            if (slot == ~0u) {
+                full = true;
+            } else {
+                ok = true;
+                atomicAdd(&t.n[slot], 1u);
+                atomicAdd(&t.sums[3 * (size_t)slot + 0], Fx);
+                atomicAdd(&t.sums[3 * (size_t)slot + 1], Fy);
+                atomicAdd(&t.sums[3 * (size_t)slot + 2], Fz);
+                if (atomicExch(&t.stamp[slot], serial) != serial) atomicAdd(&t.windows[slot], 1u);
+            }
+        }
+    }
+    // the counters: one atomic per wave and counter (every lane of the workgroup arrives here)
+    const unsigned long long b_new = __ballot(fresh), b_ok = __ballot(ok), b_rej = __ballot(i < n && !ok && !full), b_full = __ballot(full);
+    if ((threadIdx.x & 63) == 0) {
+        if (b_new) atomicAdd(&ctr[0], (unsigned long long)__popcll(b_new));
+        if (b_ok) atomicAdd(&ctr[1], (unsigned long long)__popcll(b_ok));
+        if (b_rej) atomicAdd(&ctr[2], (unsigned long long)__popcll(b_rej));
+        if (b_full) atomicAdd(&ctr[3], (unsigned long long)__popcll(b_full));
+    }
+}
+
+// every occupied slot of `from` with its state into `to` (zeroed, larger): one thread per old slot, keys are distinct
+__global__ void __launch_bounds__(kPcBlock) k_map_rehash(MapTable from, MapTable to, unsigned long long* __restrict__ ctr)
+{
+    const size_t i = (size_t)blockIdx.x * kPcBlock + threadIdx.x;
+    if (i >= ((size_t)1 << from.cap_log2)) return;
+    const unsigned long long k = from.keys[i];
+    if (k == 0ull) return;
+    bool fresh;
+    const uint32_t slot = map_slot(to.keys, (1u << to.cap_log2) - 1u, k, &fresh);
+    if (slot == ~0u) {
+        atomicAdd(&ctr[3], 1ull);
+        return;
+    }
+    to.n[slot] = from.n[i];
+    to.windows[slot] = from.windows[i];
+    to.stamp[slot] = from.stamp[i];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) to.sums[3 * (size_t)slot + a] = from.sums[3 * i + a];
+}
+
+__device__ inline bool map_passes(const MapTable& t, size_t i, uint32_t min_points, uint32_t min_windows)
+{
+    return i < ((size_t)1 << t.cap_log2) && t.keys[i] != 0ull && t.n[i] >= min_points && t.windows[i] >= min_windows;
+}
+
+// blk[b] = number of slots in [b * kPcBlock, (b + 1) * kPcBlock) that hold a cell passing the filter
+__global__ void __launch_bounds__(kPcBlock) k_map_flag_count(MapTable t, uint32_t min_points, uint32_t min_windows, uint32_t* __restrict__ blk)
+{
+    const bool f = map_passes(t, (size_t)blockIdx.x * kPcBlock + threadIdx.x, min_points, min_windows);
+    uint32_t total;
+    (void)pc_block_exclusive(f ? 1u : 0u, &total);
+    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+}
+
+// cell blk_off[block] + rank of the output, in slot order: centroid m = ((double) c + (double) (S / n) * 2^-32) * leaf per
+// axis (the bracket is exact: 21 + 32 bits), stored as float
+__global__ void __launch_bounds__(kPcBlock) k_map_extract(MapTable t, uint32_t min_points, uint32_t min_windows, double leaf,
+                                                          const uint32_t* __restrict__ blk_off, float* __restrict__ xyz,
+                                                          uint32_t* __restrict__ n_out, uint32_t* __restrict__ w_out,
+                                                          unsigned long long* __restrict__ key_out)
+{
+    const size_t i = (size_t)blockIdx.x * kPcBlock + threadIdx.x;
+    const bool f = map_passes(t, i, min_points, min_windows);
+    uint32_t total;
+    const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);
+    if (!f) return;
+    const size_t o = (size_t)blk_off[blockIdx.x] + rank;
+    const unsigned long long k = t.keys[i];
+    const uint32_t n = t.n[i];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const int c = (int)((k >> (21 * a)) & 0x1fffffull) - (kPcCellMax + 1);
+        const unsigned long long Q = t.sums[3 * i + a] / (unsigned long long)n;
+        xyz[3 * o + a] = (float)(((double)c + (double)Q * 0x1p-32) * leaf);
+    }
+    n_out[o] = n;
+    w_out[o] = t.windows[i];
+    key_out[o] = k;
+}
+
+}  // namespace
+
+size_t map_table_bytes(uint32_t cap_log2) { return ((size_t)1 << cap_log2) * (4 * sizeof(unsigned long long) + 3 * sizeof(uint32_t)); }
+
+MapTable map_table_at(void* block, uint32_t cap_log2)
+{
+    const size_t cap = (size_t)1 << cap_log2;
+    MapTable t;
+    t.keys = static_cast<unsigned long long*>(block);
+    t.sums = t.keys + cap;
+    t.n = reinterpret_cast<uint32_t*>(t.sums + 3 * cap);
+    t.windows = t.n + cap;
+    t.stamp = t.windows + cap;
+    t.cap_log2 = cap_log2;
+    return t;
+}
+
+hipError_t launch_map_integrate(hipStream_t s, const float* pts, uint32_t stride, uint32_t n, const double T_w_rv[12], double leaf,
+                                uint32_t serial, const MapTable& t, unsigned long long* ctr)
+{
+    if (n == 0) return hipSuccess;
+    MapPose T;
+    for (int k = 0; k < 12; ++k) T.m[k] = T_w_rv[k];
+    hipLaunchKernelGGL(k_map_integrate, dim3(pc_blocks(n)), dim3(kPcBlock), 0, s, pts, stride, n, T, leaf, serial, t, ctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_rehash(hipStream_t s, const MapTable& from, const MapTable& to, unsigned long long* ctr)
+{
+    hipLaunchKernelGGL(k_map_rehash, dim3(pc_blocks((size_t)1 << from.cap_log2)), dim3(kPcBlock), 0, s, from, to, ctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_count(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, uint32_t* blk, uint32_t* tiles)
+{
+    const uint32_t nb = pc_blocks((size_t)1 << t.cap_log2);
+    hipLaunchKernelGGL(k_map_flag_count, dim3(nb), dim3(kPcBlock), 0, s, t, min_points, min_windows, blk);
+    return pc_scan(s, blk, nb, tiles);
+}
+
+hipError_t launch_map_extract(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, double leaf,
+                              const uint32_t* blk, float* xyz, uint32_t* n_out, uint32_t* w_out, unsigned long long* key_out)
+{
+    const uint32_t nb = pc_blocks((size_t)1 << t.cap_log2);
+    hipLaunchKernelGGL(k_map_extract, dim3(nb), dim3(kPcBlock), 0, s, t, min_points, min_windows, leaf, blk, xyz, n_out, w_out, key_out);
+    return hipExtGetLastError();
+}
+
 // ---- focus-based collapses of a DSI (cartesian3dgrid.cpp:139-483; DESIGN.md "Focus-based collapses") ----
 //
 // Every z-slice of the volume is filtered by a 2-D separable stencil (Sobel, Laplacian, Gaussian) and a focus value

@@ -64,6 +64,11 @@ class _PointCloudOptions(C.Structure):
     _fields_ = [("radius_search", C.c_float), ("min_num_neighbors", C.c_int)]
 
 
+class _MapInfo(C.Structure):
+    _fields_ = [("leaf", C.c_double), ("capacity", C.c_uint64), ("occupied", C.c_uint64), ("calls", C.c_uint64),
+                ("accepted", C.c_uint64), ("rejected", C.c_uint64), ("growths", C.c_uint64)]
+
+
 class _ScatterPlan(C.Structure):
     _fields_ = [("q", C.c_int), ("own_begin", C.c_int), ("own_count", C.c_int), ("tail_begin", C.c_int),
                 ("tail_count", C.c_int)]
@@ -232,6 +237,15 @@ def load_library():
         "dsi_mapper_get_pointcloud": (C.c_int, [vp, f32p, u8p, C.POINTER(_PointCloudOptions), f32p, C.c_size_t, szp,
                                                 szp]),
         "dsi_radius_outlier_removal": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, C.c_float, C.c_int, u8p]),
+        "dsi_invert_pose": (C.c_int, [f64p, f64p]),
+        "dsi_map_create": (C.c_int, [vp, C.c_double, C.c_int, C.POINTER(vp)]),
+        "dsi_map_destroy": (C.c_int, [vp]),
+        "dsi_map_reset": (C.c_int, [vp]),
+        "dsi_map_integrate": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, f64p, szp]),
+        "dsi_map_integrate_mapper": (C.c_int, [vp, vp, C.POINTER(_PointCloudOptions), f64p, szp, szp]),
+        "dsi_map_info": (C.c_int, [vp, C.POINTER(_MapInfo)]),
+        "dsi_map_count": (C.c_int, [vp, C.c_uint32, C.c_uint32, szp]),
+        "dsi_map_extract": (C.c_int, [vp, C.c_uint32, C.c_uint32, f32p, u32p, u32p, u64p, C.c_size_t, szp]),
         "dsi_event_image": (C.c_int, [vp, u16p, u16p, u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, u8p, szp]),
         "dsi_event_image_dev": (C.c_int, [vp, u16p, u16p, u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, vp]),
         "dsi_batch_event_image": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_int, u8p, szp]),
@@ -950,6 +964,115 @@ def radius_outlier_removal(ctx, xyz, radius, min_neighbors):
     _check(load_library().dsi_radius_outlier_removal(ctx._h, _ptr(xyz, C.c_float), xyz.shape[1], n, C.c_float(radius),
                                                      int(min_neighbors), _ptr(keep, C.c_uint8)))
     return keep.astype(bool)
+
+
+def pose_matrix(pose):
+    """A pose as the 12 doubles, row-major [R | t], that the world map takes: a 7-vector (tx, ty, tz, qw, qx, qy, qz) --
+    the form process.py's reference views have -- or anything of 12 numbers (3 x 4, or 4 x 4 without its last row)."""
+    p = np.asarray(pose, np.float64)
+    if p.shape == (4, 4):
+        p = p[:3]
+    if p.size == 12:
+        return np.ascontiguousarray(p.reshape(12))
+    if p.shape != (7,):
+        raise ValueError("a pose is 7 numbers (t, q) or a 3 x 4 matrix")
+    w, x, y, z = p[3:]
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                  [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                  [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+    return np.ascontiguousarray(np.concatenate([R, p[:3, None]], axis=1).reshape(12))
+
+
+def invert_pose(T):
+    """The inverse of a rigid pose (dsi_invert_pose, the routine dsi::invert_pose calls too): T as pose_matrix takes it,
+    the result 12 doubles, row-major [R | t], with R' = R^T and t'_i = -((r0i t0 + r1i t1) + r2i t2) in double without
+    FMA.  Turns a window's T_rv_w into the T_w_rv that WorldMap.integrate takes."""
+    T = pose_matrix(T)
+    out = np.empty(12, np.float64)
+    _check(load_library().dsi_invert_pose(_ptr(T, C.c_double), _ptr(out, C.c_double)))
+    return out
+
+
+class WorldMap:
+    """A persistent world-frame map on the device (dsi_map_*): every integrate call moves one window's cloud
+    from its reference view to the world frame with T_w_rv and merges it into cubic cells of edge `leaf` -- a centroid
+    per cell as PCL's VoxelGrid gives, the number of points and the number of calls (windows) that reached the cell.
+    The cell sums are 64-bit fixed point: the map's bits depend neither on the order of the points nor on how they are
+    split into calls nor on the table's size (tests/world_map_reference.py restates the arithmetic).  capacity_log2: the
+    initial table of 2**capacity_log2 slots (8..27); it doubles by itself."""
+
+    def __init__(self, ctx, leaf, capacity_log2=16):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        _check(load_library().dsi_map_create(ctx._h, float(leaf), int(capacity_log2), C.byref(self._h)))
+        _track(self)
+
+    def integrate(self, xyz, T_w_rv):
+        """One call (window) of host points: xyz (N, 3) or (N, 4) float32, x y z first (a getPointcloud result as it is);
+        T_w_rv as pose_matrix takes it.  N = 0 still counts as a call.  Returns the number of points rejected (not
+        finite in the world frame, or beyond +-(2**20 - 2) cells)."""
+        xyz = _arr(xyz, np.float32)
+        if xyz.ndim != 2 or xyz.shape[1] not in (3, 4):
+            raise ValueError("xyz must be (N, 3) or (N, 4)")
+        T = pose_matrix(T_w_rv)
+        rej = C.c_size_t()
+        _check(load_library().dsi_map_integrate(self._h, _ptr(xyz, C.c_float), xyz.shape[1], xyz.shape[0], _ptr(T, C.c_double),
+                                                C.byref(rej)))
+        return rej.value
+
+    def integrate_mapper(self, mapper, T_w_rv, options_pc=None):
+        """One call of the cloud mapper.getPointcloud(options_pc=options_pc) would return -- the filtered maps the last
+        getDepthMapFromDSI(..., options_depth_map) / filterDepthMap left on the device -- without bringing it to the
+        host.  The mapper must live on the map's context.  Returns (points in the cloud, points rejected)."""
+        o = options_pc or OptionsPointCloud()
+        opts = _PointCloudOptions(o.radius_search_, o.min_num_neighbors_)
+        T = pose_matrix(T_w_rv)
+        n, rej = C.c_size_t(), C.c_size_t()
+        _check(load_library().dsi_map_integrate_mapper(self._h, mapper._h, C.byref(opts), _ptr(T, C.c_double), C.byref(n),
+                                                       C.byref(rej)))
+        return n.value, rej.value
+
+    def count(self, min_points=1, min_windows=1):
+        n = C.c_size_t()
+        _check(load_library().dsi_map_count(self._h, int(min_points), int(min_windows), C.byref(n)))
+        return n.value
+
+    def extract(self, min_points=1, min_windows=1, sort=True):
+        """The cells with at least min_points points, seen in at least min_windows calls: dict of xyz (M, 3) float32
+        centroids, n and windows (uint32) and keys (uint64, the packed cell coordinates).  sort=True orders them by
+        ascending key on the host (reproducible files); otherwise the order is the table's.  For a PCD file:
+        io.save_pcd_ascii(path, np.column_stack([xyz, windows])) writes the window count as the intensity."""
+        L = load_library()
+        n = C.c_size_t()
+        _check(L.dsi_map_count(self._h, int(min_points), int(min_windows), C.byref(n)))
+        m = n.value
+        out = {"xyz": np.empty((m, 3), np.float32), "n": np.empty(m, np.uint32), "windows": np.empty(m, np.uint32),
+               "keys": np.empty(m, np.uint64)}
+        _check(L.dsi_map_extract(self._h, int(min_points), int(min_windows), _ptr(out["xyz"], C.c_float), _ptr(out["n"], C.c_uint32),
+                                 _ptr(out["windows"], C.c_uint32), _ptr(out["keys"], C.c_uint64), m, C.byref(n)))
+        if sort:
+            order = np.argsort(out["keys"], kind="stable")
+            out = {k: v[order] for k, v in out.items()}
+        return out
+
+    def info(self):
+        """dict of leaf, capacity (slots), occupied (cells), calls, accepted, rejected (points) and growths (doublings)."""
+        i = _MapInfo()
+        _check(load_library().dsi_map_info(self._h, C.byref(i)))
+        out = {k: int(getattr(i, k)) for k in ("capacity", "occupied", "calls", "accepted", "rejected", "growths")}
+        out["leaf"] = float(i.leaf)
+        return out
+
+    def reset(self):
+        _check(load_library().dsi_map_reset(self._h))
+
+    def close(self):
+        if self._h:
+            load_library().dsi_map_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        _safe_del(self)
 
 
 def _polarity_bytes(polarity, n, use_polarity):

@@ -251,7 +251,9 @@ def save_pcd_ascii(path, points):
     TYPE F F F F, COUNT 1 1 1 1, WIDTH N, HEIGHT 1, VIEWPOINT 0 0 0 1 0 0 0 (the cloud's default sensor pose), POINTS N,
     DATA ascii, then one line per point, the four values at 8 significant digits (the default precision of
     savePCDFileASCII; an ostream's default float format, i.e. %.8g; NaN as "nan").  UNPINNED: restated from PCL's
-    documentation of the format, not compared with PCL's own output.  points: (N, >= 4) array, x y z intensity first."""
+    documentation of the format, not compared with PCL's own output.  points: (N, >= 4) array, x y z intensity first.
+    A world map (engine.WorldMap.extract) goes through as np.column_stack([cells["xyz"], cells["windows"]]): the number of
+    windows that saw the cell as the intensity (counts below 2^24 are exact in float32)."""
     pts = np.asarray(points, np.float32)
     if pts.size == 0:
         pts = pts.reshape(0, 4)

@@ -586,6 +586,7 @@ class WindowStream:
                            for k in range(depth)] if self.process_method != 1 and self.camera_time else []
         self.k = 0
         self.voted = 0
+        self.T_rv_w = [None] * depth   # per slot: the reference view of the window submitted into it (7-vector)
         self._pins = {}     # (slot, camera) -> page-locked (Rt, packet_first) staging of asynchronous uploads
 
     def _staging(self, slot, c, n_packets):
@@ -612,10 +613,12 @@ class WindowStream:
             if batches is not None or asynchronous or rv_pos != 0.0:
                 raise ValueError("batches, asynchronous and rv_pos apply to process_method 1 only (Alg. 2 cuts and packetises "
                                  "its sub-intervals itself; its reference view is the left camera, process2.cpp:79-81)")
+            self.T_rv_w[slot] = reference_view_process2(trajectories[0], ts)
             self._submit_alg2(slot, ctx, mappers, events, trajectories, ts)
             self.k += 1
             return slot
         T_rv_w = reference_view_process1(trajectories[0], ts, rv_pos)
+        self.T_rv_w[slot] = T_rv_w
         own, fused_batches, all_batches = [], [], []
         for c in range(2):
             if batches is not None:
@@ -743,7 +746,7 @@ class WindowStream:
 def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop_time_s, duration,
                   out_skip, fusion_method=E.FUSE_HM, forward_looking=True, rv_pos=0.0, options_depth_map=None,
                   options_point_cloud=None, polarities=None, save_images=False, out_path=None, lut=None, score=None,
-                  ground_truth=None, ground_truth_disparity=None, thicken_edges=False, **kw):
+                  ground_truth=None, ground_truth_disparity=None, thicken_edges=False, world_map=None, **kw):
     """Generator over the windows of main.cpp:177-302: yields (ts, depth, confidence, indices) per
     window, pipelined one window deep; with options_depth_map, (ts, depth_map, confidence_map, mask)
     -- the filtered outputs the reference saves per window; with options_point_cloud as well, the window's
@@ -775,7 +778,17 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
     nearest_ground_truth picks the frame -- a window whose nearest frame is 0.1 or more away is not scored, as the script
     skips it --, the projector makes its depth map and the score reads it where it lies: 2 bytes per pixel travel.
     thicken_edges=True (this path only): the window's depth map and mask go through engine.thicken_edges first, the
-    script's switch of that name (:75-79)."""
+    script's switch of that name (:75-79).
+    world_map= (an engine.WorldMap of `ctx`; needs options_depth_map and options_point_cloud): every window's cloud -- the
+    one this generator yields, for process_method 2 / 5 the time_camera output's -- is also merged into the map where it
+    lies on the device (WorldMap.integrate_mapper) with T_w_rv = engine.invert_pose(the window's T_rv_w), before the
+    window is yielded: the reference views differ per window, the map is in the world frame.  What is yielded does not
+    change.  The map lives on one context, so concurrent=True (a context per window in flight) is refused."""
+    if world_map is not None:
+        if options_point_cloud is None:
+            raise ValueError("world_map needs options_depth_map and options_point_cloud: the map is made of the windows' clouds")
+        if kw.get("concurrent"):
+            raise ValueError("world_map lives on one context: concurrent=True gives every window in flight its own")
     if ground_truth is not None and ground_truth_disparity is not None:
         raise ValueError("ground_truth and ground_truth_disparity exclude each other")
     if thicken_edges and ground_truth_disparity is None:
@@ -817,10 +830,10 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
                                                     cams[0]) for c in range(2)]       # cam0.fullResolution(), :246
             slot = ws.submit(ev, trajectories, ts, rv_pos)
             if pending is not None:
-                yield _window_result(ws, pending, options_depth_map, options_point_cloud, images, scoring)
-            pending = (ts, slot, event_images)
+                yield _window_result(ws, pending, options_depth_map, options_point_cloud, images, scoring, world_map)
+            pending = (ts, slot, event_images, ws.T_rv_w[slot])
         if pending is not None:
-            yield _window_result(ws, pending, options_depth_map, options_point_cloud, images, scoring)
+            yield _window_result(ws, pending, options_depth_map, options_point_cloud, images, scoring, world_map)
     finally:
         ws.close()
 
@@ -845,8 +858,10 @@ def nearest_ground_truth(gt_times, t, max_dt=0.1):
     return None if abs(float(gt_times[i]) - float(t)) >= max_dt else i
 
 
-def _window_result(ws, pending, options_depth_map, options_point_cloud, images=None, scoring=None):
+def _window_result(ws, pending, options_depth_map, options_point_cloud, images=None, scoring=None, world_map=None):
     out = ws.fetch(pending[1], options_depth_map, options_point_cloud)
+    if world_map is not None:       # (the filtered maps of the window are still on the device: fetch left them there)
+        world_map.integrate_mapper(ws.extract[pending[1]], E.invert_pose(pending[3]), options_point_cloud)
     if scoring is not None and scoring[1] is not None:
         gt = scoring[1](pending[0])
         if gt is not None:

@@ -984,6 +984,65 @@ DSI_API int dsi_mapper_create_with_lens(dsi_context_t *ctx, const dsi_mapper_con
 DSI_API int dsi_radius_outlier_removal(dsi_context_t *ctx, const float *xyz_host, size_t stride_floats, size_t n,
                                        float radius, int min_neighbors, uint8_t *keep_host);
 
+/* ---- the world map: per-window point clouds fused in a voxel hash on the device (definitions: DESIGN.md 7j) ----
+ * A map lives on the device of its context and persists across windows.  Every integrate call moves a cloud from its
+ * reference view to the world frame and merges it into cubic cells of edge `leaf`: a centroid per cell (what PCL's
+ * VoxelGrid gives), the number of points and the number of CALLS (windows) that reached the cell.
+ * THE ARITHMETIC (double, every product and sum rounded on its own, no FMA).  A point is float32 (x, y, z); the pose
+ * T_w_rv is 12 doubles, row-major [R | t]:
+ *   1. X = ((r00 x + r01 y) + r02 z) + t0, Y and Z alike with rows 1 and 2;
+ *   2. per axis q = X / leaf, c = floor(q), f = q - c, F = (uint64) floor(f * 2^32).  f is exact and in [0, 1) except for
+ *      -2^-54 < q < 0, where q + 1 rounds to 1 and F = 2^32: the cell's upper face;
+ *   3. a point is REJECTED (counted, nothing else changes) when X, Y or Z is not finite or some |c| > 2^20 - 2;
+ *   4. per cell: n (u32) accepted points, S[3] (u64) the sums of F, windows (u32) the integrate calls that put at least
+ *      one accepted point into the cell;
+ *   5. on extraction, per axis Q = S / n (integer division), m = ((double) c + (double) Q * 2^-32) * leaf -- the bracket is
+ *      exact -- and the output is (float) m;
+ *   6. the cell key is (cx + 2^20 - 1) | (cy + 2^20 - 1) << 21 | (cz + 2^20 - 1) << 42.
+ * All of a cell's state is integer sums: the map's bits depend neither on the order of the points, nor on how they are
+ * split into calls (windows does, by its definition), nor on the table's size.  The table grows by itself (doubling,
+ * while occupied cells + points of the call > 3/4 of the slots) up to 2^27 slots; a call that would need more returns
+ * DSI_ERR_INVALID and leaves the map as it was.  Nothing is ever dropped silently.  All calls run on the context's stream. */
+typedef struct dsi_map dsi_map_t;
+typedef struct dsi_map_info {
+    double leaf;
+    uint64_t capacity;   /* slots of the table now */
+    uint64_t occupied;   /* cells */
+    uint64_t calls;      /* integrate calls since creation / reset (empty ones included) */
+    uint64_t accepted;   /* points merged */
+    uint64_t rejected;   /* points rejected by rule 3 */
+    uint64_t growths;    /* doublings of the table since creation / reset */
+} dsi_map_info_t;
+/* Host only: the inverse of a rigid pose of 12 doubles, row-major [R | t]: R' = R^T, t'_i = -((r0i t0 + r1i t1) + r2i t2)
+ * (doubles, no FMA) -- T_rv_w to the T_w_rv the integrate calls take.  out may be T itself. */
+DSI_API int dsi_invert_pose(const double T[12], double out[12]);
+/* leaf: finite and > 0; capacity_log2: the initial table, 2^8 .. 2^27 slots of 44 bytes.  DSI_ERR_INVALID otherwise. */
+DSI_API int dsi_map_create(dsi_context_t *ctx, double leaf, int capacity_log2, dsi_map_t **out);
+DSI_API int dsi_map_destroy(dsi_map_t *map);
+/* an empty map again: no cells, every count of dsi_map_info zero; the table keeps its present size */
+DSI_API int dsi_map_reset(dsi_map_t *map);
+/* One call (window) of n host points, stride_floats = 3 or 4 floats per point (x, y, z first), by rules 1-4 above.
+ * n = 0 is legal (xyz_host may then be NULL) and still counts as a call.  *n_rejected (may be NULL): the points of this
+ * call rejected by rule 3.  Synchronises. */
+DSI_API int dsi_map_integrate(dsi_map_t *map, const float *xyz_host, size_t stride_floats, size_t n,
+                              const double T_w_rv[12], size_t *n_rejected);
+/* One call of the mapper's own cloud: the points dsi_mapper_get_pointcloud(m, NULL, NULL, opts_pc, ...) returns -- made by
+ * the same routine from the filtered maps left on the device, with the same refusals -- integrated where they lie, by
+ * rules 1-4; only the counts travel.  *n_points / *n_rejected may be NULL.  DSI_ERR_CONTEXT when the map and the mapper
+ * were created from different contexts.  Synchronises. */
+DSI_API int dsi_map_integrate_mapper(dsi_map_t *map, dsi_mapper_t *m, const dsi_pointcloud_options_t *opts_pc,
+                                     const double T_w_rv[12], size_t *n_points, size_t *n_rejected);
+DSI_API int dsi_map_info(dsi_map_t *map, dsi_map_info_t *info);
+/* the number of cells with n >= min_points and windows >= min_windows (rule 4's counts).  Synchronises. */
+DSI_API int dsi_map_count(dsi_map_t *map, uint32_t min_points, uint32_t min_windows, size_t *n);
+/* Those cells: centroid by rule 5 (xyz_host, 3 floats per cell), n, windows and key (rule 6); any output may be NULL.
+ * The order is the table's -- unspecified, but the same for every call while the map is unchanged; sort by key for a
+ * reproducible one.  When capacity < *n nothing is written, *n is the size needed and the call returns DSI_ERR_INVALID
+ * (dsi_mapper_get_pointcloud's protocol).  Synchronises. */
+DSI_API int dsi_map_extract(dsi_map_t *map, uint32_t min_points, uint32_t min_windows, float *xyz_host,
+                            uint32_t *n_points_host, uint32_t *n_windows_host, uint64_t *keys_host, size_t capacity,
+                            size_t *n);
+
 /* HIP-event stopwatch around the voting kernel (the replacement of fillVoxelGrid's hot
  * loop, mapper_emvs_stereo.cpp:168-203) on the context's stream: enable, run any number of
  * evaluate/fill calls, then read the summed kernel time and launch count (synchronises and

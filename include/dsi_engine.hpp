@@ -20,6 +20,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -1546,6 +1547,110 @@ public:
 
 private:
     dsi_score_t* h_ = nullptr;
+};
+
+// A rigid pose as the 12 doubles, row-major [R | t], that the world map takes
+inline std::array<double, 12> pose_matrix(const Transformation& T)
+{
+    const double w = T.q[0], x = T.q[1], y = T.q[2], z = T.q[3];
+    return {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), T.t[0],
+            2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x), T.t[1],
+            2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y), T.t[2]};
+}
+// its inverse (dsi_invert_pose, the routine the Python binding calls too): R' = R^T, t'_i = -((r0i t0 + r1i t1) + r2i t2) --
+// a window's T_rv_w to the T_w_rv that WorldMap::integrate takes
+inline std::array<double, 12> invert_pose(const std::array<double, 12>& T)
+{
+    std::array<double, 12> out;
+    check(dsi_invert_pose(T.data(), out.data()));
+    return out;
+}
+inline std::array<double, 12> invert_pose(const Transformation& T) { return invert_pose(pose_matrix(T)); }
+
+// A persistent world-frame map on the device (dsi_map_*): every integrate call moves one window's cloud from
+// its reference view to the world frame and merges it into cubic cells of edge `leaf` -- a centroid per cell (PCL's
+// VoxelGrid), the number of points and the number of calls (windows) that reached the cell.  The arithmetic is stated in
+// dsi_engine.h; the map's bits depend neither on the order of the points nor on how they are split into calls.
+struct WorldMapCells {  // by ascending key when sorted
+    std::vector<float> xyz;  // 3 per cell
+    std::vector<uint32_t> n, windows;
+    std::vector<uint64_t> keys;
+    size_t size() const { return keys.size(); }
+};
+class WorldMap {
+public:
+    WorldMap(Context& ctx, double leaf, int capacity_log2 = 16) : ctx_(ctx) { check(dsi_map_create(ctx.handle(), leaf, capacity_log2, &h_)); }
+    ~WorldMap() { dsi_map_destroy(h_); }
+    WorldMap(const WorldMap&) = delete;
+    WorldMap& operator=(const WorldMap&) = delete;
+    dsi_map_t* handle() const { return h_; }
+    Context& context() const { return ctx_; }
+
+    // one call of n host points, stride 3 or 4 floats (x, y, z first); returns the number of points rejected
+    size_t integrate(const float* xyz, size_t stride_floats, size_t n, const std::array<double, 12>& T_w_rv)
+    {
+        size_t rejected = 0;
+        check(dsi_map_integrate(h_, xyz, stride_floats, n, T_w_rv.data(), &rejected));
+        return rejected;
+    }
+    size_t integrate(const PointCloud& pc, const std::array<double, 12>& T_w_rv)
+    {
+        static_assert(sizeof(PointXYZI) == 4 * sizeof(float), "PointXYZI is x, y, z, intensity");
+        return integrate(pc.points.empty() ? nullptr : &pc.points[0].x, 4, pc.points.size(), T_w_rv);
+    }
+    // one call of the cloud mapper.getPointcloud(options_pc, cloud) would return, where it lies on the device; the mapper
+    // must live on the map's context.  Returns the number of points rejected; *n_points: the cloud's size.
+    template <typename MapperT, typename OptionsT>
+    size_t integrateMapper(MapperT& mapper, const OptionsT& options_pc, const std::array<double, 12>& T_w_rv, size_t* n_points = nullptr)
+    {
+        dsi_pointcloud_options_t o{};
+        o.radius_search = options_pc.radius_search_;
+        o.min_num_neighbors = options_pc.min_num_neighbors_;
+        size_t n = 0, rejected = 0;
+        check(dsi_map_integrate_mapper(h_, mapper.handle(), &o, T_w_rv.data(), &n, &rejected));
+        if (n_points) *n_points = n;
+        return rejected;
+    }
+    size_t count(uint32_t min_points = 1, uint32_t min_windows = 1) const
+    {
+        size_t n = 0;
+        check(dsi_map_count(h_, min_points, min_windows, &n));
+        return n;
+    }
+    // the cells with n >= min_points and windows >= min_windows; sort: by ascending key (reproducible files)
+    WorldMapCells extract(uint32_t min_points = 1, uint32_t min_windows = 1, bool sort = true) const
+    {
+        WorldMapCells raw;
+        size_t n = count(min_points, min_windows);
+        raw.xyz.resize(3 * n);
+        raw.n.resize(n);
+        raw.windows.resize(n);
+        raw.keys.resize(n);
+        check(dsi_map_extract(h_, min_points, min_windows, raw.xyz.data(), raw.n.data(), raw.windows.data(), raw.keys.data(), n, &n));
+        if (!sort) return raw;
+        std::vector<size_t> order(n);
+        for (size_t i = 0; i < n; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return raw.keys[a] < raw.keys[b]; });
+        WorldMapCells out;
+        for (size_t i : order) {
+            out.xyz.insert(out.xyz.end(), raw.xyz.begin() + 3 * i, raw.xyz.begin() + 3 * i + 3);
+            out.n.push_back(raw.n[i]);
+            out.windows.push_back(raw.windows[i]);
+            out.keys.push_back(raw.keys[i]);
+        }
+        return out;
+    }
+    dsi_map_info_t info() const
+    {
+        dsi_map_info_t i;
+        check(dsi_map_info(h_, &i));
+        return i;
+    }
+    void reset() { check(dsi_map_reset(h_)); }
+
+private:
+    Context& ctx_;
+    dsi_map_t* h_ = nullptr;
 };
 
 }  // namespace dsi

@@ -496,6 +496,19 @@ private:
     std::thread th_;  // (last: the thread starts when every other member exists)
 };
 
+// world_map (optional, on both streams): every window's cloud also goes into the map on the device, moved to the world
+// frame with T_w_rv = invert_pose(the window's T_rv_w) (for Alg. 2: the time_camera output's cloud).  The map lives on one
+// context, so every slot then works on the map's context -- one stream, the windows one after the other on the GPU -- and
+// `devices` must name the map's device alone.  Needs options_point_cloud.  What on_window receives does not change.
+inline void check_world_map(const WorldMap* world_map, const std::vector<int>& devices, const EMVS::OptionsPointCloud* options_point_cloud)
+{
+    if (!world_map) return;
+    if (!options_point_cloud) throw Error(DSI_ERR_INVALID, "full_sequence_depth_maps: world_map needs options_point_cloud (and options_depth_map)");
+    for (int dev : devices)
+        if (dev != dsi_context_device(world_map->context().handle()))
+            throw Error(DSI_ERR_CONTEXT, "full_sequence_depth_maps: world_map lives on one device: `devices` must name that one alone");
+}
+
 // devices: slot k (window k, k + depth, ...) lives on devices[k % devices.size()] -- windows are independent (fresh
 // mappers per window in the reference, main.cpp:262-275), so several GPUs of a node take them in turn, no collective
 // ("replicas"); depth >= devices.size() to use them all.
@@ -508,7 +521,8 @@ inline size_t full_sequence_depth_maps(const std::vector<int>& devices, const Pi
                                        OnWindow&& on_window, int depth = 2, double rv_pos = 0.0,
                                        const EMVS::OptionsDepthMap* options_depth_map = nullptr,
                                        WindowStreamStats* stats = nullptr,
-                                       const EMVS::OptionsPointCloud* options_point_cloud = nullptr)
+                                       const EMVS::OptionsPointCloud* options_point_cloud = nullptr,
+                                       WorldMap* world_map = nullptr)
 {
     using clock = std::chrono::steady_clock;
     const clock::time_point t_call = clock::now();
@@ -520,8 +534,10 @@ inline size_t full_sequence_depth_maps(const std::vector<int>& devices, const Pi
     if (options_point_cloud && !options_depth_map)
         throw Error(DSI_ERR_INVALID, "full_sequence_depth_maps: the point cloud is made of the filtered maps: options_point_cloud "
                                      "needs options_depth_map");
+    check_world_map(world_map, devices, options_point_cloud);
     struct Slot {
-        Context ctx;
+        std::unique_ptr<Context> own;  // (none with a world map: the map lives on ONE context, every slot works there)
+        Context& ctx;
         EMVS::MapperEMVS m0, m1, out;
         dsi_batch_t* batch[2] = {nullptr, nullptr};
         void* host[3] = {nullptr, nullptr, nullptr};  // page-locked depth, confidence, indices
@@ -534,8 +550,8 @@ inline size_t full_sequence_depth_maps(const std::vector<int>& devices, const Pi
         size_t np[2] = {0, 0};
         int prc[2] = {DSI_OK, DSI_OK};
         bool busy = false;
-        Slot(int dev, const PinholeCameraModel& c0, const PinholeCameraModel& c1, const EMVS::ShapeDSI& sh)
-            : ctx(dev), m0(ctx, c0, sh), m1(ctx, c1, sh), out(ctx, c0, sh) {}
+        Slot(int dev, Context* shared, const PinholeCameraModel& c0, const PinholeCameraModel& c1, const EMVS::ShapeDSI& sh)
+            : own(shared ? nullptr : new Context(dev)), ctx(shared ? *shared : *own), m0(ctx, c0, sh), m1(ctx, c1, sh), out(ctx, c0, sh) {}
         ~Slot()
         {
             if (busy) dsi_mapper_fetch_wait(out.handle());
@@ -567,7 +583,7 @@ inline size_t full_sequence_depth_maps(const std::vector<int>& devices, const Pi
         }
     };
     std::vector<std::unique_ptr<Slot>> slots;
-    for (int k = 0; k < depth; ++k) slots.emplace_back(new Slot(devices[(size_t)k % devices.size()], cam0, cam1, dsi_shape));
+    for (int k = 0; k < depth; ++k) slots.emplace_back(new Slot(devices[(size_t)k % devices.size()], world_map ? &world_map->context() : nullptr, cam0, cam1, dsi_shape));
     int nx = 0, ny = 0, nz = 0;
     slots[0]->out.dsi_.getDimensions(&nx, &ny, &nz);
     const size_t npix = (size_t)nx * ny;
@@ -605,6 +621,8 @@ inline size_t full_sequence_depth_maps(const std::vector<int>& devices, const Pi
             s.out.filterDepthMap(s.w.filtered_depth_map, s.w.filtered_confidence_map, s.w.semidense_mask, *options_depth_map);
         if (options_point_cloud)  // ... and the point cloud is made of the filtered maps the filters left there
             s.out.getPointcloud(*options_point_cloud, s.w.point_cloud);
+        if (world_map)  // ... and goes into the world map where it lies, through T_w_rv = T_rv_w^-1
+            world_map->integrateMapper(s.out, *options_point_cloud, invert_pose(s.w.T_rv_w));
         on_window(static_cast<const WindowDepthMap&>(s.w));
         st.deliver_ms += since(t0);
     };
@@ -742,12 +760,13 @@ inline size_t full_sequence_depth_maps(int device, const PinholeCameraModel& cam
                                        OnWindow&& on_window, int depth = 2, double rv_pos = 0.0,
                                        const EMVS::OptionsDepthMap* options_depth_map = nullptr,
                                        WindowStreamStats* stats = nullptr,
-                                       const EMVS::OptionsPointCloud* options_point_cloud = nullptr)
+                                       const EMVS::OptionsPointCloud* options_point_cloud = nullptr,
+                                       WorldMap* world_map = nullptr)
 {
     return full_sequence_depth_maps(std::vector<int>{device}, cam0, cam1, dsi_shape, trajectory0, trajectory1, events0, events1,
                                     start_time_s, stop_time_s, duration, out_skip, forward_looking, fusion_method,
                                     std::forward<OnWindow>(on_window), depth, rv_pos, options_depth_map, stats,
-                                    options_point_cloud);
+                                    options_point_cloud, world_map);
 }
 
 }  // namespace dsi
@@ -1111,7 +1130,8 @@ inline size_t full_sequence_depth_maps_alg2(const std::vector<int>& devices, con
                                             bool forward_looking, const Alg2Options& alg2, OnWindow&& on_window, int depth = 2,
                                             const EMVS::OptionsDepthMap* options_depth_map = nullptr,
                                             WindowStreamStats* stats = nullptr,
-                                            const EMVS::OptionsPointCloud* options_point_cloud = nullptr)
+                                            const EMVS::OptionsPointCloud* options_point_cloud = nullptr,
+                                            WorldMap* world_map = nullptr)
 {
     using clock = std::chrono::steady_clock;
     const clock::time_point t_call = clock::now();
@@ -1127,9 +1147,11 @@ inline size_t full_sequence_depth_maps_alg2(const std::vector<int>& devices, con
     if (devices.empty()) throw Error(DSI_ERR_INVALID, "full_sequence_depth_maps_alg2: no device");
     if (options_point_cloud && !options_depth_map)
         throw Error(DSI_ERR_INVALID, "full_sequence_depth_maps_alg2: options_point_cloud needs options_depth_map");
+    check_world_map(world_map, devices, options_point_cloud);
     const size_t nb = 2 * (size_t)n_sub;
     struct Slot {
-        Context ctx;
+        std::unique_ptr<Context> own;  // (none with a world map: every slot works on the map's context)
+        Context& ctx;
         EMVS::MapperEMVS m0, m1, out, out_ct;
         std::vector<dsi_batch_t*> batch;
         void* host[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};  // page-locked maps per output
@@ -1140,8 +1162,8 @@ inline size_t full_sequence_depth_maps_alg2(const std::vector<int>& devices, con
         std::vector<int> prc;
         WindowDepthMapsAlg2 w, next;
         bool busy = false, fused = true, next_fused = true;
-        Slot(int dev, const PinholeCameraModel& c0, const PinholeCameraModel& c1, const EMVS::ShapeDSI& sh, size_t nb)
-            : ctx(dev), m0(ctx, c0, sh), m1(ctx, c1, sh), out(ctx, c0, sh), out_ct(ctx, c0, sh), batch(nb, nullptr),
+        Slot(int dev, Context* shared, const PinholeCameraModel& c0, const PinholeCameraModel& c1, const EMVS::ShapeDSI& sh, size_t nb)
+            : own(shared ? nullptr : new Context(dev)), ctx(shared ? *shared : *own), m0(ctx, c0, sh), m1(ctx, c1, sh), out(ctx, c0, sh), out_ct(ctx, c0, sh), batch(nb, nullptr),
               ev_off(nb), ev_n(nb), pk_off(nb), np(nb), prc(nb, DSI_OK) {}
         ~Slot()
         {
@@ -1181,7 +1203,7 @@ inline size_t full_sequence_depth_maps_alg2(const std::vector<int>& devices, con
         }
     };
     std::vector<std::unique_ptr<Slot>> slots;
-    for (int k = 0; k < depth; ++k) slots.emplace_back(new Slot(devices[(size_t)k % devices.size()], cam0, cam1, dsi_shape, nb));
+    for (int k = 0; k < depth; ++k) slots.emplace_back(new Slot(devices[(size_t)k % devices.size()], world_map ? &world_map->context() : nullptr, cam0, cam1, dsi_shape, nb));
     int nx = 0, ny = 0, nz = 0;
     slots[0]->out.dsi_.getDimensions(&nx, &ny, &nz);
     const size_t npix = (size_t)nx * ny;
@@ -1222,6 +1244,7 @@ inline size_t full_sequence_depth_maps_alg2(const std::vector<int>& devices, con
             fill(w.depth_cell_indices, s.host[o][2]);
             if (options_depth_map) ms[o]->filterDepthMap(w.filtered_depth_map, w.filtered_confidence_map, w.semidense_mask, *options_depth_map);
             if (options_point_cloud) ms[o]->getPointcloud(*options_point_cloud, w.point_cloud);
+            if (world_map && o == 0) world_map->integrateMapper(*ms[o], *options_point_cloud, invert_pose(w.T_rv_w));
         }
         s.w.has_camera_time = ct;
         on_window(static_cast<const WindowDepthMapsAlg2&>(s.w));
@@ -1411,11 +1434,13 @@ inline size_t full_sequence_depth_maps_alg2(int device, const PinholeCameraModel
                                             double duration, double out_skip, bool forward_looking, const Alg2Options& alg2,
                                             OnWindow&& on_window, int depth = 2, const EMVS::OptionsDepthMap* options_depth_map = nullptr,
                                             WindowStreamStats* stats = nullptr,
-                                            const EMVS::OptionsPointCloud* options_point_cloud = nullptr)
+                                            const EMVS::OptionsPointCloud* options_point_cloud = nullptr,
+                                            WorldMap* world_map = nullptr)
 {
     return full_sequence_depth_maps_alg2(std::vector<int>{device}, cam0, cam1, dsi_shape, trajectory0, trajectory1, events0,
                                          events1, start_time_s, stop_time_s, duration, out_skip, forward_looking, alg2,
-                                         std::forward<OnWindow>(on_window), depth, options_depth_map, stats, options_point_cloud);
+                                         std::forward<OnWindow>(on_window), depth, options_depth_map, stats, options_point_cloud,
+                                         world_map);
 }
 
 }  // namespace dsi
