@@ -14,6 +14,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -4203,11 +4204,30 @@ struct dsi_map {
     DevBuf<float> upload, xyz;           // a call's host points; the extraction's outputs
     DevBuf<uint32_t> blk, tiles, n_out, w_out;
     DevBuf<unsigned long long> key_out;
+    // the last render (dsi_map_render): valid until the map changes
+    DevBuf<unsigned long long> zkey, render_ctr;
+    DevBuf<uint32_t> hits, render_windows;
+    DevBuf<float> render_depth;
+    DevBuf<uint8_t> render_mask;
+    int render_width = 0, render_height = 0;
+    bool render_valid = false;
 };
 
 namespace {
 
 constexpr int kMapMinLog2 = 8, kMapMaxLog2 = 27;
+constexpr int kMapViewMaxLog2 = 26, kMapMaxSplat = 4;
+
+void map_render_release(dsi_map* mp)
+{
+    mp->zkey.release();
+    mp->hits.release();
+    mp->render_windows.release();
+    mp->render_depth.release();
+    mp->render_mask.release();
+    mp->render_width = mp->render_height = 0;
+    mp->render_valid = false;
+}
 
 void map_free(dsi_map* mp)
 {
@@ -4220,6 +4240,8 @@ void map_free(dsi_map* mp)
     mp->n_out.release();
     mp->w_out.release();
     mp->key_out.release();
+    map_render_release(mp);
+    mp->render_ctr.release();
     delete mp;
 }
 
@@ -4250,6 +4272,7 @@ int map_grow_for(dsi_map* mp, size_t n)
 // one integrate call of n device points (stride floats each) on the map's stream; synchronises
 int map_integrate_device(dsi_map* mp, const float* pts_dev, size_t stride, size_t n, const double T_w_rv[12], size_t* n_rejected)
 {
+    mp->render_valid = false;  // (the map may change from here on)
     REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
     REQUIRE(mp->calls < 0xffffffffull, DSI_ERR_INVALID, "at most 2^32 - 1 integrate calls per map");
     REQUIRE((mp->host_ctr[0] + n) * 4 <= ((uint64_t)3 << kMapMaxLog2), DSI_ERR_INVALID,
@@ -4342,6 +4365,7 @@ int dsi_map_destroy(dsi_map_t* mp)
 int dsi_map_reset(dsi_map_t* mp)
 {
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    mp->render_valid = false;
     if (int rc = set_device(mp->ctx)) return rc;
     HIP_TRY(hipMemsetAsync(mp->block, 0, dsi::map_table_bytes(mp->cap_log2), mp->ctx->stream));
     HIP_TRY(hipMemsetAsync(mp->ctr, 0, sizeof mp->host_ctr, mp->ctx->stream));
@@ -4420,6 +4444,116 @@ int dsi_map_extract(dsi_map_t* mp, uint32_t min_points, uint32_t min_windows, fl
     if (keys_host) HIP_TRY(hipMemcpyAsync(keys_host, mp->key_out.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return DSI_OK;
+}
+
+int dsi_map_render(dsi_map_t* mp, const dsi_map_view_t* view, dsi_map_render_info_t* info)
+{
+    // (the view first: its bounds can then be exercised without a device, with no map at hand)
+    REQUIRE(view, DSI_ERR_INVALID, "view is null");
+    REQUIRE(view->width >= 1 && view->height >= 1, DSI_ERR_INVALID, "the view must be at least 1 x 1 (got %d x %d)", view->width,
+            view->height);
+    REQUIRE((uint64_t)view->width * (uint64_t)view->height <= ((uint64_t)1 << kMapViewMaxLog2), DSI_ERR_INVALID,
+            "a view holds at most 2^%d pixels (got %d x %d)", kMapViewMaxLog2, view->width, view->height);
+    REQUIRE(view->splat >= 0 && view->splat <= kMapMaxSplat, DSI_ERR_INVALID, "splat must be in 0..%d (got %d)", kMapMaxSplat,
+            view->splat);
+    REQUIRE(std::isfinite(view->fx) && std::isfinite(view->fy) && view->fx != 0.0 && view->fy != 0.0, DSI_ERR_INVALID,
+            "fx and fy must be finite and not 0 (got %g, %g)", view->fx, view->fy);
+    REQUIRE(std::isfinite(view->cx) && std::isfinite(view->cy), DSI_ERR_INVALID, "cx and cy must be finite (got %g, %g)", view->cx,
+            view->cy);
+    REQUIRE(std::isfinite(view->min_depth) && std::isfinite(view->max_depth) && view->min_depth >= (double)FLT_MIN &&
+                view->min_depth < view->max_depth && view->max_depth <= (double)FLT_MAX,
+            DSI_ERR_INVALID, "the depth range must satisfy FLT_MIN <= min_depth < max_depth <= FLT_MAX (got %g, %g)", view->min_depth,
+            view->max_depth);
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    if (int rc = set_device(mp->ctx)) return rc;
+    hipStream_t st = mp->ctx->stream;
+    const size_t npix = (size_t)view->width * (size_t)view->height;
+    mp->render_valid = false;
+    if (npix != (size_t)mp->render_width * (size_t)mp->render_height) {
+        HIP_TRY(hipStreamSynchronize(st));
+        map_render_release(mp);
+    }
+    HIP_TRY(mp->zkey.reserve(npix));
+    HIP_TRY(mp->hits.reserve(npix));
+    HIP_TRY(mp->render_windows.reserve(npix));
+    HIP_TRY(mp->render_depth.reserve(npix));
+    HIP_TRY(mp->render_mask.reserve(npix));
+    HIP_TRY(mp->render_ctr.reserve(dsi::kMapRenderCounters));
+    mp->render_width = view->width;
+    mp->render_height = view->height;
+    dsi::MapView v;
+    std::memcpy(v.T, view->T_v_w, sizeof v.T);
+    v.fx = view->fx, v.fy = view->fy, v.cx = view->cx, v.cy = view->cy;
+    v.min_depth = view->min_depth, v.max_depth = view->max_depth;
+    v.width = view->width, v.height = view->height, v.splat = view->splat;
+    v.min_points = view->min_points, v.min_windows = view->min_windows;
+    const dsi::MapImage img{mp->zkey.p, mp->hits.p, mp->render_windows.p, mp->render_depth.p, mp->render_mask.p};
+    unsigned long long ctr[dsi::kMapRenderCounters] = {0, 0, 0, 0, 0};
+    HIP_TRY(dsi::launch_map_render(st, dsi::map_table_at(mp->block, mp->cap_log2), v, mp->leaf, img, mp->render_ctr.p));
+    HIP_TRY(hipMemcpyAsync(ctr, mp->render_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    mp->render_valid = true;
+    if (info) {
+        info->width = view->width;
+        info->height = view->height;
+        info->n_cells = ctr[0];
+        info->n_clipped = ctr[1];
+        info->n_outside = ctr[2];
+        info->n_drawn = ctr[3];
+        info->n_pixels = ctr[4];
+    }
+    return DSI_OK;
+}
+
+namespace {
+
+int map_render_check(const dsi_map* mp)
+{
+    REQUIRE(mp->render_valid, DSI_ERR_INVALID,
+            "no render of the map as it stands: call dsi_map_render (after the last dsi_map_reset or integrate call)");
+    return DSI_OK;
+}
+
+}  // namespace
+
+int dsi_map_render_fetch(dsi_map_t* mp, float* depth_host, uint32_t* windows_host, uint32_t* hits_host, uint8_t* mask_host)
+{
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    if (int rc = map_render_check(mp)) return rc;
+    if (int rc = set_device(mp->ctx)) return rc;
+    hipStream_t st = mp->ctx->stream;
+    const size_t npix = (size_t)mp->render_width * (size_t)mp->render_height;
+    if (depth_host) HIP_TRY(hipMemcpyAsync(depth_host, mp->render_depth.p, npix * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (windows_host) HIP_TRY(hipMemcpyAsync(windows_host, mp->render_windows.p, npix * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (hits_host) HIP_TRY(hipMemcpyAsync(hits_host, mp->hits.p, npix * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (mask_host) HIP_TRY(hipMemcpyAsync(mask_host, mp->render_mask.p, npix, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+int dsi_score_add_map_render(dsi_score_t* s, dsi_map_t* mp, const float* gt_host)
+{
+    REQUIRE(s && mp && gt_host, DSI_ERR_INVALID, "null argument");
+    REQUIRE(mp->ctx == s->ctx, DSI_ERR_CONTEXT, "map and score belong to different contexts");
+    if (int rc = map_render_check(mp)) return rc;
+    if (int rc = set_device(s->ctx)) return rc;
+    const size_t npix = (size_t)mp->render_width * (size_t)mp->render_height;
+    HIP_TRY(s->gt.reserve(npix));
+    HIP_TRY(hipMemcpyAsync(s->gt.p, gt_host, npix * sizeof(float), hipMemcpyHostToDevice, s->ctx->stream));
+    return score_add_device(s, mp->render_depth.p, mp->render_mask.p, s->gt.p, npix);
+}
+
+int dsi_score_add_map_render_gt(dsi_score_t* s, dsi_map_t* mp, dsi_gt_t* gt)
+{
+    REQUIRE(s && mp && gt, DSI_ERR_INVALID, "null argument");
+    REQUIRE(mp->ctx == s->ctx, DSI_ERR_CONTEXT, "map and score belong to different contexts");
+    REQUIRE(gt->ctx == s->ctx, DSI_ERR_CONTEXT, "projector and score belong to different contexts");
+    if (int rc = map_render_check(mp)) return rc;
+    const size_t npix = (size_t)mp->render_width * (size_t)mp->render_height;
+    REQUIRE(npix == gt_npix(gt), DSI_ERR_INVALID, "the render holds %d x %d pixels, the projector's map %d x %d", mp->render_width,
+            mp->render_height, gt->width, gt->height);
+    if (int rc = set_device(s->ctx)) return rc;
+    return score_add_device(s, mp->render_depth.p, mp->render_mask.p, gt_out(gt), npix);
 }
 
 int dsi_mapper_last_vote_info(const dsi_mapper_t* m, dsi_vote_info_t* info)

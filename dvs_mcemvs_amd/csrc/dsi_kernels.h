@@ -353,7 +353,23 @@ hipError_t launch_map_count(hipStream_t s, const MapTable& t, uint32_t min_point
 // after launch_map_count with the same filter: the cells in slot order -- centroid (3 floats), n, windows, key
 hipError_t launch_map_extract(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, double leaf,
                               const uint32_t* blk, float* xyz, uint32_t* n_out, uint32_t* w_out, unsigned long long* key_out);
-
+// the map rendered into a pinhole view (dsi_map_render; DESIGN.md 7j "Rendering"); the host has checked every bound of v
+struct MapView {
+    double T[12];  // world -> view, row-major [R | t]
+    double fx, fy, cx, cy, min_depth, max_depth;
+    int width, height, splat;
+    uint32_t min_points, min_windows;
+};
+// 21 bytes per pixel: zkey / hits are the render's working state, depth / windows / mask what the finish pass unpacks
+struct MapImage {
+    unsigned long long* zkey;
+    uint32_t *hits, *windows;
+    float* depth;
+    uint8_t* mask;
+};
+constexpr int kMapRenderCounters = 5;  // cells that passed the filter, clipped, outside, drawn, covered pixels
+// clears zkey (all ones), hits and ctr, draws every cell that passes v's filter and unpacks the image; ctr: kMapRenderCounters u64
+hipError_t launch_map_render(hipStream_t s, const MapTable& t, const MapView& v, double leaf, const MapImage& img, unsigned long long* ctr);
 
 // focus-based collapses (Grid3D::collapseZSliceBy*, cartesian3dgrid.cpp:192-414; DESIGN.md "Focus-based collapses"):
 // method 0 LocalVar, 1 LocalMeanSquare, 2 GradMag (half_patchsize 0..8), 3 LaplacianMag, 4 DoG.  keys: scratch of

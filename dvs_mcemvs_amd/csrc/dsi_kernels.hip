@@ -6882,6 +6882,15 @@ __device__ inline bool map_passes(const MapTable& t, size_t i, uint32_t min_poin
     return i < ((size_t)1 << t.cap_log2) && t.keys[i] != 0ull && t.n[i] >= min_points && t.windows[i] >= min_windows;
 }
 
+// axis a of the centroid of slot i (key k, n points): m = ((double) c + (double) (S / n) * 2^-32) * leaf (the bracket is
+// exact: 21 + 32 bits), as float -- the one expression that extraction and rendering share
+__device__ inline float map_centroid(const MapTable& t, size_t i, unsigned long long k, uint32_t n, int a, double leaf)
+{
+    const int c = (int)((k >> (21 * a)) & 0x1fffffull) - (kPcCellMax + 1);
+    const unsigned long long Q = t.sums[3 * i + a] / (unsigned long long)n;
+    return (float)(((double)c + (double)Q * 0x1p-32) * leaf);
+}
+
 // blk[b] = number of slots in [b * kPcBlock, (b + 1) * kPcBlock) that hold a cell passing the filter
 __global__ void __launch_bounds__(kPcBlock) k_map_flag_count(MapTable t, uint32_t min_points, uint32_t min_windows, uint32_t* __restrict__ blk)
 {
@@ -6891,8 +6900,7 @@ __global__ void __launch_bounds__(kPcBlock) k_map_flag_count(MapTable t, uint32_
     if (threadIdx.x == 0) blk[blockIdx.x] = total;
 }
 
-// cell blk_off[block] + rank of the output, in slot order: centroid m = ((double) c + (double) (S / n) * 2^-32) * leaf per
-// axis (the bracket is exact: 21 + 32 bits), stored as float
+// cell blk_off[block] + rank of the output, in slot order: centroid (map_centroid) per axis
 __global__ void __launch_bounds__(kPcBlock) k_map_extract(MapTable t, uint32_t min_points, uint32_t min_windows, double leaf,
                                                           const uint32_t* __restrict__ blk_off, float* __restrict__ xyz,
                                                           uint32_t* __restrict__ n_out, uint32_t* __restrict__ w_out,
@@ -6907,14 +6915,115 @@ __global__ void __launch_bounds__(kPcBlock) k_map_extract(MapTable t, uint32_t m
     const unsigned long long k = t.keys[i];
     const uint32_t n = t.n[i];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const int c = (int)((k >> (21 * a)) & 0x1fffffull) - (kPcCellMax + 1);
-        const unsigned long long Q = t.sums[3 * i + a] / (unsigned long long)n;
-        xyz[3 * o + a] = (float)(((double)c + (double)Q * 0x1p-32) * leaf);
-    }
+    for (int a = 0; a < 3; ++a) xyz[3 * o + a] = map_centroid(t, i, k, n, a, leaf);
     n_out[o] = n;
     w_out[o] = t.windows[i];
     key_out[o] = k;
+}
+
+// The map as a pinhole camera at v.T (world -> view) sees it: a pass over the table's SLOTS, no compaction.  A cell that
+// passes the filter is its extracted centroid (float, widened to double); X = ((r00 x + r01 y) + r02 z) + t0 and Y, Z
+// alike; CLIPPED when X, Y or Z is not finite or not min_depth <= Z <= max_depth (NaN fails); u = (fx * (X / Z)) + cx,
+// iu = floor(u + 0.5), v / iv alike; the footprint is the (2 splat + 1)^2 pixels around (iu, iv), each tested against the
+// image on its own; OUTSIDE when none is inside.  Per footprint pixel: hits += 1 and
+// zkey = min(zkey, bits((float) Z) << 32 | ~windows) -- Z > 0, so the bits order as the value; equal float depths go to
+// the cell seen by more windows.  zkey starts at all ones, hits at 0 (the host's two memsets).  Integer atomics on
+// initialised words only: the image depends neither on the thread order nor on the table's size nor on the probing.
+// ctr: [0] cells that passed the filter, [1] clipped, [2] outside, [3] drawn.
+// The image tests are made in double before anything becomes an integer: iu + dx with |dx| <= splat <= 4 is inside
+// [0, width) for some dx iff -splat <= iu <= width - 1 + splat, which huge, infinite and NaN values fail; past that test
+// iu is an integer in [-4, 2^26 + 3] and the per-pixel tests are exact in int.
+// At most kMapRenderMaxBlocks workgroups walk the table in strides (the capacity is a multiple of the workgroup, so every
+// lane of a wave takes part in every ballot; at most 2^27 / (1024 * 256) = 512 rounds): a wave keeps its four counts in
+// uniform registers, adds them to LDS once, and the workgroup issues one global atomic per counter.  One thread per slot
+// with one global atomic per wave and counter was bound by exactly those atomics -- 98 k of them on one cache line for a
+// table of 2^21 slots, at the 83 per microsecond one line takes.
+constexpr uint32_t kMapRenderMaxBlocks = 1024;
+
+__global__ void __launch_bounds__(kPcBlock) k_map_render(MapTable t, MapView v, double leaf, unsigned long long* __restrict__ zkey,
+                                                         uint32_t* __restrict__ hits, unsigned long long* __restrict__ ctr)
+{
+    __shared__ uint32_t s_cnt[4];
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    uint32_t c_f = 0, c_clip = 0, c_out = 0, c_draw = 0;  // (the same in every lane of a wave)
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        const bool f = map_passes(t, i, v.min_points, v.min_windows);
+        bool clipped = false, outside = false;
+        if (f) {
+            const unsigned long long k = t.keys[i];
+            const uint32_t n = t.n[i];
+            const double x = (double)map_centroid(t, i, k, n, 0, leaf), y = (double)map_centroid(t, i, k, n, 1, leaf),
+                         z = (double)map_centroid(t, i, k, n, 2, leaf);
+            const double X = ((v.T[0] * x + v.T[1] * y) + v.T[2] * z) + v.T[3];
+            const double Y = ((v.T[4] * x + v.T[5] * y) + v.T[6] * z) + v.T[7];
+            const double Z = ((v.T[8] * x + v.T[9] * y) + v.T[10] * z) + v.T[11];
+            if (!(isfinite(X) && isfinite(Y) && Z >= v.min_depth && Z <= v.max_depth)) {  // (min/max_depth are finite)
+                clipped = true;
+            } else {
+                const double du = floor(((v.fx * (X / Z)) + v.cx) + 0.5), dv = floor(((v.fy * (Y / Z)) + v.cy) + 0.5);
+                const double s = (double)v.splat;
+                if (!(du >= -s && du <= (double)(v.width - 1) + s && dv >= -s && dv <= (double)(v.height - 1) + s)) {
+                    outside = true;
+                } else {
+                    const int iu = (int)du, iv = (int)dv;
+                    const unsigned long long key =
+                        ((unsigned long long)__float_as_uint((float)Z) << 32) | (unsigned long long)(0xffffffffu - t.windows[i]);
+                    const int y0 = max(iv - v.splat, 0), y1 = min(iv + v.splat, v.height - 1);
+                    const int x0 = max(iu - v.splat, 0), x1 = min(iu + v.splat, v.width - 1);
+                    for (int py = y0; py <= y1; ++py)
+                        for (int px = x0; px <= x1; ++px) {
+                            const size_t p = (size_t)py * (size_t)v.width + (size_t)px;
+                            atomicMin(&zkey[p], key);
+                            atomicAdd(&hits[p], 1u);
+                        }
+                }
+            }
+        }
+        c_f += (uint32_t)__popcll(__ballot(f));
+        c_clip += (uint32_t)__popcll(__ballot(clipped));
+        c_out += (uint32_t)__popcll(__ballot(outside));
+        c_draw += (uint32_t)__popcll(__ballot(f && !clipped && !outside));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (c_f) atomicAdd(&s_cnt[0], c_f);
+        if (c_clip) atomicAdd(&s_cnt[1], c_clip);
+        if (c_out) atomicAdd(&s_cnt[2], c_out);
+        if (c_draw) atomicAdd(&s_cnt[3], c_draw);
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
+// the winner's key unpacked per pixel -- depth = (float) Z and windows where hits > 0, zeros elsewhere, mask = hits > 0;
+// ctr[4] += covered pixels.  Strided and counted like k_map_render: one global atomic per workgroup.
+__global__ void __launch_bounds__(kPcBlock) k_map_render_finish(const unsigned long long* __restrict__ zkey,
+                                                                const uint32_t* __restrict__ hits, uint32_t npix,
+                                                                float* __restrict__ depth, uint32_t* __restrict__ windows,
+                                                                uint8_t* __restrict__ mask, unsigned long long* __restrict__ ctr)
+{
+    __shared__ uint32_t s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0u;
+    __syncthreads();
+    uint32_t c = 0;
+    const uint32_t stride = gridDim.x * kPcBlock;  // (<= 2^18; npix <= 2^26: base cannot wrap)
+    for (uint32_t base = blockIdx.x * kPcBlock; base < npix; base += stride) {
+        const uint32_t i = base + threadIdx.x;
+        bool covered = false;
+        if (i < npix) {
+            covered = hits[i] > 0u;
+            const unsigned long long k = zkey[i];
+            depth[i] = covered ? __uint_as_float((uint32_t)(k >> 32)) : 0.f;
+            windows[i] = covered ? 0xffffffffu - (uint32_t)k : 0u;
+            mask[i] = covered ? 1 : 0;
+        }
+        c += (uint32_t)__popcll(__ballot(covered));
+    }
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt, c);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt) atomicAdd(&ctr[4], (unsigned long long)s_cnt);
 }
 
 }  // namespace
@@ -6962,6 +7071,20 @@ hipError_t launch_map_extract(hipStream_t s, const MapTable& t, uint32_t min_poi
 {
     const uint32_t nb = pc_blocks((size_t)1 << t.cap_log2);
     hipLaunchKernelGGL(k_map_extract, dim3(nb), dim3(kPcBlock), 0, s, t, min_points, min_windows, leaf, blk, xyz, n_out, w_out, key_out);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_render(hipStream_t s, const MapTable& t, const MapView& v, double leaf, const MapImage& img, unsigned long long* ctr)
+{
+    const size_t npix = (size_t)v.width * (size_t)v.height;
+    hipError_t e = hipMemsetAsync(img.zkey, 0xff, npix * sizeof(unsigned long long), s);
+    if (e == hipSuccess) e = hipMemsetAsync(img.hits, 0, npix * sizeof(uint32_t), s);
+    if (e == hipSuccess) e = hipMemsetAsync(ctr, 0, kMapRenderCounters * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_map_render, dim3(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s, t, v,
+                       leaf, img.zkey, img.hits, ctr);
+    hipLaunchKernelGGL(k_map_render_finish, dim3(std::min(pc_blocks(npix), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s, img.zkey,
+                       img.hits, (uint32_t)npix, img.depth, img.windows, img.mask, ctr);
     return hipExtGetLastError();
 }
 

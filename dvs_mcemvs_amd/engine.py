@@ -69,6 +69,17 @@ class _MapInfo(C.Structure):
                 ("accepted", C.c_uint64), ("rejected", C.c_uint64), ("growths", C.c_uint64)]
 
 
+class _MapView(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("splat", C.c_int32), ("min_points", C.c_uint32),
+                ("min_windows", C.c_uint32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("min_depth", C.c_double), ("max_depth", C.c_double), ("T_v_w", C.c_double * 12)]
+
+
+class _MapRenderInfo(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_cells", C.c_uint64), ("n_clipped", C.c_uint64),
+                ("n_outside", C.c_uint64), ("n_drawn", C.c_uint64), ("n_pixels", C.c_uint64)]
+
+
 class _ScatterPlan(C.Structure):
     _fields_ = [("q", C.c_int), ("own_begin", C.c_int), ("own_count", C.c_int), ("tail_begin", C.c_int),
                 ("tail_count", C.c_int)]
@@ -246,6 +257,10 @@ def load_library():
         "dsi_map_info": (C.c_int, [vp, C.POINTER(_MapInfo)]),
         "dsi_map_count": (C.c_int, [vp, C.c_uint32, C.c_uint32, szp]),
         "dsi_map_extract": (C.c_int, [vp, C.c_uint32, C.c_uint32, f32p, u32p, u32p, u64p, C.c_size_t, szp]),
+        "dsi_map_render": (C.c_int, [vp, C.POINTER(_MapView), C.POINTER(_MapRenderInfo)]),
+        "dsi_map_render_fetch": (C.c_int, [vp, f32p, u32p, u32p, u8p]),
+        "dsi_score_add_map_render": (C.c_int, [vp, vp, f32p]),
+        "dsi_score_add_map_render_gt": (C.c_int, [vp, vp, vp]),
         "dsi_event_image": (C.c_int, [vp, u16p, u16p, u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, u8p, szp]),
         "dsi_event_image_dev": (C.c_int, [vp, u16p, u16p, u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, vp]),
         "dsi_batch_event_image": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_int, u8p, szp]),
@@ -999,7 +1014,8 @@ class WorldMap:
     per cell as PCL's VoxelGrid gives, the number of points and the number of calls (windows) that reached the cell.
     The cell sums are 64-bit fixed point: the map's bits depend neither on the order of the points nor on how they are
     split into calls nor on the table's size (tests/world_map_reference.py restates the arithmetic).  capacity_log2: the
-    initial table of 2**capacity_log2 slots (8..27); it doubles by itself."""
+    initial table of 2**capacity_log2 slots (8..27); it doubles by itself.  render() gives the depth image the map presents
+    to a camera, for DepthScore.addMapRender and renderImage."""
 
     def __init__(self, ctx, leaf, capacity_log2=16):
         self.ctx = ctx
@@ -1062,6 +1078,52 @@ class WorldMap:
         out = {k: int(getattr(i, k)) for k in ("capacity", "occupied", "calls", "accepted", "rejected", "growths")}
         out["leaf"] = float(i.leaf)
         return out
+
+    def render(self, T_v_w, width, height, fx, fy, cx, cy, min_depth, max_depth, splat=0, min_points=1, min_windows=1,
+               fetch=True):
+        """The depth image the map presents to a pinhole camera (dsi_map_render; DESIGN.md 7j "Rendering"): every cell
+        that passes extract()'s filter is projected through T_v_w (world -> view, as pose_matrix takes it; invert_pose
+        makes it from the camera's pose in the world) and the nearest one per pixel is kept; a cell is drawn on the
+        (2 splat + 1)^2 pixels around its own.  Integer pixel coordinates are pixel centres.  Returns the counts n_cells
+        (passed the filter) = n_clipped + n_outside + n_drawn, n_pixels (covered), width and height, and with fetch=True
+        the images (height, width): depth float32 (0 where empty), windows uint32 (the winner's window count), hits uint32
+        (cells drawn on the pixel) and mask uint8.  The images stay on the device for renderImage and
+        DepthScore.addMapRender until the map changes."""
+        v = _MapView()
+        v.width, v.height, v.splat = int(width), int(height), int(splat)
+        v.min_points, v.min_windows = int(min_points), int(min_windows)
+        v.fx, v.fy, v.cx, v.cy = float(fx), float(fy), float(cx), float(cy)
+        v.min_depth, v.max_depth = float(min_depth), float(max_depth)
+        v.T_v_w[:] = pose_matrix(T_v_w).tolist()
+        i = _MapRenderInfo()
+        _check(load_library().dsi_map_render(self._h, C.byref(v), C.byref(i)))
+        self._render_shape = (int(i.height), int(i.width))
+        out = {k: int(getattr(i, k)) for k in ("width", "height", "n_cells", "n_clipped", "n_outside", "n_drawn", "n_pixels")}
+        if fetch:
+            out.update(self.fetchRender())
+        return out
+
+    def fetchRender(self):
+        """dict of depth, windows, hits and mask of the last render (dsi_map_render_fetch); raises DsiError when the map
+        changed since, or was never rendered."""
+        shape = getattr(self, "_render_shape", (0, 0))
+        out = {"depth": np.empty(shape, np.float32), "windows": np.empty(shape, np.uint32), "hits": np.empty(shape, np.uint32),
+               "mask": np.empty(shape, np.uint8)}
+        _check(load_library().dsi_map_render_fetch(self._h, _ptr(out["depth"], C.c_float), _ptr(out["windows"], C.c_uint32),
+                                                   _ptr(out["hits"], C.c_uint32), _ptr(out["mask"], C.c_uint8)))
+        return out
+
+    def renderImage(self, min_depth, max_depth, lut=None):
+        """The inverse-depth colour image (height, width, 3) uint8, B G R, of the last render: its depth and mask through
+        depth_images' encoder (dsi_depth_images without a confidence map)."""
+        r = self.fetchRender()
+        rows, cols = r["depth"].shape
+        lut = _lut_bytes(lut)
+        bgr = np.empty((rows, cols, 3), np.uint8)
+        _check(load_library().dsi_depth_images(self.ctx._h, _ptr(r["depth"], C.c_float), None, _ptr(r["mask"], C.c_uint8), rows, cols,
+                                               C.c_float(min_depth), C.c_float(max_depth),
+                                               None if lut is None else _ptr(lut, C.c_uint8), None, _ptr(bgr, C.c_uint8)))
+        return bgr
 
     def reset(self):
         _check(load_library().dsi_map_reset(self._h))
@@ -1229,6 +1291,18 @@ class DepthScore:
     def addMapperGroundTruth(self, mapper, projector):
         """addMapper() against the projector's depth map: both sides are on the device, nothing is uploaded."""
         _check(load_library().dsi_score_add_mapper_gt(self._h, mapper._h, projector._h))
+
+    def addMapRender(self, world_map, gt):
+        """One frame from the depth image and mask that world_map.render(...) left on the device (a WorldMap of this
+        context), against gt: a host depth map of the render's (height, width) -- only it is uploaded -- or a
+        GroundTruthProjector of that size, whose last projection is read where it lies."""
+        if isinstance(gt, GroundTruthProjector):
+            _check(load_library().dsi_score_add_map_render_gt(self._h, world_map._h, gt._h))
+            return
+        gt = _arr(gt, np.float32)
+        if gt.shape != getattr(world_map, "_render_shape", None):
+            raise ValueError("gt must have the render's (height, width) shape")
+        _check(load_library().dsi_score_add_map_render(self._h, world_map._h, _ptr(gt, C.c_float)))
 
     def reset(self):
         _check(load_library().dsi_score_reset(self._h))

@@ -858,6 +858,22 @@ def nearest_ground_truth(gt_times, t, max_dt=0.1):
     return None if abs(float(gt_times[i]) - float(t)) >= max_dt else i
 
 
+def score_world_map(world_map, score, frames, camera, min_depth, max_depth, splat=0, min_points=1, min_windows=1):
+    """Map-level metrics of a finished full_sequence(..., world_map=) run: per frame of `frames` -- (T_w_v, gt) with T_w_v
+    the camera's pose in the world (as engine.pose_matrix takes it) and gt a host depth map (height, width) or a
+    GroundTruthProjector already holding that frame -- the map is rendered into camera = (width, height, fx, fy, cx, cy) at
+    engine.invert_pose(T_w_v), without fetching the images, and added to `score` (a DepthScore of the map's context)
+    against gt.  Cells farther than max_depth or nearer than min_depth are clipped; splat, min_points, min_windows as
+    WorldMap.render takes them.  Returns the list of the frames' count dicts."""
+    width, height, fx, fy, cx, cy = camera
+    counts = []
+    for T_w_v, gt in frames:
+        counts.append(world_map.render(E.invert_pose(T_w_v), width, height, fx, fy, cx, cy, min_depth, max_depth, splat=splat,
+                                       min_points=min_points, min_windows=min_windows, fetch=False))
+        score.addMapRender(world_map, gt)
+    return counts
+
+
 def _window_result(ws, pending, options_depth_map, options_point_cloud, images=None, scoring=None, world_map=None):
     out = ws.fetch(pending[1], options_depth_map, options_point_cloud)
     if world_map is not None:       # (the filtered maps of the window are still on the device: fetch left them there)

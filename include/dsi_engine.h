@@ -1043,6 +1043,63 @@ DSI_API int dsi_map_extract(dsi_map_t *map, uint32_t min_points, uint32_t min_wi
                             uint32_t *n_points_host, uint32_t *n_windows_host, uint64_t *keys_host, size_t capacity,
                             size_t *n);
 
+/* ---- the map rendered into a camera view: a z-buffered depth image on the device (DESIGN.md 7j "Rendering") ----
+ * The depth image the map presents to a pinhole camera at an arbitrary pose: every cell projected, the nearest kept per
+ * pixel.  THE ARITHMETIC (double, every product and sum rounded on its own, no FMA), for every cell with
+ * n >= min_points && windows >= min_windows:
+ *   1. the point (x, y, z) is the cell's centroid exactly as dsi_map_extract returns it -- rule 5 above, rounded to float32 --
+ *      widened to double: rendering the map and rendering its extracted cloud are the same thing;
+ *   2. X = ((r00 x + r01 y) + r02 z) + t0, Y and Z alike with rows 1 and 2 of T_v_w;
+ *   3. the cell is CLIPPED (counted, nothing else changes) when X, Y or Z is not finite or when
+ *      Z >= min_depth && Z <= max_depth does not hold (NaN fails);
+ *   4. u = (fx * (X / Z)) + cx, v = (fy * (Y / Z)) + cy, iu = floor(u + 0.5), iv = floor(v + 0.5): integer pixel coordinates
+ *      are pixel centres (dsi_mapper_get_pointcloud's back-projection convention).  The footprint is the pixels
+ *      (iu + dx, iv + dy), |dx|, |dy| <= splat, each tested on its own against 0 <= . < width, 0 <= . < height -- in double,
+ *      before anything becomes an integer: huge, infinite and NaN coordinates are dropped, never saturated.  A cell none of
+ *      whose footprint pixels lies inside the image is OUTSIDE (counted);
+ *   5. a DRAWN cell does, per footprint pixel, hits += 1 (u32) and zkey = min(zkey, key) with
+ *      key = (uint64) bits((float) Z) << 32 | (0xFFFFFFFF - windows): Z > 0, so the float's bits order as its value, and
+ *      among cells whose float32 depths tie exactly the one seen by the most windows wins.  An empty pixel holds all ones,
+ *      which no key equals (its upper half would be a NaN);
+ *   6. the images, height x width, row-major: depth (f32) = (float) Z of the winner and 0 where hits == 0, windows (u32) the
+ *      winner's count and 0 where empty, hits (u32), mask (u8) = hits > 0.
+ * Every effect of a cell is an integer atomic on initialised memory: the images depend neither on the order of the threads,
+ * nor on the table's size, nor on where probing put a cell -- they are a function of the map (and the view) alone.
+ * tests/world_map_render_reference.py restates this in numpy. */
+typedef struct dsi_map_view {
+    int32_t width, height;        /* >= 1, width * height <= 2^26 */
+    int32_t splat;                /* 0..4: a cell is drawn on the (2 splat + 1)^2 pixels around its pixel */
+    uint32_t min_points, min_windows;   /* dsi_map_extract's filter */
+    double fx, fy, cx, cy;        /* finite, fx and fy != 0 */
+    double min_depth, max_depth;  /* finite, FLT_MIN <= min_depth < max_depth <= FLT_MAX */
+    double T_v_w[12];             /* world -> view, row-major [R | t]; dsi_invert_pose makes it from T_w_v */
+} dsi_map_view_t;
+typedef struct dsi_map_render_info {
+    int32_t width, height;
+    uint64_t n_cells;     /* passed the filter; = n_clipped + n_outside + n_drawn */
+    uint64_t n_clipped;   /* rule 3 */
+    uint64_t n_outside;   /* rule 4 */
+    uint64_t n_drawn;
+    uint64_t n_pixels;    /* pixels with hits > 0 */
+} dsi_map_render_info_t;
+/* Renders and leaves the four images on the device, in buffers that belong to the map (21 bytes per pixel, allocated on
+ * first use, reallocated when width * height changes, freed by dsi_map_destroy).  info may be NULL.  DSI_ERR_INVALID for a
+ * NULL map or view or a violated bound of dsi_map_view_t, decided before the GPU is touched.  An empty map renders an empty
+ * image.  Synchronises. */
+DSI_API int dsi_map_render(dsi_map_t *map, const dsi_map_view_t *view, dsi_map_render_info_t *info);
+/* The last render's images to the host (height * width elements each; any may be NULL).  DSI_ERR_INVALID when there is
+ * none: before the first render and after dsi_map_reset or any integrate call -- a changed map invalidates its render.
+ * Synchronises. */
+DSI_API int dsi_map_render_fetch(dsi_map_t *map, float *depth_host, uint32_t *windows_host, uint32_t *hits_host,
+                                 uint8_t *mask_host);
+/* dsi_score_add_dev of the last render's depth and mask, where they lie, against gt_host[height * width]: only the ground
+ * truth travels.  DSI_ERR_CONTEXT when score and map were created from different contexts, DSI_ERR_INVALID without a
+ * valid render.  Queued on the context's stream. */
+DSI_API int dsi_score_add_map_render(dsi_score_t *score, dsi_map_t *map, const float *gt_host);
+/* The same against the depth map the projector last made: nothing travels.  DSI_ERR_INVALID unless the render's
+ * width * height equals the projector's. */
+DSI_API int dsi_score_add_map_render_gt(dsi_score_t *score, dsi_map_t *map, dsi_gt_t *gt);
+
 /* HIP-event stopwatch around the voting kernel (the replacement of fillVoxelGrid's hot
  * loop, mapper_emvs_stereo.cpp:168-203) on the context's stream: enable, run any number of
  * evaluate/fill calls, then read the summed kernel time and launch count (synchronises and

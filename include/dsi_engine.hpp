@@ -1498,6 +1498,19 @@ public:
     {
         check(dsi_score_add_mapper_gt(h_, mapper.handle(), projector.handle()));
     }
+    // one frame from the depth image and mask that WorldMap::render left on the device, against ground_truth[height * width]
+    // of the render's size: only it is uploaded
+    template <typename MapT>
+    void addMapRender(MapT& world_map, const float* ground_truth)
+    {
+        check(dsi_score_add_map_render(h_, world_map.handle(), ground_truth));
+    }
+    // the same against a projector's depth map: nothing is uploaded
+    template <typename MapT>
+    void addMapRender(MapT& world_map, const GroundTruthProjector& projector)
+    {
+        check(dsi_score_add_map_render_gt(h_, world_map.handle(), projector.handle()));
+    }
     dsi_score_metrics_t metrics() const
     {
         dsi_score_metrics_t m;
@@ -1577,6 +1590,15 @@ struct WorldMapCells {  // by ascending key when sorted
     std::vector<uint64_t> keys;
     size_t size() const { return keys.size(); }
 };
+// a view of the map and what a render of it counts (dsi_map_view_t: size, splat, filter, fx fy cx cy, depth range, T_v_w)
+using MapView = dsi_map_view_t;
+using MapRenderInfo = dsi_map_render_info_t;
+struct MapRenderImages {  // height x width, row-major
+    int width = 0, height = 0;
+    std::vector<float> depth;
+    std::vector<uint32_t> windows, hits;
+    std::vector<uint8_t> mask;
+};
 class WorldMap {
 public:
     WorldMap(Context& ctx, double leaf, int capacity_log2 = 16) : ctx_(ctx) { check(dsi_map_create(ctx.handle(), leaf, capacity_log2, &h_)); }
@@ -1648,9 +1670,39 @@ public:
     }
     void reset() { check(dsi_map_reset(h_)); }
 
+    // the depth image the map presents to a pinhole camera (dsi_map_render; the arithmetic is stated in dsi_engine.h): the
+    // images stay on the device for fetch_render and DepthScore::addMapRender until the map changes
+    MapRenderInfo render(const MapView& view)
+    {
+        MapRenderInfo info;
+        check(dsi_map_render(h_, &view, &info));
+        width_ = info.width;
+        height_ = info.height;
+        return info;
+    }
+    // the last render's images, height * width elements each; any may be nullptr
+    void fetch_render(float* depth, uint32_t* windows = nullptr, uint32_t* hits = nullptr, uint8_t* mask = nullptr) const
+    {
+        check(dsi_map_render_fetch(h_, depth, windows, hits, mask));
+    }
+    MapRenderImages fetch_render() const
+    {
+        MapRenderImages out;
+        out.width = width_;
+        out.height = height_;
+        const size_t n = (size_t)width_ * (size_t)height_;
+        out.depth.resize(n);
+        out.windows.resize(n);
+        out.hits.resize(n);
+        out.mask.resize(n);
+        fetch_render(out.depth.data(), out.windows.data(), out.hits.data(), out.mask.data());
+        return out;
+    }
+
 private:
     Context& ctx_;
     dsi_map_t* h_ = nullptr;
+    int width_ = 0, height_ = 0;  // of the last render
 };
 
 }  // namespace dsi
