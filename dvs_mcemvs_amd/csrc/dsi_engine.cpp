@@ -5,6 +5,8 @@
 //   dsi_batch_t   <-> the (events, per-packet pose) pairs evaluateDSI iterates over
 // There is no CPU implementation behind this ABI: without a gfx950 device every
 // constructor fails with DSI_ERR_NO_DEVICE.
+// Every object owns its device memory, events and streams through the move-only members of dsi_owned.hpp: `delete obj`
+// frees them (in reverse order of declaration), a dsi_*_destroy only checks, synchronises and counts before it.
 #include "../../include/dsi_engine.h"
 
 #include <hip/hip_runtime.h>
@@ -30,6 +32,7 @@
 
 #include "dsi_host.hpp"
 #include "dsi_kernels.h"
+#include "dsi_owned.hpp"
 
 #pragma clang fp contract(off)
 
@@ -61,41 +64,10 @@ int fail(int code, const char* fmt, ...)
         if (!(cond)) return fail(code, __VA_ARGS__); \
     } while (0)
 
-// device buffer that only ever grows
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t n)
-    {
-        if (n <= cap) return hipSuccess;
-        if (p) {
-            hipError_t e = hipFree(p);  // implicit device sync
-            p = nullptr;
-            cap = 0;
-            if (e != hipSuccess) return e;
-        }
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
-template <typename T>
-struct TmpDev {  // call-scoped device memory
-    T* p = nullptr;
-    hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void**>(&p), (n ? n : 1) * sizeof(T)); }
-    ~TmpDev()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
+using dsi::DevBuf;
+using dsi::Event;
+using dsi::HostPinned;
+using dsi::Stream;
 
 // device scratch of the point-cloud path (dsi_mapper_get_pointcloud, dsi_radius_outlier_removal): grown, never shrunk
 struct PcBuffers {
@@ -119,47 +91,34 @@ struct PcBuffers {
         return hipSuccess;
     }
     dsi::PcScratch scratch() const { return dsi::PcScratch{spts.p, key.p, skey.p, slot.p, bstart.p, tiles.p}; }
-    void release()
-    {
-        depth.release();
-        mask.release();
-        pts.release();
-        spts.release();
-        out.release();
-        key.release();
-        skey.release();
-        slot.release();
-        bstart.release();
-        tiles.release();
-        blk.release();
-        blk2.release();
-        n.release();
-        keep.release();
-    }
 };
 
 }  // namespace
 
+// OWNERSHIP (here and in every object struct below): device memory, events and streams are owning members
+// (dsi_owned.hpp), freed by `delete obj`; a destroy function only synchronises before it.  Members go in reverse order
+// of declaration, so a stream is declared BEFORE whatever is recorded on it or queued to it: it is destroyed last.
 struct dsi_context {
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    std::vector<hipEvent_t> marks;  // dsi_context_timeline_mark
+    Stream stream;  // first: outlives every event and buffer below
+    // device -> host copies of depth maps that must not wait for later work of the compute stream
+    // (dsi_mapper_fetch_depth_map[_async]); created on first use
+    Stream copy_stream;
+    Event t0, t1;
+    std::vector<Event> marks;  // dsi_context_timeline_mark
     size_t n_marks = 0;
-    hipEvent_t sync_ev = nullptr;  // dsi_context_wait_for: "everything queued on this stream so far"
-    double* ms_accum = nullptr;    // device scalar for mean-square
+    Event sync_ev;  // dsi_context_wait_for: "everything queued on this stream so far"
+    DevBuf<double> ms_accum;  // device scalar for mean-square
     // Event batches are uploaded on their own stream so that the upload of the next batch (camera,
     // window) overlaps the voting of the current one; "ready" / "freed" events order the two streams.
     // ONE upload stream per device, shared by its contexts (uploads share the PCIe link anyway): the runtime maps
     // streams onto four hardware queues by default, and a pipeline of windows -- one context per window in flight --
     // that gave every context two streams of its own had its uploads queue behind another window's kernel
     // (profiles/r04_cpp_window_stream.txt: 0.41 ms per window waiting for uploads).
-    hipStream_t upload_stream = nullptr;
-    // device -> host copies of depth maps that must not wait for later work of the compute stream
-    // (dsi_mapper_fetch_depth_map[_async]); created on first use
-    hipStream_t copy_stream = nullptr;
+    hipStream_t upload_stream = nullptr;  // (not owned: upload_stream_acquire / _release)
     // Released event-batch blocks, reused by the next dsi_batch_create on this context: a stream of
-    // windows then costs no hipMalloc / hipFree (hipFree synchronises the device).
+    // windows then costs no hipMalloc / hipFree (hipFree synchronises the device).  A plain value, copied between
+    // the pool and a batch: whichever holds it frees it (pool_give's trim and ~dsi_context; dsi_batch_destroy gives it back).
     struct PoolBlock {
         void* p;
         size_t bytes;
@@ -168,8 +127,7 @@ struct dsi_context {
     std::vector<PoolBlock> batch_pool;
     // grow-only scratch of Grid3D::collapseMaxZSlice's host-output form (no hipMalloc / hipFree --
     // i.e. no device synchronisation -- per call)
-    void* collapse_scratch = nullptr;
-    size_t collapse_scratch_bytes = 0;
+    DevBuf<unsigned char> collapse_scratch;
     // focus-based collapses: one arg-max key per pixel and plane range; dsi_grid_local_focus in place: the new volume
     DevBuf<unsigned long long> focus_keys;
     DevBuf<float> focus_volume;
@@ -188,6 +146,7 @@ struct dsi_context {
     // context refuses to go while any is alive (destroying it first was a use-after-free in their destroy)
     std::atomic<int> children{0};
     PcBuffers pc;  // dsi_radius_outlier_removal
+    ~dsi_context();  // what is not an owning member: the shared upload stream and the pooled blocks
 };
 
 // the per-device upload stream (see dsi_context::upload_stream)
@@ -223,10 +182,19 @@ void upload_stream_release(int device)
     }
 }
 
+dsi_context::~dsi_context()
+{
+    if (upload_stream) upload_stream_release(device);
+    for (auto& blk : batch_pool) {
+        (void)hipFree(blk.p);
+        (void)hipEventDestroy(blk.freed);
+    }
+}
+
 hipError_t copy_stream_of(dsi_context* ctx, hipStream_t* out)
 {
     if (!ctx->copy_stream)
-        if (hipError_t e = hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking)) return e;
+        if (hipError_t e = ctx->copy_stream.create(hipStreamNonBlocking)) return e;
     *out = ctx->copy_stream;
     return hipSuccess;
 }
@@ -275,14 +243,14 @@ struct dsi_grid {
     dsi_context* ctx = nullptr;
     int nx = 0, ny = 0, nz = 0;
     size_t n = 0;
-    float* data = nullptr;
-    bool owned = false;
+    float* data = nullptr;  // the volume: `own.p`, or the caller's memory (dsi_grid_wrap), which is not freed
+    DevBuf<float> own;
 };
 
 struct dsi_batch {
     dsi_context* ctx = nullptr;
     dsi_context::PoolBlock block{nullptr, 0, nullptr};  // one device allocation holding the four arrays below
-    hipEvent_t ready = nullptr;  // recorded on the copy stream after the upload
+    Event ready;  // recorded on the copy stream after the upload
     uint16_t *x = nullptr, *y = nullptr;
     uint32_t* first = nullptr;
     float* Rt = nullptr;
@@ -307,34 +275,31 @@ struct TieScratch {
     bool interval_most_live = false;
     DevBuf<uint2> unproven;     // ... and the columns it could not prove (pixel, float bits of the gap the column needs)
     size_t n_unproven = 0;
-    unsigned* host = nullptr;  // page-locked copy of the counters: the three reads of a call are plain DMAs
+    HostPinned<unsigned> host;  // page-locked copy of the counters: the three reads of a call are plain DMAs
     hipError_t host_counters(unsigned** out)
     {
         if (!host)
-            if (hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&host), 64 * sizeof(unsigned), hipHostMallocDefault)) return e;
+            if (hipError_t e = host.alloc(64, hipHostMallocDefault)) return e;
         *out = host;
         return hipSuccess;
-    }
-    void release()
-    {
-        if (host) (void)hipHostFree(host);
-        host = nullptr;
-        cand.release(); count.release(); desc.release(); cols.release(); counters.release();
-        for (auto& v : votes) v.release();
-        unproven.release(); interval_most.release();
-        keys.release(); keys2.release(); w.release(); exact.release(); diff.release(); tmp.release();
-        rank_count.release(); rank_start.release(); rank_cursor.release();
     }
 };
 
 struct dsi_mapper {
     dsi_context* ctx = nullptr;
+    // Opt-in experiment (DSI_PREP_OVERLAP=1): stage A, the packet sort and the coefficient tables of
+    // evaluateDSI on a second stream, overlapping whatever the context's stream is still doing
+    // (typically the previous camera's voting kernel).  Measured: the voting kernel loses more
+    // (1.21 -> 1.38 ms: wave slots, LDS and L2 taken by the preparation kernels) than the overlap
+    // hides, 2.80 -> 2.92 ms per step, so it is off by default.
+    Stream prep_stream;  // (a stream: before the buffers its kernels use, see dsi_context)
+    Event ev_prep, ev_vote_done;
     TieScratch tie;
     int sensor_w = 0, sensor_h = 0;
     dsi::Geom geom{};
     std::vector<float> planes;  // raw_depths_vec_ (of the planes this mapper owns)
     std::vector<float> planes_full;  // the whole depth vector (plane-sharded arg-max: index -> depth)
-    float* planes_full_dev = nullptr;
+    DevBuf<float> planes_full_dev;
     DevBuf<unsigned long long> argmax_keys;
     DevBuf<unsigned long long> fused_keys;   // dsi_mapper_depth_map_of_events: one arg-max key per pixel, kept zero between calls
     DevBuf<unsigned long long> fused_trace;  // test hook: time stamps of the fused kernel's phases
@@ -352,16 +317,9 @@ struct dsi_mapper {
                                 // 512 x 512 x 200 -- 446 vs 447 us, the slow workgroups are slow per record, not by count)
     int want_pass_lg = 0;  // test hook: log2(packets per pass) of the packed / vector-fill streams (0 = automatic)
     int plane_begin = 0;        // first owned plane of the full depth vector (plane sharding)
-    float* planes_dev = nullptr;
-    float2* lut_dev = nullptr;
+    DevBuf<float> planes_dev;
+    DevBuf<float2> lut_dev;
     dsi_grid* grid = nullptr;
-    // Opt-in experiment (DSI_PREP_OVERLAP=1): stage A, the packet sort and the coefficient tables of
-    // evaluateDSI on a second stream, overlapping whatever the context's stream is still doing
-    // (typically the previous camera's voting kernel).  Measured: the voting kernel loses more
-    // (1.21 -> 1.38 ms: wave slots, LDS and L2 taken by the preparation kernels) than the overlap
-    // hides, 2.80 -> 2.92 ms per step, so it is off by default.
-    hipStream_t prep_stream = nullptr;
-    hipEvent_t ev_prep = nullptr, ev_vote_done = nullptr;
     bool vote_recorded = false;
     int prep_overlap = 0;
     int algo = DSI_VOTE_AUTO;
@@ -396,28 +354,19 @@ struct dsi_mapper {
         DevBuf<uint32_t> nvalid, cuts;
         DevBuf<uint16_t> rowstart;
         DevBuf<dsi::PlaneCoef> coef;
-        void release()
-        {
-            centers.release();
-            sxy.release();
-            nvalid.release();
-            cuts.release();
-            rowstart.release();
-            coef.release();
-        }
     };
-    std::vector<BatchTables> alg2_tables;
+    std::vector<BatchTables> alg2_tables;  // (resize relocates the tables: DevBuf moves)
     bool fused_keys_dirty = false;  // the fused kernel may have written keys that no unpack cleared
     // The depth map leaves the device on the context's COPY stream, so that fetching window w's map
     // does not queue behind window w+1's kernels on the compute stream: "ready" (compute stream, after
     // the arg-max) gates the copies, "read" (copy stream, after them) gates the next arg-max into the
     // same buffers.
-    hipEvent_t ev_depth_ready = nullptr, ev_depth_read = nullptr;
+    Event ev_depth_ready, ev_depth_read;
     bool depth_read_pending = false;
     // HIP-event stopwatch around the dominant (voting) kernel, for bench.py's roofline
     bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> timing_pairs;  // recorded, not yet read
-    std::vector<hipEvent_t> timing_pool;
+    std::vector<Event> timing_pairs;  // recorded, not yet read: [2 i] before and [2 i + 1] after launch i
+    std::vector<Event> timing_pool;
 };
 
 namespace {
@@ -653,21 +602,21 @@ int upload_async(dsi_context* ctx, void* dst, const void* src, size_t bytes)
     return DSI_OK;
 }
 
-hipEvent_t timing_event(dsi_mapper* m)
+Event timing_event(dsi_mapper* m)
 {
+    Event e;
     if (!m->timing_pool.empty()) {
-        hipEvent_t e = m->timing_pool.back();
+        e = std::move(m->timing_pool.back());
         m->timing_pool.pop_back();
-        return e;
+    } else {
+        (void)e.create(hipEventDefault);  // (empty on failure: the launch goes untimed)
     }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
     return e;
 }
 
 struct VoteTimer {  // records an event pair around the voting kernel when timing is on
     dsi_mapper* m;
-    hipEvent_t a = nullptr, b = nullptr;
+    Event a, b;
     explicit VoteTimer(dsi_mapper* m_) : m(m_)
     {
         if (!m->timing) return;
@@ -679,8 +628,8 @@ struct VoteTimer {  // records an event pair around the voting kernel when timin
     {
         if (!a || !b) return;
         (void)hipEventRecord(b, m->ctx->stream);
-        m->timing_pairs.emplace_back(a, b);
-        a = b = nullptr;
+        m->timing_pairs.push_back(std::move(a));
+        m->timing_pairs.push_back(std::move(b));
     }
 };
 
@@ -692,9 +641,9 @@ int prep_begin(dsi_mapper* m, hipStream_t* ps)
     *ps = m->ctx->stream;
     if (!m->prep_overlap) return DSI_OK;
     if (!m->prep_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&m->prep_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&m->ev_prep, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&m->ev_vote_done, hipEventDisableTiming));
+        HIP_TRY(m->prep_stream.create(hipStreamNonBlocking));
+        HIP_TRY(m->ev_prep.create(hipEventDisableTiming));
+        HIP_TRY(m->ev_vote_done.create(hipEventDisableTiming));
     }
     if (m->vote_recorded) HIP_TRY(hipStreamWaitEvent(m->prep_stream, m->ev_vote_done, 0));
     *ps = m->prep_stream;
@@ -732,10 +681,10 @@ int depth_buffers_acquire(dsi_mapper* m)
 int depth_buffers_ready(dsi_mapper* m)
 {
     if (!m->ev_depth_ready) {
-        HIP_TRY(hipEventCreateWithFlags(&m->ev_depth_ready, hipEventDisableTiming));
+        HIP_TRY(m->ev_depth_ready.create(hipEventDisableTiming));
         // (the in-order fetch STORES the maps into mapped host memory from a kernel: the event that says "read" must
         //  release those stores to the system, or the host may see stale maps in non-coherent pinned memory -- ADVICE r05)
-        HIP_TRY(hipEventCreateWithFlags(&m->ev_depth_read, hipEventDisableTiming | hipEventReleaseToSystem));
+        HIP_TRY(m->ev_depth_read.create(hipEventDisableTiming | hipEventReleaseToSystem));
     }
     HIP_TRY(hipEventRecord(m->ev_depth_ready, m->ctx->stream));
     m->depth_valid = true;
@@ -802,7 +751,7 @@ int vote_device(dsi_mapper* m, const float2* xy, const float* centers, size_t np
         HIP_TRY(m->H.reserve(np * 9));
         HIP_TRY(m->xy.reserve(np * dsi::kPacket));
         HIP_TRY(dsi::launch_packet_geometry(ps, raw->Rt, (int)np, m->geom, m->centers.p, m->H.p));
-        HIP_TRY(dsi::launch_warp_z0(ps, raw->x, raw->y, raw->first, (int)np, m->H.p, m->lut_dev, m->sensor_w, m->sensor_h,
+        HIP_TRY(dsi::launch_warp_z0(ps, raw->x, raw->y, raw->first, (int)np, m->H.p, m->lut_dev.p, m->sensor_w, m->sensor_h,
                                     m->xy.p));
         xy = m->xy.p;
         return DSI_OK;
@@ -827,7 +776,7 @@ int vote_device(dsi_mapper* m, const float2* xy, const float* centers, size_t np
         if (int rc = prep_end(m, ps)) return rc;
         if (!accumulate) HIP_TRY(hipMemsetAsync(g->data, 0, g->n * sizeof(float), ctx->stream));
         VoteTimer vt(m);
-        HIP_TRY(dsi::launch_vote_global(ctx->stream, xy, centers, (int)np, m->planes_dev, geom, g->data));
+        HIP_TRY(dsi::launch_vote_global(ctx->stream, xy, centers, (int)np, m->planes_dev.p, geom, g->data));
         vt.stop();
         return vote_done(m);
     }
@@ -885,7 +834,7 @@ int vote_device(dsi_mapper* m, const float2* xy, const float* centers, size_t np
         HIP_TRY(dsi::launch_sort_groups(ps, xy, (int)np, S, geom.ny, geom.nz, bp.row_pad, m->sxy.p, m->spk.p,
                                         m->nvalid.p, m->rowstart.p));
         // per-packet coefficients + row-bin ranges (cuts buffer), then the per-group runs
-        HIP_TRY(dsi::launch_plane_coef(ps, centers, m->planes_dev, m->rowstart.p, m->nvalid.p, (int)np,
+        HIP_TRY(dsi::launch_plane_coef(ps, centers, m->planes_dev.p, m->rowstart.p, m->nvalid.p, (int)np,
                                        geom, bp, m->coef.p, m->cuts.p));
         HIP_TRY(dsi::launch_group_cuts(ps, m->cuts.p, m->rowstart.p, (int)np, S, geom, bp, m->gcuts.p));
         if (int rc = prep_end(m, ps)) return rc;
@@ -895,7 +844,7 @@ int vote_device(dsi_mapper* m, const float2* xy, const float* centers, size_t np
         vt.stop();
     } else {
     if (raw && !m->keep_z0) {
-        HIP_TRY(dsi::launch_sort_packets_raw(ps, raw->Rt, raw->x, raw->y, raw->first, m->lut_dev, m->sensor_w, m->sensor_h, geom,
+        HIP_TRY(dsi::launch_sort_packets_raw(ps, raw->Rt, raw->x, raw->y, raw->first, m->lut_dev.p, m->sensor_w, m->sensor_h, geom,
                                              m->centers.p, (int)np, bp.row_pad, m->sxy.p, m->nvalid.p,
                                              m->rowstart.p, m->unit_multiplicity));
     } else {
@@ -903,7 +852,7 @@ int vote_device(dsi_mapper* m, const float2* xy, const float* centers, size_t np
         HIP_TRY(dsi::launch_sort_packets(ps, xy, (int)np, geom.ny, geom.nz, bp.row_pad, m->sxy.p, m->nvalid.p,
                                          m->rowstart.p));
     }
-    HIP_TRY(dsi::launch_plane_coef(ps, centers, m->planes_dev, m->rowstart.p, m->nvalid.p, (int)np,
+    HIP_TRY(dsi::launch_plane_coef(ps, centers, m->planes_dev.p, m->rowstart.p, m->nvalid.p, (int)np,
                                    geom, bp, m->coef.p, m->cuts.p));
     if (int rc = prep_end(m, ps)) return rc;
     VoteTimer vt(m);
@@ -960,13 +909,13 @@ int dsi_context_create(int device_id, dsi_context_t** out)
     dsi_context* ctx = new (std::nothrow) dsi_context();
     REQUIRE(ctx, DSI_ERR_INVALID, "out of host memory");
     ctx->device = device_id;
-    hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
+    hipError_t e = ctx->stream.create(hipStreamNonBlocking);
     if (e == hipSuccess) e = upload_stream_acquire(device_id, &ctx->upload_stream);
-    if (e == hipSuccess) e = hipEventCreate(&ctx->t0);
-    if (e == hipSuccess) e = hipEventCreate(&ctx->t1);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ctx->ms_accum), sizeof(double));
+    if (e == hipSuccess) e = ctx->t0.create(hipEventDefault);
+    if (e == hipSuccess) e = ctx->t1.create(hipEventDefault);
+    if (e == hipSuccess) e = ctx->ms_accum.reserve(1);
     if (e != hipSuccess) {
-        dsi_context_destroy(ctx);
+        delete ctx;
         return fail(DSI_ERR_HIP, "context setup failed: %s", hipGetErrorString(e));
     }
     *out = ctx;
@@ -982,34 +931,7 @@ int dsi_context_destroy(dsi_context_t* ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
-    if (ctx->upload_stream) {
-        (void)hipStreamSynchronize(ctx->upload_stream);
-        upload_stream_release(ctx->device);
-        ctx->upload_stream = nullptr;
-    }
-    for (auto& blk : ctx->batch_pool) {
-        (void)hipFree(blk.p);
-        (void)hipEventDestroy(blk.freed);
-    }
-    if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-    if (ctx->ms_accum) (void)hipFree(ctx->ms_accum);
-    if (ctx->collapse_scratch) (void)hipFree(ctx->collapse_scratch);
-    ctx->focus_keys.release();
-    ctx->focus_volume.release();
-    ctx->grid_words.release();
-    ctx->grid_bytes.release();
-    ctx->filter_a.release();
-    ctx->filter_b.release();
-    ctx->filter_words.release();
-    ctx->img_words.release();
-    ctx->img_bytes.release();
-    ctx->pc.release();
-    for (hipEvent_t ev : ctx->marks) (void)hipEventDestroy(ev);
-    ctx->marks.clear();
-    if (ctx->t0) (void)hipEventDestroy(ctx->t0);
-    if (ctx->t1) (void)hipEventDestroy(ctx->t1);
-    if (ctx->sync_ev) (void)hipEventDestroy(ctx->sync_ev);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    if (ctx->upload_stream) (void)hipStreamSynchronize(ctx->upload_stream);
     delete ctx;
     return DSI_OK;
 }
@@ -1027,13 +949,13 @@ int dsi_context_wait_for(dsi_context_t* ctx, dsi_context_t* other)
     REQUIRE(ctx->device == other->device, DSI_ERR_INVALID, "contexts are on different devices");
     if (ctx == other) return DSI_OK;
     if (int rc = set_device(ctx)) return rc;
-    if (!other->sync_ev) HIP_TRY(hipEventCreateWithFlags(&other->sync_ev, hipEventDisableTiming));
+    if (!other->sync_ev) HIP_TRY(other->sync_ev.create(hipEventDisableTiming));
     HIP_TRY(hipEventRecord(other->sync_ev, other->stream));
     HIP_TRY(hipStreamWaitEvent(ctx->stream, other->sync_ev, 0));
     return DSI_OK;
 }
 
-void* dsi_context_stream(dsi_context_t* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
+void* dsi_context_stream(dsi_context_t* ctx) { return ctx ? (void*)ctx->stream.h : nullptr; }
 int dsi_context_device(dsi_context_t* ctx) { return ctx ? ctx->device : -1; }
 
 int dsi_context_timer_start(dsi_context_t* ctx)
@@ -1057,9 +979,9 @@ int dsi_context_timeline_mark(dsi_context_t* ctx)
     REQUIRE(ctx, DSI_ERR_INVALID, "context is null");
     if (int rc = set_device(ctx)) return rc;
     if (ctx->n_marks == ctx->marks.size()) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreate(&e));
-        ctx->marks.push_back(e);
+        Event e;
+        HIP_TRY(e.create(hipEventDefault));
+        ctx->marks.push_back(std::move(e));
     }
     HIP_TRY(hipEventRecord(ctx->marks[ctx->n_marks], ctx->stream));
     ++ctx->n_marks;
@@ -1096,17 +1018,15 @@ static int grid_make(dsi_context_t* ctx, int nx, int ny, int nz, void* wrap, dsi
     g->n = (size_t)nx * ny * nz;
     if (wrap) {
         g->data = static_cast<float*>(wrap);
-        g->owned = false;
     } else {
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&g->data), g->n * sizeof(float));
-        if (e == hipSuccess) e = hipMemsetAsync(g->data, 0, g->n * sizeof(float), ctx->stream);
+        hipError_t e = g->own.reserve(g->n);
+        if (e == hipSuccess) e = hipMemsetAsync(g->own.p, 0, g->n * sizeof(float), ctx->stream);
         if (e != hipSuccess) {
-            if (g->data) (void)hipFree(g->data);
+            const size_t bytes = g->n * sizeof(float);
             delete g;
-            return fail(DSI_ERR_HIP, "grid allocation of %zu bytes failed: %s", g->n * sizeof(float),
-                        hipGetErrorString(e));
+            return fail(DSI_ERR_HIP, "grid allocation of %zu bytes failed: %s", bytes, hipGetErrorString(e));
         }
-        g->owned = true;
+        g->data = g->own.p;
     }
     ++ctx->children;
     *out = g;
@@ -1132,7 +1052,6 @@ int dsi_grid_destroy(dsi_grid_t* g)
     if (!g) return DSI_OK;
     (void)hipSetDevice(g->ctx->device);
     (void)hipStreamSynchronize(g->ctx->stream);
-    if (g->owned && g->data) (void)hipFree(g->data);
     --g->ctx->children;
     delete g;
     return DSI_OK;
@@ -1290,17 +1209,11 @@ int dsi_grid_collapse_max_z_dev(dsi_grid_t* g, float* conf_dev, uint8_t* idx_dev
 static int collapse_scratch(dsi_context* ctx, size_t npix, float** conf, uint8_t** idx)
 {
     const size_t need = npix * sizeof(float) + npix;
-    if (ctx->collapse_scratch_bytes < need) {
-        if (ctx->collapse_scratch) {
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-            HIP_TRY(hipFree(ctx->collapse_scratch));
-            ctx->collapse_scratch = nullptr;
-            ctx->collapse_scratch_bytes = 0;
-        }
-        HIP_TRY(hipMalloc(&ctx->collapse_scratch, need));
-        ctx->collapse_scratch_bytes = need;
+    if (ctx->collapse_scratch.cap < need) {
+        if (ctx->collapse_scratch.p) HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx->collapse_scratch.reserve(need));  // (growth frees first)
     }
-    *conf = static_cast<float*>(ctx->collapse_scratch);
+    *conf = reinterpret_cast<float*>(ctx->collapse_scratch.p);
     *idx = reinterpret_cast<uint8_t*>(*conf + npix);
     return DSI_OK;
 }
@@ -1412,10 +1325,10 @@ int dsi_grid_mean_square(dsi_grid_t* g, double* out)
     REQUIRE(g && out, DSI_ERR_INVALID, "null argument");
     dsi_context* ctx = g->ctx;
     if (int rc = set_device(ctx)) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->ms_accum, 0, sizeof(double), ctx->stream));
-    HIP_TRY(dsi::launch_mean_square(ctx->stream, g->data, g->n, ctx->ms_accum));
+    HIP_TRY(hipMemsetAsync(ctx->ms_accum.p, 0, sizeof(double), ctx->stream));
+    HIP_TRY(dsi::launch_mean_square(ctx->stream, g->data, g->n, ctx->ms_accum.p));
     double sum = 0;
-    HIP_TRY(hipMemcpyAsync(&sum, ctx->ms_accum, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&sum, ctx->ms_accum.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *out = sum / (double)g->n;  // cartesian3dgrid.cpp:173
     return DSI_OK;
@@ -1748,20 +1661,19 @@ int dsi_mapper_create(dsi_context_t* ctx, const dsi_mapper_config_t* cfg, dsi_ma
     m->planes = std::vector<float>(m->planes.begin() + m->plane_begin, m->planes.begin() + m->plane_begin + g.nz);
 
     int rc = DSI_OK;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->planes_dev), g.nz * sizeof(float));
+    hipError_t e = m->planes_dev.reserve(g.nz);
     if (e == hipSuccess)
-        e = hipMemcpy(m->planes_dev, m->planes.data(), g.nz * sizeof(float), hipMemcpyHostToDevice);
+        e = hipMemcpy(m->planes_dev.p, m->planes.data(), g.nz * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess && cfg->lut) {
-        const size_t bytes = (size_t)cfg->sensor_width * cfg->sensor_height * sizeof(float2);
-        e = hipMalloc(reinterpret_cast<void**>(&m->lut_dev), bytes);
-        if (e == hipSuccess) e = hipMemcpy(m->lut_dev, cfg->lut, bytes, hipMemcpyHostToDevice);
+        const size_t n = (size_t)cfg->sensor_width * cfg->sensor_height;
+        e = m->lut_dev.reserve(n);
+        if (e == hipSuccess) e = hipMemcpy(m->lut_dev.p, cfg->lut, n * sizeof(float2), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) rc = fail(DSI_ERR_HIP, "mapper setup failed: %s", hipGetErrorString(e));
     if (rc == DSI_OK) rc = dsi_grid_create(ctx, g.nx, g.ny, g.nz, &m->grid);  // :240
-    if (rc != DSI_OK) {
-        std::string keep = g_last_error;
-        dsi_mapper_destroy(m);
-        g_last_error = keep;
+    if (rc != DSI_OK) {  // (the grid, the last step, does not exist)
+        --ctx->children;
+        delete m;
         return rc;
     }
     *out = m;
@@ -1773,55 +1685,9 @@ int dsi_mapper_destroy(dsi_mapper_t* m)
     if (!m) return DSI_OK;
     (void)hipSetDevice(m->ctx->device);
     (void)hipStreamSynchronize(m->ctx->stream);
-    if (m->prep_stream) {
-        (void)hipStreamSynchronize(m->prep_stream);
-        (void)hipStreamDestroy(m->prep_stream);
-        (void)hipEventDestroy(m->ev_prep);
-        (void)hipEventDestroy(m->ev_vote_done);
-    }
-    if (m->ev_depth_ready) {
-        if (m->ctx->copy_stream) (void)hipStreamSynchronize(m->ctx->copy_stream);
-        (void)hipEventDestroy(m->ev_depth_ready);
-        (void)hipEventDestroy(m->ev_depth_read);
-    }
+    if (m->prep_stream) (void)hipStreamSynchronize(m->prep_stream);
+    if (m->ev_depth_ready && m->ctx->copy_stream) (void)hipStreamSynchronize(m->ctx->copy_stream);
     if (m->grid) dsi_grid_destroy(m->grid);
-    if (m->planes_dev) (void)hipFree(m->planes_dev);
-    if (m->planes_full_dev) (void)hipFree(m->planes_full_dev);
-    m->argmax_keys.release();
-    m->tie.release();
-    if (m->lut_dev) (void)hipFree(m->lut_dev);
-    m->centers.release();
-    m->H.release();
-    m->partials.release();
-    m->fused_trace.release();
-    m->fused_keys.release();
-    m->pair_work.release();
-    m->fused_splits.release();
-    m->fused_prefix.release();
-    m->Rt_tmp.release();
-    m->conf.release();
-    m->depth.release();
-    m->xy.release();
-    m->sxy.release();
-    m->seam.release();
-    m->nvalid.release();
-    m->gcuts.release();
-    m->spk.release();
-    m->rowstart.release();
-    m->cuts.release();
-    m->coef.release();
-    m->idx.release();
-    m->conf8.release();
-    m->mask.release();
-    m->idx_filtered.release();
-    m->minmax.release();
-    m->pc.release();
-    for (auto& t : m->alg2_tables) t.release();
-    for (auto& pr : m->timing_pairs) {
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-    }
-    for (hipEvent_t e : m->timing_pool) (void)hipEventDestroy(e);
     --m->ctx->children;
     delete m;
     return DSI_OK;
@@ -1966,7 +1832,7 @@ static int batch_create(dsi_context_t* ctx, const uint16_t* x, const uint16_t* y
     b->x = reinterpret_cast<uint16_t*>(base + rt_bytes + first_bytes);
     b->y = reinterpret_cast<uint16_t*>(base + rt_bytes + first_bytes + ev_bytes);
     hipStream_t cs = ctx->upload_stream;
-    hipError_t e = hipEventCreateWithFlags(&b->ready, hipEventDisableTiming);
+    hipError_t e = b->ready.create(hipEventDisableTiming);
     // the block's previous reader (a kernel on the compute stream) must be done before we overwrite it
     if (e == hipSuccess) e = hipStreamWaitEvent(cs, b->block.freed, 0);
     if (e == hipSuccess && n_events) e = hipMemcpyAsync(b->x, x, n_events * sizeof(uint16_t), hipMemcpyHostToDevice, cs);
@@ -1982,7 +1848,7 @@ static int batch_create(dsi_context_t* ctx, const uint16_t* x, const uint16_t* y
     // vouches for them (dsi_batch_create_async: page-locked memory, left alone until uploaded)
     if (e == hipSuccess && wait) e = hipStreamSynchronize(cs);
     if (e != hipSuccess) {
-        dsi_batch_destroy(b);
+        dsi_batch_destroy(b);  // (not a plain delete: the block goes back to the pool)
         return fail(DSI_ERR_HIP, "batch upload failed: %s", hipGetErrorString(e));
     }
     *out = b;
@@ -2033,7 +1899,6 @@ int dsi_batch_destroy(dsi_batch_t* b)
     // an upload that nobody waited for yet (async batch destroyed unused): order the block's reuse after it
     if (b->ready) (void)hipStreamWaitEvent(b->ctx->stream, b->ready, 0);
     pool_give(b->ctx, b->block);  // no wait: the block's "freed" event orders its reuse
-    if (b->ready) (void)hipEventDestroy(b->ready);
     --b->ctx->children;
     delete b;
     return DSI_OK;
@@ -2165,7 +2030,7 @@ int dsi_mapper_depth_map_of(dsi_mapper_t* m, dsi_grid_t* g)
     if (int rc = dsi_context_wait_for(m->ctx, g->ctx)) return rc;
     if (int rc = depth_buffers_acquire(m)) return rc;
     HIP_TRY(dsi::launch_collapse_max_z(m->ctx->stream, g->data, g->nx, g->ny, g->nz, m->conf.p, m->idx.p,
-                                       m->planes_dev, m->depth.p));
+                                       m->planes_dev.p, m->depth.p));
     if (int rc = release_to(g->ctx, m->ctx)) return rc;
     return depth_buffers_ready(m);
 }
@@ -2184,7 +2049,7 @@ int dsi_mapper_depth_map_of_focus(dsi_mapper_t* m, dsi_grid_t* g, int method)
     HIP_TRY(m->idx.reserve(npix));
     if (int rc = dsi_context_wait_for(m->ctx, g->ctx)) return rc;
     if (int rc = depth_buffers_acquire(m)) return rc;
-    if (int rc = focus_collapse(m->ctx, g, method, 1, m->conf.p, m->idx.p, m->planes_dev, m->depth.p)) return rc;
+    if (int rc = focus_collapse(m->ctx, g, method, 1, m->conf.p, m->idx.p, m->planes_dev.p, m->depth.p)) return rc;
     if (int rc = release_to(g->ctx, m->ctx)) return rc;
     return depth_buffers_ready(m);
 }
@@ -2206,7 +2071,7 @@ int dsi_mapper_depth_map_of_fusion(dsi_mapper_t* m, const dsi_grid_t* a, const d
     if (int rc = dsi_context_wait_for(m->ctx, b->ctx)) return rc;
     if (int rc = depth_buffers_acquire(m)) return rc;
     HIP_TRY(dsi::launch_collapse_max_z_fused(m->ctx->stream, a->data, b->data, a->nx, a->ny, a->nz, op, m->conf.p,
-                                             m->idx.p, m->planes_dev, m->depth.p));
+                                             m->idx.p, m->planes_dev.p, m->depth.p));
     if (int rc = release_to(a->ctx, m->ctx)) return rc;
     if (int rc = release_to(b->ctx, m->ctx)) return rc;
     return depth_buffers_ready(m);
@@ -2234,7 +2099,7 @@ int dsi_mapper_depth_map_of_fusion_n(dsi_mapper_t* m, const dsi_grid_t* const* s
         if (int rc = dsi_context_wait_for(m->ctx, srcs[i]->ctx)) return rc;
     if (int rc = depth_buffers_acquire(m)) return rc;
     HIP_TRY(dsi::launch_collapse_max_z_fused_n(m->ctx->stream, ptrs, n, mode, m->grid->nx, m->grid->ny, m->grid->nz,
-                                               m->conf.p, m->idx.p, m->planes_dev, m->depth.p));
+                                               m->conf.p, m->idx.p, m->planes_dev.p, m->depth.p));
     for (int i = 0; i < n; ++i)
         if (int rc = release_to(srcs[i]->ctx, m->ctx)) return rc;
     return depth_buffers_ready(m);
@@ -2338,8 +2203,8 @@ static int depth_map_of_events_impl(dsi_mapper_t* out, dsi_mapper_t* const* mapp
             HIP_TRY(hipMemsetAsync(m->nvalid.p, 0, ((size_t)geom.nz + 8) * sizeof(uint32_t), st));
             HIP_TRY(hipMemsetAsync(m->pair_work.p, 0, (size_t)n_pairs * sizeof(uint32_t), st));
         }
-        prep[i] = dsi::PrepCameraArgs{b->Rt, b->x, b->y, b->first, m->lut_dev, m->sensor_w, m->sensor_h, m->centers.p, (int)np,
-                                      m->sxy.p, m->nvalid.p, m->rowstart.p, m->planes_dev, m->coef.p, m->cuts.p,
+        prep[i] = dsi::PrepCameraArgs{b->Rt, b->x, b->y, b->first, m->lut_dev.p, m->sensor_w, m->sensor_h, m->centers.p, (int)np,
+                                      m->sxy.p, m->nvalid.p, m->rowstart.p, m->planes_dev.p, m->coef.p, m->cuts.p,
                                       balance ? m->pair_work.p : nullptr, m->geom};
         cams.cam[i] = dsi::FusedCamera{m->sxy.p, m->coef.p, m->cuts.p, m->nvalid.p + np, (int)np};
         m->info = dsi_vote_info_t{};
@@ -2386,7 +2251,7 @@ static int depth_map_of_events_impl(dsi_mapper_t* out, dsi_mapper_t* const* mapp
         vt.stop();
     }
     // keys -> confidence, index, depth over the planes the cameras voted (mapper_emvs_stereo.cpp:302-313)
-    HIP_TRY(dsi::launch_unpack_argmax(st, out->fused_keys.p, (int)npix, out->planes_dev, out->conf.p, out->idx.p,
+    HIP_TRY(dsi::launch_unpack_argmax(st, out->fused_keys.p, (int)npix, out->planes_dev.p, out->conf.p, out->idx.p,
                                       out->depth.p, /*clear=*/1));
     out->fused_keys_dirty = false;
     return depth_buffers_ready(out);
@@ -2512,8 +2377,8 @@ int dsi_mapper_depth_map_of_events_alg2(dsi_mapper_t* out_tc, dsi_mapper_t* out_
         if (b->ready) HIP_TRY(hipStreamWaitEvent(st, b->ready, 0));  // uploaded on the copy stream
         // no packets (< 1024 events): evaluateDSI returns false and the sub-interval's DSI stays zero
         if (np == 0) HIP_TRY(hipMemsetAsync(t.nvalid.p, 0, ((size_t)geom.nz + 8) * sizeof(uint32_t), st));
-        prep[n_prep++] = dsi::PrepCameraArgs{b->Rt, b->x, b->y, b->first, m->lut_dev, m->sensor_w, m->sensor_h, t.centers.p, (int)np,
-                                             t.sxy.p, t.nvalid.p, t.rowstart.p, m->planes_dev, t.coef.p, t.cuts.p, nullptr, m->geom};
+        prep[n_prep++] = dsi::PrepCameraArgs{b->Rt, b->x, b->y, b->first, m->lut_dev.p, m->sensor_w, m->sensor_h, t.centers.p, (int)np,
+                                             t.sxy.p, t.nvalid.p, t.rowstart.p, m->planes_dev.p, t.coef.p, t.cuts.p, nullptr, m->geom};
         bt.b[i] = dsi::FusedCamera{t.sxy.p, t.coef.p, t.cuts.p, t.nvalid.p + np, (int)np};
         if (n_prep == dsi::kFusedMaxCameras || i == n_batches - 1) {
             HIP_TRY(dsi::launch_prepare_cameras(st, prep, n_prep, geom, bp));
@@ -2547,7 +2412,7 @@ int dsi_mapper_depth_map_of_events_alg2(dsi_mapper_t* out_tc, dsi_mapper_t* out_
     }
     for (int o = 0; o < n_out; ++o) {
         dsi_mapper* m = outs[o];
-        HIP_TRY(dsi::launch_unpack_argmax(st, m->fused_keys.p, (int)npix, m->planes_dev, m->conf.p, m->idx.p, m->depth.p,
+        HIP_TRY(dsi::launch_unpack_argmax(st, m->fused_keys.p, (int)npix, m->planes_dev.p, m->conf.p, m->idx.p, m->depth.p,
                                           /*clear=*/1));
         m->fused_keys_dirty = false;
         if (int rc = depth_buffers_ready(m)) return rc;
@@ -2632,8 +2497,8 @@ static int tie_exact_values_dev(TieScratch& ts, hipStream_t st, dsi_mapper* cons
         for (int c = 0; c < n; ++c) {
             dsi_mapper* m = ms[c];
             if (!bs[c]->n_packets) continue;
-            HIP_TRY(dsi::launch_tie_hits_binned(st, bs[c]->x, bs[c]->y, bs[c]->first, m->H.p, m->lut_dev, m->sensor_w, m->sensor_h,
-                                                m->centers.p, m->planes_dev, m->geom, (int)bs[c]->n_packets, ts.desc.p, nsv,
+            HIP_TRY(dsi::launch_tie_hits_binned(st, bs[c]->x, bs[c]->y, bs[c]->first, m->H.p, m->lut_dev.p, m->sensor_w, m->sensor_h,
+                                                m->centers.p, m->planes_dev.p, m->geom, (int)bs[c]->n_packets, ts.desc.p, nsv,
                                                 (unsigned)c * (unsigned)nsv, pos_bits, sentinel, cnt + 2, cap_segs, cnt + 3,
                                                 ts.counters.p + 4, ts.keys.p, ts.w.p));
         }
@@ -2782,7 +2647,7 @@ int dsi_mapper_resolve_near_ties(dsi_mapper_t* out, dsi_mapper_t* const* mappers
         if (int rc = depth_buffers_acquire(out)) return rc;
         unsigned* cnt = reinterpret_cast<unsigned*>(ts.counters.p);
         HIP_TRY(dsi::launch_tie_pick(st, n == 2 ? op : 0, ts.cols.p, (int)n_columns, ts.cand.p, (int)n_cand, npix, ts.exact.p, ts.count.p,
-                                     ts.diff.p, out->planes_dev, out->conf.p, out->idx.p, out->depth.p, cnt + 4, rel_gap));
+                                     ts.diff.p, out->planes_dev.p, out->conf.p, out->idx.p, out->depth.p, cnt + 4, rel_gap));
         if (int rc = depth_buffers_ready(out)) return rc;
         unsigned stats[4] = {0, 0, 0, 0};
         unsigned* pinned = nullptr;
@@ -2841,8 +2706,8 @@ int dsi_mapper_prove_near_ties(dsi_mapper_t* out, dsi_mapper_t* const* mappers, 
         HIP_TRY(hipMemsetAsync(ts.votes[c].p, 0, nvox * sizeof(uint32_t), st));
         dsi_mapper* m = ms[c];
         if (!bs[c]->n_packets) continue;
-        HIP_TRY(dsi::launch_count_votes(st, bs[c]->x, bs[c]->y, bs[c]->first, m->H.p, m->lut_dev, m->sensor_w, m->sensor_h, m->centers.p,
-                                        m->planes_dev, m->geom, (int)bs[c]->n_packets, ts.votes[c].p));
+        HIP_TRY(dsi::launch_count_votes(st, bs[c]->x, bs[c]->y, bs[c]->first, m->H.p, m->lut_dev.p, m->sensor_w, m->sensor_h, m->centers.p,
+                                        m->planes_dev.p, m->geom, (int)bs[c]->n_packets, ts.votes[c].p));
     }
     HIP_TRY(ts.counters.reserve(kTieCounterWords / 2));
     unsigned* cnt = reinterpret_cast<unsigned*>(ts.counters.p);
@@ -2909,8 +2774,8 @@ int dsi_mapper_prove_near_ties_n(dsi_mapper_t* out, dsi_grid_t* fused, dsi_mappe
         HIP_TRY(ts.votes[c].reserve(nvox));
         HIP_TRY(hipMemsetAsync(ts.votes[c].p, 0, nvox * sizeof(uint32_t), st));
         if (b->n_packets)
-            HIP_TRY(dsi::launch_count_votes(st, b->x, b->y, b->first, m->H.p, m->lut_dev, m->sensor_w, m->sensor_h, m->centers.p,
-                                            m->planes_dev, m->geom, (int)b->n_packets, ts.votes[c].p));
+            HIP_TRY(dsi::launch_count_votes(st, b->x, b->y, b->first, m->H.p, m->lut_dev.p, m->sensor_w, m->sensor_h, m->centers.p,
+                                            m->planes_dev.p, m->geom, (int)b->n_packets, ts.votes[c].p));
         e[c] = m->grid->data;
         h[c] = ts.votes[c].p;
     }
@@ -2958,8 +2823,8 @@ int dsi_mapper_reference_interval(dsi_mapper_t* scratch, dsi_mapper_t* m, const 
     ts.votes_valid[7] = false;
     HIP_TRY(hipMemsetAsync(ts.votes[7].p, 0, nvox * sizeof(uint32_t), st));
     if (batch->n_packets)
-        HIP_TRY(dsi::launch_count_votes(st, batch->x, batch->y, batch->first, m->H.p, m->lut_dev, m->sensor_w, m->sensor_h, m->centers.p,
-                                        m->planes_dev, m->geom, (int)batch->n_packets, ts.votes[7].p));
+        HIP_TRY(dsi::launch_count_votes(st, batch->x, batch->y, batch->first, m->H.p, m->lut_dev.p, m->sensor_w, m->sensor_h, m->centers.p,
+                                        m->planes_dev.p, m->geom, (int)batch->n_packets, ts.votes[7].p));
     HIP_TRY(ts.interval_most.reserve(1));
     if (!ts.interval_most_live) {
         HIP_TRY(hipMemsetAsync(ts.interval_most.p, 0, sizeof(unsigned), st));
@@ -3152,7 +3017,7 @@ static int patch_depth_map(dsi_mapper_t* m, TieScratch& ts, const uint32_t* pix,
     HIP_TRY(hipMemcpyAsync(ts.exact.p, conf, n * sizeof(float), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(ts.tmp.p, idx, n, hipMemcpyHostToDevice, st));
     if (int rc = depth_buffers_acquire(m)) return rc;
-    HIP_TRY(dsi::launch_tie_patch(st, ts.count.p, reinterpret_cast<const uint8_t*>(ts.tmp.p), ts.exact.p, (int)n, m->planes_dev,
+    HIP_TRY(dsi::launch_tie_patch(st, ts.count.p, reinterpret_cast<const uint8_t*>(ts.tmp.p), ts.exact.p, (int)n, m->planes_dev.p,
                                   m->conf.p, m->idx.p, m->depth.p));
     if (int rc = depth_buffers_ready(m)) return rc;
     HIP_TRY(hipStreamSynchronize(st));  // the host arrays are pageable
@@ -3227,15 +3092,14 @@ int dsi_mapper_vote_kernel_time(dsi_mapper_t* m, float* total_ms, int* launches)
     HIP_TRY(hipStreamSynchronize(m->ctx->stream));
     float total = 0.f;
     int n = 0;
-    for (auto& pr : m->timing_pairs) {
+    for (size_t i = 0; i + 1 < m->timing_pairs.size(); i += 2) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) {
+        if (hipEventElapsedTime(&ms, m->timing_pairs[i], m->timing_pairs[i + 1]) == hipSuccess) {
             total += ms;
             ++n;
         }
-        m->timing_pool.push_back(pr.first);
-        m->timing_pool.push_back(pr.second);
     }
+    for (Event& e : m->timing_pairs) m->timing_pool.push_back(std::move(e));
     m->timing_pairs.clear();
     *total_ms = total;
     *launches = n;
@@ -3271,7 +3135,7 @@ int dsi_mapper_filter_depth_map(dsi_mapper_t* m, const dsi_depthmap_options_t* o
     HIP_TRY(m->minmax.reserve(2));
     HIP_TRY(dsi::launch_depth_map_filters(ctx->stream, m->conf.p, m->idx.p, nx, ny,
                                           opts->adaptive_threshold_kernel_size, opts->adaptive_threshold_c,
-                                          opts->median_filter_size, opts->max_confidence, m->planes_dev,
+                                          opts->median_filter_size, opts->max_confidence, m->planes_dev.p,
                                           m->minmax.p, m->conf8.p, m->mask.p, m->idx_filtered.p, m->depth.p));
     if (depth_host)
         HIP_TRY(hipMemcpyAsync(depth_host, m->depth.p, npix * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -3617,10 +3481,10 @@ struct dsi_score {
     dsi_context* ctx = nullptr;
     size_t capacity = 0;
     double baseline = 0.0, focal = 0.0, gt_min = 0.0;
-    double* buf = nullptr;  // capacity errors, then kScoreGuardWords words that nothing may touch
+    DevBuf<double> buf;  // capacity errors, then kScoreGuardWords words that nothing may touch
     // state | extremes (2) | select work area
-    unsigned long long* words = nullptr;
-    double* partials = nullptr;  // 4 * kScoreMaxBlocks
+    DevBuf<unsigned long long> words;
+    DevBuf<double> partials;  // 4 * kScoreMaxBlocks
     DevBuf<float> depth, gt;     // uploaded maps
     DevBuf<uint8_t> mask;
     DevBuf<unsigned long long> counts;
@@ -3633,26 +3497,14 @@ constexpr unsigned long long kScoreGuardPattern = 0xa5c3a5c3a5c3a5c3ull;
 constexpr size_t kScoreStateWords = sizeof(dsi::ScoreState) / sizeof(unsigned long long);
 static_assert(sizeof(dsi::ScoreState) % sizeof(unsigned long long) == 0, "ScoreState is made of 64-bit words");
 
-dsi::ScoreState* score_state(dsi_score* s) { return reinterpret_cast<dsi::ScoreState*>(s->words); }
-unsigned long long* score_mm(dsi_score* s) { return s->words + kScoreStateWords; }
-unsigned long long* score_select_words(dsi_score* s) { return s->words + kScoreStateWords + 2; }
-
-void score_free(dsi_score* s)
-{
-    if (s->buf) (void)hipFree(s->buf);
-    if (s->words) (void)hipFree(s->words);
-    if (s->partials) (void)hipFree(s->partials);
-    s->depth.release();
-    s->gt.release();
-    s->mask.release();
-    s->counts.release();
-    delete s;
-}
+dsi::ScoreState* score_state(dsi_score* s) { return reinterpret_cast<dsi::ScoreState*>(s->words.p); }
+unsigned long long* score_mm(dsi_score* s) { return s->words.p + kScoreStateWords; }
+unsigned long long* score_select_words(dsi_score* s) { return s->words.p + kScoreStateWords + 2; }
 
 int score_add_device(dsi_score* s, const float* depth_dev, const uint8_t* mask_dev, const float* gt_dev, size_t n)
 {
     HIP_TRY(dsi::launch_score_accumulate(s->ctx->stream, depth_dev, mask_dev, gt_dev, n, s->gt_min, s->baseline, s->focal,
-                                         score_state(s), s->buf, s->capacity, s->partials));
+                                         score_state(s), s->buf.p, s->capacity, s->partials.p));
     return DSI_OK;
 }
 
@@ -3666,7 +3518,7 @@ int score_check_add(const dsi_score* s, const void* a, const void* b, const void
 // the state as it stands once the stream has run; synchronises
 int score_read_state(dsi_score* s, dsi::ScoreState* st, size_t* n_stored)
 {
-    HIP_TRY(hipMemcpyAsync(st, s->words, sizeof *st, hipMemcpyDeviceToHost, s->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(st, s->words.p, sizeof *st, hipMemcpyDeviceToHost, s->ctx->stream));
     HIP_TRY(hipStreamSynchronize(s->ctx->stream));
     *n_stored = (size_t)std::min<unsigned long long>(st->cursor, s->capacity);
     return DSI_OK;
@@ -3677,7 +3529,7 @@ int score_median_of(dsi_score* s, size_t n, double* out)
 {
     unsigned long long mid[2] = {0, 0};
     unsigned long long* work = score_select_words(s);
-    HIP_TRY(dsi::launch_score_select(s->ctx->stream, s->buf, n, (n - 1) / 2, n / 2, work));
+    HIP_TRY(dsi::launch_score_select(s->ctx->stream, s->buf.p, n, (n - 1) / 2, n / 2, work));
     HIP_TRY(hipMemcpyAsync(mid, work, sizeof mid, hipMemcpyDeviceToHost, s->ctx->stream));
     HIP_TRY(hipStreamSynchronize(s->ctx->stream));
     double lo, hi;
@@ -3707,15 +3559,15 @@ int dsi_score_create(dsi_context_t* ctx, size_t capacity_points, double baseline
     s->gt_min = gt_min;
     const size_t nwords = kScoreStateWords + 2 + dsi::kScoreSelectWords;
     std::vector<unsigned long long> guard(kScoreGuardWords, kScoreGuardPattern);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->buf), (capacity_points + kScoreGuardWords) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->words), nwords * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->partials), 4 * (size_t)dsi::kScoreMaxBlocks * sizeof(double));
-    if (e == hipSuccess) e = hipMemsetAsync(s->words, 0, nwords * sizeof(unsigned long long), ctx->stream);
+    hipError_t e = s->buf.reserve(capacity_points + kScoreGuardWords);
+    if (e == hipSuccess) e = s->words.reserve(nwords);
+    if (e == hipSuccess) e = s->partials.reserve(4 * (size_t)dsi::kScoreMaxBlocks);
+    if (e == hipSuccess) e = hipMemsetAsync(s->words.p, 0, nwords * sizeof(unsigned long long), ctx->stream);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(s->buf + capacity_points, guard.data(), kScoreGuardWords * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+        e = hipMemcpyAsync(s->buf.p + capacity_points, guard.data(), kScoreGuardWords * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (`guard` is free again)
     if (e != hipSuccess) {
-        score_free(s);
+        delete s;
         return fail(DSI_ERR_HIP, "score allocation of %zu points failed: %s", capacity_points, hipGetErrorString(e));
     }
     ++ctx->children;
@@ -3729,7 +3581,7 @@ int dsi_score_destroy(dsi_score_t* s)
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
     --s->ctx->children;
-    score_free(s);
+    delete s;
     return DSI_OK;
 }
 
@@ -3737,7 +3589,7 @@ int dsi_score_reset(dsi_score_t* s)
 {
     REQUIRE(s, DSI_ERR_INVALID, "null argument");
     if (int rc = set_device(s->ctx)) return rc;
-    HIP_TRY(hipMemsetAsync(s->words, 0, kScoreStateWords * sizeof(unsigned long long), s->ctx->stream));
+    HIP_TRY(hipMemsetAsync(s->words.p, 0, kScoreStateWords * sizeof(unsigned long long), s->ctx->stream));
     return DSI_OK;
 }
 
@@ -3798,7 +3650,7 @@ int dsi_score_metrics(dsi_score_t* s, dsi_score_metrics_t* out)
     dsi::ScoreState st;
     size_t n_stored = 0;
     unsigned long long guard[kScoreGuardWords];
-    HIP_TRY(hipMemcpyAsync(guard, s->buf + s->capacity, sizeof guard, hipMemcpyDeviceToHost, s->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(guard, s->buf.p + s->capacity, sizeof guard, hipMemcpyDeviceToHost, s->ctx->stream));
     if (int rc = score_read_state(s, &st, &n_stored)) return rc;
     dsi_score_metrics_t r{};
     r.n_est = st.count[0];
@@ -3851,7 +3703,7 @@ int dsi_score_histogram(dsi_score_t* s, double binwidth, uint64_t* counts, size_
     *first_edge = *last_edge = std::nan("");
     if (n == 0) return DSI_OK;
     unsigned long long mm[2];
-    HIP_TRY(dsi::launch_score_minmax(stream, s->buf, n, score_mm(s)));
+    HIP_TRY(dsi::launch_score_minmax(stream, s->buf.p, n, score_mm(s)));
     HIP_TRY(hipMemcpyAsync(mm, score_mm(s), sizeof mm, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     double lo, hi;
@@ -3879,7 +3731,7 @@ int dsi_score_histogram(dsi_score_t* s, double binwidth, uint64_t* counts, size_
     if (!counts) return DSI_OK;
     REQUIRE(cap >= (size_t)nb, DSI_ERR_INVALID, "counts holds %zu bins, the histogram has %lld", cap, nb);
     HIP_TRY(s->counts.reserve((size_t)nb));
-    HIP_TRY(dsi::launch_score_histogram(stream, s->buf, n, B, s->counts.p));
+    HIP_TRY(dsi::launch_score_histogram(stream, s->buf.p, n, B, s->counts.p));
     static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "64-bit counts");
     HIP_TRY(hipMemcpyAsync(counts, s->counts.p, (size_t)nb * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -3893,24 +3745,17 @@ struct dsi_gt {
     int width = 0, height = 0, mode = 0;
     dsi::GtCalib calib{};
     // winner table | output map | disparity upload (4 bytes per pixel each), counters
-    uint32_t* words = nullptr;
-    unsigned int* counters = nullptr;
+    DevBuf<uint32_t> words;
+    DevBuf<unsigned int> counters;
 };
 
 namespace {
 
 size_t gt_npix(const dsi_gt* g) { return (size_t)g->width * g->height; }
-float* gt_out(const dsi_gt* g) { return reinterpret_cast<float*>(g->words + gt_npix(g)); }
-void* gt_upload(const dsi_gt* g) { return g->words + 2 * gt_npix(g); }
+float* gt_out(const dsi_gt* g) { return reinterpret_cast<float*>(g->words.p + gt_npix(g)); }
+void* gt_upload(const dsi_gt* g) { return g->words.p + 2 * gt_npix(g); }
 
-dsi::GtWork gt_work(const dsi_gt* g) { return dsi::GtWork{g->words, g->counters, gt_out(g)}; }
-
-void gt_free(dsi_gt* g)
-{
-    if (g->words) (void)hipFree(g->words);
-    if (g->counters) (void)hipFree(g->counters);
-    delete g;
-}
+dsi::GtWork gt_work(const dsi_gt* g) { return dsi::GtWork{g->words.p, g->counters.p, gt_out(g)}; }
 
 }  // namespace
 
@@ -3936,12 +3781,12 @@ int dsi_gt_create(dsi_context_t* ctx, int width, int height, const double* Q, co
     std::memcpy(g->calib.T, T, sizeof g->calib.T);
     std::memcpy(g->calib.K, K, sizeof g->calib.K);
     const size_t n = gt_npix(g);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&g->words), 3 * n * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->counters), 2 * sizeof(unsigned int));
-    if (e == hipSuccess) e = hipMemsetAsync(g->words, 0, 2 * n * sizeof(uint32_t), ctx->stream);  // (a fetch before a projection)
-    if (e == hipSuccess) e = hipMemsetAsync(g->counters, 0, 2 * sizeof(unsigned int), ctx->stream);
+    hipError_t e = g->words.reserve(3 * n);
+    if (e == hipSuccess) e = g->counters.reserve(2);
+    if (e == hipSuccess) e = hipMemsetAsync(g->words.p, 0, 2 * n * sizeof(uint32_t), ctx->stream);  // (a fetch before a projection)
+    if (e == hipSuccess) e = hipMemsetAsync(g->counters.p, 0, 2 * sizeof(unsigned int), ctx->stream);
     if (e != hipSuccess) {
-        gt_free(g);
+        delete g;
         return fail(DSI_ERR_HIP, "projector allocation of %d x %d pixels failed: %s", width, height, hipGetErrorString(e));
     }
     ++ctx->children;
@@ -3955,7 +3800,7 @@ int dsi_gt_destroy(dsi_gt_t* gt)
     (void)hipSetDevice(gt->ctx->device);
     (void)hipStreamSynchronize(gt->ctx->stream);
     --gt->ctx->children;
-    gt_free(gt);
+    delete gt;
     return DSI_OK;
 }
 
@@ -3986,7 +3831,7 @@ int dsi_gt_fetch(dsi_gt_t* gt, float* depth_host, uint64_t* n_points, uint64_t* 
     unsigned int counters[2] = {0, 0};
     hipStream_t st = gt->ctx->stream;
     if (depth_host) HIP_TRY(hipMemcpyAsync(depth_host, gt_out(gt), gt_npix(gt) * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(counters, gt->counters, sizeof counters, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(counters, gt->counters.p, sizeof counters, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (n_points) *n_points = counters[0];
     if (n_outside) *n_outside = counters[1];
@@ -4147,11 +3992,11 @@ int dsi_mapper_create_with_lens(dsi_context_t* ctx, const dsi_mapper_config_t* c
     if (int rc = dsi_mapper_create(ctx, cfg, &m)) return rc;
     // the table goes straight into the mapper's own buffer; the wait makes it visible to every stream that will read it
     // (the mapper's preparation stream does not follow the context's) and brings a failed launch back from here
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->lut_dev), (size_t)cfg->sensor_width * cfg->sensor_height * sizeof(float2));
-    if (e == hipSuccess) e = dsi::launch_rectify_lut(ctx->stream, lens->model, c, cfg->sensor_width, cfg->sensor_height, m->lut_dev);
+    hipError_t e = m->lut_dev.reserve((size_t)cfg->sensor_width * cfg->sensor_height);
+    if (e == hipSuccess) e = dsi::launch_rectify_lut(ctx->stream, lens->model, c, cfg->sensor_width, cfg->sensor_height, m->lut_dev.p);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
-        dsi_mapper_destroy(m);
+        dsi_mapper_destroy(m);  // (a whole mapper by now: its grid is a child of its own)
         return fail(DSI_ERR_HIP, "mapper lens table failed: %s", hipGetErrorString(e));
     }
     *out = m;
@@ -4197,8 +4042,8 @@ struct dsi_map {
     dsi_context* ctx = nullptr;
     double leaf = 0.0;
     uint32_t cap_log2 = 0;
-    void* block = nullptr;               // the table (dsi::map_table_at)
-    unsigned long long* ctr = nullptr;   // device: occupied, accepted, rejected, table-full
+    DevBuf<unsigned char> block;         // the table (dsi::map_table_at)
+    DevBuf<unsigned long long> ctr;      // device: occupied, accepted, rejected, table-full
     unsigned long long host_ctr[4] = {0, 0, 0, 0};  // as read back by the last integrate call
     uint64_t calls = 0, growths = 0;
     DevBuf<float> upload, xyz;           // a call's host points; the extraction's outputs
@@ -4218,31 +4063,16 @@ namespace {
 constexpr int kMapMinLog2 = 8, kMapMaxLog2 = 27;
 constexpr int kMapViewMaxLog2 = 26, kMapMaxSplat = 4;
 
+// drops the last render's buffers: a render of another size starts from nothing instead of keeping the larger ones
 void map_render_release(dsi_map* mp)
 {
-    mp->zkey.release();
-    mp->hits.release();
-    mp->render_windows.release();
-    mp->render_depth.release();
-    mp->render_mask.release();
+    mp->zkey.release();            // early, as are the four below: dsi_map_render of another size
+    mp->hits.release();            // per-pixel hit counts
+    mp->render_windows.release();  // per-pixel window counts
+    mp->render_depth.release();    // the depth image
+    mp->render_mask.release();     // its mask
     mp->render_width = mp->render_height = 0;
     mp->render_valid = false;
-}
-
-void map_free(dsi_map* mp)
-{
-    if (mp->block) (void)hipFree(mp->block);
-    if (mp->ctr) (void)hipFree(mp->ctr);
-    mp->upload.release();
-    mp->xyz.release();
-    mp->blk.release();
-    mp->tiles.release();
-    mp->n_out.release();
-    mp->w_out.release();
-    mp->key_out.release();
-    map_render_release(mp);
-    mp->render_ctr.release();
-    delete mp;
 }
 
 // the table doubled until occupied + n <= 3/4 of its slots (the caller checked that 2^27 slots are enough)
@@ -4252,18 +4082,14 @@ int map_grow_for(dsi_map* mp, size_t n)
     while ((mp->host_ctr[0] + n) * 4 > ((uint64_t)3 << want)) ++want;
     if (want == mp->cap_log2) return DSI_OK;
     hipStream_t st = mp->ctx->stream;
-    void* block = nullptr;
-    HIP_TRY(hipMalloc(&block, dsi::map_table_bytes(want)));
-    hipError_t e = hipMemsetAsync(block, 0, dsi::map_table_bytes(want), st);
+    DevBuf<unsigned char> block;
+    HIP_TRY(block.reserve(dsi::map_table_bytes(want)));
+    hipError_t e = hipMemsetAsync(block.p, 0, dsi::map_table_bytes(want), st);
     if (e == hipSuccess && mp->host_ctr[0])
-        e = dsi::launch_map_rehash(st, dsi::map_table_at(mp->block, mp->cap_log2), dsi::map_table_at(block, want), mp->ctr);
+        e = dsi::launch_map_rehash(st, dsi::map_table_at(mp->block.p, mp->cap_log2), dsi::map_table_at(block.p, want), mp->ctr.p);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void)hipFree(block);
-        return fail(DSI_ERR_HIP, "growing the map's table to 2^%u slots failed: %s", want, hipGetErrorString(e));
-    }
-    (void)hipFree(mp->block);
-    mp->block = block;
+    if (e != hipSuccess) return fail(DSI_ERR_HIP, "growing the map's table to 2^%u slots failed: %s", want, hipGetErrorString(e));
+    mp->block = std::move(block);  // (frees the old table)
     mp->growths += want - mp->cap_log2;
     mp->cap_log2 = want;
     return DSI_OK;
@@ -4282,8 +4108,8 @@ int map_integrate_device(dsi_map* mp, const float* pts_dev, size_t stride, size_
     const uint32_t serial = (uint32_t)++mp->calls;
     const unsigned long long rejected_before = mp->host_ctr[2];
     HIP_TRY(dsi::launch_map_integrate(st, pts_dev, (uint32_t)stride, (uint32_t)n, T_w_rv, mp->leaf, serial,
-                                      dsi::map_table_at(mp->block, mp->cap_log2), mp->ctr));
-    HIP_TRY(hipMemcpyAsync(mp->host_ctr, mp->ctr, sizeof mp->host_ctr, hipMemcpyDeviceToHost, st));
+                                      dsi::map_table_at(mp->block.p, mp->cap_log2), mp->ctr.p));
+    HIP_TRY(hipMemcpyAsync(mp->host_ctr, mp->ctr.p, sizeof mp->host_ctr, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_HIP, "the map's table ran full (%llu points lost): an engine bug, the map is unusable",
             mp->host_ctr[3]);
@@ -4304,7 +4130,7 @@ int map_count_device(dsi_map* mp, uint32_t min_points, uint32_t min_windows, siz
     hipStream_t st = mp->ctx->stream;
     HIP_TRY(mp->blk.reserve(words));
     HIP_TRY(mp->tiles.reserve(dsi::pc_scan_tile_words(words)));
-    HIP_TRY(dsi::launch_map_count(st, dsi::map_table_at(mp->block, mp->cap_log2), min_points, min_windows, mp->blk.p, mp->tiles.p));
+    HIP_TRY(dsi::launch_map_count(st, dsi::map_table_at(mp->block.p, mp->cap_log2), min_points, min_windows, mp->blk.p, mp->tiles.p));
     uint32_t n = 0;
     HIP_TRY(hipMemcpyAsync(&n, mp->blk.p + words - 1, sizeof n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -4339,12 +4165,12 @@ int dsi_map_create(dsi_context_t* ctx, double leaf, int capacity_log2, dsi_map_t
     mp->leaf = leaf;
     mp->cap_log2 = (uint32_t)capacity_log2;
     const size_t bytes = dsi::map_table_bytes(mp->cap_log2);
-    hipError_t e = hipMalloc(&mp->block, bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&mp->ctr), sizeof mp->host_ctr);
-    if (e == hipSuccess) e = hipMemsetAsync(mp->block, 0, bytes, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(mp->ctr, 0, sizeof mp->host_ctr, ctx->stream);
+    hipError_t e = mp->block.reserve(bytes);
+    if (e == hipSuccess) e = mp->ctr.reserve(sizeof mp->host_ctr / sizeof mp->host_ctr[0]);
+    if (e == hipSuccess) e = hipMemsetAsync(mp->block.p, 0, bytes, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(mp->ctr.p, 0, sizeof mp->host_ctr, ctx->stream);
     if (e != hipSuccess) {
-        map_free(mp);
+        delete mp;
         return fail(DSI_ERR_HIP, "map allocation of 2^%d slots failed: %s", capacity_log2, hipGetErrorString(e));
     }
     ++ctx->children;
@@ -4358,7 +4184,7 @@ int dsi_map_destroy(dsi_map_t* mp)
     (void)hipSetDevice(mp->ctx->device);
     (void)hipStreamSynchronize(mp->ctx->stream);
     --mp->ctx->children;
-    map_free(mp);
+    delete mp;
     return DSI_OK;
 }
 
@@ -4367,8 +4193,8 @@ int dsi_map_reset(dsi_map_t* mp)
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
     mp->render_valid = false;
     if (int rc = set_device(mp->ctx)) return rc;
-    HIP_TRY(hipMemsetAsync(mp->block, 0, dsi::map_table_bytes(mp->cap_log2), mp->ctx->stream));
-    HIP_TRY(hipMemsetAsync(mp->ctr, 0, sizeof mp->host_ctr, mp->ctx->stream));
+    HIP_TRY(hipMemsetAsync(mp->block.p, 0, dsi::map_table_bytes(mp->cap_log2), mp->ctx->stream));
+    HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof mp->host_ctr, mp->ctx->stream));
     std::memset(mp->host_ctr, 0, sizeof mp->host_ctr);
     mp->calls = mp->growths = 0;
     return DSI_OK;
@@ -4436,7 +4262,7 @@ int dsi_map_extract(dsi_map_t* mp, uint32_t min_points, uint32_t min_windows, fl
     HIP_TRY(mp->n_out.reserve(total));
     HIP_TRY(mp->w_out.reserve(total));
     HIP_TRY(mp->key_out.reserve(total));
-    HIP_TRY(dsi::launch_map_extract(st, dsi::map_table_at(mp->block, mp->cap_log2), min_points, min_windows, mp->leaf, mp->blk.p, mp->xyz.p,
+    HIP_TRY(dsi::launch_map_extract(st, dsi::map_table_at(mp->block.p, mp->cap_log2), min_points, min_windows, mp->leaf, mp->blk.p, mp->xyz.p,
                                     mp->n_out.p, mp->w_out.p, mp->key_out.p));
     if (xyz_host) HIP_TRY(hipMemcpyAsync(xyz_host, mp->xyz.p, 3 * total * sizeof(float), hipMemcpyDeviceToHost, st));
     if (n_points_host) HIP_TRY(hipMemcpyAsync(n_points_host, mp->n_out.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -4489,7 +4315,7 @@ int dsi_map_render(dsi_map_t* mp, const dsi_map_view_t* view, dsi_map_render_inf
     v.min_points = view->min_points, v.min_windows = view->min_windows;
     const dsi::MapImage img{mp->zkey.p, mp->hits.p, mp->render_windows.p, mp->render_depth.p, mp->render_mask.p};
     unsigned long long ctr[dsi::kMapRenderCounters] = {0, 0, 0, 0, 0};
-    HIP_TRY(dsi::launch_map_render(st, dsi::map_table_at(mp->block, mp->cap_log2), v, mp->leaf, img, mp->render_ctr.p));
+    HIP_TRY(dsi::launch_map_render(st, dsi::map_table_at(mp->block.p, mp->cap_log2), v, mp->leaf, img, mp->render_ctr.p));
     HIP_TRY(hipMemcpyAsync(ctr, mp->render_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     mp->render_valid = true;
@@ -4703,22 +4529,18 @@ DSI_API int dsi_test_div_probe(dsi_context_t* ctx, const float* n, const float* 
 {
     REQUIRE(ctx && n && d && q && ref, DSI_ERR_INVALID, "null argument");
     if (int rc = set_device(ctx)) return rc;
-    float *dn = nullptr, *dd = nullptr, *dq = nullptr, *dr = nullptr;
+    DevBuf<float> dn, dd, dq, dr;
     const size_t bytes = count * sizeof(float);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dn), bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dd), bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dq), bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dr), bytes);
-    if (e == hipSuccess) e = hipMemcpy(dn, n, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dd, d, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = dsi::launch_div_probe(ctx->stream, dn, dd, count, dq, dr);
+    hipError_t e = dn.reserve(count);
+    if (e == hipSuccess) e = dd.reserve(count);
+    if (e == hipSuccess) e = dq.reserve(count);
+    if (e == hipSuccess) e = dr.reserve(count);
+    if (e == hipSuccess) e = hipMemcpy(dn.p, n, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dd.p, d, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = dsi::launch_div_probe(ctx->stream, dn.p, dd.p, count, dq.p, dr.p);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipMemcpy(q, dq, bytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(ref, dr, bytes, hipMemcpyDeviceToHost);
-    if (dn) (void)hipFree(dn);
-    if (dd) (void)hipFree(dd);
-    if (dq) (void)hipFree(dq);
-    if (dr) (void)hipFree(dr);
+    if (e == hipSuccess) e = hipMemcpy(q, dq.p, bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(ref, dr.p, bytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(DSI_ERR_HIP, "div probe failed: %s", hipGetErrorString(e));
     return DSI_OK;
 }
@@ -4739,6 +4561,11 @@ DSI_API int dsi_test_iir_axis(dsi_grid_t* g, int axis, float sigma, int numsteps
 }  // extern "C"
 
 /* ---------------------------------------------------------- multi-GPU (RCCL) */
+struct dsi_comm {
+    ncclComm_t comm = nullptr;
+    int device = 0, rank = 0, size = 1;
+};
+
 namespace {
 
 // librccl entry points, resolved once (see load_rccl for which copy).
@@ -4830,6 +4657,24 @@ int rccl_ready(Rccl** out)
     return DSI_OK;
 }
 
+// One group of collectives, rank i's issued by per_rank(i) on the device of communicator cs[i] (which the caller has
+// checked to be its objects' device): every rank is issued whatever another returned, the first error is the one reported.
+template <typename F>
+int rccl_grouped(Rccl* r, dsi_comm_t* const* cs, int n, const char* what, F per_rank)
+{
+    RCCL_TRY(r, r->GroupStart());
+    ncclResult_t bad = ncclSuccess;
+    for (int i = 0; i < n; ++i) {
+        (void)hipSetDevice(cs[i]->device);
+        const ncclResult_t e = per_rank(i);
+        if (e != ncclSuccess && bad == ncclSuccess) bad = e;
+    }
+    const ncclResult_t e2 = r->GroupEnd();
+    if (bad != ncclSuccess) return fail(DSI_ERR_COMM, "%s failed: %s", what, r->GetErrorString(bad));
+    if (e2 != ncclSuccess) return fail(DSI_ERR_COMM, "ncclGroupEnd failed: %s", r->GetErrorString(e2));
+    return DSI_OK;
+}
+
 bool to_nccl_op(int op, ncclRedOp_t* out)
 {
     switch (op) {
@@ -4841,11 +4686,6 @@ bool to_nccl_op(int op, ncclRedOp_t* out)
 }
 
 }  // namespace
-
-struct dsi_comm {
-    ncclComm_t comm = nullptr;
-    int device = 0, rank = 0, size = 1;
-};
 
 extern "C" {
 
@@ -4967,25 +4807,16 @@ int dsi_grid_allreduce_all(dsi_comm_t* const* comms, dsi_grid_t* const* grids, i
     }
     Rccl* r = nullptr;
     if (int rc = rccl_ready(&r)) return rc;
-    RCCL_TRY(r, r->GroupStart());
-    ncclResult_t bad = ncclSuccess;
-    for (int i = 0; i < n; ++i) {
-        (void)hipSetDevice(grids[i]->ctx->device);
-        const ncclResult_t e = r->AllReduce(grids[i]->data, grids[i]->data, grids[i]->n, ncclFloat32, nop,
-                                            comms[i]->comm, grids[i]->ctx->stream);
-        if (e != ncclSuccess && bad == ncclSuccess) bad = e;
-    }
-    const ncclResult_t e2 = r->GroupEnd();
-    if (bad != ncclSuccess) return fail(DSI_ERR_COMM, "ncclAllReduce failed: %s", r->GetErrorString(bad));
-    if (e2 != ncclSuccess) return fail(DSI_ERR_COMM, "ncclGroupEnd failed: %s", r->GetErrorString(e2));
-    return DSI_OK;
+    return rccl_grouped(r, comms, n, "ncclAllReduce", [&](int i) {
+        return r->AllReduce(grids[i]->data, grids[i]->data, grids[i]->n, ncclFloat32, nop, comms[i]->comm, grids[i]->ctx->stream);
+    });
 }
 
 static int ensure_planes_full_dev(dsi_mapper_t* m)
 {
-    if (m->planes_full_dev) return DSI_OK;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->planes_full_dev), m->planes_full.size() * sizeof(float)));
-    HIP_TRY(hipMemcpyAsync(m->planes_full_dev, m->planes_full.data(), m->planes_full.size() * sizeof(float),
+    if (m->planes_full_dev.p) return DSI_OK;
+    HIP_TRY(m->planes_full_dev.reserve(m->planes_full.size()));
+    HIP_TRY(hipMemcpyAsync(m->planes_full_dev.p, m->planes_full.data(), m->planes_full.size() * sizeof(float),
                            hipMemcpyHostToDevice, m->ctx->stream));
     HIP_TRY(hipStreamSynchronize(m->ctx->stream));  // the source is host memory of this object: simplest
     return DSI_OK;
@@ -5018,7 +4849,7 @@ static int sharded_finish(dsi_mapper_t* m)
 {
     const size_t npix = (size_t)m->geom.nx * m->geom.ny;
     HIP_TRY(hipSetDevice(m->ctx->device));
-    HIP_TRY(dsi::launch_unpack_argmax(m->ctx->stream, m->argmax_keys.p, (int)npix, m->planes_full_dev, m->conf.p,
+    HIP_TRY(dsi::launch_unpack_argmax(m->ctx->stream, m->argmax_keys.p, (int)npix, m->planes_full_dev.p, m->conf.p,
                                       m->idx.p, m->depth.p));
     return depth_buffers_ready(m);
 }
@@ -5036,6 +4867,14 @@ int dsi_mapper_depth_map_sharded(dsi_mapper_t* m, dsi_grid_t* g, dsi_comm_t* c)
     return sharded_finish(m);
 }
 
+// the all-reduce(MAX) of every rank's packed arg-max keys, as one group
+static int keys_allreduce_grouped(Rccl* r, dsi_mapper_t* const* ms, dsi_comm_t* const* cs, int n, size_t npix)
+{
+    return rccl_grouped(r, cs, n, "ncclAllReduce", [&](int i) {
+        return r->AllReduce(ms[i]->argmax_keys.p, ms[i]->argmax_keys.p, npix, ncclUint64, ncclMax, cs[i]->comm, ms[i]->ctx->stream);
+    });
+}
+
 int dsi_mapper_depth_map_sharded_all(dsi_mapper_t* const* ms, dsi_grid_t* const* gs, dsi_comm_t* const* cs, int n)
 {
     REQUIRE(ms && gs && cs && n >= 1, DSI_ERR_INVALID, "bad argument");
@@ -5049,17 +4888,7 @@ int dsi_mapper_depth_map_sharded_all(dsi_mapper_t* const* ms, dsi_grid_t* const*
     Rccl* r = nullptr;
     if (int rc = rccl_ready(&r)) return rc;
     const size_t npix = (size_t)ms[0]->geom.nx * ms[0]->geom.ny;
-    RCCL_TRY(r, r->GroupStart());
-    ncclResult_t bad = ncclSuccess;
-    for (int i = 0; i < n; ++i) {
-        (void)hipSetDevice(ms[i]->ctx->device);
-        const ncclResult_t e = r->AllReduce(ms[i]->argmax_keys.p, ms[i]->argmax_keys.p, npix, ncclUint64, ncclMax,
-                                            cs[i]->comm, ms[i]->ctx->stream);
-        if (e != ncclSuccess && bad == ncclSuccess) bad = e;
-    }
-    const ncclResult_t e2 = r->GroupEnd();
-    if (bad != ncclSuccess) return fail(DSI_ERR_COMM, "ncclAllReduce failed: %s", r->GetErrorString(bad));
-    if (e2 != ncclSuccess) return fail(DSI_ERR_COMM, "ncclGroupEnd failed: %s", r->GetErrorString(e2));
+    if (int rc = keys_allreduce_grouped(r, ms, cs, n, npix)) return rc;
     for (int i = 0; i < n; ++i)
         if (int rc = sharded_finish(ms[i])) return rc;
     return DSI_OK;
@@ -5139,11 +4968,7 @@ int dsi_mapper_depth_map_reduce_scattered(dsi_mapper_t* m, dsi_grid_t* acc, dsi_
     ncclRedOp_t nop;
     REQUIRE(to_nccl_op(dsi_acc_reduce_op(mode), &nop), DSI_ERR_BAD_OP, "mode %d has no reduce op", mode);
     if (int rc = set_device(acc->ctx)) return rc;
-    RCCL_TRY(r, r->GroupStart());
-    const ncclResult_t e = scattered_reduce(r, acc, c, nop);
-    const ncclResult_t e2 = r->GroupEnd();
-    if (e != ncclSuccess) return fail(DSI_ERR_COMM, "reduce-scatter failed: %s", r->GetErrorString(e));
-    if (e2 != ncclSuccess) return fail(DSI_ERR_COMM, "ncclGroupEnd failed: %s", r->GetErrorString(e2));
+    if (int rc = rccl_grouped(r, &c, 1, "reduce-scatter", [&](int) { return scattered_reduce(r, acc, c, nop); })) return rc;
     if (int rc = scattered_local(m, acc, c->size, c->rank, mode, n_maps)) return rc;
     const size_t npix = (size_t)acc->nx * acc->ny;
     RCCL_TRY(r, r->AllReduce(m->argmax_keys.p, m->argmax_keys.p, npix, ncclUint64, ncclMax, c->comm, m->ctx->stream));
@@ -5162,29 +4987,11 @@ int dsi_mapper_depth_map_reduce_scattered_all(dsi_mapper_t* const* ms, dsi_grid_
     if (int rc = rccl_ready(&r)) return rc;
     ncclRedOp_t nop;
     REQUIRE(to_nccl_op(dsi_acc_reduce_op(mode), &nop), DSI_ERR_BAD_OP, "mode %d has no reduce op", mode);
-    RCCL_TRY(r, r->GroupStart());
-    ncclResult_t bad = ncclSuccess;
-    for (int i = 0; i < n; ++i) {
-        (void)hipSetDevice(accs[i]->ctx->device);
-        const ncclResult_t e = scattered_reduce(r, accs[i], cs[i], nop);
-        if (e != ncclSuccess && bad == ncclSuccess) bad = e;
-    }
-    ncclResult_t e2 = r->GroupEnd();
-    if (bad != ncclSuccess) return fail(DSI_ERR_COMM, "reduce-scatter failed: %s", r->GetErrorString(bad));
-    if (e2 != ncclSuccess) return fail(DSI_ERR_COMM, "ncclGroupEnd failed: %s", r->GetErrorString(e2));
+    if (int rc = rccl_grouped(r, cs, n, "reduce-scatter", [&](int i) { return scattered_reduce(r, accs[i], cs[i], nop); }))
+        return rc;
     for (int i = 0; i < n; ++i)
         if (int rc = scattered_local(ms[i], accs[i], cs[i]->size, cs[i]->rank, mode, n_maps)) return rc;
-    const size_t npix = (size_t)accs[0]->nx * accs[0]->ny;
-    RCCL_TRY(r, r->GroupStart());
-    for (int i = 0; i < n; ++i) {
-        (void)hipSetDevice(ms[i]->ctx->device);
-        const ncclResult_t e = r->AllReduce(ms[i]->argmax_keys.p, ms[i]->argmax_keys.p, npix, ncclUint64, ncclMax, cs[i]->comm,
-                                            ms[i]->ctx->stream);
-        if (e != ncclSuccess && bad == ncclSuccess) bad = e;
-    }
-    e2 = r->GroupEnd();
-    if (bad != ncclSuccess) return fail(DSI_ERR_COMM, "ncclAllReduce failed: %s", r->GetErrorString(bad));
-    if (e2 != ncclSuccess) return fail(DSI_ERR_COMM, "ncclGroupEnd failed: %s", r->GetErrorString(e2));
+    if (int rc = keys_allreduce_grouped(r, ms, cs, n, (size_t)accs[0]->nx * accs[0]->ny)) return rc;
     for (int i = 0; i < n; ++i)
         if (int rc = sharded_finish(ms[i])) return rc;
     return DSI_OK;

@@ -2,12 +2,12 @@
 against a literal restatement of process2.cpp / process5.cpp), the planner's fixed limits and the ISA of the new kernel."""
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
 from dvs_mcemvs_amd import engine as E, process
+from kernel_asm import _hipcc, kernel_asm_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -87,23 +87,11 @@ def test_planner(built):
     assert process.alg2_plan(2, 1_000, 4097, camera_time=False) == "materialize"
 
 
-def _hipcc():
-    for cand in (shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if cand and os.path.exists(cand):
-            return cand
-    return None
-
-
 @pytest.mark.skipif(_hipcc() is None, reason="hipcc not available")
-def test_alg2_kernels_isa(tmp_path):
+def test_alg2_kernels_isa():
     """Every instantiation of k_vote_fuse_argmax_alg2 (lane mappings 1, 3, 5, 6 x camera_time on / off): no scratch, no
     VGPR spills, at most 128 VGPRs (one 1024-thread workgroup per CU)."""
-    out = tmp_path / "dsi_kernels.s"
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-x", "hip",
-                           "-S", "--cuda-device-only", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "dvs_mcemvs_amd", "csrc", "dsi_kernels.hip"), "-o", str(out)],
-                          stderr=subprocess.DEVNULL)
-    text = out.read_text()
+    text = kernel_asm_text()
     seen = set()
     for block in text.split("  - .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)

@@ -5,13 +5,13 @@ against mpmath, the k_focus_* / k_collapse_min_z ISA (no scratch, no spills) and
 refuse to run without a GPU)."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import focus_reference as fr
+from kernel_asm import _hipcc, kernel_asm_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -119,21 +119,9 @@ def test_gaussian_taps_are_the_correctly_rounded_normalised_gaussian():
     assert bits == [0x3f495cb3, 0x3dda02dd, 0x398a575f, 0x3eff5285, 0x3e69ca49, 0x3cb37d42, 0x39e71393]
 
 
-def _hipcc():
-    for cand in (shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if cand and os.path.exists(cand):
-            return cand
-    return None
-
-
 @pytest.mark.skipif(_hipcc() is None, reason="hipcc not available")
-def test_focus_kernels_isa(tmp_path):
-    out = tmp_path / "dsi_kernels.s"
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-x", "hip",
-                           "-S", "--cuda-device-only", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "dvs_mcemvs_amd", "csrc", "dsi_kernels.hip"), "-o", str(out)],
-                          stderr=subprocess.DEVNULL)
-    text = out.read_text()
+def test_focus_kernels_isa():
+    text = kernel_asm_text()
     seen = set()
     for block in text.split("  - .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)

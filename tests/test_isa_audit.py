@@ -2,31 +2,16 @@
 wave loops name physical registers, so the kernels must not spill vector registers nor use scratch,
 and must stay within 64 VGPRs (8 waves per SIMD = two 1024-thread workgroups per CU; 128 for the
 vector-fill kernels, which run one workgroup per CU)."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _hipcc():
-    for cand in (shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if cand and os.path.exists(cand):
-            return cand
-    return None
+from kernel_asm import _hipcc, kernel_asm_text
 
 
 @pytest.mark.skipif(_hipcc() is None, reason="hipcc not available")
-def test_vote_kernels_do_not_spill(tmp_path):
-    out = tmp_path / "dsi_kernels.s"
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-x", "hip",
-                           "-S", "--cuda-device-only", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "dvs_mcemvs_amd", "csrc", "dsi_kernels.hip"), "-o", str(out)],
-                          stderr=subprocess.DEVNULL)
-    text = out.read_text()
+def test_vote_kernels_do_not_spill():
+    text = kernel_asm_text()
     seen = 0
     for block in text.split("  - .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)

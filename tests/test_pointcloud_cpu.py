@@ -4,7 +4,6 @@ kernels use no scratch and do not spill and the back-projection's double divide 
 sequences, and the C++ call sites compile (and refuse to run without a GPU)."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 
 import pointcloud_reference as ref
 from dvs_mcemvs_amd import io as dio
+from kernel_asm import _hipcc, kernel_asm_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -81,21 +81,9 @@ def test_save_pcd_ascii(tmp_path):
     assert el[6] == "WIDTH 0" and el[9] == "POINTS 0" and el[10] == "DATA ascii" and el[11:] == [""]
 
 
-def _hipcc():
-    for cand in (shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if cand and os.path.exists(cand):
-            return cand
-    return None
-
-
 @pytest.mark.skipif(_hipcc() is None, reason="hipcc not available")
-def test_pointcloud_kernels_isa(tmp_path):
-    out = tmp_path / "dsi_kernels.s"
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-x", "hip",
-                           "-S", "--cuda-device-only", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "dvs_mcemvs_amd", "csrc", "dsi_kernels.hip"), "-o", str(out)],
-                          stderr=subprocess.DEVNULL)
-    text = out.read_text()
+def test_pointcloud_kernels_isa():
+    text = kernel_asm_text()
     seen = set()
     for block in text.split("  - .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)

@@ -4,7 +4,6 @@ adapter on stand-in camera types."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -14,6 +13,7 @@ import dvs_mcemvs_amd as d
 import rectify_cases as cases
 import rectify_reference as rr
 from dvs_mcemvs_amd import engine
+from kernel_asm import _hipcc, kernel_asm_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -228,23 +228,11 @@ def test_cpp_lens_of_reads_stand_in_camera_types(built, tmp_path):
     assert np.array_equal(nums(("own", "K")), [100, 0, 50, 0, 101, 40, 0, 0, 1])
 
 
-def _hipcc():
-    for cand in (shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if cand and os.path.exists(cand):
-            return cand
-    return None
-
-
 @pytest.mark.skipif(_hipcc() is None, reason="hipcc not available")
-def test_rectify_kernels_use_registers_only(tmp_path):
+def test_rectify_kernels_use_registers_only():
     """k_rectify_lut<plumb_bob> and <fisheye>: no scratch, no spills, no LDS, no atomics; 256-thread workgroups; the
     coefficients and RR (21 doubles) arrive in the kernel-argument segment."""
-    out = tmp_path / "dsi_kernels.s"
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-x", "hip",
-                           "-S", "--cuda-device-only", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "dvs_mcemvs_amd", "csrc", "dsi_kernels.hip"), "-o", str(out)],
-                          stderr=subprocess.DEVNULL)
-    text = out.read_text()
+    text = kernel_asm_text()
     seen = set()
     for block in text.split("  - .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)

@@ -4,7 +4,6 @@ checks, the reference-spelled C++ call sites, and the resource usage of the new 
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -13,6 +12,7 @@ import pytest
 import dvs_mcemvs_amd as d
 import run_images_reference as rr
 from dvs_mcemvs_amd import engine, io as dio
+from kernel_asm import _hipcc, kernel_asm_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -204,21 +204,9 @@ def test_cpp_png_rgb8_writer_decodes_to_the_bytes_written(built, tmp_path):
         assert ctype == 2 and np.array_equal(px, want[:, :, ::-1])
 
 
-def _hipcc():
-    for cand in (shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if cand and os.path.exists(cand):
-            return cand
-    return None
-
-
 @pytest.mark.skipif(_hipcc() is None, reason="hipcc not available")
-def test_run_image_kernels_use_no_scratch(tmp_path):
-    out = tmp_path / "dsi_kernels.s"
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-x", "hip",
-                           "-S", "--cuda-device-only", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "dvs_mcemvs_amd", "csrc", "dsi_kernels.hip"), "-o", str(out)],
-                          stderr=subprocess.DEVNULL)
-    text = out.read_text()
+def test_run_image_kernels_use_no_scratch():
+    text = kernel_asm_text()
     seen = set()
     for block in text.split("  - .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)

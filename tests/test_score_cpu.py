@@ -6,7 +6,6 @@ import ctypes
 import math
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,6 +14,7 @@ import pytest
 import dvs_mcemvs_amd as d
 import score_reference as sr
 from dvs_mcemvs_amd import engine, io as dio, process
+from kernel_asm import _hipcc, kernel_asm_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -239,21 +239,9 @@ def test_cpp_call_sites_compile_and_refuse_without_gpu(built, tmp_path):
         assert r.returncode != 0 and "no HIP device" in (r.stdout + r.stderr)
 
 
-def _hipcc():
-    for cand in (shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if cand and os.path.exists(cand):
-            return cand
-    return None
-
-
 @pytest.mark.skipif(_hipcc() is None, reason="hipcc not available")
-def test_score_kernels_use_no_scratch(tmp_path):
-    out = tmp_path / "dsi_kernels.s"
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-x", "hip",
-                           "-S", "--cuda-device-only", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "dvs_mcemvs_amd", "csrc", "dsi_kernels.hip"), "-o", str(out)],
-                          stderr=subprocess.DEVNULL)
-    text = out.read_text()
+def test_score_kernels_use_no_scratch():
+    text = kernel_asm_text()
     seen = set()
     for block in text.split("  - .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)
