@@ -8,6 +8,7 @@
 // Every object owns its device memory, events and streams through the move-only members of dsi_owned.hpp: `delete obj`
 // frees them (in reverse order of declaration), a dsi_*_destroy only checks, synchronises and counts before it.
 #include "../../include/dsi_engine.h"
+#include "../../include/dsi_map_eval.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: librccl is loaded at run time (load_rccl)
@@ -23,6 +24,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <new>
@@ -4056,6 +4058,12 @@ struct dsi_map {
     DevBuf<uint8_t> render_mask;
     int render_width = 0, render_height = 0;
     bool render_valid = false;
+    // the last compare with this map as the first (dsx_map_compare, include/dsi_map_eval.h): valid until the map changes
+    DevBuf<uint8_t> depth_mask;          // dsx_map_integrate_depth's mask upload
+    DevBuf<float> cmp_dist, cmp_dist_out;  // per slot; compacted for a fetch
+    DevBuf<unsigned long long> cmp_hist, cmp_ctr;
+    uint32_t cmp_min_points = 0, cmp_min_windows = 0;
+    bool compare_valid = false;
 };
 
 namespace {
@@ -4095,10 +4103,11 @@ int map_grow_for(dsi_map* mp, size_t n)
     return DSI_OK;
 }
 
-// one integrate call of n device points (stride floats each) on the map's stream; synchronises
-int map_integrate_device(dsi_map* mp, const float* pts_dev, size_t stride, size_t n, const double T_w_rv[12], size_t* n_rejected)
+// one integrate call of at most n points on the map's stream, made by launch(serial, table); synchronises
+int map_integrate_call(dsi_map* mp, size_t n, const std::function<hipError_t(uint32_t, const dsi::MapTable&)>& launch, size_t* n_accepted,
+                       size_t* n_rejected)
 {
-    mp->render_valid = false;  // (the map may change from here on)
+    mp->render_valid = mp->compare_valid = false;  // (the map may change from here on)
     REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
     REQUIRE(mp->calls < 0xffffffffull, DSI_ERR_INVALID, "at most 2^32 - 1 integrate calls per map");
     REQUIRE((mp->host_ctr[0] + n) * 4 <= ((uint64_t)3 << kMapMaxLog2), DSI_ERR_INVALID,
@@ -4106,15 +4115,26 @@ int map_integrate_device(dsi_map* mp, const float* pts_dev, size_t stride, size_
     if (int rc = map_grow_for(mp, n)) return rc;
     hipStream_t st = mp->ctx->stream;
     const uint32_t serial = (uint32_t)++mp->calls;
-    const unsigned long long rejected_before = mp->host_ctr[2];
-    HIP_TRY(dsi::launch_map_integrate(st, pts_dev, (uint32_t)stride, (uint32_t)n, T_w_rv, mp->leaf, serial,
-                                      dsi::map_table_at(mp->block.p, mp->cap_log2), mp->ctr.p));
+    const unsigned long long accepted_before = mp->host_ctr[1], rejected_before = mp->host_ctr[2];
+    HIP_TRY(launch(serial, dsi::map_table_at(mp->block.p, mp->cap_log2)));
     HIP_TRY(hipMemcpyAsync(mp->host_ctr, mp->ctr.p, sizeof mp->host_ctr, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_HIP, "the map's table ran full (%llu points lost): an engine bug, the map is unusable",
             mp->host_ctr[3]);
+    if (n_accepted) *n_accepted = (size_t)(mp->host_ctr[1] - accepted_before);
     if (n_rejected) *n_rejected = (size_t)(mp->host_ctr[2] - rejected_before);
     return DSI_OK;
+}
+
+// one integrate call of n device points (stride floats each)
+int map_integrate_device(dsi_map* mp, const float* pts_dev, size_t stride, size_t n, const double T_w_rv[12], size_t* n_rejected)
+{
+    return map_integrate_call(
+        mp, n,
+        [&](uint32_t serial, const dsi::MapTable& t) {
+            return dsi::launch_map_integrate(mp->ctx->stream, pts_dev, (uint32_t)stride, (uint32_t)n, T_w_rv, mp->leaf, serial, t, mp->ctr.p);
+        },
+        nullptr, n_rejected);
 }
 
 int check_map_pose(const double T[12])
@@ -4191,7 +4211,7 @@ int dsi_map_destroy(dsi_map_t* mp)
 int dsi_map_reset(dsi_map_t* mp)
 {
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
-    mp->render_valid = false;
+    mp->render_valid = mp->compare_valid = false;
     if (int rc = set_device(mp->ctx)) return rc;
     HIP_TRY(hipMemsetAsync(mp->block.p, 0, dsi::map_table_bytes(mp->cap_log2), mp->ctx->stream));
     HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof mp->host_ctr, mp->ctx->stream));
@@ -4380,6 +4400,149 @@ int dsi_score_add_map_render_gt(dsi_score_t* s, dsi_map_t* mp, dsi_gt_t* gt)
             mp->render_height, gt->width, gt->height);
     if (int rc = set_device(s->ctx)) return rc;
     return score_add_device(s, mp->render_depth.p, mp->render_mask.p, gt_out(gt), npix);
+}
+
+// ---- the map scored in 3-D (include/dsi_map_eval.h; DESIGN.md 7j "Scoring the map in 3-D") ----
+
+namespace {
+
+// dsi_map_view_t's bounds on a depth image and its pinhole: decided without a device, before any handle is looked at
+int check_depth_image(int32_t width, int32_t height, double fx, double fy, double cx, double cy, double min_depth, double max_depth)
+{
+    REQUIRE(width >= 1 && height >= 1, DSI_ERR_INVALID, "the image must be at least 1 x 1 (got %d x %d)", width, height);
+    REQUIRE((uint64_t)width * (uint64_t)height <= ((uint64_t)1 << kMapViewMaxLog2), DSI_ERR_INVALID,
+            "an image holds at most 2^%d pixels (got %d x %d)", kMapViewMaxLog2, width, height);
+    REQUIRE(std::isfinite(fx) && std::isfinite(fy) && fx != 0.0 && fy != 0.0, DSI_ERR_INVALID,
+            "fx and fy must be finite and not 0 (got %g, %g)", fx, fy);
+    REQUIRE(std::isfinite(cx) && std::isfinite(cy), DSI_ERR_INVALID, "cx and cy must be finite (got %g, %g)", cx, cy);
+    REQUIRE(std::isfinite(min_depth) && std::isfinite(max_depth) && min_depth >= (double)FLT_MIN && min_depth < max_depth &&
+                max_depth <= (double)FLT_MAX,
+            DSI_ERR_INVALID, "the depth range must satisfy FLT_MIN <= min_depth < max_depth <= FLT_MAX (got %g, %g)", min_depth,
+            max_depth);
+    return DSI_OK;
+}
+
+// one integrate call of a device depth image (mask_dev may be null); the table grows for width * height points
+int map_integrate_depth_device(dsi_map* mp, const float* depth_dev, const uint8_t* mask_dev, int32_t width, int32_t height, double fx,
+                               double fy, double cx, double cy, double min_depth, double max_depth, const double T_w_c[12],
+                               uint64_t* n_points, uint64_t* n_rejected)
+{
+    const dsi::MapDepthImage g{(uint32_t)width, (uint32_t)width * (uint32_t)height, fx, fy, cx, cy, min_depth, max_depth};
+    size_t accepted = 0, rejected = 0;
+    if (int rc = map_integrate_call(
+            mp, g.npix,
+            [&](uint32_t serial, const dsi::MapTable& t) {
+                return dsi::launch_map_integrate_depth(mp->ctx->stream, depth_dev, mask_dev, g, T_w_c, mp->leaf, serial, t, mp->ctr.p);
+            },
+            &accepted, &rejected))
+        return rc;
+    if (n_points) *n_points = (uint64_t)accepted + (uint64_t)rejected;
+    if (n_rejected) *n_rejected = rejected;
+    return DSI_OK;
+}
+
+}  // namespace
+
+int dsx_map_integrate_depth(dsi_map_t* mp, const float* depth_host, const uint8_t* mask_host, int32_t width, int32_t height, double fx,
+                            double fy, double cx, double cy, double min_depth, double max_depth, const double T_w_c[12],
+                            uint64_t* n_points, uint64_t* n_rejected)
+{
+    if (int rc = check_depth_image(width, height, fx, fy, cx, cy, min_depth, max_depth)) return rc;
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    REQUIRE(depth_host, DSI_ERR_INVALID, "depth_host is null");
+    REQUIRE(T_w_c, DSI_ERR_INVALID, "T_w_c is null");
+    if (int rc = set_device(mp->ctx)) return rc;
+    const size_t npix = (size_t)width * (size_t)height;
+    hipStream_t st = mp->ctx->stream;
+    HIP_TRY(mp->upload.reserve(npix));
+    HIP_TRY(hipMemcpyAsync(mp->upload.p, depth_host, npix * sizeof(float), hipMemcpyHostToDevice, st));
+    if (mask_host) {
+        HIP_TRY(mp->depth_mask.reserve(npix));
+        HIP_TRY(hipMemcpyAsync(mp->depth_mask.p, mask_host, npix, hipMemcpyHostToDevice, st));
+    }
+    return map_integrate_depth_device(mp, mp->upload.p, mask_host ? mp->depth_mask.p : nullptr, width, height, fx, fy, cx, cy, min_depth,
+                                      max_depth, T_w_c, n_points, n_rejected);
+}
+
+int dsx_map_integrate_depth_gt(dsi_map_t* mp, dsi_gt_t* gt, double fx, double fy, double cx, double cy, double min_depth, double max_depth,
+                               const double T_w_c[12], uint64_t* n_points, uint64_t* n_rejected)
+{
+    if (int rc = check_depth_image(1, 1, fx, fy, cx, cy, min_depth, max_depth)) return rc;  // (the pinhole, with no handle at hand)
+    REQUIRE(mp && gt, DSI_ERR_INVALID, "null argument");
+    REQUIRE(T_w_c, DSI_ERR_INVALID, "T_w_c is null");
+    REQUIRE(mp->ctx == gt->ctx, DSI_ERR_CONTEXT, "the map and the projector live on different contexts");
+    if (int rc = check_depth_image(gt->width, gt->height, fx, fy, cx, cy, min_depth, max_depth)) return rc;
+    if (int rc = set_device(mp->ctx)) return rc;
+    return map_integrate_depth_device(mp, gt_out(gt), nullptr, gt->width, gt->height, fx, fy, cx, cy, min_depth, max_depth, T_w_c,
+                                      n_points, n_rejected);
+}
+
+int dsx_map_compare(dsi_map_t* a, dsi_map_t* b, const dsx_map_compare_opts_t* opts, uint64_t* hist_host, dsx_map_compare_info_t* info)
+{
+    // (the options first: radius and n_bins can then be exercised without a device, with no map at hand)
+    REQUIRE(opts, DSI_ERR_INVALID, "opts is null");
+    REQUIRE(std::isfinite(opts->radius) && opts->radius > 0.0, DSI_ERR_INVALID, "radius must be finite and > 0 (got %g)", opts->radius);
+    REQUIRE(opts->n_bins >= 1 && opts->n_bins <= dsi::kMapCompareMaxBins, DSI_ERR_INVALID, "n_bins must be in 1..%d (got %d)",
+            dsi::kMapCompareMaxBins, opts->n_bins);
+    const double bin_width = opts->radius / (double)opts->n_bins;
+    REQUIRE(bin_width > 0.0, DSI_ERR_INVALID, "radius / n_bins underflows to 0 (radius %g, n_bins %d)", opts->radius, opts->n_bins);
+    REQUIRE(a && b, DSI_ERR_INVALID, "map is null");
+    REQUIRE(a->ctx == b->ctx, DSI_ERR_CONTEXT, "the maps live on different contexts");
+    const double reach_d = std::ceil(opts->radius / b->leaf);
+    REQUIRE(reach_d >= 1.0 && reach_d <= (double)dsi::kMapCompareMaxReach, DSI_ERR_INVALID,
+            "reach = ceil(radius / leaf_b) must be in 1..%d (radius %g, leaf_b %g)", dsi::kMapCompareMaxReach, opts->radius, b->leaf);
+    if (int rc = set_device(a->ctx)) return rc;
+    hipStream_t st = a->ctx->stream;
+    a->compare_valid = false;
+    HIP_TRY(a->cmp_dist.reserve((size_t)1 << a->cap_log2));
+    HIP_TRY(a->cmp_hist.reserve(dsi::kMapCompareMaxBins));
+    HIP_TRY(a->cmp_ctr.reserve(dsi::kMapCompareCounters));
+    dsi::MapCompare o;
+    o.leaf_a = a->leaf, o.leaf_b = b->leaf, o.radius = opts->radius, o.bin_width = bin_width;
+    o.min_points_a = opts->min_points_a, o.min_windows_a = opts->min_windows_a;
+    o.min_points_b = opts->min_points_b, o.min_windows_b = opts->min_windows_b;
+    o.reach = (int)reach_d, o.n_bins = opts->n_bins;
+    unsigned long long ctr[dsi::kMapCompareCounters] = {0, 0, 0};
+    HIP_TRY(dsi::launch_map_compare(st, dsi::map_table_at(a->block.p, a->cap_log2), dsi::map_table_at(b->block.p, b->cap_log2), o,
+                                    a->cmp_dist.p, a->cmp_hist.p, a->cmp_ctr.p));
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "64-bit counts");
+    if (hist_host)
+        HIP_TRY(hipMemcpyAsync(hist_host, a->cmp_hist.p, (size_t)opts->n_bins * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ctr, a->cmp_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    a->cmp_min_points = opts->min_points_a;
+    a->cmp_min_windows = opts->min_windows_a;
+    a->compare_valid = true;
+    if (info) {
+        info->n_cells = ctr[0] + ctr[1];
+        info->n_matched = ctr[0];
+        info->n_unmatched = ctr[1];
+        info->sum_q = ctr[2];
+        info->reach = o.reach;
+    }
+    return DSI_OK;
+}
+
+int dsx_map_compare_fetch(dsi_map_t* a, float* dist_host, uint64_t* keys_host, size_t capacity, size_t* n)
+{
+    REQUIRE(a && n, DSI_ERR_INVALID, "null argument");
+    REQUIRE(a->compare_valid, DSI_ERR_INVALID,
+            "no compare of the map as it stands: call dsx_map_compare (after the last dsi_map_reset or integrate call)");
+    if (int rc = set_device(a->ctx)) return rc;
+    size_t total = 0;
+    if (int rc = map_count_device(a, a->cmp_min_points, a->cmp_min_windows, &total)) return rc;
+    *n = total;
+    REQUIRE(capacity >= total, DSI_ERR_INVALID, "capacity of %zu cells is too small: %zu needed", capacity, total);
+    if (!total) return DSI_OK;
+    hipStream_t st = a->ctx->stream;
+    HIP_TRY(a->cmp_dist_out.reserve(total));
+    HIP_TRY(a->key_out.reserve(total));
+    HIP_TRY(dsi::launch_map_compare_gather(st, dsi::map_table_at(a->block.p, a->cap_log2), a->cmp_min_points, a->cmp_min_windows,
+                                           a->cmp_dist.p, a->blk.p, a->cmp_dist_out.p, a->key_out.p));
+    if (dist_host) HIP_TRY(hipMemcpyAsync(dist_host, a->cmp_dist_out.p, total * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (keys_host) HIP_TRY(hipMemcpyAsync(keys_host, a->key_out.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
 }
 
 int dsi_mapper_last_vote_info(const dsi_mapper_t* m, dsi_vote_info_t* info)

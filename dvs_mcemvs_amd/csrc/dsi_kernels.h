@@ -371,6 +371,31 @@ constexpr int kMapRenderCounters = 5;  // cells that passed the filter, clipped,
 // clears zkey (all ones), hits and ctr, draws every cell that passes v's filter and unpacks the image; ctr: kMapRenderCounters u64
 hipError_t launch_map_render(hipStream_t s, const MapTable& t, const MapView& v, double leaf, const MapImage& img, unsigned long long* ctr);
 
+// ---- the map scored in 3-D (include/dsi_map_eval.h; DESIGN.md 7j "Scoring the map in 3-D") ----
+// a depth image (width * height = npix <= 2^26 pixels, row-major) and its pinhole; the host has checked every bound
+struct MapDepthImage {
+    uint32_t width, npix;
+    double fx, fy, cx, cy, min_depth, max_depth;
+};
+// one integrate call of the image's pixels (device arrays; mask may be NULL), by rules 1-4; ctr and the caller's duty as
+// launch_map_integrate's, with the call's point count bounded by npix
+hipError_t launch_map_integrate_depth(hipStream_t s, const float* depth, const uint8_t* mask, const MapDepthImage& g,
+                                      const double T_w_c[12], double leaf, uint32_t serial, const MapTable& t, unsigned long long* ctr);
+constexpr int kMapCompareMaxBins = 4096, kMapCompareMaxReach = 3;
+constexpr int kMapCompareCounters = 3;  // matched, unmatched, sum_q
+struct MapCompare {
+    double leaf_a, leaf_b, radius, bin_width;  // bin_width = radius / n_bins > 0
+    uint32_t min_points_a, min_windows_a, min_points_b, min_windows_b;
+    int reach, n_bins;                         // 1..kMapCompareMaxReach, 1..kMapCompareMaxBins
+};
+// clears hist [n_bins] and ctr [kMapCompareCounters], then every filtered cell of a against b; dist: one float per slot of a
+// (written for the cells that pass a's filter)
+hipError_t launch_map_compare(hipStream_t s, const MapTable& a, const MapTable& b, const MapCompare& o, float* dist,
+                              unsigned long long* hist, unsigned long long* ctr);
+// after launch_map_count(t, min_points, min_windows): key and dist of the filtered cells in slot order (launch_map_extract's)
+hipError_t launch_map_compare_gather(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, const float* dist,
+                                     const uint32_t* blk, float* dist_out, unsigned long long* key_out);
+
 // focus-based collapses (Grid3D::collapseZSliceBy*, cartesian3dgrid.cpp:192-414; DESIGN.md "Focus-based collapses"):
 // method 0 LocalVar, 1 LocalMeanSquare, 2 GradMag (half_patchsize 0..8), 3 LaplacianMag, 4 DoG.  keys: scratch of
 // focus_chunks(nx, ny, nz) * nx * ny words, fully written before it is read.  planes / depth as launch_collapse_max_z.

@@ -6819,6 +6819,31 @@ __device__ inline uint32_t map_slot(unsigned long long* keys, uint32_t mask, uns
     return ~0u;
 }
 
+// rules 1-4 for one float32 point (x, y, z widened to double): the one routine every integrate kernel calls.  *ok: merged into
+// its cell; *fresh: that cell is new; *full: no slot left (neither set: the point is rejected by rule 3)
+__device__ inline void map_integrate_point(double x, double y, double z, const MapPose& T, double leaf, uint32_t serial, const MapTable& t,
+                                           bool* ok, bool* fresh, bool* full)
+{
+    const double X = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
+    const double Y = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
+    const double Z = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
+    int cx, cy, cz;
+    unsigned long long Fx, Fy, Fz;
+    if (map_axis(X, leaf, &cx, &Fx) && map_axis(Y, leaf, &cy, &Fy) && map_axis(Z, leaf, &cz, &Fz)) {
+        const uint32_t slot = map_slot(t.keys, (1u << t.cap_log2) - 1u, pc_key(cx, cy, cz), fresh);
+        if (slot == ~0u) {
+            *full = true;
+        } else {
+            *ok = true;
+            atomicAdd(&t.n[slot], 1u);
+            atomicAdd(&t.sums[3 * (size_t)slot + 0], Fx);
+            atomicAdd(&t.sums[3 * (size_t)slot + 1], Fy);
+            atomicAdd(&t.sums[3 * (size_t)slot + 2], Fz);
+            if (atomicExch(&t.stamp[slot], serial) != serial) atomicAdd(&t.windows[slot], 1u);
+        }
+    }
+}
+
 // one thread per point; pts: n points of `stride` floats, x y z first
 __global__ void __launch_bounds__(kPcBlock) k_map_integrate(const float* __restrict__ pts, uint32_t stride, uint32_t n, MapPose T,
                                                             double leaf, uint32_t serial, MapTable t, unsigned long long* __restrict__ ctr)
@@ -6827,25 +6852,7 @@ __global__ void __launch_bounds__(kPcBlock) k_map_integrate(const float* __restr
     bool ok = false, fresh = false, full = false;
     if (i < n) {
         const float* p = pts + (size_t)i * stride;
-        const double x = (double)p[0], y = (double)p[1], z = (double)p[2];
-        const double X = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
-        const double Y = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
-        const double Z = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
-        int cx, cy, cz;
-        unsigned long long Fx, Fy, Fz;
-        if (map_axis(X, leaf, &cx, &Fx) && map_axis(Y, leaf, &cy, &Fy) && map_axis(Z, leaf, &cz, &Fz)) {
-            const uint32_t slot = map_slot(t.keys, (1u << t.cap_log2) - 1u, pc_key(cx, cy, cz), &fresh);
-            if (slot == ~0u) {
-                full = true;
-            } else {
-                ok = true;
-                atomicAdd(&t.n[slot], 1u);
-                atomicAdd(&t.sums[3 * (size_t)slot + 0], Fx);
-                atomicAdd(&t.sums[3 * (size_t)slot + 1], Fy);
-                atomicAdd(&t.sums[3 * (size_t)slot + 2], Fz);
-                if (atomicExch(&t.stamp[slot], serial) != serial) atomicAdd(&t.windows[slot], 1u);
-            }
-        }
+        map_integrate_point((double)p[0], (double)p[1], (double)p[2], T, leaf, serial, t, &ok, &fresh, &full);
     }
     // the counters: one atomic per wave and counter (every lane of the workgroup arrives here)
     const unsigned long long b_new = __ballot(fresh), b_ok = __ballot(ok), b_rej = __ballot(i < n && !ok && !full), b_full = __ballot(full);
@@ -7026,6 +7033,154 @@ __global__ void __launch_bounds__(kPcBlock) k_map_render_finish(const unsigned l
     if (threadIdx.x == 0 && s_cnt) atomicAdd(&ctr[4], (unsigned long long)s_cnt);
 }
 
+// ---- the map scored in 3-D (include/dsi_map_eval.h dsx_map_*; DESIGN.md 7j "Scoring the map in 3-D") ----
+// A depth image as one integrate call: one thread per pixel.  A pixel (u, v) is integrated iff mask is NULL or mask > 0,
+// and d is finite and min_depth <= d <= max_depth (in double; NaN fails); its float32 point is
+// x = (float) ((((double) u - cx) / fx) * (double) d), y alike, z = d, which goes through map_integrate_point: the call
+// is dsi_map_integrate of that point list, bit for bit.  ctr as k_map_integrate's, one global atomic per workgroup and
+// counter (the ballots go to LDS first).
+__global__ void __launch_bounds__(kPcBlock) k_map_integrate_depth(const float* __restrict__ depth, const uint8_t* __restrict__ mask,
+                                                                  MapDepthImage g, MapPose T, double leaf, uint32_t serial, MapTable t,
+                                                                  unsigned long long* __restrict__ ctr)
+{
+    __shared__ uint32_t s_cnt[4];
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kPcBlock + threadIdx.x;  // (npix <= 2^26)
+    bool in = false, ok = false, fresh = false, full = false;
+    if (i < g.npix && (mask == nullptr || mask[i] > 0)) {
+        const float df = depth[i];
+        const double d = (double)df;
+        if (isfinite(d) && d >= g.min_depth && d <= g.max_depth) {
+            in = true;
+            const uint32_t v = i / g.width, u = i - v * g.width;
+            const float x = (float)((((double)u - g.cx) / g.fx) * d);
+            const float y = (float)((((double)v - g.cy) / g.fy) * d);
+            map_integrate_point((double)x, (double)y, d, T, leaf, serial, t, &ok, &fresh, &full);
+        }
+    }
+    const unsigned long long b_new = __ballot(fresh), b_ok = __ballot(ok), b_rej = __ballot(in && !ok && !full), b_full = __ballot(full);
+    if ((threadIdx.x & 63) == 0) {
+        if (b_new) atomicAdd(&s_cnt[0], (uint32_t)__popcll(b_new));
+        if (b_ok) atomicAdd(&s_cnt[1], (uint32_t)__popcll(b_ok));
+        if (b_rej) atomicAdd(&s_cnt[2], (uint32_t)__popcll(b_rej));
+        if (b_full) atomicAdd(&s_cnt[3], (uint32_t)__popcll(b_full));
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
+// the slot of `keys` that holds k, ~0u when none does: read-only, from pc_hash(k) until the key or an empty slot, at
+// most capacity probes (a table without an empty slot ends the loop, it cannot hang)
+__device__ inline uint32_t map_find(const unsigned long long* __restrict__ keys, uint32_t mask, unsigned long long k)
+{
+    uint32_t h = pc_hash(k, mask);
+    for (uint32_t probe = 0; probe <= mask; ++probe) {
+        const unsigned long long kk = keys[h];
+        if (kk == k) return h;
+        if (kk == 0ull) return ~0u;
+        h = (h + 1u) & mask;
+    }
+    return ~0u;
+}
+
+// Every cell of `a` that passes a's filter against the cells of `b` that pass b's: p = a's extracted centroid (float,
+// widened); per axis c = floor(p / leaf_b); the candidates are b's cells at c + o, |o| <= reach per axis, an index with
+// |c + o| > kPcCellMax skipped (tested in double: a huge or non-finite c has no candidates); q = the candidate's extracted
+// centroid; d2 = ((dx dx) + dy dy) + dz dz; the minimum is kept (minima commute: the order of the offsets and of the
+// probing does not matter); d = sqrt(min d2), IEEE; MATCHED iff d <= radius (no candidate: d = +inf).  Matched:
+// hist[min((int) floor(d / w), n_bins - 1)] += 1, sum_q += (u64) floor((d / radius) * 2^32).  dist[slot] = (float) d or
+// +inf.  ctr: [0] matched, [1] unmatched, [2] sum_q.  Workgroups walk a's table in strides as k_map_render does: the
+// wave's ballots are summed in registers, the histogram and sum_q are accumulated in LDS, and a workgroup issues one
+// global atomic per counter and per non-empty bin.  Reads the tables, writes dist: a == b is legal.
+__global__ void __launch_bounds__(kPcBlock) k_map_compare(MapTable a, MapTable b, MapCompare o, float* __restrict__ dist,
+                                                          unsigned long long* __restrict__ hist, unsigned long long* __restrict__ ctr)
+{
+    __shared__ uint32_t s_hist[kMapCompareMaxBins];
+    __shared__ uint32_t s_cnt[2];
+    __shared__ unsigned long long s_sum;
+    for (int j = threadIdx.x; j < o.n_bins; j += kPcBlock) s_hist[j] = 0u;
+    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
+    if (threadIdx.x == 0) s_sum = 0ull;
+    __syncthreads();
+    uint32_t c_match = 0, c_un = 0;  // (the same in every lane of a wave)
+    unsigned long long sum_q = 0ull;
+    const uint32_t bmask = (1u << b.cap_log2) - 1u;
+    const size_t cap = (size_t)1 << a.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        const bool f = map_passes(a, i, o.min_points_a, o.min_windows_a);
+        bool matched = false;
+        if (f) {
+            const unsigned long long k = a.keys[i];
+            const uint32_t n = a.n[i];
+            double p[3], c[3];
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                p[ax] = (double)map_centroid(a, i, k, n, ax, o.leaf_a);
+                c[ax] = floor(p[ax] / o.leaf_b);
+            }
+            double best = INFINITY;
+            for (int oz = -o.reach; oz <= o.reach; ++oz) {
+                const double vz = c[2] + (double)oz;
+                if (!(fabs(vz) <= (double)kPcCellMax)) continue;  // (NaN included)
+                for (int oy = -o.reach; oy <= o.reach; ++oy) {
+                    const double vy = c[1] + (double)oy;
+                    if (!(fabs(vy) <= (double)kPcCellMax)) continue;
+                    for (int ox = -o.reach; ox <= o.reach; ++ox) {
+                        const double vx = c[0] + (double)ox;
+                        if (!(fabs(vx) <= (double)kPcCellMax)) continue;
+                        const unsigned long long kb = pc_key((int)vx, (int)vy, (int)vz);
+                        const uint32_t j = map_find(b.keys, bmask, kb);
+                        if (j == ~0u || !map_passes(b, j, o.min_points_b, o.min_windows_b)) continue;
+                        const uint32_t nb = b.n[j];
+                        const double dx = p[0] - (double)map_centroid(b, j, kb, nb, 0, o.leaf_b);
+                        const double dy = p[1] - (double)map_centroid(b, j, kb, nb, 1, o.leaf_b);
+                        const double dz = p[2] - (double)map_centroid(b, j, kb, nb, 2, o.leaf_b);
+                        const double d2 = ((dx * dx) + dy * dy) + dz * dz;
+                        if (d2 < best) best = d2;
+                    }
+                }
+            }
+            const double d = sqrt(best);
+            matched = d <= o.radius;
+            dist[i] = matched ? (float)d : INFINITY;
+            if (matched) {
+                const int bin = (int)fmin(floor(d / o.bin_width), (double)(o.n_bins - 1));  // (bin_width > 0, d >= 0: in range)
+                atomicAdd(&s_hist[bin], 1u);
+                sum_q += (unsigned long long)floor((d / o.radius) * 4294967296.0);
+            }
+        }
+        c_match += (uint32_t)__popcll(__ballot(matched));
+        c_un += (uint32_t)__popcll(__ballot(f && !matched));
+    }
+    if (sum_q) atomicAdd(&s_sum, sum_q);
+    if ((threadIdx.x & 63) == 0) {
+        if (c_match) atomicAdd(&s_cnt[0], c_match);
+        if (c_un) atomicAdd(&s_cnt[1], c_un);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    if (threadIdx.x == 2 && s_sum) atomicAdd(&ctr[2], s_sum);
+    for (int j = threadIdx.x; j < o.n_bins; j += kPcBlock)
+        if (s_hist[j]) atomicAdd(&hist[j], (unsigned long long)s_hist[j]);
+}
+
+// the compare's distances compacted like k_map_extract's cells (same filter, same blk_off): key and dist in slot order
+__global__ void __launch_bounds__(kPcBlock) k_map_compare_gather(MapTable t, uint32_t min_points, uint32_t min_windows,
+                                                                 const float* __restrict__ dist, const uint32_t* __restrict__ blk_off,
+                                                                 float* __restrict__ dist_out, unsigned long long* __restrict__ key_out)
+{
+    const size_t i = (size_t)blockIdx.x * kPcBlock + threadIdx.x;
+    const bool f = map_passes(t, i, min_points, min_windows);
+    uint32_t total;
+    const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);
+    if (!f) return;
+    const size_t o = (size_t)blk_off[blockIdx.x] + rank;
+    dist_out[o] = dist[i];
+    key_out[o] = t.keys[i];
+}
+
 }  // namespace
 
 size_t map_table_bytes(uint32_t cap_log2) { return ((size_t)1 << cap_log2) * (4 * sizeof(unsigned long long) + 3 * sizeof(uint32_t)); }
@@ -7085,6 +7240,34 @@ hipError_t launch_map_render(hipStream_t s, const MapTable& t, const MapView& v,
                        leaf, img.zkey, img.hits, ctr);
     hipLaunchKernelGGL(k_map_render_finish, dim3(std::min(pc_blocks(npix), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s, img.zkey,
                        img.hits, (uint32_t)npix, img.depth, img.windows, img.mask, ctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_integrate_depth(hipStream_t s, const float* depth, const uint8_t* mask, const MapDepthImage& g,
+                                      const double T_w_c[12], double leaf, uint32_t serial, const MapTable& t, unsigned long long* ctr)
+{
+    MapPose T;
+    for (int k = 0; k < 12; ++k) T.m[k] = T_w_c[k];
+    hipLaunchKernelGGL(k_map_integrate_depth, dim3(pc_blocks(g.npix)), dim3(kPcBlock), 0, s, depth, mask, g, T, leaf, serial, t, ctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_compare(hipStream_t s, const MapTable& a, const MapTable& b, const MapCompare& o, float* dist,
+                              unsigned long long* hist, unsigned long long* ctr)
+{
+    hipError_t e = hipMemsetAsync(hist, 0, (size_t)o.n_bins * sizeof(unsigned long long), s);
+    if (e == hipSuccess) e = hipMemsetAsync(ctr, 0, kMapCompareCounters * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_map_compare, dim3(std::min(pc_blocks((size_t)1 << a.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s, a, b,
+                       o, dist, hist, ctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_compare_gather(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, const float* dist,
+                                     const uint32_t* blk, float* dist_out, unsigned long long* key_out)
+{
+    const uint32_t nb = pc_blocks((size_t)1 << t.cap_log2);
+    hipLaunchKernelGGL(k_map_compare_gather, dim3(nb), dim3(kPcBlock), 0, s, t, min_points, min_windows, dist, blk, dist_out, key_out);
     return hipExtGetLastError();
 }
 

@@ -80,6 +80,16 @@ class _MapRenderInfo(C.Structure):
                 ("n_outside", C.c_uint64), ("n_drawn", C.c_uint64), ("n_pixels", C.c_uint64)]
 
 
+class _MapCompareOpts(C.Structure):
+    _fields_ = [("min_points_a", C.c_uint32), ("min_windows_a", C.c_uint32), ("min_points_b", C.c_uint32),
+                ("min_windows_b", C.c_uint32), ("radius", C.c_double), ("n_bins", C.c_int32)]
+
+
+class _MapCompareInfo(C.Structure):
+    _fields_ = [("n_cells", C.c_uint64), ("n_matched", C.c_uint64), ("n_unmatched", C.c_uint64), ("sum_q", C.c_uint64),
+                ("reach", C.c_int32)]
+
+
 class _ScatterPlan(C.Structure):
     _fields_ = [("q", C.c_int), ("own_begin", C.c_int), ("own_count", C.c_int), ("tail_begin", C.c_int),
                 ("tail_count", C.c_int)]
@@ -331,6 +341,11 @@ def load_library():
         "dsi_reference_accumulate": (C.c_int, [C.c_int, f32p, f32p, C.c_size_t]),
         "dsi_reference_finalize": (C.c_int, [C.c_int, f32p, C.c_size_t, C.c_int]),
         "dsi_mapper_patch_depth_map": (C.c_int, [vp, u32p, u8p, f32p, C.c_size_t]),
+        # include/dsi_map_eval.h: the map scored in 3-D
+        "dsx_map_integrate_depth": (C.c_int, [vp, f32p, u8p, C.c_int32, C.c_int32] + [C.c_double] * 6 + [f64p, u64p, u64p]),
+        "dsx_map_integrate_depth_gt": (C.c_int, [vp, vp] + [C.c_double] * 6 + [f64p, u64p, u64p]),
+        "dsx_map_compare": (C.c_int, [vp, vp, C.POINTER(_MapCompareOpts), u64p, C.POINTER(_MapCompareInfo)]),
+        "dsx_map_compare_fetch": (C.c_int, [vp, f32p, u64p, C.c_size_t, szp]),
     }
     if experiments_requested():     # hooks that exist only in the experiments flavour
         sig.update({
@@ -1125,6 +1140,73 @@ class WorldMap:
                                                None if lut is None else _ptr(lut, C.c_uint8), None, _ptr(bgr, C.c_uint8)))
         return bgr
 
+    def integrateDepth(self, depth, mask, K, min_depth, max_depth, T_w_c):
+        """One call of a depth image (dsx_map_integrate_depth; DESIGN.md 7j "Scoring the map in 3-D"): depth (height, width)
+        float32, mask (the same shape, > 0 keeps a pixel) or None, K = (fx, fy, cx, cy) or a 3 x 3 matrix, T_w_c the camera's
+        pose in the world as pose_matrix takes it.  A pixel is integrated iff it is unmasked and its depth is finite and in
+        [min_depth, max_depth]; integer pixel coordinates are pixel centres.  Bit for bit integrate() of the back-projected
+        float32 points.  Returns (pixels integrated, of those rejected)."""
+        depth = _arr(depth, np.float32)
+        if depth.ndim != 2:
+            raise ValueError("depth must be (height, width)")
+        if mask is not None:
+            mask = _arr(mask, np.uint8)
+            if mask.shape != depth.shape:
+                raise ValueError("mask must have the depth image's shape")
+        fx, fy, cx, cy = _pinhole(K)
+        T = pose_matrix(T_w_c)
+        n, rej = C.c_uint64(), C.c_uint64()
+        _check(load_library().dsx_map_integrate_depth(self._h, _ptr(depth, C.c_float), None if mask is None else _ptr(mask, C.c_uint8),
+                                                      depth.shape[1], depth.shape[0], fx, fy, cx, cy, float(min_depth), float(max_depth),
+                                                      _ptr(T, C.c_double), C.byref(n), C.byref(rej)))
+        return n.value, rej.value
+
+    def integrateGroundTruth(self, projector, K, min_depth, max_depth, T_w_c):
+        """integrateDepth of the depth map a GroundTruthProjector last made, where it lies on the device, at the projector's
+        size and without a mask (dsx_map_integrate_depth_gt): only the counts travel."""
+        fx, fy, cx, cy = _pinhole(K)
+        T = pose_matrix(T_w_c)
+        n, rej = C.c_uint64(), C.c_uint64()
+        _check(load_library().dsx_map_integrate_depth_gt(self._h, projector._h, fx, fy, cx, cy, float(min_depth), float(max_depth),
+                                                         _ptr(T, C.c_double), C.byref(n), C.byref(rej)))
+        return n.value, rej.value
+
+    def compare(self, other, radius, n_bins=16, min_points=1, min_windows=1, min_points_other=1, min_windows_other=1,
+                distances=False):
+        """For every cell of this map (that passes min_points / min_windows) the distance to the nearest centroid of `other`
+        (cells passing min_points_other / min_windows_other) within `radius`, looked up in other's table over
+        ceil(radius / other's leaf) <= 3 cells per axis (dsx_map_compare; the arithmetic is stated in dsi_map_eval.h).
+        Returns hist (uint64 [n_bins], bins of width radius / n_bins), n_cells = n_matched + n_unmatched, sum_q, reach and
+        mean (of the matched distances; nan without one); with distances=True also keys and dist (float32, inf where
+        unmatched), sorted by key."""
+        o = _MapCompareOpts(int(min_points), int(min_windows), int(min_points_other), int(min_windows_other), float(radius), int(n_bins))
+        i = _MapCompareInfo()
+        hist = np.zeros(max(int(n_bins), 0), np.uint64)
+        L = load_library()
+        _check(L.dsx_map_compare(self._h, other._h, C.byref(o), _ptr(hist, C.c_uint64) if hist.size else None, C.byref(i)))
+        out = {k: int(getattr(i, k)) for k in ("n_cells", "n_matched", "n_unmatched", "sum_q", "reach")}
+        out["hist"] = hist
+        out["mean"] = out["sum_q"] * float(radius) / 4294967296.0 / out["n_matched"] if out["n_matched"] else float("nan")
+        if distances:
+            out.update(self.fetchDistances())
+        return out
+
+    def fetchDistances(self, sort=True):
+        """keys (uint64) and dist (float32) of the last compare() of this map (dsx_map_compare_fetch); raises DsiError when
+        the map changed since, or was never compared."""
+        L = load_library()
+        n = C.c_size_t()
+        rc = L.dsx_map_compare_fetch(self._h, None, None, 0, C.byref(n))
+        if rc != OK and n.value == 0:
+            _check(rc)
+        m = n.value
+        out = {"keys": np.empty(m, np.uint64), "dist": np.empty(m, np.float32)}
+        _check(L.dsx_map_compare_fetch(self._h, _ptr(out["dist"], C.c_float), _ptr(out["keys"], C.c_uint64), m, C.byref(n)))
+        if sort:
+            order = np.argsort(out["keys"], kind="stable")
+            out = {k: v[order] for k, v in out.items()}
+        return out
+
     def reset(self):
         _check(load_library().dsi_map_reset(self._h))
 
@@ -1135,6 +1217,33 @@ class WorldMap:
 
     def __del__(self):
         _safe_del(self)
+
+
+def _pinhole(K):
+    """(fx, fy, cx, cy) as floats from those four numbers or from a 3 x 3 camera matrix"""
+    K = np.asarray(K, np.float64)
+    if K.shape == (3, 3):
+        return float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+    if K.size != 4:
+        raise ValueError("K is (fx, fy, cx, cy) or a 3 x 3 matrix")
+    return tuple(float(v) for v in K.reshape(4))
+
+
+def map_f_score(est, gt, radius, n_bins=16, min_points=1, min_windows=1, min_points_gt=1, min_windows_gt=1):
+    """3-D accuracy, completeness and F-score of the map `est` against the map `gt` (two WorldMap.compare runs, one per
+    direction; the curves of the reference's scripts/precision_completeness.py:44,60,76 taken in space): thresholds
+    (i + 1) * radius / n_bins, precision = 100 cumsum(hist_est) / n_cells_est, recall = 100 cumsum(hist_gt) / n_cells_gt,
+    f1 = 2 P R / (P + R) (0 where P + R == 0) -- float64 from the integer counts -- plus the two compare dicts."""
+    fwd = est.compare(gt, radius, n_bins, min_points, min_windows, min_points_gt, min_windows_gt)
+    bwd = gt.compare(est, radius, n_bins, min_points_gt, min_windows_gt, min_points, min_windows)
+    n_bins = int(n_bins)
+    thresholds = (np.arange(n_bins, dtype=np.float64) + 1.0) * (np.float64(radius) / np.float64(n_bins))
+    zero = np.zeros(n_bins, np.float64)
+    P = 100.0 * np.cumsum(fwd["hist"]).astype(np.float64) / np.float64(fwd["n_cells"]) if fwd["n_cells"] else zero
+    R = 100.0 * np.cumsum(bwd["hist"]).astype(np.float64) / np.float64(bwd["n_cells"]) if bwd["n_cells"] else zero
+    some = P + R > 0
+    f1 = np.where(some, 2.0 * P * R / np.where(some, P + R, 1.0), 0.0)
+    return {"thresholds": thresholds, "precision": P, "recall": R, "f1": f1, "est": fwd, "gt": bwd}
 
 
 def _polarity_bytes(polarity, n, use_polarity):

@@ -874,6 +874,32 @@ def score_world_map(world_map, score, frames, camera, min_depth, max_depth, spla
     return counts
 
 
+def ground_truth_map(ctx, frames, camera, leaf, min_depth, max_depth, capacity_log2=16):
+    """A ground-truth map for score_world_map_3d: an engine.WorldMap of `ctx` with cells of edge `leaf`, holding every frame
+    of `frames` -- (gt, T_w_c) with gt a host depth map (height, width) or a GroundTruthProjector already holding that frame
+    and T_w_c the camera's pose in the world (as engine.pose_matrix takes it) -- back-projected through
+    camera = (width, height, fx, fy, cx, cy), one integrate call per frame.  Pixels without a finite depth in
+    [min_depth, max_depth] are left out.  What goes into the map is the caller's choice: nothing is culled."""
+    width, height, fx, fy, cx, cy = camera
+    gt_map = E.WorldMap(ctx, leaf, capacity_log2)
+    for gt, T_w_c in frames:
+        if isinstance(gt, E.GroundTruthProjector):
+            gt_map.integrateGroundTruth(gt, (fx, fy, cx, cy), min_depth, max_depth, T_w_c)
+        else:
+            gt = np.asarray(gt, np.float32)
+            if gt.shape != (int(height), int(width)):
+                raise ValueError("a ground-truth depth map must be (height, width) of the camera")
+            gt_map.integrateDepth(gt, None, (fx, fy, cx, cy), min_depth, max_depth, T_w_c)
+    return gt_map
+
+
+def score_world_map_3d(world_map, gt_map, radius, n_bins=16, min_points=1, min_windows=1, min_points_gt=1, min_windows_gt=1):
+    """3-D accuracy, completeness and F-score of a finished full_sequence(..., world_map=) run against a ground-truth map
+    (ground_truth_map): engine.map_f_score of the two maps -- thresholds, precision, recall and f1 per threshold, and the
+    two directions' counts (`est`: the map's cells against the ground truth, `gt`: the reverse) with their mean distances."""
+    return E.map_f_score(world_map, gt_map, radius, n_bins, min_points, min_windows, min_points_gt, min_windows_gt)
+
+
 def _window_result(ws, pending, options_depth_map, options_point_cloud, images=None, scoring=None, world_map=None):
     out = ws.fetch(pending[1], options_depth_map, options_point_cloud)
     if world_map is not None:       # (the filtered maps of the window are still on the device: fetch left them there)

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "dsi_engine.h"
+#include "dsi_map_eval.h"
 
 namespace dsi {
 
@@ -1599,6 +1600,20 @@ struct MapRenderImages {  // height x width, row-major
     std::vector<uint32_t> windows, hits;
     std::vector<uint8_t> mask;
 };
+// map-to-map distances (dsi_map_eval.h: dsx_map_compare): the options, and what a compare counts
+using MapCompareOptions = dsx_map_compare_opts_t;
+struct MapCompareResult {
+    dsx_map_compare_info_t info{};
+    std::vector<uint64_t> hist;  // n_bins counts, bins of width radius / n_bins
+    double radius = 0.0;
+    // the mean of the matched distances: sum_q * radius / 2^32 / n_matched (0 without a matched cell)
+    double mean() const { return info.n_matched ? (double)info.sum_q * radius / 4294967296.0 / (double)info.n_matched : 0.0; }
+};
+struct MapDistances {  // by ascending key when sorted
+    std::vector<uint64_t> keys;
+    std::vector<float> dist;  // +inf where the cell is unmatched
+    size_t size() const { return keys.size(); }
+};
 class WorldMap {
 public:
     WorldMap(Context& ctx, double leaf, int capacity_log2 = 16) : ctx_(ctx) { check(dsi_map_create(ctx.handle(), leaf, capacity_log2, &h_)); }
@@ -1699,11 +1714,92 @@ public:
         return out;
     }
 
+    // one call of a host depth image (height x width, row-major; mask may be nullptr) seen by a pinhole camera at T_w_c
+    // (dsx_map_integrate_depth): bit for bit integrate() of the back-projected float32 points.  Returns the number of pixels
+    // integrated; *n_rejected: those of them rejected
+    uint64_t integrateDepth(const float* depth, const uint8_t* mask, int width, int height, double fx, double fy, double cx, double cy,
+                            double min_depth, double max_depth, const std::array<double, 12>& T_w_c, uint64_t* n_rejected = nullptr)
+    {
+        uint64_t n = 0;
+        check(dsx_map_integrate_depth(h_, depth, mask, width, height, fx, fy, cx, cy, min_depth, max_depth, T_w_c.data(), &n, n_rejected));
+        return n;
+    }
+    // the same of the depth map the projector last made, where it lies on the device, at the projector's size
+    uint64_t integrateGroundTruth(const GroundTruthProjector& projector, double fx, double fy, double cx, double cy, double min_depth,
+                                  double max_depth, const std::array<double, 12>& T_w_c, uint64_t* n_rejected = nullptr)
+    {
+        uint64_t n = 0;
+        check(dsx_map_integrate_depth_gt(h_, projector.handle(), fx, fy, cx, cy, min_depth, max_depth, T_w_c.data(), &n, n_rejected));
+        return n;
+    }
+    // every filtered cell of this map against the nearest centroid of `other` within opts.radius (dsx_map_compare; the
+    // arithmetic is stated in dsi_map_eval.h); the distances stay on the device for fetchDistances until this map changes
+    MapCompareResult compare(const WorldMap& other, const MapCompareOptions& opts)
+    {
+        MapCompareResult r;
+        r.radius = opts.radius;
+        r.hist.assign(opts.n_bins > 0 ? (size_t)opts.n_bins : 0, 0);
+        check(dsx_map_compare(h_, other.h_, &opts, r.hist.empty() ? nullptr : r.hist.data(), &r.info));
+        return r;
+    }
+    // (key, dist) of the last compare of this map; sort: by ascending key
+    MapDistances fetchDistances(bool sort = true) const
+    {
+        MapDistances raw;
+        size_t n = 0;
+        const int rc = dsx_map_compare_fetch(h_, nullptr, nullptr, 0, &n);
+        if (rc != DSI_OK && n == 0) check(rc);
+        raw.keys.resize(n);
+        raw.dist.resize(n);
+        check(dsx_map_compare_fetch(h_, raw.dist.data(), raw.keys.data(), n, &n));
+        if (!sort) return raw;
+        std::vector<size_t> order(n);
+        for (size_t i = 0; i < n; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return raw.keys[a] < raw.keys[b]; });
+        MapDistances out;
+        for (size_t i : order) {
+            out.keys.push_back(raw.keys[i]);
+            out.dist.push_back(raw.dist[i]);
+        }
+        return out;
+    }
+
 private:
     Context& ctx_;
     dsi_map_t* h_ = nullptr;
     int width_ = 0, height_ = 0;  // of the last render
 };
+
+// 3-D accuracy, completeness and F-score of the map `est` against the map `gt` (the curves of the reference's
+// scripts/precision_completeness.py:44,60,76 taken in space): one compare per direction, then, from the integer counts,
+// thresholds (i + 1) * radius / n_bins, precision = 100 cumsum(hist_est) / n_cells_est, recall = 100 cumsum(hist_gt) /
+// n_cells_gt, f1 = 2 P R / (P + R), 0 where P + R == 0.  opts: the filters with a = est and b = gt, radius, n_bins.
+struct MapFScore {
+    std::vector<double> thresholds, precision, recall, f1;
+    MapCompareResult est, gt;
+};
+inline MapFScore map_f_score(WorldMap& est, WorldMap& gt, const MapCompareOptions& opts)
+{
+    MapCompareOptions back = opts;
+    back.min_points_a = opts.min_points_b, back.min_windows_a = opts.min_windows_b;
+    back.min_points_b = opts.min_points_a, back.min_windows_b = opts.min_windows_a;
+    MapFScore f;
+    f.est = est.compare(gt, opts);
+    f.gt = gt.compare(est, back);
+    const double w = opts.radius / (double)opts.n_bins;
+    uint64_t ce = 0, cg = 0;
+    for (int i = 0; i < opts.n_bins; ++i) {
+        ce += f.est.hist[(size_t)i];
+        cg += f.gt.hist[(size_t)i];
+        const double P = f.est.info.n_cells ? 100.0 * (double)ce / (double)f.est.info.n_cells : 0.0;
+        const double R = f.gt.info.n_cells ? 100.0 * (double)cg / (double)f.gt.info.n_cells : 0.0;
+        f.thresholds.push_back(((double)i + 1.0) * w);
+        f.precision.push_back(P);
+        f.recall.push_back(R);
+        f.f1.push_back(P + R > 0.0 ? 2.0 * P * R / (P + R) : 0.0);
+    }
+    return f;
+}
 
 }  // namespace dsi
 
