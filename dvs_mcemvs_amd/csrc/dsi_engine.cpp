@@ -9,6 +9,7 @@
 // frees them (in reverse order of declaration), a dsi_*_destroy only checks, synchronises and counts before it.
 #include "../../include/dsi_engine.h"
 #include "../../include/dsi_map_eval.h"
+#include "../../include/dsi_map_prune.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: librccl is loaded at run time (load_rccl)
@@ -4064,6 +4065,10 @@ struct dsi_map {
     DevBuf<unsigned long long> cmp_hist, cmp_ctr;
     uint32_t cmp_min_points = 0, cmp_min_windows = 0;
     bool compare_valid = false;
+    // the last classification (dsx_map_prune_classify, include/dsi_map_prune.h): valid until the map changes
+    DevBuf<uint8_t> prune_first, prune_reason, prune_reason_out;  // per slot: by criteria 1-4, final; compacted for a fetch
+    DevBuf<unsigned long long> prune_ctr;
+    bool prune_valid = false;
 };
 
 namespace {
@@ -4107,7 +4112,7 @@ int map_grow_for(dsi_map* mp, size_t n)
 int map_integrate_call(dsi_map* mp, size_t n, const std::function<hipError_t(uint32_t, const dsi::MapTable&)>& launch, size_t* n_accepted,
                        size_t* n_rejected)
 {
-    mp->render_valid = mp->compare_valid = false;  // (the map may change from here on)
+    mp->render_valid = mp->compare_valid = mp->prune_valid = false;  // (the map may change from here on)
     REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
     REQUIRE(mp->calls < 0xffffffffull, DSI_ERR_INVALID, "at most 2^32 - 1 integrate calls per map");
     REQUIRE((mp->host_ctr[0] + n) * 4 <= ((uint64_t)3 << kMapMaxLog2), DSI_ERR_INVALID,
@@ -4211,7 +4216,7 @@ int dsi_map_destroy(dsi_map_t* mp)
 int dsi_map_reset(dsi_map_t* mp)
 {
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
-    mp->render_valid = mp->compare_valid = false;
+    mp->render_valid = mp->compare_valid = mp->prune_valid = false;
     if (int rc = set_device(mp->ctx)) return rc;
     HIP_TRY(hipMemsetAsync(mp->block.p, 0, dsi::map_table_bytes(mp->cap_log2), mp->ctx->stream));
     HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof mp->host_ctr, mp->ctx->stream));
@@ -4542,6 +4547,143 @@ int dsx_map_compare_fetch(dsi_map_t* a, float* dist_host, uint64_t* keys_host, s
     if (dist_host) HIP_TRY(hipMemcpyAsync(dist_host, a->cmp_dist_out.p, total * sizeof(float), hipMemcpyDeviceToHost, st));
     if (keys_host) HIP_TRY(hipMemcpyAsync(keys_host, a->key_out.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+// ---- pruning the map (include/dsi_map_prune.h; DESIGN.md 7j "Pruning") ----
+
+namespace {
+
+// the bounds of the options: decided without a device, before any handle is looked at
+int check_prune_opts(const dsx_map_prune_opts_t* o)
+{
+    REQUIRE(o, DSI_ERR_INVALID, "opts is null");
+    REQUIRE(o->use_box == 0 || o->use_box == 1, DSI_ERR_INVALID, "use_box must be 0 or 1 (got %d)", o->use_box);
+    if (o->use_box)
+        for (int a = 0; a < 3; ++a)
+            REQUIRE(o->box_lo[a] <= o->box_hi[a], DSI_ERR_INVALID, "the box needs box_lo <= box_hi without NaN on axis %d (got %g, %g)",
+                    a, o->box_lo[a], o->box_hi[a]);  // (NaN compares false)
+    REQUIRE(o->reach >= 0 && o->reach <= dsi::kMapPruneMaxReach, DSI_ERR_INVALID, "reach must be in 0..%d (got %d)",
+            dsi::kMapPruneMaxReach, o->reach);
+    const uint32_t most = (uint32_t)((2 * o->reach + 1) * (2 * o->reach + 1) * (2 * o->reach + 1) - 1);
+    if (o->reach > 0)
+        REQUIRE(o->min_neighbors >= 1 && o->min_neighbors <= most, DSI_ERR_INVALID, "min_neighbors must be in 1..%u at reach %d (got %u)",
+                most, o->reach, o->min_neighbors);
+    else
+        REQUIRE(o->min_neighbors == 0, DSI_ERR_INVALID, "min_neighbors must be 0 at reach 0 (got %u)", o->min_neighbors);
+    REQUIRE(o->shrink == 0 || o->shrink == 1, DSI_ERR_INVALID, "shrink must be 0 or 1 (got %d)", o->shrink);
+    return DSI_OK;
+}
+
+// every cell classified into mp->prune_first / prune_reason and counted into ctr (kMapPruneCounters); synchronises
+int map_prune_classify_device(dsi_map* mp, const dsx_map_prune_opts_t* opts, unsigned long long* ctr)
+{
+    hipStream_t st = mp->ctx->stream;
+    const size_t cap = (size_t)1 << mp->cap_log2;
+    HIP_TRY(mp->prune_first.reserve(cap));
+    HIP_TRY(mp->prune_reason.reserve(cap));
+    HIP_TRY(mp->prune_ctr.reserve(dsi::kMapPruneCounters));
+    dsi::MapPrune o;
+    o.leaf = mp->leaf;
+    for (int a = 0; a < 3; ++a) o.box_lo[a] = opts->box_lo[a], o.box_hi[a] = opts->box_hi[a];
+    o.max_age = opts->max_age;
+    o.min_points = opts->min_points, o.min_windows = opts->min_windows;
+    o.calls = (uint32_t)mp->calls;  // (< 2^32: map_integrate_call)
+    o.min_neighbors = opts->min_neighbors;
+    o.use_box = opts->use_box, o.reach = opts->reach;
+    HIP_TRY(dsi::launch_map_prune_classify(st, dsi::map_table_at(mp->block.p, mp->cap_log2), o, mp->prune_first.p, mp->prune_reason.p,
+                                           mp->prune_ctr.p));
+    HIP_TRY(hipMemcpyAsync(ctr, mp->prune_ctr.p, dsi::kMapPruneCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+void map_prune_info(const dsi_map* mp, const unsigned long long* ctr, dsx_map_prune_info_t* info)
+{
+    if (!info) return;
+    info->n_kept = ctr[0];
+    info->n_cells = ctr[0];
+    for (int r = 0; r < 5; ++r) {
+        info->n_removed[r] = ctr[1 + r];
+        info->n_cells += ctr[1 + r];
+    }
+    info->capacity = (uint64_t)1 << mp->cap_log2;
+}
+
+}  // namespace
+
+int dsx_map_prune_classify(dsi_map_t* mp, const dsx_map_prune_opts_t* opts, dsx_map_prune_info_t* info)
+{
+    if (int rc = check_prune_opts(opts)) return rc;  // (first: the bounds can be exercised with no map at hand)
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
+    if (int rc = set_device(mp->ctx)) return rc;
+    mp->prune_valid = false;
+    unsigned long long ctr[dsi::kMapPruneCounters] = {0, 0, 0, 0, 0, 0};
+    if (int rc = map_prune_classify_device(mp, opts, ctr)) return rc;
+    mp->prune_valid = true;
+    map_prune_info(mp, ctr, info);
+    return DSI_OK;
+}
+
+int dsx_map_prune_fetch(dsi_map_t* mp, uint8_t* reason_host, uint64_t* keys_host, size_t capacity, size_t* n)
+{
+    REQUIRE(mp && n, DSI_ERR_INVALID, "null argument");
+    REQUIRE(mp->prune_valid, DSI_ERR_INVALID,
+            "no classification of the map as it stands: call dsx_map_prune_classify (after the last reset, integrate call or prune)");
+    if (int rc = set_device(mp->ctx)) return rc;
+    size_t total = 0;
+    if (int rc = map_count_device(mp, 1, 1, &total)) return rc;
+    *n = total;
+    REQUIRE(capacity >= total, DSI_ERR_INVALID, "capacity of %zu cells is too small: %zu needed", capacity, total);
+    if (!total) return DSI_OK;
+    hipStream_t st = mp->ctx->stream;
+    HIP_TRY(mp->prune_reason_out.reserve(total));
+    HIP_TRY(mp->key_out.reserve(total));
+    HIP_TRY(dsi::launch_map_prune_gather(st, dsi::map_table_at(mp->block.p, mp->cap_log2), mp->prune_reason.p, mp->blk.p,
+                                         mp->prune_reason_out.p, mp->key_out.p));
+    if (reason_host) HIP_TRY(hipMemcpyAsync(reason_host, mp->prune_reason_out.p, total, hipMemcpyDeviceToHost, st));
+    if (keys_host) HIP_TRY(hipMemcpyAsync(keys_host, mp->key_out.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+int dsx_map_prune(dsi_map_t* mp, const dsx_map_prune_opts_t* opts, dsx_map_prune_info_t* info)
+{
+    if (int rc = check_prune_opts(opts)) return rc;
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
+    if (int rc = set_device(mp->ctx)) return rc;
+    mp->render_valid = mp->compare_valid = mp->prune_valid = false;
+    hipStream_t st = mp->ctx->stream;
+    unsigned long long ctr[dsi::kMapPruneCounters] = {0, 0, 0, 0, 0, 0};
+    if (int rc = map_prune_classify_device(mp, opts, ctr)) return rc;
+    const unsigned long long kept = ctr[0];
+    uint32_t want = mp->cap_log2;
+    if (opts->shrink)
+        for (want = kMapMinLog2; kept * 4 > ((uint64_t)3 << want); ++want) {
+        }
+    const bool none_removed = ctr[1] + ctr[2] + ctr[3] + ctr[4] + ctr[5] == 0;
+    if (!(none_removed && want == mp->cap_log2)) {  // (nothing leaves and the size stays: the table is the result already)
+        DevBuf<unsigned char> block;
+        hipError_t e = block.reserve(dsi::map_table_bytes(want));
+        if (e != hipSuccess)
+            return fail(DSI_ERR_HIP, "a pruned table of 2^%u slots could not be allocated (%s): the map is unchanged", want,
+                        hipGetErrorString(e));
+        HIP_TRY(hipMemsetAsync(block.p, 0, dsi::map_table_bytes(want), st));
+        HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof(unsigned long long), st));  // occupied: the rebuild counts the cells it moves
+        if (kept)
+            HIP_TRY(dsi::launch_map_prune_rehash(st, dsi::map_table_at(mp->block.p, mp->cap_log2), dsi::map_table_at(block.p, want),
+                                                 mp->prune_reason.p, mp->ctr.p));
+        HIP_TRY(hipMemcpyAsync(mp->host_ctr, mp->ctr.p, sizeof mp->host_ctr, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        mp->block = std::move(block);  // (frees the old table)
+        mp->cap_log2 = want;
+        REQUIRE(mp->host_ctr[3] == 0 && mp->host_ctr[0] == kept, DSI_ERR_HIP,
+                "the pruned table holds %llu of %llu kept cells (%llu found it full): an engine bug, the map is unusable", mp->host_ctr[0],
+                kept, mp->host_ctr[3]);
+    }
+    map_prune_info(mp, ctr, info);
     return DSI_OK;
 }
 

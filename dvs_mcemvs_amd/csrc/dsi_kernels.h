@@ -396,6 +396,29 @@ hipError_t launch_map_compare(hipStream_t s, const MapTable& a, const MapTable& 
 hipError_t launch_map_compare_gather(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, const float* dist,
                                      const uint32_t* blk, float* dist_out, unsigned long long* key_out);
 
+// ---- pruning the map (include/dsi_map_prune.h; DESIGN.md 7j "Pruning") ----
+// the five criteria; the host has checked every bound.  calls: the map's call count (the newest serial)
+struct MapPrune {
+    double leaf, box_lo[3], box_hi[3];
+    long long max_age;  // < 0: off
+    uint32_t min_points, min_windows, calls, min_neighbors;
+    int use_box, reach;  // reach 0..kMapPruneMaxReach
+};
+constexpr int kMapPruneMaxReach = 2;
+constexpr int kMapPruneCounters = 6;               // kept, removed by criterion 1..5
+constexpr uint8_t kMapPruneEmpty = 0xff;           // the reason of a slot that holds no cell
+// clears ctr [kMapPruneCounters]; first [cap]: every slot's reason by criteria 1-4 (0: survived them); reason [cap]: the
+// final reason, criterion 5 judged on `first` alone.  Reads the table, writes the two arrays.
+hipError_t launch_map_prune_classify(hipStream_t s, const MapTable& t, const MapPrune& o, uint8_t* first, uint8_t* reason,
+                                     unsigned long long* ctr);
+// every slot of `from` with reason 0 into `to` (zeroed by the caller); ctr: the map's four counters, [0] += the cells moved
+// (the caller cleared it), [3] += cells that found `to` full
+hipError_t launch_map_prune_rehash(hipStream_t s, const MapTable& from, const MapTable& to, const uint8_t* reason,
+                                   unsigned long long* ctr);
+// after launch_map_count(t, 1, 1): key and reason of every cell in slot order (launch_map_extract's)
+hipError_t launch_map_prune_gather(hipStream_t s, const MapTable& t, const uint8_t* reason, const uint32_t* blk, uint8_t* reason_out,
+                                   unsigned long long* key_out);
+
 // focus-based collapses (Grid3D::collapseZSliceBy*, cartesian3dgrid.cpp:192-414; DESIGN.md "Focus-based collapses"):
 // method 0 LocalVar, 1 LocalMeanSquare, 2 GradMag (half_patchsize 0..8), 3 LaplacianMag, 4 DoG.  keys: scratch of
 // focus_chunks(nx, ny, nz) * nx * ny words, fully written before it is read.  planes / depth as launch_collapse_max_z.

@@ -7181,6 +7181,168 @@ __global__ void __launch_bounds__(kPcBlock) k_map_compare_gather(MapTable t, uin
     key_out[o] = t.keys[i];
 }
 
+// ---- pruning the map (include/dsi_map_prune.h dsx_map_prune*; DESIGN.md 7j "Pruning") ----
+// Criteria 1-4 for every slot: first[slot] = the first criterion that fails, 0 when none does, kMapPruneEmpty for a slot
+// without a cell.  1: n < min_points; 2: windows < min_windows (map_passes with the other bound at 0); 3: max_age >= 0 and
+// calls - stamp > max_age (stamp <= calls: the difference is exact in 32 bits); 4: use_box and the extracted centroid
+// (map_centroid, float, widened) outside [box_lo, box_hi] on some axis, compared in double (the centroid is finite; the
+// bounds may be infinite, never NaN).  ctr[r] += the cells with reason r, r = 1..4.  Walks the slots like k_map_render:
+// a wave keeps its counts in uniform registers, the workgroup sums them in LDS and issues one global atomic per counter.
+__global__ void __launch_bounds__(kPcBlock) k_map_prune_reason(MapTable t, MapPrune o, uint8_t* __restrict__ first,
+                                                               unsigned long long* __restrict__ ctr)
+{
+    __shared__ uint32_t s_cnt[4];
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    uint32_t c1 = 0, c2 = 0, c3 = 0, c4 = 0;  // (the same in every lane of a wave)
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        uint32_t r = kMapPruneEmpty;
+        if (map_passes(t, i, 0u, 0u)) {
+            r = 0u;
+            if (!map_passes(t, i, o.min_points, 0u)) {
+                r = 1u;
+            } else if (!map_passes(t, i, 0u, o.min_windows)) {
+                r = 2u;
+            } else if (o.max_age >= 0 && (long long)(o.calls - t.stamp[i]) > o.max_age) {
+                r = 3u;
+            } else if (o.use_box) {
+                const unsigned long long k = t.keys[i];
+                const uint32_t n = t.n[i];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const double p = (double)map_centroid(t, i, k, n, a, o.leaf);
+                    if (p < o.box_lo[a] || p > o.box_hi[a]) r = 4u;
+                }
+            }
+        }
+        first[i] = (uint8_t)r;  // (cap is a multiple of the workgroup: i < cap)
+        c1 += (uint32_t)__popcll(__ballot(r == 1u));
+        c2 += (uint32_t)__popcll(__ballot(r == 2u));
+        c3 += (uint32_t)__popcll(__ballot(r == 3u));
+        c4 += (uint32_t)__popcll(__ballot(r == 4u));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (c1) atomicAdd(&s_cnt[0], c1);
+        if (c2) atomicAdd(&s_cnt[1], c2);
+        if (c3) atomicAdd(&s_cnt[2], c3);
+        if (c4) atomicAdd(&s_cnt[3], c4);
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&ctr[1 + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
+// Criterion 5 for the cells that survived 1-4, judged on `first` alone (read-only here, so the outcome does not depend on
+// the order of the threads: a neighbour that this criterion removes still counts).  The cell's index c comes from its key;
+// the neighbours are the OTHER cells at c + o, |o| <= reach per axis, an index with |c + o| > kPcCellMax skipped (it has no
+// key); a neighbour supports iff map_find finds it and first[its slot] == 0.  The sweep stops at min_neighbors supporters
+// (the count is only compared with that bound).  reason[slot] = 5 with fewer, else 0; every other slot keeps first[slot].
+// ctr[0] += kept, ctr[5] += removed here; walked and counted like k_map_prune_reason.
+__global__ void __launch_bounds__(kPcBlock) k_map_prune_support(MapTable t, MapPrune o, const uint8_t* __restrict__ first,
+                                                                uint8_t* __restrict__ reason, unsigned long long* __restrict__ ctr)
+{
+    __shared__ uint32_t s_cnt[2];
+    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    uint32_t c_kept = 0, c_lone = 0;  // (the same in every lane of a wave)
+    const uint32_t mask = (1u << t.cap_log2) - 1u;
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        uint32_t r = first[i];
+        if (r == 0u && o.reach > 0) {
+            const unsigned long long k = t.keys[i];
+            int c[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) c[a] = (int)((k >> (21 * a)) & 0x1fffffull) - (kPcCellMax + 1);
+            uint32_t found = 0;
+            for (int oz = -o.reach; oz <= o.reach && found < o.min_neighbors; ++oz) {
+                const int vz = c[2] + oz;
+                if (abs(vz) > kPcCellMax) continue;
+                for (int oy = -o.reach; oy <= o.reach && found < o.min_neighbors; ++oy) {
+                    const int vy = c[1] + oy;
+                    if (abs(vy) > kPcCellMax) continue;
+                    for (int ox = -o.reach; ox <= o.reach && found < o.min_neighbors; ++ox) {
+                        const int vx = c[0] + ox;
+                        if (abs(vx) > kPcCellMax || (ox == 0 && oy == 0 && oz == 0)) continue;
+                        const uint32_t j = map_find(t.keys, mask, pc_key(vx, vy, vz));
+                        if (j != ~0u && first[j] == 0u) ++found;
+                    }
+                }
+            }
+            if (found < o.min_neighbors) r = 5u;
+        }
+        reason[i] = (uint8_t)r;
+        c_kept += (uint32_t)__popcll(__ballot(r == 0u));
+        c_lone += (uint32_t)__popcll(__ballot(r == 5u));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (c_kept) atomicAdd(&s_cnt[0], c_kept);
+        if (c_lone) atomicAdd(&s_cnt[1], c_lone);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt[0]) atomicAdd(&ctr[0], (unsigned long long)s_cnt[0]);
+    if (threadIdx.x == 1 && s_cnt[1]) atomicAdd(&ctr[5], (unsigned long long)s_cnt[1]);
+}
+
+// the kept cells (reason 0) of `from` with all their state into `to` (zeroed; keys are distinct, so a claimed slot has one
+// writer): k_map_rehash restricted by `reason`, walked in strides.  ctr[0] += the cells moved, one global atomic per
+// workgroup; ctr[3] += cells whose probe sequence ran through the whole of `to` (the host sizes it so that none does).
+__global__ void __launch_bounds__(kPcBlock) k_map_prune_rehash(MapTable from, MapTable to, const uint8_t* __restrict__ reason,
+                                                               unsigned long long* __restrict__ ctr)
+{
+    __shared__ uint32_t s_cnt[2];
+    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    uint32_t c_moved = 0, c_full = 0;  // (the same in every lane of a wave)
+    const uint32_t mask = (1u << to.cap_log2) - 1u;
+    const size_t cap = (size_t)1 << from.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        bool moved = false, full = false;
+        if (reason[i] == 0u) {
+            bool fresh;
+            const uint32_t slot = map_slot(to.keys, mask, from.keys[i], &fresh);
+            if (slot == ~0u) {
+                full = true;
+            } else {
+                moved = true;
+                to.n[slot] = from.n[i];
+                to.windows[slot] = from.windows[i];
+                to.stamp[slot] = from.stamp[i];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) to.sums[3 * (size_t)slot + a] = from.sums[3 * i + a];
+            }
+        }
+        c_moved += (uint32_t)__popcll(__ballot(moved));
+        c_full += (uint32_t)__popcll(__ballot(full));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (c_moved) atomicAdd(&s_cnt[0], c_moved);
+        if (c_full) atomicAdd(&s_cnt[1], c_full);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt[0]) atomicAdd(&ctr[0], (unsigned long long)s_cnt[0]);
+    if (threadIdx.x == 1 && s_cnt[1]) atomicAdd(&ctr[3], (unsigned long long)s_cnt[1]);
+}
+
+// the classification compacted like k_map_extract's cells under the filter (1, 1) -- every cell --, with its blk_off: key
+// and reason in slot order
+__global__ void __launch_bounds__(kPcBlock) k_map_prune_gather(MapTable t, const uint8_t* __restrict__ reason,
+                                                               const uint32_t* __restrict__ blk_off, uint8_t* __restrict__ reason_out,
+                                                               unsigned long long* __restrict__ key_out)
+{
+    const size_t i = (size_t)blockIdx.x * kPcBlock + threadIdx.x;
+    const bool f = map_passes(t, i, 1u, 1u);
+    uint32_t total;
+    const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);
+    if (!f) return;
+    const size_t o = (size_t)blk_off[blockIdx.x] + rank;
+    reason_out[o] = reason[i];
+    key_out[o] = t.keys[i];
+}
+
 }  // namespace
 
 size_t map_table_bytes(uint32_t cap_log2) { return ((size_t)1 << cap_log2) * (4 * sizeof(unsigned long long) + 3 * sizeof(uint32_t)); }
@@ -7268,6 +7430,33 @@ hipError_t launch_map_compare_gather(hipStream_t s, const MapTable& t, uint32_t 
 {
     const uint32_t nb = pc_blocks((size_t)1 << t.cap_log2);
     hipLaunchKernelGGL(k_map_compare_gather, dim3(nb), dim3(kPcBlock), 0, s, t, min_points, min_windows, dist, blk, dist_out, key_out);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_prune_classify(hipStream_t s, const MapTable& t, const MapPrune& o, uint8_t* first, uint8_t* reason,
+                                     unsigned long long* ctr)
+{
+    hipError_t e = hipMemsetAsync(ctr, 0, kMapPruneCounters * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    const dim3 grid(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks));
+    hipLaunchKernelGGL(k_map_prune_reason, grid, dim3(kPcBlock), 0, s, t, o, first, ctr);
+    hipLaunchKernelGGL(k_map_prune_support, grid, dim3(kPcBlock), 0, s, t, o, first, reason, ctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_prune_rehash(hipStream_t s, const MapTable& from, const MapTable& to, const uint8_t* reason,
+                                   unsigned long long* ctr)
+{
+    hipLaunchKernelGGL(k_map_prune_rehash, dim3(std::min(pc_blocks((size_t)1 << from.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0,
+                       s, from, to, reason, ctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_prune_gather(hipStream_t s, const MapTable& t, const uint8_t* reason, const uint32_t* blk, uint8_t* reason_out,
+                                   unsigned long long* key_out)
+{
+    const uint32_t nb = pc_blocks((size_t)1 << t.cap_log2);
+    hipLaunchKernelGGL(k_map_prune_gather, dim3(nb), dim3(kPcBlock), 0, s, t, reason, blk, reason_out, key_out);
     return hipExtGetLastError();
 }
 

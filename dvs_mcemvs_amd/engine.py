@@ -90,6 +90,16 @@ class _MapCompareInfo(C.Structure):
                 ("reach", C.c_int32)]
 
 
+class _MapPruneOpts(C.Structure):
+    _fields_ = [("min_points", C.c_uint32), ("min_windows", C.c_uint32), ("max_age", C.c_int64), ("use_box", C.c_int32),
+                ("box_lo", C.c_double * 3), ("box_hi", C.c_double * 3), ("reach", C.c_int32), ("min_neighbors", C.c_uint32),
+                ("shrink", C.c_int32)]
+
+
+class _MapPruneInfo(C.Structure):
+    _fields_ = [("n_cells", C.c_uint64), ("n_kept", C.c_uint64), ("n_removed", C.c_uint64 * 5), ("capacity", C.c_uint64)]
+
+
 class _ScatterPlan(C.Structure):
     _fields_ = [("q", C.c_int), ("own_begin", C.c_int), ("own_count", C.c_int), ("tail_begin", C.c_int),
                 ("tail_count", C.c_int)]
@@ -346,6 +356,10 @@ def load_library():
         "dsx_map_integrate_depth_gt": (C.c_int, [vp, vp] + [C.c_double] * 6 + [f64p, u64p, u64p]),
         "dsx_map_compare": (C.c_int, [vp, vp, C.POINTER(_MapCompareOpts), u64p, C.POINTER(_MapCompareInfo)]),
         "dsx_map_compare_fetch": (C.c_int, [vp, f32p, u64p, C.c_size_t, szp]),
+        # include/dsi_map_prune.h: pruning the map
+        "dsx_map_prune_classify": (C.c_int, [vp, C.POINTER(_MapPruneOpts), C.POINTER(_MapPruneInfo)]),
+        "dsx_map_prune_fetch": (C.c_int, [vp, u8p, u64p, C.c_size_t, szp]),
+        "dsx_map_prune": (C.c_int, [vp, C.POINTER(_MapPruneOpts), C.POINTER(_MapPruneInfo)]),
     }
     if experiments_requested():     # hooks that exist only in the experiments flavour
         sig.update({
@@ -1202,6 +1216,56 @@ class WorldMap:
         m = n.value
         out = {"keys": np.empty(m, np.uint64), "dist": np.empty(m, np.float32)}
         _check(L.dsx_map_compare_fetch(self._h, _ptr(out["dist"], C.c_float), _ptr(out["keys"], C.c_uint64), m, C.byref(n)))
+        if sort:
+            order = np.argsort(out["keys"], kind="stable")
+            out = {k: v[order] for k, v in out.items()}
+        return out
+
+    def prune(self, min_points=1, min_windows=1, max_age=None, box=None, reach=0, min_neighbors=0, shrink=False):
+        """Removes cells and rebuilds the table around the rest (dsx_map_prune; the rule is stated in dsi_map_prune.h and
+        DESIGN.md 7j "Pruning").  A cell leaves by the first criterion that fails: fewer than min_points points; seen in
+        fewer than min_windows calls; max_age (None: off) -- more than max_age integrate calls since the last one that
+        reached it, empty calls included; box = (lo, hi), three numbers each (None: off) -- its extracted centroid outside
+        the closed box; reach 1 or 2 (0: off) -- fewer than min_neighbors other cells that survive the first four within
+        reach cells per axis.  The defaults remove nothing.  shrink=True: the table becomes the smallest that holds the
+        kept cells at 3/4 load (at least 2**8 slots).  Returns dict of n_cells = n_kept + sum(n_removed), n_kept,
+        n_removed (five counts, by criterion) and capacity (slots afterwards).  Render, compare and classification of the
+        map are invalid afterwards."""
+        return self._prune(load_library().dsx_map_prune, min_points, min_windows, max_age, box, reach, min_neighbors, shrink)
+
+    def classifyPrune(self, min_points=1, min_windows=1, max_age=None, box=None, reach=0, min_neighbors=0, shrink=False):
+        """prune()'s dry run (dsx_map_prune_classify): the same counts, the map unchanged and its render and compare still
+        valid; the per-cell verdicts stay on the device for fetchPruneReasons until the map changes."""
+        return self._prune(load_library().dsx_map_prune_classify, min_points, min_windows, max_age, box, reach, min_neighbors, shrink)
+
+    def _prune(self, fn, min_points, min_windows, max_age, box, reach, min_neighbors, shrink):
+        if max_age is not None and int(max_age) < 0:
+            raise ValueError("max_age is None or >= 0")
+        o = _MapPruneOpts()
+        o.min_points, o.min_windows = int(min_points), int(min_windows)
+        o.max_age = -1 if max_age is None else int(max_age)
+        o.use_box = 0 if box is None else 1
+        if box is not None:
+            lo, hi = (np.asarray(b, np.float64).reshape(3) for b in box)
+            o.box_lo[:], o.box_hi[:] = lo.tolist(), hi.tolist()
+        o.reach, o.min_neighbors, o.shrink = int(reach), int(min_neighbors), 1 if shrink else 0
+        i = _MapPruneInfo()
+        _check(fn(self._h, C.byref(o), C.byref(i)))
+        return {"n_cells": int(i.n_cells), "n_kept": int(i.n_kept), "n_removed": [int(v) for v in i.n_removed],
+                "capacity": int(i.capacity)}
+
+    def fetchPruneReasons(self, sort=True):
+        """keys (uint64) and reason (uint8: 0 kept, 1..5 the first criterion that failed) of every cell, from the last
+        classifyPrune() of this map (dsx_map_prune_fetch); raises DsiError when the map changed since, or was never
+        classified.  sort=True orders them by ascending key; otherwise the order is extract(sort=False)'s."""
+        L = load_library()
+        n = C.c_size_t()
+        rc = L.dsx_map_prune_fetch(self._h, None, None, 0, C.byref(n))
+        if rc != OK and n.value == 0:
+            _check(rc)
+        m = n.value
+        out = {"keys": np.empty(m, np.uint64), "reason": np.empty(m, np.uint8)}
+        _check(L.dsx_map_prune_fetch(self._h, _ptr(out["reason"], C.c_uint8), _ptr(out["keys"], C.c_uint64), m, C.byref(n)))
         if sort:
             order = np.argsort(out["keys"], kind="stable")
             out = {k: v[order] for k, v in out.items()}

@@ -746,7 +746,7 @@ class WindowStream:
 def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop_time_s, duration,
                   out_skip, fusion_method=E.FUSE_HM, forward_looking=True, rv_pos=0.0, options_depth_map=None,
                   options_point_cloud=None, polarities=None, save_images=False, out_path=None, lut=None, score=None,
-                  ground_truth=None, ground_truth_disparity=None, thicken_edges=False, world_map=None, **kw):
+                  ground_truth=None, ground_truth_disparity=None, thicken_edges=False, world_map=None, world_map_prune=None, **kw):
     """Generator over the windows of main.cpp:177-302: yields (ts, depth, confidence, indices) per
     window, pipelined one window deep; with options_depth_map, (ts, depth_map, confidence_map, mask)
     -- the filtered outputs the reference saves per window; with options_point_cloud as well, the window's
@@ -783,7 +783,30 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
     one this generator yields, for process_method 2 / 5 the time_camera output's -- is also merged into the map where it
     lies on the device (WorldMap.integrate_mapper) with T_w_rv = engine.invert_pose(the window's T_rv_w), before the
     window is yielded: the reference views differ per window, the map is in the world frame.  What is yielded does not
-    change.  The map lives on one context, so concurrent=True (a context per window in flight) is refused."""
+    change.  The map lives on one context, so concurrent=True (a context per window in flight) is refused.
+    world_map_prune= (with world_map=; None leaves the stream as it is): a dict of WorldMap.prune's keywords plus `every`
+    (default 1: the map is pruned after every every-th window, right after that window's cloud went in) and optionally
+    `local_box` = (hx, hy, hz) instead of `box`: the box is then the window's reference position +- the half extents,
+    lo = t - h and hi = t + h in double with t the translation of the T_w_rv the window was integrated with -- a local map
+    that forgets what lies behind the vehicle (max_age does the same by calls).  A pruned window's result gains a last
+    element, {"world_map_prune": the counts WorldMap.prune returns}."""
+    prune = None
+    if world_map_prune is not None:
+        if world_map is None:
+            raise ValueError("world_map_prune needs world_map")
+        prune = dict(world_map_prune)
+        every, local_box = prune.pop("every", 1), prune.pop("local_box", None)
+        if int(every) != every or every < 1:
+            raise ValueError("world_map_prune['every'] must be an integer >= 1")
+        if local_box is not None:
+            if prune.get("box") is not None:
+                raise ValueError("world_map_prune takes box or local_box, not both")
+            local_box = np.asarray(local_box, np.float64).reshape(3)
+        unknown = set(prune) - {"min_points", "min_windows", "max_age", "box", "reach", "min_neighbors", "shrink"}
+        if unknown:
+            raise ValueError("world_map_prune: unknown keys %s" % sorted(unknown))
+        prune = (prune, int(every), local_box)
+    windows_seen = 0
     if world_map is not None:
         if options_point_cloud is None:
             raise ValueError("world_map needs options_depth_map and options_point_cloud: the map is made of the windows' clouds")
@@ -820,6 +843,16 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
     if save_images:
         images = {"fusion_method": int(fusion_method), "min_depth": dsi_shape.min_depth_, "max_depth": dsi_shape.max_depth_, "out_path": out_path,
                   "lut": lut}
+
+    def result(pending):
+        nonlocal windows_seen
+        out = _window_result(ws, pending, options_depth_map, options_point_cloud, images, scoring, world_map)
+        if prune is not None:
+            windows_seen += 1
+            if windows_seen % prune[1] == 0:
+                out = out + ({"world_map_prune": _prune_world_map(world_map, prune[0], prune[2], pending[3])},)
+        return out
+
     try:
         for t0, t1 in window_bounds(start_time_s, stop_time_s, duration, out_skip):
             ts = t1 if forward_looking else 0.5 * (t0 + t1)          # main.cpp:185-189
@@ -830,12 +863,21 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
                                                     cams[0]) for c in range(2)]       # cam0.fullResolution(), :246
             slot = ws.submit(ev, trajectories, ts, rv_pos)
             if pending is not None:
-                yield _window_result(ws, pending, options_depth_map, options_point_cloud, images, scoring, world_map)
+                yield result(pending)
             pending = (ts, slot, event_images, ws.T_rv_w[slot])
         if pending is not None:
-            yield _window_result(ws, pending, options_depth_map, options_point_cloud, images, scoring, world_map)
+            yield result(pending)
     finally:
         ws.close()
+
+
+def _prune_world_map(world_map, opts, local_box, T_rv_w):
+    """One prune of a streamed map: opts as WorldMap.prune takes them; with local_box the box around the window's reference
+    position, the translation of engine.invert_pose(T_rv_w) -- the T_w_rv the window's cloud was integrated with."""
+    if local_box is not None:
+        t = E.invert_pose(T_rv_w)[[3, 7, 11]]
+        opts = dict(opts, box=(t - local_box, t + local_box))
+    return world_map.prune(**opts)
 
 
 def _window_event_image(ctx, events, polarity, t_start, t_stop, cam):

@@ -34,6 +34,7 @@
 
 #include "dsi_engine.h"
 #include "dsi_map_eval.h"
+#include "dsi_map_prune.h"
 
 namespace dsi {
 
@@ -1614,6 +1615,27 @@ struct MapDistances {  // by ascending key when sorted
     std::vector<float> dist;  // +inf where the cell is unmatched
     size_t size() const { return keys.size(); }
 };
+// pruning (dsi_map_prune.h: dsx_map_prune): the options -- the defaults switch every criterion off -- and what a prune counts
+struct MapPruneOptions : dsx_map_prune_opts_t {
+    MapPruneOptions() : dsx_map_prune_opts_t{}
+    {
+        min_points = min_windows = 1;
+        max_age = -1;
+    }
+    // criterion 4: the closed box [lo, hi]
+    MapPruneOptions& box(const std::array<double, 3>& lo, const std::array<double, 3>& hi)
+    {
+        use_box = 1;
+        for (int a = 0; a < 3; ++a) box_lo[a] = lo[(size_t)a], box_hi[a] = hi[(size_t)a];
+        return *this;
+    }
+};
+using MapPruneInfo = dsx_map_prune_info_t;
+struct MapPruneReasons {  // by ascending key when sorted
+    std::vector<uint64_t> keys;
+    std::vector<uint8_t> reason;  // 0 kept, 1..5 the first criterion that failed
+    size_t size() const { return keys.size(); }
+};
 class WorldMap {
 public:
     WorldMap(Context& ctx, double leaf, int capacity_log2 = 16) : ctx_(ctx) { check(dsi_map_create(ctx.handle(), leaf, capacity_log2, &h_)); }
@@ -1760,6 +1782,44 @@ public:
         for (size_t i : order) {
             out.keys.push_back(raw.keys[i]);
             out.dist.push_back(raw.dist[i]);
+        }
+        return out;
+    }
+
+    // removes the cells that fail opts and rebuilds the table around the rest (dsx_map_prune; the rule is stated in
+    // dsi_map_prune.h); render, compare and classification of the map are invalid afterwards
+    MapPruneInfo prune(const MapPruneOptions& opts = MapPruneOptions())
+    {
+        MapPruneInfo info;
+        check(dsx_map_prune(h_, &opts, &info));
+        return info;
+    }
+    // prune's dry run (dsx_map_prune_classify): the same counts, the map unchanged; the verdicts stay on the device for
+    // fetchPruneReasons until the map changes
+    MapPruneInfo classifyPrune(const MapPruneOptions& opts = MapPruneOptions())
+    {
+        MapPruneInfo info;
+        check(dsx_map_prune_classify(h_, &opts, &info));
+        return info;
+    }
+    // (key, reason) of every cell from the last classifyPrune of this map; sort: by ascending key
+    MapPruneReasons fetchPruneReasons(bool sort = true) const
+    {
+        MapPruneReasons raw;
+        size_t n = 0;
+        const int rc = dsx_map_prune_fetch(h_, nullptr, nullptr, 0, &n);
+        if (rc != DSI_OK && n == 0) check(rc);
+        raw.keys.resize(n);
+        raw.reason.resize(n);
+        check(dsx_map_prune_fetch(h_, raw.reason.data(), raw.keys.data(), n, &n));
+        if (!sort) return raw;
+        std::vector<size_t> order(n);
+        for (size_t i = 0; i < n; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return raw.keys[a] < raw.keys[b]; });
+        MapPruneReasons out;
+        for (size_t i : order) {
+            out.keys.push_back(raw.keys[i]);
+            out.reason.push_back(raw.reason[i]);
         }
         return out;
     }
