@@ -10,6 +10,7 @@
 #include "../../include/dsi_engine.h"
 #include "../../include/dsi_map_eval.h"
 #include "../../include/dsi_map_prune.h"
+#include "../../include/dsi_map_merge.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: librccl is loaded at run time (load_rccl)
@@ -4069,6 +4070,9 @@ struct dsi_map {
     DevBuf<uint8_t> prune_first, prune_reason, prune_reason_out;  // per slot: by criteria 1-4, final; compacted for a fetch
     DevBuf<unsigned long long> prune_ctr;
     bool prune_valid = false;
+    // dsx_map_export's remaining outputs and dsx_map_merge's counters (include/dsi_map_merge.h)
+    DevBuf<unsigned long long> sums_out, merge_ctr;
+    DevBuf<uint32_t> stamp_out;
 };
 
 namespace {
@@ -4685,6 +4689,172 @@ int dsx_map_prune(dsi_map_t* mp, const dsx_map_prune_opts_t* opts, dsx_map_prune
     }
     map_prune_info(mp, ctr, info);
     return DSI_OK;
+}
+
+// ---- merging maps and moving their state (include/dsi_map_merge.h; DESIGN.md 7j "Merging") ----
+
+namespace {
+
+// the source of a merge, whichever table holds it: another map's, or the scratch table an import built
+struct MapMergeSource {
+    dsi::MapTable t;
+    uint64_t cells, calls, accepted, rejected;
+};
+
+// the bounds that the two maps' states must meet together: judged on the host, before dst is touched
+int map_merge_check(const dsi_map* dst, uint64_t cells, uint64_t calls, uint64_t accepted)
+{
+    REQUIRE(dst->host_ctr[3] == 0, DSI_ERR_INVALID, "dst's table overflowed in an earlier call: reset the map");
+    REQUIRE(calls <= 0xffffffffull && dst->calls + calls <= 0xffffffffull, DSI_ERR_INVALID,
+            "calls: %llu + %llu integrate calls exceed 2^32 - 1 (stamps are 32 bits wide): dst is unchanged",
+            (unsigned long long)dst->calls, (unsigned long long)calls);
+    REQUIRE(accepted <= 0xffffffffull && dst->host_ctr[1] + accepted <= 0xffffffffull, DSI_ERR_INVALID,
+            "accepted: %llu + %llu accepted points exceed 2^32 - 1 (a cell's n is 32 bits wide): dst is unchanged", dst->host_ctr[1],
+            (unsigned long long)accepted);
+    REQUIRE(cells <= ((uint64_t)1 << kMapMaxLog2) && (dst->host_ctr[0] + cells) * 4 <= ((uint64_t)3 << kMapMaxLog2), DSI_ERR_INVALID,
+            "%llu cells + %llu cells need more than 2^%d slots: dst is unchanged", dst->host_ctr[0], (unsigned long long)cells, kMapMaxLog2);
+    return DSI_OK;
+}
+
+// the one routine behind dsx_map_merge and dsx_map_import: dst grown for src's cells, then src appended; synchronises
+int map_merge_apply(dsi_map* dst, const MapMergeSource& src, dsx_map_merge_info_t* info)
+{
+    hipStream_t st = dst->ctx->stream;
+    HIP_TRY(dst->merge_ctr.reserve(dsi::kMapMergeCounters));
+    const uint64_t growths_before = dst->growths;
+    if (int rc = map_grow_for(dst, (size_t)src.cells)) return rc;                 // (a failed allocation leaves dst as it is)
+    dst->render_valid = dst->compare_valid = dst->prune_valid = false;  // (the map changes from here on)
+    unsigned long long mctr[dsi::kMapMergeCounters] = {0, 0};
+    HIP_TRY(dsi::launch_map_merge(st, src.t, dsi::map_table_at(dst->block.p, dst->cap_log2), (uint32_t)dst->calls, src.accepted,
+                                  src.rejected, dst->ctr.p, dst->merge_ctr.p));
+    HIP_TRY(hipMemcpyAsync(dst->host_ctr, dst->ctr.p, sizeof dst->host_ctr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(mctr, dst->merge_ctr.p, sizeof mctr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    dst->calls += src.calls;
+    REQUIRE(dst->host_ctr[3] == 0 && mctr[0] + mctr[1] == src.cells, DSI_ERR_HIP,
+            "the merge placed %llu of %llu cells (%llu found the table full): an engine bug, the map is unusable", mctr[0] + mctr[1],
+            (unsigned long long)src.cells, dst->host_ctr[3]);
+    if (info) {
+        info->n_src_cells = src.cells;
+        info->n_new = mctr[0];
+        info->n_common = mctr[1];
+        info->capacity = (uint64_t)1 << dst->cap_log2;
+        info->growths = dst->growths - growths_before;
+    }
+    return DSI_OK;
+}
+
+}  // namespace
+
+int dsx_map_export(dsi_map_t* mp, dsx_map_state_t* state, uint64_t* keys_host, uint32_t* n_host, uint64_t* sums_host,
+                   uint32_t* windows_host, uint32_t* stamp_host, size_t capacity, size_t* count)
+{
+    REQUIRE(mp && count, DSI_ERR_INVALID, "null argument");
+    if (int rc = set_device(mp->ctx)) return rc;
+    size_t total = 0;
+    if (int rc = map_count_device(mp, 0, 0, &total)) return rc;
+    if (state) {
+        state->leaf = mp->leaf;
+        state->n_cells = total;
+        state->calls = mp->calls;
+        state->accepted = mp->host_ctr[1];
+        state->rejected = mp->host_ctr[2];
+    }
+    *count = total;
+    REQUIRE(capacity >= total, DSI_ERR_INVALID, "capacity of %zu cells is too small: %zu needed", capacity, total);
+    if (!total || !(keys_host || n_host || sums_host || windows_host || stamp_host)) return DSI_OK;
+    hipStream_t st = mp->ctx->stream;
+    HIP_TRY(mp->key_out.reserve(total));
+    HIP_TRY(mp->n_out.reserve(total));
+    HIP_TRY(mp->sums_out.reserve(3 * total));
+    HIP_TRY(mp->w_out.reserve(total));
+    HIP_TRY(mp->stamp_out.reserve(total));
+    HIP_TRY(dsi::launch_map_export(st, dsi::map_table_at(mp->block.p, mp->cap_log2), mp->blk.p, mp->key_out.p, mp->n_out.p, mp->sums_out.p,
+                                   mp->w_out.p, mp->stamp_out.p));
+    if (keys_host) HIP_TRY(hipMemcpyAsync(keys_host, mp->key_out.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (n_host) HIP_TRY(hipMemcpyAsync(n_host, mp->n_out.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (sums_host) HIP_TRY(hipMemcpyAsync(sums_host, mp->sums_out.p, 3 * total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (windows_host) HIP_TRY(hipMemcpyAsync(windows_host, mp->w_out.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (stamp_host) HIP_TRY(hipMemcpyAsync(stamp_host, mp->stamp_out.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+int dsx_map_merge(dsi_map_t* dst, dsi_map_t* src, dsx_map_merge_info_t* info)
+{
+    REQUIRE(dst, DSI_ERR_INVALID, "dst is null");
+    REQUIRE(src, DSI_ERR_INVALID, "src is null");
+    REQUIRE(dst != src, DSI_ERR_INVALID, "same map: dst and src are one map");
+    REQUIRE(dst->ctx == src->ctx, DSI_ERR_CONTEXT, "contexts: dst and src live on different contexts, export and import instead");
+    REQUIRE(std::memcmp(&dst->leaf, &src->leaf, sizeof(double)) == 0, DSI_ERR_INVALID, "leaf: dst has %.17g, src has %.17g", dst->leaf,
+            src->leaf);
+    REQUIRE(src->host_ctr[3] == 0, DSI_ERR_INVALID, "src's table overflowed in an earlier call");
+    if (int rc = map_merge_check(dst, src->host_ctr[0], src->calls, src->host_ctr[1])) return rc;
+    if (int rc = set_device(dst->ctx)) return rc;
+    const MapMergeSource s{dsi::map_table_at(src->block.p, src->cap_log2), src->host_ctr[0], src->calls, src->host_ctr[1], src->host_ctr[2]};
+    return map_merge_apply(dst, s, info);
+}
+
+int dsx_map_import(dsi_map_t* dst, const dsx_map_state_t* state, const uint64_t* keys_host, const uint32_t* n_host,
+                   const uint64_t* sums_host, const uint32_t* windows_host, const uint32_t* stamp_host, dsx_map_merge_info_t* info)
+{
+    REQUIRE(dst, DSI_ERR_INVALID, "dst is null");
+    REQUIRE(state, DSI_ERR_INVALID, "state is null");
+    REQUIRE(std::isfinite(state->leaf) && state->leaf > 0.0, DSI_ERR_INVALID, "leaf: must be finite and > 0 (got %g)", state->leaf);
+    const uint64_t m = state->n_cells;
+    REQUIRE(m <= ((uint64_t)1 << kMapMaxLog2), DSI_ERR_INVALID, "n_cells: at most 2^%d cells (got %llu)", kMapMaxLog2, (unsigned long long)m);
+    if (m) {
+        REQUIRE(keys_host, DSI_ERR_INVALID, "keys is null");
+        REQUIRE(n_host, DSI_ERR_INVALID, "n is null");
+        REQUIRE(sums_host, DSI_ERR_INVALID, "sums is null");
+        REQUIRE(windows_host, DSI_ERR_INVALID, "windows is null");
+        REQUIRE(stamp_host, DSI_ERR_INVALID, "stamp is null");
+    }
+    REQUIRE(std::memcmp(&dst->leaf, &state->leaf, sizeof(double)) == 0, DSI_ERR_INVALID, "leaf: dst has %.17g, the state has %.17g",
+            dst->leaf, state->leaf);
+    if (int rc = map_merge_check(dst, m, state->calls, state->accepted)) return rc;
+    if (int rc = set_device(dst->ctx)) return rc;
+    hipStream_t st = dst->ctx->stream;
+    // the scratch table: the smallest that holds m cells at 3/4 load; it and the uploads live for this call
+    uint32_t want = kMapMinLog2;
+    while (m * 4 > ((uint64_t)3 << want)) ++want;
+    DevBuf<unsigned char> scratch;
+    DevBuf<unsigned long long> keys, sums, ctr;
+    DevBuf<uint32_t> n, windows, stamp;
+    hipError_t e = scratch.reserve(dsi::map_table_bytes(want));
+    if (e == hipSuccess) e = ctr.reserve(dsi::kMapImportCounters);
+    if (e == hipSuccess && m) e = keys.reserve(m);
+    if (e == hipSuccess && m) e = sums.reserve(3 * m);
+    if (e == hipSuccess && m) e = n.reserve(m);
+    if (e == hipSuccess && m) e = windows.reserve(m);
+    if (e == hipSuccess && m) e = stamp.reserve(m);
+    if (e != hipSuccess)
+        return fail(DSI_ERR_HIP, "a scratch table of 2^%u slots for %llu cells could not be allocated (%s): dst is unchanged", want,
+                    (unsigned long long)m, hipGetErrorString(e));
+    HIP_TRY(hipMemsetAsync(scratch.p, 0, dsi::map_table_bytes(want), st));
+    if (m) {
+        HIP_TRY(hipMemcpyAsync(keys.p, keys_host, m * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(sums.p, sums_host, 3 * m * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(n.p, n_host, m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(windows.p, windows_host, m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(stamp.p, stamp_host, m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
+    const dsi::MapTable table = dsi::map_table_at(scratch.p, want);
+    unsigned long long c[dsi::kMapImportCounters] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIP_TRY(dsi::launch_map_import_build(st, keys.p, n.p, sums.p, windows.p, stamp.p, (uint32_t)m, (uint32_t)state->calls, table, ctr.p));
+    HIP_TRY(hipMemcpyAsync(c, ctr.p, sizeof c, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    REQUIRE(c[0] == 0, DSI_ERR_INVALID, "keys: %llu cells have the key 0 or a packed coordinate outside [1, 2^21 - 3]", c[0]);
+    REQUIRE(c[1] == 0, DSI_ERR_INVALID, "keys: %llu duplicate keys", c[1]);
+    REQUIRE(c[2] == 0, DSI_ERR_INVALID, "n: %llu cells have n == 0", c[2]);
+    REQUIRE(c[3] == 0, DSI_ERR_INVALID, "windows: %llu cells have windows == 0, windows > n or windows > stamp", c[3]);
+    REQUIRE(c[4] == 0, DSI_ERR_INVALID, "stamp: %llu cells have stamp == 0 or stamp > calls (%llu)", c[4], (unsigned long long)state->calls);
+    REQUIRE(c[5] == 0, DSI_ERR_INVALID, "sums: %llu cells have a sum above n * 2^32", c[5]);
+    REQUIRE(c[6] == 0, DSI_ERR_HIP, "the scratch table ran full (%llu cells lost): an engine bug; dst is unchanged", c[6]);
+    REQUIRE(state->accepted >= c[7], DSI_ERR_INVALID, "accepted: the state names %llu accepted points, its cells hold %llu",
+            (unsigned long long)state->accepted, c[7]);
+    const MapMergeSource s{table, m, state->calls, state->accepted, state->rejected};
+    return map_merge_apply(dst, s, info);
 }
 
 int dsi_mapper_last_vote_info(const dsi_mapper_t* m, dsi_vote_info_t* info)

@@ -419,6 +419,23 @@ hipError_t launch_map_prune_rehash(hipStream_t s, const MapTable& from, const Ma
 hipError_t launch_map_prune_gather(hipStream_t s, const MapTable& t, const uint8_t* reason, const uint32_t* blk, uint8_t* reason_out,
                                    unsigned long long* key_out);
 
+// ---- merging maps and moving their state (include/dsi_map_merge.h; DESIGN.md 7j "Merging") ----
+constexpr int kMapImportCounters = 8;  // bad key, duplicate, n == 0, bad windows, bad stamp, S too large, table full, sum of n
+constexpr int kMapMergeCounters = 2;   // cells new to dst, cells both maps hold
+// after launch_map_count(t, 0, 0): the raw state of every cell in slot order (launch_map_extract's); sums_out: 3 per cell
+hipError_t launch_map_export(hipStream_t s, const MapTable& t, const uint32_t* blk, unsigned long long* key_out, uint32_t* n_out,
+                             unsigned long long* sums_out, uint32_t* w_out, uint32_t* stamp_out);
+// clears ctr [kMapImportCounters]; m incoming cells (device arrays) checked against `calls` and built into `to` (zeroed by
+// the caller, 4 m <= 3 slots); the state is usable only when ctr[0..6] are all 0
+hipError_t launch_map_import_build(hipStream_t s, const unsigned long long* keys, const uint32_t* n, const unsigned long long* sums,
+                                   const uint32_t* windows, const uint32_t* stamp, uint32_t m, uint32_t calls, const MapTable& to,
+                                   unsigned long long* ctr);
+// clears mctr [kMapMergeCounters]; every cell of src appended to dst with its stamp moved by off; ctr: dst's four counters,
+// [0] += new cells, [1] += add_accepted, [2] += add_rejected, [3] += cells that found dst full.  The caller keeps dst's
+// occupied + src's cells <= 3/4 of dst's capacity and every sum below 2^32.
+hipError_t launch_map_merge(hipStream_t s, const MapTable& src, const MapTable& dst, uint32_t off, unsigned long long add_accepted,
+                            unsigned long long add_rejected, unsigned long long* ctr, unsigned long long* mctr);
+
 // focus-based collapses (Grid3D::collapseZSliceBy*, cartesian3dgrid.cpp:192-414; DESIGN.md "Focus-based collapses"):
 // method 0 LocalVar, 1 LocalMeanSquare, 2 GradMag (half_patchsize 0..8), 3 LaplacianMag, 4 DoG.  keys: scratch of
 // focus_chunks(nx, ny, nz) * nx * ny words, fully written before it is read.  planes / depth as launch_collapse_max_z.

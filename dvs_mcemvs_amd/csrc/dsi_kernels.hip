@@ -7343,6 +7343,160 @@ __global__ void __launch_bounds__(kPcBlock) k_map_prune_gather(MapTable t, const
     key_out[o] = t.keys[i];
 }
 
+// ---- merging maps and moving their state (include/dsi_map_merge.h dsx_map_export / import / merge; DESIGN.md 7j "Merging") ----
+// Every occupied slot's raw state compacted like k_map_extract's cells under the filter (0, 0), with its blk_off (one
+// offset per tile of kPcBlock slots): key, n, S[3], windows and stamp in slot order.  Walked in strides like k_map_render;
+// reads the table only.
+__global__ void __launch_bounds__(kPcBlock) k_map_export(MapTable t, const uint32_t* __restrict__ blk_off,
+                                                         unsigned long long* __restrict__ key_out, uint32_t* __restrict__ n_out,
+                                                         unsigned long long* __restrict__ sums_out, uint32_t* __restrict__ w_out,
+                                                         uint32_t* __restrict__ stamp_out)
+{
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        const bool f = map_passes(t, i, 0u, 0u);
+        uint32_t total;
+        const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);  // (every thread of the workgroup, every round)
+        if (f) {
+            const size_t o = (size_t)blk_off[base / kPcBlock] + rank;
+            key_out[o] = t.keys[i];
+            n_out[o] = t.n[i];
+            w_out[o] = t.windows[i];
+            stamp_out[o] = t.stamp[i];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) sums_out[3 * o + a] = t.sums[3 * i + a];
+        }
+    }
+}
+
+// m incoming cells (host arrays, nothing trusted) checked and built into the zeroed table `to`.  Per cell, each counted on
+// its own: [0] key 0 or a packed coordinate outside [1, 2 kPcCellMax + 1]; [1] a duplicate -- map_slot does not report the
+// key as fresh (a bad key is not inserted); [2] n == 0; [3] windows == 0, > n or > stamp; [4] stamp == 0 or > calls;
+// [5] some S[a] > n * 2^32 (n < 2^32: the product is exact in 64 bits); [6] `to` found full; [7] the sum of n.  A fresh
+// slot has one writer: plain stores.  ctr [kMapImportCounters]: one global atomic per workgroup and counter.
+__global__ void __launch_bounds__(kPcBlock) k_map_import_build(const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ n,
+                                                               const unsigned long long* __restrict__ sums,
+                                                               const uint32_t* __restrict__ windows, const uint32_t* __restrict__ stamp,
+                                                               uint32_t m, uint32_t calls, MapTable to, unsigned long long* __restrict__ ctr)
+{
+    __shared__ unsigned long long s_cnt[kMapImportCounters];
+    if (threadIdx.x < kMapImportCounters) s_cnt[threadIdx.x] = 0ull;
+    __syncthreads();
+    uint32_t c[kMapImportCounters - 1] = {0, 0, 0, 0, 0, 0, 0};  // (the same in every lane of a wave)
+    unsigned long long sum_n = 0ull;                            // (per lane)
+    const uint32_t mask = (1u << to.cap_log2) - 1u;
+    const size_t stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < m; base += stride) {
+        const size_t i = base + threadIdx.x;
+        bool bad[kMapImportCounters - 1] = {false, false, false, false, false, false, false};
+        if (i < m) {
+            const unsigned long long k = keys[i];
+            const uint32_t cn = n[i], cw = windows[i], cs = stamp[i];
+            const unsigned long long S0 = sums[3 * i], S1 = sums[3 * i + 1], S2 = sums[3 * i + 2];
+            bad[0] = k == 0ull || (k >> 63) != 0ull;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const uint32_t p = (uint32_t)((k >> (21 * a)) & 0x1fffffull);
+                bad[0] = bad[0] || p < 1u || p > 2u * (uint32_t)kPcCellMax + 1u;
+            }
+            bad[2] = cn == 0u;
+            bad[3] = cw == 0u || cw > cn || cw > cs;
+            bad[4] = cs == 0u || cs > calls;
+            const unsigned long long most = (unsigned long long)cn << 32;
+            bad[5] = S0 > most || S1 > most || S2 > most;
+            sum_n += cn;
+            if (!bad[0]) {
+                bool fresh = false;
+                const uint32_t slot = map_slot(to.keys, mask, k, &fresh);
+                if (slot == ~0u) {
+                    bad[6] = true;
+                } else if (!fresh) {
+                    bad[1] = true;
+                } else {
+                    to.n[slot] = cn;
+                    to.windows[slot] = cw;
+                    to.stamp[slot] = cs;
+                    to.sums[3 * (size_t)slot + 0] = S0;
+                    to.sums[3 * (size_t)slot + 1] = S1;
+                    to.sums[3 * (size_t)slot + 2] = S2;
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kMapImportCounters - 1; ++q) c[q] += (uint32_t)__popcll(__ballot(bad[q]));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum_n += __shfl_down(sum_n, off, 64);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < kMapImportCounters - 1; ++q)
+            if (c[q]) atomicAdd(&s_cnt[q], (unsigned long long)c[q]);
+        if (sum_n) atomicAdd(&s_cnt[kMapImportCounters - 1], sum_n);
+    }
+    __syncthreads();
+    if (threadIdx.x < kMapImportCounters && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], s_cnt[threadIdx.x]);
+}
+
+// src appended to dst (dsi_map_merge.h "the rule"): one thread per slot of src, in strides.  src's keys are distinct, so
+// exactly one thread finds or claims a given slot of dst and nothing else writes dst meanwhile: after map_slot's
+// compare-and-swap the cell's words are read, combined and stored plainly -- n, S[3] and windows added, stamp =
+// max(stamp, stamp_src + off); a claimed slot holds zeros.  Sums and maxima of integers: the result depends neither on the
+// thread order nor on either table's size nor on the probing.  The host has checked that no sum wraps.  mctr: [0] += cells
+// new to dst, [1] += cells both hold; ctr (dst's four counters): [0] += new, [3] += cells that found dst full (map_slot is
+// bounded by the capacity: an error, not a hang), and one thread adds src's accepted and rejected points to [1] and [2].
+__global__ void __launch_bounds__(kPcBlock) k_map_merge(MapTable src, MapTable dst, uint32_t off, unsigned long long add_accepted,
+                                                        unsigned long long add_rejected, unsigned long long* __restrict__ ctr,
+                                                        unsigned long long* __restrict__ mctr)
+{
+    __shared__ uint32_t s_cnt[3];
+    if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    uint32_t c_new = 0, c_common = 0, c_full = 0;  // (the same in every lane of a wave)
+    const uint32_t mask = (1u << dst.cap_log2) - 1u;
+    const size_t cap = (size_t)1 << src.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        const unsigned long long k = src.keys[i];  // (cap is a multiple of the workgroup: i < cap)
+        bool is_new = false, is_common = false, full = false;
+        if (k != 0ull) {
+            bool fresh = false;
+            const uint32_t slot = map_slot(dst.keys, mask, k, &fresh);
+            if (slot == ~0u) {
+                full = true;
+            } else {
+                is_new = fresh;
+                is_common = !fresh;
+                dst.n[slot] += src.n[i];
+                dst.windows[slot] += src.windows[i];
+                const uint32_t moved = src.stamp[i] + off, had = dst.stamp[slot];
+                dst.stamp[slot] = moved > had ? moved : had;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) dst.sums[3 * (size_t)slot + a] += src.sums[3 * i + a];
+            }
+        }
+        c_new += (uint32_t)__popcll(__ballot(is_new));
+        c_common += (uint32_t)__popcll(__ballot(is_common));
+        c_full += (uint32_t)__popcll(__ballot(full));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (c_new) atomicAdd(&s_cnt[0], c_new);
+        if (c_common) atomicAdd(&s_cnt[1], c_common);
+        if (c_full) atomicAdd(&s_cnt[2], c_full);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt[0]) {
+        atomicAdd(&ctr[0], (unsigned long long)s_cnt[0]);
+        atomicAdd(&mctr[0], (unsigned long long)s_cnt[0]);
+    }
+    if (threadIdx.x == 1 && s_cnt[1]) atomicAdd(&mctr[1], (unsigned long long)s_cnt[1]);
+    if (threadIdx.x == 2 && s_cnt[2]) atomicAdd(&ctr[3], (unsigned long long)s_cnt[2]);
+    if (blockIdx.x == 0 && threadIdx.x == 3) {
+        if (add_accepted) atomicAdd(&ctr[1], add_accepted);
+        if (add_rejected) atomicAdd(&ctr[2], add_rejected);
+    }
+}
+
 }  // namespace
 
 size_t map_table_bytes(uint32_t cap_log2) { return ((size_t)1 << cap_log2) * (4 * sizeof(unsigned long long) + 3 * sizeof(uint32_t)); }
@@ -7457,6 +7611,35 @@ hipError_t launch_map_prune_gather(hipStream_t s, const MapTable& t, const uint8
 {
     const uint32_t nb = pc_blocks((size_t)1 << t.cap_log2);
     hipLaunchKernelGGL(k_map_prune_gather, dim3(nb), dim3(kPcBlock), 0, s, t, reason, blk, reason_out, key_out);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_export(hipStream_t s, const MapTable& t, const uint32_t* blk, unsigned long long* key_out, uint32_t* n_out,
+                             unsigned long long* sums_out, uint32_t* w_out, uint32_t* stamp_out)
+{
+    hipLaunchKernelGGL(k_map_export, dim3(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s, t, blk,
+                       key_out, n_out, sums_out, w_out, stamp_out);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_import_build(hipStream_t s, const unsigned long long* keys, const uint32_t* n, const unsigned long long* sums,
+                                   const uint32_t* windows, const uint32_t* stamp, uint32_t m, uint32_t calls, const MapTable& to,
+                                   unsigned long long* ctr)
+{
+    hipError_t e = hipMemsetAsync(ctr, 0, kMapImportCounters * sizeof(unsigned long long), s);
+    if (e != hipSuccess || m == 0) return e;
+    hipLaunchKernelGGL(k_map_import_build, dim3(std::min(pc_blocks(m), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s, keys, n, sums, windows,
+                       stamp, m, calls, to, ctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_merge(hipStream_t s, const MapTable& src, const MapTable& dst, uint32_t off, unsigned long long add_accepted,
+                            unsigned long long add_rejected, unsigned long long* ctr, unsigned long long* mctr)
+{
+    hipError_t e = hipMemsetAsync(mctr, 0, kMapMergeCounters * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_map_merge, dim3(std::min(pc_blocks((size_t)1 << src.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s, src,
+                       dst, off, add_accepted, add_rejected, ctr, mctr);
     return hipExtGetLastError();
 }
 

@@ -100,6 +100,16 @@ class _MapPruneInfo(C.Structure):
     _fields_ = [("n_cells", C.c_uint64), ("n_kept", C.c_uint64), ("n_removed", C.c_uint64 * 5), ("capacity", C.c_uint64)]
 
 
+class _MapState(C.Structure):
+    _fields_ = [("leaf", C.c_double), ("n_cells", C.c_uint64), ("calls", C.c_uint64), ("accepted", C.c_uint64),
+                ("rejected", C.c_uint64)]
+
+
+class _MapMergeInfo(C.Structure):
+    _fields_ = [("n_src_cells", C.c_uint64), ("n_new", C.c_uint64), ("n_common", C.c_uint64), ("capacity", C.c_uint64),
+                ("growths", C.c_uint64)]
+
+
 class _ScatterPlan(C.Structure):
     _fields_ = [("q", C.c_int), ("own_begin", C.c_int), ("own_count", C.c_int), ("tail_begin", C.c_int),
                 ("tail_count", C.c_int)]
@@ -360,6 +370,10 @@ def load_library():
         "dsx_map_prune_classify": (C.c_int, [vp, C.POINTER(_MapPruneOpts), C.POINTER(_MapPruneInfo)]),
         "dsx_map_prune_fetch": (C.c_int, [vp, u8p, u64p, C.c_size_t, szp]),
         "dsx_map_prune": (C.c_int, [vp, C.POINTER(_MapPruneOpts), C.POINTER(_MapPruneInfo)]),
+        # include/dsi_map_merge.h: merging maps, exporting and importing their state
+        "dsx_map_export": (C.c_int, [vp, C.POINTER(_MapState), u64p, u32p, u64p, u32p, u32p, C.c_size_t, szp]),
+        "dsx_map_import": (C.c_int, [vp, C.POINTER(_MapState), u64p, u32p, u64p, u32p, u32p, C.POINTER(_MapMergeInfo)]),
+        "dsx_map_merge": (C.c_int, [vp, vp, C.POINTER(_MapMergeInfo)]),
     }
     if experiments_requested():     # hooks that exist only in the experiments flavour
         sig.update({
@@ -1270,6 +1284,61 @@ class WorldMap:
             order = np.argsort(out["keys"], kind="stable")
             out = {k: v[order] for k, v in out.items()}
         return out
+
+    def exportState(self, sort=True):
+        """The map's exact state (dsx_map_export; the rule is stated in dsi_map_merge.h and DESIGN.md 7j "Merging"): dict
+        of leaf, calls, accepted, rejected and, per cell, keys (uint64), n (uint32), S (uint64, (M, 3): the sums of the
+        32-bit cell fractions), windows and stamp (uint32).  sort=True orders the cells by ascending key; otherwise the
+        order is extract(sort=False)'s.  importState() of it into an empty map restores the map bit for bit, ages
+        included; io.save_world_map writes it to a file.  Changes nothing: render, compare and classification stay."""
+        L = load_library()
+        st, cnt = _MapState(), C.c_size_t()
+        rc = L.dsx_map_export(self._h, C.byref(st), None, None, None, None, None, 0, C.byref(cnt))
+        if rc != OK and cnt.value == 0:
+            _check(rc)
+        m = cnt.value
+        cells = {"keys": np.empty(m, np.uint64), "n": np.empty(m, np.uint32), "S": np.empty((m, 3), np.uint64),
+                 "windows": np.empty(m, np.uint32), "stamp": np.empty(m, np.uint32)}
+        _check(L.dsx_map_export(self._h, C.byref(st), _ptr(cells["keys"], C.c_uint64), _ptr(cells["n"], C.c_uint32),
+                                _ptr(cells["S"], C.c_uint64), _ptr(cells["windows"], C.c_uint32), _ptr(cells["stamp"], C.c_uint32), m,
+                                C.byref(cnt)))
+        if sort:
+            order = np.argsort(cells["keys"], kind="stable")
+            cells = {k: v[order] for k, v in cells.items()}
+        out = {"leaf": float(st.leaf), "calls": int(st.calls), "accepted": int(st.accepted), "rejected": int(st.rejected)}
+        out.update(cells)
+        return out
+
+    @staticmethod
+    def _merge_info(i):
+        return {k: int(getattr(i, k)) for k in ("n_src_cells", "n_new", "n_common", "capacity", "growths")}
+
+    def importState(self, state):
+        """Appends an exported state to this map (dsx_map_import), exactly as merge() appends the map it came from: into
+        an empty map with no calls it restores that map.  state: exportState()'s dict (any cell order); the arrays are
+        validated on the device and a state that no map could have produced is refused, this map unchanged.  Returns
+        dict of n_src_cells = n_new + n_common, capacity (slots afterwards) and growths (doublings made by this call)."""
+        keys = np.ascontiguousarray(state["keys"], np.uint64).reshape(-1)
+        m = keys.shape[0]
+        n, w, s = (np.ascontiguousarray(state[k], np.uint32).reshape(-1) for k in ("n", "windows", "stamp"))
+        S = np.ascontiguousarray(state["S"], np.uint64).reshape(-1)
+        if not (n.shape[0] == w.shape[0] == s.shape[0] == m and S.shape[0] == 3 * m):
+            raise ValueError("keys, n, windows and stamp need one entry per cell and S three")
+        st = _MapState(float(state["leaf"]), m, int(state["calls"]), int(state["accepted"]), int(state["rejected"]))
+        i = _MapMergeInfo()
+        _check(load_library().dsx_map_import(self._h, C.byref(st), _ptr(keys, C.c_uint64), _ptr(n, C.c_uint32), _ptr(S, C.c_uint64),
+                                             _ptr(w, C.c_uint32), _ptr(s, C.c_uint32), C.byref(i)))
+        return self._merge_info(i)
+
+    def merge(self, other):
+        """Appends `other` (a WorldMap on the same context and of the same leaf) to this map on the device
+        (dsx_map_merge): afterwards this map is, bit for bit, the map that had made its own integrate calls and then
+        other's -- n, S and windows add up, other's stamps move behind this map's calls.  other is unchanged; this map's
+        render, compare and classification are invalid afterwards.  Maps of different contexts:
+        process.merge_world_maps.  Returns importState()'s dict."""
+        i = _MapMergeInfo()
+        _check(load_library().dsx_map_merge(self._h, other._h, C.byref(i)))
+        return self._merge_info(i)
 
     def reset(self):
         _check(load_library().dsi_map_reset(self._h))

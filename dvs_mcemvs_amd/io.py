@@ -281,6 +281,54 @@ def save_pcd_ascii(path, points):
     return n
 
 
+_MAP_SCALARS = (("leaf", np.float64), ("calls", np.uint64), ("accepted", np.uint64), ("rejected", np.uint64))
+_MAP_ARRAYS = (("keys", np.uint64, 1), ("n", np.uint32, 1), ("S", np.uint64, 2), ("windows", np.uint32, 1), ("stamp", np.uint32, 1))
+
+
+def save_world_map(path, state):
+    """A world map's exact state (engine.WorldMap.exportState) as one .npz file, with numpy alone: leaf (float64), calls,
+    accepted, rejected (uint64) and per cell keys (uint64), n (uint32), S (uint64, (M, 3)), windows and stamp (uint32).
+    Written to exactly `path` (no ".npz" is appended).  load_world_map reads it back; WorldMap.importState of that into
+    an empty map restores the map bit for bit."""
+    out = {k: np.asarray(state[k], t).reshape(()) for k, t in _MAP_SCALARS}
+    for k, t, ndim in _MAP_ARRAYS:
+        a = np.asarray(state[k])
+        if a.dtype != t or a.ndim != ndim:
+            raise ValueError("%s must be %s with %d dimension(s) (got %s, %s)" % (k, np.dtype(t).name, ndim, a.dtype.name, a.shape))
+        out[k] = a
+    _check_world_map_shapes(out)
+    with open(path, "wb") as f:
+        np.savez(f, **out)
+
+
+def _check_world_map_shapes(a):
+    m = a["keys"].shape[0]
+    if a["S"].shape != (m, 3) or any(a[k].shape != (m,) for k in ("n", "windows", "stamp")):
+        raise ValueError("keys, n, windows and stamp need one entry per cell and S three: got %s"
+                         % {k: a[k].shape for k, _, _ in _MAP_ARRAYS})
+
+
+def load_world_map(path):
+    """The state save_world_map wrote, as exportState returns it (Python numbers for leaf, calls, accepted, rejected).
+    ValueError for a missing entry, a wrong dtype or a wrong shape: nothing is converted."""
+    with np.load(path, allow_pickle=False) as z:
+        missing = [k for k, _ in _MAP_SCALARS] + [k for k, _, _ in _MAP_ARRAYS]
+        missing = [k for k in missing if k not in z.files]
+        if missing:
+            raise ValueError("not a world map file: %s missing" % ", ".join(missing))
+        a = {k: z[k] for k in z.files}
+    for k, t in _MAP_SCALARS:
+        if a[k].dtype != t or a[k].shape != ():
+            raise ValueError("%s must be a %s scalar (got %s, %s)" % (k, np.dtype(t).name, a[k].dtype.name, a[k].shape))
+    for k, t, ndim in _MAP_ARRAYS:
+        if a[k].dtype != t or a[k].ndim != ndim:
+            raise ValueError("%s must be %s with %d dimension(s) (got %s, %s)" % (k, np.dtype(t).name, ndim, a[k].dtype.name, a[k].shape))
+    _check_world_map_shapes(a)
+    out = {"leaf": float(a["leaf"]), "calls": int(a["calls"]), "accepted": int(a["accepted"]), "rejected": int(a["rejected"])}
+    out.update({k: a[k] for k, _, _ in _MAP_ARRAYS})
+    return out
+
+
 # ------------------------------------------------------------------ ROSBAG v2.0 (subset)
 _MAGIC = b"#ROSBAG V2.0\n"
 _OP_MSG, _OP_BAG_HEADER, _OP_INDEX, _OP_CHUNK, _OP_CHUNK_INFO, _OP_CONN = 2, 3, 4, 5, 6, 7

@@ -942,6 +942,22 @@ def score_world_map_3d(world_map, gt_map, radius, n_bins=16, min_points=1, min_w
     return E.map_f_score(world_map, gt_map, radius, n_bins, min_points, min_windows, min_points_gt, min_windows_gt)
 
 
+def merge_world_maps(dst, maps):
+    """Appends every map of `maps` to `dst` in the given order (engine.WorldMap.merge; the rule is stated in
+    dsi_map_merge.h and DESIGN.md 7j "Merging"): afterwards dst is, bit for bit, the map that had made its own integrate
+    calls, then those of maps[0], then those of maps[1] and so on -- for maps that hold consecutive runs of windows, the
+    map of the whole run, stamps included.  A map on dst's context is merged on the device; a map of another context
+    (another GPU, another process's state read with io.load_world_map and imported there) goes through exportState and
+    importState, with the same result.  The sources stay as they are.  Returns the list of the merges' info dicts."""
+    infos = []
+    for m in maps:
+        if m.ctx is dst.ctx:
+            infos.append(dst.merge(m))
+        else:
+            infos.append(dst.importState(m.exportState(sort=False)))
+    return infos
+
+
 def _window_result(ws, pending, options_depth_map, options_point_cloud, images=None, scoring=None, world_map=None):
     out = ws.fetch(pending[1], options_depth_map, options_point_cloud)
     if world_map is not None:       # (the filtered maps of the window are still on the device: fetch left them there)

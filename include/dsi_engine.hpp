@@ -35,6 +35,7 @@
 #include "dsi_engine.h"
 #include "dsi_map_eval.h"
 #include "dsi_map_prune.h"
+#include "dsi_map_merge.h"
 
 namespace dsi {
 
@@ -1636,6 +1637,17 @@ struct MapPruneReasons {  // by ascending key when sorted
     std::vector<uint8_t> reason;  // 0 kept, 1..5 the first criterion that failed
     size_t size() const { return keys.size(); }
 };
+// merging and moving the state (dsi_map_merge.h): a map's exact state on the host, and what a merge counts
+struct MapState {  // by ascending key when sorted
+    double leaf = 0.0;
+    uint64_t calls = 0, accepted = 0, rejected = 0;
+    std::vector<uint64_t> keys;
+    std::vector<uint32_t> n;
+    std::vector<uint64_t> S;  // 3 per cell: the sums of the 32-bit cell fractions
+    std::vector<uint32_t> windows, stamp;
+    size_t size() const { return keys.size(); }
+};
+using MapMergeInfo = dsx_map_merge_info_t;
 class WorldMap {
 public:
     WorldMap(Context& ctx, double leaf, int capacity_log2 = 16) : ctx_(ctx) { check(dsi_map_create(ctx.handle(), leaf, capacity_log2, &h_)); }
@@ -1822,6 +1834,60 @@ public:
             out.reason.push_back(raw.reason[i]);
         }
         return out;
+    }
+
+    // appends `other` (same context, same leaf) to this map on the device (dsx_map_merge; the rule is stated in
+    // dsi_map_merge.h): this map becomes the map that had made its own integrate calls and then other's.  other is
+    // unchanged; render, compare and classification of this map are invalid afterwards
+    MapMergeInfo merge(const WorldMap& other)
+    {
+        MapMergeInfo info;
+        check(dsx_map_merge(h_, other.h_, &info));
+        return info;
+    }
+    // the map's exact state (dsx_map_export); sort: by ascending key.  Changes nothing
+    MapState exportState(bool sort = true) const
+    {
+        MapState raw;
+        dsx_map_state_t st;
+        size_t m = 0;
+        const int rc = dsx_map_export(h_, &st, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &m);
+        if (rc != DSI_OK && m == 0) check(rc);
+        raw.keys.resize(m);
+        raw.n.resize(m);
+        raw.S.resize(3 * m);
+        raw.windows.resize(m);
+        raw.stamp.resize(m);
+        check(dsx_map_export(h_, &st, raw.keys.data(), raw.n.data(), raw.S.data(), raw.windows.data(), raw.stamp.data(), m, &m));
+        raw.leaf = st.leaf;
+        raw.calls = st.calls, raw.accepted = st.accepted, raw.rejected = st.rejected;
+        if (!sort) return raw;
+        std::vector<size_t> order(m);
+        for (size_t i = 0; i < m; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return raw.keys[a] < raw.keys[b]; });
+        MapState out;
+        out.leaf = raw.leaf;
+        out.calls = raw.calls, out.accepted = raw.accepted, out.rejected = raw.rejected;
+        for (size_t i : order) {
+            out.keys.push_back(raw.keys[i]);
+            out.n.push_back(raw.n[i]);
+            for (size_t a = 0; a < 3; ++a) out.S.push_back(raw.S[3 * i + a]);
+            out.windows.push_back(raw.windows[i]);
+            out.stamp.push_back(raw.stamp[i]);
+        }
+        return out;
+    }
+    // appends an exported state as merge appends the map it came from (dsx_map_import): into an empty map without calls
+    // it restores that map.  The state is validated on the device; a refused state leaves this map unchanged
+    MapMergeInfo importState(const MapState& state)
+    {
+        const size_t m = state.keys.size();
+        if (state.n.size() != m || state.windows.size() != m || state.stamp.size() != m || state.S.size() != 3 * m)
+            throw Error(DSI_ERR_INVALID, "MapState: keys, n, windows and stamp need one entry per cell and S three");
+        const dsx_map_state_t st{state.leaf, (uint64_t)m, state.calls, state.accepted, state.rejected};
+        MapMergeInfo info;
+        check(dsx_map_import(h_, &st, state.keys.data(), state.n.data(), state.S.data(), state.windows.data(), state.stamp.data(), &info));
+        return info;
     }
 
 private:
