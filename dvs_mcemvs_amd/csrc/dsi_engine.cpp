@@ -11,6 +11,7 @@
 #include "../../include/dsi_map_eval.h"
 #include "../../include/dsi_map_prune.h"
 #include "../../include/dsi_map_merge.h"
+#include "../../include/dsi_map_align.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: librccl is loaded at run time (load_rccl)
@@ -4073,6 +4074,12 @@ struct dsi_map {
     // dsx_map_export's remaining outputs and dsx_map_merge's counters (include/dsi_map_merge.h)
     DevBuf<unsigned long long> sums_out, merge_ctr;
     DevBuf<uint32_t> stamp_out;
+    // the last correspondence pass with this map as the first (dsx_map_align_step, include/dsi_map_align.h): valid until
+    // the map changes
+    DevBuf<unsigned long long> align_key, align_key_out, align_ctr;  // per slot: the correspondence's key; compacted; the moments
+    DevBuf<float> align_dist, align_dist_out;
+    uint32_t align_min_points = 0, align_min_windows = 0;
+    bool align_valid = false;
 };
 
 namespace {
@@ -4116,7 +4123,7 @@ int map_grow_for(dsi_map* mp, size_t n)
 int map_integrate_call(dsi_map* mp, size_t n, const std::function<hipError_t(uint32_t, const dsi::MapTable&)>& launch, size_t* n_accepted,
                        size_t* n_rejected)
 {
-    mp->render_valid = mp->compare_valid = mp->prune_valid = false;  // (the map may change from here on)
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = false;  // (the map may change from here on)
     REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
     REQUIRE(mp->calls < 0xffffffffull, DSI_ERR_INVALID, "at most 2^32 - 1 integrate calls per map");
     REQUIRE((mp->host_ctr[0] + n) * 4 <= ((uint64_t)3 << kMapMaxLog2), DSI_ERR_INVALID,
@@ -4220,7 +4227,7 @@ int dsi_map_destroy(dsi_map_t* mp)
 int dsi_map_reset(dsi_map_t* mp)
 {
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
-    mp->render_valid = mp->compare_valid = mp->prune_valid = false;
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = false;
     if (int rc = set_device(mp->ctx)) return rc;
     HIP_TRY(hipMemsetAsync(mp->block.p, 0, dsi::map_table_bytes(mp->cap_log2), mp->ctx->stream));
     HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof mp->host_ctr, mp->ctx->stream));
@@ -4658,7 +4665,7 @@ int dsx_map_prune(dsi_map_t* mp, const dsx_map_prune_opts_t* opts, dsx_map_prune
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
     REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
     if (int rc = set_device(mp->ctx)) return rc;
-    mp->render_valid = mp->compare_valid = mp->prune_valid = false;
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = false;
     hipStream_t st = mp->ctx->stream;
     unsigned long long ctr[dsi::kMapPruneCounters] = {0, 0, 0, 0, 0, 0};
     if (int rc = map_prune_classify_device(mp, opts, ctr)) return rc;
@@ -4723,7 +4730,7 @@ int map_merge_apply(dsi_map* dst, const MapMergeSource& src, dsx_map_merge_info_
     HIP_TRY(dst->merge_ctr.reserve(dsi::kMapMergeCounters));
     const uint64_t growths_before = dst->growths;
     if (int rc = map_grow_for(dst, (size_t)src.cells)) return rc;                 // (a failed allocation leaves dst as it is)
-    dst->render_valid = dst->compare_valid = dst->prune_valid = false;  // (the map changes from here on)
+    dst->render_valid = dst->compare_valid = dst->prune_valid = dst->align_valid = false;  // (the map changes from here on)
     unsigned long long mctr[dsi::kMapMergeCounters] = {0, 0};
     HIP_TRY(dsi::launch_map_merge(st, src.t, dsi::map_table_at(dst->block.p, dst->cap_log2), (uint32_t)dst->calls, src.accepted,
                                   src.rejected, dst->ctr.p, dst->merge_ctr.p));
@@ -4855,6 +4862,280 @@ int dsx_map_import(dsi_map_t* dst, const dsx_map_state_t* state, const uint64_t*
             (unsigned long long)state->accepted, c[7]);
     const MapMergeSource s{table, m, state->calls, state->accepted, state->rejected};
     return map_merge_apply(dst, s, info);
+}
+
+// ---- aligning maps (include/dsi_map_align.h; DESIGN.md 7j "Aligning") ----
+
+namespace {
+
+int check_finite_pose(const double T[12], const char* name)
+{
+    REQUIRE(T, DSI_ERR_INVALID, "%s is null", name);
+    for (int k = 0; k < 12; ++k) REQUIRE(std::isfinite(T[k]), DSI_ERR_INVALID, "%s[%d] is not finite (%g)", name, k, T[k]);
+    return DSI_OK;
+}
+
+// what a step needs of its arguments, in the order the header gives: opts and T without a map at hand, then the maps
+int check_align_step(const dsi_map* a, const dsi_map* b, const dsx_map_align_opts_t* opts, const double T[12], const char* T_name)
+{
+    REQUIRE(opts, DSI_ERR_INVALID, "opts is null");
+    REQUIRE(std::isfinite(opts->radius) && opts->radius > 0.0, DSI_ERR_INVALID, "radius must be finite and > 0 (got %g)", opts->radius);
+    if (int rc = check_finite_pose(T, T_name)) return rc;
+    REQUIRE(a && b, DSI_ERR_INVALID, "map is null");
+    REQUIRE(a->ctx == b->ctx, DSI_ERR_CONTEXT, "the maps live on different contexts");
+    const double reach_d = std::ceil(opts->radius / b->leaf);
+    REQUIRE(reach_d >= 1.0 && reach_d <= (double)dsi::kMapCompareMaxReach, DSI_ERR_INVALID,
+            "reach = ceil(radius / leaf_b) must be in 1..%d (radius %g, leaf_b %g)", dsi::kMapCompareMaxReach, opts->radius, b->leaf);
+    REQUIRE(a->host_ctr[3] == 0 && b->host_ctr[3] == 0, DSI_ERR_INVALID, "a map's table overflowed in an earlier call: reset the map");
+    return DSI_OK;
+}
+
+int check_align_loop(const dsx_map_align_opts_t* opts)
+{
+    REQUIRE(opts, DSI_ERR_INVALID, "opts is null");
+    REQUIRE(opts->max_iterations >= 1 && opts->max_iterations <= 64, DSI_ERR_INVALID, "max_iterations must be in 1..64 (got %d)",
+            opts->max_iterations);
+    REQUIRE(std::isfinite(opts->eps_rot) && opts->eps_rot >= 0.0, DSI_ERR_INVALID, "eps_rot must be finite and >= 0 (got %g)", opts->eps_rot);
+    REQUIRE(std::isfinite(opts->eps_trans) && opts->eps_trans >= 0.0, DSI_ERR_INVALID, "eps_trans must be finite and >= 0 (got %g)",
+            opts->eps_trans);
+    return DSI_OK;
+}
+
+// one pass on the device (the arguments are checked, the device is set); synchronises for the moment block
+int map_align_step_device(dsi_map* a, dsi_map* b, const dsx_map_align_opts_t* opts, const double T[12], dsx_map_align_moments_t* m)
+{
+    hipStream_t st = a->ctx->stream;
+    a->align_valid = false;
+    HIP_TRY(a->align_key.reserve((size_t)1 << a->cap_log2));
+    HIP_TRY(a->align_dist.reserve((size_t)1 << a->cap_log2));
+    HIP_TRY(a->align_ctr.reserve(dsi::kMapAlignCounters));
+    dsi::MapAlign o;
+    std::memcpy(o.T, T, sizeof o.T);
+    o.leaf_a = a->leaf, o.leaf_b = b->leaf, o.radius = opts->radius, o.quantum = b->leaf * 0x1p-10;
+    o.min_points_a = opts->min_points_a, o.min_windows_a = opts->min_windows_a;
+    o.min_points_b = opts->min_points_b, o.min_windows_b = opts->min_windows_b;
+    o.reach = (int)std::ceil(opts->radius / b->leaf);
+    unsigned long long ctr[dsi::kMapAlignCounters];
+    HIP_TRY(dsi::launch_map_align_step(st, dsi::map_table_at(a->block.p, a->cap_log2), dsi::map_table_at(b->block.p, b->cap_log2), o,
+                                       a->align_key.p, a->align_dist.p, a->align_ctr.p));
+    HIP_TRY(hipMemcpyAsync(ctr, a->align_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    a->align_min_points = opts->min_points_a;
+    a->align_min_windows = opts->min_windows_a;
+    a->align_valid = true;
+    m->n_cells = ctr[0] + ctr[1];
+    m->n_matched = ctr[0];
+    m->n_unmatched = ctr[1];
+    for (int k = 0; k < 3; ++k) m->su[k] = (int64_t)ctr[2 + k], m->sv[k] = (int64_t)ctr[5 + k];
+    for (int k = 0; k < 9; ++k) m->suv_hi[k] = (int64_t)ctr[8 + k], m->suv_lo[k] = ctr[17 + k];
+    m->e2 = ctr[26];
+    m->quantum = o.quantum;
+    m->reach = o.reach;
+    m->reserved = 0;
+    return DSI_OK;
+}
+
+}  // namespace
+
+int dsx_map_align_step(dsi_map_t* a, dsi_map_t* b, const dsx_map_align_opts_t* opts, const double T[12], dsx_map_align_moments_t* moments)
+{
+    if (int rc = check_align_step(a, b, opts, T, "T")) return rc;
+    REQUIRE(moments, DSI_ERR_INVALID, "moments is null");
+    if (int rc = set_device(a->ctx)) return rc;
+    return map_align_step_device(a, b, opts, T, moments);
+}
+
+int dsx_map_align_fetch(dsi_map_t* a, uint64_t* keys_a, uint64_t* keys_b, float* dist, size_t capacity, size_t* n)
+{
+    REQUIRE(a && n, DSI_ERR_INVALID, "null argument");
+    REQUIRE(a->align_valid, DSI_ERR_INVALID,
+            "no alignment step of the map as it stands: call dsx_map_align_step (after the last dsi_map_reset, integrate call, merge or prune)");
+    if (int rc = set_device(a->ctx)) return rc;
+    size_t total = 0;
+    if (int rc = map_count_device(a, a->align_min_points, a->align_min_windows, &total)) return rc;
+    *n = total;
+    REQUIRE(capacity >= total, DSI_ERR_INVALID, "capacity of %zu cells is too small: %zu needed", capacity, total);
+    if (!total) return DSI_OK;
+    hipStream_t st = a->ctx->stream;
+    HIP_TRY(a->key_out.reserve(total));
+    HIP_TRY(a->align_key_out.reserve(total));
+    HIP_TRY(a->align_dist_out.reserve(total));
+    HIP_TRY(dsi::launch_map_align_gather(st, dsi::map_table_at(a->block.p, a->cap_log2), a->align_min_points, a->align_min_windows,
+                                         a->align_key.p, a->align_dist.p, a->blk.p, a->key_out.p, a->align_key_out.p, a->align_dist_out.p));
+    if (keys_a) HIP_TRY(hipMemcpyAsync(keys_a, a->key_out.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (keys_b) HIP_TRY(hipMemcpyAsync(keys_b, a->align_key_out.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (dist) HIP_TRY(hipMemcpyAsync(dist, a->align_dist_out.p, total * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+int dsx_pose_compose(const double A[12], const double B[12], double out[12])
+{
+    REQUIRE(A && B && out, DSI_ERR_INVALID, "null argument");
+    double r[12];
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) r[4 * i + j] = (A[4 * i] * B[j] + A[4 * i + 1] * B[4 + j]) + A[4 * i + 2] * B[8 + j];
+        r[4 * i + 3] = ((A[4 * i] * B[3] + A[4 * i + 1] * B[7]) + A[4 * i + 2] * B[11]) + A[4 * i + 3];
+    }
+    std::memcpy(out, r, sizeof r);
+    return DSI_OK;
+}
+
+int dsx_map_align_solve(const dsx_map_align_moments_t* m, double T_delta[12], dsx_map_align_solve_info_t* info)
+{
+    REQUIRE(m && T_delta, DSI_ERR_INVALID, "null argument");
+    REQUIRE(m->n_matched >= 3, DSI_ERR_INVALID, "n_matched: %llu matched pairs, a rigid motion needs at least 3",
+            (unsigned long long)m->n_matched);
+    REQUIRE(std::isfinite(m->quantum) && m->quantum > 0.0, DSI_ERR_INVALID, "quantum must be finite and > 0 (got %g)", m->quantum);
+    const double nd = (double)m->n_matched;
+    const double scale = (m->quantum * m->quantum) / (nd * nd);
+    double S[9];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            const __int128 sum_p = (__int128)m->suv_hi[3 * r + c] * ((__int128)1 << 32) + (__int128)m->suv_lo[3 * r + c];
+            const __int128 centred = (__int128)m->n_matched * sum_p - (__int128)m->su[r] * (__int128)m->sv[c];
+            S[3 * r + c] = (double)centred * scale;
+        }
+    const double Sxx = S[0], Sxy = S[1], Sxz = S[2], Syx = S[3], Syy = S[4], Syz = S[5], Szx = S[6], Szy = S[7], Szz = S[8];
+    double A[4][4] = {{(Sxx + Syy) + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx},
+                      {Syz - Szy, (Sxx - Syy) - Szz, Sxy + Syx, Szx + Sxz},
+                      {Szx - Sxz, Sxy + Syx, (Syy - Sxx) - Szz, Syz + Szy},
+                      {Sxy - Syx, Szx + Sxz, Syz + Szy, (Szz - Sxx) - Syy}};
+    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
+    for (int sweep = 0; sweep < 16; ++sweep)
+        for (int p = 0; p < 3; ++p)
+            for (int q = p + 1; q < 4; ++q) {
+                if (A[p][q] == 0.0) continue;
+                const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
+                const double t = (theta < 0.0 ? -1.0 : 1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < 4; ++k) {
+                    const double akp = A[k][p], akq = A[k][q];
+                    A[k][p] = c * akp - s * akq;
+                    A[k][q] = s * akp + c * akq;
+                }
+                for (int k = 0; k < 4; ++k) {
+                    const double apk = A[p][k], aqk = A[q][k];
+                    A[p][k] = c * apk - s * aqk;
+                    A[q][k] = s * apk + c * aqk;
+                }
+                for (int k = 0; k < 4; ++k) {
+                    const double vkp = V[k][p], vkq = V[k][q];
+                    V[k][p] = c * vkp - s * vkq;
+                    V[k][q] = s * vkp + c * vkq;
+                }
+            }
+    int i0 = 0;
+    for (int k = 1; k < 4; ++k)
+        if (A[k][k] > A[i0][i0]) i0 = k;
+    int i1 = i0 == 0 ? 1 : 0;
+    for (int k = 0; k < 4; ++k)
+        if (k != i0 && A[k][k] > A[i1][i1]) i1 = k;
+    const double l0 = A[i0][i0], l1 = A[i1][i1];
+    const double size = ((std::fabs(A[0][0]) + std::fabs(A[1][1])) + std::fabs(A[2][2])) + std::fabs(A[3][3]);
+    const double rms = std::sqrt(((double)m->e2 * (m->quantum * m->quantum)) / nd);
+    if (!(l0 - l1 > 0x1p-26 * size)) {
+        if (info) {
+            info->n_matched = m->n_matched;
+            info->rms = rms;
+            info->angle = info->trans = 0.0;
+            info->lambda[0] = l0, info->lambda[1] = l1;
+        }
+        return fail(DSI_ERR_INVALID,
+                    "degenerate: the largest eigenvalue %.17g is not separated from the second %.17g (collinear or coincident pairs)", l0, l1);
+    }
+    double w = V[0][i0], x = V[1][i0], y = V[2][i0], z = V[3][i0];
+    const double norm = std::sqrt(((w * w + x * x) + y * y) + z * z);
+    w = w / norm, x = x / norm, y = y / norm, z = z / norm;
+    if (w < 0.0) w = -w, x = -x, y = -y, z = -z;
+    const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                         2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                         2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
+    double mu[3], mv[3], t[3];
+    for (int r = 0; r < 3; ++r) mu[r] = ((double)m->su[r] / nd) * m->quantum, mv[r] = ((double)m->sv[r] / nd) * m->quantum;
+    for (int r = 0; r < 3; ++r) t[r] = mv[r] - ((R[3 * r] * mu[0] + R[3 * r + 1] * mu[1]) + R[3 * r + 2] * mu[2]);
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) T_delta[4 * r + c] = R[3 * r + c];
+        T_delta[4 * r + 3] = t[r];
+    }
+    if (info) {
+        info->n_matched = m->n_matched;
+        info->rms = rms;
+        info->angle = 2.0 * std::atan2(std::sqrt((x * x + y * y) + z * z), w);
+        info->trans = std::sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
+        info->lambda[0] = l0, info->lambda[1] = l1;
+    }
+    return DSI_OK;
+}
+
+int dsx_map_align(dsi_map_t* a, dsi_map_t* b, const dsx_map_align_opts_t* opts, const double T_init[12], double T_out[12],
+                  dsx_map_align_info_t* info)
+{
+    if (int rc = check_align_loop(opts)) return rc;
+    REQUIRE(T_out, DSI_ERR_INVALID, "T_out is null");
+    if (int rc = check_align_step(a, b, opts, T_init, "T_init")) return rc;
+    if (int rc = set_device(a->ctx)) return rc;
+    double T[12];
+    std::memcpy(T, T_init, sizeof T);
+    dsx_map_align_info_t out{};
+    int rc = DSI_OK;
+    for (int it = 0; it < opts->max_iterations; ++it) {
+        dsx_map_align_moments_t m;
+        if ((rc = map_align_step_device(a, b, opts, T, &m)) != DSI_OK) break;
+        out.iterations = it + 1;
+        out.reach = m.reach;
+        out.n_cells = m.n_cells;
+        if (it == 0) out.n_matched_first = m.n_matched;
+        out.n_matched_last = m.n_matched;
+        if (m.n_matched < opts->min_matched) {
+            out.stopped = 1;
+            rc = fail(DSI_ERR_INVALID, "round %d matched %llu cells, fewer than min_matched = %llu: T_out is the last good pose", it + 1,
+                      (unsigned long long)m.n_matched, (unsigned long long)opts->min_matched);
+            break;
+        }
+        double T_delta[12];
+        dsx_map_align_solve_info_t si;
+        if ((rc = dsx_map_align_solve(&m, T_delta, &si)) != DSI_OK) {
+            out.stopped = 2;
+            break;
+        }
+        if (it == 0) out.rms_first = si.rms;
+        out.rms_last = si.rms;
+        out.angle_last = si.angle, out.trans_last = si.trans;
+        dsx_pose_compose(T_delta, T, T);
+        if (si.angle <= opts->eps_rot && si.trans <= opts->eps_trans) {
+            out.converged = 1;
+            break;
+        }
+    }
+    std::memcpy(T_out, T, sizeof T);
+    if (info) *info = out;
+    return rc;
+}
+
+int dsx_map_integrate_map(dsi_map_t* dst, dsi_map_t* src, const double T[12], uint32_t min_points, uint32_t min_windows,
+                          uint64_t* n_points, uint64_t* n_rejected)
+{
+    REQUIRE(dst, DSI_ERR_INVALID, "dst is null");
+    REQUIRE(src, DSI_ERR_INVALID, "src is null");
+    if (int rc = check_finite_pose(T, "T")) return rc;
+    REQUIRE(dst != src, DSI_ERR_INVALID, "same map: dst and src are one map");
+    REQUIRE(dst->ctx == src->ctx, DSI_ERR_CONTEXT, "contexts: dst and src live on different contexts");
+    REQUIRE(src->host_ctr[3] == 0, DSI_ERR_INVALID, "src's table overflowed in an earlier call");
+    REQUIRE(dst->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
+    if (int rc = set_device(dst->ctx)) return rc;
+    size_t accepted = 0, rejected = 0;
+    if (int rc = map_integrate_call(
+            dst, (size_t)src->host_ctr[0],
+            [&](uint32_t serial, const dsi::MapTable& t) {
+                return dsi::launch_map_integrate_map(dst->ctx->stream, dsi::map_table_at(src->block.p, src->cap_log2), min_points,
+                                                     min_windows, src->leaf, T, dst->leaf, serial, t, dst->ctr.p);
+            },
+            &accepted, &rejected))
+        return rc;
+    if (n_points) *n_points = (uint64_t)accepted + (uint64_t)rejected;
+    if (n_rejected) *n_rejected = rejected;
+    return DSI_OK;
 }
 
 int dsi_mapper_last_vote_info(const dsi_mapper_t* m, dsi_vote_info_t* info)

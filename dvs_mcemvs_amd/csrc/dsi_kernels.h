@@ -436,6 +436,29 @@ hipError_t launch_map_import_build(hipStream_t s, const unsigned long long* keys
 hipError_t launch_map_merge(hipStream_t s, const MapTable& src, const MapTable& dst, uint32_t off, unsigned long long add_accepted,
                             unsigned long long add_rejected, unsigned long long* ctr, unsigned long long* mctr);
 
+// ---- aligning maps (include/dsi_map_align.h; DESIGN.md 7j "Aligning") ----
+constexpr int kMapAlignSums = 25;                     // su[3], sv[3], suv_hi[9], suv_lo[9], e2
+constexpr int kMapAlignCounters = 2 + kMapAlignSums;  // matched, unmatched, then the sums
+struct MapAlign {
+    double T[12];  // a's frame in b's, row-major [R | t]
+    double leaf_a, leaf_b, radius, quantum;  // quantum = leaf_b * 2^-10
+    uint32_t min_points_a, min_windows_a, min_points_b, min_windows_b;
+    int reach;     // 1..kMapCompareMaxReach
+};
+// clears ctr [kMapAlignCounters], then every filtered cell of a, moved by o.T, against b; key_b and dist: one word per slot
+// of a (written for the cells that pass a's filter)
+hipError_t launch_map_align_step(hipStream_t s, const MapTable& a, const MapTable& b, const MapAlign& o, unsigned long long* key_b,
+                                 float* dist, unsigned long long* ctr);
+// after launch_map_count(t, min_points, min_windows): a's key, the correspondence's key and the distance of the filtered
+// cells in slot order (launch_map_extract's)
+hipError_t launch_map_align_gather(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows,
+                                   const unsigned long long* key_b, const float* dist, const uint32_t* blk, unsigned long long* key_a_out,
+                                   unsigned long long* key_b_out, float* dist_out);
+// one integrate call of src's filtered cells (their extracted centroids at leaf_src) under T into dst as call `serial`; ctr
+// and the caller's duty as launch_map_integrate's, with the call's point count bounded by src's cells
+hipError_t launch_map_integrate_map(hipStream_t s, const MapTable& src, uint32_t min_points, uint32_t min_windows, double leaf_src,
+                                    const double T[12], double leaf, uint32_t serial, const MapTable& dst, unsigned long long* ctr);
+
 // focus-based collapses (Grid3D::collapseZSliceBy*, cartesian3dgrid.cpp:192-414; DESIGN.md "Focus-based collapses"):
 // method 0 LocalVar, 1 LocalMeanSquare, 2 GradMag (half_patchsize 0..8), 3 LaplacianMag, 4 DoG.  keys: scratch of
 // focus_chunks(nx, ny, nz) * nx * ny words, fully written before it is read.  planes / depth as launch_collapse_max_z.

@@ -7497,6 +7497,182 @@ __global__ void __launch_bounds__(kPcBlock) k_map_merge(MapTable src, MapTable d
     }
 }
 
+// ---- aligning maps (include/dsi_map_align.h dsx_map_align*; DESIGN.md 7j "Aligning") ----
+// One correspondence pass.  Every cell of `a` that passes a's filter: p = its extracted centroid (float, widened);
+// p' = T p by rule 1; c = floor(p' / leaf_b) per axis; the candidates are b's filtered cells at c + o, |o| <= reach per
+// axis, an index with |c + o| > kPcCellMax skipped (a non-finite p' has no candidates); q = the candidate's extracted
+// centroid; d2 = ((dx dx) + dy dy) + dz dz; the least (d2, key) wins -- a total order, so neither the
+// order of the offsets nor the probing matters; MATCHED iff sqrt(d2) <= radius.  key_b[slot] = the winner's key or 0,
+// dist[slot] = (float) sqrt(d2) or +inf.  A matched pair is quantised, U = llrint(p' / quantum), V = llrint(q / quantum)
+// (|U|, |V| < 2^31: dsi_map_align.h), and adds to 25 64-bit sums: su[3], sv[3], the high and low words of the nine
+// products U[r] V[c], and e2.  A thread keeps the 25 sums in registers over its strides (two's-complement adds: the signed
+// sums are kept as unsigned words); at the end a wave adds them across its lanes by shuffles, its first lane adds the
+// wave's totals to LDS, and the workgroup issues one global atomic per non-zero sum.  ctr: [0] matched, [1] unmatched,
+// [2 + k] sum k.  Reads the tables, writes key_b, dist and ctr: a == b is legal.
+__global__ void __launch_bounds__(kPcBlock, 4) k_map_align_step(MapTable a, MapTable b, MapAlign o, unsigned long long* __restrict__ key_b,
+                                                             float* __restrict__ dist, unsigned long long* __restrict__ ctr)
+{
+    __shared__ unsigned long long s_acc[kMapAlignSums];
+    __shared__ uint32_t s_cnt[2];
+    __shared__ double s_T[12];  // (the pose is read once per cell: in LDS it holds no scalar registers over the lookups)
+    if (threadIdx.x < kMapAlignSums) s_acc[threadIdx.x] = 0ull;
+    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
+    if (threadIdx.x >= 64 && threadIdx.x < 64 + 12) s_T[threadIdx.x - 64] = o.T[threadIdx.x - 64];
+    __syncthreads();
+    uint32_t c_match = 0, c_un = 0;  // (the same in every lane of a wave)
+    unsigned long long acc[kMapAlignSums];
+#pragma unroll
+    for (int k = 0; k < kMapAlignSums; ++k) acc[k] = 0ull;
+    const uint32_t bmask = (1u << b.cap_log2) - 1u;
+    const uint32_t cap = 1u << a.cap_log2, stride = gridDim.x * kPcBlock;  // (at most 2^27 slots: 32 bits hold base + stride)
+    for (uint32_t base = blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const uint32_t i = base + threadIdx.x;
+        const bool f = map_passes(a, i, o.min_points_a, o.min_windows_a);
+        bool matched = false;
+        if (f) {
+            const unsigned long long k = a.keys[i];
+            const uint32_t n = a.n[i];
+            const double x = (double)map_centroid(a, i, k, n, 0, o.leaf_a), y = (double)map_centroid(a, i, k, n, 1, o.leaf_a),
+                         z = (double)map_centroid(a, i, k, n, 2, o.leaf_a);
+            // c as integers: a cell index beyond kPcCellMax + reach (a non-finite one included) has no candidate on its
+            // axis, and within that range c + o is the same number in int as in double
+            double p[3];
+            int c[3];
+            bool any = true;
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                p[ax] = ((s_T[4 * ax] * x + s_T[4 * ax + 1] * y) + s_T[4 * ax + 2] * z) + s_T[4 * ax + 3];
+                const double cf = floor(p[ax] / o.leaf_b);
+                any = any && fabs(cf) <= (double)(kPcCellMax + kMapCompareMaxReach);  // (NaN and the infinities fail)
+                c[ax] = any ? (int)cf : 0;
+            }
+            double best = INFINITY;
+            unsigned long long best_key = 0ull;
+            uint32_t best_j = 0u;
+            const int reach = any ? o.reach : -1;  // (-1: the sweep is empty)
+            for (int oz = -reach; oz <= reach; ++oz) {
+                const int vz = c[2] + oz;
+                if (abs(vz) > kPcCellMax) continue;
+                for (int oy = -reach; oy <= reach; ++oy) {
+                    const int vy = c[1] + oy;
+                    if (abs(vy) > kPcCellMax) continue;
+                    for (int ox = -reach; ox <= reach; ++ox) {
+                        const int vx = c[0] + ox;
+                        if (abs(vx) > kPcCellMax) continue;
+                        const unsigned long long kb = pc_key(vx, vy, vz);
+                        const uint32_t j = map_find(b.keys, bmask, kb);
+                        if (j == ~0u || !map_passes(b, j, o.min_points_b, o.min_windows_b)) continue;
+                        const uint32_t nb = b.n[j];
+                        const double dx = p[0] - (double)map_centroid(b, j, kb, nb, 0, o.leaf_b);
+                        const double dy = p[1] - (double)map_centroid(b, j, kb, nb, 1, o.leaf_b);
+                        const double dz = p[2] - (double)map_centroid(b, j, kb, nb, 2, o.leaf_b);
+                        const double d2 = ((dx * dx) + dy * dy) + dz * dz;
+                        if (d2 < best || (d2 == best && kb < best_key)) best = d2, best_key = kb, best_j = j;
+                    }
+                }
+            }
+            const double d = sqrt(best);
+            matched = best_key != 0ull && d <= o.radius;
+            dist[i] = matched ? (float)d : INFINITY;
+            key_b[i] = matched ? best_key : 0ull;
+            if (matched) {
+                const uint32_t nb = b.n[best_j];  // (the winner's centroid again: three loads per matched cell, no registers held)
+                long long U[3], V[3];
+#pragma unroll
+                for (int ax = 0; ax < 3; ++ax) {
+                    U[ax] = llrint(p[ax] / o.quantum);
+                    V[ax] = llrint((double)map_centroid(b, best_j, best_key, nb, ax, o.leaf_b) / o.quantum);
+                    acc[ax] += (unsigned long long)U[ax];
+                    acc[3 + ax] += (unsigned long long)V[ax];
+                    const long long e = U[ax] - V[ax];
+                    acc[24] += (unsigned long long)(e * e);
+                }
+#pragma unroll
+                for (int r = 0; r < 3; ++r)
+#pragma unroll
+                    for (int cc = 0; cc < 3; ++cc) {
+                        const long long P = U[r] * V[cc];
+                        acc[6 + 3 * r + cc] += (unsigned long long)(P >> 32);
+                        acc[15 + 3 * r + cc] += (unsigned long long)P & 0xffffffffull;
+                    }
+            }
+        }
+        c_match += (uint32_t)__popcll(__ballot(matched));
+        c_un += (uint32_t)__popcll(__ballot(f && !matched));
+    }
+#pragma unroll
+    for (int k = 0; k < kMapAlignSums; ++k) {
+        unsigned long long v = acc[k];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&s_acc[k], v);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (c_match) atomicAdd(&s_cnt[0], c_match);
+        if (c_un) atomicAdd(&s_cnt[1], c_un);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    if (threadIdx.x >= 64 && threadIdx.x < 64 + kMapAlignSums && s_acc[threadIdx.x - 64])
+        atomicAdd(&ctr[2 + threadIdx.x - 64], s_acc[threadIdx.x - 64]);
+}
+
+// the step's correspondences compacted like k_map_extract's cells (same filter, same blk_off): a's key, the winner's key
+// and the distance in slot order
+__global__ void __launch_bounds__(kPcBlock) k_map_align_gather(MapTable t, uint32_t min_points, uint32_t min_windows,
+                                                               const unsigned long long* __restrict__ key_b, const float* __restrict__ dist,
+                                                               const uint32_t* __restrict__ blk_off, unsigned long long* __restrict__ key_a_out,
+                                                               unsigned long long* __restrict__ key_b_out, float* __restrict__ dist_out)
+{
+    const size_t i = (size_t)blockIdx.x * kPcBlock + threadIdx.x;
+    const bool f = map_passes(t, i, min_points, min_windows);
+    uint32_t total;
+    const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);
+    if (!f) return;
+    const size_t o = (size_t)blk_off[blockIdx.x] + rank;
+    key_a_out[o] = t.keys[i];
+    key_b_out[o] = key_b[i];
+    dist_out[o] = dist[i];
+}
+
+// One map into another as one integrate call: every cell of src that passes the filter is its extracted centroid (float,
+// widened), which goes through map_integrate_point under T into dst -- dsi_map_integrate of dsi_map_extract's list, bit for
+// bit.  src is only read and dst != src.  Walks src's slots in strides; ctr as k_map_integrate_depth's, one global atomic
+// per workgroup and counter.
+__global__ void __launch_bounds__(kPcBlock) k_map_integrate_map(MapTable src, uint32_t min_points, uint32_t min_windows, double leaf_src,
+                                                                MapPose T, double leaf, uint32_t serial, MapTable dst,
+                                                                unsigned long long* __restrict__ ctr)
+{
+    __shared__ uint32_t s_cnt[4];
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    uint32_t c_new = 0, c_ok = 0, c_rej = 0, c_full = 0;  // (the same in every lane of a wave)
+    const size_t cap = (size_t)1 << src.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        const bool in = map_passes(src, i, min_points, min_windows);
+        bool ok = false, fresh = false, full = false;
+        if (in) {
+            const unsigned long long k = src.keys[i];
+            const uint32_t n = src.n[i];
+            map_integrate_point((double)map_centroid(src, i, k, n, 0, leaf_src), (double)map_centroid(src, i, k, n, 1, leaf_src),
+                                (double)map_centroid(src, i, k, n, 2, leaf_src), T, leaf, serial, dst, &ok, &fresh, &full);
+        }
+        c_new += (uint32_t)__popcll(__ballot(fresh));
+        c_ok += (uint32_t)__popcll(__ballot(ok));
+        c_rej += (uint32_t)__popcll(__ballot(in && !ok && !full));
+        c_full += (uint32_t)__popcll(__ballot(full));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (c_new) atomicAdd(&s_cnt[0], c_new);
+        if (c_ok) atomicAdd(&s_cnt[1], c_ok);
+        if (c_rej) atomicAdd(&s_cnt[2], c_rej);
+        if (c_full) atomicAdd(&s_cnt[3], c_full);
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
 }  // namespace
 
 size_t map_table_bytes(uint32_t cap_log2) { return ((size_t)1 << cap_log2) * (4 * sizeof(unsigned long long) + 3 * sizeof(uint32_t)); }
@@ -7640,6 +7816,36 @@ hipError_t launch_map_merge(hipStream_t s, const MapTable& src, const MapTable& 
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_map_merge, dim3(std::min(pc_blocks((size_t)1 << src.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s, src,
                        dst, off, add_accepted, add_rejected, ctr, mctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_align_step(hipStream_t s, const MapTable& a, const MapTable& b, const MapAlign& o, unsigned long long* key_b,
+                                 float* dist, unsigned long long* ctr)
+{
+    hipError_t e = hipMemsetAsync(ctr, 0, kMapAlignCounters * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_map_align_step, dim3(std::min(pc_blocks((size_t)1 << a.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s, a,
+                       b, o, key_b, dist, ctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_align_gather(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows,
+                                   const unsigned long long* key_b, const float* dist, const uint32_t* blk, unsigned long long* key_a_out,
+                                   unsigned long long* key_b_out, float* dist_out)
+{
+    const uint32_t nb = pc_blocks((size_t)1 << t.cap_log2);
+    hipLaunchKernelGGL(k_map_align_gather, dim3(nb), dim3(kPcBlock), 0, s, t, min_points, min_windows, key_b, dist, blk, key_a_out,
+                       key_b_out, dist_out);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_integrate_map(hipStream_t s, const MapTable& src, uint32_t min_points, uint32_t min_windows, double leaf_src,
+                                    const double T_in[12], double leaf, uint32_t serial, const MapTable& dst, unsigned long long* ctr)
+{
+    MapPose T;
+    for (int k = 0; k < 12; ++k) T.m[k] = T_in[k];
+    hipLaunchKernelGGL(k_map_integrate_map, dim3(std::min(pc_blocks((size_t)1 << src.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0,
+                       s, src, min_points, min_windows, leaf_src, T, leaf, serial, dst, ctr);
     return hipExtGetLastError();
 }
 

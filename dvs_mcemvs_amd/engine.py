@@ -110,6 +110,29 @@ class _MapMergeInfo(C.Structure):
                 ("growths", C.c_uint64)]
 
 
+class _MapAlignOpts(C.Structure):
+    _fields_ = [("min_points_a", C.c_uint32), ("min_windows_a", C.c_uint32), ("min_points_b", C.c_uint32),
+                ("min_windows_b", C.c_uint32), ("radius", C.c_double), ("max_iterations", C.c_int32), ("reserved", C.c_int32),
+                ("min_matched", C.c_uint64), ("eps_rot", C.c_double), ("eps_trans", C.c_double)]
+
+
+class _MapAlignMoments(C.Structure):
+    _fields_ = [("n_cells", C.c_uint64), ("n_matched", C.c_uint64), ("n_unmatched", C.c_uint64), ("su", C.c_int64 * 3),
+                ("sv", C.c_int64 * 3), ("suv_hi", C.c_int64 * 9), ("suv_lo", C.c_uint64 * 9), ("e2", C.c_uint64),
+                ("quantum", C.c_double), ("reach", C.c_int32), ("reserved", C.c_int32)]
+
+
+class _MapAlignSolveInfo(C.Structure):
+    _fields_ = [("n_matched", C.c_uint64), ("rms", C.c_double), ("angle", C.c_double), ("trans", C.c_double),
+                ("lambda_", C.c_double * 2)]
+
+
+class _MapAlignInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("stopped", C.c_int32), ("reach", C.c_int32),
+                ("n_cells", C.c_uint64), ("n_matched_first", C.c_uint64), ("n_matched_last", C.c_uint64),
+                ("rms_first", C.c_double), ("rms_last", C.c_double), ("angle_last", C.c_double), ("trans_last", C.c_double)]
+
+
 class _ScatterPlan(C.Structure):
     _fields_ = [("q", C.c_int), ("own_begin", C.c_int), ("own_count", C.c_int), ("tail_begin", C.c_int),
                 ("tail_count", C.c_int)]
@@ -374,6 +397,13 @@ def load_library():
         "dsx_map_export": (C.c_int, [vp, C.POINTER(_MapState), u64p, u32p, u64p, u32p, u32p, C.c_size_t, szp]),
         "dsx_map_import": (C.c_int, [vp, C.POINTER(_MapState), u64p, u32p, u64p, u32p, u32p, C.POINTER(_MapMergeInfo)]),
         "dsx_map_merge": (C.c_int, [vp, vp, C.POINTER(_MapMergeInfo)]),
+        # include/dsi_map_align.h: aligning maps
+        "dsx_map_align_step": (C.c_int, [vp, vp, C.POINTER(_MapAlignOpts), f64p, C.POINTER(_MapAlignMoments)]),
+        "dsx_map_align_fetch": (C.c_int, [vp, u64p, u64p, f32p, C.c_size_t, szp]),
+        "dsx_pose_compose": (C.c_int, [f64p, f64p, f64p]),
+        "dsx_map_align_solve": (C.c_int, [C.POINTER(_MapAlignMoments), f64p, C.POINTER(_MapAlignSolveInfo)]),
+        "dsx_map_align": (C.c_int, [vp, vp, C.POINTER(_MapAlignOpts), f64p, f64p, C.POINTER(_MapAlignInfo)]),
+        "dsx_map_integrate_map": (C.c_int, [vp, vp, f64p, C.c_uint32, C.c_uint32, u64p, u64p]),
     }
     if experiments_requested():     # hooks that exist only in the experiments flavour
         sig.update({
@@ -1340,6 +1370,86 @@ class WorldMap:
         _check(load_library().dsx_map_merge(self._h, other._h, C.byref(i)))
         return self._merge_info(i)
 
+    @staticmethod
+    def _align_opts(radius, min_points, min_windows, min_points_other, min_windows_other, max_iterations=1, min_matched=0,
+                    eps_rot=0.0, eps_trans=0.0):
+        return _MapAlignOpts(int(min_points), int(min_windows), int(min_points_other), int(min_windows_other), float(radius),
+                             int(max_iterations), 0, int(min_matched), float(eps_rot), float(eps_trans))
+
+    def alignStep(self, other, radius, T=None, min_points=1, min_windows=1, min_points_other=1, min_windows_other=1,
+                  correspondences=False):
+        """One correspondence pass of ICP (dsx_map_align_step; the arithmetic is stated in dsi_map_align.h and DESIGN.md 7j
+        "Aligning"): every filtered cell of this map, moved by T (this map's frame in other's, as pose_matrix takes it; None:
+        the identity), is paired with the nearest filtered centroid of `other` within `radius`, ties to the smaller key.
+        Returns the exact integer moments of the matched pairs as Python ints -- n_cells = n_matched + n_unmatched, su, sv
+        (3), suv_hi, suv_lo (9, row-major: sum U[r] V[c] = suv_hi * 2**32 + suv_lo), e2 -- with quantum and reach: what
+        solve_alignment takes.  correspondences=True adds fetchAlignment()'s arrays."""
+        o = self._align_opts(radius, min_points, min_windows, min_points_other, min_windows_other)
+        T = pose_matrix(np.eye(4)[:3] if T is None else T)
+        m = _MapAlignMoments()
+        _check(load_library().dsx_map_align_step(self._h, other._h, C.byref(o), _ptr(T, C.c_double), C.byref(m)))
+        out = _moments_dict(m)
+        if correspondences:
+            out.update(self.fetchAlignment())
+        return out
+
+    def fetchAlignment(self, sort=True):
+        """keys (uint64, this map's), keys_other (uint64, the correspondence's key in the other map; 0 where unmatched) and
+        dist (float32, inf where unmatched) of the last alignStep() or align() of this map (dsx_map_align_fetch); raises
+        DsiError when the map changed since, or was never aligned.  sort=True orders them by ascending key."""
+        L = load_library()
+        n = C.c_size_t()
+        rc = L.dsx_map_align_fetch(self._h, None, None, None, 0, C.byref(n))
+        if rc != OK and n.value == 0:
+            _check(rc)
+        m = n.value
+        out = {"keys": np.empty(m, np.uint64), "keys_other": np.empty(m, np.uint64), "dist": np.empty(m, np.float32)}
+        _check(L.dsx_map_align_fetch(self._h, _ptr(out["keys"], C.c_uint64), _ptr(out["keys_other"], C.c_uint64),
+                                     _ptr(out["dist"], C.c_float), m, C.byref(n)))
+        if sort:
+            order = np.argsort(out["keys"], kind="stable")
+            out = {k: v[order] for k, v in out.items()}
+        return out
+
+    def align(self, other, radius, T_init=None, max_iterations=20, min_matched=3, eps_rot=1e-6, eps_trans=None, min_points=1,
+              min_windows=1, min_points_other=1, min_windows_other=1):
+        """ICP of this map onto `other` (dsx_map_align): up to max_iterations rounds of alignStep, solve_alignment and
+        T <- compose_pose(T_delta, T), from T_init (None: the identity), until a round's T_delta turns by at most eps_rot
+        radians and moves by at most eps_trans (None: 1e-4 of other's leaf).  Returns (T, info): T the 12 doubles of this
+        map's frame in other's, info a dict of iterations, converged, stopped, reach, n_cells, n_matched_first / _last,
+        rms_first / _last, angle_last and trans_last.  A round that matches fewer than min_matched cells, or whose pairs do
+        not determine a rotation, raises DsiError; the exception's `T` and `info` hold the last good pose."""
+        if eps_trans is None:
+            eps_trans = 1e-4 * other.info()["leaf"]
+        o = self._align_opts(radius, min_points, min_windows, min_points_other, min_windows_other, max_iterations, min_matched,
+                             eps_rot, eps_trans)
+        T0 = pose_matrix(np.eye(4)[:3] if T_init is None else T_init)
+        T = np.empty(12, np.float64)
+        i = _MapAlignInfo()
+        rc = load_library().dsx_map_align(self._h, other._h, C.byref(o), _ptr(T0, C.c_double), _ptr(T, C.c_double), C.byref(i))
+        info = {k: int(getattr(i, k)) for k in ("iterations", "converged", "stopped", "reach", "n_cells", "n_matched_first",
+                                                 "n_matched_last")}
+        info.update({k: float(getattr(i, k)) for k in ("rms_first", "rms_last", "angle_last", "trans_last")})
+        if rc != OK:
+            try:
+                _check(rc)
+            except DsiError as e:
+                if i.stopped:
+                    e.T, e.info = T, info
+                raise
+        return T, info
+
+    def integrateMap(self, other, T=None, min_points=1, min_windows=1):
+        """One integrate call of `other`'s cells that pass min_points / min_windows, each as its float32 centroid, under
+        the pose T (other's frame in this map's; None: the identity), on the device (dsx_map_integrate_map): bit for bit
+        integrate(other.extract(min_points, min_windows)["xyz"], T).  The leaves may differ; other must be another map on
+        the same context.  Returns (cells integrated, of those rejected)."""
+        T = pose_matrix(np.eye(4)[:3] if T is None else T)
+        n, rej = C.c_uint64(), C.c_uint64()
+        _check(load_library().dsx_map_integrate_map(self._h, other._h, _ptr(T, C.c_double), int(min_points), int(min_windows),
+                                                    C.byref(n), C.byref(rej)))
+        return n.value, rej.value
+
     def reset(self):
         _check(load_library().dsi_map_reset(self._h))
 
@@ -1360,6 +1470,51 @@ def _pinhole(K):
     if K.size != 4:
         raise ValueError("K is (fx, fy, cx, cy) or a 3 x 3 matrix")
     return tuple(float(v) for v in K.reshape(4))
+
+
+MOMENT_COUNTS = ("n_cells", "n_matched", "n_unmatched", "e2", "reach")
+MOMENT_SUMS = ("su", "sv", "suv_hi", "suv_lo")
+
+
+def _moments_dict(m):
+    out = {k: int(getattr(m, k)) for k in MOMENT_COUNTS}
+    out.update({k: [int(v) for v in getattr(m, k)] for k in MOMENT_SUMS})
+    out["quantum"] = float(m.quantum)
+    return out
+
+
+def _moments_struct(moments):
+    m = _MapAlignMoments()
+    for k in ("n_cells", "n_matched", "n_unmatched", "e2"):
+        setattr(m, k, int(moments[k]))
+    for k in MOMENT_SUMS:
+        getattr(m, k)[:] = [int(v) for v in moments[k]]
+    m.quantum = float(moments["quantum"])
+    m.reach = int(moments.get("reach", 0))
+    return m
+
+
+def compose_pose(A, B):
+    """A o B of two rigid poses as pose_matrix takes them (dsx_pose_compose, the routine dsi::compose_pose calls too):
+    R = A_R B_R, t = A_R B_t + A_t, 12 doubles, every dot product ((a0 b0 + a1 b1) + a2 b2) in double without FMA."""
+    A, B = pose_matrix(A), pose_matrix(B)
+    out = np.empty(12, np.float64)
+    _check(load_library().dsx_pose_compose(_ptr(A, C.c_double), _ptr(B, C.c_double), _ptr(out, C.c_double)))
+    return out
+
+
+def solve_alignment(moments):
+    """The rigid motion that carries the matched cells onto their correspondences in the least-squares sense, from
+    WorldMap.alignStep's moments alone (dsx_map_align_solve: Horn's quaternion form, a 4 x 4 Jacobi eigen-solve; stated
+    in dsi_map_align.h; no device is touched).  Returns (T_delta, info): 12 doubles and a dict of n_matched, rms (of the
+    pairs as matched), angle (radians) and trans of T_delta and the two largest eigenvalues `lambda`.  Raises DsiError
+    for fewer than 3 pairs and for pairs that do not determine a rotation (collinear or coincident)."""
+    m = _moments_struct(moments)
+    T = np.empty(12, np.float64)
+    i = _MapAlignSolveInfo()
+    _check(load_library().dsx_map_align_solve(C.byref(m), _ptr(T, C.c_double), C.byref(i)))
+    return T, {"n_matched": int(i.n_matched), "rms": float(i.rms), "angle": float(i.angle), "trans": float(i.trans),
+               "lambda": [float(v) for v in i.lambda_]}
 
 
 def map_f_score(est, gt, radius, n_bins=16, min_points=1, min_windows=1, min_points_gt=1, min_windows_gt=1):

@@ -935,11 +935,44 @@ def ground_truth_map(ctx, frames, camera, leaf, min_depth, max_depth, capacity_l
     return gt_map
 
 
-def score_world_map_3d(world_map, gt_map, radius, n_bins=16, min_points=1, min_windows=1, min_points_gt=1, min_windows_gt=1):
+def align_world_maps(src, dst, radius, T_init=None, max_iterations=20, min_matched=3, eps_rot=1e-6, eps_trans=None, min_points=1,
+                     min_windows=1, min_points_dst=1, min_windows_dst=1):
+    """The rigid motion that carries the map `src` onto the map `dst` (engine.WorldMap.align: ICP whose correspondence
+    passes run on the device and hand back exact integer moments; the arithmetic is stated in dsi_map_align.h and
+    DESIGN.md 7j "Aligning").  radius: how far a cell of src looks for its partner in dst, at most 3 of dst's leaves; T_init:
+    a first guess of src's frame in dst's, within that radius of the truth (None: the identity).  Returns (T, info): T the
+    12 doubles of src's frame in dst's -- dst.integrateMap(src, T) puts src into dst's frame -- and info the loop's dict."""
+    return src.align(dst, radius, T_init, max_iterations, min_matched, eps_rot, eps_trans, min_points, min_windows, min_points_dst,
+                     min_windows_dst)
+
+
+def score_world_map_3d(world_map, gt_map, radius, n_bins=16, min_points=1, min_windows=1, min_points_gt=1, min_windows_gt=1,
+                       align=None):
     """3-D accuracy, completeness and F-score of a finished full_sequence(..., world_map=) run against a ground-truth map
     (ground_truth_map): engine.map_f_score of the two maps -- thresholds, precision, recall and f1 per threshold, and the
-    two directions' counts (`est`: the map's cells against the ground truth, `gt`: the reverse) with their mean distances."""
-    return E.map_f_score(world_map, gt_map, radius, n_bins, min_points, min_windows, min_points_gt, min_windows_gt)
+    two directions' counts (`est`: the map's cells against the ground truth, `gt`: the reverse) with their mean distances.
+    align: None scores the maps as they stand; a dict of align_world_maps' options (`radius` defaults to this call's)
+    first registers the estimate to the ground truth, as multi-view-stereo benchmarks do -- the estimate's filtered cells
+    are re-integrated at the pose found into a scratch map of the estimate's leaf (WorldMap.integrateMap) and that map is
+    scored with the filter (1, 1); the result gains "T" (the estimate's frame in the ground truth's) and "align" (the
+    loop's info).  world_map itself is not changed."""
+    if align is None:
+        return E.map_f_score(world_map, gt_map, radius, n_bins, min_points, min_windows, min_points_gt, min_windows_gt)
+    opts = dict(align)
+    opts.setdefault("radius", radius)
+    opts.setdefault("min_points", min_points)
+    opts.setdefault("min_windows", min_windows)
+    opts.setdefault("min_points_dst", min_points_gt)
+    opts.setdefault("min_windows_dst", min_windows_gt)
+    T, info = align_world_maps(world_map, gt_map, **opts)
+    scratch = E.WorldMap(world_map.ctx, world_map.info()["leaf"])
+    try:
+        scratch.integrateMap(world_map, T, min_points, min_windows)
+        out = E.map_f_score(scratch, gt_map, radius, n_bins, 1, 1, min_points_gt, min_windows_gt)
+    finally:
+        scratch.close()
+    out["T"], out["align"] = T, info
+    return out
 
 
 def merge_world_maps(dst, maps):

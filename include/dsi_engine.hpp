@@ -36,6 +36,7 @@
 #include "dsi_map_eval.h"
 #include "dsi_map_prune.h"
 #include "dsi_map_merge.h"
+#include "dsi_map_align.h"
 
 namespace dsi {
 
@@ -1582,6 +1583,14 @@ inline std::array<double, 12> invert_pose(const std::array<double, 12>& T)
     return out;
 }
 inline std::array<double, 12> invert_pose(const Transformation& T) { return invert_pose(pose_matrix(T)); }
+// A o B (dsx_pose_compose, the routine the Python binding calls too): R = A_R B_R, t = A_R B_t + A_t, every dot product
+// ((a0 b0 + a1 b1) + a2 b2) in double without FMA
+inline std::array<double, 12> compose_pose(const std::array<double, 12>& A, const std::array<double, 12>& B)
+{
+    std::array<double, 12> out;
+    check(dsx_pose_compose(A.data(), B.data(), out.data()));
+    return out;
+}
 
 // A persistent world-frame map on the device (dsi_map_*): every integrate call moves one window's cloud from
 // its reference view to the world frame and merges it into cubic cells of edge `leaf` -- a centroid per cell (PCL's
@@ -1648,6 +1657,32 @@ struct MapState {  // by ascending key when sorted
     size_t size() const { return keys.size(); }
 };
 using MapMergeInfo = dsx_map_merge_info_t;
+// aligning (dsi_map_align.h): the options -- the defaults make one pass with the filters open --, the exact integer moments
+// of a correspondence pass, and what the ICP loop reports
+struct MapAlignOptions : dsx_map_align_opts_t {
+    explicit MapAlignOptions(double radius_) : dsx_map_align_opts_t{}
+    {
+        min_points_a = min_windows_a = min_points_b = min_windows_b = 1;
+        radius = radius_;
+        max_iterations = 1;
+    }
+};
+using MapAlignMoments = dsx_map_align_moments_t;
+using MapAlignSolveInfo = dsx_map_align_solve_info_t;
+struct MapAlignResult {
+    std::array<double, 12> T{};  // the frame of the aligned map in the other's; the last good pose when !ok
+    dsx_map_align_info_t info{};
+    bool ok = false;             // false: a round matched fewer than min_matched cells or its pairs were degenerate
+};
+constexpr std::array<double, 12> kIdentityPose = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+// the rigid motion of a pass's moments (dsx_map_align_solve; no device is touched); throws for fewer than 3 pairs and for
+// pairs that do not determine a rotation
+inline std::array<double, 12> solve_alignment(const MapAlignMoments& moments, MapAlignSolveInfo* info = nullptr)
+{
+    std::array<double, 12> T;
+    check(dsx_map_align_solve(&moments, T.data(), info));
+    return T;
+}
 class WorldMap {
 public:
     WorldMap(Context& ctx, double leaf, int capacity_log2 = 16) : ctx_(ctx) { check(dsi_map_create(ctx.handle(), leaf, capacity_log2, &h_)); }
@@ -1888,6 +1923,35 @@ public:
         MapMergeInfo info;
         check(dsx_map_import(h_, &st, state.keys.data(), state.n.data(), state.S.data(), state.windows.data(), state.stamp.data(), &info));
         return info;
+    }
+
+    // one correspondence pass of ICP (dsx_map_align_step; the arithmetic is stated in dsi_map_align.h): every filtered
+    // cell of this map, moved by T (this map's frame in other's), against the nearest filtered centroid of `other` within
+    // opts.radius; the exact integer moments of the matched pairs come back, the pairs stay on the device
+    MapAlignMoments align_step(const WorldMap& other, const MapAlignOptions& opts, const std::array<double, 12>& T = kIdentityPose)
+    {
+        MapAlignMoments m;
+        check(dsx_map_align_step(h_, other.h_, &opts, T.data(), &m));
+        return m;
+    }
+    // ICP of this map onto `other` from T_init (dsx_map_align).  A round with too few matched cells or degenerate pairs
+    // does not throw: the result then has ok == false, the last good pose and info.stopped; every other error throws
+    MapAlignResult align(const WorldMap& other, const MapAlignOptions& opts, const std::array<double, 12>& T_init = kIdentityPose)
+    {
+        MapAlignResult r;
+        const int rc = dsx_map_align(h_, other.h_, &opts, T_init.data(), r.T.data(), &r.info);
+        if (rc != DSI_OK && !(rc == DSI_ERR_INVALID && r.info.stopped != 0)) check(rc);
+        r.ok = rc == DSI_OK;
+        return r;
+    }
+    // one integrate call of other's filtered cells, each as its float32 centroid, under T (other's frame in this map's) on
+    // the device (dsx_map_integrate_map): bit for bit integrate() of other.extract()'s xyz.  Returns the cells integrated
+    uint64_t integrate_map(const WorldMap& other, const std::array<double, 12>& T = kIdentityPose, uint32_t min_points = 1,
+                           uint32_t min_windows = 1, uint64_t* n_rejected = nullptr)
+    {
+        uint64_t n = 0;
+        check(dsx_map_integrate_map(h_, other.h_, T.data(), min_points, min_windows, &n, n_rejected));
+        return n;
     }
 
 private:
