@@ -9,6 +9,7 @@
 // frees them (in reverse order of declaration), a dsi_*_destroy only checks, synchronises and counts before it.
 #include "../../include/dsi_engine.h"
 #include "../../include/dsi_map_eval.h"
+#include "../../include/dsi_map_components.h"
 #include "../../include/dsi_map_prune.h"
 #include "../../include/dsi_map_merge.h"
 #include "../../include/dsi_map_align.h"
@@ -4080,6 +4081,14 @@ struct dsi_map {
     DevBuf<float> align_dist, align_dist_out;
     uint32_t align_min_points = 0, align_min_windows = 0;
     bool align_valid = false;
+    // the last labelling (dsx_map_components, include/dsi_map_components.h): valid until the map changes; the selection
+    // (dsx_map_components_select) is valid as long as the labelling it was made on
+    DevBuf<uint32_t> comp_parent, comp_cells;           // per slot: the root's slot; at a root, its component's cells
+    DevBuf<unsigned long long> comp_label, comp_points; // at a root: the component's label and points
+    DevBuf<uint8_t> comp_reason, comp_reason_out;       // per slot: the selection's reason; compacted for a fetch
+    DevBuf<unsigned long long> comp_ctr, comp_top, comp_label_out, comp_cells_out, comp_points_out;
+    uint32_t comp_min_points = 0, comp_min_windows = 0;
+    bool comp_valid = false, comp_select_valid = false;
 };
 
 namespace {
@@ -4123,7 +4132,7 @@ int map_grow_for(dsi_map* mp, size_t n)
 int map_integrate_call(dsi_map* mp, size_t n, const std::function<hipError_t(uint32_t, const dsi::MapTable&)>& launch, size_t* n_accepted,
                        size_t* n_rejected)
 {
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = false;  // (the map may change from here on)
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = false;  // (the map may change from here on)
     REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
     REQUIRE(mp->calls < 0xffffffffull, DSI_ERR_INVALID, "at most 2^32 - 1 integrate calls per map");
     REQUIRE((mp->host_ctr[0] + n) * 4 <= ((uint64_t)3 << kMapMaxLog2), DSI_ERR_INVALID,
@@ -4227,7 +4236,7 @@ int dsi_map_destroy(dsi_map_t* mp)
 int dsi_map_reset(dsi_map_t* mp)
 {
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = false;
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = false;
     if (int rc = set_device(mp->ctx)) return rc;
     HIP_TRY(hipMemsetAsync(mp->block.p, 0, dsi::map_table_bytes(mp->cap_log2), mp->ctx->stream));
     HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof mp->host_ctr, mp->ctx->stream));
@@ -4665,7 +4674,7 @@ int dsx_map_prune(dsi_map_t* mp, const dsx_map_prune_opts_t* opts, dsx_map_prune
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
     REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
     if (int rc = set_device(mp->ctx)) return rc;
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = false;
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = false;
     hipStream_t st = mp->ctx->stream;
     unsigned long long ctr[dsi::kMapPruneCounters] = {0, 0, 0, 0, 0, 0};
     if (int rc = map_prune_classify_device(mp, opts, ctr)) return rc;
@@ -4695,6 +4704,217 @@ int dsx_map_prune(dsi_map_t* mp, const dsx_map_prune_opts_t* opts, dsx_map_prune
                 kept, mp->host_ctr[3]);
     }
     map_prune_info(mp, ctr, info);
+    return DSI_OK;
+}
+
+// ---- the map's connected components (include/dsi_map_components.h; DESIGN.md 7j "Components") ----
+
+namespace {
+
+// the bounds of the options: decided without a device, before any handle is looked at
+int check_components_opts(const dsx_map_components_opts_t* o)
+{
+    REQUIRE(o, DSI_ERR_INVALID, "opts is null");
+    REQUIRE(o->connectivity == 6 || o->connectivity == 18 || o->connectivity == 26 || o->connectivity == 124, DSI_ERR_INVALID,
+            "connectivity must be 6, 18, 26 or 124 (got %d)", o->connectivity);
+    return DSI_OK;
+}
+
+int check_components_selection(const dsx_map_components_selection_t* s)
+{
+    REQUIRE(s, DSI_ERR_INVALID, "sel is null");
+    REQUIRE(s->keep_largest >= 0 && s->keep_largest <= dsi::kMapCompMaxKeep, DSI_ERR_INVALID, "keep_largest must be in 0..%d (got %d)",
+            dsi::kMapCompMaxKeep, s->keep_largest);
+    REQUIRE(s->shrink == 0 || s->shrink == 1, DSI_ERR_INVALID, "shrink must be 0 or 1 (got %d)", s->shrink);
+    return DSI_OK;
+}
+
+dsi::MapComponents map_components_of(const dsi_map* mp)
+{
+    return dsi::MapComponents{mp->comp_parent.p, mp->comp_label.p, mp->comp_cells.p, mp->comp_points.p};
+}
+
+// what every entry point that reads the labelling asks of the map
+int check_labelling(const dsi_map* mp)
+{
+    REQUIRE(mp->comp_valid, DSI_ERR_INVALID,
+            "no labelling of the map as it stands: call dsx_map_components (after the last reset, integrate call, merge, import or prune)");
+    return DSI_OK;
+}
+
+// every cell's reason into mp->comp_reason and the counts into ctr (kMapCompSelectCounters); synchronises
+int map_components_select_device(dsi_map* mp, const dsx_map_components_selection_t* sel, unsigned long long* ctr)
+{
+    hipStream_t st = mp->ctx->stream;
+    HIP_TRY(mp->comp_reason.reserve((size_t)1 << mp->cap_log2));
+    const dsi::MapCompSelect o{sel->min_cells, sel->min_component_points, sel->keep_largest};
+    HIP_TRY(dsi::launch_map_components_select(st, dsi::map_table_at(mp->block.p, mp->cap_log2), map_components_of(mp), o, mp->comp_reason.p,
+                                              mp->comp_top.p, mp->comp_ctr.p));
+    HIP_TRY(hipMemcpyAsync(ctr, mp->comp_ctr.p, dsi::kMapCompSelectCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+void map_components_select_info(const dsi_map* mp, const unsigned long long* ctr, dsx_map_components_select_info_t* info)
+{
+    if (!info) return;
+    info->n_kept = ctr[0];
+    info->n_cells = ctr[0];
+    for (int r = 0; r < 4; ++r) {
+        info->n_removed[r] = ctr[1 + r];
+        info->n_cells += ctr[1 + r];
+    }
+    info->n_components_kept = ctr[5];
+    info->capacity = (uint64_t)1 << mp->cap_log2;
+}
+
+}  // namespace
+
+int dsx_map_components(dsi_map_t* mp, const dsx_map_components_opts_t* opts, dsx_map_components_info_t* info)
+{
+    if (int rc = check_components_opts(opts)) return rc;  // (first: the bounds can be exercised with no map at hand)
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
+    if (int rc = set_device(mp->ctx)) return rc;
+    mp->comp_valid = mp->comp_select_valid = false;
+    hipStream_t st = mp->ctx->stream;
+    const size_t cap = (size_t)1 << mp->cap_log2;
+    HIP_TRY(mp->comp_parent.reserve(cap));
+    HIP_TRY(mp->comp_label.reserve(cap));
+    HIP_TRY(mp->comp_cells.reserve(cap));
+    HIP_TRY(mp->comp_points.reserve(cap));
+    HIP_TRY(mp->comp_ctr.reserve(std::max(dsi::kMapCompCounters, dsi::kMapCompSelectCounters)));
+    HIP_TRY(mp->comp_top.reserve(dsi::kMapCompTopWords));
+    unsigned long long ctr[dsi::kMapCompCounters] = {0, 0, 0, 0, 0}, top[2] = {0, 0};
+    HIP_TRY(dsi::launch_map_components(st, dsi::map_table_at(mp->block.p, mp->cap_log2), opts->min_points, opts->min_windows,
+                                       opts->connectivity, map_components_of(mp), mp->comp_top.p, mp->comp_ctr.p));
+    HIP_TRY(hipMemcpyAsync(ctr, mp->comp_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(top, mp->comp_top.p, sizeof top, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    mp->comp_min_points = opts->min_points, mp->comp_min_windows = opts->min_windows;
+    mp->comp_valid = true;
+    if (info) {
+        info->n_cells = ctr[0];
+        info->n_unlabelled = ctr[1];
+        info->n_components = ctr[2];
+        info->n_singletons = ctr[3];
+        info->largest_cells = top[0];
+        info->largest_label = top[0] ? top[1] : 0;
+        info->largest_points = top[0] ? ctr[4] : 0;
+    }
+    return DSI_OK;
+}
+
+int dsx_map_components_fetch(dsi_map_t* mp, uint64_t* keys_host, uint64_t* labels_host, uint8_t* reasons_host, size_t capacity, size_t* count)
+{
+    REQUIRE(mp && count, DSI_ERR_INVALID, "null argument");
+    if (int rc = check_labelling(mp)) return rc;
+    REQUIRE(!reasons_host || mp->comp_select_valid, DSI_ERR_INVALID,
+            "no selection on this labelling: call dsx_map_components_select before asking for reasons");
+    if (int rc = set_device(mp->ctx)) return rc;
+    size_t total = 0;
+    if (int rc = map_count_device(mp, mp->comp_min_points, mp->comp_min_windows, &total)) return rc;
+    *count = total;
+    REQUIRE(capacity >= total, DSI_ERR_INVALID, "capacity of %zu cells is too small: %zu needed", capacity, total);
+    if (!total) return DSI_OK;
+    hipStream_t st = mp->ctx->stream;
+    HIP_TRY(mp->key_out.reserve(total));
+    HIP_TRY(mp->comp_label_out.reserve(total));
+    if (reasons_host) HIP_TRY(mp->comp_reason_out.reserve(total));
+    HIP_TRY(dsi::launch_map_components_gather(st, dsi::map_table_at(mp->block.p, mp->cap_log2), mp->comp_min_points, mp->comp_min_windows,
+                                              map_components_of(mp), reasons_host ? mp->comp_reason.p : nullptr, mp->blk.p, mp->key_out.p,
+                                              mp->comp_label_out.p, reasons_host ? mp->comp_reason_out.p : nullptr));
+    if (keys_host) HIP_TRY(hipMemcpyAsync(keys_host, mp->key_out.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (labels_host) HIP_TRY(hipMemcpyAsync(labels_host, mp->comp_label_out.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (reasons_host) HIP_TRY(hipMemcpyAsync(reasons_host, mp->comp_reason_out.p, total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+int dsx_map_components_list(dsi_map_t* mp, uint64_t* labels_host, uint64_t* cells_host, uint64_t* points_host, size_t capacity, size_t* count)
+{
+    REQUIRE(mp && count, DSI_ERR_INVALID, "null argument");
+    if (int rc = check_labelling(mp)) return rc;
+    if (int rc = set_device(mp->ctx)) return rc;
+    hipStream_t st = mp->ctx->stream;
+    const size_t words = dsi::pc_block_words((size_t)1 << mp->cap_log2);
+    HIP_TRY(mp->blk.reserve(words));
+    HIP_TRY(mp->tiles.reserve(dsi::pc_scan_tile_words(words)));
+    const dsi::MapTable t = dsi::map_table_at(mp->block.p, mp->cap_log2);
+    HIP_TRY(dsi::launch_map_components_count_roots(st, t, map_components_of(mp), mp->blk.p, mp->tiles.p));
+    uint32_t n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, mp->blk.p + words - 1, sizeof n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const size_t total = n;
+    *count = total;
+    REQUIRE(capacity >= total, DSI_ERR_INVALID, "capacity of %zu components is too small: %zu needed", capacity, total);
+    if (!total) return DSI_OK;
+    HIP_TRY(mp->comp_label_out.reserve(total));
+    HIP_TRY(mp->comp_cells_out.reserve(total));
+    HIP_TRY(mp->comp_points_out.reserve(total));
+    HIP_TRY(dsi::launch_map_components_list(st, t, map_components_of(mp), mp->blk.p, mp->comp_label_out.p, mp->comp_cells_out.p,
+                                            mp->comp_points_out.p));
+    if (labels_host) HIP_TRY(hipMemcpyAsync(labels_host, mp->comp_label_out.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (cells_host) HIP_TRY(hipMemcpyAsync(cells_host, mp->comp_cells_out.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (points_host) HIP_TRY(hipMemcpyAsync(points_host, mp->comp_points_out.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+int dsx_map_components_select(dsi_map_t* mp, const dsx_map_components_selection_t* sel, dsx_map_components_select_info_t* info)
+{
+    if (int rc = check_components_selection(sel)) return rc;  // (first: the bounds can be exercised with no map at hand)
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    if (int rc = check_labelling(mp)) return rc;
+    if (int rc = set_device(mp->ctx)) return rc;
+    mp->comp_select_valid = false;
+    unsigned long long ctr[dsi::kMapCompSelectCounters] = {0, 0, 0, 0, 0, 0};
+    if (int rc = map_components_select_device(mp, sel, ctr)) return rc;
+    mp->comp_select_valid = true;
+    map_components_select_info(mp, ctr, info);
+    return DSI_OK;
+}
+
+int dsx_map_prune_components(dsi_map_t* mp, const dsx_map_components_selection_t* sel, dsx_map_components_select_info_t* info)
+{
+    if (int rc = check_components_selection(sel)) return rc;
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    if (int rc = check_labelling(mp)) return rc;
+    if (int rc = set_device(mp->ctx)) return rc;
+    hipStream_t st = mp->ctx->stream;
+    mp->comp_select_valid = false;
+    unsigned long long ctr[dsi::kMapCompSelectCounters] = {0, 0, 0, 0, 0, 0};
+    if (int rc = map_components_select_device(mp, sel, ctr)) return rc;
+    mp->comp_select_valid = true;  // (the reasons are those of the map as it stands, should the rebuild fail to allocate)
+    const unsigned long long kept = ctr[0];
+    uint32_t want = mp->cap_log2;
+    if (sel->shrink)
+        for (want = kMapMinLog2; kept * 4 > ((uint64_t)3 << want); ++want) {
+        }
+    DevBuf<unsigned char> block;
+    const bool rebuild = !(ctr[1] + ctr[2] + ctr[3] + ctr[4] == 0 && want == mp->cap_log2);  // (else the table is the result already)
+    if (rebuild) {
+        const hipError_t e = block.reserve(dsi::map_table_bytes(want));
+        if (e != hipSuccess)
+            return fail(DSI_ERR_HIP, "a pruned table of 2^%u slots could not be allocated (%s): the map is unchanged", want,
+                        hipGetErrorString(e));
+    }
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->comp_select_valid = false;
+    if (rebuild) {
+        HIP_TRY(hipMemsetAsync(block.p, 0, dsi::map_table_bytes(want), st));
+        HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof(unsigned long long), st));  // occupied: the rebuild counts the cells it moves
+        if (kept)
+            HIP_TRY(dsi::launch_map_prune_rehash(st, dsi::map_table_at(mp->block.p, mp->cap_log2), dsi::map_table_at(block.p, want),
+                                                 mp->comp_reason.p, mp->ctr.p));
+        HIP_TRY(hipMemcpyAsync(mp->host_ctr, mp->ctr.p, sizeof mp->host_ctr, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        mp->block = std::move(block);  // (frees the old table)
+        mp->cap_log2 = want;
+        REQUIRE(mp->host_ctr[3] == 0 && mp->host_ctr[0] == kept, DSI_ERR_HIP,
+                "the pruned table holds %llu of %llu kept cells (%llu found it full): an engine bug, the map is unusable", mp->host_ctr[0],
+                kept, mp->host_ctr[3]);
+    }
+    map_components_select_info(mp, ctr, info);
     return DSI_OK;
 }
 
@@ -4730,7 +4950,7 @@ int map_merge_apply(dsi_map* dst, const MapMergeSource& src, dsx_map_merge_info_
     HIP_TRY(dst->merge_ctr.reserve(dsi::kMapMergeCounters));
     const uint64_t growths_before = dst->growths;
     if (int rc = map_grow_for(dst, (size_t)src.cells)) return rc;                 // (a failed allocation leaves dst as it is)
-    dst->render_valid = dst->compare_valid = dst->prune_valid = dst->align_valid = false;  // (the map changes from here on)
+    dst->render_valid = dst->compare_valid = dst->prune_valid = dst->align_valid = dst->comp_valid = false;  // (the map changes from here on)
     unsigned long long mctr[dsi::kMapMergeCounters] = {0, 0};
     HIP_TRY(dsi::launch_map_merge(st, src.t, dsi::map_table_at(dst->block.p, dst->cap_log2), (uint32_t)dst->calls, src.accepted,
                                   src.rejected, dst->ctr.p, dst->merge_ctr.p));

@@ -419,6 +419,45 @@ hipError_t launch_map_prune_rehash(hipStream_t s, const MapTable& from, const Ma
 hipError_t launch_map_prune_gather(hipStream_t s, const MapTable& t, const uint8_t* reason, const uint32_t* blk, uint8_t* reason_out,
                                    unsigned long long* key_out);
 
+// ---- the map's connected components (include/dsi_map_components.h; DESIGN.md 7j "Components") ----
+// the labelling of a table, per slot: parent (after launch_map_components the root's slot for a node, kMapCompNone
+// elsewhere) and, meaningful at a root's slot only, the component's label (its smallest key), cells and points
+struct MapComponents {
+    uint32_t* parent;
+    unsigned long long* label;
+    uint32_t* cells;
+    unsigned long long* points;
+};
+constexpr uint32_t kMapCompNone = 0xffffffffu;
+constexpr int kMapCompMaxKeep = 16;
+constexpr int kMapCompCounters = 5;        // nodes, unlabelled cells, components, singletons, the largest's points
+constexpr int kMapCompSelectCounters = 6;  // kept, removed by reason 1..4, components kept
+constexpr int kMapCompTopWords = 2 * kMapCompMaxKeep;  // per rank: cells, label
+// the selection's criteria 2-4; keep 0..kMapCompMaxKeep
+struct MapCompSelect {
+    unsigned long long min_cells, min_points;
+    int keep;
+};
+// clears ctr [kMapCompCounters] and top [kMapCompTopWords]; labels the nodes of t (the cells that pass the filter) at
+// connectivity 6, 18, 26 or 124; top[0], top[1]: the largest component's cells and label (0, ~0 without a node).  A fixed
+// number of launches, whatever the table holds.
+hipError_t launch_map_components(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, int connectivity,
+                                 const MapComponents& c, unsigned long long* top, unsigned long long* ctr);
+// clears ctr [kMapCompSelectCounters] and top; reason [cap]: every slot's reason under o (kMapPruneEmpty without a cell):
+// two launches per rank of o.keep and one for the reasons
+hipError_t launch_map_components_select(hipStream_t s, const MapTable& t, const MapComponents& c, const MapCompSelect& o, uint8_t* reason,
+                                        unsigned long long* top, unsigned long long* ctr);
+// after launch_map_count(t, min_points, min_windows) with the labelling's filter: key, label and (reason != NULL) reason of
+// every node in slot order (launch_map_extract's)
+hipError_t launch_map_components_gather(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, const MapComponents& c,
+                                        const uint8_t* reason, const uint32_t* blk, unsigned long long* key_out,
+                                        unsigned long long* label_out, uint8_t* reason_out);
+// the roots counted per tile of the table and scanned, as launch_map_count does for cells
+hipError_t launch_map_components_count_roots(hipStream_t s, const MapTable& t, const MapComponents& c, uint32_t* blk, uint32_t* tiles);
+// after launch_map_components_count_roots: label, cells and points of every component in slot order of the roots
+hipError_t launch_map_components_list(hipStream_t s, const MapTable& t, const MapComponents& c, const uint32_t* blk,
+                                      unsigned long long* label_out, unsigned long long* cells_out, unsigned long long* points_out);
+
 // ---- merging maps and moving their state (include/dsi_map_merge.h; DESIGN.md 7j "Merging") ----
 constexpr int kMapImportCounters = 8;  // bad key, duplicate, n == 0, bad windows, bad stamp, S too large, table full, sum of n
 constexpr int kMapMergeCounters = 2;   // cells new to dst, cells both maps hold

@@ -7343,6 +7343,367 @@ __global__ void __launch_bounds__(kPcBlock) k_map_prune_gather(MapTable t, const
     key_out[o] = t.keys[i];
 }
 
+// ---- the map's connected components (include/dsi_map_components.h dsx_map_components*; DESIGN.md 7j "Components") ----
+// A lock-free union-find over SLOT indices: parent[slot] = slot for a node (a cell that passes the filter), kMapCompNone
+// elsewhere; a component's root is its smallest slot.  The launches are fixed -- init, union, flatten, reduce, two for the
+// largest, count -- whatever the table holds.  Every kernel walks the slots like k_map_render and counts like
+// k_map_prune_reason.
+//
+// init: parent as above; label = all ones, cells = points = 0 (the reduce's atomics meet initialised words);
+// ctr[0] += nodes, ctr[1] += occupied slots that are no node.
+__global__ void __launch_bounds__(kPcBlock) k_map_comp_init(MapTable t, uint32_t min_points, uint32_t min_windows, MapComponents c,
+                                                            unsigned long long* __restrict__ ctr)
+{
+    __shared__ uint32_t s_cnt[2];
+    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    uint32_t c_node = 0, c_other = 0;  // (the same in every lane of a wave)
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        const bool occupied = map_passes(t, i, 0u, 0u), node = occupied && map_passes(t, i, min_points, min_windows);
+        c.parent[i] = node ? (uint32_t)i : kMapCompNone;  // (cap is a multiple of the workgroup: i < cap)
+        c.label[i] = ~0ull;
+        c.cells[i] = 0u;
+        c.points[i] = 0ull;
+        c_node += (uint32_t)__popcll(__ballot(node));
+        c_other += (uint32_t)__popcll(__ballot(occupied && !node));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (c_node) atomicAdd(&s_cnt[0], c_node);
+        if (c_other) atomicAdd(&s_cnt[1], c_other);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
+__device__ inline uint32_t comp_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root above x as far as this thread can see it; halves the path on the way (a parent becomes its own parent)
+__device__ inline uint32_t comp_find(uint32_t* parent, uint32_t x)
+{
+    uint32_t p = comp_load(&parent[x]);
+    while (p != x) {
+        const uint32_t g = comp_load(&parent[p]);
+        if (g != p) __hip_atomic_store(&parent[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        x = p;
+        p = g;
+    }
+    return x;
+}
+
+// One thread per node and, per node, the POSITIVE half of the connectivity's offsets (the first non-zero of oz, oy, ox is
+// positive: 3 / 9 / 13 / 62 lookups at 6 / 18 / 26 / 124), so that every edge is met once; an index with
+// |c + o| > kPcCellMax is skipped (it has no key).  A neighbour that map_find finds and that is a node is united with the
+// cell: both roots are found, and the root with the larger slot is hooked under the smaller by
+// atomicCAS(&parent[hi], hi, lo); when the CAS fails the find goes on from the value it returned.  The walks start from
+// ancestors already in hand -- the cell's side from where the last neighbour's unite ended, the neighbour's from the parent
+// that the node test loaded -- and a neighbour whose parent IS that ancestor costs no further load: inside a large
+// component most do, and every walk saved is a load of the one line that holds the root.
+// parent[i] <= i holds under every interleaving (a root is hooked under a smaller slot, a halving store writes an
+// ancestor, and ancestors are smaller), so no cycle can form and every walk ends; every failed CAS is another thread's
+// successful one, and there are fewer of those than nodes.
+// A STALE read of parent is harmless, which is why there is no fence, no flag and no waiting here (a CU's L1 is not
+// refreshed by other CUs' stores and the XCDs' L2s are not coherent; the loads are relaxed agent-scope atomics only so
+// that retries stay few): only roots are ever hooked, and halving only replaces a parent by an ancestor, so "a is an
+// ancestor of b" never stops being true -- whatever value of parent[x] a thread sees, old or new, is an ancestor of x.
+// Two finds that meet at one slot therefore prove one component, and nothing is decided on a value that may be stale:
+// a new edge enters only through the CAS, which executes at the coherence point, succeeds only on a slot that is a
+// root at that moment and reports the current parent when it fails.
+__global__ void __launch_bounds__(kPcBlock) k_map_comp_union(MapTable t, int connectivity, uint32_t* parent)
+{
+    const int reach = connectivity == 124 ? 2 : 1;
+    const int most = connectivity == 6 ? 1 : connectivity == 18 ? 2 : 6;  // the largest |o|_1
+    const uint32_t mask = (1u << t.cap_log2) - 1u;
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const uint32_t i = (uint32_t)(base + threadIdx.x);
+        if (comp_load(&parent[i]) == kMapCompNone) continue;  // (nodes keep a slot, the others kMapCompNone, for good)
+        const unsigned long long k = t.keys[i];
+        int c[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) c[a] = (int)((k >> (21 * a)) & 0x1fffffull) - (kPcCellMax + 1);
+        uint32_t up = i;  // the nearest ancestor of i this thread knows: the next neighbour's walk starts there
+        for (int oz = 0; oz <= reach; ++oz) {
+            const int vz = c[2] + oz;
+            if (vz > kPcCellMax) continue;
+            for (int oy = -reach; oy <= reach; ++oy) {
+                const int vy = c[1] + oy;
+                if (abs(vy) > kPcCellMax) continue;
+                for (int ox = -reach; ox <= reach; ++ox) {
+                    const int vx = c[0] + ox;
+                    if (!(oz > 0 || oy > 0 || (oy == 0 && ox > 0)) || abs(ox) + abs(oy) + oz > most || abs(vx) > kPcCellMax) continue;
+                    const uint32_t j = map_find(t.keys, mask, pc_key(vx, vy, vz));
+                    if (j == ~0u) continue;
+                    uint32_t a = up, b = comp_load(&parent[j]);  // ancestors of i and of j
+                    if (b == kMapCompNone) continue;
+                    while (a != b) {
+                        a = comp_find(parent, a);
+                        b = comp_find(parent, b);
+                        if (a == b) break;
+                        const uint32_t hi = max(a, b), lo = min(a, b);
+                        const uint32_t seen = atomicCAS(&parent[hi], hi, lo);
+                        a = lo;
+                        if (seen == hi) break;
+                        b = seen;  // (hi was hooked by another thread meanwhile: on from its current parent)
+                    }
+                    up = a;  // (a == b, or lo with hi hooked under it: an ancestor of i either way)
+                }
+            }
+        }
+    }
+}
+
+// every node's parent becomes its root.  Reads what k_map_comp_union left; a slot another thread of this launch has
+// flattened already holds its root instead of a nearer ancestor, and either leads to the same root (a root is never written).
+__global__ void __launch_bounds__(kPcBlock) k_map_comp_flatten(uint32_t cap_log2, uint32_t* parent)
+{
+    const size_t cap = (size_t)1 << cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        uint32_t r = parent[i];
+        if (r == kMapCompNone || r == (uint32_t)i) continue;
+        for (uint32_t p = parent[r]; p != r; p = parent[r]) r = p;
+        parent[i] = r;
+    }
+}
+
+__device__ inline unsigned long long comp_wave_min(unsigned long long v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(v, off, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+__device__ inline unsigned long long comp_wave_sum(unsigned long long v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// per node, at its root's slot: label = min(label, key), cells += 1, points += n -- integer atomics on words that
+// k_map_comp_init wrote, so the order of the threads does not matter.  The nodes among a wave's 64 slots are taken root by
+// root (a uniform loop: the first node left names the root, every lane with that root joins): a root that one lane holds
+// gets that lane's three atomics; a root that several hold -- the rule inside a large component, whose cells the hash
+// scatters over the table -- is reduced in registers and gets the three atomics once.  Per-lane atomics alone were bound by
+// the largest component: each of its cells an atomic on the same three words, at the 83 per microsecond one line takes.
+__global__ void __launch_bounds__(kPcBlock) k_map_comp_reduce(MapTable t, MapComponents c)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        const uint32_t r = c.parent[i];
+        const bool node = r != kMapCompNone;
+        const unsigned long long key = node ? t.keys[i] : ~0ull, n = node ? (unsigned long long)t.n[i] : 0ull;
+        unsigned long long left = __ballot(node);  // (the same in every lane of the wave, as is the loop below)
+        while (left != 0ull) {
+            const int lead = __ffsll((long long)left) - 1;
+            const uint32_t r0 = __shfl(r, lead, 64);
+            const bool mine = node && r == r0;
+            const unsigned long long same = __ballot(mine);  // (lanes taken earlier hold other roots)
+            if (__popcll(same) == 1) {
+                if (mine) {
+                    atomicMin(&c.label[r0], key);
+                    atomicAdd(&c.cells[r0], 1u);
+                    atomicAdd(&c.points[r0], n);
+                }
+            } else {
+                const unsigned long long k_min = comp_wave_min(mine ? key : ~0ull), n_sum = comp_wave_sum(mine ? n : 0ull);
+                if (lane == lead) {
+                    atomicMin(&c.label[r0], k_min);
+                    atomicAdd(&c.cells[r0], (uint32_t)__popcll(same));
+                    atomicAdd(&c.points[r0], n_sum);
+                }
+            }
+            left &= ~same;
+        }
+    }
+}
+
+// whether the root at slot i passes the selection's criteria 2 and 3
+__device__ inline bool comp_eligible(const MapComponents& c, size_t i, const MapCompSelect& o)
+{
+    return c.parent[i] == (uint32_t)i && (unsigned long long)c.cells[i] >= o.min_cells && c.points[i] >= o.min_points;
+}
+
+// whether (cells, label) comes strictly after rank k - 1 of `top` in the order cells descending, label ascending
+__device__ inline bool comp_after(const unsigned long long* __restrict__ top, int k, unsigned long long cells, unsigned long long label)
+{
+    if (k == 0) return true;
+    const unsigned long long tc = top[2 * (k - 1)], tl = top[2 * (k - 1) + 1];
+    return cells < tc || (cells == tc && label > tl);
+}
+
+// Rank k of the selection's order, in two launches: top[2 k] = the most cells among the eligible roots after rank k - 1
+// (0 when none is left: top was cleared), then top[2 k + 1] = the smallest label among those with that many cells (all
+// ones when none is left).  Ranks 0 .. k - 1 are read as earlier launches left them.
+__global__ void __launch_bounds__(kPcBlock) k_map_comp_rank_cells(uint32_t cap_log2, MapComponents c, MapCompSelect o, int k,
+                                                                  unsigned long long* __restrict__ top)
+{
+    __shared__ uint32_t s_max;
+    if (threadIdx.x == 0) s_max = 0u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) top[2 * k + 1] = ~0ull;  // (k_map_comp_rank_label's start)
+    __syncthreads();
+    uint32_t best = 0;
+    const size_t cap = (size_t)1 << cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        if (comp_eligible(c, i, o) && comp_after(top, k, c.cells[i], c.label[i])) best = max(best, c.cells[i]);
+    }
+    if (best) atomicMax(&s_max, best);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_max) atomicMax(&top[2 * k], (unsigned long long)s_max);
+}
+
+__global__ void __launch_bounds__(kPcBlock) k_map_comp_rank_label(uint32_t cap_log2, MapComponents c, MapCompSelect o, int k,
+                                                                  unsigned long long* __restrict__ top)
+{
+    const unsigned long long want = top[2 * k];
+    if (want == 0ull) return;  // (no component is left for this rank)
+    const size_t cap = (size_t)1 << cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        if (comp_eligible(c, i, o) && (unsigned long long)c.cells[i] == want && comp_after(top, k, want, c.label[i]))
+            atomicMin(&top[2 * k + 1], c.label[i]);  // (a handful of roots at most share the largest count)
+    }
+}
+
+// ctr[2] += roots, ctr[3] += roots of one cell; ctr[4] = the points of the root that top[0], top[1] name (one writer)
+__global__ void __launch_bounds__(kPcBlock) k_map_comp_count(uint32_t cap_log2, MapComponents c, const unsigned long long* __restrict__ top,
+                                                             unsigned long long* __restrict__ ctr)
+{
+    __shared__ uint32_t s_cnt[2];
+    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    uint32_t c_root = 0, c_single = 0;  // (the same in every lane of a wave)
+    const size_t cap = (size_t)1 << cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        const bool root = c.parent[i] == (uint32_t)i;
+        const uint32_t cells = root ? c.cells[i] : 0u;
+        if (root && (unsigned long long)cells == top[0] && c.label[i] == top[1]) ctr[4] = c.points[i];
+        c_root += (uint32_t)__popcll(__ballot(root));
+        c_single += (uint32_t)__popcll(__ballot(cells == 1u));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (c_root) atomicAdd(&s_cnt[0], c_root);
+        if (c_single) atomicAdd(&s_cnt[1], c_single);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&ctr[2 + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
+// The selection's reason of every slot (kMapPruneEmpty without a cell), the first that holds: 1 no node; 2 its
+// component's cells < min_cells; 3 its points < min_points; 4 keep > 0 and the component comes after rank keep - 1 of
+// `top` (a rank that found no component -- cells 0 -- means that fewer than keep exist: all of them stay).
+// ctr[0] += kept, ctr[r] += removed by reason r, ctr[5] += roots kept.
+__global__ void __launch_bounds__(kPcBlock) k_map_comp_select(MapTable t, MapComponents c, MapCompSelect o,
+                                                              const unsigned long long* __restrict__ top, uint8_t* __restrict__ reason,
+                                                              unsigned long long* __restrict__ ctr)
+{
+    __shared__ uint32_t s_cnt[kMapCompSelectCounters];
+    if (threadIdx.x < kMapCompSelectCounters) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c_root = 0;  // (the same in every lane of a wave)
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        uint32_t r = kMapPruneEmpty;
+        bool root = false;
+        if (map_passes(t, i, 0u, 0u)) {
+            const uint32_t p = c.parent[i];
+            if (p == kMapCompNone) {
+                r = 1u;
+            } else {
+                const unsigned long long cells = c.cells[p], label = c.label[p];
+                if (cells < o.min_cells)
+                    r = 2u;
+                else if (c.points[p] < o.min_points)
+                    r = 3u;
+                else if (o.keep > 0 && top[2 * (o.keep - 1)] != 0ull && comp_after(top, o.keep, cells, label))
+                    r = 4u;
+                else
+                    r = 0u;
+                root = r == 0u && p == (uint32_t)i;
+            }
+        }
+        reason[i] = (uint8_t)r;
+        c0 += (uint32_t)__popcll(__ballot(r == 0u));
+        c1 += (uint32_t)__popcll(__ballot(r == 1u));
+        c2 += (uint32_t)__popcll(__ballot(r == 2u));
+        c3 += (uint32_t)__popcll(__ballot(r == 3u));
+        c4 += (uint32_t)__popcll(__ballot(r == 4u));
+        c_root += (uint32_t)__popcll(__ballot(root));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (c0) atomicAdd(&s_cnt[0], c0);
+        if (c1) atomicAdd(&s_cnt[1], c1);
+        if (c2) atomicAdd(&s_cnt[2], c2);
+        if (c3) atomicAdd(&s_cnt[3], c3);
+        if (c4) atomicAdd(&s_cnt[4], c4);
+        if (c_root) atomicAdd(&s_cnt[5], c_root);
+    }
+    __syncthreads();
+    if (threadIdx.x < kMapCompSelectCounters && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
+// the labelling compacted like k_map_extract's cells under the labelling's filter, with its blk_off (one offset per tile of
+// kPcBlock slots): key, label and, when asked for, the selection's reason, in slot order; walked in strides like k_map_export
+__global__ void __launch_bounds__(kPcBlock) k_map_comp_gather(MapTable t, uint32_t min_points, uint32_t min_windows, MapComponents c,
+                                                              const uint8_t* __restrict__ reason, const uint32_t* __restrict__ blk_off,
+                                                              unsigned long long* __restrict__ key_out,
+                                                              unsigned long long* __restrict__ label_out, uint8_t* __restrict__ reason_out)
+{
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        const bool f = map_passes(t, i, min_points, min_windows);
+        uint32_t total;
+        const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);  // (every thread of the workgroup, every round)
+        if (f) {
+            const size_t o = (size_t)blk_off[base / kPcBlock] + rank;
+            key_out[o] = t.keys[i];
+            label_out[o] = c.label[c.parent[i]];
+            if (reason) reason_out[o] = reason[i];
+        }
+    }
+}
+
+// blk[b] = number of roots in [b * kPcBlock, (b + 1) * kPcBlock): k_map_flag_count for components
+__global__ void __launch_bounds__(kPcBlock) k_map_comp_root_count(const uint32_t* __restrict__ parent, uint32_t* __restrict__ blk)
+{
+    const size_t i = (size_t)blockIdx.x * kPcBlock + threadIdx.x;  // (< cap: a multiple of the workgroup)
+    uint32_t total;
+    (void)pc_block_exclusive(parent[i] == (uint32_t)i ? 1u : 0u, &total);
+    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+}
+
+// one row per root, in slot order, with k_map_comp_root_count's scanned blk_off
+__global__ void __launch_bounds__(kPcBlock) k_map_comp_list(uint32_t cap_log2, MapComponents c, const uint32_t* __restrict__ blk_off,
+                                                            unsigned long long* __restrict__ label_out,
+                                                            unsigned long long* __restrict__ cells_out,
+                                                            unsigned long long* __restrict__ points_out)
+{
+    const size_t cap = (size_t)1 << cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        const bool f = c.parent[i] == (uint32_t)i;
+        uint32_t total;
+        const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);  // (every thread of the workgroup, every round)
+        if (f) {
+            const size_t o = (size_t)blk_off[base / kPcBlock] + rank;
+            label_out[o] = c.label[i];
+            cells_out[o] = (unsigned long long)c.cells[i];
+            points_out[o] = c.points[i];
+        }
+    }
+}
+
 // ---- merging maps and moving their state (include/dsi_map_merge.h dsx_map_export / import / merge; DESIGN.md 7j "Merging") ----
 // Every occupied slot's raw state compacted like k_map_extract's cells under the filter (0, 0), with its blk_off (one
 // offset per tile of kPcBlock slots): key, n, S[3], windows and stamp in slot order.  Walked in strides like k_map_render;
@@ -7787,6 +8148,63 @@ hipError_t launch_map_prune_gather(hipStream_t s, const MapTable& t, const uint8
 {
     const uint32_t nb = pc_blocks((size_t)1 << t.cap_log2);
     hipLaunchKernelGGL(k_map_prune_gather, dim3(nb), dim3(kPcBlock), 0, s, t, reason, blk, reason_out, key_out);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_components(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, int connectivity,
+                                 const MapComponents& c, unsigned long long* top, unsigned long long* ctr)
+{
+    hipError_t e = hipMemsetAsync(ctr, 0, kMapCompCounters * sizeof(unsigned long long), s);
+    if (e == hipSuccess) e = hipMemsetAsync(top, 0, kMapCompTopWords * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    const dim3 grid(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), block(kPcBlock);
+    const MapCompSelect all{0ull, 0ull, 1};
+    hipLaunchKernelGGL(k_map_comp_init, grid, block, 0, s, t, min_points, min_windows, c, ctr);
+    hipLaunchKernelGGL(k_map_comp_union, grid, block, 0, s, t, connectivity, c.parent);
+    hipLaunchKernelGGL(k_map_comp_flatten, grid, block, 0, s, t.cap_log2, c.parent);
+    hipLaunchKernelGGL(k_map_comp_reduce, grid, block, 0, s, t, c);
+    hipLaunchKernelGGL(k_map_comp_rank_cells, grid, block, 0, s, t.cap_log2, c, all, 0, top);
+    hipLaunchKernelGGL(k_map_comp_rank_label, grid, block, 0, s, t.cap_log2, c, all, 0, top);
+    hipLaunchKernelGGL(k_map_comp_count, grid, block, 0, s, t.cap_log2, c, top, ctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_components_select(hipStream_t s, const MapTable& t, const MapComponents& c, const MapCompSelect& o, uint8_t* reason,
+                                        unsigned long long* top, unsigned long long* ctr)
+{
+    hipError_t e = hipMemsetAsync(ctr, 0, kMapCompSelectCounters * sizeof(unsigned long long), s);
+    if (e == hipSuccess) e = hipMemsetAsync(top, 0, kMapCompTopWords * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    const dim3 grid(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), block(kPcBlock);
+    for (int k = 0; k < o.keep; ++k) {
+        hipLaunchKernelGGL(k_map_comp_rank_cells, grid, block, 0, s, t.cap_log2, c, o, k, top);
+        hipLaunchKernelGGL(k_map_comp_rank_label, grid, block, 0, s, t.cap_log2, c, o, k, top);
+    }
+    hipLaunchKernelGGL(k_map_comp_select, grid, block, 0, s, t, c, o, top, reason, ctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_components_gather(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, const MapComponents& c,
+                                        const uint8_t* reason, const uint32_t* blk, unsigned long long* key_out,
+                                        unsigned long long* label_out, uint8_t* reason_out)
+{
+    hipLaunchKernelGGL(k_map_comp_gather, dim3(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s, t,
+                       min_points, min_windows, c, reason, blk, key_out, label_out, reason_out);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_components_count_roots(hipStream_t s, const MapTable& t, const MapComponents& c, uint32_t* blk, uint32_t* tiles)
+{
+    const uint32_t nb = pc_blocks((size_t)1 << t.cap_log2);
+    hipLaunchKernelGGL(k_map_comp_root_count, dim3(nb), dim3(kPcBlock), 0, s, c.parent, blk);
+    return pc_scan(s, blk, nb, tiles);
+}
+
+hipError_t launch_map_components_list(hipStream_t s, const MapTable& t, const MapComponents& c, const uint32_t* blk,
+                                      unsigned long long* label_out, unsigned long long* cells_out, unsigned long long* points_out)
+{
+    hipLaunchKernelGGL(k_map_comp_list, dim3(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s,
+                       t.cap_log2, c, blk, label_out, cells_out, points_out);
     return hipExtGetLastError();
 }
 

@@ -100,6 +100,24 @@ class _MapPruneInfo(C.Structure):
     _fields_ = [("n_cells", C.c_uint64), ("n_kept", C.c_uint64), ("n_removed", C.c_uint64 * 5), ("capacity", C.c_uint64)]
 
 
+class _MapComponentsOpts(C.Structure):
+    _fields_ = [("min_points", C.c_uint32), ("min_windows", C.c_uint32), ("connectivity", C.c_int32)]
+
+
+class _MapComponentsInfo(C.Structure):
+    _fields_ = [("n_cells", C.c_uint64), ("n_unlabelled", C.c_uint64), ("n_components", C.c_uint64), ("n_singletons", C.c_uint64),
+                ("largest_label", C.c_uint64), ("largest_cells", C.c_uint64), ("largest_points", C.c_uint64)]
+
+
+class _MapComponentsSelection(C.Structure):
+    _fields_ = [("min_cells", C.c_uint64), ("min_component_points", C.c_uint64), ("keep_largest", C.c_int32), ("shrink", C.c_int32)]
+
+
+class _MapComponentsSelectInfo(C.Structure):
+    _fields_ = [("n_cells", C.c_uint64), ("n_kept", C.c_uint64), ("n_removed", C.c_uint64 * 4), ("n_components_kept", C.c_uint64),
+                ("capacity", C.c_uint64)]
+
+
 class _MapState(C.Structure):
     _fields_ = [("leaf", C.c_double), ("n_cells", C.c_uint64), ("calls", C.c_uint64), ("accepted", C.c_uint64),
                 ("rejected", C.c_uint64)]
@@ -393,6 +411,12 @@ def load_library():
         "dsx_map_prune_classify": (C.c_int, [vp, C.POINTER(_MapPruneOpts), C.POINTER(_MapPruneInfo)]),
         "dsx_map_prune_fetch": (C.c_int, [vp, u8p, u64p, C.c_size_t, szp]),
         "dsx_map_prune": (C.c_int, [vp, C.POINTER(_MapPruneOpts), C.POINTER(_MapPruneInfo)]),
+        # include/dsi_map_components.h: the map's connected components
+        "dsx_map_components": (C.c_int, [vp, C.POINTER(_MapComponentsOpts), C.POINTER(_MapComponentsInfo)]),
+        "dsx_map_components_fetch": (C.c_int, [vp, u64p, u64p, u8p, C.c_size_t, szp]),
+        "dsx_map_components_list": (C.c_int, [vp, u64p, u64p, u64p, C.c_size_t, szp]),
+        "dsx_map_components_select": (C.c_int, [vp, C.POINTER(_MapComponentsSelection), C.POINTER(_MapComponentsSelectInfo)]),
+        "dsx_map_prune_components": (C.c_int, [vp, C.POINTER(_MapComponentsSelection), C.POINTER(_MapComponentsSelectInfo)]),
         # include/dsi_map_merge.h: merging maps, exporting and importing their state
         "dsx_map_export": (C.c_int, [vp, C.POINTER(_MapState), u64p, u32p, u64p, u32p, u32p, C.c_size_t, szp]),
         "dsx_map_import": (C.c_int, [vp, C.POINTER(_MapState), u64p, u32p, u64p, u32p, u32p, C.POINTER(_MapMergeInfo)]),
@@ -1314,6 +1338,79 @@ class WorldMap:
             order = np.argsort(out["keys"], kind="stable")
             out = {k: v[order] for k, v in out.items()}
         return out
+
+    def components(self, min_points=1, min_windows=1, connectivity=26):
+        """Labels the map's connected components (dsx_map_components; the rule is stated in dsi_map_components.h and
+        DESIGN.md 7j "Components").  The nodes are the cells extract(min_points, min_windows) returns; two are adjacent
+        when their cell indices differ by an offset of the connectivity: 6 (faces), 18 (and edges), 26 (and corners) or
+        124 (the 5 x 5 x 5 box).  A component's label is the smallest key among its cells.  Returns dict of n_cells
+        (nodes), n_unlabelled, n_components, n_singletons, largest_label, largest_cells, largest_points (the largest by
+        cells, then by the smaller label).  The labelling stays on the device for fetchComponents, listComponents,
+        selectComponents and pruneComponents until the map changes; nothing else of the map changes."""
+        o = _MapComponentsOpts(int(min_points), int(min_windows), int(connectivity))
+        i = _MapComponentsInfo()
+        _check(load_library().dsx_map_components(self._h, C.byref(o), C.byref(i)))
+        self._components_selected = False
+        return {k: int(getattr(i, k)) for k, _ in _MapComponentsInfo._fields_}
+
+    def fetchComponents(self, sort=True):
+        """keys and labels (uint64) of every node of the last components() of this map and, after a selectComponents() on
+        it, reason (uint8: 0 kept, 1..4 the first reason of the selection that holds) (dsx_map_components_fetch); raises
+        DsiError when the map changed since.  sort=True orders them by ascending key; otherwise the order is
+        extract(sort=False)'s under the labelling's filter."""
+        L = load_library()
+        n = C.c_size_t()
+        rc = L.dsx_map_components_fetch(self._h, None, None, None, 0, C.byref(n))
+        if rc != OK and n.value == 0:
+            _check(rc)
+        m = n.value
+        out = {"keys": np.empty(m, np.uint64), "labels": np.empty(m, np.uint64)}
+        if getattr(self, "_components_selected", False):
+            out["reason"] = np.empty(m, np.uint8)
+        _check(L.dsx_map_components_fetch(self._h, _ptr(out["keys"], C.c_uint64), _ptr(out["labels"], C.c_uint64),
+                                          _ptr(out["reason"], C.c_uint8) if "reason" in out else None, m, C.byref(n)))
+        if sort:
+            order = np.argsort(out["keys"], kind="stable")
+            out = {k: v[order] for k, v in out.items()}
+        return out
+
+    def listComponents(self):
+        """labels, cells and points (uint64) of every component of the last components() of this map
+        (dsx_map_components_list), by cells descending, then label ascending; raises DsiError when the map changed since."""
+        L = load_library()
+        n = C.c_size_t()
+        rc = L.dsx_map_components_list(self._h, None, None, None, 0, C.byref(n))
+        if rc != OK and n.value == 0:
+            _check(rc)
+        m = n.value
+        out = {"labels": np.empty(m, np.uint64), "cells": np.empty(m, np.uint64), "points": np.empty(m, np.uint64)}
+        _check(L.dsx_map_components_list(self._h, _ptr(out["labels"], C.c_uint64), _ptr(out["cells"], C.c_uint64),
+                                         _ptr(out["points"], C.c_uint64), m, C.byref(n)))
+        order = np.lexsort((out["labels"], -out["cells"].astype(np.int64)))
+        return {k: v[order] for k, v in out.items()}
+
+    def selectComponents(self, min_cells=1, min_component_points=1, keep_largest=0, shrink=False):
+        """pruneComponents()'s dry run (dsx_map_components_select): the same counts, the map unchanged; the per-cell reasons
+        stay on the device for fetchComponents until the map changes."""
+        return self._select_components(load_library().dsx_map_components_select, min_cells, min_component_points, keep_largest, shrink)
+
+    def pruneComponents(self, min_cells=1, min_component_points=1, keep_largest=0, shrink=False):
+        """Removes cells by the last components() of this map and rebuilds the table around the rest
+        (dsx_map_prune_components).  A cell leaves by the first reason that holds: it is unlabelled; its component has fewer
+        than min_cells cells; fewer than min_component_points points; keep_largest (1..16; 0: off) -- its component is not
+        among the keep_largest first of those left, by cells descending, then label ascending.  shrink as prune()'s.
+        Returns dict of n_cells = n_kept + sum(n_removed), n_kept, n_removed (four counts, by reason), n_components_kept
+        and capacity (slots afterwards).  Render, compare, alignment, classification and labelling are invalid afterwards."""
+        return self._select_components(load_library().dsx_map_prune_components, min_cells, min_component_points, keep_largest, shrink)
+
+    def _select_components(self, fn, min_cells, min_component_points, keep_largest, shrink):
+        s = _MapComponentsSelection(int(min_cells), int(min_component_points), int(keep_largest), 1 if shrink else 0)
+        i = _MapComponentsSelectInfo()
+        self._components_selected = False
+        _check(fn(self._h, C.byref(s), C.byref(i)))
+        self._components_selected = True
+        return {"n_cells": int(i.n_cells), "n_kept": int(i.n_kept), "n_removed": [int(v) for v in i.n_removed],
+                "n_components_kept": int(i.n_components_kept), "capacity": int(i.capacity)}
 
     def exportState(self, sort=True):
         """The map's exact state (dsx_map_export; the rule is stated in dsi_map_merge.h and DESIGN.md 7j "Merging"): dict

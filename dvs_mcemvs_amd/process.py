@@ -746,7 +746,8 @@ class WindowStream:
 def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop_time_s, duration,
                   out_skip, fusion_method=E.FUSE_HM, forward_looking=True, rv_pos=0.0, options_depth_map=None,
                   options_point_cloud=None, polarities=None, save_images=False, out_path=None, lut=None, score=None,
-                  ground_truth=None, ground_truth_disparity=None, thicken_edges=False, world_map=None, world_map_prune=None, **kw):
+                  ground_truth=None, ground_truth_disparity=None, thicken_edges=False, world_map=None, world_map_prune=None,
+                  world_map_components=None, **kw):
     """Generator over the windows of main.cpp:177-302: yields (ts, depth, confidence, indices) per
     window, pipelined one window deep; with options_depth_map, (ts, depth_map, confidence_map, mask)
     -- the filtered outputs the reference saves per window; with options_point_cloud as well, the window's
@@ -789,7 +790,26 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
     `local_box` = (hx, hy, hz) instead of `box`: the box is then the window's reference position +- the half extents,
     lo = t - h and hi = t + h in double with t the translation of the T_w_rv the window was integrated with -- a local map
     that forgets what lies behind the vehicle (max_age does the same by calls).  A pruned window's result gains a last
-    element, {"world_map_prune": the counts WorldMap.prune returns}."""
+    element, {"world_map_prune": the counts WorldMap.prune returns}.
+    world_map_components= (with world_map=; None leaves the stream as it is): a dict of the keywords of WorldMap.components
+    (min_points, min_windows, connectivity) and of WorldMap.pruneComponents (min_cells, min_component_points, keep_largest,
+    shrink) plus `every` (default 1): after every every-th window, right after that window's cloud went in -- and after
+    world_map_prune's prune, when both fall on the window --, the map is labelled and pruned by component.  Such a window's
+    result gains a last element, {"world_map_components": the counts of WorldMap.components, and under "prune" those of
+    WorldMap.pruneComponents}."""
+    comps = None
+    if world_map_components is not None:
+        if world_map is None:
+            raise ValueError("world_map_components needs world_map")
+        comps = dict(world_map_components)
+        every = comps.pop("every", 1)
+        if int(every) != every or every < 1:
+            raise ValueError("world_map_components['every'] must be an integer >= 1")
+        label_keys, select_keys = {"min_points", "min_windows", "connectivity"}, {"min_cells", "min_component_points", "keep_largest", "shrink"}
+        unknown = set(comps) - label_keys - select_keys
+        if unknown:
+            raise ValueError("world_map_components: unknown keys %s" % sorted(unknown))
+        comps = ({k: v for k, v in comps.items() if k in label_keys}, {k: v for k, v in comps.items() if k in select_keys}, int(every))
     prune = None
     if world_map_prune is not None:
         if world_map is None:
@@ -847,10 +867,13 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
     def result(pending):
         nonlocal windows_seen
         out = _window_result(ws, pending, options_depth_map, options_point_cloud, images, scoring, world_map)
-        if prune is not None:
-            windows_seen += 1
-            if windows_seen % prune[1] == 0:
-                out = out + ({"world_map_prune": _prune_world_map(world_map, prune[0], prune[2], pending[3])},)
+        windows_seen += 1
+        if prune is not None and windows_seen % prune[1] == 0:
+            out = out + ({"world_map_prune": _prune_world_map(world_map, prune[0], prune[2], pending[3])},)
+        if comps is not None and windows_seen % comps[2] == 0:
+            counts = world_map.components(**comps[0])
+            counts["prune"] = world_map.pruneComponents(**comps[1])
+            out = out + ({"world_map_components": counts},)
         return out
 
     try:

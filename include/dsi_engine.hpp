@@ -34,6 +34,7 @@
 
 #include "dsi_engine.h"
 #include "dsi_map_eval.h"
+#include "dsi_map_components.h"
 #include "dsi_map_prune.h"
 #include "dsi_map_merge.h"
 #include "dsi_map_align.h"
@@ -1646,6 +1647,29 @@ struct MapPruneReasons {  // by ascending key when sorted
     std::vector<uint8_t> reason;  // 0 kept, 1..5 the first criterion that failed
     size_t size() const { return keys.size(); }
 };
+// connected components (dsi_map_components.h): the labelling's options -- the defaults label every cell at connectivity
+// 26 --, the selection's -- the defaults keep every labelled cell --, and what comes back
+struct MapComponentsOptions : dsx_map_components_opts_t {
+    MapComponentsOptions() : dsx_map_components_opts_t{}
+    {
+        min_points = min_windows = 1;
+        connectivity = 26;
+    }
+};
+struct MapComponentsSelection : dsx_map_components_selection_t {
+    MapComponentsSelection() : dsx_map_components_selection_t{} { min_cells = min_component_points = 1; }
+};
+using MapComponentsInfo = dsx_map_components_info_t;
+using MapComponentsSelectInfo = dsx_map_components_select_info_t;
+struct MapComponentLabels {  // one row per labelled cell, by ascending key when sorted
+    std::vector<uint64_t> keys, labels;
+    std::vector<uint8_t> reason;  // with_reasons only: 0 kept, 1..4 the first reason of the selection that holds
+    size_t size() const { return keys.size(); }
+};
+struct MapComponentList {  // one row per component, by cells descending, then label ascending
+    std::vector<uint64_t> labels, cells, points;
+    size_t size() const { return labels.size(); }
+};
 // merging and moving the state (dsi_map_merge.h): a map's exact state on the host, and what a merge counts
 struct MapState {  // by ascending key when sorted
     double leaf = 0.0;
@@ -1869,6 +1893,82 @@ public:
             out.reason.push_back(raw.reason[i]);
         }
         return out;
+    }
+
+    // labels the map's connected components (dsx_map_components; the rule is stated in dsi_map_components.h); the labelling
+    // stays on the device until the map changes, and nothing else of the map changes
+    MapComponentsInfo components(const MapComponentsOptions& opts = MapComponentsOptions())
+    {
+        MapComponentsInfo info;
+        check(dsx_map_components(h_, &opts, &info));
+        return info;
+    }
+    // (key, label) of every labelled cell from the last components() of this map, and with_reasons -- after a
+    // selectComponents on it -- the selection's reason; sort: by ascending key
+    MapComponentLabels fetchComponents(bool with_reasons = false, bool sort = true) const
+    {
+        MapComponentLabels raw;
+        size_t n = 0;
+        const int rc = dsx_map_components_fetch(h_, nullptr, nullptr, nullptr, 0, &n);
+        if (rc != DSI_OK && n == 0) check(rc);
+        raw.keys.resize(n);
+        raw.labels.resize(n);
+        if (with_reasons) raw.reason.resize(n);
+        uint8_t none = 0;  // (an empty vector's data() may be null, which would not ask for the reasons)
+        check(dsx_map_components_fetch(h_, raw.keys.data(), raw.labels.data(), with_reasons ? (n ? raw.reason.data() : &none) : nullptr, n,
+                                       &n));
+        if (!sort) return raw;
+        std::vector<size_t> order(n);
+        for (size_t i = 0; i < n; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return raw.keys[a] < raw.keys[b]; });
+        MapComponentLabels out;
+        for (size_t i : order) {
+            out.keys.push_back(raw.keys[i]);
+            out.labels.push_back(raw.labels[i]);
+            if (with_reasons) out.reason.push_back(raw.reason[i]);
+        }
+        return out;
+    }
+    // (label, cells, points) of every component from the last components() of this map, by cells descending, then label
+    // ascending
+    MapComponentList listComponents() const
+    {
+        MapComponentList raw;
+        size_t n = 0;
+        const int rc = dsx_map_components_list(h_, nullptr, nullptr, nullptr, 0, &n);
+        if (rc != DSI_OK && n == 0) check(rc);
+        raw.labels.resize(n);
+        raw.cells.resize(n);
+        raw.points.resize(n);
+        check(dsx_map_components_list(h_, raw.labels.data(), raw.cells.data(), raw.points.data(), n, &n));
+        std::vector<size_t> order(n);
+        for (size_t i = 0; i < n; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+            return raw.cells[a] != raw.cells[b] ? raw.cells[a] > raw.cells[b] : raw.labels[a] < raw.labels[b];
+        });
+        MapComponentList out;
+        for (size_t i : order) {
+            out.labels.push_back(raw.labels[i]);
+            out.cells.push_back(raw.cells[i]);
+            out.points.push_back(raw.points[i]);
+        }
+        return out;
+    }
+    // pruneComponents' dry run (dsx_map_components_select): the same counts, the map unchanged; the reasons stay on the
+    // device for fetchComponents(true) until the map changes
+    MapComponentsSelectInfo selectComponents(const MapComponentsSelection& sel = MapComponentsSelection())
+    {
+        MapComponentsSelectInfo info;
+        check(dsx_map_components_select(h_, &sel, &info));
+        return info;
+    }
+    // removes the cells that the selection rejects and rebuilds the table around the rest (dsx_map_prune_components);
+    // render, compare, alignment, classification and labelling of the map are invalid afterwards
+    MapComponentsSelectInfo pruneComponents(const MapComponentsSelection& sel = MapComponentsSelection())
+    {
+        MapComponentsSelectInfo info;
+        check(dsx_map_prune_components(h_, &sel, &info));
+        return info;
     }
 
     // appends `other` (same context, same leaf) to this map on the device (dsx_map_merge; the rule is stated in
