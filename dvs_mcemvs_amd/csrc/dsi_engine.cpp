@@ -10,6 +10,7 @@
 #include "../../include/dsi_engine.h"
 #include "../../include/dsi_map_eval.h"
 #include "../../include/dsi_map_components.h"
+#include "../../include/dsi_map_knn.h"
 #include "../../include/dsi_map_prune.h"
 #include "../../include/dsi_map_merge.h"
 #include "../../include/dsi_map_align.h"
@@ -38,6 +39,7 @@
 
 #include "dsi_host.hpp"
 #include "dsi_kernels.h"
+#include "dsi_knn_host.hpp"
 #include "dsi_owned.hpp"
 
 #pragma clang fp contract(off)
@@ -4089,11 +4091,22 @@ struct dsi_map {
     DevBuf<unsigned long long> comp_ctr, comp_top, comp_label_out, comp_cells_out, comp_points_out;
     uint32_t comp_min_points = 0, comp_min_windows = 0;
     bool comp_valid = false, comp_select_valid = false;
+    // the last self query (dsx_map_knn, include/dsi_map_knn.h): valid until the map changes; the selection
+    // (dsx_map_knn_select) is valid as long as the query it was made on
+    DevBuf<uint8_t> knn_found, knn_found_out, knn_reason, knn_reason_out;  // per slot; compacted for a fetch
+    DevBuf<uint32_t> knn_q, knn_q_out;
+    DevBuf<float> knn_mean, knn_mean_out, knn_dist_out;                    // knn_dist_out and the two below: dsx_map_knn_points' rows
+    DevBuf<unsigned long long> knn_key_out, knn_ctr;
+    DevBuf<uint8_t> knn_pt_found;
+    dsx_map_knn_opts_t knn_opts = {};
+    unsigned long long knn_moments[4] = {0, 0, 0, 0};  // N, sum_q, sum_q2 low and high
+    bool knn_valid = false, knn_select_valid = false;
 };
 
 namespace {
 
 constexpr int kMapMinLog2 = 8, kMapMaxLog2 = 27;
+static_assert(dsi::kKnnMaxCells == (uint64_t)1 << kMapMaxLog2, "the threshold's bound on N is the table's");
 constexpr int kMapViewMaxLog2 = 26, kMapMaxSplat = 4;
 
 // drops the last render's buffers: a render of another size starts from nothing instead of keeping the larger ones
@@ -4132,7 +4145,7 @@ int map_grow_for(dsi_map* mp, size_t n)
 int map_integrate_call(dsi_map* mp, size_t n, const std::function<hipError_t(uint32_t, const dsi::MapTable&)>& launch, size_t* n_accepted,
                        size_t* n_rejected)
 {
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = false;  // (the map may change from here on)
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->knn_valid = false;  // (the map may change from here on)
     REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
     REQUIRE(mp->calls < 0xffffffffull, DSI_ERR_INVALID, "at most 2^32 - 1 integrate calls per map");
     REQUIRE((mp->host_ctr[0] + n) * 4 <= ((uint64_t)3 << kMapMaxLog2), DSI_ERR_INVALID,
@@ -4236,7 +4249,7 @@ int dsi_map_destroy(dsi_map_t* mp)
 int dsi_map_reset(dsi_map_t* mp)
 {
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = false;
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->knn_valid = false;
     if (int rc = set_device(mp->ctx)) return rc;
     HIP_TRY(hipMemsetAsync(mp->block.p, 0, dsi::map_table_bytes(mp->cap_log2), mp->ctx->stream));
     HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof mp->host_ctr, mp->ctx->stream));
@@ -4674,7 +4687,7 @@ int dsx_map_prune(dsi_map_t* mp, const dsx_map_prune_opts_t* opts, dsx_map_prune
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
     REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
     if (int rc = set_device(mp->ctx)) return rc;
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = false;
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->knn_valid = false;
     hipStream_t st = mp->ctx->stream;
     unsigned long long ctr[dsi::kMapPruneCounters] = {0, 0, 0, 0, 0, 0};
     if (int rc = map_prune_classify_device(mp, opts, ctr)) return rc;
@@ -4899,7 +4912,7 @@ int dsx_map_prune_components(dsi_map_t* mp, const dsx_map_components_selection_t
             return fail(DSI_ERR_HIP, "a pruned table of 2^%u slots could not be allocated (%s): the map is unchanged", want,
                         hipGetErrorString(e));
     }
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->comp_select_valid = false;
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->comp_select_valid = mp->knn_valid = false;
     if (rebuild) {
         HIP_TRY(hipMemsetAsync(block.p, 0, dsi::map_table_bytes(want), st));
         HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof(unsigned long long), st));  // occupied: the rebuild counts the cells it moves
@@ -4915,6 +4928,259 @@ int dsx_map_prune_components(dsi_map_t* mp, const dsx_map_components_selection_t
                 kept, mp->host_ctr[3]);
     }
     map_components_select_info(mp, ctr, info);
+    return DSI_OK;
+}
+
+// ---- the map's k nearest cells (include/dsi_map_knn.h; DESIGN.md 7j "Neighbours and statistical outliers") ----
+
+namespace {
+
+// the bounds of the options that need no map: decided without a device, before any handle is looked at
+int check_knn_opts(const dsx_map_knn_opts_t* o)
+{
+    REQUIRE(o, DSI_ERR_INVALID, "opts is null");
+    REQUIRE(o->k >= 1 && o->k <= dsi::kMapKnnMaxK, DSI_ERR_INVALID, "k must be in 1..%d (got %d)", dsi::kMapKnnMaxK, o->k);
+    REQUIRE(o->min_found >= 1 && o->min_found <= o->k, DSI_ERR_INVALID, "min_found must be in 1..k = %d (got %d)", o->k, o->min_found);
+    REQUIRE(std::isfinite(o->radius) && o->radius > 0.0, DSI_ERR_INVALID, "radius must be finite and > 0 (got %g)", o->radius);
+    return DSI_OK;
+}
+
+int check_knn_selection(const dsx_map_knn_selection_t* s)
+{
+    REQUIRE(s, DSI_ERR_INVALID, "sel is null");
+    REQUIRE(std::isfinite(s->std_mult), DSI_ERR_INVALID, "std_mult must be finite (got %g)", s->std_mult);
+    REQUIRE(s->shrink == 0 || s->shrink == 1, DSI_ERR_INVALID, "shrink must be 0 or 1 (got %d)", s->shrink);
+    return DSI_OK;
+}
+
+// the kernels' view of the options; reach = ceil(radius / leaf) is judged here, with the map at hand
+int map_knn_of(const dsi_map* mp, const dsx_map_knn_opts_t* opts, dsi::MapKnn* o)
+{
+    const double reach_d = std::ceil(opts->radius / mp->leaf);
+    REQUIRE(reach_d >= 1.0 && reach_d <= (double)dsi::kMapKnnMaxReach, DSI_ERR_INVALID,
+            "reach = ceil(radius / leaf) must be in 1..%d (radius %g, leaf %g)", dsi::kMapKnnMaxReach, opts->radius, mp->leaf);
+    o->leaf = mp->leaf, o->radius = opts->radius;
+    o->min_points = opts->min_points, o->min_windows = opts->min_windows;
+    o->k = opts->k, o->min_found = opts->min_found, o->reach = (int)reach_d;
+    return DSI_OK;
+}
+
+dsi::MapKnnCells map_knn_cells_of(const dsi_map* mp) { return dsi::MapKnnCells{mp->knn_found.p, mp->knn_q.p, mp->knn_mean.p}; }
+
+// what every entry point that reads the self query asks of the map
+int check_self_query(const dsi_map* mp)
+{
+    REQUIRE(mp->knn_valid, DSI_ERR_INVALID,
+            "no self query of the map as it stands: call dsx_map_knn (after the last reset, integrate call, merge, import or prune)");
+    return DSI_OK;
+}
+
+// the threshold of the map's self query, then every cell's reason into mp->knn_reason and the counts into ctr
+// (kMapKnnSelectCounters); synchronises
+int map_knn_select_device(dsi_map* mp, const dsx_map_knn_selection_t* sel, unsigned long long* ctr, dsx_map_knn_select_info_t* thr)
+{
+    if (int rc = dsx_map_knn_threshold(mp->knn_moments[0], mp->knn_moments[1], reinterpret_cast<const uint64_t*>(&mp->knn_moments[2]),
+                                       sel->std_mult, &thr->mu, &thr->sigma, &thr->T_q))
+        return rc;
+    hipStream_t st = mp->ctx->stream;
+    HIP_TRY(mp->knn_reason.reserve((size_t)1 << mp->cap_log2));
+    dsi::MapKnn o;
+    if (int rc = map_knn_of(mp, &mp->knn_opts, &o)) return rc;
+    HIP_TRY(dsi::launch_map_knn_select(st, dsi::map_table_at(mp->block.p, mp->cap_log2), o, map_knn_cells_of(mp), sel->std_mult >= 0.0,
+                                       (uint32_t)thr->T_q, mp->knn_reason.p, mp->knn_ctr.p));
+    HIP_TRY(hipMemcpyAsync(ctr, mp->knn_ctr.p, dsi::kMapKnnSelectCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+void map_knn_select_info(const dsi_map* mp, const unsigned long long* ctr, const dsx_map_knn_select_info_t& thr, dsx_map_knn_select_info_t* info)
+{
+    if (!info) return;
+    info->n_kept = ctr[0];
+    info->n_cells = ctr[0];
+    for (int r = 0; r < 3; ++r) {
+        info->n_removed[r] = ctr[1 + r];
+        info->n_cells += ctr[1 + r];
+    }
+    info->T_q = thr.T_q, info->mu = thr.mu, info->sigma = thr.sigma;
+    info->capacity = (uint64_t)1 << mp->cap_log2;
+}
+
+}  // namespace
+
+int dsx_map_knn_points(dsi_map_t* mp, const float* xyz_host, size_t stride_floats, size_t n, const dsx_map_knn_opts_t* opts,
+                       uint64_t* keys_host, float* dist_host, uint8_t* found_host)
+{
+    if (int rc = check_knn_opts(opts)) return rc;  // (first: the bounds can be exercised with no map at hand)
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    REQUIRE(stride_floats == 3 || stride_floats == 4, DSI_ERR_INVALID, "stride_floats must be 3 or 4 (got %zu)", stride_floats);
+    REQUIRE(n == 0 || xyz_host, DSI_ERR_INVALID, "xyz_host is null");
+    REQUIRE(n <= ((size_t)1 << kMapMaxLog2), DSI_ERR_INVALID, "at most 2^%d points per call (got %zu)", kMapMaxLog2, n);
+    REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
+    dsi::MapKnn o;
+    if (int rc = map_knn_of(mp, opts, &o)) return rc;
+    if (!n) return DSI_OK;
+    if (int rc = set_device(mp->ctx)) return rc;
+    hipStream_t st = mp->ctx->stream;
+    const size_t rows = n * (size_t)o.k;
+    HIP_TRY(mp->upload.reserve(n * stride_floats));
+    if (keys_host) HIP_TRY(mp->knn_key_out.reserve(rows));
+    if (dist_host) HIP_TRY(mp->knn_dist_out.reserve(rows));
+    if (found_host) HIP_TRY(mp->knn_pt_found.reserve(n));
+    HIP_TRY(hipMemcpyAsync(mp->upload.p, xyz_host, n * stride_floats * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(dsi::launch_map_knn_points(st, dsi::map_table_at(mp->block.p, mp->cap_log2), o, mp->upload.p, (uint32_t)stride_floats, (uint32_t)n,
+                                       keys_host ? mp->knn_key_out.p : nullptr, dist_host ? mp->knn_dist_out.p : nullptr,
+                                       found_host ? mp->knn_pt_found.p : nullptr));
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "64-bit keys");
+    if (keys_host) HIP_TRY(hipMemcpyAsync(keys_host, mp->knn_key_out.p, rows * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (dist_host) HIP_TRY(hipMemcpyAsync(dist_host, mp->knn_dist_out.p, rows * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (found_host) HIP_TRY(hipMemcpyAsync(found_host, mp->knn_pt_found.p, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+int dsx_map_knn(dsi_map_t* mp, const dsx_map_knn_opts_t* opts, dsx_map_knn_info_t* info)
+{
+    if (int rc = check_knn_opts(opts)) return rc;  // (first: the bounds can be exercised with no map at hand)
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
+    dsi::MapKnn o;
+    if (int rc = map_knn_of(mp, opts, &o)) return rc;
+    if (int rc = set_device(mp->ctx)) return rc;
+    mp->knn_valid = mp->knn_select_valid = false;
+    hipStream_t st = mp->ctx->stream;
+    const size_t cap = (size_t)1 << mp->cap_log2;
+    HIP_TRY(mp->knn_found.reserve(cap));
+    HIP_TRY(mp->knn_q.reserve(cap));
+    HIP_TRY(mp->knn_mean.reserve(cap));
+    HIP_TRY(mp->knn_ctr.reserve(std::max(dsi::kMapKnnCounters, dsi::kMapKnnSelectCounters)));
+    unsigned long long ctr[dsi::kMapKnnCounters] = {0, 0, 0, 0, 0, 0, 0};
+    HIP_TRY(dsi::launch_map_knn_self(st, dsi::map_table_at(mp->block.p, mp->cap_log2), o, map_knn_cells_of(mp), mp->knn_ctr.p));
+    HIP_TRY(hipMemcpyAsync(ctr, mp->knn_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    uint64_t sum_q2[2];
+    dsi::knn_sum_q2(ctr[5], ctr[6], sum_q2);
+    mp->knn_opts = *opts;
+    mp->knn_moments[0] = ctr[2], mp->knn_moments[1] = ctr[4];
+    mp->knn_moments[2] = sum_q2[0], mp->knn_moments[3] = sum_q2[1];
+    mp->knn_valid = true;
+    if (info) {
+        info->n_cells = ctr[0];
+        info->n_unqueried = ctr[1];
+        info->n_scored = ctr[2];
+        info->n_isolated = ctr[3];
+        info->sum_q = ctr[4];
+        info->sum_q2[0] = mp->knn_moments[2], info->sum_q2[1] = mp->knn_moments[3];
+        info->reach = o.reach;
+    }
+    return DSI_OK;
+}
+
+int dsx_map_knn_threshold(uint64_t N, uint64_t sum_q, const uint64_t sum_q2[2], double std_mult, double* mu, double* sigma, uint64_t* T_q)
+{
+    REQUIRE(sum_q2, DSI_ERR_INVALID, "sum_q2 is null");
+    REQUIRE(std::isfinite(std_mult), DSI_ERR_INVALID, "std_mult must be finite (got %g)", std_mult);
+    double m = 0.0, sd = 0.0;
+    uint64_t tq = 0;
+    const dsi::KnnThresholdError e = dsi::knn_threshold_host(N, sum_q, sum_q2, std_mult, &m, &sd, &tq);
+    REQUIRE(e != dsi::kKnnTooManyCells, DSI_ERR_INVALID, "N must be at most 2^%d (got %llu)", kMapMaxLog2, (unsigned long long)N);
+    REQUIRE(e != dsi::kKnnMomentsTooLarge, DSI_ERR_INVALID, "moments too large for N = %llu cells with q <= 2^30", (unsigned long long)N);
+    REQUIRE(e != dsi::kKnnNegativeVariance, DSI_ERR_INVALID, "N * sum_q2 < sum_q^2: no set of N values has these moments");
+    if (mu) *mu = m;
+    if (sigma) *sigma = sd;
+    if (T_q) *T_q = tq;
+    return DSI_OK;
+}
+
+int dsx_map_knn_select(dsi_map_t* mp, const dsx_map_knn_selection_t* sel, dsx_map_knn_select_info_t* info)
+{
+    if (int rc = check_knn_selection(sel)) return rc;  // (first: the bounds can be exercised with no map at hand)
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    if (int rc = check_self_query(mp)) return rc;
+    if (int rc = set_device(mp->ctx)) return rc;
+    mp->knn_select_valid = false;
+    unsigned long long ctr[dsi::kMapKnnSelectCounters] = {0, 0, 0, 0};
+    dsx_map_knn_select_info_t thr = {};
+    if (int rc = map_knn_select_device(mp, sel, ctr, &thr)) return rc;
+    mp->knn_select_valid = true;
+    map_knn_select_info(mp, ctr, thr, info);
+    return DSI_OK;
+}
+
+int dsx_map_knn_fetch(dsi_map_t* mp, uint64_t* keys_host, uint8_t* found_host, float* mean_host, uint32_t* q_host, uint8_t* reasons_host,
+                      size_t capacity, size_t* count)
+{
+    REQUIRE(mp && count, DSI_ERR_INVALID, "null argument");
+    if (int rc = check_self_query(mp)) return rc;
+    REQUIRE(!reasons_host || mp->knn_select_valid, DSI_ERR_INVALID,
+            "no selection on this self query: call dsx_map_knn_select before asking for reasons");
+    if (int rc = set_device(mp->ctx)) return rc;
+    size_t total = 0;
+    if (int rc = map_count_device(mp, mp->knn_opts.min_points, mp->knn_opts.min_windows, &total)) return rc;
+    *count = total;
+    REQUIRE(capacity >= total, DSI_ERR_INVALID, "capacity of %zu cells is too small: %zu needed", capacity, total);
+    if (!total) return DSI_OK;
+    hipStream_t st = mp->ctx->stream;
+    HIP_TRY(mp->key_out.reserve(total));
+    HIP_TRY(mp->knn_found_out.reserve(total));
+    HIP_TRY(mp->knn_mean_out.reserve(total));
+    HIP_TRY(mp->knn_q_out.reserve(total));
+    if (reasons_host) HIP_TRY(mp->knn_reason_out.reserve(total));
+    HIP_TRY(dsi::launch_map_knn_gather(st, dsi::map_table_at(mp->block.p, mp->cap_log2), mp->knn_opts.min_points, mp->knn_opts.min_windows,
+                                       map_knn_cells_of(mp), reasons_host ? mp->knn_reason.p : nullptr, mp->blk.p, mp->key_out.p,
+                                       mp->knn_found_out.p, mp->knn_mean_out.p, mp->knn_q_out.p,
+                                       reasons_host ? mp->knn_reason_out.p : nullptr));
+    if (keys_host) HIP_TRY(hipMemcpyAsync(keys_host, mp->key_out.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (found_host) HIP_TRY(hipMemcpyAsync(found_host, mp->knn_found_out.p, total, hipMemcpyDeviceToHost, st));
+    if (mean_host) HIP_TRY(hipMemcpyAsync(mean_host, mp->knn_mean_out.p, total * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (q_host) HIP_TRY(hipMemcpyAsync(q_host, mp->knn_q_out.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (reasons_host) HIP_TRY(hipMemcpyAsync(reasons_host, mp->knn_reason_out.p, total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+int dsx_map_prune_knn(dsi_map_t* mp, const dsx_map_knn_selection_t* sel, dsx_map_knn_select_info_t* info)
+{
+    if (int rc = check_knn_selection(sel)) return rc;
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    if (int rc = check_self_query(mp)) return rc;
+    if (int rc = set_device(mp->ctx)) return rc;
+    hipStream_t st = mp->ctx->stream;
+    mp->knn_select_valid = false;
+    unsigned long long ctr[dsi::kMapKnnSelectCounters] = {0, 0, 0, 0};
+    dsx_map_knn_select_info_t thr = {};
+    if (int rc = map_knn_select_device(mp, sel, ctr, &thr)) return rc;
+    mp->knn_select_valid = true;  // (the reasons are those of the map as it stands, should the rebuild fail to allocate)
+    const unsigned long long kept = ctr[0];
+    uint32_t want = mp->cap_log2;
+    if (sel->shrink)
+        for (want = kMapMinLog2; kept * 4 > ((uint64_t)3 << want); ++want) {
+        }
+    DevBuf<unsigned char> block;
+    const bool rebuild = !(ctr[1] + ctr[2] + ctr[3] == 0 && want == mp->cap_log2);  // (else the table is the result already)
+    if (rebuild) {
+        const hipError_t e = block.reserve(dsi::map_table_bytes(want));
+        if (e != hipSuccess)
+            return fail(DSI_ERR_HIP, "a pruned table of 2^%u slots could not be allocated (%s): the map is unchanged", want,
+                        hipGetErrorString(e));
+    }
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->comp_select_valid = false;
+    mp->knn_valid = mp->knn_select_valid = false;
+    if (rebuild) {
+        HIP_TRY(hipMemsetAsync(block.p, 0, dsi::map_table_bytes(want), st));
+        HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof(unsigned long long), st));  // occupied: the rebuild counts the cells it moves
+        if (kept)
+            HIP_TRY(dsi::launch_map_prune_rehash(st, dsi::map_table_at(mp->block.p, mp->cap_log2), dsi::map_table_at(block.p, want),
+                                                 mp->knn_reason.p, mp->ctr.p));
+        HIP_TRY(hipMemcpyAsync(mp->host_ctr, mp->ctr.p, sizeof mp->host_ctr, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        mp->block = std::move(block);  // (frees the old table)
+        mp->cap_log2 = want;
+        REQUIRE(mp->host_ctr[3] == 0 && mp->host_ctr[0] == kept, DSI_ERR_HIP,
+                "the pruned table holds %llu of %llu kept cells (%llu found it full): an engine bug, the map is unusable", mp->host_ctr[0],
+                kept, mp->host_ctr[3]);
+    }
+    map_knn_select_info(mp, ctr, thr, info);
     return DSI_OK;
 }
 
@@ -4950,7 +5216,7 @@ int map_merge_apply(dsi_map* dst, const MapMergeSource& src, dsx_map_merge_info_
     HIP_TRY(dst->merge_ctr.reserve(dsi::kMapMergeCounters));
     const uint64_t growths_before = dst->growths;
     if (int rc = map_grow_for(dst, (size_t)src.cells)) return rc;                 // (a failed allocation leaves dst as it is)
-    dst->render_valid = dst->compare_valid = dst->prune_valid = dst->align_valid = dst->comp_valid = false;  // (the map changes from here on)
+    dst->render_valid = dst->compare_valid = dst->prune_valid = dst->align_valid = dst->comp_valid = dst->knn_valid = false;  // (the map changes from here on)
     unsigned long long mctr[dsi::kMapMergeCounters] = {0, 0};
     HIP_TRY(dsi::launch_map_merge(st, src.t, dsi::map_table_at(dst->block.p, dst->cap_log2), (uint32_t)dst->calls, src.accepted,
                                   src.rejected, dst->ctr.p, dst->merge_ctr.p));

@@ -458,6 +458,38 @@ hipError_t launch_map_components_count_roots(hipStream_t s, const MapTable& t, c
 hipError_t launch_map_components_list(hipStream_t s, const MapTable& t, const MapComponents& c, const uint32_t* blk,
                                       unsigned long long* label_out, unsigned long long* cells_out, unsigned long long* points_out);
 
+// ---- the map's k nearest cells (include/dsi_map_knn.h; DESIGN.md 7j "Neighbours and statistical outliers") ----
+constexpr int kMapKnnMaxK = 16, kMapKnnMaxReach = 3;
+constexpr int kMapKnnCounters = 7;        // queries, unqueried cells, scored, isolated, sum_q, sum q^2's low 32 bits, its rest
+constexpr int kMapKnnSelectCounters = 4;  // kept, removed by reason 1..3
+// the query; the host has checked every bound (k 1..kMapKnnMaxK, min_found 1..k, reach 1..kMapKnnMaxReach)
+struct MapKnn {
+    double leaf, radius;
+    uint32_t min_points, min_windows;
+    int k, min_found, reach;
+};
+// the self query's result, per slot (written for the cells that pass the filter)
+struct MapKnnCells {
+    uint8_t* found;
+    uint32_t* q;
+    float* mean;
+};
+// the neighbours of n points (stride floats each, x y z first): keys [n][k] (padded with 0), dist [n][k] (padded with
+// +inf), found [n]; any of the three may be NULL.  Reads the table.
+hipError_t launch_map_knn_points(hipStream_t s, const MapTable& t, const MapKnn& o, const float* pts, uint32_t stride, uint32_t n,
+                                 unsigned long long* keys, float* dist, uint8_t* found);
+// clears ctr [kMapKnnCounters], then every filtered cell of t against the others: c as above
+hipError_t launch_map_knn_self(hipStream_t s, const MapTable& t, const MapKnn& o, const MapKnnCells& c, unsigned long long* ctr);
+// clears ctr [kMapKnnSelectCounters]; reason [cap]: every slot's reason (kMapPruneEmpty without a cell) with criterion 3
+// judged against T_q when use_threshold
+hipError_t launch_map_knn_select(hipStream_t s, const MapTable& t, const MapKnn& o, const MapKnnCells& c, int use_threshold, uint32_t T_q,
+                                 uint8_t* reason, unsigned long long* ctr);
+// after launch_map_count(t, min_points, min_windows) with the query's filter: key, found, mean, q and (reason != NULL)
+// reason of every query in slot order (launch_map_extract's)
+hipError_t launch_map_knn_gather(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, const MapKnnCells& c,
+                                 const uint8_t* reason, const uint32_t* blk, unsigned long long* key_out, uint8_t* found_out,
+                                 float* mean_out, uint32_t* q_out, uint8_t* reason_out);
+
 // ---- merging maps and moving their state (include/dsi_map_merge.h; DESIGN.md 7j "Merging") ----
 constexpr int kMapImportCounters = 8;  // bad key, duplicate, n == 0, bad windows, bad stamp, S too large, table full, sum of n
 constexpr int kMapMergeCounters = 2;   // cells new to dst, cells both maps hold

@@ -7704,6 +7704,233 @@ __global__ void __launch_bounds__(kPcBlock) k_map_comp_list(uint32_t cap_log2, M
     }
 }
 
+// ---- the map's k nearest cells (include/dsi_map_knn.h dsx_map_knn*; DESIGN.md 7j "Neighbours and statistical outliers") ----
+// One thread per query.  The running top-k is a list of K (d2, key) pairs sorted ascending, K in {1, 2, 4, 8, 16} a
+// template parameter and every index into the list a compile-time constant, so that the list lives in registers (an array
+// indexed at run time would go to scratch); the runtime k is served by the next K and a truncation -- the first k of the K
+// smallest are the k smallest.  An empty place holds (+inf, all ones), which no candidate ties with: an admitted d2 is finite.
+//
+// (nd, nk) into its place: one unrolled compare-and-swap pass carries the larger of the pair and the list's entry onward,
+// and what falls off the end is dropped.  The order (d2, key) is total, so the list does not depend on the order of the calls.
+template <int K>
+__device__ inline void knn_insert(double (&d2)[K], unsigned long long (&key)[K], double nd, unsigned long long nk)
+{
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const bool before = nd < d2[j] || (nd == d2[j] && nk < key[j]);
+        const double td = d2[j];
+        const unsigned long long tk = key[j];
+        d2[j] = before ? nd : td;
+        key[j] = before ? nk : tk;
+        nd = before ? td : nd;
+        nk = before ? tk : nk;
+    }
+}
+
+// the query p against the table: per axis c = floor(p / leaf); the candidates are the cells that pass the filter at
+// c + o, |o| <= reach per axis, an index with |c + o| > kPcCellMax skipped (tested in double as k_map_compare does: a huge
+// or non-finite c has no candidates), and the cell with key `self` (0: none) left out; q = the candidate's extracted
+// centroid; d2 = ((dx dx) + dy dy) + dz dz; admitted iff sqrt(d2) <= radius.  Returns the number admitted; the list holds
+// the first K of them by (d2, key).  Every probe loop is map_find's: bounded by the capacity.
+template <int K>
+__device__ inline uint32_t knn_scan(const MapTable& t, uint32_t mask, const MapKnn& o, const double (&p)[3], unsigned long long self,
+                                    double (&d2)[K], unsigned long long (&key)[K])
+{
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        d2[j] = INFINITY;
+        key[j] = ~0ull;
+    }
+    double c[3];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) c[ax] = floor(p[ax] / o.leaf);
+    uint32_t admitted = 0;
+    for (int oz = -o.reach; oz <= o.reach; ++oz) {
+        const double vz = c[2] + (double)oz;
+        if (!(fabs(vz) <= (double)kPcCellMax)) continue;  // (NaN included)
+        for (int oy = -o.reach; oy <= o.reach; ++oy) {
+            const double vy = c[1] + (double)oy;
+            if (!(fabs(vy) <= (double)kPcCellMax)) continue;
+            for (int ox = -o.reach; ox <= o.reach; ++ox) {
+                const double vx = c[0] + (double)ox;
+                if (!(fabs(vx) <= (double)kPcCellMax)) continue;
+                const unsigned long long kb = pc_key((int)vx, (int)vy, (int)vz);
+                if (kb == self) continue;
+                const uint32_t j = map_find(t.keys, mask, kb);
+                if (j == ~0u || !map_passes(t, j, o.min_points, o.min_windows)) continue;
+                const uint32_t nb = t.n[j];
+                const double dx = p[0] - (double)map_centroid(t, j, kb, nb, 0, o.leaf);
+                const double dy = p[1] - (double)map_centroid(t, j, kb, nb, 1, o.leaf);
+                const double dz = p[2] - (double)map_centroid(t, j, kb, nb, 2, o.leaf);
+                const double dd = ((dx * dx) + dy * dy) + dz * dz;
+                if (!(sqrt(dd) <= o.radius)) continue;
+                ++admitted;
+                knn_insert<K>(d2, key, dd, kb);
+            }
+        }
+    }
+    return admitted;
+}
+
+// the neighbours of n points, walked in strides: keys / dist [n][k] in rank order, padded with 0 / +inf; found [n]
+template <int K>
+__global__ void __launch_bounds__(kPcBlock) k_map_knn_points(MapTable t, MapKnn o, const float* __restrict__ pts, uint32_t stride, uint32_t n,
+                                                             unsigned long long* __restrict__ keys, float* __restrict__ dist,
+                                                             uint8_t* __restrict__ found)
+{
+    const uint32_t mask = (1u << t.cap_log2) - 1u;
+    const size_t step = (size_t)gridDim.x * kPcBlock;
+    for (size_t i = (size_t)blockIdx.x * kPcBlock + threadIdx.x; i < (size_t)n; i += step) {
+        double p[3], d2[K];
+        unsigned long long key[K];
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) p[ax] = (double)pts[i * stride + ax];
+        const uint32_t admitted = knn_scan<K>(t, mask, o, p, 0ull, d2, key);
+        const int f = (int)min(admitted, (uint32_t)o.k);
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            if (j < o.k) {
+                const size_t at = i * (size_t)o.k + j;
+                if (keys) keys[at] = j < f ? key[j] : 0ull;
+                if (dist) dist[at] = j < f ? (float)sqrt(d2[j]) : INFINITY;
+            }
+        }
+        if (found) found[i] = (uint8_t)f;
+    }
+}
+
+// The self query: every cell that passes the filter against the others (itself left out by key), its table walked in
+// strides as k_map_compare's.  Per query found = min(k, admitted), m = (((d_1 + d_2) + ...) + d_found) / found in rank
+// order and q = (u64) floor((m / radius) * 2^30) (found == 0: m = +inf, q = 0), written per slot; scored iff
+// found >= min_found.  ctr: [0] queries, [1] occupied slots the filter leaves out, [2] scored, [3] isolated, and over the
+// scored [4] sum q, [5] sum of q^2's low 32 bits, [6] sum of q^2 >> 32 (q^2 <= 2^60 and at most 2^27 cells: neither word
+// overflows; the host puts the 128-bit sum together).  The ballots are summed in registers, the sums per thread, both
+// then in LDS, and a workgroup issues one global atomic per counter.
+template <int K>
+__global__ void __launch_bounds__(kPcBlock) k_map_knn_self(MapTable t, MapKnn o, MapKnnCells c, unsigned long long* __restrict__ ctr)
+{
+    __shared__ uint32_t s_cnt[4];
+    __shared__ unsigned long long s_sum[3];
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0u;
+    if (threadIdx.x < 3) s_sum[threadIdx.x] = 0ull;
+    __syncthreads();
+    uint32_t c_query = 0, c_other = 0, c_scored = 0, c_isolated = 0;  // (the same in every lane of a wave)
+    unsigned long long sum_q = 0ull, sq_lo = 0ull, sq_hi = 0ull;
+    const uint32_t mask = (1u << t.cap_log2) - 1u;
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        const bool occupied = map_passes(t, i, 0u, 0u), f = occupied && map_passes(t, i, o.min_points, o.min_windows);
+        bool scored = false;
+        if (f) {
+            const unsigned long long k = t.keys[i];
+            const uint32_t n = t.n[i];
+            double p[3], d2[K];
+            unsigned long long key[K];
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) p[ax] = (double)map_centroid(t, i, k, n, ax, o.leaf);
+            const uint32_t admitted = knn_scan<K>(t, mask, o, p, k, d2, key);
+            const int fnd = (int)min(admitted, (uint32_t)o.k);
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+                if (j < fnd) s = s + sqrt(d2[j]);
+            const double m = s / (double)fnd;
+            const unsigned long long q = fnd ? (unsigned long long)floor((m / o.radius) * 1073741824.0) : 0ull;
+            c.found[i] = (uint8_t)fnd;
+            c.q[i] = (uint32_t)q;
+            c.mean[i] = fnd ? (float)m : INFINITY;
+            scored = fnd >= o.min_found;
+            if (scored) {
+                const unsigned long long q2 = q * q;
+                sum_q += q;
+                sq_lo += q2 & 0xffffffffull;
+                sq_hi += q2 >> 32;
+            }
+        }
+        c_query += (uint32_t)__popcll(__ballot(f));
+        c_other += (uint32_t)__popcll(__ballot(occupied && !f));
+        c_scored += (uint32_t)__popcll(__ballot(scored));
+        c_isolated += (uint32_t)__popcll(__ballot(f && !scored));
+    }
+    if (sum_q) atomicAdd(&s_sum[0], sum_q);
+    if (sq_lo) atomicAdd(&s_sum[1], sq_lo);
+    if (sq_hi) atomicAdd(&s_sum[2], sq_hi);
+    if ((threadIdx.x & 63) == 0) {
+        if (c_query) atomicAdd(&s_cnt[0], c_query);
+        if (c_other) atomicAdd(&s_cnt[1], c_other);
+        if (c_scored) atomicAdd(&s_cnt[2], c_scored);
+        if (c_isolated) atomicAdd(&s_cnt[3], c_isolated);
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    if (threadIdx.x >= 4 && threadIdx.x < 7 && s_sum[threadIdx.x - 4]) atomicAdd(&ctr[threadIdx.x], s_sum[threadIdx.x - 4]);
+}
+
+// The selection's reason of every slot (kMapPruneEmpty without a cell), the first that holds: 1 the cell fails the
+// query's filter; 2 found < min_found; 3 use_threshold and q > T_q.  ctr[0] += kept, ctr[r] += removed by reason r.
+__global__ void __launch_bounds__(kPcBlock) k_map_knn_select(MapTable t, MapKnn o, MapKnnCells c, int use_threshold, uint32_t T_q,
+                                                             uint8_t* __restrict__ reason, unsigned long long* __restrict__ ctr)
+{
+    __shared__ uint32_t s_cnt[kMapKnnSelectCounters];
+    if (threadIdx.x < kMapKnnSelectCounters) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;  // (the same in every lane of a wave)
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        uint32_t r = kMapPruneEmpty;
+        if (map_passes(t, i, 0u, 0u)) {
+            if (!map_passes(t, i, o.min_points, o.min_windows))
+                r = 1u;
+            else if ((int)c.found[i] < o.min_found)
+                r = 2u;
+            else if (use_threshold && c.q[i] > T_q)
+                r = 3u;
+            else
+                r = 0u;
+        }
+        reason[i] = (uint8_t)r;
+        c0 += (uint32_t)__popcll(__ballot(r == 0u));
+        c1 += (uint32_t)__popcll(__ballot(r == 1u));
+        c2 += (uint32_t)__popcll(__ballot(r == 2u));
+        c3 += (uint32_t)__popcll(__ballot(r == 3u));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (c0) atomicAdd(&s_cnt[0], c0);
+        if (c1) atomicAdd(&s_cnt[1], c1);
+        if (c2) atomicAdd(&s_cnt[2], c2);
+        if (c3) atomicAdd(&s_cnt[3], c3);
+    }
+    __syncthreads();
+    if (threadIdx.x < kMapKnnSelectCounters && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
+// the self query compacted like k_map_extract's cells under the query's filter, with its blk_off (one offset per tile of
+// kPcBlock slots): key, found, mean, q and, when asked for, the selection's reason, in slot order; walked in strides
+__global__ void __launch_bounds__(kPcBlock) k_map_knn_gather(MapTable t, uint32_t min_points, uint32_t min_windows, MapKnnCells c,
+                                                             const uint8_t* __restrict__ reason, const uint32_t* __restrict__ blk_off,
+                                                             unsigned long long* __restrict__ key_out, uint8_t* __restrict__ found_out,
+                                                             float* __restrict__ mean_out, uint32_t* __restrict__ q_out,
+                                                             uint8_t* __restrict__ reason_out)
+{
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        const bool f = map_passes(t, i, min_points, min_windows);
+        uint32_t total;
+        const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);  // (every thread of the workgroup, every round)
+        if (f) {
+            const size_t at = (size_t)blk_off[base / kPcBlock] + rank;
+            key_out[at] = t.keys[i];
+            found_out[at] = c.found[i];
+            mean_out[at] = c.mean[i];
+            q_out[at] = c.q[i];
+            if (reason) reason_out[at] = reason[i];
+        }
+    }
+}
+
 // ---- merging maps and moving their state (include/dsi_map_merge.h dsx_map_export / import / merge; DESIGN.md 7j "Merging") ----
 // Every occupied slot's raw state compacted like k_map_extract's cells under the filter (0, 0), with its blk_off (one
 // offset per tile of kPcBlock slots): key, n, S[3], windows and stamp in slot order.  Walked in strides like k_map_render;
@@ -8205,6 +8432,62 @@ hipError_t launch_map_components_list(hipStream_t s, const MapTable& t, const Ma
 {
     hipLaunchKernelGGL(k_map_comp_list, dim3(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s,
                        t.cap_log2, c, blk, label_out, cells_out, points_out);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_knn_points(hipStream_t s, const MapTable& t, const MapKnn& o, const float* pts, uint32_t stride, uint32_t n,
+                                 unsigned long long* keys, float* dist, uint8_t* found)
+{
+    if (n == 0) return hipSuccess;
+    const dim3 grid(std::min(pc_blocks(n), kMapRenderMaxBlocks)), block(kPcBlock);
+    // (the instantiation is the smallest K >= k: its list's first k are the result)
+    if (o.k <= 1)
+        hipLaunchKernelGGL(k_map_knn_points<1>, grid, block, 0, s, t, o, pts, stride, n, keys, dist, found);
+    else if (o.k <= 2)
+        hipLaunchKernelGGL(k_map_knn_points<2>, grid, block, 0, s, t, o, pts, stride, n, keys, dist, found);
+    else if (o.k <= 4)
+        hipLaunchKernelGGL(k_map_knn_points<4>, grid, block, 0, s, t, o, pts, stride, n, keys, dist, found);
+    else if (o.k <= 8)
+        hipLaunchKernelGGL(k_map_knn_points<8>, grid, block, 0, s, t, o, pts, stride, n, keys, dist, found);
+    else
+        hipLaunchKernelGGL(k_map_knn_points<16>, grid, block, 0, s, t, o, pts, stride, n, keys, dist, found);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_knn_self(hipStream_t s, const MapTable& t, const MapKnn& o, const MapKnnCells& c, unsigned long long* ctr)
+{
+    const hipError_t e = hipMemsetAsync(ctr, 0, kMapKnnCounters * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    const dim3 grid(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), block(kPcBlock);
+    if (o.k <= 1)
+        hipLaunchKernelGGL(k_map_knn_self<1>, grid, block, 0, s, t, o, c, ctr);
+    else if (o.k <= 2)
+        hipLaunchKernelGGL(k_map_knn_self<2>, grid, block, 0, s, t, o, c, ctr);
+    else if (o.k <= 4)
+        hipLaunchKernelGGL(k_map_knn_self<4>, grid, block, 0, s, t, o, c, ctr);
+    else if (o.k <= 8)
+        hipLaunchKernelGGL(k_map_knn_self<8>, grid, block, 0, s, t, o, c, ctr);
+    else
+        hipLaunchKernelGGL(k_map_knn_self<16>, grid, block, 0, s, t, o, c, ctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_knn_select(hipStream_t s, const MapTable& t, const MapKnn& o, const MapKnnCells& c, int use_threshold, uint32_t T_q,
+                                 uint8_t* reason, unsigned long long* ctr)
+{
+    const hipError_t e = hipMemsetAsync(ctr, 0, kMapKnnSelectCounters * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_map_knn_select, dim3(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s, t, o,
+                       c, use_threshold, T_q, reason, ctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_knn_gather(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, const MapKnnCells& c,
+                                 const uint8_t* reason, const uint32_t* blk, unsigned long long* key_out, uint8_t* found_out,
+                                 float* mean_out, uint32_t* q_out, uint8_t* reason_out)
+{
+    hipLaunchKernelGGL(k_map_knn_gather, dim3(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s, t,
+                       min_points, min_windows, c, reason, blk, key_out, found_out, mean_out, q_out, reason_out);
     return hipExtGetLastError();
 }
 

@@ -118,6 +118,25 @@ class _MapComponentsSelectInfo(C.Structure):
                 ("capacity", C.c_uint64)]
 
 
+class _MapKnnOpts(C.Structure):
+    _fields_ = [("min_points", C.c_uint32), ("min_windows", C.c_uint32), ("k", C.c_int32), ("min_found", C.c_int32),
+                ("radius", C.c_double)]
+
+
+class _MapKnnInfo(C.Structure):
+    _fields_ = [("n_cells", C.c_uint64), ("n_unqueried", C.c_uint64), ("n_scored", C.c_uint64), ("n_isolated", C.c_uint64),
+                ("sum_q", C.c_uint64), ("sum_q2", C.c_uint64 * 2), ("reach", C.c_int32)]
+
+
+class _MapKnnSelection(C.Structure):
+    _fields_ = [("std_mult", C.c_double), ("shrink", C.c_int32)]
+
+
+class _MapKnnSelectInfo(C.Structure):
+    _fields_ = [("n_cells", C.c_uint64), ("n_kept", C.c_uint64), ("n_removed", C.c_uint64 * 3), ("T_q", C.c_uint64),
+                ("mu", C.c_double), ("sigma", C.c_double), ("capacity", C.c_uint64)]
+
+
 class _MapState(C.Structure):
     _fields_ = [("leaf", C.c_double), ("n_cells", C.c_uint64), ("calls", C.c_uint64), ("accepted", C.c_uint64),
                 ("rejected", C.c_uint64)]
@@ -417,6 +436,13 @@ def load_library():
         "dsx_map_components_list": (C.c_int, [vp, u64p, u64p, u64p, C.c_size_t, szp]),
         "dsx_map_components_select": (C.c_int, [vp, C.POINTER(_MapComponentsSelection), C.POINTER(_MapComponentsSelectInfo)]),
         "dsx_map_prune_components": (C.c_int, [vp, C.POINTER(_MapComponentsSelection), C.POINTER(_MapComponentsSelectInfo)]),
+        # include/dsi_map_knn.h: the map's k nearest cells and its statistical outliers
+        "dsx_map_knn_points": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, C.POINTER(_MapKnnOpts), u64p, f32p, u8p]),
+        "dsx_map_knn": (C.c_int, [vp, C.POINTER(_MapKnnOpts), C.POINTER(_MapKnnInfo)]),
+        "dsx_map_knn_threshold": (C.c_int, [C.c_uint64, C.c_uint64, u64p, C.c_double, f64p, f64p, u64p]),
+        "dsx_map_knn_select": (C.c_int, [vp, C.POINTER(_MapKnnSelection), C.POINTER(_MapKnnSelectInfo)]),
+        "dsx_map_knn_fetch": (C.c_int, [vp, u64p, u8p, f32p, u32p, u8p, C.c_size_t, szp]),
+        "dsx_map_prune_knn": (C.c_int, [vp, C.POINTER(_MapKnnSelection), C.POINTER(_MapKnnSelectInfo)]),
         # include/dsi_map_merge.h: merging maps, exporting and importing their state
         "dsx_map_export": (C.c_int, [vp, C.POINTER(_MapState), u64p, u32p, u64p, u32p, u32p, C.c_size_t, szp]),
         "dsx_map_import": (C.c_int, [vp, C.POINTER(_MapState), u64p, u32p, u64p, u32p, u32p, C.POINTER(_MapMergeInfo)]),
@@ -1412,6 +1438,80 @@ class WorldMap:
         return {"n_cells": int(i.n_cells), "n_kept": int(i.n_kept), "n_removed": [int(v) for v in i.n_removed],
                 "n_components_kept": int(i.n_components_kept), "capacity": int(i.capacity)}
 
+    def query(self, points, k, radius, min_points=1, min_windows=1):
+        """The k nearest cells of every point (dsx_map_knn_points; the rule is stated in dsi_map_knn.h and DESIGN.md 7j
+        "Neighbours and statistical outliers"): points (N, 3) or (N, 4) float32, x y z first; the candidates are the cells
+        extract(min_points, min_windows) returns, within radius (at most three leaves) of the point, ordered by distance,
+        then by key.  Returns dict of keys (N, k) uint64 padded with 0, dist (N, k) float32 padded with +inf and found
+        (N,) uint8.  A non-finite point has found 0.  Reads the map only."""
+        pts = _arr(points, np.float32)
+        if pts.ndim != 2 or pts.shape[1] not in (3, 4):
+            raise ValueError("points must be (N, 3) or (N, 4)")
+        o = _MapKnnOpts(int(min_points), int(min_windows), int(k), 1, float(radius))
+        n, kk = pts.shape[0], max(int(k), 0)
+        out = {"keys": np.zeros((n, kk), np.uint64), "dist": np.full((n, kk), np.inf, np.float32), "found": np.zeros(n, np.uint8)}
+        _check(load_library().dsx_map_knn_points(self._h, _ptr(pts, C.c_float), pts.shape[1], n, C.byref(o), _ptr(out["keys"], C.c_uint64),
+                                                 _ptr(out["dist"], C.c_float), _ptr(out["found"], C.c_uint8)))
+        return out
+
+    def knn(self, k, radius, min_found=1, min_points=1, min_windows=1):
+        """The self query (dsx_map_knn): every cell extract(min_points, min_windows) returns asks for its k nearest other
+        cells within radius, from its own centroid; per cell found, the mean distance m and q = floor(m / radius * 2**30)
+        stay on the device for fetchKnn, selectOutliers and pruneOutliers until the map changes.  A cell is scored when
+        found >= min_found.  Returns dict of n_cells, n_unqueried, n_scored, n_isolated, sum_q, sum_q2 (a Python int, the
+        exact sum of q * q over the scored cells) and reach.  Nothing else of the map changes."""
+        o = _MapKnnOpts(int(min_points), int(min_windows), int(k), int(min_found), float(radius))
+        i = _MapKnnInfo()
+        _check(load_library().dsx_map_knn(self._h, C.byref(o), C.byref(i)))
+        self._knn_selected = False
+        out = {f: int(getattr(i, f)) for f in ("n_cells", "n_unqueried", "n_scored", "n_isolated", "sum_q", "reach")}
+        out["sum_q2"] = int(i.sum_q2[0]) | (int(i.sum_q2[1]) << 64)
+        return out
+
+    def fetchKnn(self, sort=True):
+        """keys (uint64), found (uint8), mean (float32, +inf where found is 0) and q (uint32) of every query of the last
+        knn() of this map and, after a selectOutliers() on it, reason (uint8: 0 kept, 1..3 the first reason that holds)
+        (dsx_map_knn_fetch); raises DsiError when the map changed since.  sort=True orders them by ascending key; otherwise
+        the order is extract(sort=False)'s under the query's filter."""
+        L = load_library()
+        n = C.c_size_t()
+        rc = L.dsx_map_knn_fetch(self._h, None, None, None, None, None, 0, C.byref(n))
+        if rc != OK and n.value == 0:
+            _check(rc)
+        m = n.value
+        out = {"keys": np.empty(m, np.uint64), "found": np.empty(m, np.uint8), "mean": np.empty(m, np.float32), "q": np.empty(m, np.uint32)}
+        if getattr(self, "_knn_selected", False):
+            out["reason"] = np.empty(m, np.uint8)
+        _check(L.dsx_map_knn_fetch(self._h, _ptr(out["keys"], C.c_uint64), _ptr(out["found"], C.c_uint8), _ptr(out["mean"], C.c_float),
+                                   _ptr(out["q"], C.c_uint32), _ptr(out["reason"], C.c_uint8) if "reason" in out else None, m, C.byref(n)))
+        if sort:
+            order = np.argsort(out["keys"], kind="stable")
+            out = {f: v[order] for f, v in out.items()}
+        return out
+
+    def selectOutliers(self, std_mult=1.0, shrink=False):
+        """pruneOutliers()'s dry run (dsx_map_knn_select): the same counts, the map unchanged; the per-cell reasons stay on
+        the device for fetchKnn until the map changes."""
+        return self._select_outliers(load_library().dsx_map_knn_select, std_mult, shrink)
+
+    def pruneOutliers(self, std_mult=1.0, shrink=False):
+        """PCL's StatisticalOutlierRemoval on the last knn() of this map (dsx_map_prune_knn): a cell leaves by the first
+        reason that holds -- it fails the query's filter; it is isolated (found < min_found); std_mult >= 0 and its q lies
+        above T_q = floor(mu + std_mult * sigma), mu and sigma the mean and the sample deviation of q over the scored cells
+        (knn_threshold) -- and the table is rebuilt around the rest, shrink as prune()'s.  Returns dict of n_cells = n_kept +
+        sum(n_removed), n_kept, n_removed (three counts, by reason), T_q, mu, sigma and capacity (slots afterwards).
+        Render, compare, alignment, classification, labelling and self query are invalid afterwards."""
+        return self._select_outliers(load_library().dsx_map_prune_knn, std_mult, shrink)
+
+    def _select_outliers(self, fn, std_mult, shrink):
+        s = _MapKnnSelection(float(std_mult), 1 if shrink else 0)
+        i = _MapKnnSelectInfo()
+        self._knn_selected = False
+        _check(fn(self._h, C.byref(s), C.byref(i)))
+        self._knn_selected = True
+        return {"n_cells": int(i.n_cells), "n_kept": int(i.n_kept), "n_removed": [int(v) for v in i.n_removed], "T_q": int(i.T_q),
+                "mu": float(i.mu), "sigma": float(i.sigma), "capacity": int(i.capacity)}
+
     def exportState(self, sort=True):
         """The map's exact state (dsx_map_export; the rule is stated in dsi_map_merge.h and DESIGN.md 7j "Merging"): dict
         of leaf, calls, accepted, rejected and, per cell, keys (uint64), n (uint32), S (uint64, (M, 3): the sums of the
@@ -1612,6 +1712,21 @@ def solve_alignment(moments):
     _check(load_library().dsx_map_align_solve(C.byref(m), _ptr(T, C.c_double), C.byref(i)))
     return T, {"n_matched": int(i.n_matched), "rms": float(i.rms), "angle": float(i.angle), "trans": float(i.trans),
                "lambda": [float(v) for v in i.lambda_]}
+
+
+def knn_threshold(n_scored, sum_q, sum_q2, std_mult):
+    """The outlier threshold from WorldMap.knn's moments alone (dsx_map_knn_threshold, the routine dsi::knn_threshold and
+    the selection call too; stated in dsi_map_knn.h; no device is touched): V = N sum_q2 - sum_q**2 exactly, mu = sum_q / N,
+    sigma = sqrt(V / (N (N - 1))), T_q = floor(mu + std_mult * sigma) clamped to [0, 2**30]; N = 0 gives 2**30.  sum_q2 is
+    a Python int below 2**128.  Returns dict of mu, sigma and T_q."""
+    s2 = int(sum_q2)
+    if not 0 <= s2 < 1 << 128:
+        raise ValueError("sum_q2 must be in 0..2**128 - 1")
+    words = (C.c_uint64 * 2)(s2 & 0xffffffffffffffff, s2 >> 64)
+    mu, sigma, tq = C.c_double(), C.c_double(), C.c_uint64()
+    _check(load_library().dsx_map_knn_threshold(int(n_scored), int(sum_q), words, float(std_mult), C.byref(mu), C.byref(sigma),
+                                                C.byref(tq)))
+    return {"mu": mu.value, "sigma": sigma.value, "T_q": int(tq.value)}
 
 
 def map_f_score(est, gt, radius, n_bins=16, min_points=1, min_windows=1, min_points_gt=1, min_windows_gt=1):

@@ -747,7 +747,7 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
                   out_skip, fusion_method=E.FUSE_HM, forward_looking=True, rv_pos=0.0, options_depth_map=None,
                   options_point_cloud=None, polarities=None, save_images=False, out_path=None, lut=None, score=None,
                   ground_truth=None, ground_truth_disparity=None, thicken_edges=False, world_map=None, world_map_prune=None,
-                  world_map_components=None, **kw):
+                  world_map_components=None, world_map_outliers=None, **kw):
     """Generator over the windows of main.cpp:177-302: yields (ts, depth, confidence, indices) per
     window, pipelined one window deep; with options_depth_map, (ts, depth_map, confidence_map, mask)
     -- the filtered outputs the reference saves per window; with options_point_cloud as well, the window's
@@ -796,7 +796,27 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
     shrink) plus `every` (default 1): after every every-th window, right after that window's cloud went in -- and after
     world_map_prune's prune, when both fall on the window --, the map is labelled and pruned by component.  Such a window's
     result gains a last element, {"world_map_components": the counts of WorldMap.components, and under "prune" those of
-    WorldMap.pruneComponents}."""
+    WorldMap.pruneComponents}.
+    world_map_outliers= (with world_map=; None leaves the stream as it is): a dict of the keywords of WorldMap.knn (k, radius,
+    min_found, min_points, min_windows) and of WorldMap.pruneOutliers (std_mult, shrink) plus `every` (default 1): after
+    every every-th window, after world_map_prune's and world_map_components' work on that window, the map queries itself
+    and loses its isolated cells and statistical outliers.  Such a window's result gains a last element,
+    {"world_map_outliers": the counts of WorldMap.knn, and under "prune" those of WorldMap.pruneOutliers}."""
+    outl = None
+    if world_map_outliers is not None:
+        if world_map is None:
+            raise ValueError("world_map_outliers needs world_map")
+        outl = dict(world_map_outliers)
+        every = outl.pop("every", 1)
+        if int(every) != every or every < 1:
+            raise ValueError("world_map_outliers['every'] must be an integer >= 1")
+        knn_keys, select_keys = {"k", "radius", "min_found", "min_points", "min_windows"}, {"std_mult", "shrink"}
+        unknown = set(outl) - knn_keys - select_keys
+        if unknown:
+            raise ValueError("world_map_outliers: unknown keys %s" % sorted(unknown))
+        if "k" not in outl or "radius" not in outl:
+            raise ValueError("world_map_outliers needs k and radius")
+        outl = ({k: v for k, v in outl.items() if k in knn_keys}, {k: v for k, v in outl.items() if k in select_keys}, int(every))
     comps = None
     if world_map_components is not None:
         if world_map is None:
@@ -874,6 +894,10 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
             counts = world_map.components(**comps[0])
             counts["prune"] = world_map.pruneComponents(**comps[1])
             out = out + ({"world_map_components": counts},)
+        if outl is not None and windows_seen % outl[2] == 0:
+            counts = world_map.knn(**outl[0])
+            counts["prune"] = world_map.pruneOutliers(**outl[1])
+            out = out + ({"world_map_outliers": counts},)
         return out
 
     try:

@@ -24,6 +24,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -35,6 +36,7 @@
 #include "dsi_engine.h"
 #include "dsi_map_eval.h"
 #include "dsi_map_components.h"
+#include "dsi_map_knn.h"
 #include "dsi_map_prune.h"
 #include "dsi_map_merge.h"
 #include "dsi_map_align.h"
@@ -1670,6 +1672,48 @@ struct MapComponentList {  // one row per component, by cells descending, then l
     std::vector<uint64_t> labels, cells, points;
     size_t size() const { return labels.size(); }
 };
+// the k nearest cells and the statistical outliers (dsi_map_knn.h): the query's options -- the defaults ask every cell for
+// its 8 nearest and score a cell that found one --, the selection's -- one deviation above the mean --, and what comes back
+struct MapKnnOptions : dsx_map_knn_opts_t {
+    explicit MapKnnOptions(double radius_, int k_ = 8) : dsx_map_knn_opts_t{}
+    {
+        min_points = min_windows = 1;
+        k = k_;
+        min_found = 1;
+        radius = radius_;
+    }
+};
+struct MapKnnSelection : dsx_map_knn_selection_t {
+    explicit MapKnnSelection(double std_mult_ = 1.0, bool shrink_ = false) : dsx_map_knn_selection_t{}
+    {
+        std_mult = std_mult_;
+        shrink = shrink_ ? 1 : 0;
+    }
+};
+using MapKnnInfo = dsx_map_knn_info_t;
+using MapKnnSelectInfo = dsx_map_knn_select_info_t;
+struct MapNeighbours {  // one row of k per query point: keys padded with 0, dist with +inf
+    int k = 0;
+    std::vector<uint64_t> keys;
+    std::vector<float> dist;
+    std::vector<uint8_t> found;
+    size_t size() const { return found.size(); }
+};
+struct MapKnnThreshold {
+    double mu = 0.0, sigma = 0.0;
+    uint64_t T_q = 0;
+};
+// the outlier threshold of a self query's moments (dsx_map_knn_threshold; no device is touched)
+inline MapKnnThreshold knn_threshold(uint64_t n_scored, uint64_t sum_q, const uint64_t sum_q2[2], double std_mult)
+{
+    MapKnnThreshold t;
+    check(dsx_map_knn_threshold(n_scored, sum_q, sum_q2, std_mult, &t.mu, &t.sigma, &t.T_q));
+    return t;
+}
+inline MapKnnThreshold knn_threshold(const MapKnnInfo& info, double std_mult)
+{
+    return knn_threshold(info.n_scored, info.sum_q, info.sum_q2, std_mult);
+}
 // merging and moving the state (dsi_map_merge.h): a map's exact state on the host, and what a merge counts
 struct MapState {  // by ascending key when sorted
     double leaf = 0.0;
@@ -1968,6 +2012,36 @@ public:
     {
         MapComponentsSelectInfo info;
         check(dsx_map_prune_components(h_, &sel, &info));
+        return info;
+    }
+
+    // the k nearest cells of n host points, stride 3 or 4 floats (dsx_map_knn_points; the rule is stated in dsi_map_knn.h);
+    // reads the map only
+    MapNeighbours query(const float* xyz, size_t stride_floats, size_t n, const MapKnnOptions& opts) const
+    {
+        MapNeighbours out;
+        out.k = opts.k;
+        const size_t rows = opts.k > 0 ? n * (size_t)opts.k : 0;
+        out.keys.assign(rows, 0);
+        out.dist.assign(rows, std::numeric_limits<float>::infinity());
+        out.found.assign(n, 0);
+        check(dsx_map_knn_points(h_, xyz, stride_floats, n, &opts, out.keys.data(), out.dist.data(), out.found.data()));
+        return out;
+    }
+    // the self query (dsx_map_knn): every cell asks for its k nearest other cells; the result stays on the device for
+    // pruneOutliers until the map changes, and nothing else of the map changes
+    MapKnnInfo knn(const MapKnnOptions& opts)
+    {
+        MapKnnInfo info;
+        check(dsx_map_knn(h_, &opts, &info));
+        return info;
+    }
+    // removes the isolated cells and the statistical outliers of the last knn() and rebuilds the table around the rest
+    // (dsx_map_prune_knn); everything derived from the map is invalid afterwards
+    MapKnnSelectInfo pruneOutliers(const MapKnnSelection& sel = MapKnnSelection())
+    {
+        MapKnnSelectInfo info;
+        check(dsx_map_prune_knn(h_, &sel, &info));
         return info;
     }
 
