@@ -15,10 +15,11 @@ OUT = os.path.join(HERE, "libdsi_engine.so")
 # DSIs on purpose) is a DIFFERENT file, loaded only by an explicit opt-in (engine.load_library: DSI_ENGINE_EXPERIMENTS=1)
 OUT_EXPERIMENTS = os.path.join(HERE, "libdsi_engine_experiments.so")
 SOURCES = ["dsi_kernels.hip", "dsi_engine.cpp"]
-HEADERS = ["dsi_kernels.h", "dsi_vote_asm.h", "dsi_host.hpp", "dsi_owned.hpp", "dsi_knn_host.hpp", os.path.join("..", "..", "include", "dsi_engine.h"),
+HEADERS = ["dsi_kernels.h", "dsi_vote_asm.h", "dsi_host.hpp", "dsi_owned.hpp", "dsi_knn_host.hpp", "dsi_pca_host.hpp", os.path.join("..", "..", "include", "dsi_engine.h"),
            os.path.join("..", "..", "include", "dsi_map_eval.h"), os.path.join("..", "..", "include", "dsi_map_prune.h"),
            os.path.join("..", "..", "include", "dsi_map_merge.h"), os.path.join("..", "..", "include", "dsi_map_align.h"),
-           os.path.join("..", "..", "include", "dsi_map_components.h"), os.path.join("..", "..", "include", "dsi_map_knn.h")]
+           os.path.join("..", "..", "include", "dsi_map_components.h"), os.path.join("..", "..", "include", "dsi_map_knn.h"),
+           os.path.join("..", "..", "include", "dsi_map_pca.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
          "-fvisibility=hidden", "-Wall", "-Wextra", "-Wno-unused-parameter", "-x", "hip"]
 

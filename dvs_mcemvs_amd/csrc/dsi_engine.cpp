@@ -11,6 +11,7 @@
 #include "../../include/dsi_map_eval.h"
 #include "../../include/dsi_map_components.h"
 #include "../../include/dsi_map_knn.h"
+#include "../../include/dsi_map_pca.h"
 #include "../../include/dsi_map_prune.h"
 #include "../../include/dsi_map_merge.h"
 #include "../../include/dsi_map_align.h"
@@ -41,6 +42,7 @@
 #include "dsi_kernels.h"
 #include "dsi_knn_host.hpp"
 #include "dsi_owned.hpp"
+#include "dsi_pca_host.hpp"
 
 #pragma clang fp contract(off)
 
@@ -4101,6 +4103,15 @@ struct dsi_map {
     dsx_map_knn_opts_t knn_opts = {};
     unsigned long long knn_moments[4] = {0, 0, 0, 0};  // N, sum_q, sum_q2 low and high
     bool knn_valid = false, knn_select_valid = false;
+    // the last local-shape pass (dsx_map_pca, include/dsi_map_pca.h): valid until the map changes; the selection
+    // (dsx_map_pca_select) is valid as long as the pass it was made on
+    DevBuf<float> pca_normal, pca_tangent, pca_eval, pca_normal_out, pca_tangent_out, pca_eval_out;  // per slot; compacted for a fetch
+    DevBuf<uint16_t> pca_members, pca_members_out;
+    DevBuf<uint8_t> pca_label, pca_flags, pca_reason, pca_label_out, pca_flags_out, pca_reason_out;
+    DevBuf<long long> pca_moments, pca_moments_out;  // with keep_moments only
+    DevBuf<unsigned long long> pca_ctr;
+    dsx_map_pca_opts_t pca_opts = {};
+    bool pca_valid = false, pca_select_valid = false;
 };
 
 namespace {
@@ -4145,7 +4156,7 @@ int map_grow_for(dsi_map* mp, size_t n)
 int map_integrate_call(dsi_map* mp, size_t n, const std::function<hipError_t(uint32_t, const dsi::MapTable&)>& launch, size_t* n_accepted,
                        size_t* n_rejected)
 {
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->knn_valid = false;  // (the map may change from here on)
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->knn_valid = mp->pca_valid = false;  // (the map may change from here on)
     REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
     REQUIRE(mp->calls < 0xffffffffull, DSI_ERR_INVALID, "at most 2^32 - 1 integrate calls per map");
     REQUIRE((mp->host_ctr[0] + n) * 4 <= ((uint64_t)3 << kMapMaxLog2), DSI_ERR_INVALID,
@@ -4249,7 +4260,7 @@ int dsi_map_destroy(dsi_map_t* mp)
 int dsi_map_reset(dsi_map_t* mp)
 {
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->knn_valid = false;
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->knn_valid = mp->pca_valid = false;
     if (int rc = set_device(mp->ctx)) return rc;
     HIP_TRY(hipMemsetAsync(mp->block.p, 0, dsi::map_table_bytes(mp->cap_log2), mp->ctx->stream));
     HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof mp->host_ctr, mp->ctx->stream));
@@ -4687,7 +4698,7 @@ int dsx_map_prune(dsi_map_t* mp, const dsx_map_prune_opts_t* opts, dsx_map_prune
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
     REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
     if (int rc = set_device(mp->ctx)) return rc;
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->knn_valid = false;
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->knn_valid = mp->pca_valid = false;
     hipStream_t st = mp->ctx->stream;
     unsigned long long ctr[dsi::kMapPruneCounters] = {0, 0, 0, 0, 0, 0};
     if (int rc = map_prune_classify_device(mp, opts, ctr)) return rc;
@@ -4912,7 +4923,7 @@ int dsx_map_prune_components(dsi_map_t* mp, const dsx_map_components_selection_t
             return fail(DSI_ERR_HIP, "a pruned table of 2^%u slots could not be allocated (%s): the map is unchanged", want,
                         hipGetErrorString(e));
     }
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->comp_select_valid = mp->knn_valid = false;
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->comp_select_valid = mp->knn_valid = mp->pca_valid = false;
     if (rebuild) {
         HIP_TRY(hipMemsetAsync(block.p, 0, dsi::map_table_bytes(want), st));
         HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof(unsigned long long), st));  // occupied: the rebuild counts the cells it moves
@@ -5165,7 +5176,7 @@ int dsx_map_prune_knn(dsi_map_t* mp, const dsx_map_knn_selection_t* sel, dsx_map
                         hipGetErrorString(e));
     }
     mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->comp_select_valid = false;
-    mp->knn_valid = mp->knn_select_valid = false;
+    mp->knn_valid = mp->knn_select_valid = mp->pca_valid = false;
     if (rebuild) {
         HIP_TRY(hipMemsetAsync(block.p, 0, dsi::map_table_bytes(want), st));
         HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof(unsigned long long), st));  // occupied: the rebuild counts the cells it moves
@@ -5181,6 +5192,251 @@ int dsx_map_prune_knn(dsi_map_t* mp, const dsx_map_knn_selection_t* sel, dsx_map
                 kept, mp->host_ctr[3]);
     }
     map_knn_select_info(mp, ctr, thr, info);
+    return DSI_OK;
+}
+
+// ---- the map's local shape (include/dsi_map_pca.h; DESIGN.md 7j "Local shape") ----
+
+namespace {
+
+constexpr int kMapPcaMaxFound = 342;  // (2 * kMapKnnMaxReach + 1)^3 - 1
+static_assert(dsi::kPcaMaxMembers == (uint32_t)kMapPcaMaxFound + 1, "the solver's bound on m is the largest neighbourhood's");
+
+// the bounds of the options that need no map: decided without a device, before any handle is looked at
+int check_pca_opts(const dsx_map_pca_opts_t* o)
+{
+    REQUIRE(o, DSI_ERR_INVALID, "opts is null");
+    REQUIRE(o->k >= 0 && o->k <= dsi::kMapKnnMaxK, DSI_ERR_INVALID, "k must be in 0..%d (got %d)", dsi::kMapKnnMaxK, o->k);
+    const int top = o->k == 0 ? kMapPcaMaxFound : std::max(o->k, 2);
+    REQUIRE(o->min_found >= 2 && o->min_found <= top, DSI_ERR_INVALID, "min_found must be in 2..%d for k = %d (got %d)", top, o->k,
+            o->min_found);
+    REQUIRE(std::isfinite(o->radius) && o->radius > 0.0, DSI_ERR_INVALID, "radius must be finite and > 0 (got %g)", o->radius);
+    REQUIRE(o->orient == 0 || o->orient == 1, DSI_ERR_INVALID, "orient must be 0 or 1 (got %d)", o->orient);
+    REQUIRE(o->keep_moments == 0 || o->keep_moments == 1, DSI_ERR_INVALID, "keep_moments must be 0 or 1 (got %d)", o->keep_moments);
+    REQUIRE(std::isfinite(o->viewpoint[0]) && std::isfinite(o->viewpoint[1]) && std::isfinite(o->viewpoint[2]), DSI_ERR_INVALID,
+            "viewpoint must be finite (got %g %g %g)", o->viewpoint[0], o->viewpoint[1], o->viewpoint[2]);
+    return DSI_OK;
+}
+
+int check_pca_selection(const dsx_map_pca_selection_t* s)
+{
+    REQUIRE(s, DSI_ERR_INVALID, "sel is null");
+    REQUIRE(s->keep_labels >= 1u && s->keep_labels <= 7u, DSI_ERR_INVALID, "keep_labels must be a non-zero mask over the labels 1..3 (got %u)",
+            s->keep_labels);
+    REQUIRE(s->remove_sparse == 0 || s->remove_sparse == 1, DSI_ERR_INVALID, "remove_sparse must be 0 or 1 (got %d)", s->remove_sparse);
+    REQUIRE(s->shrink == 0 || s->shrink == 1, DSI_ERR_INVALID, "shrink must be 0 or 1 (got %d)", s->shrink);
+    return DSI_OK;
+}
+
+dsi::MapPcaCells map_pca_cells_of(const dsi_map* mp)
+{
+    return dsi::MapPcaCells{mp->pca_normal.p, mp->pca_tangent.p, mp->pca_eval.p, mp->pca_members.p,
+                            mp->pca_label.p,  mp->pca_flags.p,   mp->pca_opts.keep_moments ? mp->pca_moments.p : nullptr};
+}
+
+// what every entry point that reads the pass asks of the map
+int check_pca_pass(const dsi_map* mp)
+{
+    REQUIRE(mp->pca_valid, DSI_ERR_INVALID,
+            "no local-shape pass of the map as it stands: call dsx_map_pca (after the last reset, integrate call, merge, import or prune)");
+    return DSI_OK;
+}
+
+// every cell's reason into mp->pca_reason and the counts into ctr (kMapPcaSelectCounters); synchronises
+int map_pca_select_device(dsi_map* mp, const dsx_map_pca_selection_t* sel, unsigned long long* ctr)
+{
+    hipStream_t st = mp->ctx->stream;
+    HIP_TRY(mp->pca_reason.reserve((size_t)1 << mp->cap_log2));
+    HIP_TRY(dsi::launch_map_pca_select(st, dsi::map_table_at(mp->block.p, mp->cap_log2), mp->pca_opts.min_points, mp->pca_opts.min_windows,
+                                       mp->pca_label.p, sel->keep_labels, sel->remove_sparse, mp->pca_reason.p, mp->pca_ctr.p));
+    HIP_TRY(hipMemcpyAsync(ctr, mp->pca_ctr.p, dsi::kMapPcaSelectCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+void map_pca_select_info(const dsi_map* mp, const unsigned long long* ctr, dsx_map_pca_select_info_t* info)
+{
+    if (!info) return;
+    info->n_kept = ctr[0];
+    info->n_cells = ctr[0];
+    for (int r = 0; r < 3; ++r) {
+        info->n_removed[r] = ctr[1 + r];
+        info->n_cells += ctr[1 + r];
+    }
+    info->capacity = (uint64_t)1 << mp->cap_log2;
+}
+
+}  // namespace
+
+int dsx_map_pca(dsi_map_t* mp, const dsx_map_pca_opts_t* opts, dsx_map_pca_info_t* info)
+{
+    if (int rc = check_pca_opts(opts)) return rc;  // (first: the bounds can be exercised with no map at hand)
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
+    dsi::MapPca o;
+    {
+        dsx_map_knn_opts_t q = {};
+        q.min_points = opts->min_points, q.min_windows = opts->min_windows;
+        q.k = opts->k, q.min_found = opts->min_found, q.radius = opts->radius;
+        if (int rc = map_knn_of(mp, &q, &o.q)) return rc;
+    }
+    o.quantum = mp->leaf * dsi::kPcaQuantumPerLeaf;
+    for (int a = 0; a < 3; ++a) o.viewpoint[a] = opts->viewpoint[a];
+    o.orient = opts->orient;
+    if (int rc = set_device(mp->ctx)) return rc;
+    mp->pca_valid = mp->pca_select_valid = false;
+    hipStream_t st = mp->ctx->stream;
+    const size_t cap = (size_t)1 << mp->cap_log2;
+    HIP_TRY(mp->pca_normal.reserve(3 * cap));
+    HIP_TRY(mp->pca_tangent.reserve(3 * cap));
+    HIP_TRY(mp->pca_eval.reserve(3 * cap));
+    HIP_TRY(mp->pca_members.reserve(cap));
+    HIP_TRY(mp->pca_label.reserve(cap));
+    HIP_TRY(mp->pca_flags.reserve(cap));
+    if (opts->keep_moments) HIP_TRY(mp->pca_moments.reserve(9 * cap));
+    HIP_TRY(mp->pca_ctr.reserve(std::max(dsi::kMapPcaCounters, dsi::kMapPcaSelectCounters)));
+    mp->pca_opts = *opts;
+    unsigned long long ctr[dsi::kMapPcaCounters] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    HIP_TRY(dsi::launch_map_pca(st, dsi::map_table_at(mp->block.p, mp->cap_log2), o, map_pca_cells_of(mp), mp->pca_ctr.p));
+    HIP_TRY(hipMemcpyAsync(ctr, mp->pca_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    mp->pca_valid = true;
+    if (info) {
+        info->n_cells = ctr[0];
+        info->n_unqueried = ctr[1];
+        info->n_sparse = ctr[2];
+        for (int l = 0; l < 3; ++l) info->n_label[l] = ctr[3 + l];
+        info->n_normal_determined = ctr[6];
+        info->n_tangent_determined = ctr[7];
+        info->sum_members = ctr[8];
+        info->reach = o.q.reach;
+    }
+    return DSI_OK;
+}
+
+int dsx_map_pca_fetch(dsi_map_t* mp, uint64_t* keys_host, float* normal_host, float* tangent_host, float* eval_host, uint16_t* members_host,
+                      uint8_t* label_host, uint8_t* flags_host, int64_t* moments_host, uint8_t* reasons_host, size_t capacity, size_t* count)
+{
+    REQUIRE(mp && count, DSI_ERR_INVALID, "null argument");
+    if (int rc = check_pca_pass(mp)) return rc;
+    REQUIRE(!moments_host || mp->pca_opts.keep_moments, DSI_ERR_INVALID, "the pass kept no moments: call dsx_map_pca with keep_moments = 1");
+    REQUIRE(!reasons_host || mp->pca_select_valid, DSI_ERR_INVALID,
+            "no selection on this pass: call dsx_map_pca_select before asking for reasons");
+    if (int rc = set_device(mp->ctx)) return rc;
+    size_t total = 0;
+    if (int rc = map_count_device(mp, mp->pca_opts.min_points, mp->pca_opts.min_windows, &total)) return rc;
+    *count = total;
+    REQUIRE(capacity >= total, DSI_ERR_INVALID, "capacity of %zu cells is too small: %zu needed", capacity, total);
+    if (!total) return DSI_OK;
+    hipStream_t st = mp->ctx->stream;
+    HIP_TRY(mp->key_out.reserve(total));
+    HIP_TRY(mp->pca_normal_out.reserve(3 * total));
+    HIP_TRY(mp->pca_tangent_out.reserve(3 * total));
+    HIP_TRY(mp->pca_eval_out.reserve(3 * total));
+    HIP_TRY(mp->pca_members_out.reserve(total));
+    HIP_TRY(mp->pca_label_out.reserve(total));
+    HIP_TRY(mp->pca_flags_out.reserve(total));
+    if (moments_host) HIP_TRY(mp->pca_moments_out.reserve(9 * total));
+    if (reasons_host) HIP_TRY(mp->pca_reason_out.reserve(total));
+    const dsi::MapPcaCells out{mp->pca_normal_out.p, mp->pca_tangent_out.p, mp->pca_eval_out.p, mp->pca_members_out.p,
+                               mp->pca_label_out.p,  mp->pca_flags_out.p,   moments_host ? mp->pca_moments_out.p : nullptr};
+    HIP_TRY(dsi::launch_map_pca_gather(st, dsi::map_table_at(mp->block.p, mp->cap_log2), mp->pca_opts.min_points, mp->pca_opts.min_windows,
+                                       map_pca_cells_of(mp), reasons_host ? mp->pca_reason.p : nullptr, mp->blk.p, mp->key_out.p, out,
+                                       reasons_host ? mp->pca_reason_out.p : nullptr));
+    static_assert(sizeof(int64_t) == sizeof(long long), "64-bit moments");
+    if (keys_host) HIP_TRY(hipMemcpyAsync(keys_host, mp->key_out.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (normal_host) HIP_TRY(hipMemcpyAsync(normal_host, out.normal, 3 * total * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (tangent_host) HIP_TRY(hipMemcpyAsync(tangent_host, out.tangent, 3 * total * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (eval_host) HIP_TRY(hipMemcpyAsync(eval_host, out.eval, 3 * total * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (members_host) HIP_TRY(hipMemcpyAsync(members_host, out.members, total * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+    if (label_host) HIP_TRY(hipMemcpyAsync(label_host, out.label, total, hipMemcpyDeviceToHost, st));
+    if (flags_host) HIP_TRY(hipMemcpyAsync(flags_host, out.flags, total, hipMemcpyDeviceToHost, st));
+    if (moments_host) HIP_TRY(hipMemcpyAsync(moments_host, out.moments, 9 * total * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (reasons_host) HIP_TRY(hipMemcpyAsync(reasons_host, mp->pca_reason_out.p, total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+int dsx_pca_solve(uint32_t m, const int64_t s[3], const int64_t ss[6], double quantum, int32_t orient, const double viewpoint[3],
+                  const double p[3], dsx_pca_row_t* out)
+{
+    REQUIRE(s && ss && out, DSI_ERR_INVALID, "null argument");
+    REQUIRE(std::isfinite(quantum) && quantum > 0.0, DSI_ERR_INVALID, "quantum must be finite and > 0 (got %g)", quantum);
+    REQUIRE(orient == 0 || orient == 1, DSI_ERR_INVALID, "orient must be 0 or 1 (got %d)", orient);
+    if (orient) {
+        REQUIRE(viewpoint && p, DSI_ERR_INVALID, "orient needs viewpoint and p");
+        for (int a = 0; a < 3; ++a)
+            REQUIRE(std::isfinite(viewpoint[a]) && std::isfinite(p[a]), DSI_ERR_INVALID, "viewpoint and p must be finite");
+    }
+    dsi::PcaSolved r;
+    const dsi::PcaSolveError e = dsi::pca_solve_host(m, s, ss, quantum, orient, viewpoint, p, &r);
+    REQUIRE(e != dsi::kPcaBadMembers, DSI_ERR_INVALID, "m must be in 1..%u (got %u)", dsi::kPcaMaxMembers, m);
+    REQUIRE(e != dsi::kPcaMomentsTooLarge, DSI_ERR_INVALID, "moments beyond what m = %u members with |D| <= %lld can sum to", m,
+            (long long)dsi::kPcaMaxOffset);
+    REQUIRE(e != dsi::kPcaNegativeVariance, DSI_ERR_INVALID, "m * ss < s^2 on an axis: no set of m offsets has these moments");
+    for (int a = 0; a < 3; ++a) {
+        out->normal_d[a] = r.normal[a], out->tangent_d[a] = r.tangent[a], out->lambda[a] = r.lambda[a];
+        out->normal[a] = r.normal_f[a], out->tangent[a] = r.tangent_f[a], out->eval[a] = r.eval[a];
+    }
+    out->label = r.label, out->flags = r.flags;
+    return DSI_OK;
+}
+
+int dsx_map_pca_select(dsi_map_t* mp, const dsx_map_pca_selection_t* sel, dsx_map_pca_select_info_t* info)
+{
+    if (int rc = check_pca_selection(sel)) return rc;  // (first: the bounds can be exercised with no map at hand)
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    if (int rc = check_pca_pass(mp)) return rc;
+    if (int rc = set_device(mp->ctx)) return rc;
+    mp->pca_select_valid = false;
+    unsigned long long ctr[dsi::kMapPcaSelectCounters] = {0, 0, 0, 0};
+    if (int rc = map_pca_select_device(mp, sel, ctr)) return rc;
+    mp->pca_select_valid = true;
+    map_pca_select_info(mp, ctr, info);
+    return DSI_OK;
+}
+
+int dsx_map_prune_pca(dsi_map_t* mp, const dsx_map_pca_selection_t* sel, dsx_map_pca_select_info_t* info)
+{
+    if (int rc = check_pca_selection(sel)) return rc;
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    if (int rc = check_pca_pass(mp)) return rc;
+    if (int rc = set_device(mp->ctx)) return rc;
+    hipStream_t st = mp->ctx->stream;
+    mp->pca_select_valid = false;
+    unsigned long long ctr[dsi::kMapPcaSelectCounters] = {0, 0, 0, 0};
+    if (int rc = map_pca_select_device(mp, sel, ctr)) return rc;
+    mp->pca_select_valid = true;  // (the reasons are those of the map as it stands, should the rebuild fail to allocate)
+    const unsigned long long kept = ctr[0];
+    uint32_t want = mp->cap_log2;
+    if (sel->shrink)
+        for (want = kMapMinLog2; kept * 4 > ((uint64_t)3 << want); ++want) {
+        }
+    DevBuf<unsigned char> block;
+    const bool rebuild = !(ctr[1] + ctr[2] + ctr[3] == 0 && want == mp->cap_log2);  // (else the table is the result already)
+    if (rebuild) {
+        const hipError_t e = block.reserve(dsi::map_table_bytes(want));
+        if (e != hipSuccess)
+            return fail(DSI_ERR_HIP, "a pruned table of 2^%u slots could not be allocated (%s): the map is unchanged", want,
+                        hipGetErrorString(e));
+    }
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->comp_select_valid = false;
+    mp->knn_valid = mp->knn_select_valid = mp->pca_valid = mp->pca_select_valid = false;
+    if (rebuild) {
+        HIP_TRY(hipMemsetAsync(block.p, 0, dsi::map_table_bytes(want), st));
+        HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof(unsigned long long), st));  // occupied: the rebuild counts the cells it moves
+        if (kept)
+            HIP_TRY(dsi::launch_map_prune_rehash(st, dsi::map_table_at(mp->block.p, mp->cap_log2), dsi::map_table_at(block.p, want),
+                                                 mp->pca_reason.p, mp->ctr.p));
+        HIP_TRY(hipMemcpyAsync(mp->host_ctr, mp->ctr.p, sizeof mp->host_ctr, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        mp->block = std::move(block);  // (frees the old table)
+        mp->cap_log2 = want;
+        REQUIRE(mp->host_ctr[3] == 0 && mp->host_ctr[0] == kept, DSI_ERR_HIP,
+                "the pruned table holds %llu of %llu kept cells (%llu found it full): an engine bug, the map is unusable", mp->host_ctr[0],
+                kept, mp->host_ctr[3]);
+    }
+    map_pca_select_info(mp, ctr, info);
     return DSI_OK;
 }
 
@@ -5216,7 +5472,7 @@ int map_merge_apply(dsi_map* dst, const MapMergeSource& src, dsx_map_merge_info_
     HIP_TRY(dst->merge_ctr.reserve(dsi::kMapMergeCounters));
     const uint64_t growths_before = dst->growths;
     if (int rc = map_grow_for(dst, (size_t)src.cells)) return rc;                 // (a failed allocation leaves dst as it is)
-    dst->render_valid = dst->compare_valid = dst->prune_valid = dst->align_valid = dst->comp_valid = dst->knn_valid = false;  // (the map changes from here on)
+    dst->render_valid = dst->compare_valid = dst->prune_valid = dst->align_valid = dst->comp_valid = dst->knn_valid = dst->pca_valid = false;  // (the map changes from here on)
     unsigned long long mctr[dsi::kMapMergeCounters] = {0, 0};
     HIP_TRY(dsi::launch_map_merge(st, src.t, dsi::map_table_at(dst->block.p, dst->cap_log2), (uint32_t)dst->calls, src.accepted,
                                   src.rejected, dst->ctr.p, dst->merge_ctr.p));

@@ -490,6 +490,35 @@ hipError_t launch_map_knn_gather(hipStream_t s, const MapTable& t, uint32_t min_
                                  const uint8_t* reason, const uint32_t* blk, unsigned long long* key_out, uint8_t* found_out,
                                  float* mean_out, uint32_t* q_out, uint8_t* reason_out);
 
+// ---- the map's local shape (include/dsi_map_pca.h; DESIGN.md 7j "Local shape") ----
+constexpr int kMapPcaCounters = 9;        // queries, unqueried cells, sparse, label 1..3, normal / tangent determined, sum of members
+constexpr int kMapPcaSelectCounters = 4;  // kept, removed by reason 1..3
+// the pass; the host has checked every bound.  q is the neighbour search's view: k 0..kMapKnnMaxK (0: the radius search),
+// min_found from 2 on, reach 1..kMapKnnMaxReach; quantum = leaf * 2^-10
+struct MapPca {
+    MapKnn q;
+    double quantum, viewpoint[3];
+    int orient;
+};
+// the pass's result, per slot (written for the cells that pass the filter): normal, tangent, eval [3] each; moments [9]
+// (s[3], ss[6]) or NULL
+struct MapPcaCells {
+    float *normal, *tangent, *eval;
+    uint16_t* members;
+    uint8_t *label, *flags;
+    long long* moments;
+};
+// clears ctr [kMapPcaCounters], then every filtered cell of t: its neighbourhood's moments, their solve, the row into c
+hipError_t launch_map_pca(hipStream_t s, const MapTable& t, const MapPca& o, const MapPcaCells& c, unsigned long long* ctr);
+// clears ctr [kMapPcaSelectCounters]; reason [cap]: every slot's reason (kMapPruneEmpty without a cell) from the pass's labels
+hipError_t launch_map_pca_select(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, const uint8_t* label,
+                                 uint32_t keep_labels, int remove_sparse, uint8_t* reason, unsigned long long* ctr);
+// after launch_map_count(t, min_points, min_windows) with the pass's filter: the rows of every query in slot order
+// (launch_map_extract's) into key_out and out (compacted; out.moments NULL: not wanted) and (reason != NULL) reason_out
+hipError_t launch_map_pca_gather(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, const MapPcaCells& c,
+                                 const uint8_t* reason, const uint32_t* blk, unsigned long long* key_out, const MapPcaCells& out,
+                                 uint8_t* reason_out);
+
 // ---- merging maps and moving their state (include/dsi_map_merge.h; DESIGN.md 7j "Merging") ----
 constexpr int kMapImportCounters = 8;  // bad key, duplicate, n == 0, bad windows, bad stamp, S too large, table full, sum of n
 constexpr int kMapMergeCounters = 2;   // cells new to dst, cells both maps hold

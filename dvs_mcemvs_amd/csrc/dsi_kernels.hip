@@ -15,6 +15,8 @@
 // it); explicit fmaf() calls are the only fused operations.
 #include "dsi_kernels.h"
 #include "dsi_vote_asm.h"
+#define DSI_PCA_FN __host__ __device__ inline  // (the solve of dsi_pca_host.hpp runs in k_map_pca too)
+#include "dsi_pca_host.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -7931,6 +7933,228 @@ __global__ void __launch_bounds__(kPcBlock) k_map_knn_gather(MapTable t, uint32_
     }
 }
 
+// ---- the map's local shape (include/dsi_map_pca.h dsx_map_pca*; DESIGN.md 7j "Local shape") ----
+// One thread per query cell.  The neighbourhood's nine integer moments are summed in registers -- straight in the scan for
+// K == 0 (every admitted cell is a member), after knn_scan<K> for K > 0, whose found keys are looked up again for their
+// offsets --, and the solve is dsi_pca_host.hpp's, the statements the host runs: its eighteen doubles sit behind
+// compile-time indices.
+
+// D = llrint((q - p) / quantum) per axis of the cell in slot j (key kb) against the query p, added to s and ss
+__device__ inline void pca_accumulate(const MapTable& t, uint32_t j, unsigned long long kb, const MapPca& o, const double (&p)[3],
+                                      long long (&s)[3], long long (&ss)[6])
+{
+    const uint32_t nb = t.n[j];
+    const long long dx = llrint(((double)map_centroid(t, j, kb, nb, 0, o.q.leaf) - p[0]) / o.quantum);
+    const long long dy = llrint(((double)map_centroid(t, j, kb, nb, 1, o.q.leaf) - p[1]) / o.quantum);
+    const long long dz = llrint(((double)map_centroid(t, j, kb, nb, 2, o.q.leaf) - p[2]) / o.quantum);
+    s[0] += dx, s[1] += dy, s[2] += dz;
+    ss[0] += dx * dx, ss[1] += dx * dy, ss[2] += dx * dz;
+    ss[3] += dy * dy, ss[4] += dy * dz, ss[5] += dz * dz;
+}
+
+// knn_scan's walk with every admitted candidate a member: returns their number, the moments in s and ss
+__device__ inline uint32_t pca_scan_all(const MapTable& t, uint32_t mask, const MapPca& o, const double (&p)[3], unsigned long long self,
+                                        long long (&s)[3], long long (&ss)[6])
+{
+    double c[3];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) c[ax] = floor(p[ax] / o.q.leaf);
+    uint32_t admitted = 0;
+    for (int oz = -o.q.reach; oz <= o.q.reach; ++oz) {
+        const double vz = c[2] + (double)oz;
+        if (!(fabs(vz) <= (double)kPcCellMax)) continue;  // (NaN included)
+        for (int oy = -o.q.reach; oy <= o.q.reach; ++oy) {
+            const double vy = c[1] + (double)oy;
+            if (!(fabs(vy) <= (double)kPcCellMax)) continue;
+            for (int ox = -o.q.reach; ox <= o.q.reach; ++ox) {
+                const double vx = c[0] + (double)ox;
+                if (!(fabs(vx) <= (double)kPcCellMax)) continue;
+                const unsigned long long kb = pc_key((int)vx, (int)vy, (int)vz);
+                if (kb == self) continue;
+                const uint32_t j = map_find(t.keys, mask, kb);
+                if (j == ~0u || !map_passes(t, j, o.q.min_points, o.q.min_windows)) continue;
+                const uint32_t nb = t.n[j];
+                const double dx = p[0] - (double)map_centroid(t, j, kb, nb, 0, o.q.leaf);
+                const double dy = p[1] - (double)map_centroid(t, j, kb, nb, 1, o.q.leaf);
+                const double dz = p[2] - (double)map_centroid(t, j, kb, nb, 2, o.q.leaf);
+                const double dd = ((dx * dx) + dy * dy) + dz * dz;
+                if (!(sqrt(dd) <= o.q.radius)) continue;
+                ++admitted;
+                pca_accumulate(t, j, kb, o, p, s, ss);
+            }
+        }
+    }
+    return admitted;
+}
+
+// The pass: every cell that passes the filter, the table walked in strides as k_map_knn_self's.  Per query the row of
+// dsi_map_pca.h step 8 into c (a sparse query: label 0, flags 0, vectors 0, eigenvalues +inf).  ctr: [0] queries, [1] occupied
+// slots the filter leaves out, [2] sparse, [3..5] label 1..3, [6] normal determined, [7] tangent determined, [8] sum of m.
+// The ballots are summed in registers, the members per thread, both then in LDS, and a workgroup issues one global atomic
+// per counter.
+template <int K>
+__global__ void __launch_bounds__(kPcBlock) k_map_pca(MapTable t, MapPca o, MapPcaCells c, unsigned long long* __restrict__ ctr)
+{
+    __shared__ uint32_t s_cnt[kMapPcaCounters];
+    if (threadIdx.x < kMapPcaCounters) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    uint32_t c_query = 0, c_other = 0, c_sparse = 0, c_l1 = 0, c_l2 = 0, c_l3 = 0, c_nd = 0, c_td = 0;  // (the same in every lane of a wave)
+    uint32_t members = 0;
+    const uint32_t mask = (1u << t.cap_log2) - 1u;
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        const bool occupied = map_passes(t, i, 0u, 0u), f = occupied && map_passes(t, i, o.q.min_points, o.q.min_windows);
+        uint32_t label = 0u, flags = 0u;
+        if (f) {
+            const unsigned long long k = t.keys[i];
+            const uint32_t n = t.n[i];
+            double p[3];
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) p[ax] = (double)map_centroid(t, i, k, n, ax, o.q.leaf);
+            long long s[3] = {0, 0, 0}, ss[6] = {0, 0, 0, 0, 0, 0};
+            uint32_t found;
+            if constexpr (K == 0) {
+                found = pca_scan_all(t, mask, o, p, k, s, ss);
+            } else {
+                double d2[K];
+                unsigned long long key[K];
+                const uint32_t admitted = knn_scan<K>(t, mask, o.q, p, k, d2, key);
+                found = min(admitted, (uint32_t)o.q.k);
+#pragma unroll
+                for (int j = 0; j < K; ++j)
+                    if (j < (int)found) {
+                        const uint32_t slot = map_find(t.keys, mask, key[j]);
+                        if (slot != ~0u) pca_accumulate(t, slot, key[j], o, p, s, ss);  // (always found: the scan saw it)
+                    }
+            }
+            const uint32_t m = found + 1u;
+            members += m;
+            PcaSolved r;
+            if ((int)found >= o.q.min_found) {
+                const int64_t s3[3] = {s[0], s[1], s[2]}, ss6[6] = {ss[0], ss[1], ss[2], ss[3], ss[4], ss[5]};
+                pca_solve_core(m, s3, ss6, o.quantum, o.orient, o.viewpoint, p, r);
+                label = r.label, flags = r.flags;
+            } else {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) r.normal_f[a] = r.tangent_f[a] = 0.0f, r.eval[a] = INFINITY;
+            }
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                c.normal[3 * i + a] = r.normal_f[a];
+                c.tangent[3 * i + a] = r.tangent_f[a];
+                c.eval[3 * i + a] = r.eval[a];
+            }
+            c.members[i] = (uint16_t)m;
+            c.label[i] = (uint8_t)label;
+            c.flags[i] = (uint8_t)flags;
+            if (c.moments) {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) c.moments[9 * i + a] = s[a];
+#pragma unroll
+                for (int a = 0; a < 6; ++a) c.moments[9 * i + 3 + a] = ss[a];
+            }
+        }
+        c_query += (uint32_t)__popcll(__ballot(f));
+        c_other += (uint32_t)__popcll(__ballot(occupied && !f));
+        c_sparse += (uint32_t)__popcll(__ballot(f && label == 0u));
+        c_l1 += (uint32_t)__popcll(__ballot(label == 1u));
+        c_l2 += (uint32_t)__popcll(__ballot(label == 2u));
+        c_l3 += (uint32_t)__popcll(__ballot(label == 3u));
+        c_nd += (uint32_t)__popcll(__ballot((flags & 1u) != 0u));
+        c_td += (uint32_t)__popcll(__ballot((flags & 2u) != 0u));
+    }
+    if (members) atomicAdd(&s_cnt[8], members);  // (at most 343 per round: a workgroup's sum stays far below 2^32)
+    if ((threadIdx.x & 63) == 0) {
+        if (c_query) atomicAdd(&s_cnt[0], c_query);
+        if (c_other) atomicAdd(&s_cnt[1], c_other);
+        if (c_sparse) atomicAdd(&s_cnt[2], c_sparse);
+        if (c_l1) atomicAdd(&s_cnt[3], c_l1);
+        if (c_l2) atomicAdd(&s_cnt[4], c_l2);
+        if (c_l3) atomicAdd(&s_cnt[5], c_l3);
+        if (c_nd) atomicAdd(&s_cnt[6], c_nd);
+        if (c_td) atomicAdd(&s_cnt[7], c_td);
+    }
+    __syncthreads();
+    if (threadIdx.x < kMapPcaCounters && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
+// The selection's reason of every slot (kMapPruneEmpty without a cell), the first that holds: 1 the cell fails the pass's
+// filter; 2 it is sparse (label 0) and remove_sparse; 3 its label's bit 1 << (label - 1) is not in keep_labels (a sparse cell
+// that stays is kept).  ctr[0] += kept, ctr[r] += removed by reason r.
+__global__ void __launch_bounds__(kPcBlock) k_map_pca_select(MapTable t, uint32_t min_points, uint32_t min_windows, const uint8_t* __restrict__ label,
+                                                             uint32_t keep_labels, int remove_sparse, uint8_t* __restrict__ reason,
+                                                             unsigned long long* __restrict__ ctr)
+{
+    __shared__ uint32_t s_cnt[kMapPcaSelectCounters];
+    if (threadIdx.x < kMapPcaSelectCounters) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;  // (the same in every lane of a wave)
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        uint32_t r = kMapPruneEmpty;
+        if (map_passes(t, i, 0u, 0u)) {
+            if (!map_passes(t, i, min_points, min_windows)) {
+                r = 1u;
+            } else {
+                const uint32_t l = label[i];
+                if (l == 0u)
+                    r = remove_sparse ? 2u : 0u;
+                else
+                    r = (keep_labels >> (l - 1u)) & 1u ? 0u : 3u;
+            }
+        }
+        reason[i] = (uint8_t)r;
+        c0 += (uint32_t)__popcll(__ballot(r == 0u));
+        c1 += (uint32_t)__popcll(__ballot(r == 1u));
+        c2 += (uint32_t)__popcll(__ballot(r == 2u));
+        c3 += (uint32_t)__popcll(__ballot(r == 3u));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (c0) atomicAdd(&s_cnt[0], c0);
+        if (c1) atomicAdd(&s_cnt[1], c1);
+        if (c2) atomicAdd(&s_cnt[2], c2);
+        if (c3) atomicAdd(&s_cnt[3], c3);
+    }
+    __syncthreads();
+    if (threadIdx.x < kMapPcaSelectCounters && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
+// the pass compacted like k_map_extract's cells under the pass's filter, with its blk_off (one offset per tile of kPcBlock
+// slots), in slot order and walked in strides; out.moments and reason_out are written when asked for (not NULL)
+__global__ void __launch_bounds__(kPcBlock) k_map_pca_gather(MapTable t, uint32_t min_points, uint32_t min_windows, MapPcaCells c,
+                                                             const uint8_t* __restrict__ reason, const uint32_t* __restrict__ blk_off,
+                                                             unsigned long long* __restrict__ key_out, MapPcaCells out,
+                                                             uint8_t* __restrict__ reason_out)
+{
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        const bool f = map_passes(t, i, min_points, min_windows);
+        uint32_t total;
+        const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);  // (every thread of the workgroup, every round)
+        if (f) {
+            const size_t at = (size_t)blk_off[base / kPcBlock] + rank;
+            key_out[at] = t.keys[i];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                out.normal[3 * at + a] = c.normal[3 * i + a];
+                out.tangent[3 * at + a] = c.tangent[3 * i + a];
+                out.eval[3 * at + a] = c.eval[3 * i + a];
+            }
+            out.members[at] = c.members[i];
+            out.label[at] = c.label[i];
+            out.flags[at] = c.flags[i];
+            if (out.moments) {
+#pragma unroll
+                for (int a = 0; a < 9; ++a) out.moments[9 * at + a] = c.moments[9 * i + a];
+            }
+            if (reason_out) reason_out[at] = reason[i];
+        }
+    }
+}
+
 // ---- merging maps and moving their state (include/dsi_map_merge.h dsx_map_export / import / merge; DESIGN.md 7j "Merging") ----
 // Every occupied slot's raw state compacted like k_map_extract's cells under the filter (0, 0), with its blk_off (one
 // offset per tile of kPcBlock slots): key, n, S[3], windows and stamp in slot order.  Walked in strides like k_map_render;
@@ -8488,6 +8712,46 @@ hipError_t launch_map_knn_gather(hipStream_t s, const MapTable& t, uint32_t min_
 {
     hipLaunchKernelGGL(k_map_knn_gather, dim3(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s, t,
                        min_points, min_windows, c, reason, blk, key_out, found_out, mean_out, q_out, reason_out);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_pca(hipStream_t s, const MapTable& t, const MapPca& o, const MapPcaCells& c, unsigned long long* ctr)
+{
+    const hipError_t e = hipMemsetAsync(ctr, 0, kMapPcaCounters * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    const dim3 grid(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), block(kPcBlock);
+    // (the instantiation is the smallest K >= k: its list's first k are the neighbourhood; 0 is the radius search)
+    if (o.q.k <= 0)
+        hipLaunchKernelGGL(k_map_pca<0>, grid, block, 0, s, t, o, c, ctr);
+    else if (o.q.k <= 1)
+        hipLaunchKernelGGL(k_map_pca<1>, grid, block, 0, s, t, o, c, ctr);
+    else if (o.q.k <= 2)
+        hipLaunchKernelGGL(k_map_pca<2>, grid, block, 0, s, t, o, c, ctr);
+    else if (o.q.k <= 4)
+        hipLaunchKernelGGL(k_map_pca<4>, grid, block, 0, s, t, o, c, ctr);
+    else if (o.q.k <= 8)
+        hipLaunchKernelGGL(k_map_pca<8>, grid, block, 0, s, t, o, c, ctr);
+    else
+        hipLaunchKernelGGL(k_map_pca<16>, grid, block, 0, s, t, o, c, ctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_pca_select(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, const uint8_t* label,
+                                 uint32_t keep_labels, int remove_sparse, uint8_t* reason, unsigned long long* ctr)
+{
+    const hipError_t e = hipMemsetAsync(ctr, 0, kMapPcaSelectCounters * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_map_pca_select, dim3(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s, t,
+                       min_points, min_windows, label, keep_labels, remove_sparse, reason, ctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_pca_gather(hipStream_t s, const MapTable& t, uint32_t min_points, uint32_t min_windows, const MapPcaCells& c,
+                                 const uint8_t* reason, const uint32_t* blk, unsigned long long* key_out, const MapPcaCells& out,
+                                 uint8_t* reason_out)
+{
+    hipLaunchKernelGGL(k_map_pca_gather, dim3(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s, t,
+                       min_points, min_windows, c, reason, blk, key_out, out, reason_out);
     return hipExtGetLastError();
 }
 

@@ -137,6 +137,31 @@ class _MapKnnSelectInfo(C.Structure):
                 ("mu", C.c_double), ("sigma", C.c_double), ("capacity", C.c_uint64)]
 
 
+class _MapPcaOpts(C.Structure):
+    _fields_ = [("min_points", C.c_uint32), ("min_windows", C.c_uint32), ("k", C.c_int32), ("min_found", C.c_int32),
+                ("radius", C.c_double), ("orient", C.c_int32), ("keep_moments", C.c_int32), ("viewpoint", C.c_double * 3)]
+
+
+class _MapPcaInfo(C.Structure):
+    _fields_ = [("n_cells", C.c_uint64), ("n_unqueried", C.c_uint64), ("n_sparse", C.c_uint64), ("n_label", C.c_uint64 * 3),
+                ("n_normal_determined", C.c_uint64), ("n_tangent_determined", C.c_uint64), ("sum_members", C.c_uint64),
+                ("reach", C.c_int32)]
+
+
+class _PcaRow(C.Structure):
+    _fields_ = [("normal_d", C.c_double * 3), ("tangent_d", C.c_double * 3), ("lambda_", C.c_double * 3),
+                ("normal", C.c_float * 3), ("tangent", C.c_float * 3), ("eval", C.c_float * 3), ("label", C.c_uint8),
+                ("flags", C.c_uint8)]
+
+
+class _MapPcaSelection(C.Structure):
+    _fields_ = [("keep_labels", C.c_uint32), ("remove_sparse", C.c_int32), ("shrink", C.c_int32)]
+
+
+class _MapPcaSelectInfo(C.Structure):
+    _fields_ = [("n_cells", C.c_uint64), ("n_kept", C.c_uint64), ("n_removed", C.c_uint64 * 3), ("capacity", C.c_uint64)]
+
+
 class _MapState(C.Structure):
     _fields_ = [("leaf", C.c_double), ("n_cells", C.c_uint64), ("calls", C.c_uint64), ("accepted", C.c_uint64),
                 ("rejected", C.c_uint64)]
@@ -443,6 +468,13 @@ def load_library():
         "dsx_map_knn_select": (C.c_int, [vp, C.POINTER(_MapKnnSelection), C.POINTER(_MapKnnSelectInfo)]),
         "dsx_map_knn_fetch": (C.c_int, [vp, u64p, u8p, f32p, u32p, u8p, C.c_size_t, szp]),
         "dsx_map_prune_knn": (C.c_int, [vp, C.POINTER(_MapKnnSelection), C.POINTER(_MapKnnSelectInfo)]),
+        # include/dsi_map_pca.h: the map's local shape
+        "dsx_map_pca": (C.c_int, [vp, C.POINTER(_MapPcaOpts), C.POINTER(_MapPcaInfo)]),
+        "dsx_map_pca_fetch": (C.c_int, [vp, u64p, f32p, f32p, f32p, u16p, u8p, u8p, C.POINTER(C.c_int64), u8p, C.c_size_t, szp]),
+        "dsx_pca_solve": (C.c_int, [C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_double, C.c_int32, f64p, f64p,
+                                    C.POINTER(_PcaRow)]),
+        "dsx_map_pca_select": (C.c_int, [vp, C.POINTER(_MapPcaSelection), C.POINTER(_MapPcaSelectInfo)]),
+        "dsx_map_prune_pca": (C.c_int, [vp, C.POINTER(_MapPcaSelection), C.POINTER(_MapPcaSelectInfo)]),
         # include/dsi_map_merge.h: merging maps, exporting and importing their state
         "dsx_map_export": (C.c_int, [vp, C.POINTER(_MapState), u64p, u32p, u64p, u32p, u32p, C.c_size_t, szp]),
         "dsx_map_import": (C.c_int, [vp, C.POINTER(_MapState), u64p, u32p, u64p, u32p, u32p, C.POINTER(_MapMergeInfo)]),
@@ -1512,6 +1544,81 @@ class WorldMap:
         return {"n_cells": int(i.n_cells), "n_kept": int(i.n_kept), "n_removed": [int(v) for v in i.n_removed], "T_q": int(i.T_q),
                 "mu": float(i.mu), "sigma": float(i.sigma), "capacity": int(i.capacity)}
 
+    def pca(self, k, radius, min_found=2, orient=False, viewpoint=None, keep_moments=False, min_points=1, min_windows=1):
+        """The local shape of every cell extract(min_points, min_windows) returns (dsx_map_pca; the rule is stated in
+        dsi_map_pca.h and DESIGN.md 7j "Local shape"): the principal components of the cell and its neighbours within
+        radius (at most three leaves) -- all of them for k = 0, the k nearest for k in 1..16 --, from exact integer moments.
+        Per cell a normal, a tangent, three eigenvalues, the number of members, a label (0 sparse: fewer than min_found
+        neighbours; 1 linear, 2 planar, 3 scattered) and flags (bit 0: the normal is determined, bit 1: the tangent) stay on
+        the device for fetchPca, selectShapes and pruneShapes until the map changes.  orient=True turns every normal towards
+        viewpoint (three finite numbers); keep_moments=True keeps the nine integers per cell for fetchPca.  Returns dict of
+        n_cells, n_unqueried, n_sparse, n_label (linear, planar, scattered), n_normal_determined, n_tangent_determined,
+        sum_members and reach.  Nothing else of the map changes."""
+        vp = (0.0, 0.0, 0.0) if viewpoint is None else tuple(float(v) for v in viewpoint)
+        if len(vp) != 3:
+            raise ValueError("viewpoint must be three numbers")
+        if orient and viewpoint is None:
+            raise ValueError("orient needs a viewpoint")
+        o = _MapPcaOpts(int(min_points), int(min_windows), int(k), int(min_found), float(radius), 1 if orient else 0,
+                        1 if keep_moments else 0, (C.c_double * 3)(*vp))
+        i = _MapPcaInfo()
+        self._pca_selected = False
+        self._pca_moments = False
+        _check(load_library().dsx_map_pca(self._h, C.byref(o), C.byref(i)))
+        self._pca_moments = bool(keep_moments)
+        out = {f: int(getattr(i, f)) for f in ("n_cells", "n_unqueried", "n_sparse", "n_normal_determined", "n_tangent_determined",
+                                               "sum_members", "reach")}
+        out["n_label"] = [int(v) for v in i.n_label]
+        return out
+
+    def fetchPca(self, sort=False):
+        """keys (uint64), normal, tangent and eval ((M, 3) float32), members (uint16), label and flags (uint8) of every query
+        of the last pca() of this map, moments ((M, 9) int64: s[3], ss[6]) when it kept them and, after a selectShapes() on
+        it, reason (uint8: 0 kept, 1..3 the first reason that holds) (dsx_map_pca_fetch); raises DsiError when the map
+        changed since.  The order is extract(sort=False)'s under the pass's filter; sort=True orders by ascending key."""
+        L = load_library()
+        n = C.c_size_t()
+        rc = L.dsx_map_pca_fetch(self._h, None, None, None, None, None, None, None, None, None, 0, C.byref(n))
+        if rc != OK and n.value == 0:
+            _check(rc)
+        m = n.value
+        out = {"keys": np.empty(m, np.uint64), "normal": np.empty((m, 3), np.float32), "tangent": np.empty((m, 3), np.float32),
+               "eval": np.empty((m, 3), np.float32), "members": np.empty(m, np.uint16), "label": np.empty(m, np.uint8),
+               "flags": np.empty(m, np.uint8)}
+        if getattr(self, "_pca_moments", False):
+            out["moments"] = np.empty((m, 9), np.int64)
+        if getattr(self, "_pca_selected", False):
+            out["reason"] = np.empty(m, np.uint8)
+        _check(L.dsx_map_pca_fetch(self._h, _ptr(out["keys"], C.c_uint64), _ptr(out["normal"], C.c_float), _ptr(out["tangent"], C.c_float),
+                                   _ptr(out["eval"], C.c_float), _ptr(out["members"], C.c_uint16), _ptr(out["label"], C.c_uint8),
+                                   _ptr(out["flags"], C.c_uint8), _ptr(out["moments"], C.c_int64) if "moments" in out else None,
+                                   _ptr(out["reason"], C.c_uint8) if "reason" in out else None, m, C.byref(n)))
+        if sort:
+            order = np.argsort(out["keys"], kind="stable")
+            out = {f: v[order] for f, v in out.items()}
+        return out
+
+    def selectShapes(self, keep=("linear", "planar"), remove_sparse=True, shrink=False):
+        """pruneShapes()'s dry run (dsx_map_pca_select): the same counts, the map unchanged; the per-cell reasons stay on the
+        device for fetchPca until the map changes."""
+        return self._select_shapes(load_library().dsx_map_pca_select, keep, remove_sparse, shrink)
+
+    def pruneShapes(self, keep=("linear", "planar"), remove_sparse=True, shrink=False):
+        """Keeps the cells of the last pca() of this map whose label is in keep -- names out of "linear", "planar" and
+        "scattered", or the mask itself (1, 2, 4) -- (dsx_map_prune_pca): a cell leaves by the first reason that holds -- it
+        fails the pass's filter; it is sparse and remove_sparse; its label is not kept -- and the table is rebuilt around the
+        rest, shrink as prune()'s.  Returns dict of n_cells = n_kept + sum(n_removed), n_kept, n_removed (three counts, by
+        reason) and capacity (slots afterwards).  Everything derived from the map is invalid afterwards."""
+        return self._select_shapes(load_library().dsx_map_prune_pca, keep, remove_sparse, shrink)
+
+    def _select_shapes(self, fn, keep, remove_sparse, shrink):
+        s = _MapPcaSelection(shape_mask(keep), 1 if remove_sparse else 0, 1 if shrink else 0)
+        i = _MapPcaSelectInfo()
+        self._pca_selected = False
+        _check(fn(self._h, C.byref(s), C.byref(i)))
+        self._pca_selected = True
+        return {"n_cells": int(i.n_cells), "n_kept": int(i.n_kept), "n_removed": [int(v) for v in i.n_removed], "capacity": int(i.capacity)}
+
     def exportState(self, sort=True):
         """The map's exact state (dsx_map_export; the rule is stated in dsi_map_merge.h and DESIGN.md 7j "Merging"): dict
         of leaf, calls, accepted, rejected and, per cell, keys (uint64), n (uint32), S (uint64, (M, 3): the sums of the
@@ -1727,6 +1834,39 @@ def knn_threshold(n_scored, sum_q, sum_q2, std_mult):
     _check(load_library().dsx_map_knn_threshold(int(n_scored), int(sum_q), words, float(std_mult), C.byref(mu), C.byref(sigma),
                                                 C.byref(tq)))
     return {"mu": mu.value, "sigma": sigma.value, "T_q": int(tq.value)}
+
+
+SHAPE_LABELS = {"linear": 1, "planar": 2, "scattered": 4}
+
+
+def shape_mask(keep):
+    """keep_labels of dsi_map_pca.h from names ("linear", "planar", "scattered") or from the mask itself"""
+    if isinstance(keep, str):
+        keep = (keep,)
+    if isinstance(keep, (int, np.integer)):
+        return int(keep) & 0xffffffff
+    mask = 0
+    for name in keep:
+        if name not in SHAPE_LABELS:
+            raise ValueError("unknown shape %r: linear, planar or scattered" % (name,))
+        mask |= SHAPE_LABELS[name]
+    return mask
+
+
+def pca_solve(m, s, ss, quantum, orient=False, viewpoint=None, p=None):
+    """One cell's local shape from its integer moments alone (dsx_pca_solve, the routine the pass runs per cell; stated in
+    dsi_map_pca.h; no device is touched): m members, s the three sums and ss the six sums of products of the quantised
+    offsets, quantum = leaf / 1024; orient=True needs viewpoint and the cell's centroid p.  Returns dict of normal, tangent
+    and eval (float32 [3], the row's bits), label, flags, and the doubles normal_d, tangent_d and lambda (ascending)."""
+    sv = (C.c_int64 * 3)(*[int(v) for v in s])
+    ssv = (C.c_int64 * 6)(*[int(v) for v in ss])
+    vp = None if viewpoint is None else (C.c_double * 3)(*[float(v) for v in viewpoint])
+    pp = None if p is None else (C.c_double * 3)(*[float(v) for v in p])
+    r = _PcaRow()
+    _check(load_library().dsx_pca_solve(int(m), sv, ssv, float(quantum), 1 if orient else 0, vp, pp, C.byref(r)))
+    return {"normal": np.array(r.normal[:], np.float32), "tangent": np.array(r.tangent[:], np.float32),
+            "eval": np.array(r.eval[:], np.float32), "label": int(r.label), "flags": int(r.flags),
+            "normal_d": np.array(r.normal_d[:]), "tangent_d": np.array(r.tangent_d[:]), "lambda": np.array(r.lambda_[:])}
 
 
 def map_f_score(est, gt, radius, n_bins=16, min_points=1, min_windows=1, min_points_gt=1, min_windows_gt=1):

@@ -12,6 +12,7 @@ trajectories can be replayed without ROS:
   dsec_disparity_name   the file name of a ground-truth frame, scripts/evaluate_mcemvs_dsec.py:99
   save_depth_maps       saveDepthMaps                  utils.cpp:22-104               (the txt and the two .png it writes)
   save_pcd_ascii        pcl::io::savePCDFileASCII       main.cpp:397-402               (.pcd v0.7, PointXYZI, ascii)
+  save_pcd_normals_ascii, load_pcd_normals_ascii   the same for PointNormal (a world map's cells with WorldMap.fetchPca's normals)
   read_pose_bag         parse of geometry_msgs/PoseStamped bags   data_loading.cpp:221-302 (ROSBAG v2.0; none / bz2 chunks)
   read_event_bag        parse of dvs_msgs/EventArray bags         data_loading.cpp:31-107, 211-216
   write_pose_bag, write_event_bag   test helpers: minimal writers of the same subset of the format
@@ -279,6 +280,66 @@ def save_pcd_ascii(path, points):
         for p in pts[:, :4]:
             f.write(" ".join(fmt(v) for v in p) + "\n")
     return n
+
+
+def pcd_curvature(evals):
+    """PCL's surface variation eval0 / ((eval0 + eval1) + eval2) in float64 from rows of ascending eigenvalues (engine.
+    WorldMap.fetchPca's eval); NaN where the sum is 0 or not finite (a lone or sparse cell)"""
+    e = np.asarray(evals, np.float64).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        total = (e[:, 0] + e[:, 1]) + e[:, 2]
+        return np.where(np.isfinite(total) & (total > 0.0), e[:, 0] / total, np.nan)
+
+
+_PCD_NORMAL_FIELDS = "x y z normal_x normal_y normal_z curvature"
+
+
+def save_pcd_normals_ascii(path, points, normals, curvature):
+    """What pcl::io::savePCDFileASCII writes for a pcl::PointCloud<pcl::PointNormal> of N points, restated from PCL's
+    documentation of the format as save_pcd_ascii is: FIELDS x y z normal_x normal_y normal_z curvature, seven float32
+    (NaN as "nan") at 9 significant digits -- savePCDFileASCII's precision argument, one above its default, because 8 digits
+    do not bring every float32 back and a unit normal should stay one.  points and normals: (N, >= 3); curvature: N values
+    -- pcd_curvature of the eigenvalues that engine.WorldMap.fetchPca returns.  Returns N."""
+    pts, nrm = np.asarray(points, np.float32), np.asarray(normals, np.float32)
+    cur = np.asarray(curvature, np.float64).reshape(-1).astype(np.float32)
+    if pts.size == 0 and nrm.size == 0:
+        pts, nrm = pts.reshape(0, 3), nrm.reshape(0, 3)
+    if pts.ndim != 2 or nrm.ndim != 2 or pts.shape[1] < 3 or nrm.shape[1] < 3 or not pts.shape[0] == nrm.shape[0] == cur.shape[0]:
+        raise ValueError("points and normals must be (N, 3) and curvature N values")
+    n = pts.shape[0]
+    rows = np.column_stack([pts[:, :3], nrm[:, :3], cur])
+
+    def fmt(v):
+        return "nan" if np.isnan(v) else "%.9g" % float(v)
+
+    with open(path, "w") as f:
+        f.write("# .PCD v0.7 - Point Cloud Data file format\n"
+                "VERSION 0.7\n"
+                "FIELDS %s\n"
+                "SIZE 4 4 4 4 4 4 4\n"
+                "TYPE F F F F F F F\n"
+                "COUNT 1 1 1 1 1 1 1\n"
+                "WIDTH %d\n"
+                "HEIGHT 1\n"
+                "VIEWPOINT 0 0 0 1 0 0 0\n"
+                "POINTS %d\n"
+                "DATA ascii\n" % (_PCD_NORMAL_FIELDS, n, n))
+        for r in rows:
+            f.write(" ".join(fmt(v) for v in r) + "\n")
+    return n
+
+
+def load_pcd_normals_ascii(path):
+    """Reads back what save_pcd_normals_ascii wrote: dict of points (N, 3), normals (N, 3) and curvature [N], float32 (%.9g
+    round-trips a float32 exactly).  Raises ValueError for any other header."""
+    with open(path) as f:
+        lines = f.read().split("\n")
+    head = dict(l.split(" ", 1) for l in lines[1:11])
+    if head.get("FIELDS") != _PCD_NORMAL_FIELDS or head.get("DATA") != "ascii" or head.get("TYPE") != "F F F F F F F":
+        raise ValueError("%s: not an ascii PCD file of x y z normal_x normal_y normal_z curvature" % path)
+    n = int(head["POINTS"])
+    rows = np.array([[float(v) for v in l.split()] for l in lines[11:11 + n]], np.float64).reshape(n, 7).astype(np.float32)
+    return {"points": rows[:, :3], "normals": rows[:, 3:6], "curvature": rows[:, 6]}
 
 
 _MAP_SCALARS = (("leaf", np.float64), ("calls", np.uint64), ("accepted", np.uint64), ("rejected", np.uint64))

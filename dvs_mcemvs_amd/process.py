@@ -747,7 +747,8 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
                   out_skip, fusion_method=E.FUSE_HM, forward_looking=True, rv_pos=0.0, options_depth_map=None,
                   options_point_cloud=None, polarities=None, save_images=False, out_path=None, lut=None, score=None,
                   ground_truth=None, ground_truth_disparity=None, thicken_edges=False, world_map=None, world_map_prune=None,
-                  world_map_components=None, world_map_outliers=None, **kw):
+                  world_map_components=None, world_map_outliers=None, world_map_shapes=None,
+                  **kw):
     """Generator over the windows of main.cpp:177-302: yields (ts, depth, confidence, indices) per
     window, pipelined one window deep; with options_depth_map, (ts, depth_map, confidence_map, mask)
     -- the filtered outputs the reference saves per window; with options_point_cloud as well, the window's
@@ -801,7 +802,30 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
     min_found, min_points, min_windows) and of WorldMap.pruneOutliers (std_mult, shrink) plus `every` (default 1): after
     every every-th window, after world_map_prune's and world_map_components' work on that window, the map queries itself
     and loses its isolated cells and statistical outliers.  Such a window's result gains a last element,
-    {"world_map_outliers": the counts of WorldMap.knn, and under "prune" those of WorldMap.pruneOutliers}."""
+    {"world_map_outliers": the counts of WorldMap.knn, and under "prune" those of WorldMap.pruneOutliers}.
+    world_map_shapes= (with world_map=; None leaves the stream as it is): a dict of the keywords of WorldMap.pca (k, radius,
+    min_found, orient, viewpoint, min_points, min_windows) and of WorldMap.pruneShapes (keep, remove_sparse, shrink) plus
+    `every` (default 1): after every every-th window, after world_map_outliers' work on that window, the map analyses its
+    cells' local shape and keeps the labels in keep.  Such a window's result gains a last element, {"world_map_shapes": the
+    counts of WorldMap.pca, and under "prune" those of WorldMap.pruneShapes}."""
+    shapes = None
+    if world_map_shapes is not None:
+        if world_map is None:
+            raise ValueError("world_map_shapes needs world_map")
+        shapes = dict(world_map_shapes)
+        every = shapes.pop("every", 1)
+        if int(every) != every or every < 1:
+            raise ValueError("world_map_shapes['every'] must be an integer >= 1")
+        pca_keys = {"k", "radius", "min_found", "orient", "viewpoint", "min_points", "min_windows"}
+        select_keys = {"keep", "remove_sparse", "shrink"}
+        unknown = set(shapes) - pca_keys - select_keys
+        if unknown:
+            raise ValueError("world_map_shapes: unknown keys %s" % sorted(unknown))
+        if "k" not in shapes or "radius" not in shapes:
+            raise ValueError("world_map_shapes needs k and radius")
+        if E.shape_mask(shapes.get("keep", ("linear", "planar"))) not in range(1, 8):
+            raise ValueError("world_map_shapes['keep'] must name at least one of linear, planar and scattered")
+        shapes = ({k: v for k, v in shapes.items() if k in pca_keys}, {k: v for k, v in shapes.items() if k in select_keys}, int(every))
     outl = None
     if world_map_outliers is not None:
         if world_map is None:
@@ -898,6 +922,10 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
             counts = world_map.knn(**outl[0])
             counts["prune"] = world_map.pruneOutliers(**outl[1])
             out = out + ({"world_map_outliers": counts},)
+        if shapes is not None and windows_seen % shapes[2] == 0:
+            counts = world_map.pca(**shapes[0])
+            counts["prune"] = world_map.pruneShapes(**shapes[1])
+            out = out + ({"world_map_shapes": counts},)
         return out
 
     try:

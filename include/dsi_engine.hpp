@@ -37,6 +37,7 @@
 #include "dsi_map_eval.h"
 #include "dsi_map_components.h"
 #include "dsi_map_knn.h"
+#include "dsi_map_pca.h"
 #include "dsi_map_prune.h"
 #include "dsi_map_merge.h"
 #include "dsi_map_align.h"
@@ -1714,6 +1715,51 @@ inline MapKnnThreshold knn_threshold(const MapKnnInfo& info, double std_mult)
 {
     return knn_threshold(info.n_scored, info.sum_q, info.sum_q2, std_mult);
 }
+// the local shape (dsi_map_pca.h): the pass's options -- the defaults take the 8 nearest cells within the radius and ask
+// for two of them --, the selection's -- curves and surfaces stay, scattered and sparse cells leave --, and what comes back
+struct MapPcaOptions : dsx_map_pca_opts_t {
+    explicit MapPcaOptions(double radius_, int k_ = 8) : dsx_map_pca_opts_t{}
+    {
+        min_points = min_windows = 1;
+        k = k_;
+        min_found = 2;
+        radius = radius_;
+    }
+    MapPcaOptions& lookAt(double x, double y, double z)  // the normals turn towards this point
+    {
+        orient = 1;
+        viewpoint[0] = x, viewpoint[1] = y, viewpoint[2] = z;
+        return *this;
+    }
+};
+struct MapPcaSelection : dsx_map_pca_selection_t {
+    explicit MapPcaSelection(uint32_t keep_ = DSX_PCA_LINEAR | DSX_PCA_PLANAR, bool remove_sparse_ = true, bool shrink_ = false)
+        : dsx_map_pca_selection_t{}
+    {
+        keep_labels = keep_;
+        remove_sparse = remove_sparse_ ? 1 : 0;
+        shrink = shrink_ ? 1 : 0;
+    }
+};
+using MapPcaInfo = dsx_map_pca_info_t;
+using MapPcaSelectInfo = dsx_map_pca_select_info_t;
+using PcaRow = dsx_pca_row_t;
+struct MapShapes {  // one row per query, in extract's order under the pass's filter: normal, tangent, eval 3 floats each
+    std::vector<uint64_t> keys;
+    std::vector<float> normal, tangent, eval;
+    std::vector<uint16_t> members;
+    std::vector<uint8_t> label, flags;
+    std::vector<int64_t> moments;  // 9 per row (s[3], ss[6]) when the pass kept them, else empty
+    size_t size() const { return keys.size(); }
+};
+// one cell's local shape from its integer moments (dsx_pca_solve; no device is touched); viewpoint and p orient the normal
+inline PcaRow pca_solve(uint32_t m, const int64_t s[3], const int64_t ss[6], double quantum, const double* viewpoint = nullptr,
+                        const double* p = nullptr)
+{
+    PcaRow r;
+    check(dsx_pca_solve(m, s, ss, quantum, viewpoint ? 1 : 0, viewpoint, p, &r));
+    return r;
+}
 // merging and moving the state (dsi_map_merge.h): a map's exact state on the host, and what a merge counts
 struct MapState {  // by ascending key when sorted
     double leaf = 0.0;
@@ -2045,6 +2091,39 @@ public:
         return info;
     }
 
+    // the local shape of every cell (dsx_map_pca; the rule is stated in dsi_map_pca.h): the result stays on the device for
+    // fetchPca and pruneShapes until the map changes, and nothing else of the map changes
+    MapPcaInfo pca(const MapPcaOptions& opts)
+    {
+        MapPcaInfo info;
+        check(dsx_map_pca(h_, &opts, &info));
+        pca_moments_ = opts.keep_moments != 0;
+        return info;
+    }
+    // the rows of the last pca() (dsx_map_pca_fetch)
+    MapShapes fetchPca() const
+    {
+        MapShapes out;
+        size_t n = 0;
+        const int rc = dsx_map_pca_fetch(h_, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &n);
+        if (rc != DSI_OK && n == 0) check(rc);
+        out.keys.resize(n), out.normal.resize(3 * n), out.tangent.resize(3 * n), out.eval.resize(3 * n);
+        out.members.resize(n), out.label.resize(n), out.flags.resize(n);
+        if (pca_moments_) out.moments.resize(9 * n);
+        if (n)
+            check(dsx_map_pca_fetch(h_, out.keys.data(), out.normal.data(), out.tangent.data(), out.eval.data(), out.members.data(),
+                                    out.label.data(), out.flags.data(), pca_moments_ ? out.moments.data() : nullptr, nullptr, n, &n));
+        return out;
+    }
+    // keeps the cells of the last pca() whose label is in the selection and rebuilds the table around them
+    // (dsx_map_prune_pca); everything derived from the map is invalid afterwards
+    MapPcaSelectInfo pruneShapes(const MapPcaSelection& sel = MapPcaSelection())
+    {
+        MapPcaSelectInfo info;
+        check(dsx_map_prune_pca(h_, &sel, &info));
+        return info;
+    }
+
     // appends `other` (same context, same leaf) to this map on the device (dsx_map_merge; the rule is stated in
     // dsi_map_merge.h): this map becomes the map that had made its own integrate calls and then other's.  other is
     // unchanged; render, compare and classification of this map are invalid afterwards
@@ -2132,6 +2211,7 @@ private:
     Context& ctx_;
     dsi_map_t* h_ = nullptr;
     int width_ = 0, height_ = 0;  // of the last render
+    bool pca_moments_ = false;    // the last pca() kept its moments
 };
 
 // 3-D accuracy, completeness and F-score of the map `est` against the map `gt` (the curves of the reference's
