@@ -4132,6 +4132,16 @@ void map_render_release(dsi_map* mp)
     mp->render_valid = false;
 }
 
+// The map changes (or may change) from here on: every derived result is stale, the selections with the passes they were
+// made on.  The render keeps its buffers (map_render_release drops them: a render of another size).  A reader of a
+// *_select_valid flag tests the parent flag first and a parent pass clears its selection when it starts, so that clearing
+// the selections here is not observable; it keeps the list in one place.
+void map_changed(dsi_map* mp)
+{
+    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = false;
+    mp->comp_valid = mp->comp_select_valid = mp->knn_valid = mp->knn_select_valid = mp->pca_valid = mp->pca_select_valid = false;
+}
+
 // the table doubled until occupied + n <= 3/4 of its slots (the caller checked that 2^27 slots are enough)
 int map_grow_for(dsi_map* mp, size_t n)
 {
@@ -4156,7 +4166,7 @@ int map_grow_for(dsi_map* mp, size_t n)
 int map_integrate_call(dsi_map* mp, size_t n, const std::function<hipError_t(uint32_t, const dsi::MapTable&)>& launch, size_t* n_accepted,
                        size_t* n_rejected)
 {
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->knn_valid = mp->pca_valid = false;  // (the map may change from here on)
+    map_changed(mp);
     REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
     REQUIRE(mp->calls < 0xffffffffull, DSI_ERR_INVALID, "at most 2^32 - 1 integrate calls per map");
     REQUIRE((mp->host_ctr[0] + n) * 4 <= ((uint64_t)3 << kMapMaxLog2), DSI_ERR_INVALID,
@@ -4204,6 +4214,16 @@ int map_count_device(dsi_map* mp, uint32_t min_points, uint32_t min_windows, siz
     HIP_TRY(hipMemcpyAsync(&n, mp->blk.p + words - 1, sizeof n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     *total = n;
+    return DSI_OK;
+}
+
+// what every dsx_map_*_fetch does before its gather: the cells under the pass's filter counted and scanned into mp->blk,
+// *n and *total their number, refused when `capacity` is smaller.  *total == 0: there is nothing to gather.  Synchronises.
+int map_fetch_count(dsi_map* mp, uint32_t min_points, uint32_t min_windows, size_t capacity, size_t* n, size_t* total)
+{
+    if (int rc = map_count_device(mp, min_points, min_windows, total)) return rc;
+    *n = *total;
+    REQUIRE(capacity >= *total, DSI_ERR_INVALID, "capacity of %zu cells is too small: %zu needed", capacity, *total);
     return DSI_OK;
 }
 
@@ -4260,7 +4280,7 @@ int dsi_map_destroy(dsi_map_t* mp)
 int dsi_map_reset(dsi_map_t* mp)
 {
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->knn_valid = mp->pca_valid = false;
+    map_changed(mp);
     if (int rc = set_device(mp->ctx)) return rc;
     HIP_TRY(hipMemsetAsync(mp->block.p, 0, dsi::map_table_bytes(mp->cap_log2), mp->ctx->stream));
     HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof mp->host_ctr, mp->ctx->stream));
@@ -4579,9 +4599,7 @@ int dsx_map_compare_fetch(dsi_map_t* a, float* dist_host, uint64_t* keys_host, s
             "no compare of the map as it stands: call dsx_map_compare (after the last dsi_map_reset or integrate call)");
     if (int rc = set_device(a->ctx)) return rc;
     size_t total = 0;
-    if (int rc = map_count_device(a, a->cmp_min_points, a->cmp_min_windows, &total)) return rc;
-    *n = total;
-    REQUIRE(capacity >= total, DSI_ERR_INVALID, "capacity of %zu cells is too small: %zu needed", capacity, total);
+    if (int rc = map_fetch_count(a, a->cmp_min_points, a->cmp_min_windows, capacity, n, &total)) return rc;
     if (!total) return DSI_OK;
     hipStream_t st = a->ctx->stream;
     HIP_TRY(a->cmp_dist_out.reserve(total));
@@ -4654,6 +4672,42 @@ void map_prune_info(const dsi_map* mp, const unsigned long long* ctr, dsx_map_pr
     info->capacity = (uint64_t)1 << mp->cap_log2;
 }
 
+// The rebuild that every prune ends with: the `kept` cells with reason_dev[slot] == 0 into a fresh table, of the smallest
+// size that holds them at 3/4 when `shrink`, else of the present size.  Nothing leaves (!removed_any) and the size stays:
+// the table is the result already.  The new table is allocated before anything is touched -- when that fails the map and
+// its derived results are as the caller left them --, then map_changed, then the rebuild on the map's stream; synchronises.
+int map_rebuild_kept(dsi_map* mp, const uint8_t* reason_dev, unsigned long long kept, bool removed_any, int shrink)
+{
+    hipStream_t st = mp->ctx->stream;
+    uint32_t want = mp->cap_log2;
+    if (shrink)
+        for (want = kMapMinLog2; kept * 4 > ((uint64_t)3 << want); ++want) {
+        }
+    DevBuf<unsigned char> block;
+    const bool rebuild = removed_any || want != mp->cap_log2;
+    if (rebuild) {
+        const hipError_t e = block.reserve(dsi::map_table_bytes(want));
+        if (e != hipSuccess)
+            return fail(DSI_ERR_HIP, "a pruned table of 2^%u slots could not be allocated (%s): the map is unchanged", want,
+                        hipGetErrorString(e));
+    }
+    map_changed(mp);
+    if (!rebuild) return DSI_OK;
+    HIP_TRY(hipMemsetAsync(block.p, 0, dsi::map_table_bytes(want), st));
+    HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof(unsigned long long), st));  // occupied: the rebuild counts the cells it moves
+    if (kept)
+        HIP_TRY(dsi::launch_map_prune_rehash(st, dsi::map_table_at(mp->block.p, mp->cap_log2), dsi::map_table_at(block.p, want), reason_dev,
+                                             mp->ctr.p));
+    HIP_TRY(hipMemcpyAsync(mp->host_ctr, mp->ctr.p, sizeof mp->host_ctr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    mp->block = std::move(block);  // (frees the old table)
+    mp->cap_log2 = want;
+    REQUIRE(mp->host_ctr[3] == 0 && mp->host_ctr[0] == kept, DSI_ERR_HIP,
+            "the pruned table holds %llu of %llu kept cells (%llu found it full): an engine bug, the map is unusable", mp->host_ctr[0], kept,
+            mp->host_ctr[3]);
+    return DSI_OK;
+}
+
 }  // namespace
 
 int dsx_map_prune_classify(dsi_map_t* mp, const dsx_map_prune_opts_t* opts, dsx_map_prune_info_t* info)
@@ -4677,9 +4731,7 @@ int dsx_map_prune_fetch(dsi_map_t* mp, uint8_t* reason_host, uint64_t* keys_host
             "no classification of the map as it stands: call dsx_map_prune_classify (after the last reset, integrate call or prune)");
     if (int rc = set_device(mp->ctx)) return rc;
     size_t total = 0;
-    if (int rc = map_count_device(mp, 1, 1, &total)) return rc;
-    *n = total;
-    REQUIRE(capacity >= total, DSI_ERR_INVALID, "capacity of %zu cells is too small: %zu needed", capacity, total);
+    if (int rc = map_fetch_count(mp, 1, 1, capacity, n, &total)) return rc;
     if (!total) return DSI_OK;
     hipStream_t st = mp->ctx->stream;
     HIP_TRY(mp->prune_reason_out.reserve(total));
@@ -4698,35 +4750,11 @@ int dsx_map_prune(dsi_map_t* mp, const dsx_map_prune_opts_t* opts, dsx_map_prune
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
     REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
     if (int rc = set_device(mp->ctx)) return rc;
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->knn_valid = mp->pca_valid = false;
-    hipStream_t st = mp->ctx->stream;
+    map_changed(mp);  // (before the classification: this prune's results are stale even when the rebuild cannot allocate)
     unsigned long long ctr[dsi::kMapPruneCounters] = {0, 0, 0, 0, 0, 0};
     if (int rc = map_prune_classify_device(mp, opts, ctr)) return rc;
-    const unsigned long long kept = ctr[0];
-    uint32_t want = mp->cap_log2;
-    if (opts->shrink)
-        for (want = kMapMinLog2; kept * 4 > ((uint64_t)3 << want); ++want) {
-        }
-    const bool none_removed = ctr[1] + ctr[2] + ctr[3] + ctr[4] + ctr[5] == 0;
-    if (!(none_removed && want == mp->cap_log2)) {  // (nothing leaves and the size stays: the table is the result already)
-        DevBuf<unsigned char> block;
-        hipError_t e = block.reserve(dsi::map_table_bytes(want));
-        if (e != hipSuccess)
-            return fail(DSI_ERR_HIP, "a pruned table of 2^%u slots could not be allocated (%s): the map is unchanged", want,
-                        hipGetErrorString(e));
-        HIP_TRY(hipMemsetAsync(block.p, 0, dsi::map_table_bytes(want), st));
-        HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof(unsigned long long), st));  // occupied: the rebuild counts the cells it moves
-        if (kept)
-            HIP_TRY(dsi::launch_map_prune_rehash(st, dsi::map_table_at(mp->block.p, mp->cap_log2), dsi::map_table_at(block.p, want),
-                                                 mp->prune_reason.p, mp->ctr.p));
-        HIP_TRY(hipMemcpyAsync(mp->host_ctr, mp->ctr.p, sizeof mp->host_ctr, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        mp->block = std::move(block);  // (frees the old table)
-        mp->cap_log2 = want;
-        REQUIRE(mp->host_ctr[3] == 0 && mp->host_ctr[0] == kept, DSI_ERR_HIP,
-                "the pruned table holds %llu of %llu kept cells (%llu found it full): an engine bug, the map is unusable", mp->host_ctr[0],
-                kept, mp->host_ctr[3]);
-    }
+    const bool removed_any = ctr[1] + ctr[2] + ctr[3] + ctr[4] + ctr[5] != 0;
+    if (int rc = map_rebuild_kept(mp, mp->prune_reason.p, ctr[0], removed_any, opts->shrink)) return rc;
     map_prune_info(mp, ctr, info);
     return DSI_OK;
 }
@@ -4837,9 +4865,7 @@ int dsx_map_components_fetch(dsi_map_t* mp, uint64_t* keys_host, uint64_t* label
             "no selection on this labelling: call dsx_map_components_select before asking for reasons");
     if (int rc = set_device(mp->ctx)) return rc;
     size_t total = 0;
-    if (int rc = map_count_device(mp, mp->comp_min_points, mp->comp_min_windows, &total)) return rc;
-    *count = total;
-    REQUIRE(capacity >= total, DSI_ERR_INVALID, "capacity of %zu cells is too small: %zu needed", capacity, total);
+    if (int rc = map_fetch_count(mp, mp->comp_min_points, mp->comp_min_windows, capacity, count, &total)) return rc;
     if (!total) return DSI_OK;
     hipStream_t st = mp->ctx->stream;
     HIP_TRY(mp->key_out.reserve(total));
@@ -4905,39 +4931,11 @@ int dsx_map_prune_components(dsi_map_t* mp, const dsx_map_components_selection_t
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
     if (int rc = check_labelling(mp)) return rc;
     if (int rc = set_device(mp->ctx)) return rc;
-    hipStream_t st = mp->ctx->stream;
     mp->comp_select_valid = false;
     unsigned long long ctr[dsi::kMapCompSelectCounters] = {0, 0, 0, 0, 0, 0};
     if (int rc = map_components_select_device(mp, sel, ctr)) return rc;
     mp->comp_select_valid = true;  // (the reasons are those of the map as it stands, should the rebuild fail to allocate)
-    const unsigned long long kept = ctr[0];
-    uint32_t want = mp->cap_log2;
-    if (sel->shrink)
-        for (want = kMapMinLog2; kept * 4 > ((uint64_t)3 << want); ++want) {
-        }
-    DevBuf<unsigned char> block;
-    const bool rebuild = !(ctr[1] + ctr[2] + ctr[3] + ctr[4] == 0 && want == mp->cap_log2);  // (else the table is the result already)
-    if (rebuild) {
-        const hipError_t e = block.reserve(dsi::map_table_bytes(want));
-        if (e != hipSuccess)
-            return fail(DSI_ERR_HIP, "a pruned table of 2^%u slots could not be allocated (%s): the map is unchanged", want,
-                        hipGetErrorString(e));
-    }
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->comp_select_valid = mp->knn_valid = mp->pca_valid = false;
-    if (rebuild) {
-        HIP_TRY(hipMemsetAsync(block.p, 0, dsi::map_table_bytes(want), st));
-        HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof(unsigned long long), st));  // occupied: the rebuild counts the cells it moves
-        if (kept)
-            HIP_TRY(dsi::launch_map_prune_rehash(st, dsi::map_table_at(mp->block.p, mp->cap_log2), dsi::map_table_at(block.p, want),
-                                                 mp->comp_reason.p, mp->ctr.p));
-        HIP_TRY(hipMemcpyAsync(mp->host_ctr, mp->ctr.p, sizeof mp->host_ctr, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        mp->block = std::move(block);  // (frees the old table)
-        mp->cap_log2 = want;
-        REQUIRE(mp->host_ctr[3] == 0 && mp->host_ctr[0] == kept, DSI_ERR_HIP,
-                "the pruned table holds %llu of %llu kept cells (%llu found it full): an engine bug, the map is unusable", mp->host_ctr[0],
-                kept, mp->host_ctr[3]);
-    }
+    if (int rc = map_rebuild_kept(mp, mp->comp_reason.p, ctr[0], ctr[1] + ctr[2] + ctr[3] + ctr[4] != 0, sel->shrink)) return rc;
     map_components_select_info(mp, ctr, info);
     return DSI_OK;
 }
@@ -5127,9 +5125,7 @@ int dsx_map_knn_fetch(dsi_map_t* mp, uint64_t* keys_host, uint8_t* found_host, f
             "no selection on this self query: call dsx_map_knn_select before asking for reasons");
     if (int rc = set_device(mp->ctx)) return rc;
     size_t total = 0;
-    if (int rc = map_count_device(mp, mp->knn_opts.min_points, mp->knn_opts.min_windows, &total)) return rc;
-    *count = total;
-    REQUIRE(capacity >= total, DSI_ERR_INVALID, "capacity of %zu cells is too small: %zu needed", capacity, total);
+    if (int rc = map_fetch_count(mp, mp->knn_opts.min_points, mp->knn_opts.min_windows, capacity, count, &total)) return rc;
     if (!total) return DSI_OK;
     hipStream_t st = mp->ctx->stream;
     HIP_TRY(mp->key_out.reserve(total));
@@ -5156,41 +5152,12 @@ int dsx_map_prune_knn(dsi_map_t* mp, const dsx_map_knn_selection_t* sel, dsx_map
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
     if (int rc = check_self_query(mp)) return rc;
     if (int rc = set_device(mp->ctx)) return rc;
-    hipStream_t st = mp->ctx->stream;
     mp->knn_select_valid = false;
     unsigned long long ctr[dsi::kMapKnnSelectCounters] = {0, 0, 0, 0};
     dsx_map_knn_select_info_t thr = {};
     if (int rc = map_knn_select_device(mp, sel, ctr, &thr)) return rc;
     mp->knn_select_valid = true;  // (the reasons are those of the map as it stands, should the rebuild fail to allocate)
-    const unsigned long long kept = ctr[0];
-    uint32_t want = mp->cap_log2;
-    if (sel->shrink)
-        for (want = kMapMinLog2; kept * 4 > ((uint64_t)3 << want); ++want) {
-        }
-    DevBuf<unsigned char> block;
-    const bool rebuild = !(ctr[1] + ctr[2] + ctr[3] == 0 && want == mp->cap_log2);  // (else the table is the result already)
-    if (rebuild) {
-        const hipError_t e = block.reserve(dsi::map_table_bytes(want));
-        if (e != hipSuccess)
-            return fail(DSI_ERR_HIP, "a pruned table of 2^%u slots could not be allocated (%s): the map is unchanged", want,
-                        hipGetErrorString(e));
-    }
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->comp_select_valid = false;
-    mp->knn_valid = mp->knn_select_valid = mp->pca_valid = false;
-    if (rebuild) {
-        HIP_TRY(hipMemsetAsync(block.p, 0, dsi::map_table_bytes(want), st));
-        HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof(unsigned long long), st));  // occupied: the rebuild counts the cells it moves
-        if (kept)
-            HIP_TRY(dsi::launch_map_prune_rehash(st, dsi::map_table_at(mp->block.p, mp->cap_log2), dsi::map_table_at(block.p, want),
-                                                 mp->knn_reason.p, mp->ctr.p));
-        HIP_TRY(hipMemcpyAsync(mp->host_ctr, mp->ctr.p, sizeof mp->host_ctr, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        mp->block = std::move(block);  // (frees the old table)
-        mp->cap_log2 = want;
-        REQUIRE(mp->host_ctr[3] == 0 && mp->host_ctr[0] == kept, DSI_ERR_HIP,
-                "the pruned table holds %llu of %llu kept cells (%llu found it full): an engine bug, the map is unusable", mp->host_ctr[0],
-                kept, mp->host_ctr[3]);
-    }
+    if (int rc = map_rebuild_kept(mp, mp->knn_reason.p, ctr[0], ctr[1] + ctr[2] + ctr[3] != 0, sel->shrink)) return rc;
     map_knn_select_info(mp, ctr, thr, info);
     return DSI_OK;
 }
@@ -5324,9 +5291,7 @@ int dsx_map_pca_fetch(dsi_map_t* mp, uint64_t* keys_host, float* normal_host, fl
             "no selection on this pass: call dsx_map_pca_select before asking for reasons");
     if (int rc = set_device(mp->ctx)) return rc;
     size_t total = 0;
-    if (int rc = map_count_device(mp, mp->pca_opts.min_points, mp->pca_opts.min_windows, &total)) return rc;
-    *count = total;
-    REQUIRE(capacity >= total, DSI_ERR_INVALID, "capacity of %zu cells is too small: %zu needed", capacity, total);
+    if (int rc = map_fetch_count(mp, mp->pca_opts.min_points, mp->pca_opts.min_windows, capacity, count, &total)) return rc;
     if (!total) return DSI_OK;
     hipStream_t st = mp->ctx->stream;
     HIP_TRY(mp->key_out.reserve(total));
@@ -5402,40 +5367,11 @@ int dsx_map_prune_pca(dsi_map_t* mp, const dsx_map_pca_selection_t* sel, dsx_map
     REQUIRE(mp, DSI_ERR_INVALID, "map is null");
     if (int rc = check_pca_pass(mp)) return rc;
     if (int rc = set_device(mp->ctx)) return rc;
-    hipStream_t st = mp->ctx->stream;
     mp->pca_select_valid = false;
     unsigned long long ctr[dsi::kMapPcaSelectCounters] = {0, 0, 0, 0};
     if (int rc = map_pca_select_device(mp, sel, ctr)) return rc;
     mp->pca_select_valid = true;  // (the reasons are those of the map as it stands, should the rebuild fail to allocate)
-    const unsigned long long kept = ctr[0];
-    uint32_t want = mp->cap_log2;
-    if (sel->shrink)
-        for (want = kMapMinLog2; kept * 4 > ((uint64_t)3 << want); ++want) {
-        }
-    DevBuf<unsigned char> block;
-    const bool rebuild = !(ctr[1] + ctr[2] + ctr[3] == 0 && want == mp->cap_log2);  // (else the table is the result already)
-    if (rebuild) {
-        const hipError_t e = block.reserve(dsi::map_table_bytes(want));
-        if (e != hipSuccess)
-            return fail(DSI_ERR_HIP, "a pruned table of 2^%u slots could not be allocated (%s): the map is unchanged", want,
-                        hipGetErrorString(e));
-    }
-    mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = mp->comp_valid = mp->comp_select_valid = false;
-    mp->knn_valid = mp->knn_select_valid = mp->pca_valid = mp->pca_select_valid = false;
-    if (rebuild) {
-        HIP_TRY(hipMemsetAsync(block.p, 0, dsi::map_table_bytes(want), st));
-        HIP_TRY(hipMemsetAsync(mp->ctr.p, 0, sizeof(unsigned long long), st));  // occupied: the rebuild counts the cells it moves
-        if (kept)
-            HIP_TRY(dsi::launch_map_prune_rehash(st, dsi::map_table_at(mp->block.p, mp->cap_log2), dsi::map_table_at(block.p, want),
-                                                 mp->pca_reason.p, mp->ctr.p));
-        HIP_TRY(hipMemcpyAsync(mp->host_ctr, mp->ctr.p, sizeof mp->host_ctr, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        mp->block = std::move(block);  // (frees the old table)
-        mp->cap_log2 = want;
-        REQUIRE(mp->host_ctr[3] == 0 && mp->host_ctr[0] == kept, DSI_ERR_HIP,
-                "the pruned table holds %llu of %llu kept cells (%llu found it full): an engine bug, the map is unusable", mp->host_ctr[0],
-                kept, mp->host_ctr[3]);
-    }
+    if (int rc = map_rebuild_kept(mp, mp->pca_reason.p, ctr[0], ctr[1] + ctr[2] + ctr[3] != 0, sel->shrink)) return rc;
     map_pca_select_info(mp, ctr, info);
     return DSI_OK;
 }
@@ -5472,7 +5408,7 @@ int map_merge_apply(dsi_map* dst, const MapMergeSource& src, dsx_map_merge_info_
     HIP_TRY(dst->merge_ctr.reserve(dsi::kMapMergeCounters));
     const uint64_t growths_before = dst->growths;
     if (int rc = map_grow_for(dst, (size_t)src.cells)) return rc;                 // (a failed allocation leaves dst as it is)
-    dst->render_valid = dst->compare_valid = dst->prune_valid = dst->align_valid = dst->comp_valid = dst->knn_valid = dst->pca_valid = false;  // (the map changes from here on)
+    map_changed(dst);
     unsigned long long mctr[dsi::kMapMergeCounters] = {0, 0};
     HIP_TRY(dsi::launch_map_merge(st, src.t, dsi::map_table_at(dst->block.p, dst->cap_log2), (uint32_t)dst->calls, src.accepted,
                                   src.rejected, dst->ctr.p, dst->merge_ctr.p));
@@ -5694,9 +5630,7 @@ int dsx_map_align_fetch(dsi_map_t* a, uint64_t* keys_a, uint64_t* keys_b, float*
             "no alignment step of the map as it stands: call dsx_map_align_step (after the last dsi_map_reset, integrate call, merge or prune)");
     if (int rc = set_device(a->ctx)) return rc;
     size_t total = 0;
-    if (int rc = map_count_device(a, a->align_min_points, a->align_min_windows, &total)) return rc;
-    *n = total;
-    REQUIRE(capacity >= total, DSI_ERR_INVALID, "capacity of %zu cells is too small: %zu needed", capacity, total);
+    if (int rc = map_fetch_count(a, a->align_min_points, a->align_min_windows, capacity, n, &total)) return rc;
     if (!total) return DSI_OK;
     hipStream_t st = a->ctx->stream;
     HIP_TRY(a->key_out.reserve(total));

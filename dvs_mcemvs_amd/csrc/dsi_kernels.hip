@@ -6891,13 +6891,116 @@ __device__ inline bool map_passes(const MapTable& t, size_t i, uint32_t min_poin
     return i < ((size_t)1 << t.cap_log2) && t.keys[i] != 0ull && t.n[i] >= min_points && t.windows[i] >= min_windows;
 }
 
-// axis a of the centroid of slot i (key k, n points): m = ((double) c + (double) (S / n) * 2^-32) * leaf (the bracket is
+// what pc_key packed into key k on axis a: the 21-bit coordinate (an import checks it as it comes), and the cell index it
+// stands for
+__device__ inline uint32_t pc_packed_of(unsigned long long k, int a) { return (uint32_t)((k >> (21 * a)) & 0x1fffffull); }
+__device__ inline int pc_cell_of(unsigned long long k, int a) { return (int)pc_packed_of(k, a) - (kPcCellMax + 1); }
+
+// axis a of the centroid of slot i (key k, n points): m =((double) c + (double) (S / n) * 2^-32) * leaf (the bracket is
 // exact: 21 + 32 bits), as float -- the one expression that extraction and rendering share
 __device__ inline float map_centroid(const MapTable& t, size_t i, unsigned long long k, uint32_t n, int a, double leaf)
 {
-    const int c = (int)((k >> (21 * a)) & 0x1fffffull) - (kPcCellMax + 1);
     const unsigned long long Q = t.sums[3 * i + a] / (unsigned long long)n;
-    return (float)(((double)c + (double)Q * 0x1p-32) * leaf);
+    return (float)(((double)pc_cell_of(k, a) + (double)Q * 0x1p-32) * leaf);
+}
+
+// ---- the map's kernel skeleton: the counted slot walk and the compaction (DESIGN.md 7j "The map's kernel skeleton") ----
+// THE COUNTED SLOT WALK.  A kernel that visits every slot and counts what it saw is launched with at most
+// kMapRenderMaxBlocks workgroups, which walk the table in strides:
+//     MapCounts<N> cnt;                                         (before anything diverges)
+//     const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+//     for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) { i = base + threadIdx.x; ... cnt.count<k>(pred); }
+//     cnt.flush(ctr);
+// The contract: (1) the capacity is a multiple of the workgroup (a power of two >= kPcBlock), so i < cap for every thread
+// of every round (at most 2^27 / (1024 * 256) = 512 rounds) and (2) EVERY lane of a wave reaches every count() of every
+// round -- count() is a ballot: no `continue`, no early return and no divergent branch around it.  A wave keeps its N
+// counts in uniform registers; flush() adds them to LDS once per wave and the workgroup issues ONE global atomic per
+// non-zero counter.  One thread per slot with one global atomic per wave and counter was bound by exactly those atomics
+// -- 98 k of them on one cache line for a table of 2^21 slots, at the 83 per microsecond one line takes.
+// Kernels that walk something else than slots (pixels, incoming cells) keep (2) and guard the element instead of (1).
+constexpr uint32_t kMapRenderMaxBlocks = 1024;
+
+template <int N>
+struct MapCounts {
+    uint32_t c[N] = {};  // the counts (the same in every lane of a wave)
+    uint32_t t[N] = {};  // the per-thread sums
+
+    static __device__ __forceinline__ uint32_t* lds()
+    {
+        __shared__ uint32_t s_cnt[N];
+        return s_cnt;
+    }
+    // by every thread of the workgroup; a kernel's own LDS words zeroed before this are covered by the same barrier
+    __device__ __forceinline__ MapCounts()
+    {
+        if (threadIdx.x < N) lds()[threadIdx.x] = 0u;
+        __syncthreads();
+    }
+    template <int K>
+    __device__ __forceinline__ void count(bool pred)
+    {
+        static_assert(K >= 0 && K < N, "no such counter");
+        c[K] += (uint32_t)__popcll(__ballot(pred));
+    }
+    // counter K as a per-THREAD sum instead of a count (the workgroup's total must stay below 2^32); a counter is fed by
+    // count<K> or by sum<K>, not by both.  The sums live here, not in a local of the kernel beside this object: with
+    // k_map_pca's members in such a local the compiler kept all eight counts in vector registers, and the kernel lost a wave
+    template <int K>
+    __device__ __forceinline__ void sum(uint32_t v)
+    {
+        static_assert(K >= 0 && K < N, "no such counter");
+        t[K] += v;
+    }
+    // the LDS stage; after it every thread may read the workgroup's totals
+    __device__ __forceinline__ const uint32_t* stage()
+    {
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+            if (t[k]) atomicAdd(&lds()[k], t[k]);  // (a counter that is never summed costs nothing: its t is the constant 0)
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int k = 0; k < N; ++k)
+                if (c[k]) atomicAdd(&lds()[k], c[k]);
+        }
+        __syncthreads();
+        return lds();
+    }
+    // the workgroup's total of counter k, for every thread once a flush has staged it
+    __device__ __forceinline__ uint32_t total(int k) const { return lds()[k]; }
+    // counter k into ctr[k]
+    __device__ __forceinline__ void flush(unsigned long long* __restrict__ ctr)
+    {
+        const uint32_t* s = stage();
+        if (threadIdx.x < N && s[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s[threadIdx.x]);
+    }
+    // counter k into *dst[k], thread k's atomic (the indices are compile-time constants: dst stays in registers)
+    __device__ __forceinline__ void flush_to(unsigned long long* const (&dst)[N])
+    {
+        const uint32_t* s = stage();
+#pragma unroll
+        for (uint32_t k = 0; k < (uint32_t)N; ++k)
+            if (threadIdx.x == k && s[k]) atomicAdd(dst[k], (unsigned long long)s[k]);
+    }
+};
+
+// THE COMPACTION.  Output place blk_off[tile] + rank for every slot that keep(i) keeps, in slot order: blk_off is the
+// scanned count per tile of kPcBlock slots (k_map_flag_count's, or a kernel's that counts the same predicate), the rank
+// comes from pc_block_exclusive, which EVERY thread of the workgroup calls EVERY round (it holds barriers), and
+// write(i, at) copies the slot's row.  Walks the 2^cap_log2 slots in strides; ONE_ROUND is for the kernels that are launched
+// with one workgroup per tile: the same round without the loop around it and without its test of base (the grid is the
+// tiles, and map_passes tests i against the capacity); with the loop k_map_extract's call took 6 % longer on 827,644 cells.
+template <bool ONE_ROUND = false, typename Keep, typename Write>
+__device__ __forceinline__ void map_compact(uint32_t cap_log2, const uint32_t* __restrict__ blk_off, Keep keep, Write write)
+{
+    const size_t cap = (size_t)1 << cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; ONE_ROUND || base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        const bool f = keep(i);
+        uint32_t total;
+        const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);
+        if (f) write(i, (size_t)blk_off[base / kPcBlock] + rank);
+        if (ONE_ROUND) break;
+    }
 }
 
 // blk[b] = number of slots in [b * kPcBlock, (b + 1) * kPcBlock) that hold a cell passing the filter
@@ -6915,19 +7018,17 @@ __global__ void __launch_bounds__(kPcBlock) k_map_extract(MapTable t, uint32_t m
                                                           uint32_t* __restrict__ n_out, uint32_t* __restrict__ w_out,
                                                           unsigned long long* __restrict__ key_out)
 {
-    const size_t i = (size_t)blockIdx.x * kPcBlock + threadIdx.x;
-    const bool f = map_passes(t, i, min_points, min_windows);
-    uint32_t total;
-    const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);
-    if (!f) return;
-    const size_t o = (size_t)blk_off[blockIdx.x] + rank;
-    const unsigned long long k = t.keys[i];
-    const uint32_t n = t.n[i];
+    map_compact<true>(
+        t.cap_log2, blk_off, [&](size_t i) { return map_passes(t, i, min_points, min_windows); },
+        [&](size_t i, size_t o) {
+            const unsigned long long k = t.keys[i];
+            const uint32_t n = t.n[i];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) xyz[3 * o + a] = map_centroid(t, i, k, n, a, leaf);
-    n_out[o] = n;
-    w_out[o] = t.windows[i];
-    key_out[o] = k;
+            for (int a = 0; a < 3; ++a) xyz[3 * o + a] = map_centroid(t, i, k, n, a, leaf);
+            n_out[o] = n;
+            w_out[o] = t.windows[i];
+            key_out[o] = k;
+        });
 }
 
 // The map as a pinhole camera at v.T (world -> view) sees it: a pass over the table's SLOTS, no compaction.  A cell that
@@ -6942,20 +7043,11 @@ __global__ void __launch_bounds__(kPcBlock) k_map_extract(MapTable t, uint32_t m
 // The image tests are made in double before anything becomes an integer: iu + dx with |dx| <= splat <= 4 is inside
 // [0, width) for some dx iff -splat <= iu <= width - 1 + splat, which huge, infinite and NaN values fail; past that test
 // iu is an integer in [-4, 2^26 + 3] and the per-pixel tests are exact in int.
-// At most kMapRenderMaxBlocks workgroups walk the table in strides (the capacity is a multiple of the workgroup, so every
-// lane of a wave takes part in every ballot; at most 2^27 / (1024 * 256) = 512 rounds): a wave keeps its four counts in
-// uniform registers, adds them to LDS once, and the workgroup issues one global atomic per counter.  One thread per slot
-// with one global atomic per wave and counter was bound by exactly those atomics -- 98 k of them on one cache line for a
-// table of 2^21 slots, at the 83 per microsecond one line takes.
-constexpr uint32_t kMapRenderMaxBlocks = 1024;
-
+// A counted slot walk (MapCounts).
 __global__ void __launch_bounds__(kPcBlock) k_map_render(MapTable t, MapView v, double leaf, unsigned long long* __restrict__ zkey,
                                                          uint32_t* __restrict__ hits, unsigned long long* __restrict__ ctr)
 {
-    __shared__ uint32_t s_cnt[4];
-    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    uint32_t c_f = 0, c_clip = 0, c_out = 0, c_draw = 0;  // (the same in every lane of a wave)
+    MapCounts<4> cnt;
     const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
     for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
         const size_t i = base + threadIdx.x;
@@ -6991,32 +7083,22 @@ __global__ void __launch_bounds__(kPcBlock) k_map_render(MapTable t, MapView v, 
                 }
             }
         }
-        c_f += (uint32_t)__popcll(__ballot(f));
-        c_clip += (uint32_t)__popcll(__ballot(clipped));
-        c_out += (uint32_t)__popcll(__ballot(outside));
-        c_draw += (uint32_t)__popcll(__ballot(f && !clipped && !outside));
+        cnt.count<0>(f);
+        cnt.count<1>(clipped);
+        cnt.count<2>(outside);
+        cnt.count<3>(f && !clipped && !outside);
     }
-    if ((threadIdx.x & 63) == 0) {
-        if (c_f) atomicAdd(&s_cnt[0], c_f);
-        if (c_clip) atomicAdd(&s_cnt[1], c_clip);
-        if (c_out) atomicAdd(&s_cnt[2], c_out);
-        if (c_draw) atomicAdd(&s_cnt[3], c_draw);
-    }
-    __syncthreads();
-    if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    cnt.flush(ctr);
 }
 
 // the winner's key unpacked per pixel -- depth = (float) Z and windows where hits > 0, zeros elsewhere, mask = hits > 0;
-// ctr[4] += covered pixels.  Strided and counted like k_map_render: one global atomic per workgroup.
+// ctr[4] += covered pixels.  MapCounts' walk over pixels: i is tested against npix, every lane reaches the count.
 __global__ void __launch_bounds__(kPcBlock) k_map_render_finish(const unsigned long long* __restrict__ zkey,
                                                                 const uint32_t* __restrict__ hits, uint32_t npix,
                                                                 float* __restrict__ depth, uint32_t* __restrict__ windows,
                                                                 uint8_t* __restrict__ mask, unsigned long long* __restrict__ ctr)
 {
-    __shared__ uint32_t s_cnt;
-    if (threadIdx.x == 0) s_cnt = 0u;
-    __syncthreads();
-    uint32_t c = 0;
+    MapCounts<1> cnt;
     const uint32_t stride = gridDim.x * kPcBlock;  // (<= 2^18; npix <= 2^26: base cannot wrap)
     for (uint32_t base = blockIdx.x * kPcBlock; base < npix; base += stride) {
         const uint32_t i = base + threadIdx.x;
@@ -7028,26 +7110,22 @@ __global__ void __launch_bounds__(kPcBlock) k_map_render_finish(const unsigned l
             windows[i] = covered ? 0xffffffffu - (uint32_t)k : 0u;
             mask[i] = covered ? 1 : 0;
         }
-        c += (uint32_t)__popcll(__ballot(covered));
+        cnt.count<0>(covered);
     }
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt, c);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_cnt) atomicAdd(&ctr[4], (unsigned long long)s_cnt);
+    cnt.flush(ctr + 4);
 }
 
 // ---- the map scored in 3-D (include/dsi_map_eval.h dsx_map_*; DESIGN.md 7j "Scoring the map in 3-D") ----
 // A depth image as one integrate call: one thread per pixel.  A pixel (u, v) is integrated iff mask is NULL or mask > 0,
 // and d is finite and min_depth <= d <= max_depth (in double; NaN fails); its float32 point is
 // x = (float) ((((double) u - cx) / fx) * (double) d), y alike, z = d, which goes through map_integrate_point: the call
-// is dsi_map_integrate of that point list, bit for bit.  ctr as k_map_integrate's, one global atomic per workgroup and
-// counter (the ballots go to LDS first).
+// is dsi_map_integrate of that point list, bit for bit.  ctr as k_map_integrate's, counted by MapCounts (one round: one
+// global atomic per workgroup and counter).
 __global__ void __launch_bounds__(kPcBlock) k_map_integrate_depth(const float* __restrict__ depth, const uint8_t* __restrict__ mask,
                                                                   MapDepthImage g, MapPose T, double leaf, uint32_t serial, MapTable t,
                                                                   unsigned long long* __restrict__ ctr)
 {
-    __shared__ uint32_t s_cnt[4];
-    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
+    MapCounts<4> cnt;
     const uint32_t i = blockIdx.x * kPcBlock + threadIdx.x;  // (npix <= 2^26)
     bool in = false, ok = false, fresh = false, full = false;
     if (i < g.npix && (mask == nullptr || mask[i] > 0)) {
@@ -7061,15 +7139,11 @@ __global__ void __launch_bounds__(kPcBlock) k_map_integrate_depth(const float* _
             map_integrate_point((double)x, (double)y, d, T, leaf, serial, t, &ok, &fresh, &full);
         }
     }
-    const unsigned long long b_new = __ballot(fresh), b_ok = __ballot(ok), b_rej = __ballot(in && !ok && !full), b_full = __ballot(full);
-    if ((threadIdx.x & 63) == 0) {
-        if (b_new) atomicAdd(&s_cnt[0], (uint32_t)__popcll(b_new));
-        if (b_ok) atomicAdd(&s_cnt[1], (uint32_t)__popcll(b_ok));
-        if (b_rej) atomicAdd(&s_cnt[2], (uint32_t)__popcll(b_rej));
-        if (b_full) atomicAdd(&s_cnt[3], (uint32_t)__popcll(b_full));
-    }
-    __syncthreads();
-    if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    cnt.count<0>(fresh);
+    cnt.count<1>(ok);
+    cnt.count<2>(in && !ok && !full);
+    cnt.count<3>(full);
+    cnt.flush(ctr);
 }
 
 // the slot of `keys` that holds k, ~0u when none does: read-only, from pc_hash(k) until the key or an empty slot, at
@@ -7086,26 +7160,58 @@ __device__ inline uint32_t map_find(const unsigned long long* __restrict__ keys,
     return ~0u;
 }
 
+// THE CANDIDATE SWEEP.  The point p against table t (mask = capacity - 1): per axis c = floor(p / leaf); the candidates
+// are the cells that pass the filter at c + o, |o| <= reach per axis, an index with |c + o| > kPcCellMax skipped (tested
+// in double, NaN included: a huge or non-finite c has no candidates) and the cell with key `self` (0: none) left out --
+// BEFORE the probe: tested after it, the key stays live over map_find and costs the callers registers and a wave of
+// occupancy; q = the candidate's extracted centroid; fn(slot, key, d2) with d2 = ((dx dx) + dy dy) + dz dz.  Every probe
+// loop is map_find's: bounded by the capacity.
+template <typename F>
+__device__ __forceinline__ void map_near_cells(const MapTable& t, uint32_t mask, uint32_t min_points, uint32_t min_windows, double leaf,
+                                               int reach, const double (&p)[3], unsigned long long self, F fn)
+{
+    double c[3];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) c[ax] = floor(p[ax] / leaf);
+    for (int oz = -reach; oz <= reach; ++oz) {
+        const double vz = c[2] + (double)oz;
+        if (!(fabs(vz) <= (double)kPcCellMax)) continue;  // (NaN included)
+        for (int oy = -reach; oy <= reach; ++oy) {
+            const double vy = c[1] + (double)oy;
+            if (!(fabs(vy) <= (double)kPcCellMax)) continue;
+            for (int ox = -reach; ox <= reach; ++ox) {
+                const double vx = c[0] + (double)ox;
+                if (!(fabs(vx) <= (double)kPcCellMax)) continue;
+                const unsigned long long kb = pc_key((int)vx, (int)vy, (int)vz);
+                __builtin_assume(kb != 0ull);  // (every packed coordinate is >= 1: with self == 0 the test below costs nothing)
+                if (kb == self) continue;
+                const uint32_t j = map_find(t.keys, mask, kb);
+                if (j == ~0u || !map_passes(t, j, min_points, min_windows)) continue;
+                const uint32_t nb = t.n[j];
+                const double dx = p[0] - (double)map_centroid(t, j, kb, nb, 0, leaf);
+                const double dy = p[1] - (double)map_centroid(t, j, kb, nb, 1, leaf);
+                const double dz = p[2] - (double)map_centroid(t, j, kb, nb, 2, leaf);
+                fn(j, kb, ((dx * dx) + dy * dy) + dz * dz);
+            }
+        }
+    }
+}
+
 // Every cell of `a` that passes a's filter against the cells of `b` that pass b's: p = a's extracted centroid (float,
-// widened); per axis c = floor(p / leaf_b); the candidates are b's cells at c + o, |o| <= reach per axis, an index with
-// |c + o| > kPcCellMax skipped (tested in double: a huge or non-finite c has no candidates); q = the candidate's extracted
-// centroid; d2 = ((dx dx) + dy dy) + dz dz; the minimum is kept (minima commute: the order of the offsets and of the
+// widened) swept over b by map_near_cells; the minimum d2 is kept (minima commute: the order of the offsets and of the
 // probing does not matter); d = sqrt(min d2), IEEE; MATCHED iff d <= radius (no candidate: d = +inf).  Matched:
 // hist[min((int) floor(d / w), n_bins - 1)] += 1, sum_q += (u64) floor((d / radius) * 2^32).  dist[slot] = (float) d or
-// +inf.  ctr: [0] matched, [1] unmatched, [2] sum_q.  Workgroups walk a's table in strides as k_map_render does: the
-// wave's ballots are summed in registers, the histogram and sum_q are accumulated in LDS, and a workgroup issues one
-// global atomic per counter and per non-empty bin.  Reads the tables, writes dist: a == b is legal.
+// +inf.  ctr: [0] matched, [1] unmatched, [2] sum_q.  A counted slot walk (MapCounts) over a's table; the histogram and
+// sum_q are accumulated in LDS beside the counts, and a workgroup issues one global atomic per counter and per non-empty
+// bin.  Reads the tables, writes dist: a == b is legal.
 __global__ void __launch_bounds__(kPcBlock) k_map_compare(MapTable a, MapTable b, MapCompare o, float* __restrict__ dist,
                                                           unsigned long long* __restrict__ hist, unsigned long long* __restrict__ ctr)
 {
     __shared__ uint32_t s_hist[kMapCompareMaxBins];
-    __shared__ uint32_t s_cnt[2];
     __shared__ unsigned long long s_sum;
     for (int j = threadIdx.x; j < o.n_bins; j += kPcBlock) s_hist[j] = 0u;
-    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
     if (threadIdx.x == 0) s_sum = 0ull;
-    __syncthreads();
-    uint32_t c_match = 0, c_un = 0;  // (the same in every lane of a wave)
+    MapCounts<2> cnt;
     unsigned long long sum_q = 0ull;
     const uint32_t bmask = (1u << b.cap_log2) - 1u;
     const size_t cap = (size_t)1 << a.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
@@ -7116,34 +7222,14 @@ __global__ void __launch_bounds__(kPcBlock) k_map_compare(MapTable a, MapTable b
         if (f) {
             const unsigned long long k = a.keys[i];
             const uint32_t n = a.n[i];
-            double p[3], c[3];
+            double p[3];
 #pragma unroll
-            for (int ax = 0; ax < 3; ++ax) {
-                p[ax] = (double)map_centroid(a, i, k, n, ax, o.leaf_a);
-                c[ax] = floor(p[ax] / o.leaf_b);
-            }
+            for (int ax = 0; ax < 3; ++ax) p[ax] = (double)map_centroid(a, i, k, n, ax, o.leaf_a);
             double best = INFINITY;
-            for (int oz = -o.reach; oz <= o.reach; ++oz) {
-                const double vz = c[2] + (double)oz;
-                if (!(fabs(vz) <= (double)kPcCellMax)) continue;  // (NaN included)
-                for (int oy = -o.reach; oy <= o.reach; ++oy) {
-                    const double vy = c[1] + (double)oy;
-                    if (!(fabs(vy) <= (double)kPcCellMax)) continue;
-                    for (int ox = -o.reach; ox <= o.reach; ++ox) {
-                        const double vx = c[0] + (double)ox;
-                        if (!(fabs(vx) <= (double)kPcCellMax)) continue;
-                        const unsigned long long kb = pc_key((int)vx, (int)vy, (int)vz);
-                        const uint32_t j = map_find(b.keys, bmask, kb);
-                        if (j == ~0u || !map_passes(b, j, o.min_points_b, o.min_windows_b)) continue;
-                        const uint32_t nb = b.n[j];
-                        const double dx = p[0] - (double)map_centroid(b, j, kb, nb, 0, o.leaf_b);
-                        const double dy = p[1] - (double)map_centroid(b, j, kb, nb, 1, o.leaf_b);
-                        const double dz = p[2] - (double)map_centroid(b, j, kb, nb, 2, o.leaf_b);
-                        const double d2 = ((dx * dx) + dy * dy) + dz * dz;
-                        if (d2 < best) best = d2;
-                    }
-                }
-            }
+            map_near_cells(b, bmask, o.min_points_b, o.min_windows_b, o.leaf_b, o.reach, p, 0ull,
+                           [&](uint32_t, unsigned long long, double d2) {
+                               if (d2 < best) best = d2;
+                           });
             const double d = sqrt(best);
             matched = d <= o.radius;
             dist[i] = matched ? (float)d : INFINITY;
@@ -7153,16 +7239,11 @@ __global__ void __launch_bounds__(kPcBlock) k_map_compare(MapTable a, MapTable b
                 sum_q += (unsigned long long)floor((d / o.radius) * 4294967296.0);
             }
         }
-        c_match += (uint32_t)__popcll(__ballot(matched));
-        c_un += (uint32_t)__popcll(__ballot(f && !matched));
+        cnt.count<0>(matched);
+        cnt.count<1>(f && !matched);
     }
     if (sum_q) atomicAdd(&s_sum, sum_q);
-    if ((threadIdx.x & 63) == 0) {
-        if (c_match) atomicAdd(&s_cnt[0], c_match);
-        if (c_un) atomicAdd(&s_cnt[1], c_un);
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    cnt.flush(ctr);
     if (threadIdx.x == 2 && s_sum) atomicAdd(&ctr[2], s_sum);
     for (int j = threadIdx.x; j < o.n_bins; j += kPcBlock)
         if (s_hist[j]) atomicAdd(&hist[j], (unsigned long long)s_hist[j]);
@@ -7173,14 +7254,12 @@ __global__ void __launch_bounds__(kPcBlock) k_map_compare_gather(MapTable t, uin
                                                                  const float* __restrict__ dist, const uint32_t* __restrict__ blk_off,
                                                                  float* __restrict__ dist_out, unsigned long long* __restrict__ key_out)
 {
-    const size_t i = (size_t)blockIdx.x * kPcBlock + threadIdx.x;
-    const bool f = map_passes(t, i, min_points, min_windows);
-    uint32_t total;
-    const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);
-    if (!f) return;
-    const size_t o = (size_t)blk_off[blockIdx.x] + rank;
-    dist_out[o] = dist[i];
-    key_out[o] = t.keys[i];
+    map_compact<true>(
+        t.cap_log2, blk_off, [&](size_t i) { return map_passes(t, i, min_points, min_windows); },
+        [&](size_t i, size_t o) {
+            dist_out[o] = dist[i];
+            key_out[o] = t.keys[i];
+        });
 }
 
 // ---- pruning the map (include/dsi_map_prune.h dsx_map_prune*; DESIGN.md 7j "Pruning") ----
@@ -7188,15 +7267,11 @@ __global__ void __launch_bounds__(kPcBlock) k_map_compare_gather(MapTable t, uin
 // without a cell.  1: n < min_points; 2: windows < min_windows (map_passes with the other bound at 0); 3: max_age >= 0 and
 // calls - stamp > max_age (stamp <= calls: the difference is exact in 32 bits); 4: use_box and the extracted centroid
 // (map_centroid, float, widened) outside [box_lo, box_hi] on some axis, compared in double (the centroid is finite; the
-// bounds may be infinite, never NaN).  ctr[r] += the cells with reason r, r = 1..4.  Walks the slots like k_map_render:
-// a wave keeps its counts in uniform registers, the workgroup sums them in LDS and issues one global atomic per counter.
+// bounds may be infinite, never NaN).  ctr[r] += the cells with reason r, r = 1..4.  A counted slot walk (MapCounts).
 __global__ void __launch_bounds__(kPcBlock) k_map_prune_reason(MapTable t, MapPrune o, uint8_t* __restrict__ first,
                                                                unsigned long long* __restrict__ ctr)
 {
-    __shared__ uint32_t s_cnt[4];
-    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    uint32_t c1 = 0, c2 = 0, c3 = 0, c4 = 0;  // (the same in every lane of a wave)
+    MapCounts<4> cnt;
     const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
     for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
         const size_t i = base + threadIdx.x;
@@ -7220,19 +7295,12 @@ __global__ void __launch_bounds__(kPcBlock) k_map_prune_reason(MapTable t, MapPr
             }
         }
         first[i] = (uint8_t)r;  // (cap is a multiple of the workgroup: i < cap)
-        c1 += (uint32_t)__popcll(__ballot(r == 1u));
-        c2 += (uint32_t)__popcll(__ballot(r == 2u));
-        c3 += (uint32_t)__popcll(__ballot(r == 3u));
-        c4 += (uint32_t)__popcll(__ballot(r == 4u));
+        cnt.count<0>(r == 1u);
+        cnt.count<1>(r == 2u);
+        cnt.count<2>(r == 3u);
+        cnt.count<3>(r == 4u);
     }
-    if ((threadIdx.x & 63) == 0) {
-        if (c1) atomicAdd(&s_cnt[0], c1);
-        if (c2) atomicAdd(&s_cnt[1], c2);
-        if (c3) atomicAdd(&s_cnt[2], c3);
-        if (c4) atomicAdd(&s_cnt[3], c4);
-    }
-    __syncthreads();
-    if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&ctr[1 + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    cnt.flush(ctr + 1);
 }
 
 // Criterion 5 for the cells that survived 1-4, judged on `first` alone (read-only here, so the outcome does not depend on
@@ -7240,14 +7308,11 @@ __global__ void __launch_bounds__(kPcBlock) k_map_prune_reason(MapTable t, MapPr
 // the neighbours are the OTHER cells at c + o, |o| <= reach per axis, an index with |c + o| > kPcCellMax skipped (it has no
 // key); a neighbour supports iff map_find finds it and first[its slot] == 0.  The sweep stops at min_neighbors supporters
 // (the count is only compared with that bound).  reason[slot] = 5 with fewer, else 0; every other slot keeps first[slot].
-// ctr[0] += kept, ctr[5] += removed here; walked and counted like k_map_prune_reason.
+// ctr[0] += kept, ctr[5] += removed here.  A counted slot walk (MapCounts).
 __global__ void __launch_bounds__(kPcBlock) k_map_prune_support(MapTable t, MapPrune o, const uint8_t* __restrict__ first,
                                                                 uint8_t* __restrict__ reason, unsigned long long* __restrict__ ctr)
 {
-    __shared__ uint32_t s_cnt[2];
-    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    uint32_t c_kept = 0, c_lone = 0;  // (the same in every lane of a wave)
+    MapCounts<2> cnt;
     const uint32_t mask = (1u << t.cap_log2) - 1u;
     const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
     for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
@@ -7257,7 +7322,7 @@ __global__ void __launch_bounds__(kPcBlock) k_map_prune_support(MapTable t, MapP
             const unsigned long long k = t.keys[i];
             int c[3];
 #pragma unroll
-            for (int a = 0; a < 3; ++a) c[a] = (int)((k >> (21 * a)) & 0x1fffffull) - (kPcCellMax + 1);
+            for (int a = 0; a < 3; ++a) c[a] = pc_cell_of(k, a);
             uint32_t found = 0;
             for (int oz = -o.reach; oz <= o.reach && found < o.min_neighbors; ++oz) {
                 const int vz = c[2] + oz;
@@ -7276,28 +7341,19 @@ __global__ void __launch_bounds__(kPcBlock) k_map_prune_support(MapTable t, MapP
             if (found < o.min_neighbors) r = 5u;
         }
         reason[i] = (uint8_t)r;
-        c_kept += (uint32_t)__popcll(__ballot(r == 0u));
-        c_lone += (uint32_t)__popcll(__ballot(r == 5u));
+        cnt.count<0>(r == 0u);
+        cnt.count<1>(r == 5u);
     }
-    if ((threadIdx.x & 63) == 0) {
-        if (c_kept) atomicAdd(&s_cnt[0], c_kept);
-        if (c_lone) atomicAdd(&s_cnt[1], c_lone);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_cnt[0]) atomicAdd(&ctr[0], (unsigned long long)s_cnt[0]);
-    if (threadIdx.x == 1 && s_cnt[1]) atomicAdd(&ctr[5], (unsigned long long)s_cnt[1]);
+    cnt.flush_to({&ctr[0], &ctr[5]});
 }
 
 // the kept cells (reason 0) of `from` with all their state into `to` (zeroed; keys are distinct, so a claimed slot has one
-// writer): k_map_rehash restricted by `reason`, walked in strides.  ctr[0] += the cells moved, one global atomic per
-// workgroup; ctr[3] += cells whose probe sequence ran through the whole of `to` (the host sizes it so that none does).
+// writer): k_map_rehash restricted by `reason`, as a counted slot walk (MapCounts).  ctr[0] += the cells moved;
+// ctr[3] += cells whose probe sequence ran through the whole of `to` (the host sizes it so that none does).
 __global__ void __launch_bounds__(kPcBlock) k_map_prune_rehash(MapTable from, MapTable to, const uint8_t* __restrict__ reason,
                                                                unsigned long long* __restrict__ ctr)
 {
-    __shared__ uint32_t s_cnt[2];
-    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    uint32_t c_moved = 0, c_full = 0;  // (the same in every lane of a wave)
+    MapCounts<2> cnt;
     const uint32_t mask = (1u << to.cap_log2) - 1u;
     const size_t cap = (size_t)1 << from.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
     for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
@@ -7317,16 +7373,10 @@ __global__ void __launch_bounds__(kPcBlock) k_map_prune_rehash(MapTable from, Ma
                 for (int a = 0; a < 3; ++a) to.sums[3 * (size_t)slot + a] = from.sums[3 * i + a];
             }
         }
-        c_moved += (uint32_t)__popcll(__ballot(moved));
-        c_full += (uint32_t)__popcll(__ballot(full));
+        cnt.count<0>(moved);
+        cnt.count<1>(full);
     }
-    if ((threadIdx.x & 63) == 0) {
-        if (c_moved) atomicAdd(&s_cnt[0], c_moved);
-        if (c_full) atomicAdd(&s_cnt[1], c_full);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_cnt[0]) atomicAdd(&ctr[0], (unsigned long long)s_cnt[0]);
-    if (threadIdx.x == 1 && s_cnt[1]) atomicAdd(&ctr[3], (unsigned long long)s_cnt[1]);
+    cnt.flush_to({&ctr[0], &ctr[3]});
 }
 
 // the classification compacted like k_map_extract's cells under the filter (1, 1) -- every cell --, with its blk_off: key
@@ -7335,31 +7385,26 @@ __global__ void __launch_bounds__(kPcBlock) k_map_prune_gather(MapTable t, const
                                                                const uint32_t* __restrict__ blk_off, uint8_t* __restrict__ reason_out,
                                                                unsigned long long* __restrict__ key_out)
 {
-    const size_t i = (size_t)blockIdx.x * kPcBlock + threadIdx.x;
-    const bool f = map_passes(t, i, 1u, 1u);
-    uint32_t total;
-    const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);
-    if (!f) return;
-    const size_t o = (size_t)blk_off[blockIdx.x] + rank;
-    reason_out[o] = reason[i];
-    key_out[o] = t.keys[i];
+    map_compact<true>(
+        t.cap_log2, blk_off, [&](size_t i) { return map_passes(t, i, 1u, 1u); },
+        [&](size_t i, size_t o) {
+            reason_out[o] = reason[i];
+            key_out[o] = t.keys[i];
+        });
 }
 
 // ---- the map's connected components (include/dsi_map_components.h dsx_map_components*; DESIGN.md 7j "Components") ----
 // A lock-free union-find over SLOT indices: parent[slot] = slot for a node (a cell that passes the filter), kMapCompNone
 // elsewhere; a component's root is its smallest slot.  The launches are fixed -- init, union, flatten, reduce, two for the
-// largest, count -- whatever the table holds.  Every kernel walks the slots like k_map_render and counts like
-// k_map_prune_reason.
+// largest, count -- whatever the table holds.  Every kernel walks the slots in strides; those that count are counted
+// slot walks (MapCounts).
 //
 // init: parent as above; label = all ones, cells = points = 0 (the reduce's atomics meet initialised words);
 // ctr[0] += nodes, ctr[1] += occupied slots that are no node.
 __global__ void __launch_bounds__(kPcBlock) k_map_comp_init(MapTable t, uint32_t min_points, uint32_t min_windows, MapComponents c,
                                                             unsigned long long* __restrict__ ctr)
 {
-    __shared__ uint32_t s_cnt[2];
-    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    uint32_t c_node = 0, c_other = 0;  // (the same in every lane of a wave)
+    MapCounts<2> cnt;
     const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
     for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
         const size_t i = base + threadIdx.x;
@@ -7368,15 +7413,10 @@ __global__ void __launch_bounds__(kPcBlock) k_map_comp_init(MapTable t, uint32_t
         c.label[i] = ~0ull;
         c.cells[i] = 0u;
         c.points[i] = 0ull;
-        c_node += (uint32_t)__popcll(__ballot(node));
-        c_other += (uint32_t)__popcll(__ballot(occupied && !node));
+        cnt.count<0>(node);
+        cnt.count<1>(occupied && !node);
     }
-    if ((threadIdx.x & 63) == 0) {
-        if (c_node) atomicAdd(&s_cnt[0], c_node);
-        if (c_other) atomicAdd(&s_cnt[1], c_other);
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    cnt.flush(ctr);
 }
 
 __device__ inline uint32_t comp_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -7424,7 +7464,7 @@ __global__ void __launch_bounds__(kPcBlock) k_map_comp_union(MapTable t, int con
         const unsigned long long k = t.keys[i];
         int c[3];
 #pragma unroll
-        for (int a = 0; a < 3; ++a) c[a] = (int)((k >> (21 * a)) & 0x1fffffull) - (kPcCellMax + 1);
+        for (int a = 0; a < 3; ++a) c[a] = pc_cell_of(k, a);
         uint32_t up = i;  // the nearest ancestor of i this thread knows: the next neighbour's walk starts there
         for (int oz = 0; oz <= reach; ++oz) {
             const int vz = c[2] + oz;
@@ -7579,25 +7619,17 @@ __global__ void __launch_bounds__(kPcBlock) k_map_comp_rank_label(uint32_t cap_l
 __global__ void __launch_bounds__(kPcBlock) k_map_comp_count(uint32_t cap_log2, MapComponents c, const unsigned long long* __restrict__ top,
                                                              unsigned long long* __restrict__ ctr)
 {
-    __shared__ uint32_t s_cnt[2];
-    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    uint32_t c_root = 0, c_single = 0;  // (the same in every lane of a wave)
+    MapCounts<2> cnt;
     const size_t cap = (size_t)1 << cap_log2, stride = (size_t)gridDim.x * kPcBlock;
     for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
         const size_t i = base + threadIdx.x;
         const bool root = c.parent[i] == (uint32_t)i;
         const uint32_t cells = root ? c.cells[i] : 0u;
         if (root && (unsigned long long)cells == top[0] && c.label[i] == top[1]) ctr[4] = c.points[i];
-        c_root += (uint32_t)__popcll(__ballot(root));
-        c_single += (uint32_t)__popcll(__ballot(cells == 1u));
+        cnt.count<0>(root);
+        cnt.count<1>(cells == 1u);
     }
-    if ((threadIdx.x & 63) == 0) {
-        if (c_root) atomicAdd(&s_cnt[0], c_root);
-        if (c_single) atomicAdd(&s_cnt[1], c_single);
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&ctr[2 + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    cnt.flush(ctr + 2);
 }
 
 // The selection's reason of every slot (kMapPruneEmpty without a cell), the first that holds: 1 no node; 2 its
@@ -7608,10 +7640,7 @@ __global__ void __launch_bounds__(kPcBlock) k_map_comp_select(MapTable t, MapCom
                                                               const unsigned long long* __restrict__ top, uint8_t* __restrict__ reason,
                                                               unsigned long long* __restrict__ ctr)
 {
-    __shared__ uint32_t s_cnt[kMapCompSelectCounters];
-    if (threadIdx.x < kMapCompSelectCounters) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c_root = 0;  // (the same in every lane of a wave)
+    MapCounts<kMapCompSelectCounters> cnt;
     const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
     for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
         const size_t i = base + threadIdx.x;
@@ -7635,45 +7664,30 @@ __global__ void __launch_bounds__(kPcBlock) k_map_comp_select(MapTable t, MapCom
             }
         }
         reason[i] = (uint8_t)r;
-        c0 += (uint32_t)__popcll(__ballot(r == 0u));
-        c1 += (uint32_t)__popcll(__ballot(r == 1u));
-        c2 += (uint32_t)__popcll(__ballot(r == 2u));
-        c3 += (uint32_t)__popcll(__ballot(r == 3u));
-        c4 += (uint32_t)__popcll(__ballot(r == 4u));
-        c_root += (uint32_t)__popcll(__ballot(root));
+        cnt.count<0>(r == 0u);
+        cnt.count<1>(r == 1u);
+        cnt.count<2>(r == 2u);
+        cnt.count<3>(r == 3u);
+        cnt.count<4>(r == 4u);
+        cnt.count<5>(root);
     }
-    if ((threadIdx.x & 63) == 0) {
-        if (c0) atomicAdd(&s_cnt[0], c0);
-        if (c1) atomicAdd(&s_cnt[1], c1);
-        if (c2) atomicAdd(&s_cnt[2], c2);
-        if (c3) atomicAdd(&s_cnt[3], c3);
-        if (c4) atomicAdd(&s_cnt[4], c4);
-        if (c_root) atomicAdd(&s_cnt[5], c_root);
-    }
-    __syncthreads();
-    if (threadIdx.x < kMapCompSelectCounters && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    cnt.flush(ctr);
 }
 
 // the labelling compacted like k_map_extract's cells under the labelling's filter, with its blk_off (one offset per tile of
-// kPcBlock slots): key, label and, when asked for, the selection's reason, in slot order; walked in strides like k_map_export
+// kPcBlock slots): key, label and, when asked for, the selection's reason, in slot order; walked in strides
 __global__ void __launch_bounds__(kPcBlock) k_map_comp_gather(MapTable t, uint32_t min_points, uint32_t min_windows, MapComponents c,
                                                               const uint8_t* __restrict__ reason, const uint32_t* __restrict__ blk_off,
                                                               unsigned long long* __restrict__ key_out,
                                                               unsigned long long* __restrict__ label_out, uint8_t* __restrict__ reason_out)
 {
-    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
-    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
-        const size_t i = base + threadIdx.x;
-        const bool f = map_passes(t, i, min_points, min_windows);
-        uint32_t total;
-        const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);  // (every thread of the workgroup, every round)
-        if (f) {
-            const size_t o = (size_t)blk_off[base / kPcBlock] + rank;
+    map_compact(
+        t.cap_log2, blk_off, [&](size_t i) { return map_passes(t, i, min_points, min_windows); },
+        [&](size_t i, size_t o) {
             key_out[o] = t.keys[i];
             label_out[o] = c.label[c.parent[i]];
             if (reason) reason_out[o] = reason[i];
-        }
-    }
+        });
 }
 
 // blk[b] = number of roots in [b * kPcBlock, (b + 1) * kPcBlock): k_map_flag_count for components
@@ -7691,19 +7705,13 @@ __global__ void __launch_bounds__(kPcBlock) k_map_comp_list(uint32_t cap_log2, M
                                                             unsigned long long* __restrict__ cells_out,
                                                             unsigned long long* __restrict__ points_out)
 {
-    const size_t cap = (size_t)1 << cap_log2, stride = (size_t)gridDim.x * kPcBlock;
-    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
-        const size_t i = base + threadIdx.x;
-        const bool f = c.parent[i] == (uint32_t)i;
-        uint32_t total;
-        const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);  // (every thread of the workgroup, every round)
-        if (f) {
-            const size_t o = (size_t)blk_off[base / kPcBlock] + rank;
+    map_compact(
+        cap_log2, blk_off, [&](size_t i) { return c.parent[i] == (uint32_t)i; },  // (a slot of the table: i < cap)
+        [&](size_t i, size_t o) {
             label_out[o] = c.label[i];
             cells_out[o] = (unsigned long long)c.cells[i];
             points_out[o] = c.points[i];
-        }
-    }
+        });
 }
 
 // ---- the map's k nearest cells (include/dsi_map_knn.h dsx_map_knn*; DESIGN.md 7j "Neighbours and statistical outliers") ----
@@ -7729,11 +7737,8 @@ __device__ inline void knn_insert(double (&d2)[K], unsigned long long (&key)[K],
     }
 }
 
-// the query p against the table: per axis c = floor(p / leaf); the candidates are the cells that pass the filter at
-// c + o, |o| <= reach per axis, an index with |c + o| > kPcCellMax skipped (tested in double as k_map_compare does: a huge
-// or non-finite c has no candidates), and the cell with key `self` (0: none) left out; q = the candidate's extracted
-// centroid; d2 = ((dx dx) + dy dy) + dz dz; admitted iff sqrt(d2) <= radius.  Returns the number admitted; the list holds
-// the first K of them by (d2, key).  Every probe loop is map_find's: bounded by the capacity.
+// the query p against the table: map_near_cells' candidates, the cell with key `self` (0: none) left out; admitted iff
+// sqrt(d2) <= radius.  Returns the number admitted; the list holds the first K of them by (d2, key).
 template <int K>
 __device__ inline uint32_t knn_scan(const MapTable& t, uint32_t mask, const MapKnn& o, const double (&p)[3], unsigned long long self,
                                     double (&d2)[K], unsigned long long (&key)[K])
@@ -7743,34 +7748,12 @@ __device__ inline uint32_t knn_scan(const MapTable& t, uint32_t mask, const MapK
         d2[j] = INFINITY;
         key[j] = ~0ull;
     }
-    double c[3];
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) c[ax] = floor(p[ax] / o.leaf);
     uint32_t admitted = 0;
-    for (int oz = -o.reach; oz <= o.reach; ++oz) {
-        const double vz = c[2] + (double)oz;
-        if (!(fabs(vz) <= (double)kPcCellMax)) continue;  // (NaN included)
-        for (int oy = -o.reach; oy <= o.reach; ++oy) {
-            const double vy = c[1] + (double)oy;
-            if (!(fabs(vy) <= (double)kPcCellMax)) continue;
-            for (int ox = -o.reach; ox <= o.reach; ++ox) {
-                const double vx = c[0] + (double)ox;
-                if (!(fabs(vx) <= (double)kPcCellMax)) continue;
-                const unsigned long long kb = pc_key((int)vx, (int)vy, (int)vz);
-                if (kb == self) continue;
-                const uint32_t j = map_find(t.keys, mask, kb);
-                if (j == ~0u || !map_passes(t, j, o.min_points, o.min_windows)) continue;
-                const uint32_t nb = t.n[j];
-                const double dx = p[0] - (double)map_centroid(t, j, kb, nb, 0, o.leaf);
-                const double dy = p[1] - (double)map_centroid(t, j, kb, nb, 1, o.leaf);
-                const double dz = p[2] - (double)map_centroid(t, j, kb, nb, 2, o.leaf);
-                const double dd = ((dx * dx) + dy * dy) + dz * dz;
-                if (!(sqrt(dd) <= o.radius)) continue;
-                ++admitted;
-                knn_insert<K>(d2, key, dd, kb);
-            }
-        }
-    }
+    map_near_cells(t, mask, o.min_points, o.min_windows, o.leaf, o.reach, p, self, [&](uint32_t, unsigned long long kb, double dd) {
+        if (!(sqrt(dd) <= o.radius)) return;
+        ++admitted;
+        knn_insert<K>(d2, key, dd, kb);
+    });
     return admitted;
 }
 
@@ -7801,22 +7784,19 @@ __global__ void __launch_bounds__(kPcBlock) k_map_knn_points(MapTable t, MapKnn 
     }
 }
 
-// The self query: every cell that passes the filter against the others (itself left out by key), its table walked in
-// strides as k_map_compare's.  Per query found = min(k, admitted), m = (((d_1 + d_2) + ...) + d_found) / found in rank
+// The self query: every cell that passes the filter against the others (itself left out by key), a counted slot walk
+// (MapCounts).  Per query found = min(k, admitted), m = (((d_1 + d_2) + ...) + d_found) / found in rank
 // order and q = (u64) floor((m / radius) * 2^30) (found == 0: m = +inf, q = 0), written per slot; scored iff
 // found >= min_found.  ctr: [0] queries, [1] occupied slots the filter leaves out, [2] scored, [3] isolated, and over the
 // scored [4] sum q, [5] sum of q^2's low 32 bits, [6] sum of q^2 >> 32 (q^2 <= 2^60 and at most 2^27 cells: neither word
-// overflows; the host puts the 128-bit sum together).  The ballots are summed in registers, the sums per thread, both
-// then in LDS, and a workgroup issues one global atomic per counter.
+// overflows; the host puts the 128-bit sum together).  The three sums are kept per thread and added in LDS beside the
+// counts: one global atomic per workgroup for each of them too.
 template <int K>
 __global__ void __launch_bounds__(kPcBlock) k_map_knn_self(MapTable t, MapKnn o, MapKnnCells c, unsigned long long* __restrict__ ctr)
 {
-    __shared__ uint32_t s_cnt[4];
     __shared__ unsigned long long s_sum[3];
-    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0u;
     if (threadIdx.x < 3) s_sum[threadIdx.x] = 0ull;
-    __syncthreads();
-    uint32_t c_query = 0, c_other = 0, c_scored = 0, c_isolated = 0;  // (the same in every lane of a wave)
+    MapCounts<4> cnt;
     unsigned long long sum_q = 0ull, sq_lo = 0ull, sq_hi = 0ull;
     const uint32_t mask = (1u << t.cap_log2) - 1u;
     const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
@@ -7850,22 +7830,15 @@ __global__ void __launch_bounds__(kPcBlock) k_map_knn_self(MapTable t, MapKnn o,
                 sq_hi += q2 >> 32;
             }
         }
-        c_query += (uint32_t)__popcll(__ballot(f));
-        c_other += (uint32_t)__popcll(__ballot(occupied && !f));
-        c_scored += (uint32_t)__popcll(__ballot(scored));
-        c_isolated += (uint32_t)__popcll(__ballot(f && !scored));
+        cnt.count<0>(f);
+        cnt.count<1>(occupied && !f);
+        cnt.count<2>(scored);
+        cnt.count<3>(f && !scored);
     }
     if (sum_q) atomicAdd(&s_sum[0], sum_q);
     if (sq_lo) atomicAdd(&s_sum[1], sq_lo);
     if (sq_hi) atomicAdd(&s_sum[2], sq_hi);
-    if ((threadIdx.x & 63) == 0) {
-        if (c_query) atomicAdd(&s_cnt[0], c_query);
-        if (c_other) atomicAdd(&s_cnt[1], c_other);
-        if (c_scored) atomicAdd(&s_cnt[2], c_scored);
-        if (c_isolated) atomicAdd(&s_cnt[3], c_isolated);
-    }
-    __syncthreads();
-    if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    cnt.flush(ctr);
     if (threadIdx.x >= 4 && threadIdx.x < 7 && s_sum[threadIdx.x - 4]) atomicAdd(&ctr[threadIdx.x], s_sum[threadIdx.x - 4]);
 }
 
@@ -7874,10 +7847,7 @@ __global__ void __launch_bounds__(kPcBlock) k_map_knn_self(MapTable t, MapKnn o,
 __global__ void __launch_bounds__(kPcBlock) k_map_knn_select(MapTable t, MapKnn o, MapKnnCells c, int use_threshold, uint32_t T_q,
                                                              uint8_t* __restrict__ reason, unsigned long long* __restrict__ ctr)
 {
-    __shared__ uint32_t s_cnt[kMapKnnSelectCounters];
-    if (threadIdx.x < kMapKnnSelectCounters) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;  // (the same in every lane of a wave)
+    MapCounts<kMapKnnSelectCounters> cnt;
     const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
     for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
         const size_t i = base + threadIdx.x;
@@ -7893,19 +7863,12 @@ __global__ void __launch_bounds__(kPcBlock) k_map_knn_select(MapTable t, MapKnn 
                 r = 0u;
         }
         reason[i] = (uint8_t)r;
-        c0 += (uint32_t)__popcll(__ballot(r == 0u));
-        c1 += (uint32_t)__popcll(__ballot(r == 1u));
-        c2 += (uint32_t)__popcll(__ballot(r == 2u));
-        c3 += (uint32_t)__popcll(__ballot(r == 3u));
+        cnt.count<0>(r == 0u);
+        cnt.count<1>(r == 1u);
+        cnt.count<2>(r == 2u);
+        cnt.count<3>(r == 3u);
     }
-    if ((threadIdx.x & 63) == 0) {
-        if (c0) atomicAdd(&s_cnt[0], c0);
-        if (c1) atomicAdd(&s_cnt[1], c1);
-        if (c2) atomicAdd(&s_cnt[2], c2);
-        if (c3) atomicAdd(&s_cnt[3], c3);
-    }
-    __syncthreads();
-    if (threadIdx.x < kMapKnnSelectCounters && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    cnt.flush(ctr);
 }
 
 // the self query compacted like k_map_extract's cells under the query's filter, with its blk_off (one offset per tile of
@@ -7916,21 +7879,15 @@ __global__ void __launch_bounds__(kPcBlock) k_map_knn_gather(MapTable t, uint32_
                                                              float* __restrict__ mean_out, uint32_t* __restrict__ q_out,
                                                              uint8_t* __restrict__ reason_out)
 {
-    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
-    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
-        const size_t i = base + threadIdx.x;
-        const bool f = map_passes(t, i, min_points, min_windows);
-        uint32_t total;
-        const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);  // (every thread of the workgroup, every round)
-        if (f) {
-            const size_t at = (size_t)blk_off[base / kPcBlock] + rank;
+    map_compact(
+        t.cap_log2, blk_off, [&](size_t i) { return map_passes(t, i, min_points, min_windows); },
+        [&](size_t i, size_t at) {
             key_out[at] = t.keys[i];
             found_out[at] = c.found[i];
             mean_out[at] = c.mean[i];
             q_out[at] = c.q[i];
             if (reason) reason_out[at] = reason[i];
-        }
-    }
+        });
 }
 
 // ---- the map's local shape (include/dsi_map_pca.h dsx_map_pca*; DESIGN.md 7j "Local shape") ----
@@ -7956,50 +7913,24 @@ __device__ inline void pca_accumulate(const MapTable& t, uint32_t j, unsigned lo
 __device__ inline uint32_t pca_scan_all(const MapTable& t, uint32_t mask, const MapPca& o, const double (&p)[3], unsigned long long self,
                                         long long (&s)[3], long long (&ss)[6])
 {
-    double c[3];
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) c[ax] = floor(p[ax] / o.q.leaf);
     uint32_t admitted = 0;
-    for (int oz = -o.q.reach; oz <= o.q.reach; ++oz) {
-        const double vz = c[2] + (double)oz;
-        if (!(fabs(vz) <= (double)kPcCellMax)) continue;  // (NaN included)
-        for (int oy = -o.q.reach; oy <= o.q.reach; ++oy) {
-            const double vy = c[1] + (double)oy;
-            if (!(fabs(vy) <= (double)kPcCellMax)) continue;
-            for (int ox = -o.q.reach; ox <= o.q.reach; ++ox) {
-                const double vx = c[0] + (double)ox;
-                if (!(fabs(vx) <= (double)kPcCellMax)) continue;
-                const unsigned long long kb = pc_key((int)vx, (int)vy, (int)vz);
-                if (kb == self) continue;
-                const uint32_t j = map_find(t.keys, mask, kb);
-                if (j == ~0u || !map_passes(t, j, o.q.min_points, o.q.min_windows)) continue;
-                const uint32_t nb = t.n[j];
-                const double dx = p[0] - (double)map_centroid(t, j, kb, nb, 0, o.q.leaf);
-                const double dy = p[1] - (double)map_centroid(t, j, kb, nb, 1, o.q.leaf);
-                const double dz = p[2] - (double)map_centroid(t, j, kb, nb, 2, o.q.leaf);
-                const double dd = ((dx * dx) + dy * dy) + dz * dz;
-                if (!(sqrt(dd) <= o.q.radius)) continue;
-                ++admitted;
-                pca_accumulate(t, j, kb, o, p, s, ss);
-            }
-        }
-    }
+    map_near_cells(t, mask, o.q.min_points, o.q.min_windows, o.q.leaf, o.q.reach, p, self,
+                   [&](uint32_t j, unsigned long long kb, double dd) {
+                       if (!(sqrt(dd) <= o.q.radius)) return;
+                       ++admitted;
+                       pca_accumulate(t, j, kb, o, p, s, ss);
+                   });
     return admitted;
 }
 
-// The pass: every cell that passes the filter, the table walked in strides as k_map_knn_self's.  Per query the row of
+// The pass: every cell that passes the filter, a counted slot walk (MapCounts).  Per query the row of
 // dsi_map_pca.h step 8 into c (a sparse query: label 0, flags 0, vectors 0, eigenvalues +inf).  ctr: [0] queries, [1] occupied
 // slots the filter leaves out, [2] sparse, [3..5] label 1..3, [6] normal determined, [7] tangent determined, [8] sum of m.
-// The ballots are summed in registers, the members per thread, both then in LDS, and a workgroup issues one global atomic
-// per counter.
+// The members are counter 8, a per-thread sum.
 template <int K>
 __global__ void __launch_bounds__(kPcBlock) k_map_pca(MapTable t, MapPca o, MapPcaCells c, unsigned long long* __restrict__ ctr)
 {
-    __shared__ uint32_t s_cnt[kMapPcaCounters];
-    if (threadIdx.x < kMapPcaCounters) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    uint32_t c_query = 0, c_other = 0, c_sparse = 0, c_l1 = 0, c_l2 = 0, c_l3 = 0, c_nd = 0, c_td = 0;  // (the same in every lane of a wave)
-    uint32_t members = 0;
+    MapCounts<kMapPcaCounters> cnt;
     const uint32_t mask = (1u << t.cap_log2) - 1u;
     const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
     for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
@@ -8029,7 +7960,7 @@ __global__ void __launch_bounds__(kPcBlock) k_map_pca(MapTable t, MapPca o, MapP
                     }
             }
             const uint32_t m = found + 1u;
-            members += m;
+            cnt.sum<8>(m);  // (at most 343 per round: a workgroup's sum stays far below 2^32)
             PcaSolved r;
             if ((int)found >= o.q.min_found) {
                 const int64_t s3[3] = {s[0], s[1], s[2]}, ss6[6] = {ss[0], ss[1], ss[2], ss[3], ss[4], ss[5]};
@@ -8055,28 +7986,16 @@ __global__ void __launch_bounds__(kPcBlock) k_map_pca(MapTable t, MapPca o, MapP
                 for (int a = 0; a < 6; ++a) c.moments[9 * i + 3 + a] = ss[a];
             }
         }
-        c_query += (uint32_t)__popcll(__ballot(f));
-        c_other += (uint32_t)__popcll(__ballot(occupied && !f));
-        c_sparse += (uint32_t)__popcll(__ballot(f && label == 0u));
-        c_l1 += (uint32_t)__popcll(__ballot(label == 1u));
-        c_l2 += (uint32_t)__popcll(__ballot(label == 2u));
-        c_l3 += (uint32_t)__popcll(__ballot(label == 3u));
-        c_nd += (uint32_t)__popcll(__ballot((flags & 1u) != 0u));
-        c_td += (uint32_t)__popcll(__ballot((flags & 2u) != 0u));
+        cnt.count<0>(f);
+        cnt.count<1>(occupied && !f);
+        cnt.count<2>(f && label == 0u);
+        cnt.count<3>(label == 1u);
+        cnt.count<4>(label == 2u);
+        cnt.count<5>(label == 3u);
+        cnt.count<6>((flags & 1u) != 0u);
+        cnt.count<7>((flags & 2u) != 0u);
     }
-    if (members) atomicAdd(&s_cnt[8], members);  // (at most 343 per round: a workgroup's sum stays far below 2^32)
-    if ((threadIdx.x & 63) == 0) {
-        if (c_query) atomicAdd(&s_cnt[0], c_query);
-        if (c_other) atomicAdd(&s_cnt[1], c_other);
-        if (c_sparse) atomicAdd(&s_cnt[2], c_sparse);
-        if (c_l1) atomicAdd(&s_cnt[3], c_l1);
-        if (c_l2) atomicAdd(&s_cnt[4], c_l2);
-        if (c_l3) atomicAdd(&s_cnt[5], c_l3);
-        if (c_nd) atomicAdd(&s_cnt[6], c_nd);
-        if (c_td) atomicAdd(&s_cnt[7], c_td);
-    }
-    __syncthreads();
-    if (threadIdx.x < kMapPcaCounters && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    cnt.flush(ctr);
 }
 
 // The selection's reason of every slot (kMapPruneEmpty without a cell), the first that holds: 1 the cell fails the pass's
@@ -8086,10 +8005,7 @@ __global__ void __launch_bounds__(kPcBlock) k_map_pca_select(MapTable t, uint32_
                                                              uint32_t keep_labels, int remove_sparse, uint8_t* __restrict__ reason,
                                                              unsigned long long* __restrict__ ctr)
 {
-    __shared__ uint32_t s_cnt[kMapPcaSelectCounters];
-    if (threadIdx.x < kMapPcaSelectCounters) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;  // (the same in every lane of a wave)
+    MapCounts<kMapPcaSelectCounters> cnt;
     const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
     for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
         const size_t i = base + threadIdx.x;
@@ -8106,19 +8022,12 @@ __global__ void __launch_bounds__(kPcBlock) k_map_pca_select(MapTable t, uint32_
             }
         }
         reason[i] = (uint8_t)r;
-        c0 += (uint32_t)__popcll(__ballot(r == 0u));
-        c1 += (uint32_t)__popcll(__ballot(r == 1u));
-        c2 += (uint32_t)__popcll(__ballot(r == 2u));
-        c3 += (uint32_t)__popcll(__ballot(r == 3u));
+        cnt.count<0>(r == 0u);
+        cnt.count<1>(r == 1u);
+        cnt.count<2>(r == 2u);
+        cnt.count<3>(r == 3u);
     }
-    if ((threadIdx.x & 63) == 0) {
-        if (c0) atomicAdd(&s_cnt[0], c0);
-        if (c1) atomicAdd(&s_cnt[1], c1);
-        if (c2) atomicAdd(&s_cnt[2], c2);
-        if (c3) atomicAdd(&s_cnt[3], c3);
-    }
-    __syncthreads();
-    if (threadIdx.x < kMapPcaSelectCounters && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    cnt.flush(ctr);
 }
 
 // the pass compacted like k_map_extract's cells under the pass's filter, with its blk_off (one offset per tile of kPcBlock
@@ -8128,14 +8037,9 @@ __global__ void __launch_bounds__(kPcBlock) k_map_pca_gather(MapTable t, uint32_
                                                              unsigned long long* __restrict__ key_out, MapPcaCells out,
                                                              uint8_t* __restrict__ reason_out)
 {
-    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
-    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
-        const size_t i = base + threadIdx.x;
-        const bool f = map_passes(t, i, min_points, min_windows);
-        uint32_t total;
-        const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);  // (every thread of the workgroup, every round)
-        if (f) {
-            const size_t at = (size_t)blk_off[base / kPcBlock] + rank;
+    map_compact(
+        t.cap_log2, blk_off, [&](size_t i) { return map_passes(t, i, min_points, min_windows); },
+        [&](size_t i, size_t at) {
             key_out[at] = t.keys[i];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -8151,42 +8055,35 @@ __global__ void __launch_bounds__(kPcBlock) k_map_pca_gather(MapTable t, uint32_
                 for (int a = 0; a < 9; ++a) out.moments[9 * at + a] = c.moments[9 * i + a];
             }
             if (reason_out) reason_out[at] = reason[i];
-        }
-    }
+        });
 }
 
 // ---- merging maps and moving their state (include/dsi_map_merge.h dsx_map_export / import / merge; DESIGN.md 7j "Merging") ----
 // Every occupied slot's raw state compacted like k_map_extract's cells under the filter (0, 0), with its blk_off (one
-// offset per tile of kPcBlock slots): key, n, S[3], windows and stamp in slot order.  Walked in strides like k_map_render;
-// reads the table only.
+// offset per tile of kPcBlock slots): key, n, S[3], windows and stamp in slot order.  Walked in strides; reads the table only.
 __global__ void __launch_bounds__(kPcBlock) k_map_export(MapTable t, const uint32_t* __restrict__ blk_off,
                                                          unsigned long long* __restrict__ key_out, uint32_t* __restrict__ n_out,
                                                          unsigned long long* __restrict__ sums_out, uint32_t* __restrict__ w_out,
                                                          uint32_t* __restrict__ stamp_out)
 {
-    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
-    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
-        const size_t i = base + threadIdx.x;
-        const bool f = map_passes(t, i, 0u, 0u);
-        uint32_t total;
-        const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);  // (every thread of the workgroup, every round)
-        if (f) {
-            const size_t o = (size_t)blk_off[base / kPcBlock] + rank;
+    map_compact(
+        t.cap_log2, blk_off, [&](size_t i) { return map_passes(t, i, 0u, 0u); },
+        [&](size_t i, size_t o) {
             key_out[o] = t.keys[i];
             n_out[o] = t.n[i];
             w_out[o] = t.windows[i];
             stamp_out[o] = t.stamp[i];
 #pragma unroll
             for (int a = 0; a < 3; ++a) sums_out[3 * o + a] = t.sums[3 * i + a];
-        }
-    }
+        });
 }
 
 // m incoming cells (host arrays, nothing trusted) checked and built into the zeroed table `to`.  Per cell, each counted on
 // its own: [0] key 0 or a packed coordinate outside [1, 2 kPcCellMax + 1]; [1] a duplicate -- map_slot does not report the
 // key as fresh (a bad key is not inserted); [2] n == 0; [3] windows == 0, > n or > stamp; [4] stamp == 0 or > calls;
 // [5] some S[a] > n * 2^32 (n < 2^32: the product is exact in 64 bits); [6] `to` found full; [7] the sum of n.  A fresh
-// slot has one writer: plain stores.  ctr [kMapImportCounters]: one global atomic per workgroup and counter.
+// slot has one writer: plain stores.  ctr [kMapImportCounters]: one global atomic per workgroup and counter.  MapCounts'
+// contract with a stage of its own: the sum of n shares it, so its LDS words are 64 bits wide.
 __global__ void __launch_bounds__(kPcBlock) k_map_import_build(const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ n,
                                                                const unsigned long long* __restrict__ sums,
                                                                const uint32_t* __restrict__ windows, const uint32_t* __restrict__ stamp,
@@ -8209,7 +8106,7 @@ __global__ void __launch_bounds__(kPcBlock) k_map_import_build(const unsigned lo
             bad[0] = k == 0ull || (k >> 63) != 0ull;
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                const uint32_t p = (uint32_t)((k >> (21 * a)) & 0x1fffffull);
+                const uint32_t p = pc_packed_of(k, a);
                 bad[0] = bad[0] || p < 1u || p > 2u * (uint32_t)kPcCellMax + 1u;
             }
             bad[2] = cn == 0u;
@@ -8261,10 +8158,7 @@ __global__ void __launch_bounds__(kPcBlock) k_map_merge(MapTable src, MapTable d
                                                         unsigned long long add_rejected, unsigned long long* __restrict__ ctr,
                                                         unsigned long long* __restrict__ mctr)
 {
-    __shared__ uint32_t s_cnt[3];
-    if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    uint32_t c_new = 0, c_common = 0, c_full = 0;  // (the same in every lane of a wave)
+    MapCounts<3> cnt;
     const uint32_t mask = (1u << dst.cap_log2) - 1u;
     const size_t cap = (size_t)1 << src.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
     for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
@@ -8287,22 +8181,13 @@ __global__ void __launch_bounds__(kPcBlock) k_map_merge(MapTable src, MapTable d
                 for (int a = 0; a < 3; ++a) dst.sums[3 * (size_t)slot + a] += src.sums[3 * i + a];
             }
         }
-        c_new += (uint32_t)__popcll(__ballot(is_new));
-        c_common += (uint32_t)__popcll(__ballot(is_common));
-        c_full += (uint32_t)__popcll(__ballot(full));
+        cnt.count<0>(is_new);
+        cnt.count<1>(is_common);
+        cnt.count<2>(full);
     }
-    if ((threadIdx.x & 63) == 0) {
-        if (c_new) atomicAdd(&s_cnt[0], c_new);
-        if (c_common) atomicAdd(&s_cnt[1], c_common);
-        if (c_full) atomicAdd(&s_cnt[2], c_full);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_cnt[0]) {
-        atomicAdd(&ctr[0], (unsigned long long)s_cnt[0]);
-        atomicAdd(&mctr[0], (unsigned long long)s_cnt[0]);
-    }
-    if (threadIdx.x == 1 && s_cnt[1]) atomicAdd(&mctr[1], (unsigned long long)s_cnt[1]);
-    if (threadIdx.x == 2 && s_cnt[2]) atomicAdd(&ctr[3], (unsigned long long)s_cnt[2]);
+    cnt.flush_to({&ctr[0], &mctr[1], &ctr[3]});
+    const uint32_t n_new = cnt.total(0);  // (the new cells count in both arrays)
+    if (threadIdx.x == 0 && n_new) atomicAdd(&mctr[0], (unsigned long long)n_new);
     if (blockIdx.x == 0 && threadIdx.x == 3) {
         if (add_accepted) atomicAdd(&ctr[1], add_accepted);
         if (add_rejected) atomicAdd(&ctr[2], add_rejected);
@@ -8325,13 +8210,10 @@ __global__ void __launch_bounds__(kPcBlock, 4) k_map_align_step(MapTable a, MapT
                                                              float* __restrict__ dist, unsigned long long* __restrict__ ctr)
 {
     __shared__ unsigned long long s_acc[kMapAlignSums];
-    __shared__ uint32_t s_cnt[2];
     __shared__ double s_T[12];  // (the pose is read once per cell: in LDS it holds no scalar registers over the lookups)
     if (threadIdx.x < kMapAlignSums) s_acc[threadIdx.x] = 0ull;
-    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
     if (threadIdx.x >= 64 && threadIdx.x < 64 + 12) s_T[threadIdx.x - 64] = o.T[threadIdx.x - 64];
-    __syncthreads();
-    uint32_t c_match = 0, c_un = 0;  // (the same in every lane of a wave)
+    MapCounts<2> cnt;
     unsigned long long acc[kMapAlignSums];
 #pragma unroll
     for (int k = 0; k < kMapAlignSums; ++k) acc[k] = 0ull;
@@ -8409,8 +8291,8 @@ __global__ void __launch_bounds__(kPcBlock, 4) k_map_align_step(MapTable a, MapT
                     }
             }
         }
-        c_match += (uint32_t)__popcll(__ballot(matched));
-        c_un += (uint32_t)__popcll(__ballot(f && !matched));
+        cnt.count<0>(matched);
+        cnt.count<1>(f && !matched);
     }
 #pragma unroll
     for (int k = 0; k < kMapAlignSums; ++k) {
@@ -8419,12 +8301,7 @@ __global__ void __launch_bounds__(kPcBlock, 4) k_map_align_step(MapTable a, MapT
         for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
         if ((threadIdx.x & 63) == 0 && v) atomicAdd(&s_acc[k], v);
     }
-    if ((threadIdx.x & 63) == 0) {
-        if (c_match) atomicAdd(&s_cnt[0], c_match);
-        if (c_un) atomicAdd(&s_cnt[1], c_un);
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    cnt.flush(ctr);
     if (threadIdx.x >= 64 && threadIdx.x < 64 + kMapAlignSums && s_acc[threadIdx.x - 64])
         atomicAdd(&ctr[2 + threadIdx.x - 64], s_acc[threadIdx.x - 64]);
 }
@@ -8436,29 +8313,23 @@ __global__ void __launch_bounds__(kPcBlock) k_map_align_gather(MapTable t, uint3
                                                                const uint32_t* __restrict__ blk_off, unsigned long long* __restrict__ key_a_out,
                                                                unsigned long long* __restrict__ key_b_out, float* __restrict__ dist_out)
 {
-    const size_t i = (size_t)blockIdx.x * kPcBlock + threadIdx.x;
-    const bool f = map_passes(t, i, min_points, min_windows);
-    uint32_t total;
-    const uint32_t rank = pc_block_exclusive(f ? 1u : 0u, &total);
-    if (!f) return;
-    const size_t o = (size_t)blk_off[blockIdx.x] + rank;
-    key_a_out[o] = t.keys[i];
-    key_b_out[o] = key_b[i];
-    dist_out[o] = dist[i];
+    map_compact<true>(
+        t.cap_log2, blk_off, [&](size_t i) { return map_passes(t, i, min_points, min_windows); },
+        [&](size_t i, size_t o) {
+            key_a_out[o] = t.keys[i];
+            key_b_out[o] = key_b[i];
+            dist_out[o] = dist[i];
+        });
 }
 
 // One map into another as one integrate call: every cell of src that passes the filter is its extracted centroid (float,
 // widened), which goes through map_integrate_point under T into dst -- dsi_map_integrate of dsi_map_extract's list, bit for
-// bit.  src is only read and dst != src.  Walks src's slots in strides; ctr as k_map_integrate_depth's, one global atomic
-// per workgroup and counter.
+// bit.  src is only read and dst != src.  A counted slot walk (MapCounts) over src; ctr as k_map_integrate_depth's.
 __global__ void __launch_bounds__(kPcBlock) k_map_integrate_map(MapTable src, uint32_t min_points, uint32_t min_windows, double leaf_src,
                                                                 MapPose T, double leaf, uint32_t serial, MapTable dst,
                                                                 unsigned long long* __restrict__ ctr)
 {
-    __shared__ uint32_t s_cnt[4];
-    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    uint32_t c_new = 0, c_ok = 0, c_rej = 0, c_full = 0;  // (the same in every lane of a wave)
+    MapCounts<4> cnt;
     const size_t cap = (size_t)1 << src.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
     for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
         const size_t i = base + threadIdx.x;
@@ -8470,19 +8341,12 @@ __global__ void __launch_bounds__(kPcBlock) k_map_integrate_map(MapTable src, ui
             map_integrate_point((double)map_centroid(src, i, k, n, 0, leaf_src), (double)map_centroid(src, i, k, n, 1, leaf_src),
                                 (double)map_centroid(src, i, k, n, 2, leaf_src), T, leaf, serial, dst, &ok, &fresh, &full);
         }
-        c_new += (uint32_t)__popcll(__ballot(fresh));
-        c_ok += (uint32_t)__popcll(__ballot(ok));
-        c_rej += (uint32_t)__popcll(__ballot(in && !ok && !full));
-        c_full += (uint32_t)__popcll(__ballot(full));
+        cnt.count<0>(fresh);
+        cnt.count<1>(ok);
+        cnt.count<2>(in && !ok && !full);
+        cnt.count<3>(full);
     }
-    if ((threadIdx.x & 63) == 0) {
-        if (c_new) atomicAdd(&s_cnt[0], c_new);
-        if (c_ok) atomicAdd(&s_cnt[1], c_ok);
-        if (c_rej) atomicAdd(&s_cnt[2], c_rej);
-        if (c_full) atomicAdd(&s_cnt[3], c_full);
-    }
-    __syncthreads();
-    if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    cnt.flush(ctr);
 }
 
 }  // namespace
