@@ -11,6 +11,7 @@ DsiError carrying the C status code.  numpy arrays cross the boundary as plain
 pointers; nothing here computes on the CPU.
 """
 import atexit
+import collections
 import ctypes as C
 import os
 import sys
@@ -555,6 +556,31 @@ def _check(rc):
 
 def _ptr(a, ct):
     return a.ctypes.data_as(C.POINTER(ct))
+
+
+def _info_dict(info, fields=None):
+    """A ctypes struct of counts as a dict: an integer field an int, a floating one a float, an array field a list of those.
+    fields: the names to take, in the dict's order (None: every field, in the struct's)."""
+    out = {}
+    for name in fields or [f[0] for f in info._fields_]:
+        v = getattr(info, name)
+        out[name] = list(v) if isinstance(v, C.Array) else v
+    return out
+
+
+# What WorldMap._fetch_rows is told of a fetch.  _Kind: a column's element, as numpy and as the C entry point take it.
+# _Column: its name in the returned dict, its element, the shape of one row and, for an optional column, the WorldMap flag
+# that says whether it is there.
+_Kind = collections.namedtuple("_Kind", "dtype pointer")
+_Column = collections.namedtuple("_Column", "name kind shape flag", defaults=((), None))
+
+
+def _kind(ctype):
+    return _Kind(np.dtype(ctype), C.POINTER(ctype))
+
+
+_U8, _U16, _U32, _U64 = _kind(C.c_uint8), _kind(C.c_uint16), _kind(C.c_uint32), _kind(C.c_uint64)
+_I64, _F32 = _kind(C.c_int64), _kind(C.c_float)
 
 
 def _arr(a, dtype):
@@ -1176,7 +1202,43 @@ class WorldMap:
         self.ctx = ctx
         self._h = C.c_void_p()
         _check(load_library().dsi_map_create(ctx._h, float(leaf), int(capacity_log2), C.byref(self._h)))
+        # what the library keeps of the last passes and does not tell: the render's size; whether a selection left reasons
+        # beside the labelling, the self query and the local-shape pass; whether that pass kept its moments
+        self._render_shape = (0, 0)
+        self._components_selected = self._knn_selected = self._pca_selected = self._pca_moments = False
         _track(self)
+
+    @staticmethod
+    def _by_key(rows):
+        order = np.argsort(rows["keys"], kind="stable")
+        return {k: v[order] for k, v in rows.items()}
+
+    def _fetch_rows(self, fn, columns, sort, lead=()):
+        """The two calls of a fetch, fn(self._h, *lead, one pointer per column, capacity, &n).  The first, with no column and
+        no room, asks for the number of rows: it is refused for want of room as soon as there are rows, so its refusal counts
+        only when it leaves n at 0.  The second fills fresh arrays, also when there is no row.  columns: one _Column per
+        pointer, in the order of fn's arguments (the table stands above each fetch); an optional column whose flag is down
+        is passed as None and left out.  Returns the dict of the arrays, keys first (dsx_map_compare_fetch and
+        dsx_map_prune_fetch take their values before the keys), in the table's order or, with sort, by ascending key."""
+        n = C.c_size_t()
+        no_columns = [None] * len(columns)
+        rc = fn(self._h, *lead, *no_columns, 0, C.byref(n))
+        if rc != OK and n.value == 0:
+            _check(rc)
+        m = n.value
+        out = {c.name: np.empty((m,) + c.shape, c.kind.dtype) for c in columns if c.flag is None or getattr(self, c.flag)}
+        pointers = [out[c.name].ctypes.data_as(c.kind.pointer) if c.name in out else None for c in columns]
+        _check(fn(self._h, *lead, *pointers, m, C.byref(n)))
+        if "keys" in out:
+            out = {"keys": out.pop("keys"), **out}
+        return self._by_key(out) if sort else out
+
+    def _select(self, fn, selection, info, flag):
+        """A selection or the prune by it: the flag that fetches read falls before the call and rises after it went through"""
+        setattr(self, flag, False)
+        _check(fn(self._h, C.byref(selection), C.byref(info)))
+        setattr(self, flag, True)
+        return _info_dict(info)
 
     def integrate(self, xyz, T_w_rv):
         """One call (window) of host points: xyz (N, 3) or (N, 4) float32, x y z first (a getPointcloud result as it is);
@@ -1221,18 +1283,13 @@ class WorldMap:
                "keys": np.empty(m, np.uint64)}
         _check(L.dsi_map_extract(self._h, int(min_points), int(min_windows), _ptr(out["xyz"], C.c_float), _ptr(out["n"], C.c_uint32),
                                  _ptr(out["windows"], C.c_uint32), _ptr(out["keys"], C.c_uint64), m, C.byref(n)))
-        if sort:
-            order = np.argsort(out["keys"], kind="stable")
-            out = {k: v[order] for k, v in out.items()}
-        return out
+        return self._by_key(out) if sort else out
 
     def info(self):
         """dict of leaf, capacity (slots), occupied (cells), calls, accepted, rejected (points) and growths (doublings)."""
         i = _MapInfo()
         _check(load_library().dsi_map_info(self._h, C.byref(i)))
-        out = {k: int(getattr(i, k)) for k in ("capacity", "occupied", "calls", "accepted", "rejected", "growths")}
-        out["leaf"] = float(i.leaf)
-        return out
+        return _info_dict(i, ("capacity", "occupied", "calls", "accepted", "rejected", "growths", "leaf"))
 
     def render(self, T_v_w, width, height, fx, fy, cx, cy, min_depth, max_depth, splat=0, min_points=1, min_windows=1,
                fetch=True):
@@ -1253,7 +1310,7 @@ class WorldMap:
         i = _MapRenderInfo()
         _check(load_library().dsi_map_render(self._h, C.byref(v), C.byref(i)))
         self._render_shape = (int(i.height), int(i.width))
-        out = {k: int(getattr(i, k)) for k in ("width", "height", "n_cells", "n_clipped", "n_outside", "n_drawn", "n_pixels")}
+        out = _info_dict(i)
         if fetch:
             out.update(self.fetchRender())
         return out
@@ -1261,7 +1318,7 @@ class WorldMap:
     def fetchRender(self):
         """dict of depth, windows, hits and mask of the last render (dsi_map_render_fetch); raises DsiError when the map
         changed since, or was never rendered."""
-        shape = getattr(self, "_render_shape", (0, 0))
+        shape = self._render_shape
         out = {"depth": np.empty(shape, np.float32), "windows": np.empty(shape, np.uint32), "hits": np.empty(shape, np.uint32),
                "mask": np.empty(shape, np.uint8)}
         _check(load_library().dsi_map_render_fetch(self._h, _ptr(out["depth"], C.c_float), _ptr(out["windows"], C.c_uint32),
@@ -1324,28 +1381,19 @@ class WorldMap:
         hist = np.zeros(max(int(n_bins), 0), np.uint64)
         L = load_library()
         _check(L.dsx_map_compare(self._h, other._h, C.byref(o), _ptr(hist, C.c_uint64) if hist.size else None, C.byref(i)))
-        out = {k: int(getattr(i, k)) for k in ("n_cells", "n_matched", "n_unmatched", "sum_q", "reach")}
+        out = _info_dict(i)
         out["hist"] = hist
         out["mean"] = out["sum_q"] * float(radius) / 4294967296.0 / out["n_matched"] if out["n_matched"] else float("nan")
         if distances:
             out.update(self.fetchDistances())
         return out
 
+    _DISTANCE_COLUMNS = (_Column("dist", _F32), _Column("keys", _U64))  # (dsx_map_compare_fetch takes the values first)
+
     def fetchDistances(self, sort=True):
         """keys (uint64) and dist (float32) of the last compare() of this map (dsx_map_compare_fetch); raises DsiError when
         the map changed since, or was never compared."""
-        L = load_library()
-        n = C.c_size_t()
-        rc = L.dsx_map_compare_fetch(self._h, None, None, 0, C.byref(n))
-        if rc != OK and n.value == 0:
-            _check(rc)
-        m = n.value
-        out = {"keys": np.empty(m, np.uint64), "dist": np.empty(m, np.float32)}
-        _check(L.dsx_map_compare_fetch(self._h, _ptr(out["dist"], C.c_float), _ptr(out["keys"], C.c_uint64), m, C.byref(n)))
-        if sort:
-            order = np.argsort(out["keys"], kind="stable")
-            out = {k: v[order] for k, v in out.items()}
-        return out
+        return self._fetch_rows(load_library().dsx_map_compare_fetch, self._DISTANCE_COLUMNS, sort)
 
     def prune(self, min_points=1, min_windows=1, max_age=None, box=None, reach=0, min_neighbors=0, shrink=False):
         """Removes cells and rebuilds the table around the rest (dsx_map_prune; the rule is stated in dsi_map_prune.h and
@@ -1377,25 +1425,15 @@ class WorldMap:
         o.reach, o.min_neighbors, o.shrink = int(reach), int(min_neighbors), 1 if shrink else 0
         i = _MapPruneInfo()
         _check(fn(self._h, C.byref(o), C.byref(i)))
-        return {"n_cells": int(i.n_cells), "n_kept": int(i.n_kept), "n_removed": [int(v) for v in i.n_removed],
-                "capacity": int(i.capacity)}
+        return _info_dict(i)
+
+    _PRUNE_COLUMNS = (_Column("reason", _U8), _Column("keys", _U64))  # (dsx_map_prune_fetch takes the values first)
 
     def fetchPruneReasons(self, sort=True):
         """keys (uint64) and reason (uint8: 0 kept, 1..5 the first criterion that failed) of every cell, from the last
         classifyPrune() of this map (dsx_map_prune_fetch); raises DsiError when the map changed since, or was never
         classified.  sort=True orders them by ascending key; otherwise the order is extract(sort=False)'s."""
-        L = load_library()
-        n = C.c_size_t()
-        rc = L.dsx_map_prune_fetch(self._h, None, None, 0, C.byref(n))
-        if rc != OK and n.value == 0:
-            _check(rc)
-        m = n.value
-        out = {"keys": np.empty(m, np.uint64), "reason": np.empty(m, np.uint8)}
-        _check(L.dsx_map_prune_fetch(self._h, _ptr(out["reason"], C.c_uint8), _ptr(out["keys"], C.c_uint64), m, C.byref(n)))
-        if sort:
-            order = np.argsort(out["keys"], kind="stable")
-            out = {k: v[order] for k, v in out.items()}
-        return out
+        return self._fetch_rows(load_library().dsx_map_prune_fetch, self._PRUNE_COLUMNS, sort)
 
     def components(self, min_points=1, min_windows=1, connectivity=26):
         """Labels the map's connected components (dsx_map_components; the rule is stated in dsi_map_components.h and
@@ -1409,48 +1447,32 @@ class WorldMap:
         i = _MapComponentsInfo()
         _check(load_library().dsx_map_components(self._h, C.byref(o), C.byref(i)))
         self._components_selected = False
-        return {k: int(getattr(i, k)) for k, _ in _MapComponentsInfo._fields_}
+        return _info_dict(i)
+
+    _COMPONENT_COLUMNS = (_Column("keys", _U64), _Column("labels", _U64), _Column("reason", _U8, flag="_components_selected"))
 
     def fetchComponents(self, sort=True):
         """keys and labels (uint64) of every node of the last components() of this map and, after a selectComponents() on
         it, reason (uint8: 0 kept, 1..4 the first reason of the selection that holds) (dsx_map_components_fetch); raises
         DsiError when the map changed since.  sort=True orders them by ascending key; otherwise the order is
         extract(sort=False)'s under the labelling's filter."""
-        L = load_library()
-        n = C.c_size_t()
-        rc = L.dsx_map_components_fetch(self._h, None, None, None, 0, C.byref(n))
-        if rc != OK and n.value == 0:
-            _check(rc)
-        m = n.value
-        out = {"keys": np.empty(m, np.uint64), "labels": np.empty(m, np.uint64)}
-        if getattr(self, "_components_selected", False):
-            out["reason"] = np.empty(m, np.uint8)
-        _check(L.dsx_map_components_fetch(self._h, _ptr(out["keys"], C.c_uint64), _ptr(out["labels"], C.c_uint64),
-                                          _ptr(out["reason"], C.c_uint8) if "reason" in out else None, m, C.byref(n)))
-        if sort:
-            order = np.argsort(out["keys"], kind="stable")
-            out = {k: v[order] for k, v in out.items()}
-        return out
+        return self._fetch_rows(load_library().dsx_map_components_fetch, self._COMPONENT_COLUMNS, sort)
+
+    _COMPONENT_LIST_COLUMNS = (_Column("labels", _U64), _Column("cells", _U64), _Column("points", _U64))
 
     def listComponents(self):
         """labels, cells and points (uint64) of every component of the last components() of this map
         (dsx_map_components_list), by cells descending, then label ascending; raises DsiError when the map changed since."""
-        L = load_library()
-        n = C.c_size_t()
-        rc = L.dsx_map_components_list(self._h, None, None, None, 0, C.byref(n))
-        if rc != OK and n.value == 0:
-            _check(rc)
-        m = n.value
-        out = {"labels": np.empty(m, np.uint64), "cells": np.empty(m, np.uint64), "points": np.empty(m, np.uint64)}
-        _check(L.dsx_map_components_list(self._h, _ptr(out["labels"], C.c_uint64), _ptr(out["cells"], C.c_uint64),
-                                         _ptr(out["points"], C.c_uint64), m, C.byref(n)))
+        out = self._fetch_rows(load_library().dsx_map_components_list, self._COMPONENT_LIST_COLUMNS, sort=False)
         order = np.lexsort((out["labels"], -out["cells"].astype(np.int64)))
         return {k: v[order] for k, v in out.items()}
 
     def selectComponents(self, min_cells=1, min_component_points=1, keep_largest=0, shrink=False):
         """pruneComponents()'s dry run (dsx_map_components_select): the same counts, the map unchanged; the per-cell reasons
         stay on the device for fetchComponents until the map changes."""
-        return self._select_components(load_library().dsx_map_components_select, min_cells, min_component_points, keep_largest, shrink)
+        return self._select(load_library().dsx_map_components_select,
+                            _MapComponentsSelection(int(min_cells), int(min_component_points), int(keep_largest), 1 if shrink else 0),
+                            _MapComponentsSelectInfo(), "_components_selected")
 
     def pruneComponents(self, min_cells=1, min_component_points=1, keep_largest=0, shrink=False):
         """Removes cells by the last components() of this map and rebuilds the table around the rest
@@ -1459,16 +1481,9 @@ class WorldMap:
         among the keep_largest first of those left, by cells descending, then label ascending.  shrink as prune()'s.
         Returns dict of n_cells = n_kept + sum(n_removed), n_kept, n_removed (four counts, by reason), n_components_kept
         and capacity (slots afterwards).  Render, compare, alignment, classification and labelling are invalid afterwards."""
-        return self._select_components(load_library().dsx_map_prune_components, min_cells, min_component_points, keep_largest, shrink)
-
-    def _select_components(self, fn, min_cells, min_component_points, keep_largest, shrink):
-        s = _MapComponentsSelection(int(min_cells), int(min_component_points), int(keep_largest), 1 if shrink else 0)
-        i = _MapComponentsSelectInfo()
-        self._components_selected = False
-        _check(fn(self._h, C.byref(s), C.byref(i)))
-        self._components_selected = True
-        return {"n_cells": int(i.n_cells), "n_kept": int(i.n_kept), "n_removed": [int(v) for v in i.n_removed],
-                "n_components_kept": int(i.n_components_kept), "capacity": int(i.capacity)}
+        return self._select(load_library().dsx_map_prune_components,
+                            _MapComponentsSelection(int(min_cells), int(min_component_points), int(keep_largest), 1 if shrink else 0),
+                            _MapComponentsSelectInfo(), "_components_selected")
 
     def query(self, points, k, radius, min_points=1, min_windows=1):
         """The k nearest cells of every point (dsx_map_knn_points; the rule is stated in dsi_map_knn.h and DESIGN.md 7j
@@ -1496,35 +1511,25 @@ class WorldMap:
         i = _MapKnnInfo()
         _check(load_library().dsx_map_knn(self._h, C.byref(o), C.byref(i)))
         self._knn_selected = False
-        out = {f: int(getattr(i, f)) for f in ("n_cells", "n_unqueried", "n_scored", "n_isolated", "sum_q", "reach")}
+        out = _info_dict(i, ("n_cells", "n_unqueried", "n_scored", "n_isolated", "sum_q", "reach"))
         out["sum_q2"] = int(i.sum_q2[0]) | (int(i.sum_q2[1]) << 64)
         return out
+
+    _KNN_COLUMNS = (_Column("keys", _U64), _Column("found", _U8), _Column("mean", _F32), _Column("q", _U32),
+                    _Column("reason", _U8, flag="_knn_selected"))
 
     def fetchKnn(self, sort=True):
         """keys (uint64), found (uint8), mean (float32, +inf where found is 0) and q (uint32) of every query of the last
         knn() of this map and, after a selectOutliers() on it, reason (uint8: 0 kept, 1..3 the first reason that holds)
         (dsx_map_knn_fetch); raises DsiError when the map changed since.  sort=True orders them by ascending key; otherwise
         the order is extract(sort=False)'s under the query's filter."""
-        L = load_library()
-        n = C.c_size_t()
-        rc = L.dsx_map_knn_fetch(self._h, None, None, None, None, None, 0, C.byref(n))
-        if rc != OK and n.value == 0:
-            _check(rc)
-        m = n.value
-        out = {"keys": np.empty(m, np.uint64), "found": np.empty(m, np.uint8), "mean": np.empty(m, np.float32), "q": np.empty(m, np.uint32)}
-        if getattr(self, "_knn_selected", False):
-            out["reason"] = np.empty(m, np.uint8)
-        _check(L.dsx_map_knn_fetch(self._h, _ptr(out["keys"], C.c_uint64), _ptr(out["found"], C.c_uint8), _ptr(out["mean"], C.c_float),
-                                   _ptr(out["q"], C.c_uint32), _ptr(out["reason"], C.c_uint8) if "reason" in out else None, m, C.byref(n)))
-        if sort:
-            order = np.argsort(out["keys"], kind="stable")
-            out = {f: v[order] for f, v in out.items()}
-        return out
+        return self._fetch_rows(load_library().dsx_map_knn_fetch, self._KNN_COLUMNS, sort)
 
     def selectOutliers(self, std_mult=1.0, shrink=False):
         """pruneOutliers()'s dry run (dsx_map_knn_select): the same counts, the map unchanged; the per-cell reasons stay on
         the device for fetchKnn until the map changes."""
-        return self._select_outliers(load_library().dsx_map_knn_select, std_mult, shrink)
+        return self._select(load_library().dsx_map_knn_select, _MapKnnSelection(float(std_mult), 1 if shrink else 0), _MapKnnSelectInfo(),
+                            "_knn_selected")
 
     def pruneOutliers(self, std_mult=1.0, shrink=False):
         """PCL's StatisticalOutlierRemoval on the last knn() of this map (dsx_map_prune_knn): a cell leaves by the first
@@ -1533,16 +1538,8 @@ class WorldMap:
         (knn_threshold) -- and the table is rebuilt around the rest, shrink as prune()'s.  Returns dict of n_cells = n_kept +
         sum(n_removed), n_kept, n_removed (three counts, by reason), T_q, mu, sigma and capacity (slots afterwards).
         Render, compare, alignment, classification, labelling and self query are invalid afterwards."""
-        return self._select_outliers(load_library().dsx_map_prune_knn, std_mult, shrink)
-
-    def _select_outliers(self, fn, std_mult, shrink):
-        s = _MapKnnSelection(float(std_mult), 1 if shrink else 0)
-        i = _MapKnnSelectInfo()
-        self._knn_selected = False
-        _check(fn(self._h, C.byref(s), C.byref(i)))
-        self._knn_selected = True
-        return {"n_cells": int(i.n_cells), "n_kept": int(i.n_kept), "n_removed": [int(v) for v in i.n_removed], "T_q": int(i.T_q),
-                "mu": float(i.mu), "sigma": float(i.sigma), "capacity": int(i.capacity)}
+        return self._select(load_library().dsx_map_prune_knn, _MapKnnSelection(float(std_mult), 1 if shrink else 0), _MapKnnSelectInfo(),
+                            "_knn_selected")
 
     def pca(self, k, radius, min_found=2, orient=False, viewpoint=None, keep_moments=False, min_points=1, min_windows=1):
         """The local shape of every cell extract(min_points, min_windows) returns (dsx_map_pca; the rule is stated in
@@ -1566,42 +1563,26 @@ class WorldMap:
         self._pca_moments = False
         _check(load_library().dsx_map_pca(self._h, C.byref(o), C.byref(i)))
         self._pca_moments = bool(keep_moments)
-        out = {f: int(getattr(i, f)) for f in ("n_cells", "n_unqueried", "n_sparse", "n_normal_determined", "n_tangent_determined",
-                                               "sum_members", "reach")}
-        out["n_label"] = [int(v) for v in i.n_label]
-        return out
+        return _info_dict(i, ("n_cells", "n_unqueried", "n_sparse", "n_normal_determined", "n_tangent_determined", "sum_members", "reach",
+                              "n_label"))
+
+    _PCA_COLUMNS = (_Column("keys", _U64), _Column("normal", _F32, (3,)), _Column("tangent", _F32, (3,)), _Column("eval", _F32, (3,)),
+                    _Column("members", _U16), _Column("label", _U8), _Column("flags", _U8), _Column("moments", _I64, (9,), flag="_pca_moments"),
+                    _Column("reason", _U8, flag="_pca_selected"))
 
     def fetchPca(self, sort=False):
         """keys (uint64), normal, tangent and eval ((M, 3) float32), members (uint16), label and flags (uint8) of every query
         of the last pca() of this map, moments ((M, 9) int64: s[3], ss[6]) when it kept them and, after a selectShapes() on
         it, reason (uint8: 0 kept, 1..3 the first reason that holds) (dsx_map_pca_fetch); raises DsiError when the map
         changed since.  The order is extract(sort=False)'s under the pass's filter; sort=True orders by ascending key."""
-        L = load_library()
-        n = C.c_size_t()
-        rc = L.dsx_map_pca_fetch(self._h, None, None, None, None, None, None, None, None, None, 0, C.byref(n))
-        if rc != OK and n.value == 0:
-            _check(rc)
-        m = n.value
-        out = {"keys": np.empty(m, np.uint64), "normal": np.empty((m, 3), np.float32), "tangent": np.empty((m, 3), np.float32),
-               "eval": np.empty((m, 3), np.float32), "members": np.empty(m, np.uint16), "label": np.empty(m, np.uint8),
-               "flags": np.empty(m, np.uint8)}
-        if getattr(self, "_pca_moments", False):
-            out["moments"] = np.empty((m, 9), np.int64)
-        if getattr(self, "_pca_selected", False):
-            out["reason"] = np.empty(m, np.uint8)
-        _check(L.dsx_map_pca_fetch(self._h, _ptr(out["keys"], C.c_uint64), _ptr(out["normal"], C.c_float), _ptr(out["tangent"], C.c_float),
-                                   _ptr(out["eval"], C.c_float), _ptr(out["members"], C.c_uint16), _ptr(out["label"], C.c_uint8),
-                                   _ptr(out["flags"], C.c_uint8), _ptr(out["moments"], C.c_int64) if "moments" in out else None,
-                                   _ptr(out["reason"], C.c_uint8) if "reason" in out else None, m, C.byref(n)))
-        if sort:
-            order = np.argsort(out["keys"], kind="stable")
-            out = {f: v[order] for f, v in out.items()}
-        return out
+        return self._fetch_rows(load_library().dsx_map_pca_fetch, self._PCA_COLUMNS, sort)
 
     def selectShapes(self, keep=("linear", "planar"), remove_sparse=True, shrink=False):
         """pruneShapes()'s dry run (dsx_map_pca_select): the same counts, the map unchanged; the per-cell reasons stay on the
         device for fetchPca until the map changes."""
-        return self._select_shapes(load_library().dsx_map_pca_select, keep, remove_sparse, shrink)
+        return self._select(load_library().dsx_map_pca_select,
+                            _MapPcaSelection(shape_mask(keep), 1 if remove_sparse else 0, 1 if shrink else 0), _MapPcaSelectInfo(),
+                            "_pca_selected")
 
     def pruneShapes(self, keep=("linear", "planar"), remove_sparse=True, shrink=False):
         """Keeps the cells of the last pca() of this map whose label is in keep -- names out of "linear", "planar" and
@@ -1609,15 +1590,11 @@ class WorldMap:
         fails the pass's filter; it is sparse and remove_sparse; its label is not kept -- and the table is rebuilt around the
         rest, shrink as prune()'s.  Returns dict of n_cells = n_kept + sum(n_removed), n_kept, n_removed (three counts, by
         reason) and capacity (slots afterwards).  Everything derived from the map is invalid afterwards."""
-        return self._select_shapes(load_library().dsx_map_prune_pca, keep, remove_sparse, shrink)
+        return self._select(load_library().dsx_map_prune_pca,
+                            _MapPcaSelection(shape_mask(keep), 1 if remove_sparse else 0, 1 if shrink else 0), _MapPcaSelectInfo(),
+                            "_pca_selected")
 
-    def _select_shapes(self, fn, keep, remove_sparse, shrink):
-        s = _MapPcaSelection(shape_mask(keep), 1 if remove_sparse else 0, 1 if shrink else 0)
-        i = _MapPcaSelectInfo()
-        self._pca_selected = False
-        _check(fn(self._h, C.byref(s), C.byref(i)))
-        self._pca_selected = True
-        return {"n_cells": int(i.n_cells), "n_kept": int(i.n_kept), "n_removed": [int(v) for v in i.n_removed], "capacity": int(i.capacity)}
+    _STATE_COLUMNS = (_Column("keys", _U64), _Column("n", _U32), _Column("S", _U64, (3,)), _Column("windows", _U32), _Column("stamp", _U32))
 
     def exportState(self, sort=True):
         """The map's exact state (dsx_map_export; the rule is stated in dsi_map_merge.h and DESIGN.md 7j "Merging"): dict
@@ -1625,27 +1602,9 @@ class WorldMap:
         32-bit cell fractions), windows and stamp (uint32).  sort=True orders the cells by ascending key; otherwise the
         order is extract(sort=False)'s.  importState() of it into an empty map restores the map bit for bit, ages
         included; io.save_world_map writes it to a file.  Changes nothing: render, compare and classification stay."""
-        L = load_library()
-        st, cnt = _MapState(), C.c_size_t()
-        rc = L.dsx_map_export(self._h, C.byref(st), None, None, None, None, None, 0, C.byref(cnt))
-        if rc != OK and cnt.value == 0:
-            _check(rc)
-        m = cnt.value
-        cells = {"keys": np.empty(m, np.uint64), "n": np.empty(m, np.uint32), "S": np.empty((m, 3), np.uint64),
-                 "windows": np.empty(m, np.uint32), "stamp": np.empty(m, np.uint32)}
-        _check(L.dsx_map_export(self._h, C.byref(st), _ptr(cells["keys"], C.c_uint64), _ptr(cells["n"], C.c_uint32),
-                                _ptr(cells["S"], C.c_uint64), _ptr(cells["windows"], C.c_uint32), _ptr(cells["stamp"], C.c_uint32), m,
-                                C.byref(cnt)))
-        if sort:
-            order = np.argsort(cells["keys"], kind="stable")
-            cells = {k: v[order] for k, v in cells.items()}
-        out = {"leaf": float(st.leaf), "calls": int(st.calls), "accepted": int(st.accepted), "rejected": int(st.rejected)}
-        out.update(cells)
-        return out
-
-    @staticmethod
-    def _merge_info(i):
-        return {k: int(getattr(i, k)) for k in ("n_src_cells", "n_new", "n_common", "capacity", "growths")}
+        st = _MapState()
+        cells = self._fetch_rows(load_library().dsx_map_export, self._STATE_COLUMNS, sort, lead=(C.byref(st),))
+        return dict(_info_dict(st, ("leaf", "calls", "accepted", "rejected")), **cells)
 
     def importState(self, state):
         """Appends an exported state to this map (dsx_map_import), exactly as merge() appends the map it came from: into
@@ -1662,7 +1621,7 @@ class WorldMap:
         i = _MapMergeInfo()
         _check(load_library().dsx_map_import(self._h, C.byref(st), _ptr(keys, C.c_uint64), _ptr(n, C.c_uint32), _ptr(S, C.c_uint64),
                                              _ptr(w, C.c_uint32), _ptr(s, C.c_uint32), C.byref(i)))
-        return self._merge_info(i)
+        return _info_dict(i)
 
     def merge(self, other):
         """Appends `other` (a WorldMap on the same context and of the same leaf) to this map on the device
@@ -1672,7 +1631,7 @@ class WorldMap:
         process.merge_world_maps.  Returns importState()'s dict."""
         i = _MapMergeInfo()
         _check(load_library().dsx_map_merge(self._h, other._h, C.byref(i)))
-        return self._merge_info(i)
+        return _info_dict(i)
 
     @staticmethod
     def _align_opts(radius, min_points, min_windows, min_points_other, min_windows_other, max_iterations=1, min_matched=0,
@@ -1697,23 +1656,13 @@ class WorldMap:
             out.update(self.fetchAlignment())
         return out
 
+    _ALIGNMENT_COLUMNS = (_Column("keys", _U64), _Column("keys_other", _U64), _Column("dist", _F32))
+
     def fetchAlignment(self, sort=True):
         """keys (uint64, this map's), keys_other (uint64, the correspondence's key in the other map; 0 where unmatched) and
         dist (float32, inf where unmatched) of the last alignStep() or align() of this map (dsx_map_align_fetch); raises
         DsiError when the map changed since, or was never aligned.  sort=True orders them by ascending key."""
-        L = load_library()
-        n = C.c_size_t()
-        rc = L.dsx_map_align_fetch(self._h, None, None, None, 0, C.byref(n))
-        if rc != OK and n.value == 0:
-            _check(rc)
-        m = n.value
-        out = {"keys": np.empty(m, np.uint64), "keys_other": np.empty(m, np.uint64), "dist": np.empty(m, np.float32)}
-        _check(L.dsx_map_align_fetch(self._h, _ptr(out["keys"], C.c_uint64), _ptr(out["keys_other"], C.c_uint64),
-                                     _ptr(out["dist"], C.c_float), m, C.byref(n)))
-        if sort:
-            order = np.argsort(out["keys"], kind="stable")
-            out = {k: v[order] for k, v in out.items()}
-        return out
+        return self._fetch_rows(load_library().dsx_map_align_fetch, self._ALIGNMENT_COLUMNS, sort)
 
     def align(self, other, radius, T_init=None, max_iterations=20, min_matched=3, eps_rot=1e-6, eps_trans=None, min_points=1,
               min_windows=1, min_points_other=1, min_windows_other=1):
@@ -1731,9 +1680,7 @@ class WorldMap:
         T = np.empty(12, np.float64)
         i = _MapAlignInfo()
         rc = load_library().dsx_map_align(self._h, other._h, C.byref(o), _ptr(T0, C.c_double), _ptr(T, C.c_double), C.byref(i))
-        info = {k: int(getattr(i, k)) for k in ("iterations", "converged", "stopped", "reach", "n_cells", "n_matched_first",
-                                                 "n_matched_last")}
-        info.update({k: float(getattr(i, k)) for k in ("rms_first", "rms_last", "angle_last", "trans_last")})
+        info = _info_dict(i)
         if rc != OK:
             try:
                 _check(rc)

@@ -10,6 +10,8 @@ engine kernel.
     full_sequence / WindowStream   mapper_emvs_stereo/src/main.cpp:174-302  (--full_seq: a window of
                 `duration` seconds every `out_skip` seconds, process_1 per window)
 """
+import collections
+
 import numpy as np
 
 from . import engine as E
@@ -743,6 +745,71 @@ class WindowStream:
         self._pins = {}
 
 
+def _prune_world_map(opts, local_box, T_rv_w):
+    """The options of one prune of a streamed map: opts as WorldMap.prune takes them; with local_box the box around the
+    window's reference position, the translation of engine.invert_pose(T_rv_w) -- the T_w_rv the window's cloud was
+    integrated with."""
+    if local_box is None:
+        return opts
+    t = E.invert_pose(T_rv_w)[[3, 7, 11]]
+    return dict(opts, box=(t - local_box, t + local_box))
+
+
+def _pop_local_box(opts):
+    """world_map_prune's local_box, taken out of opts before its keys are checked: the half extents as three doubles"""
+    local_box = opts.pop("local_box", None)
+    if local_box is not None:
+        if opts.get("box") is not None:
+            raise ValueError("world_map_prune takes box or local_box, not both")
+        local_box = np.asarray(local_box, np.float64).reshape(3)
+    return local_box
+
+
+def _check_keep(opts):
+    if E.shape_mask(opts.get("keep", ("linear", "planar"))) not in range(1, 8):
+        raise ValueError("world_map_shapes['keep'] must name at least one of linear, planar and scattered")
+
+
+# full_sequence's map stages, in the order they run on a window.  name: the keyword, and the key of the element a window's
+# result gains; run, run_keys: the WorldMap method of the pass (None: the stage only prunes) and the keywords it takes;
+# required: those that have no default; prune, prune_keys: the method that removes cells, and its keywords; prepare(opts):
+# called before the keys are checked, takes what belongs to neither method out of opts and returns it; check(opts): a last
+# look at the values; per_window(prune_opts, what prepare returned, the window's T_rv_w): the prune's keywords for one window.
+# A new stage is one more row (and its keyword in full_sequence's signature and docstring).
+_MapStage = collections.namedtuple("_MapStage", "name run run_keys required prune prune_keys prepare check per_window",
+                                   defaults=(None, None, None))
+_MAP_STAGES = (
+    _MapStage("world_map_prune", None, (), (), "prune",
+              ("min_points", "min_windows", "max_age", "box", "reach", "min_neighbors", "shrink"), _pop_local_box, None, _prune_world_map),
+    _MapStage("world_map_components", "components", ("min_points", "min_windows", "connectivity"), (), "pruneComponents",
+              ("min_cells", "min_component_points", "keep_largest", "shrink")),
+    _MapStage("world_map_outliers", "knn", ("k", "radius", "min_found", "min_points", "min_windows"), ("k", "radius"), "pruneOutliers",
+              ("std_mult", "shrink")),
+    _MapStage("world_map_shapes", "pca", ("k", "radius", "min_found", "orient", "viewpoint", "min_points", "min_windows"), ("k", "radius"),
+              "pruneShapes", ("keep", "remove_sparse", "shrink"), None, _check_keep),
+)
+
+
+def _map_stage_options(stage, opts, world_map):
+    """One stage's keyword of full_sequence, checked: (the pass's keywords, the prune's, every, what stage.prepare returned)"""
+    if world_map is None:
+        raise ValueError("%s needs world_map" % stage.name)
+    opts = dict(opts)
+    every = opts.pop("every", 1)
+    if int(every) != every or every < 1:
+        raise ValueError("%s['every'] must be an integer >= 1" % stage.name)
+    state = stage.prepare(opts) if stage.prepare else None
+    unknown = set(opts) - set(stage.run_keys) - set(stage.prune_keys)
+    if unknown:
+        raise ValueError("%s: unknown keys %s" % (stage.name, sorted(unknown)))
+    if any(k not in opts for k in stage.required):
+        raise ValueError("%s needs %s" % (stage.name, " and ".join(stage.required)))
+    if stage.check:
+        stage.check(opts)
+    return ({k: v for k, v in opts.items() if k in stage.run_keys}, {k: v for k, v in opts.items() if k in stage.prune_keys}, int(every),
+            state)
+
+
 def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop_time_s, duration,
                   out_skip, fusion_method=E.FUSE_HM, forward_looking=True, rv_pos=0.0, options_depth_map=None,
                   options_point_cloud=None, polarities=None, save_images=False, out_path=None, lut=None, score=None,
@@ -808,68 +875,13 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
     `every` (default 1): after every every-th window, after world_map_outliers' work on that window, the map analyses its
     cells' local shape and keeps the labels in keep.  Such a window's result gains a last element, {"world_map_shapes": the
     counts of WorldMap.pca, and under "prune" those of WorldMap.pruneShapes}."""
-    shapes = None
-    if world_map_shapes is not None:
-        if world_map is None:
-            raise ValueError("world_map_shapes needs world_map")
-        shapes = dict(world_map_shapes)
-        every = shapes.pop("every", 1)
-        if int(every) != every or every < 1:
-            raise ValueError("world_map_shapes['every'] must be an integer >= 1")
-        pca_keys = {"k", "radius", "min_found", "orient", "viewpoint", "min_points", "min_windows"}
-        select_keys = {"keep", "remove_sparse", "shrink"}
-        unknown = set(shapes) - pca_keys - select_keys
-        if unknown:
-            raise ValueError("world_map_shapes: unknown keys %s" % sorted(unknown))
-        if "k" not in shapes or "radius" not in shapes:
-            raise ValueError("world_map_shapes needs k and radius")
-        if E.shape_mask(shapes.get("keep", ("linear", "planar"))) not in range(1, 8):
-            raise ValueError("world_map_shapes['keep'] must name at least one of linear, planar and scattered")
-        shapes = ({k: v for k, v in shapes.items() if k in pca_keys}, {k: v for k, v in shapes.items() if k in select_keys}, int(every))
-    outl = None
-    if world_map_outliers is not None:
-        if world_map is None:
-            raise ValueError("world_map_outliers needs world_map")
-        outl = dict(world_map_outliers)
-        every = outl.pop("every", 1)
-        if int(every) != every or every < 1:
-            raise ValueError("world_map_outliers['every'] must be an integer >= 1")
-        knn_keys, select_keys = {"k", "radius", "min_found", "min_points", "min_windows"}, {"std_mult", "shrink"}
-        unknown = set(outl) - knn_keys - select_keys
-        if unknown:
-            raise ValueError("world_map_outliers: unknown keys %s" % sorted(unknown))
-        if "k" not in outl or "radius" not in outl:
-            raise ValueError("world_map_outliers needs k and radius")
-        outl = ({k: v for k, v in outl.items() if k in knn_keys}, {k: v for k, v in outl.items() if k in select_keys}, int(every))
-    comps = None
-    if world_map_components is not None:
-        if world_map is None:
-            raise ValueError("world_map_components needs world_map")
-        comps = dict(world_map_components)
-        every = comps.pop("every", 1)
-        if int(every) != every or every < 1:
-            raise ValueError("world_map_components['every'] must be an integer >= 1")
-        label_keys, select_keys = {"min_points", "min_windows", "connectivity"}, {"min_cells", "min_component_points", "keep_largest", "shrink"}
-        unknown = set(comps) - label_keys - select_keys
-        if unknown:
-            raise ValueError("world_map_components: unknown keys %s" % sorted(unknown))
-        comps = ({k: v for k, v in comps.items() if k in label_keys}, {k: v for k, v in comps.items() if k in select_keys}, int(every))
-    prune = None
-    if world_map_prune is not None:
-        if world_map is None:
-            raise ValueError("world_map_prune needs world_map")
-        prune = dict(world_map_prune)
-        every, local_box = prune.pop("every", 1), prune.pop("local_box", None)
-        if int(every) != every or every < 1:
-            raise ValueError("world_map_prune['every'] must be an integer >= 1")
-        if local_box is not None:
-            if prune.get("box") is not None:
-                raise ValueError("world_map_prune takes box or local_box, not both")
-            local_box = np.asarray(local_box, np.float64).reshape(3)
-        unknown = set(prune) - {"min_points", "min_windows", "max_age", "box", "reach", "min_neighbors", "shrink"}
-        if unknown:
-            raise ValueError("world_map_prune: unknown keys %s" % sorted(unknown))
-        prune = (prune, int(every), local_box)
+    given = {"world_map_prune": world_map_prune, "world_map_components": world_map_components,
+             "world_map_outliers": world_map_outliers, "world_map_shapes": world_map_shapes}
+    checked = {}
+    for stage in reversed(_MAP_STAGES):              # the last stage's keyword is checked first: its refusal wins
+        if given[stage.name] is not None:
+            checked[stage.name] = _map_stage_options(stage, given[stage.name], world_map)
+    stages = [(stage, checked[stage.name]) for stage in _MAP_STAGES if stage.name in checked]    # in the order they run
     windows_seen = 0
     if world_map is not None:
         if options_point_cloud is None:
@@ -912,20 +924,18 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
         nonlocal windows_seen
         out = _window_result(ws, pending, options_depth_map, options_point_cloud, images, scoring, world_map)
         windows_seen += 1
-        if prune is not None and windows_seen % prune[1] == 0:
-            out = out + ({"world_map_prune": _prune_world_map(world_map, prune[0], prune[2], pending[3])},)
-        if comps is not None and windows_seen % comps[2] == 0:
-            counts = world_map.components(**comps[0])
-            counts["prune"] = world_map.pruneComponents(**comps[1])
-            out = out + ({"world_map_components": counts},)
-        if outl is not None and windows_seen % outl[2] == 0:
-            counts = world_map.knn(**outl[0])
-            counts["prune"] = world_map.pruneOutliers(**outl[1])
-            out = out + ({"world_map_outliers": counts},)
-        if shapes is not None and windows_seen % shapes[2] == 0:
-            counts = world_map.pca(**shapes[0])
-            counts["prune"] = world_map.pruneShapes(**shapes[1])
-            out = out + ({"world_map_shapes": counts},)
+        for stage, (pass_opts, prune_opts, every, state) in stages:
+            if windows_seen % every:
+                continue
+            if stage.per_window is not None:
+                prune_opts = stage.per_window(prune_opts, state, pending[3])
+            counts = getattr(world_map, stage.run)(**pass_opts) if stage.run else None
+            pruned = getattr(world_map, stage.prune)(**prune_opts)
+            if counts is None:
+                counts = pruned
+            else:
+                counts["prune"] = pruned
+            out = out + ({stage.name: counts},)
         return out
 
     try:
@@ -944,15 +954,6 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
             yield result(pending)
     finally:
         ws.close()
-
-
-def _prune_world_map(world_map, opts, local_box, T_rv_w):
-    """One prune of a streamed map: opts as WorldMap.prune takes them; with local_box the box around the window's reference
-    position, the translation of engine.invert_pose(T_rv_w) -- the T_w_rv the window's cloud was integrated with."""
-    if local_box is not None:
-        t = E.invert_pose(T_rv_w)[[3, 7, 11]]
-        opts = dict(opts, box=(t - local_box, t + local_box))
-    return world_map.prune(**opts)
 
 
 def _window_event_image(ctx, events, polarity, t_start, t_stop, cam):

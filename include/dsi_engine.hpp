@@ -1596,6 +1596,65 @@ inline std::array<double, 12> compose_pose(const std::array<double, 12>& A, cons
     return out;
 }
 
+// What WorldMap's members share (DESIGN.md 7j "The map's bindings").
+namespace detail {
+// f(args..., &info), checked: the counts of a pass
+template <typename Info, typename F, typename... Args>
+inline Info info_of(F f, Args... args)
+{
+    Info info;
+    check(f(args..., &info));
+    return info;
+}
+// null for a vector without elements: an output that is not asked for
+template <typename T>
+inline T* ptr(std::vector<T>& v) { return v.empty() ? nullptr : v.data(); }
+// The two calls of a fetch.  call(0, &n) asks for the number of rows -- it is refused for want of room as soon as there are
+// rows, so its refusal counts only when it leaves n at 0 --, room(n) makes room, and call(n, &n) fills it; with
+// fill_when_empty == false the second call is left out when there is no row.
+template <typename Call, typename Room>
+inline size_t fetch_rows(Call call, Room room, bool fill_when_empty = true)
+{
+    size_t n = 0;
+    const int rc = call((size_t)0, &n);
+    if (rc != DSI_OK && n == 0) check(rc);
+    room(n);
+    if (n || fill_when_empty) check(call(n, &n));
+    return n;
+}
+// rows[i] <- rows[order[i]] of a column of order.size() rows; a column without elements (an optional one) stays so
+template <typename T>
+inline void gather_rows(const std::vector<size_t>& order, std::vector<T>& column)
+{
+    if (column.empty()) return;
+    const size_t width = column.size() / order.size();
+    std::vector<T> out(column.size());
+    for (size_t i = 0; i < order.size(); ++i) std::copy_n(column.begin() + width * order[i], width, out.begin() + width * i);
+    column.swap(out);
+}
+template <typename T, typename... Rest>
+inline void gather_rows(const std::vector<size_t>& order, std::vector<T>& column, std::vector<Rest>&... rest)
+{
+    gather_rows(order, column);
+    gather_rows(order, rest...);
+}
+// the n rows of the columns in the order of less(a, b) over their indices, which may read the columns: they move afterwards
+template <typename Less, typename... Columns>
+inline void sort_rows(size_t n, Less less, Columns&... columns)
+{
+    std::vector<size_t> order(n);
+    for (size_t i = 0; i < n; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), less);
+    gather_rows(order, columns...);
+}
+// by ascending key: the order of a sorted fetch
+template <typename... Columns>
+inline void sort_rows_by_key(std::vector<uint64_t>& keys, Columns&... columns)
+{
+    sort_rows(keys.size(), [&](size_t a, size_t b) { return keys[a] < keys[b]; }, keys, columns...);
+}
+}  // namespace detail
+
 // A persistent world-frame map on the device (dsi_map_*): every integrate call moves one window's cloud from
 // its reference view to the world frame and merges it into cubic cells of edge `leaf` -- a centroid per cell (PCL's
 // VoxelGrid), the number of points and the number of calls (windows) that reached the cell.  The arithmetic is stated in
@@ -1840,40 +1899,24 @@ public:
     // the cells with n >= min_points and windows >= min_windows; sort: by ascending key (reproducible files)
     WorldMapCells extract(uint32_t min_points = 1, uint32_t min_windows = 1, bool sort = true) const
     {
-        WorldMapCells raw;
-        size_t n = count(min_points, min_windows);
-        raw.xyz.resize(3 * n);
-        raw.n.resize(n);
-        raw.windows.resize(n);
-        raw.keys.resize(n);
-        check(dsi_map_extract(h_, min_points, min_windows, raw.xyz.data(), raw.n.data(), raw.windows.data(), raw.keys.data(), n, &n));
-        if (!sort) return raw;
-        std::vector<size_t> order(n);
-        for (size_t i = 0; i < n; ++i) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return raw.keys[a] < raw.keys[b]; });
         WorldMapCells out;
-        for (size_t i : order) {
-            out.xyz.insert(out.xyz.end(), raw.xyz.begin() + 3 * i, raw.xyz.begin() + 3 * i + 3);
-            out.n.push_back(raw.n[i]);
-            out.windows.push_back(raw.windows[i]);
-            out.keys.push_back(raw.keys[i]);
-        }
+        size_t n = count(min_points, min_windows);
+        out.xyz.resize(3 * n);
+        out.n.resize(n);
+        out.windows.resize(n);
+        out.keys.resize(n);
+        check(dsi_map_extract(h_, min_points, min_windows, out.xyz.data(), out.n.data(), out.windows.data(), out.keys.data(), n, &n));
+        if (sort) detail::sort_rows_by_key(out.keys, out.xyz, out.n, out.windows);
         return out;
     }
-    dsi_map_info_t info() const
-    {
-        dsi_map_info_t i;
-        check(dsi_map_info(h_, &i));
-        return i;
-    }
+    dsi_map_info_t info() const { return detail::info_of<dsi_map_info_t>(dsi_map_info, h_); }
     void reset() { check(dsi_map_reset(h_)); }
 
     // the depth image the map presents to a pinhole camera (dsi_map_render; the arithmetic is stated in dsi_engine.h): the
     // images stay on the device for fetch_render and DepthScore::addMapRender until the map changes
     MapRenderInfo render(const MapView& view)
     {
-        MapRenderInfo info;
-        check(dsi_map_render(h_, &view, &info));
+        const MapRenderInfo info = detail::info_of<MapRenderInfo>(dsi_map_render, h_, &view);
         width_ = info.width;
         height_ = info.height;
         return info;
@@ -1928,22 +1971,10 @@ public:
     // (key, dist) of the last compare of this map; sort: by ascending key
     MapDistances fetchDistances(bool sort = true) const
     {
-        MapDistances raw;
-        size_t n = 0;
-        const int rc = dsx_map_compare_fetch(h_, nullptr, nullptr, 0, &n);
-        if (rc != DSI_OK && n == 0) check(rc);
-        raw.keys.resize(n);
-        raw.dist.resize(n);
-        check(dsx_map_compare_fetch(h_, raw.dist.data(), raw.keys.data(), n, &n));
-        if (!sort) return raw;
-        std::vector<size_t> order(n);
-        for (size_t i = 0; i < n; ++i) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return raw.keys[a] < raw.keys[b]; });
-        MapDistances out;
-        for (size_t i : order) {
-            out.keys.push_back(raw.keys[i]);
-            out.dist.push_back(raw.dist[i]);
-        }
+        MapDistances out;  // (the values come before the keys in this entry point and in dsx_map_prune_fetch)
+        detail::fetch_rows([&](size_t room, size_t* n) { return dsx_map_compare_fetch(h_, detail::ptr(out.dist), detail::ptr(out.keys), room, n); },
+                           [&](size_t n) { out.keys.resize(n), out.dist.resize(n); });
+        if (sort) detail::sort_rows_by_key(out.keys, out.dist);
         return out;
     }
 
@@ -1951,37 +1982,21 @@ public:
     // dsi_map_prune.h); render, compare and classification of the map are invalid afterwards
     MapPruneInfo prune(const MapPruneOptions& opts = MapPruneOptions())
     {
-        MapPruneInfo info;
-        check(dsx_map_prune(h_, &opts, &info));
-        return info;
+        return detail::info_of<MapPruneInfo>(dsx_map_prune, h_, &opts);
     }
     // prune's dry run (dsx_map_prune_classify): the same counts, the map unchanged; the verdicts stay on the device for
     // fetchPruneReasons until the map changes
     MapPruneInfo classifyPrune(const MapPruneOptions& opts = MapPruneOptions())
     {
-        MapPruneInfo info;
-        check(dsx_map_prune_classify(h_, &opts, &info));
-        return info;
+        return detail::info_of<MapPruneInfo>(dsx_map_prune_classify, h_, &opts);
     }
     // (key, reason) of every cell from the last classifyPrune of this map; sort: by ascending key
     MapPruneReasons fetchPruneReasons(bool sort = true) const
     {
-        MapPruneReasons raw;
-        size_t n = 0;
-        const int rc = dsx_map_prune_fetch(h_, nullptr, nullptr, 0, &n);
-        if (rc != DSI_OK && n == 0) check(rc);
-        raw.keys.resize(n);
-        raw.reason.resize(n);
-        check(dsx_map_prune_fetch(h_, raw.reason.data(), raw.keys.data(), n, &n));
-        if (!sort) return raw;
-        std::vector<size_t> order(n);
-        for (size_t i = 0; i < n; ++i) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return raw.keys[a] < raw.keys[b]; });
         MapPruneReasons out;
-        for (size_t i : order) {
-            out.keys.push_back(raw.keys[i]);
-            out.reason.push_back(raw.reason[i]);
-        }
+        detail::fetch_rows([&](size_t room, size_t* n) { return dsx_map_prune_fetch(h_, detail::ptr(out.reason), detail::ptr(out.keys), room, n); },
+                           [&](size_t n) { out.keys.resize(n), out.reason.resize(n); });
+        if (sort) detail::sort_rows_by_key(out.keys, out.reason);
         return out;
     }
 
@@ -1989,76 +2004,45 @@ public:
     // stays on the device until the map changes, and nothing else of the map changes
     MapComponentsInfo components(const MapComponentsOptions& opts = MapComponentsOptions())
     {
-        MapComponentsInfo info;
-        check(dsx_map_components(h_, &opts, &info));
-        return info;
+        return detail::info_of<MapComponentsInfo>(dsx_map_components, h_, &opts);
     }
     // (key, label) of every labelled cell from the last components() of this map, and with_reasons -- after a
     // selectComponents on it -- the selection's reason; sort: by ascending key
     MapComponentLabels fetchComponents(bool with_reasons = false, bool sort = true) const
     {
-        MapComponentLabels raw;
-        size_t n = 0;
-        const int rc = dsx_map_components_fetch(h_, nullptr, nullptr, nullptr, 0, &n);
-        if (rc != DSI_OK && n == 0) check(rc);
-        raw.keys.resize(n);
-        raw.labels.resize(n);
-        if (with_reasons) raw.reason.resize(n);
-        uint8_t none = 0;  // (an empty vector's data() may be null, which would not ask for the reasons)
-        check(dsx_map_components_fetch(h_, raw.keys.data(), raw.labels.data(), with_reasons ? (n ? raw.reason.data() : &none) : nullptr, n,
-                                       &n));
-        if (!sort) return raw;
-        std::vector<size_t> order(n);
-        for (size_t i = 0; i < n; ++i) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return raw.keys[a] < raw.keys[b]; });
         MapComponentLabels out;
-        for (size_t i : order) {
-            out.keys.push_back(raw.keys[i]);
-            out.labels.push_back(raw.labels[i]);
-            if (with_reasons) out.reason.push_back(raw.reason[i]);
-        }
+        uint8_t none = 0, *reasons = nullptr;  // (no vector's data(): without a row it may be null, which would not ask for the reasons)
+        detail::fetch_rows([&](size_t room, size_t* n) { return dsx_map_components_fetch(h_, detail::ptr(out.keys), detail::ptr(out.labels), reasons, room, n); },
+                           [&](size_t n) {
+                               out.keys.resize(n), out.labels.resize(n);
+                               if (with_reasons) out.reason.resize(n), reasons = n ? out.reason.data() : &none;
+                           });
+        if (sort) detail::sort_rows_by_key(out.keys, out.labels, out.reason);
         return out;
     }
     // (label, cells, points) of every component from the last components() of this map, by cells descending, then label
     // ascending
     MapComponentList listComponents() const
     {
-        MapComponentList raw;
-        size_t n = 0;
-        const int rc = dsx_map_components_list(h_, nullptr, nullptr, nullptr, 0, &n);
-        if (rc != DSI_OK && n == 0) check(rc);
-        raw.labels.resize(n);
-        raw.cells.resize(n);
-        raw.points.resize(n);
-        check(dsx_map_components_list(h_, raw.labels.data(), raw.cells.data(), raw.points.data(), n, &n));
-        std::vector<size_t> order(n);
-        for (size_t i = 0; i < n; ++i) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
-            return raw.cells[a] != raw.cells[b] ? raw.cells[a] > raw.cells[b] : raw.labels[a] < raw.labels[b];
-        });
         MapComponentList out;
-        for (size_t i : order) {
-            out.labels.push_back(raw.labels[i]);
-            out.cells.push_back(raw.cells[i]);
-            out.points.push_back(raw.points[i]);
-        }
+        const size_t n = detail::fetch_rows(
+            [&](size_t room, size_t* m) { return dsx_map_components_list(h_, detail::ptr(out.labels), detail::ptr(out.cells), detail::ptr(out.points), room, m); },
+            [&](size_t m) { out.labels.resize(m), out.cells.resize(m), out.points.resize(m); });
+        detail::sort_rows(n, [&](size_t a, size_t b) { return out.cells[a] != out.cells[b] ? out.cells[a] > out.cells[b] : out.labels[a] < out.labels[b]; },
+                          out.labels, out.cells, out.points);
         return out;
     }
     // pruneComponents' dry run (dsx_map_components_select): the same counts, the map unchanged; the reasons stay on the
     // device for fetchComponents(true) until the map changes
     MapComponentsSelectInfo selectComponents(const MapComponentsSelection& sel = MapComponentsSelection())
     {
-        MapComponentsSelectInfo info;
-        check(dsx_map_components_select(h_, &sel, &info));
-        return info;
+        return detail::info_of<MapComponentsSelectInfo>(dsx_map_components_select, h_, &sel);
     }
     // removes the cells that the selection rejects and rebuilds the table around the rest (dsx_map_prune_components);
     // render, compare, alignment, classification and labelling of the map are invalid afterwards
     MapComponentsSelectInfo pruneComponents(const MapComponentsSelection& sel = MapComponentsSelection())
     {
-        MapComponentsSelectInfo info;
-        check(dsx_map_prune_components(h_, &sel, &info));
-        return info;
+        return detail::info_of<MapComponentsSelectInfo>(dsx_map_prune_components, h_, &sel);
     }
 
     // the k nearest cells of n host points, stride 3 or 4 floats (dsx_map_knn_points; the rule is stated in dsi_map_knn.h);
@@ -2078,91 +2062,66 @@ public:
     // pruneOutliers until the map changes, and nothing else of the map changes
     MapKnnInfo knn(const MapKnnOptions& opts)
     {
-        MapKnnInfo info;
-        check(dsx_map_knn(h_, &opts, &info));
-        return info;
+        return detail::info_of<MapKnnInfo>(dsx_map_knn, h_, &opts);
     }
     // removes the isolated cells and the statistical outliers of the last knn() and rebuilds the table around the rest
     // (dsx_map_prune_knn); everything derived from the map is invalid afterwards
     MapKnnSelectInfo pruneOutliers(const MapKnnSelection& sel = MapKnnSelection())
     {
-        MapKnnSelectInfo info;
-        check(dsx_map_prune_knn(h_, &sel, &info));
-        return info;
+        return detail::info_of<MapKnnSelectInfo>(dsx_map_prune_knn, h_, &sel);
     }
 
     // the local shape of every cell (dsx_map_pca; the rule is stated in dsi_map_pca.h): the result stays on the device for
     // fetchPca and pruneShapes until the map changes, and nothing else of the map changes
     MapPcaInfo pca(const MapPcaOptions& opts)
     {
-        MapPcaInfo info;
-        check(dsx_map_pca(h_, &opts, &info));
+        const MapPcaInfo info = detail::info_of<MapPcaInfo>(dsx_map_pca, h_, &opts);
         pca_moments_ = opts.keep_moments != 0;
         return info;
     }
     // the rows of the last pca() (dsx_map_pca_fetch)
     MapShapes fetchPca() const
     {
-        MapShapes out;
-        size_t n = 0;
-        const int rc = dsx_map_pca_fetch(h_, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &n);
-        if (rc != DSI_OK && n == 0) check(rc);
-        out.keys.resize(n), out.normal.resize(3 * n), out.tangent.resize(3 * n), out.eval.resize(3 * n);
-        out.members.resize(n), out.label.resize(n), out.flags.resize(n);
-        if (pca_moments_) out.moments.resize(9 * n);
-        if (n)
-            check(dsx_map_pca_fetch(h_, out.keys.data(), out.normal.data(), out.tangent.data(), out.eval.data(), out.members.data(),
-                                    out.label.data(), out.flags.data(), pca_moments_ ? out.moments.data() : nullptr, nullptr, n, &n));
+        MapShapes out;  // (without a row the second call is left out, which the Python binding makes)
+        detail::fetch_rows(
+            [&](size_t room, size_t* n) {
+                return dsx_map_pca_fetch(h_, detail::ptr(out.keys), detail::ptr(out.normal), detail::ptr(out.tangent), detail::ptr(out.eval),
+                                         detail::ptr(out.members), detail::ptr(out.label), detail::ptr(out.flags), detail::ptr(out.moments),
+                                         nullptr, room, n);
+            },
+            [&](size_t n) {
+                out.keys.resize(n), out.normal.resize(3 * n), out.tangent.resize(3 * n), out.eval.resize(3 * n);
+                out.members.resize(n), out.label.resize(n), out.flags.resize(n);
+                if (pca_moments_) out.moments.resize(9 * n);
+            },
+            false);
         return out;
     }
     // keeps the cells of the last pca() whose label is in the selection and rebuilds the table around them
     // (dsx_map_prune_pca); everything derived from the map is invalid afterwards
     MapPcaSelectInfo pruneShapes(const MapPcaSelection& sel = MapPcaSelection())
     {
-        MapPcaSelectInfo info;
-        check(dsx_map_prune_pca(h_, &sel, &info));
-        return info;
+        return detail::info_of<MapPcaSelectInfo>(dsx_map_prune_pca, h_, &sel);
     }
 
     // appends `other` (same context, same leaf) to this map on the device (dsx_map_merge; the rule is stated in
     // dsi_map_merge.h): this map becomes the map that had made its own integrate calls and then other's.  other is
     // unchanged; render, compare and classification of this map are invalid afterwards
-    MapMergeInfo merge(const WorldMap& other)
-    {
-        MapMergeInfo info;
-        check(dsx_map_merge(h_, other.h_, &info));
-        return info;
-    }
+    MapMergeInfo merge(const WorldMap& other) { return detail::info_of<MapMergeInfo>(dsx_map_merge, h_, other.h_); }
     // the map's exact state (dsx_map_export); sort: by ascending key.  Changes nothing
     MapState exportState(bool sort = true) const
     {
-        MapState raw;
-        dsx_map_state_t st;
-        size_t m = 0;
-        const int rc = dsx_map_export(h_, &st, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &m);
-        if (rc != DSI_OK && m == 0) check(rc);
-        raw.keys.resize(m);
-        raw.n.resize(m);
-        raw.S.resize(3 * m);
-        raw.windows.resize(m);
-        raw.stamp.resize(m);
-        check(dsx_map_export(h_, &st, raw.keys.data(), raw.n.data(), raw.S.data(), raw.windows.data(), raw.stamp.data(), m, &m));
-        raw.leaf = st.leaf;
-        raw.calls = st.calls, raw.accepted = st.accepted, raw.rejected = st.rejected;
-        if (!sort) return raw;
-        std::vector<size_t> order(m);
-        for (size_t i = 0; i < m; ++i) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return raw.keys[a] < raw.keys[b]; });
         MapState out;
-        out.leaf = raw.leaf;
-        out.calls = raw.calls, out.accepted = raw.accepted, out.rejected = raw.rejected;
-        for (size_t i : order) {
-            out.keys.push_back(raw.keys[i]);
-            out.n.push_back(raw.n[i]);
-            for (size_t a = 0; a < 3; ++a) out.S.push_back(raw.S[3 * i + a]);
-            out.windows.push_back(raw.windows[i]);
-            out.stamp.push_back(raw.stamp[i]);
-        }
+        dsx_map_state_t st;
+        detail::fetch_rows(
+            [&](size_t room, size_t* m) {
+                return dsx_map_export(h_, &st, detail::ptr(out.keys), detail::ptr(out.n), detail::ptr(out.S), detail::ptr(out.windows),
+                                      detail::ptr(out.stamp), room, m);
+            },
+            [&](size_t m) { out.keys.resize(m), out.n.resize(m), out.S.resize(3 * m), out.windows.resize(m), out.stamp.resize(m); });
+        out.leaf = st.leaf;
+        out.calls = st.calls, out.accepted = st.accepted, out.rejected = st.rejected;
+        if (sort) detail::sort_rows_by_key(out.keys, out.n, out.S, out.windows, out.stamp);
         return out;
     }
     // appends an exported state as merge appends the map it came from (dsx_map_import): into an empty map without calls
@@ -2173,9 +2132,8 @@ public:
         if (state.n.size() != m || state.windows.size() != m || state.stamp.size() != m || state.S.size() != 3 * m)
             throw Error(DSI_ERR_INVALID, "MapState: keys, n, windows and stamp need one entry per cell and S three");
         const dsx_map_state_t st{state.leaf, (uint64_t)m, state.calls, state.accepted, state.rejected};
-        MapMergeInfo info;
-        check(dsx_map_import(h_, &st, state.keys.data(), state.n.data(), state.S.data(), state.windows.data(), state.stamp.data(), &info));
-        return info;
+        return detail::info_of<MapMergeInfo>(dsx_map_import, h_, &st, state.keys.data(), state.n.data(), state.S.data(), state.windows.data(),
+                                             state.stamp.data());
     }
 
     // one correspondence pass of ICP (dsx_map_align_step; the arithmetic is stated in dsi_map_align.h): every filtered
@@ -2183,9 +2141,7 @@ public:
     // opts.radius; the exact integer moments of the matched pairs come back, the pairs stay on the device
     MapAlignMoments align_step(const WorldMap& other, const MapAlignOptions& opts, const std::array<double, 12>& T = kIdentityPose)
     {
-        MapAlignMoments m;
-        check(dsx_map_align_step(h_, other.h_, &opts, T.data(), &m));
-        return m;
+        return detail::info_of<MapAlignMoments>(dsx_map_align_step, h_, other.h_, &opts, T.data());
     }
     // ICP of this map onto `other` from T_init (dsx_map_align).  A round with too few matched cells or degenerate pairs
     // does not throw: the result then has ok == false, the last good pose and info.stopped; every other error throws
