@@ -19,7 +19,7 @@ HEADERS = ["dsi_kernels.h", "dsi_vote_asm.h", "dsi_host.hpp", "dsi_owned.hpp", "
            os.path.join("..", "..", "include", "dsi_map_eval.h"), os.path.join("..", "..", "include", "dsi_map_prune.h"),
            os.path.join("..", "..", "include", "dsi_map_merge.h"), os.path.join("..", "..", "include", "dsi_map_align.h"),
            os.path.join("..", "..", "include", "dsi_map_components.h"), os.path.join("..", "..", "include", "dsi_map_knn.h"),
-           os.path.join("..", "..", "include", "dsi_map_pca.h")]
+           os.path.join("..", "..", "include", "dsi_map_pca.h"), os.path.join("..", "..", "include", "dsi_map_visibility.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
          "-fvisibility=hidden", "-Wall", "-Wextra", "-Wno-unused-parameter", "-x", "hip"]
 

@@ -12,6 +12,7 @@
 #include "../../include/dsi_map_components.h"
 #include "../../include/dsi_map_knn.h"
 #include "../../include/dsi_map_pca.h"
+#include "../../include/dsi_map_visibility.h"
 #include "../../include/dsi_map_prune.h"
 #include "../../include/dsi_map_merge.h"
 #include "../../include/dsi_map_align.h"
@@ -4112,6 +4113,14 @@ struct dsi_map {
     DevBuf<unsigned long long> pca_ctr;
     dsx_map_pca_opts_t pca_opts = {};
     bool pca_valid = false, pca_select_valid = false;
+    // the visibility tally (dsx_map_observe, include/dsi_map_visibility.h): accumulates over observations until the map
+    // changes or dsx_map_visibility_clear; the selection (dsx_map_visibility_select) is valid until the next observation
+    DevBuf<uint32_t> vis_seen, vis_agree, vis_through, vis_seen_out, vis_agree_out, vis_through_out;  // per slot; compacted for a fetch
+    DevBuf<uint8_t> vis_reason, vis_reason_out, vis_mask;  // vis_mask and vis_depth: dsx_map_observe's staging
+    DevBuf<float> vis_depth;
+    DevBuf<unsigned long long> vis_ctr;
+    uint64_t vis_views = 0;
+    bool vis_valid = false, vis_select_valid = false;
 };
 
 namespace {
@@ -4140,6 +4149,7 @@ void map_changed(dsi_map* mp)
 {
     mp->render_valid = mp->compare_valid = mp->prune_valid = mp->align_valid = false;
     mp->comp_valid = mp->comp_select_valid = mp->knn_valid = mp->knn_select_valid = mp->pca_valid = mp->pca_select_valid = false;
+    mp->vis_valid = mp->vis_select_valid = false;
 }
 
 // the table doubled until occupied + n <= 3/4 of its slots (the caller checked that 2^27 slots are enough)
@@ -5373,6 +5383,209 @@ int dsx_map_prune_pca(dsi_map_t* mp, const dsx_map_pca_selection_t* sel, dsx_map
     mp->pca_select_valid = true;  // (the reasons are those of the map as it stands, should the rebuild fail to allocate)
     if (int rc = map_rebuild_kept(mp, mp->pca_reason.p, ctr[0], ctr[1] + ctr[2] + ctr[3] != 0, sel->shrink)) return rc;
     map_pca_select_info(mp, ctr, info);
+    return DSI_OK;
+}
+
+// ---- the map carved by free space (include/dsi_map_visibility.h; DESIGN.md 7j "Visibility") ----
+
+namespace {
+
+// the bounds of an observation: decided without a device, before any handle is looked at
+int check_observation(const dsx_map_observation_t* o)
+{
+    REQUIRE(o, DSI_ERR_INVALID, "obs is null");
+    if (int rc = check_depth_image(o->width, o->height, o->fx, o->fy, o->cx, o->cy, o->min_depth, o->max_depth)) return rc;
+    REQUIRE(o->window >= 0 && o->window <= dsi::kMapObserveMaxWindow, DSI_ERR_INVALID, "window must be in 0..%d (got %d)",
+            dsi::kMapObserveMaxWindow, o->window);
+    REQUIRE(std::isfinite(o->abs_tol) && o->abs_tol >= 0.0 && std::isfinite(o->rel_tol) && o->rel_tol >= 0.0, DSI_ERR_INVALID,
+            "abs_tol and rel_tol must be finite and >= 0 (got %g, %g)", o->abs_tol, o->rel_tol);
+    return DSI_OK;
+}
+
+int check_visibility_selection(const dsx_map_visibility_selection_t* s)
+{
+    REQUIRE(s, DSI_ERR_INVALID, "sel is null");
+    REQUIRE(s->min_through >= 1u, DSI_ERR_INVALID, "min_through must be >= 1 (got %u)", s->min_through);
+    REQUIRE(s->shrink == 0 || s->shrink == 1, DSI_ERR_INVALID, "shrink must be 0 or 1 (got %d)", s->shrink);
+    return DSI_OK;
+}
+
+dsi::MapTally map_tally_of(const dsi_map* mp) { return dsi::MapTally{mp->vis_seen.p, mp->vis_agree.p, mp->vis_through.p}; }
+
+// what every entry point that reads the tally asks of the map
+int check_visibility_tally(const dsi_map* mp)
+{
+    REQUIRE(mp->vis_valid, DSI_ERR_INVALID,
+            "no visibility tally of the map as it stands: call dsx_map_observe (after the last reset, integrate call, merge, import, prune "
+            "or dsx_map_visibility_clear)");
+    return DSI_OK;
+}
+
+// one observation of a device depth image (mask_dev may be null) into the tally, which starts zeroed when there is none;
+// the caller checked obs and set the device.  Synchronises.
+int map_observe_device(dsi_map* mp, const float* depth_dev, const uint8_t* mask_dev, const dsx_map_observation_t* obs,
+                       dsx_map_observe_info_t* info)
+{
+    REQUIRE(mp->host_ctr[3] == 0, DSI_ERR_INVALID, "the map's table overflowed in an earlier call: reset the map");
+    REQUIRE(!mp->vis_valid || mp->vis_views < 0xffffffffull, DSI_ERR_INVALID, "at most 2^32 - 1 views per tally: clear it");
+    hipStream_t st = mp->ctx->stream;
+    const size_t cap = (size_t)1 << mp->cap_log2;
+    mp->vis_select_valid = false;
+    if (!mp->vis_valid) {
+        HIP_TRY(mp->vis_seen.reserve(cap));
+        HIP_TRY(mp->vis_agree.reserve(cap));
+        HIP_TRY(mp->vis_through.reserve(cap));
+        HIP_TRY(hipMemsetAsync(mp->vis_seen.p, 0, cap * sizeof(uint32_t), st));
+        HIP_TRY(hipMemsetAsync(mp->vis_agree.p, 0, cap * sizeof(uint32_t), st));
+        HIP_TRY(hipMemsetAsync(mp->vis_through.p, 0, cap * sizeof(uint32_t), st));
+        mp->vis_views = 0;
+    }
+    mp->vis_valid = false;  // (until the kernel went through: a tally that a failed launch may have half written is none)
+    HIP_TRY(mp->vis_ctr.reserve(std::max(dsi::kMapObserveCounters, dsi::kMapVisibilitySelectCounters)));
+    dsi::MapObserve o;
+    std::memcpy(o.T, obs->T_v_w, sizeof o.T);
+    o.fx = obs->fx, o.fy = obs->fy, o.cx = obs->cx, o.cy = obs->cy;
+    o.min_depth = obs->min_depth, o.max_depth = obs->max_depth;
+    o.abs_tol = obs->abs_tol, o.rel_tol = obs->rel_tol;
+    o.width = obs->width, o.height = obs->height, o.window = obs->window;
+    unsigned long long ctr[dsi::kMapObserveCounters] = {0, 0, 0, 0, 0, 0, 0};
+    HIP_TRY(dsi::launch_map_observe(st, dsi::map_table_at(mp->block.p, mp->cap_log2), o, mp->leaf, depth_dev, mask_dev, map_tally_of(mp),
+                                    mp->vis_ctr.p));
+    HIP_TRY(hipMemcpyAsync(ctr, mp->vis_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    mp->vis_valid = true;
+    ++mp->vis_views;
+    if (info) {
+        info->n_clipped = ctr[0], info->n_outside = ctr[1], info->n_unseen = ctr[2];
+        info->n_agree = ctr[3], info->n_through = ctr[4], info->n_behind = ctr[5];
+        info->n_cells = ((ctr[0] + ctr[1]) + (ctr[2] + ctr[3])) + (ctr[4] + ctr[5]);
+        info->n_valid_pixels = ctr[6];
+        info->views = mp->vis_views;
+    }
+    return DSI_OK;
+}
+
+// every cell's reason into mp->vis_reason and the counts into ctr (kMapVisibilitySelectCounters); synchronises
+int map_visibility_select_device(dsi_map* mp, const dsx_map_visibility_selection_t* sel, unsigned long long* ctr)
+{
+    hipStream_t st = mp->ctx->stream;
+    HIP_TRY(mp->vis_reason.reserve((size_t)1 << mp->cap_log2));
+    HIP_TRY(dsi::launch_map_visibility_select(st, dsi::map_table_at(mp->block.p, mp->cap_log2), map_tally_of(mp), sel->min_through,
+                                              sel->agree_weight, mp->vis_reason.p, mp->vis_ctr.p));
+    HIP_TRY(hipMemcpyAsync(ctr, mp->vis_ctr.p, dsi::kMapVisibilitySelectCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+void map_visibility_select_info(const dsi_map* mp, const unsigned long long* ctr, dsx_map_visibility_select_info_t* info)
+{
+    if (!info) return;
+    info->n_kept = ctr[0];
+    info->n_removed = ctr[1];
+    info->n_cells = ctr[0] + ctr[1];
+    info->capacity = (uint64_t)1 << mp->cap_log2;
+}
+
+}  // namespace
+
+int dsx_map_observe(dsi_map_t* mp, const float* depth_host, const uint8_t* mask_host, const dsx_map_observation_t* obs,
+                    dsx_map_observe_info_t* info)
+{
+    if (int rc = check_observation(obs)) return rc;  // (first: the bounds can be exercised with no map at hand)
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    REQUIRE(depth_host, DSI_ERR_INVALID, "depth_host is null");
+    if (int rc = set_device(mp->ctx)) return rc;
+    const size_t npix = (size_t)obs->width * (size_t)obs->height;
+    hipStream_t st = mp->ctx->stream;
+    HIP_TRY(mp->vis_depth.reserve(npix));
+    HIP_TRY(hipMemcpyAsync(mp->vis_depth.p, depth_host, npix * sizeof(float), hipMemcpyHostToDevice, st));
+    if (mask_host) {
+        HIP_TRY(mp->vis_mask.reserve(npix));
+        HIP_TRY(hipMemcpyAsync(mp->vis_mask.p, mask_host, npix, hipMemcpyHostToDevice, st));
+    }
+    return map_observe_device(mp, mp->vis_depth.p, mask_host ? mp->vis_mask.p : nullptr, obs, info);
+}
+
+int dsx_map_observe_mapper(dsi_map_t* mp, dsi_mapper_t* m, const dsx_map_observation_t* obs, dsx_map_observe_info_t* info)
+{
+    if (int rc = check_observation(obs)) return rc;
+    REQUIRE(mp && m, DSI_ERR_INVALID, "null argument");
+    REQUIRE(mp->ctx == m->ctx, DSI_ERR_CONTEXT, "the map and the mapper live on different contexts");
+    REQUIRE((size_t)m->geom.nz == m->planes_full.size(), DSI_ERR_INVALID,
+            "a plane-sharded mapper holds no whole depth map of its own: the observation needs the whole arg-max");
+    REQUIRE(m->filtered_valid, DSI_ERR_INVALID,
+            "no filtered depth map on the device: call dsi_mapper_filter_depth_map or dsi_mapper_get_depth_map_from_dsi "
+            "after the depth map was computed, or pass the maps to dsx_map_observe");
+    REQUIRE(obs->width == m->geom.nx && obs->height == m->geom.ny, DSI_ERR_INVALID, "the observation is %d x %d, the mapper's depth map %d x %d",
+            obs->width, obs->height, m->geom.nx, m->geom.ny);
+    if (int rc = set_device(mp->ctx)) return rc;
+    if (int rc = depth_buffers_acquire(m)) return rc;
+    return map_observe_device(mp, m->depth.p, m->mask.p, obs, info);
+}
+
+int dsx_map_visibility_clear(dsi_map_t* mp)
+{
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    mp->vis_valid = mp->vis_select_valid = false;  // (the next observation zeroes the words)
+    return DSI_OK;
+}
+
+int dsx_map_visibility_fetch(dsi_map_t* mp, uint64_t* keys_host, uint32_t* seen_host, uint32_t* agree_host, uint32_t* through_host,
+                             uint8_t* reasons_host, size_t capacity, size_t* count)
+{
+    REQUIRE(mp && count, DSI_ERR_INVALID, "null argument");
+    if (int rc = check_visibility_tally(mp)) return rc;
+    REQUIRE(!reasons_host || mp->vis_select_valid, DSI_ERR_INVALID,
+            "no selection on this tally: call dsx_map_visibility_select before asking for reasons");
+    if (int rc = set_device(mp->ctx)) return rc;
+    size_t total = 0;
+    if (int rc = map_fetch_count(mp, 1, 1, capacity, count, &total)) return rc;
+    if (!total) return DSI_OK;
+    hipStream_t st = mp->ctx->stream;
+    HIP_TRY(mp->key_out.reserve(total));
+    HIP_TRY(mp->vis_seen_out.reserve(total));
+    HIP_TRY(mp->vis_agree_out.reserve(total));
+    HIP_TRY(mp->vis_through_out.reserve(total));
+    if (reasons_host) HIP_TRY(mp->vis_reason_out.reserve(total));
+    const dsi::MapTally out{mp->vis_seen_out.p, mp->vis_agree_out.p, mp->vis_through_out.p};
+    HIP_TRY(dsi::launch_map_visibility_gather(st, dsi::map_table_at(mp->block.p, mp->cap_log2), map_tally_of(mp),
+                                              reasons_host ? mp->vis_reason.p : nullptr, mp->blk.p, mp->key_out.p, out,
+                                              reasons_host ? mp->vis_reason_out.p : nullptr));
+    if (keys_host) HIP_TRY(hipMemcpyAsync(keys_host, mp->key_out.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (seen_host) HIP_TRY(hipMemcpyAsync(seen_host, out.seen, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (agree_host) HIP_TRY(hipMemcpyAsync(agree_host, out.agree, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (through_host) HIP_TRY(hipMemcpyAsync(through_host, out.through, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (reasons_host) HIP_TRY(hipMemcpyAsync(reasons_host, mp->vis_reason_out.p, total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DSI_OK;
+}
+
+int dsx_map_visibility_select(dsi_map_t* mp, const dsx_map_visibility_selection_t* sel, dsx_map_visibility_select_info_t* info)
+{
+    if (int rc = check_visibility_selection(sel)) return rc;  // (first: the bounds can be exercised with no map at hand)
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    if (int rc = check_visibility_tally(mp)) return rc;
+    if (int rc = set_device(mp->ctx)) return rc;
+    mp->vis_select_valid = false;
+    unsigned long long ctr[dsi::kMapVisibilitySelectCounters] = {0, 0};
+    if (int rc = map_visibility_select_device(mp, sel, ctr)) return rc;
+    mp->vis_select_valid = true;
+    map_visibility_select_info(mp, ctr, info);
+    return DSI_OK;
+}
+
+int dsx_map_prune_visibility(dsi_map_t* mp, const dsx_map_visibility_selection_t* sel, dsx_map_visibility_select_info_t* info)
+{
+    if (int rc = check_visibility_selection(sel)) return rc;
+    REQUIRE(mp, DSI_ERR_INVALID, "map is null");
+    if (int rc = check_visibility_tally(mp)) return rc;
+    if (int rc = set_device(mp->ctx)) return rc;
+    mp->vis_select_valid = false;
+    unsigned long long ctr[dsi::kMapVisibilitySelectCounters] = {0, 0};
+    if (int rc = map_visibility_select_device(mp, sel, ctr)) return rc;
+    mp->vis_select_valid = true;  // (the reasons are those of the map as it stands, should the rebuild fail to allocate)
+    if (int rc = map_rebuild_kept(mp, mp->vis_reason.p, ctr[0], ctr[1] != 0, sel->shrink)) return rc;
+    map_visibility_select_info(mp, ctr, info);
     return DSI_OK;
 }
 

@@ -519,6 +519,31 @@ hipError_t launch_map_pca_gather(hipStream_t s, const MapTable& t, uint32_t min_
                                  const uint8_t* reason, const uint32_t* blk, unsigned long long* key_out, const MapPcaCells& out,
                                  uint8_t* reason_out);
 
+// ---- the map carved by free space (include/dsi_map_visibility.h; DESIGN.md 7j "Visibility") ----
+constexpr int kMapObserveMaxWindow = 3;
+constexpr int kMapObserveCounters = 7;           // clipped, outside, unseen, agree, through, behind, the image's valid pixels
+constexpr int kMapVisibilitySelectCounters = 2;  // kept, carved
+// one observation; the host has checked every bound (window 0..kMapObserveMaxWindow, width * height <= 2^26)
+struct MapObserve {
+    double T[12];  // world -> view, row-major [R | t]
+    double fx, fy, cx, cy, min_depth, max_depth, abs_tol, rel_tol;
+    int width, height, window;
+};
+// the tally, per slot: the views with a verdict, and those that agreed and looked through
+struct MapTally {
+    uint32_t *seen, *agree, *through;
+};
+// clears ctr [kMapObserveCounters], then every occupied cell of t against the depth image (device arrays; mask may be NULL):
+// its verdict added to the tally
+hipError_t launch_map_observe(hipStream_t s, const MapTable& t, const MapObserve& o, double leaf, const float* depth, const uint8_t* mask,
+                              const MapTally& c, unsigned long long* ctr);
+// clears ctr [kMapVisibilitySelectCounters]; reason [cap]: every slot's reason (kMapPruneEmpty without a cell) from the tally
+hipError_t launch_map_visibility_select(hipStream_t s, const MapTable& t, const MapTally& c, uint32_t min_through, uint32_t agree_weight,
+                                        uint8_t* reason, unsigned long long* ctr);
+// after launch_map_count(t, 1, 1): key, tally and (reason != NULL) reason of every cell in slot order (launch_map_extract's)
+hipError_t launch_map_visibility_gather(hipStream_t s, const MapTable& t, const MapTally& c, const uint8_t* reason, const uint32_t* blk,
+                                        unsigned long long* key_out, const MapTally& out, uint8_t* reason_out);
+
 // ---- merging maps and moving their state (include/dsi_map_merge.h; DESIGN.md 7j "Merging") ----
 constexpr int kMapImportCounters = 8;  // bad key, duplicate, n == 0, bad windows, bad stamp, S too large, table full, sum of n
 constexpr int kMapMergeCounters = 2;   // cells new to dst, cells both maps hold

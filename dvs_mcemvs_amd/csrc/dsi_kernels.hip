@@ -8058,6 +8058,128 @@ __global__ void __launch_bounds__(kPcBlock) k_map_pca_gather(MapTable t, uint32_
         });
 }
 
+// ---- the map carved by free space (include/dsi_map_visibility.h dsx_map_observe / visibility_*; DESIGN.md 7j "Visibility") ----
+// k_map_integrate_depth's test of a pixel: unmasked (m > 0; the caller passes 1 without a mask), d finite and in the range
+__device__ __forceinline__ bool map_depth_valid(double d, uint32_t m, double min_depth, double max_depth)
+{
+    return m > 0u && isfinite(d) && d >= min_depth && d <= max_depth;
+}
+
+// One observation: every occupied cell against the depth image, by the rule of dsi_map_visibility.h.  The cell is
+// k_map_render's point -- its extracted centroid through o.T, CLIPPED as there --; OUTSIDE unless its centre pixel is in
+// the image (in double, before anything becomes an integer); its (2 W + 1)^2 pixels are loaded with their coordinates
+// clamped into the image and counted only where the unclamped ones are inside: W is a template parameter, the loads are
+// unrolled, none depends on another and none is out of bounds.  The verdict goes into the slot's own tally words, plain
+// read-modify-writes by the slot's one thread (the host zeroed them before the tally's first view).
+// ctr: [0] clipped, [1] outside, [2] unseen, [3] agree, [4] through, [5] behind, [6] the image's valid pixels -- counted
+// by a second walk, over the pixels, whose rounds every lane of a workgroup enters together.  A counted slot walk (MapCounts).
+template <int W>
+__global__ void __launch_bounds__(kPcBlock) k_map_observe(MapTable t, MapObserve o, double leaf, const float* __restrict__ depth,
+                                                          const uint8_t* __restrict__ mask, MapTally c, unsigned long long* __restrict__ ctr)
+{
+    enum : uint32_t { kNone, kClipped, kOutside, kUnseen, kAgree, kThrough, kBehind };
+    MapCounts<kMapObserveCounters> cnt;
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        uint32_t verdict = kNone;
+        if (map_passes(t, i, 0u, 0u)) {
+            const unsigned long long k = t.keys[i];
+            const uint32_t n = t.n[i];
+            const double x = (double)map_centroid(t, i, k, n, 0, leaf), y = (double)map_centroid(t, i, k, n, 1, leaf),
+                         z = (double)map_centroid(t, i, k, n, 2, leaf);
+            const double X = ((o.T[0] * x + o.T[1] * y) + o.T[2] * z) + o.T[3];
+            const double Y = ((o.T[4] * x + o.T[5] * y) + o.T[6] * z) + o.T[7];
+            const double Z = ((o.T[8] * x + o.T[9] * y) + o.T[10] * z) + o.T[11];
+            if (!(isfinite(X) && isfinite(Y) && Z >= o.min_depth && Z <= o.max_depth)) {  // (min/max_depth are finite)
+                verdict = kClipped;
+            } else {
+                const double du = floor(((o.fx * (X / Z)) + o.cx) + 0.5), dv = floor(((o.fy * (Y / Z)) + o.cy) + 0.5);
+                if (!(du >= 0.0 && du <= (double)(o.width - 1) && dv >= 0.0 && dv <= (double)(o.height - 1))) {
+                    verdict = kOutside;
+                } else {
+                    const int iu = (int)du, iv = (int)dv;  // (in [0, 2^26): exact)
+                    const double tol = (o.rel_tol * Z) + o.abs_tol, lo = Z - tol, hi = Z + tol;
+                    uint32_t n_valid = 0u, n_agree = 0u, n_through = 0u;
+#pragma unroll
+                    for (int dy = -W; dy <= W; ++dy) {
+#pragma unroll
+                        for (int dx = -W; dx <= W; ++dx) {
+                            const int px = iu + dx, py = iv + dy;
+                            const bool in = px >= 0 && px < o.width && py >= 0 && py < o.height;
+                            const size_t p = (size_t)min(max(py, 0), o.height - 1) * (size_t)o.width + (size_t)min(max(px, 0), o.width - 1);
+                            const double d = (double)depth[p];
+                            const uint32_t m = mask ? (uint32_t)mask[p] : 1u;
+                            const bool valid = in && map_depth_valid(d, m, o.min_depth, o.max_depth);
+                            n_valid += valid ? 1u : 0u;
+                            n_agree += valid && d >= lo && d <= hi ? 1u : 0u;
+                            n_through += valid && d > hi ? 1u : 0u;
+                        }
+                    }
+                    verdict = n_valid == 0u ? kUnseen : n_agree > 0u ? kAgree : n_through == n_valid ? kThrough : kBehind;
+                    if (verdict != kUnseen) {
+                        c.seen[i] += 1u;
+                        if (verdict == kAgree) c.agree[i] += 1u;
+                        if (verdict == kThrough) c.through[i] += 1u;
+                    }
+                }
+            }
+        }
+        cnt.count<0>(verdict == kClipped);
+        cnt.count<1>(verdict == kOutside);
+        cnt.count<2>(verdict == kUnseen);
+        cnt.count<3>(verdict == kAgree);
+        cnt.count<4>(verdict == kThrough);
+        cnt.count<5>(verdict == kBehind);
+    }
+    const uint32_t npix = (uint32_t)o.width * (uint32_t)o.height, pstride = gridDim.x * kPcBlock;  // (<= 2^26, <= 2^18: base cannot wrap)
+    for (uint32_t base = blockIdx.x * kPcBlock; base < npix; base += pstride) {
+        const uint32_t p = base + threadIdx.x;
+        bool valid = false;
+        if (p < npix) valid = map_depth_valid((double)depth[p], mask ? (uint32_t)mask[p] : 1u, o.min_depth, o.max_depth);
+        cnt.count<6>(valid);
+    }
+    cnt.flush(ctr);
+}
+
+// The selection's reason of every slot (kMapPruneEmpty without a cell): 1 (carved) iff through >= min_through and
+// through > agree_weight * agree in 64 bits, else 0.  ctr[0] += kept, ctr[1] += carved.  A counted slot walk (MapCounts).
+__global__ void __launch_bounds__(kPcBlock) k_map_visibility_select(MapTable t, MapTally c, uint32_t min_through, uint32_t agree_weight,
+                                                                    uint8_t* __restrict__ reason, unsigned long long* __restrict__ ctr)
+{
+    MapCounts<kMapVisibilitySelectCounters> cnt;
+    const size_t cap = (size_t)1 << t.cap_log2, stride = (size_t)gridDim.x * kPcBlock;
+    for (size_t base = (size_t)blockIdx.x * kPcBlock; base < cap; base += stride) {
+        const size_t i = base + threadIdx.x;
+        uint32_t r = kMapPruneEmpty;
+        if (map_passes(t, i, 0u, 0u)) {
+            const uint32_t through = c.through[i];
+            r = through >= min_through && (unsigned long long)through > (unsigned long long)agree_weight * (unsigned long long)c.agree[i] ? 1u : 0u;
+        }
+        reason[i] = (uint8_t)r;
+        cnt.count<0>(r == 0u);
+        cnt.count<1>(r == 1u);
+    }
+    cnt.flush(ctr);
+}
+
+// the tally compacted like k_map_extract's cells under the filter (1, 1), with its blk_off (one offset per tile of kPcBlock
+// slots), in slot order: one workgroup per tile; reason_out is written when asked for (not NULL)
+__global__ void __launch_bounds__(kPcBlock) k_map_visibility_gather(MapTable t, MapTally c, const uint8_t* __restrict__ reason,
+                                                                    const uint32_t* __restrict__ blk_off, unsigned long long* __restrict__ key_out,
+                                                                    MapTally out, uint8_t* __restrict__ reason_out)
+{
+    map_compact<true>(
+        t.cap_log2, blk_off, [&](size_t i) { return map_passes(t, i, 1u, 1u); },
+        [&](size_t i, size_t at) {
+            key_out[at] = t.keys[i];
+            out.seen[at] = c.seen[i];
+            out.agree[at] = c.agree[i];
+            out.through[at] = c.through[i];
+            if (reason_out) reason_out[at] = reason[i];
+        });
+}
+
 // ---- merging maps and moving their state (include/dsi_map_merge.h dsx_map_export / import / merge; DESIGN.md 7j "Merging") ----
 // Every occupied slot's raw state compacted like k_map_extract's cells under the filter (0, 0), with its blk_off (one
 // offset per tile of kPcBlock slots): key, n, S[3], windows and stamp in slot order.  Walked in strides; reads the table only.
@@ -8616,6 +8738,40 @@ hipError_t launch_map_pca_gather(hipStream_t s, const MapTable& t, uint32_t min_
 {
     hipLaunchKernelGGL(k_map_pca_gather, dim3(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s, t,
                        min_points, min_windows, c, reason, blk, key_out, out, reason_out);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_observe(hipStream_t s, const MapTable& t, const MapObserve& o, double leaf, const float* depth, const uint8_t* mask,
+                              const MapTally& c, unsigned long long* ctr)
+{
+    const hipError_t e = hipMemsetAsync(ctr, 0, kMapObserveCounters * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    const dim3 grid(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), block(kPcBlock);
+    switch (o.window) {
+    case 0: hipLaunchKernelGGL(k_map_observe<0>, grid, block, 0, s, t, o, leaf, depth, mask, c, ctr); break;
+    case 1: hipLaunchKernelGGL(k_map_observe<1>, grid, block, 0, s, t, o, leaf, depth, mask, c, ctr); break;
+    case 2: hipLaunchKernelGGL(k_map_observe<2>, grid, block, 0, s, t, o, leaf, depth, mask, c, ctr); break;
+    case 3: hipLaunchKernelGGL(k_map_observe<3>, grid, block, 0, s, t, o, leaf, depth, mask, c, ctr); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_visibility_select(hipStream_t s, const MapTable& t, const MapTally& c, uint32_t min_through, uint32_t agree_weight,
+                                        uint8_t* reason, unsigned long long* ctr)
+{
+    const hipError_t e = hipMemsetAsync(ctr, 0, kMapVisibilitySelectCounters * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_map_visibility_select, dim3(std::min(pc_blocks((size_t)1 << t.cap_log2), kMapRenderMaxBlocks)), dim3(kPcBlock), 0, s,
+                       t, c, min_through, agree_weight, reason, ctr);
+    return hipExtGetLastError();
+}
+
+hipError_t launch_map_visibility_gather(hipStream_t s, const MapTable& t, const MapTally& c, const uint8_t* reason, const uint32_t* blk,
+                                        unsigned long long* key_out, const MapTally& out, uint8_t* reason_out)
+{
+    hipLaunchKernelGGL(k_map_visibility_gather, dim3(pc_blocks((size_t)1 << t.cap_log2)), dim3(kPcBlock), 0, s, t, c, reason, blk, key_out, out,
+                       reason_out);
     return hipExtGetLastError();
 }
 

@@ -163,6 +163,26 @@ class _MapPcaSelectInfo(C.Structure):
     _fields_ = [("n_cells", C.c_uint64), ("n_kept", C.c_uint64), ("n_removed", C.c_uint64 * 3), ("capacity", C.c_uint64)]
 
 
+class _MapObservation(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("window", C.c_int32), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("min_depth", C.c_double), ("max_depth", C.c_double), ("abs_tol", C.c_double),
+                ("rel_tol", C.c_double), ("T_v_w", C.c_double * 12)]
+
+
+class _MapObserveInfo(C.Structure):
+    _fields_ = [("n_cells", C.c_uint64), ("n_clipped", C.c_uint64), ("n_outside", C.c_uint64), ("n_unseen", C.c_uint64),
+                ("n_agree", C.c_uint64), ("n_through", C.c_uint64), ("n_behind", C.c_uint64), ("n_valid_pixels", C.c_uint64),
+                ("views", C.c_uint64)]
+
+
+class _MapVisibilitySelection(C.Structure):
+    _fields_ = [("min_through", C.c_uint32), ("agree_weight", C.c_uint32), ("shrink", C.c_int32)]
+
+
+class _MapVisibilitySelectInfo(C.Structure):
+    _fields_ = [("n_cells", C.c_uint64), ("n_kept", C.c_uint64), ("n_removed", C.c_uint64), ("capacity", C.c_uint64)]
+
+
 class _MapState(C.Structure):
     _fields_ = [("leaf", C.c_double), ("n_cells", C.c_uint64), ("calls", C.c_uint64), ("accepted", C.c_uint64),
                 ("rejected", C.c_uint64)]
@@ -476,6 +496,13 @@ def load_library():
                                     C.POINTER(_PcaRow)]),
         "dsx_map_pca_select": (C.c_int, [vp, C.POINTER(_MapPcaSelection), C.POINTER(_MapPcaSelectInfo)]),
         "dsx_map_prune_pca": (C.c_int, [vp, C.POINTER(_MapPcaSelection), C.POINTER(_MapPcaSelectInfo)]),
+        # include/dsi_map_visibility.h: the map carved by free space
+        "dsx_map_observe": (C.c_int, [vp, f32p, u8p, C.POINTER(_MapObservation), C.POINTER(_MapObserveInfo)]),
+        "dsx_map_observe_mapper": (C.c_int, [vp, vp, C.POINTER(_MapObservation), C.POINTER(_MapObserveInfo)]),
+        "dsx_map_visibility_clear": (C.c_int, [vp]),
+        "dsx_map_visibility_fetch": (C.c_int, [vp, u64p, u32p, u32p, u32p, u8p, C.c_size_t, szp]),
+        "dsx_map_visibility_select": (C.c_int, [vp, C.POINTER(_MapVisibilitySelection), C.POINTER(_MapVisibilitySelectInfo)]),
+        "dsx_map_prune_visibility": (C.c_int, [vp, C.POINTER(_MapVisibilitySelection), C.POINTER(_MapVisibilitySelectInfo)]),
         # include/dsi_map_merge.h: merging maps, exporting and importing their state
         "dsx_map_export": (C.c_int, [vp, C.POINTER(_MapState), u64p, u32p, u64p, u32p, u32p, C.c_size_t, szp]),
         "dsx_map_import": (C.c_int, [vp, C.POINTER(_MapState), u64p, u32p, u64p, u32p, u32p, C.POINTER(_MapMergeInfo)]),
@@ -1203,9 +1230,9 @@ class WorldMap:
         self._h = C.c_void_p()
         _check(load_library().dsi_map_create(ctx._h, float(leaf), int(capacity_log2), C.byref(self._h)))
         # what the library keeps of the last passes and does not tell: the render's size; whether a selection left reasons
-        # beside the labelling, the self query and the local-shape pass; whether that pass kept its moments
+        # beside the labelling, the self query, the local-shape pass and the visibility tally; whether that pass kept its moments
         self._render_shape = (0, 0)
-        self._components_selected = self._knn_selected = self._pca_selected = self._pca_moments = False
+        self._components_selected = self._knn_selected = self._pca_selected = self._pca_moments = self._visibility_selected = False
         _track(self)
 
     @staticmethod
@@ -1593,6 +1620,82 @@ class WorldMap:
         return self._select(load_library().dsx_map_prune_pca,
                             _MapPcaSelection(shape_mask(keep), 1 if remove_sparse else 0, 1 if shrink else 0), _MapPcaSelectInfo(),
                             "_pca_selected")
+
+    @staticmethod
+    def _observation(width, height, K, min_depth, max_depth, T_v_w, window, abs_tol, rel_tol):
+        o = _MapObservation()
+        o.width, o.height, o.window = int(width), int(height), int(window)
+        o.fx, o.fy, o.cx, o.cy = _pinhole(K)
+        o.min_depth, o.max_depth = float(min_depth), float(max_depth)
+        o.abs_tol, o.rel_tol = float(abs_tol), float(rel_tol)
+        o.T_v_w[:] = pose_matrix(T_v_w).tolist()
+        return o
+
+    def observe(self, depth, mask, K, min_depth, max_depth, T_v_w, window=1, abs_tol=0.0, rel_tol=0.0):
+        """What one depth image says about every cell (dsx_map_observe; the rule is stated in dsi_map_visibility.h and
+        DESIGN.md 7j "Visibility"): depth (height, width) float32, mask (the same shape, > 0 keeps a pixel) or None,
+        K = (fx, fy, cx, cy) or a 3 x 3 matrix, T_v_w world -> view as render() takes it.  A cell is projected as render()
+        projects it and judged by the valid pixels -- unmasked, finite, in [min_depth, max_depth] -- among the
+        (2 window + 1)^2 around its own, against its depth Z with tol = rel_tol * Z + abs_tol: the view AGREES when any of
+        them lies within Z +- tol, looks THROUGH the cell when every one lies beyond Z + tol, and otherwise sees a surface
+        in front (BEHIND).  The verdicts accumulate per cell over the observations until the map changes or
+        clearVisibility(), for fetchVisibility, selectCarved and pruneCarved.  Returns this view's counts: n_cells =
+        n_clipped + n_outside + n_unseen + n_agree + n_through + n_behind, n_valid_pixels and views (observations in the
+        tally).  Nothing else of the map changes."""
+        depth = _arr(depth, np.float32)
+        if depth.ndim != 2:
+            raise ValueError("depth must be (height, width)")
+        if mask is not None:
+            mask = _arr(mask, np.uint8)
+            if mask.shape != depth.shape:
+                raise ValueError("mask must have the depth image's shape")
+        o = self._observation(depth.shape[1], depth.shape[0], K, min_depth, max_depth, T_v_w, window, abs_tol, rel_tol)
+        i = _MapObserveInfo()
+        self._visibility_selected = False
+        _check(load_library().dsx_map_observe(self._h, _ptr(depth, C.c_float), None if mask is None else _ptr(mask, C.c_uint8), C.byref(o),
+                                              C.byref(i)))
+        return _info_dict(i)
+
+    def observeMapper(self, mapper, K, min_depth, max_depth, T_v_w, window=1, abs_tol=0.0, rel_tol=0.0):
+        """observe() of the filtered depth map and mask the mapper's last getDepthMapFromDSI(..., options_depth_map) /
+        filterDepthMap left on the device, read where they lie (dsx_map_observe_mapper): only the counts travel.  The
+        mapper must live on the map's context."""
+        o = self._observation(mapper.dimX, mapper.dimY, K, min_depth, max_depth, T_v_w, window, abs_tol, rel_tol)
+        i = _MapObserveInfo()
+        self._visibility_selected = False
+        _check(load_library().dsx_map_observe_mapper(self._h, mapper._h, C.byref(o), C.byref(i)))
+        return _info_dict(i)
+
+    def clearVisibility(self):
+        """Zeroes the tally (dsx_map_visibility_clear): the next observe() is the first."""
+        self._visibility_selected = False
+        _check(load_library().dsx_map_visibility_clear(self._h))
+
+    _VISIBILITY_COLUMNS = (_Column("keys", _U64), _Column("seen", _U32), _Column("agree", _U32), _Column("through", _U32),
+                           _Column("reason", _U8, flag="_visibility_selected"))
+
+    def fetchVisibility(self, sort=True):
+        """keys (uint64), seen, agree and through (uint32: the views with a verdict on the cell, and those that agreed and
+        looked through; behind = seen - agree - through) of every cell and, after a selectCarved() on this tally, reason
+        (uint8: 1 carved, 0 kept) (dsx_map_visibility_fetch); raises DsiError without an observe() since the map last
+        changed.  sort=True orders by ascending key; otherwise the order is extract(sort=False)'s."""
+        return self._fetch_rows(load_library().dsx_map_visibility_fetch, self._VISIBILITY_COLUMNS, sort)
+
+    def selectCarved(self, min_through=2, agree_weight=1, shrink=False):
+        """pruneCarved()'s dry run (dsx_map_visibility_select): the same counts, the map unchanged; the per-cell reasons stay
+        on the device for fetchVisibility until the next observe()."""
+        return self._select(load_library().dsx_map_visibility_select,
+                            _MapVisibilitySelection(int(min_through), int(agree_weight), 1 if shrink else 0), _MapVisibilitySelectInfo(),
+                            "_visibility_selected")
+
+    def pruneCarved(self, min_through=2, agree_weight=1, shrink=False):
+        """Removes the cells that the observed views carve away (dsx_map_prune_visibility): those with through >= min_through
+        and through > agree_weight * agree; the table is rebuilt around the rest, shrink as prune()'s.  Returns dict of
+        n_cells = n_kept + n_removed, n_kept, n_removed and capacity (slots afterwards).  Everything derived from the map
+        is invalid afterwards, the tally included."""
+        return self._select(load_library().dsx_map_prune_visibility,
+                            _MapVisibilitySelection(int(min_through), int(agree_weight), 1 if shrink else 0), _MapVisibilitySelectInfo(),
+                            "_visibility_selected")
 
     _STATE_COLUMNS = (_Column("keys", _U64), _Column("n", _U32), _Column("S", _U64, (3,)), _Column("windows", _U32), _Column("stamp", _U32))
 

@@ -770,14 +770,77 @@ def _check_keep(opts):
         raise ValueError("world_map_shapes['keep'] must name at least one of linear, planar and scattered")
 
 
+def _pop_views(opts):
+    """world_map_carve's `views`, taken out of opts before its keys are checked: the ring of the last windows' views"""
+    if "views" not in opts:
+        raise ValueError("world_map_carve needs views")
+    views = opts.pop("views")
+    if isinstance(views, bool) or int(views) != views or views < 1:
+        raise ValueError("world_map_carve['views'] must be an integer >= 1")
+    return {"ring": collections.deque(maxlen=int(views)), "camera": None}
+
+
+def _check_carve(opts):
+    """the bounds of dsi_map_visibility.h, before the stream starts"""
+    window, min_through, agree_weight = opts.get("window", 1), opts.get("min_through", 2), opts.get("agree_weight", 1)
+    if isinstance(window, bool) or int(window) != window or not 0 <= window <= 3:
+        raise ValueError("world_map_carve['window'] must be an integer in 0..3")
+    for k in ("abs_tol", "rel_tol"):
+        if not (np.isfinite(opts.get(k, 0.0)) and opts.get(k, 0.0) >= 0.0):
+            raise ValueError("world_map_carve[%r] must be finite and >= 0" % k)
+    if int(min_through) != min_through or not 1 <= min_through <= 0xffffffff:
+        raise ValueError("world_map_carve['min_through'] must be an integer >= 1")
+    if int(agree_weight) != agree_weight or not 0 <= agree_weight <= 0xffffffff:
+        raise ValueError("world_map_carve['agree_weight'] must be an integer >= 0")
+
+
+def _collect_view(state, maps, T_rv_w, mapper):
+    """world_map_carve's hook on every window: the window's filtered depth map and mask -- the host arrays the stream yields
+    -- and its T_rv_w join the ring; the camera is the mapper's virtual one, the depth range that of its planes"""
+    state["ring"].append((maps[0], maps[2], np.array(E.pose_matrix(T_rv_w))))
+    state["camera"] = (mapper.virtual_cam_, float(mapper.raw_depths_vec_.min()), float(mapper.raw_depths_vec_.max()))
+
+
+def _observe_ring(world_map, state, **observe_opts):
+    """world_map_carve's pass: the tally cleared, then every view of the ring; the last one's counts"""
+    K, min_depth, max_depth = state["camera"]
+    return _observe_views(world_map, state["ring"], K, min_depth, max_depth, **observe_opts)
+
+
+def _observe_views(world_map, views, K, min_depth, max_depth, **observe_opts):
+    world_map.clearVisibility()
+    counts = None
+    for depth, mask, T_v_w in views:
+        counts = world_map.observe(depth, mask, K, min_depth, max_depth, T_v_w, **observe_opts)
+    if counts is None:
+        raise ValueError("no view to carve the map with")
+    return counts
+
+
+def carve_world_map(world_map, views, K, min_depth, max_depth, window=1, abs_tol=0.0, rel_tol=0.0, min_through=2, agree_weight=1,
+                    shrink=False):
+    """Carves a map by the free space that depth maps saw (engine.WorldMap.observe / pruneCarved; the rule is stated in
+    dsi_map_visibility.h and DESIGN.md 7j "Visibility"): the tally is cleared, every view of `views` -- (depth, mask, T_v_w)
+    with depth a host depth map (height, width), mask its mask or None and T_v_w the pose world -> view (a window's T_rv_w)
+    -- is observed through K = (fx, fy, cx, cy) with the depth range and window, abs_tol, rel_tol, and the cells with
+    through >= min_through and through > agree_weight * agree are removed.  Returns the last view's counts and, under
+    "prune", those of pruneCarved."""
+    counts = _observe_views(world_map, views, K, min_depth, max_depth, window=window, abs_tol=abs_tol, rel_tol=rel_tol)
+    counts["prune"] = world_map.pruneCarved(min_through, agree_weight, shrink)
+    return counts
+
+
 # full_sequence's map stages, in the order they run on a window.  name: the keyword, and the key of the element a window's
-# result gains; run, run_keys: the WorldMap method of the pass (None: the stage only prunes) and the keywords it takes;
+# result gains; run, run_keys: the WorldMap method of the pass (None: the stage only prunes; a function: called as
+# run(world_map, what prepare returned, **keywords)) and the keywords it takes;
 # required: those that have no default; prune, prune_keys: the method that removes cells, and its keywords; prepare(opts):
 # called before the keys are checked, takes what belongs to neither method out of opts and returns it; check(opts): a last
-# look at the values; per_window(prune_opts, what prepare returned, the window's T_rv_w): the prune's keywords for one window.
+# look at the values; per_window(prune_opts, what prepare returned, the window's T_rv_w): the prune's keywords for one window;
+# collect(what prepare returned, the window's filtered maps, its T_rv_w, its mapper): called on EVERY window, also those
+# between two every-th ones.
 # A new stage is one more row (and its keyword in full_sequence's signature and docstring).
-_MapStage = collections.namedtuple("_MapStage", "name run run_keys required prune prune_keys prepare check per_window",
-                                   defaults=(None, None, None))
+_MapStage = collections.namedtuple("_MapStage", "name run run_keys required prune prune_keys prepare check per_window collect",
+                                   defaults=(None, None, None, None))
 _MAP_STAGES = (
     _MapStage("world_map_prune", None, (), (), "prune",
               ("min_points", "min_windows", "max_age", "box", "reach", "min_neighbors", "shrink"), _pop_local_box, None, _prune_world_map),
@@ -787,6 +850,8 @@ _MAP_STAGES = (
               ("std_mult", "shrink")),
     _MapStage("world_map_shapes", "pca", ("k", "radius", "min_found", "orient", "viewpoint", "min_points", "min_windows"), ("k", "radius"),
               "pruneShapes", ("keep", "remove_sparse", "shrink"), None, _check_keep),
+    _MapStage("world_map_carve", _observe_ring, ("window", "abs_tol", "rel_tol"), (), "pruneCarved", ("min_through", "agree_weight", "shrink"),
+              _pop_views, _check_carve, None, _collect_view),
 )
 
 
@@ -814,7 +879,7 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
                   out_skip, fusion_method=E.FUSE_HM, forward_looking=True, rv_pos=0.0, options_depth_map=None,
                   options_point_cloud=None, polarities=None, save_images=False, out_path=None, lut=None, score=None,
                   ground_truth=None, ground_truth_disparity=None, thicken_edges=False, world_map=None, world_map_prune=None,
-                  world_map_components=None, world_map_outliers=None, world_map_shapes=None,
+                  world_map_components=None, world_map_outliers=None, world_map_shapes=None, world_map_carve=None,
                   **kw):
     """Generator over the windows of main.cpp:177-302: yields (ts, depth, confidence, indices) per
     window, pipelined one window deep; with options_depth_map, (ts, depth_map, confidence_map, mask)
@@ -874,9 +939,18 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
     min_found, orient, viewpoint, min_points, min_windows) and of WorldMap.pruneShapes (keep, remove_sparse, shrink) plus
     `every` (default 1): after every every-th window, after world_map_outliers' work on that window, the map analyses its
     cells' local shape and keeps the labels in keep.  Such a window's result gains a last element, {"world_map_shapes": the
-    counts of WorldMap.pca, and under "prune" those of WorldMap.pruneShapes}."""
+    counts of WorldMap.pca, and under "prune" those of WorldMap.pruneShapes}.
+    world_map_carve= (with world_map=; None leaves the stream as it is): a dict of `views` (required: how many of the last
+    windows' views are kept), the keywords of WorldMap.observe (window, abs_tol, rel_tol) and of WorldMap.pruneCarved
+    (min_through, agree_weight, shrink) plus `every` (default 1).  Every window's filtered depth map, mask and T_rv_w --
+    the host arrays this generator yields anyway, for process_method 2 / 5 those of the time_camera output: nothing more
+    is downloaded -- join a ring of the last `views` windows.  After every every-th window, after world_map_shapes' work on
+    that window, the ring is replayed against the map (carve_world_map: the tally cleared, one observe per view through
+    the mapper's virtual camera and the depth range of its planes) and the cells that the views look through are
+    removed: a floater of one window is refuted by the windows around it.  Such a window's result gains a last element,
+    {"world_map_carve": the counts of the last observe, and under "prune" those of WorldMap.pruneCarved}."""
     given = {"world_map_prune": world_map_prune, "world_map_components": world_map_components,
-             "world_map_outliers": world_map_outliers, "world_map_shapes": world_map_shapes}
+             "world_map_outliers": world_map_outliers, "world_map_shapes": world_map_shapes, "world_map_carve": world_map_carve}
     checked = {}
     for stage in reversed(_MAP_STAGES):              # the last stage's keyword is checked first: its refusal wins
         if given[stage.name] is not None:
@@ -925,11 +999,16 @@ def full_sequence(ctx, cams, dsi_shape, events, trajectories, start_time_s, stop
         out = _window_result(ws, pending, options_depth_map, options_point_cloud, images, scoring, world_map)
         windows_seen += 1
         for stage, (pass_opts, prune_opts, every, state) in stages:
+            if stage.collect is not None:
+                stage.collect(state, out[1:] if ws.process_method == 1 else out[1], pending[3], ws.extract[pending[1]])
             if windows_seen % every:
                 continue
             if stage.per_window is not None:
                 prune_opts = stage.per_window(prune_opts, state, pending[3])
-            counts = getattr(world_map, stage.run)(**pass_opts) if stage.run else None
+            if callable(stage.run):
+                counts = stage.run(world_map, state, **pass_opts)
+            else:
+                counts = getattr(world_map, stage.run)(**pass_opts) if stage.run else None
             pruned = getattr(world_map, stage.prune)(**prune_opts)
             if counts is None:
                 counts = pruned

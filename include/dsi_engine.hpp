@@ -38,6 +38,7 @@
 #include "dsi_map_components.h"
 #include "dsi_map_knn.h"
 #include "dsi_map_pca.h"
+#include "dsi_map_visibility.h"
 #include "dsi_map_prune.h"
 #include "dsi_map_merge.h"
 #include "dsi_map_align.h"
@@ -1819,6 +1820,38 @@ inline PcaRow pca_solve(uint32_t m, const int64_t s[3], const int64_t ss[6], dou
     check(dsx_pca_solve(m, s, ss, quantum, viewpoint ? 1 : 0, viewpoint, p, &r));
     return r;
 }
+// carving by free space (dsi_map_visibility.h): one observation -- a depth image's size, pinhole, depth range and pose
+// world -> view; the defaults judge a cell by the 3 x 3 pixels around its own with no tolerance --, the selection's options
+// -- a cell leaves when two views look through it, and more views than agree with it --, and what comes back
+struct MapObservation : dsx_map_observation_t {
+    MapObservation(int width_, int height_, double fx_, double fy_, double cx_, double cy_, double min_depth_, double max_depth_,
+                   const std::array<double, 12>& T_v_w_, int window_ = 1, double abs_tol_ = 0.0, double rel_tol_ = 0.0)
+        : dsx_map_observation_t{}
+    {
+        width = width_, height = height_, window = window_;
+        fx = fx_, fy = fy_, cx = cx_, cy = cy_;
+        min_depth = min_depth_, max_depth = max_depth_;
+        abs_tol = abs_tol_, rel_tol = rel_tol_;
+        std::copy(T_v_w_.begin(), T_v_w_.end(), T_v_w);
+    }
+};
+struct MapVisibilitySelection : dsx_map_visibility_selection_t {
+    explicit MapVisibilitySelection(uint32_t min_through_ = 2, uint32_t agree_weight_ = 1, bool shrink_ = false)
+        : dsx_map_visibility_selection_t{}
+    {
+        min_through = min_through_;
+        agree_weight = agree_weight_;
+        shrink = shrink_ ? 1 : 0;
+    }
+};
+using MapObserveInfo = dsx_map_observe_info_t;
+using MapVisibilitySelectInfo = dsx_map_visibility_select_info_t;
+struct MapVisibility {  // one row per cell: the views with a verdict on it, and those that agreed and looked through
+    std::vector<uint64_t> keys;
+    std::vector<uint32_t> seen, agree, through;
+    std::vector<uint8_t> reason;  // after selectCarved() on this tally (1 carved, 0 kept), else empty
+    size_t size() const { return keys.size(); }
+};
 // merging and moving the state (dsi_map_merge.h): a map's exact state on the host, and what a merge counts
 struct MapState {  // by ascending key when sorted
     double leaf = 0.0;
@@ -2104,6 +2137,58 @@ public:
         return detail::info_of<MapPcaSelectInfo>(dsx_map_prune_pca, h_, &sel);
     }
 
+    // what one host depth image (height x width, row-major; mask may be nullptr) says about every cell (dsx_map_observe; the
+    // rule is stated in dsi_map_visibility.h): the verdicts accumulate per cell until the map changes or clearVisibility(),
+    // and nothing else of the map changes
+    MapObserveInfo observe(const float* depth, const uint8_t* mask, const MapObservation& obs)
+    {
+        visibility_selected_ = false;
+        return detail::info_of<MapObserveInfo>(dsx_map_observe, h_, depth, mask, &obs);
+    }
+    // the same of the filtered depth map and mask the mapper left on the device, read where they lie (dsx_map_observe_mapper)
+    template <typename MapperT>
+    MapObserveInfo observeMapper(MapperT& mapper, const MapObservation& obs)
+    {
+        visibility_selected_ = false;
+        return detail::info_of<MapObserveInfo>(dsx_map_observe_mapper, h_, mapper.handle(), &obs);
+    }
+    void clearVisibility()
+    {
+        visibility_selected_ = false;
+        check(dsx_map_visibility_clear(h_));
+    }
+    // the tally of every cell (dsx_map_visibility_fetch); sort: by ascending key
+    MapVisibility fetchVisibility(bool sort = true) const
+    {
+        MapVisibility out;
+        detail::fetch_rows(
+            [&](size_t room, size_t* n) {
+                return dsx_map_visibility_fetch(h_, detail::ptr(out.keys), detail::ptr(out.seen), detail::ptr(out.agree), detail::ptr(out.through),
+                                                detail::ptr(out.reason), room, n);
+            },
+            [&](size_t n) {
+                out.keys.resize(n), out.seen.resize(n), out.agree.resize(n), out.through.resize(n);
+                if (visibility_selected_) out.reason.resize(n);
+            });
+        if (sort) detail::sort_rows_by_key(out.keys, out.seen, out.agree, out.through, out.reason);
+        return out;
+    }
+    // pruneCarved()'s dry run (dsx_map_visibility_select): the same counts, the map unchanged
+    MapVisibilitySelectInfo selectCarved(const MapVisibilitySelection& sel = MapVisibilitySelection())
+    {
+        visibility_selected_ = false;
+        const MapVisibilitySelectInfo info = detail::info_of<MapVisibilitySelectInfo>(dsx_map_visibility_select, h_, &sel);
+        visibility_selected_ = true;
+        return info;
+    }
+    // removes the cells that the observed views look through and rebuilds the table around the rest
+    // (dsx_map_prune_visibility); everything derived from the map is invalid afterwards
+    MapVisibilitySelectInfo pruneCarved(const MapVisibilitySelection& sel = MapVisibilitySelection())
+    {
+        visibility_selected_ = false;
+        return detail::info_of<MapVisibilitySelectInfo>(dsx_map_prune_visibility, h_, &sel);
+    }
+
     // appends `other` (same context, same leaf) to this map on the device (dsx_map_merge; the rule is stated in
     // dsi_map_merge.h): this map becomes the map that had made its own integrate calls and then other's.  other is
     // unchanged; render, compare and classification of this map are invalid afterwards
@@ -2168,6 +2253,7 @@ private:
     dsi_map_t* h_ = nullptr;
     int width_ = 0, height_ = 0;  // of the last render
     bool pca_moments_ = false;    // the last pca() kept its moments
+    bool visibility_selected_ = false;  // a selectCarved() left reasons beside the tally
 };
 
 // 3-D accuracy, completeness and F-score of the map `est` against the map `gt` (the curves of the reference's
